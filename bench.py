@@ -14,10 +14,13 @@ aggregate scan rate (rows/s and GB/s summed over ranks, against N x the HBM peak
 per-rank kernel times beside them.
 
 Inputs are resident in HBM when the timed region starts (corpus and all W+K queries are generated
-on the device beforehand); results stay on the device.  The PCIe-inclusive host API rate is
-reported separately as `host_api_qps` and is never `value`.
+on the device beforehand, from fixed seeds: the same arguments give the same inputs); results stay on the device.
+--dump-outputs DIR writes the (D, I) of the last timed step as DIR/D.npy and DIR/I.npy.
 
-Beside the headline, at N = 1 the same JSON line carries three more blocks, measured OUTSIDE the headline's timed region
+A plain run sets up, warms up, times the K steps and prints the line (headline, p50 latency, the roofline of the timed
+launches).  --full adds everything else, all measured OUTSIDE the headline's timed region: at N = 1 the PCIe-inclusive
+host API rate (`host_api_qps`, never `value`), the opt-in fp16-shadow single-query rate, the package power under the
+step, the CPU oracle's rate over the whole corpus (`cpu_baseline`; --no-cpu-baseline skips it) and three more blocks
 (BASELINE config 5; --no-encoder skips them):
   "certified_passes_on_unfriendly_data": the batch passes (and the opt-in single-query shadow route) on an all-positive and on a
              clustered 10M x 512 corpus, where certification can fail — with the re-run rate;
@@ -28,7 +31,7 @@ Beside the headline, at N = 1 the same JSON line carries three more blocks, meas
              one-sentence-per-call latencies; "large": the bge-m3 / e5-large shape;
   "config5": encoder forward -> 256 queries -> kNN over a resident 10M x 384 corpus, end to end on the device.
 
-Launch: python bench.py [--gpus 1]       or, for N > 1 (the driver does this):
+Launch: python bench.py [--gpus 1] [--full]       or, for N > 1 (one rank per GPU):
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -636,6 +639,26 @@ def certified_passes_on_unfriendly_data(native, dev, k, n=10_000_000, d=512, nq=
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20   # under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy per array: floating results as float32, integer ids as float64 (exact below 2**53).  Past
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows is kept of every array (its row numbers in DIR/rows.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float32 if np.issubdtype(np.asarray(a).dtype, np.floating) else np.float64)
+              for name, a in arrays.items()}
+    rows = next(iter(arrays.values())).shape[0]
+    per_row = sum(a.nbytes for a in arrays.values()) / max(rows, 1) + 8
+    if per_row * rows > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, int(DUMP_LIMIT_BYTES // per_row), replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+        arrays["rows"] = keep.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -646,10 +669,15 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--nq", type=int, default=1, help="queries per step (1 = the reference API shape; >1 = one "
                     "multi-query MFMA pass per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-encoder", action="store_true", help="skip the encoder / config-5 blocks")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (host API rate, "
+                    "opt-in shadow route, power, CPU baseline, unfriendly corpora, encoder / config-5 blocks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-encoder", action="store_true", help="with --full: skip the unfriendly-corpora / encoder / "
+                    "config-5 blocks")
     ap.add_argument("--dump", default=None, help="rank 0 writes the merged (D, I) of the first 16 timed steps to this "
                     ".npz (tests/test_config4_gpu.py compares them with a single-index search)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes the (D, I) the last timed step "
+                    "returned as DIR/D.npy (float32) and DIR/I.npy (float64), at most 64 MB in all")
     args = ap.parse_args()
 
     import numpy as np
@@ -771,11 +799,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(W, W + K):
-        searcher.search_device(queries[i * nq:(i + 1) * nq])
+        last = searcher.search_device(queries[i * nq:(i + 1) * nq])
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
     native.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        # (the result buffers are reused by the next search of this nq: copy them out before anything else runs)
+        dump_outputs(args.dump_outputs, {"D": last[0].cpu().numpy(), "I": last[1].cpu().numpy()})
     # dominant kernel by batch size: GEMV scan (nq = 1), fp32-MFMA pass, the certified pass over the fp16 shadow, the
     # GEMM-tiled exact scan — whichever took the most time in the timed region
     prof = {name: native.prof_read(name) for name in scan_names}
@@ -892,7 +923,7 @@ def main():
                 "per_rank_avg_launch_ms": [round(v, 4) for v in rank_ms],
                 "per_rank_launch_ms_min_max": [round(min(rank_ms), 4), round(max(rank_ms), 4)],
             }
-        if world == 1:
+        if world == 1 and args.full:
             # PCIe-inclusive host API (numpy in, numpy out): reported, never `value`
             qh = queries[W * nq:W * nq + 64].cpu().numpy()
             for i in range(3):

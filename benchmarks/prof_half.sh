@@ -10,7 +10,7 @@ SETS="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES;SQ_
 IFS=';' read -ra ARR <<< "$SETS"
 STEPS=6
 for nq in $NQS; do
-  [ -z "$SKIP_TRACE" ] && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/htr_${nq} -- python3 $R/bench.py --nq $nq --dim $DIM --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/bench_nq${nq}_d${DIM}.json 2>/dev/null
+  [ -z "$SKIP_TRACE" ] && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/htr_${nq} -- python3 $R/bench.py --full --nq $nq --dim $DIM --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/bench_nq${nq}_d${DIM}.json 2>/dev/null
   python3 - <<PY >> $OUT/pmc_summary_d${DIM}.txt
 import csv, glob
 f = glob.glob("/tmp/htr_${nq}/**/*kernel_stats.csv", recursive=True)

@@ -28,6 +28,7 @@ def test_power_probe_parses_rocm_smi(tmp_path, monkeypatch):
     fake.write_text("#!/bin/sh\ncat <<'EOT'\n" + SMI_TEXT + "EOT\n")
     fake.chmod(fake.stat().st_mode | stat.S_IEXEC)
     monkeypatch.setenv("PATH", str(tmp_path) + os.pathsep + os.environ.get("PATH", ""))
+    monkeypatch.setattr(bench, "_hwmon_of", lambda dev_index: None)   # on a GPU box: the device's hwmon files win
     steps, syncs = [0], [0]
     got = bench.power_probe(lambda: steps.__setitem__(0, steps[0] + 1), "a test load",
                             lambda: syncs.__setitem__(0, syncs[0] + 1), seconds=0.05)
@@ -51,6 +52,7 @@ def test_power_probe_without_rocm_smi_output(tmp_path, monkeypatch):
     fake.write_text("#!/bin/sh\necho nothing useful\n")
     fake.chmod(fake.stat().st_mode | stat.S_IEXEC)
     monkeypatch.setenv("PATH", str(tmp_path) + os.pathsep + os.environ.get("PATH", ""))
+    monkeypatch.setattr(bench, "_hwmon_of", lambda dev_index: None)
     assert bench.power_probe(lambda: None, "x", lambda: None, seconds=0.01) is None
 
 

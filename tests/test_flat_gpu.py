@@ -1777,7 +1777,7 @@ def test_resident_row_sets(native):
     idx.close()
 
 
-def test_drop_in_exclude_filter_runs_as_a_resident_bitmap(native):
+def test_drop_in_exclude_filter_runs_as_a_resident_bitmap(native, tmp_path):
     """VectorDatabase.find_most_similar with an exclude-filter over everything: the reference subtracts from an O(N) set and
     gathers ~N rows into a throw-away index per query (vector_database.py:354-386, :508-523); here the excluded rows go
     up once, the search is one full-rate pass under a bitmap, and the next query under the same filter uploads nothing."""
@@ -1785,7 +1785,7 @@ def test_drop_in_exclude_filter_runs_as_a_resident_bitmap(native):
     from minivectordb_amd import _dbcore
     n, d = 6000, 64
     x = _corpus(n, d)
-    db = VectorDatabase(storage_file="/tmp/mvdb_test_excl.pkl")
+    db = VectorDatabase(storage_file=str(tmp_path / "excl.pkl"))
     db.store_embeddings_batch(list(range(n)), list(x), [{"tag": "odd" if i % 7 == 3 else "even", "i": i} for i in range(n)])
     made = []
     orig = native.FlatIndex.rowset
