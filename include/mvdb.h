@@ -324,6 +324,66 @@ int mvdb_rescue_tile_stats(int64_t* listed, int64_t* total);
 double mvdb_half_eps(int d);
 int mvdb_half_max_queries(int d);
 
+/* ---- int8 cosine index (csrc/cos8.hip) ---------------------------------------------------
+ * Replaces usearch.index.Index(ndim=d, metric='cos', dtype='int8') built per query over the filtered rows
+ *                                                minivectordb/sharded_vector_database_usearch.py:617-629
+ * with an EXACT scan under the same quantisation and distance (INTEGRATION.md "int8 cosine contract").
+ *
+ * Quantisation of a row or query x (fp32, length d), one device function (csrc/cos8_kernels.hpp: cos8_quantize_row):
+ *   mag    = sqrt(sum_i (double)x_i^2), summed sequentially in index order in fp64;
+ *   code_i = (int8) trunc((double)(float)(x_i * 127.0f) / mag), clamped to [-127, 127];
+ *   mag == 0 or not finite: all codes 0.   a2 = sum_i code_i^2 (int32).
+ * Distance for the int32 sums ab = a.b, a2, b2:
+ *   a2 == 0 and b2 == 0: 0;  exactly one of them 0, or ab == 0: 1;
+ *   else (float)(1.0 - (double)ab / sqrt((double)a2 * (double)b2))  (IEEE fp64 division and square root).
+ * Results: ascending distance, ties to the lower row; missing slots label -1 / distance +FLT_MAX.  A batch returns,
+ * bit for bit, what nq single calls return (integer dot products do not depend on summation order).
+ * Device store: codes [n, stride] (stride = d rounded up to 16 bytes, zero padded) and a2 [n]; no fp32 rows.
+ * d <= 4096.  k > 64: every distance is materialised and radix-selected.  Searches are re-entrant from many host
+ * threads; add / remove_rows / reset / reserve take the index exclusively and wait for its searches. */
+typedef struct mvdb_cos8 mvdb_cos8;
+int mvdb_cos8_create(int d, int device, mvdb_cos8** out);
+int mvdb_cos8_free(mvdb_cos8* ix);
+int mvdb_cos8_reset(mvdb_cos8* ix);
+int mvdb_cos8_reserve(mvdb_cos8* ix, int64_t n);
+int64_t mvdb_cos8_ntotal(const mvdb_cos8* ix);
+int mvdb_cos8_dim(const mvdb_cos8* ix);
+
+/* Quantise and append n fp32 rows: x_host[n,d] (C-contiguous; uploaded in chunks) or x_dev[n,d] (dense, same GPU). */
+int mvdb_cos8_add(mvdb_cos8* ix, const float* x_host, int64_t n);
+int mvdb_cos8_add_device(mvdb_cos8* ix, const float* x_dev, int64_t n);
+
+/* Rows [row0, row0 + n) back to the host: codes_host[n,d] (unpadded) and a2_host[n]; either may be NULL.  For tests. */
+int mvdb_cos8_get_codes(const mvdb_cos8* ix, int64_t row0, int64_t n, int8_t* codes_host, int32_t* a2_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_cos8_remove_rows(mvdb_cos8* ix, const int64_t* rows_host, int64_t m);
+
+/* k nearest rows for nq fp32 queries (quantised on the device by the same rule): q_host[nq,d], D_host[nq,k] distances,
+ * I_host[nq,k] row numbers. */
+int mvdb_cos8_search(const mvdb_cos8* ix, const float* q_host, int nq, int k, float* D_host, int64_t* I_host);
+
+/* Same with every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream); labels are
+ * row + label_offset.  No host synchronisation; capturable into a hipGraph after one eager call of the same shape on that
+ * stream (the eager call sizes the stream's workspace; a capture that would need a larger one fails with MVDB_ERR_ARG). */
+int mvdb_cos8_search_device(const mvdb_cos8* ix, const float* q_dev, int nq, int k, int64_t label_offset,
+                            float* D_dev, int64_t* I_dev, void* stream);
+
+/* A filter's rows resident on the device: excluded == 0 the m listed rows, excluded != 0 every row but them.  Kept as an
+ * exclusion bitmap (excluded sets, and lists that keep >= 1/8 of the rows) or a sorted row list.  Labels are row
+ * numbers either way, ties to the lower row.  A set belongs to the index state it was built against: after a removal
+ * searching it fails with MVDB_ERR_ARG; rows appended later are not part of it. */
+typedef struct mvdb_cos8_rowset mvdb_cos8_rowset;
+int mvdb_cos8_rowset_create(const mvdb_cos8* ix, const int64_t* rows_host, int64_t m, int excluded,
+                            mvdb_cos8_rowset** out);
+int64_t mvdb_cos8_rowset_size(const mvdb_cos8_rowset* rs);
+int mvdb_cos8_rowset_is_bitmap(const mvdb_cos8_rowset* rs);
+int mvdb_cos8_rowset_free(mvdb_cos8_rowset* rs);
+int mvdb_cos8_search_rowset(const mvdb_cos8* ix, const float* q_host, int nq, int k, const mvdb_cos8_rowset* rs,
+                            float* D_host, int64_t* I_host);
+int mvdb_cos8_search_rowset_device(const mvdb_cos8* ix, const float* q_dev, int nq, int k, const mvdb_cos8_rowset* rs,
+                                   int64_t label_offset, float* D_dev, int64_t* I_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

@@ -1,8 +1,8 @@
 """minivectordb_amd — MI355X-native drop-in for MiniVectorDB's embed+search hot path.
 
 Public surface mirrors the reference package (minivectordb/): ``VectorDatabase``,
-``ShardedVectorDatabase``, ``EmbeddingModel`` / ``AlternativeModel``.  All numeric work runs in
-hand-written HIP kernels behind the C-ABI in include/mvdb.h; there is no CPU fallback.
+``ShardedVectorDatabase``, ``ShardedVectorDatabaseUsearch`` (exact int8 cosine scan), ``EmbeddingModel`` /
+``AlternativeModel``.  All numeric work runs in hand-written HIP kernels behind the C-ABI in include/mvdb.h; there is no CPU fallback.
 """
 
 import os as _os
@@ -11,8 +11,8 @@ import os as _os
 # first HIP call of the process (harmless for single-GPU use)
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
-__all__ = ["VectorDatabase", "ShardedVectorDatabase", "DistributedShardedVectorDatabase", "EmbeddingModel",
-           "AlternativeModel"]
+__all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
+           "EmbeddingModel", "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -22,6 +22,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "ShardedVectorDatabase":
         from .sharded_vector_database import ShardedVectorDatabase
         return ShardedVectorDatabase
+    if name == "ShardedVectorDatabaseUsearch":
+        from .sharded_vector_database_usearch import ShardedVectorDatabaseUsearch
+        return ShardedVectorDatabaseUsearch
     if name == "DistributedShardedVectorDatabase":
         from .distributed import DistributedShardedVectorDatabase
         return DistributedShardedVectorDatabase

@@ -418,6 +418,8 @@ class FilterAndRerankMixin:
     """Needs: self.inverted_index, self._ids (_IdIndex), self.metadata, self.hash_vectorizer, self._mat (_RowStore),
     self.index, self.embedding_size, self._device, self.lock."""
 
+    _row_store = _RowStore   # the class that holds the stacked rows (ShardedVectorDatabaseUsearch keeps them on the host)
+
     # ---- device mirror -----------------------------------------------------------------------------
     def _build_index(self):
         """Bring the device matrix up to date (caller holds the lock).
@@ -443,7 +445,7 @@ class FilterAndRerankMixin:
         if self.embedding_size is None:
             self.embedding_size = vectors[0].shape[0]
         if self._mat is None:
-            self._mat = _RowStore(self.embedding_size)
+            self._mat = self._row_store(self.embedding_size)
         first = self._mat.n
         if len(vectors):
             if isinstance(vectors, np.ndarray) and vectors.ndim == 2:   # a batch that arrived as ONE float32 matrix: no per-row work

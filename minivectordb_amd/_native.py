@@ -110,6 +110,27 @@ PROTOTYPES = {
     "mvdb_prof_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_double)]),
     "mvdb_prof_symbol": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
+    # int8 cosine index (cos8.hip)
+    "mvdb_cos8_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_cos8_free": (ctypes.c_int, [c_vp]),
+    "mvdb_cos8_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_cos8_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_cos8_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_cos8_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_cos8_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_cos8_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_cos8_get_codes": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
+    "mvdb_cos8_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_cos8_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_cos8_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp,
+                                               c_vp]),
+    "mvdb_cos8_rowset_create": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_cos8_rowset_size": (ctypes.c_int64, [c_vp]),
+    "mvdb_cos8_rowset_is_bitmap": (ctypes.c_int, [c_vp]),
+    "mvdb_cos8_rowset_free": (ctypes.c_int, [c_vp]),
+    "mvdb_cos8_search_rowset": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_cos8_search_rowset_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64,
+                                                      c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -380,6 +401,126 @@ class RowSet:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib().mvdb_rowset_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Cos8Index:
+    """mvdb_cos8*: int8 codes of the rows on the device, exact int8 cosine search (include/mvdb.h "int8 cosine index").
+    D holds distances, ascending; missing slots are label -1 / +FLT_MAX.  The method names follow FlatIndex so that the
+    database layer drives either; `normalize` / `normalize_q` are accepted and ignored: the quantiser normalises."""
+
+    def __init__(self, d, device=0):
+        self._h = ctypes.c_void_p()
+        self.d = int(d)
+        self.device = device
+        check(lib().mvdb_cos8_create(self.d, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_cos8_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_cos8_ntotal(self._h))
+
+    def reset(self):
+        check(lib().mvdb_cos8_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_cos8_reserve(self._h, int(n)))
+
+    def _rows2d(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def add(self, x, normalize=None):
+        x = self._rows2d(x)
+        check(lib().mvdb_cos8_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_cos8_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def get_codes(self, row0, n):
+        """(codes int8 [n, d], a2 int32 [n]) of rows [row0, row0 + n)."""
+        codes = np.empty((int(n), self.d), dtype=np.int8)
+        a2 = np.empty(int(n), dtype=np.int32)
+        check(lib().mvdb_cos8_get_codes(self._h, int(row0), int(n), _ptr(codes), _ptr(a2)))
+        return codes, a2
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_cos8_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def _out(self, nq, k):
+        return np.empty((nq, int(k)), dtype=np.float32), np.empty((nq, int(k)), dtype=np.int64)
+
+    def search(self, q, k, normalize_q=None):
+        q = self._rows2d(q)
+        D, I = self._out(q.shape[0], k)
+        check(lib().mvdb_cos8_search(self._h, _ptr(q), q.shape[0], int(k), _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, stream=0, label_offset=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_cos8_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(label_offset),
+                                            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def rowset(self, rows, excluded=False):
+        """The listed rows (or, excluded=True, every row BUT them) resident on the device: see Cos8RowSet."""
+        return Cos8RowSet(self, rows, excluded)
+
+    def search_rowset(self, q, k, rowset, normalize_q=None):
+        """Search a resident Cos8RowSet; labels are ROW NUMBERS of the index."""
+        q = self._rows2d(q)
+        D, I = self._out(q.shape[0], k)
+        check(lib().mvdb_cos8_search_rowset(self._h, _ptr(q), q.shape[0], int(k), rowset._h, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_rowset_device(self, q_ptr, nq, k, rowset, D_ptr, I_ptr, stream=0, label_offset=0):
+        check(lib().mvdb_cos8_search_rowset_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), rowset._h, int(label_offset), ctypes.c_void_p(D_ptr),
+            ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+
+class Cos8RowSet:
+    """mvdb_cos8_rowset*: a filter's rows resident on the device (an exclusion bitmap or a sorted row list).  Valid until
+    rows are removed from the index it was built on; rows appended later are not part of it."""
+
+    def __init__(self, index, rows, excluded=False):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        self._h = ctypes.c_void_p()
+        check(lib().mvdb_cos8_rowset_create(index._h, _ptr(rows), rows.shape[0], int(bool(excluded)),
+                                            ctypes.byref(self._h)))
+
+    def __len__(self):
+        return int(lib().mvdb_cos8_rowset_size(self._h))
+
+    @property
+    def is_bitmap(self):
+        return bool(lib().mvdb_cos8_rowset_is_bitmap(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_cos8_rowset_free(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -2806,3 +2806,43 @@ int mvdb_prof_read(const char* name, int64_t* launches, double* total_ms) {
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// large-k selection for the int8 cosine index (cos8.hip): the radix select above over one query's materialised
+// scores, shared rather than compiled twice (the select kernels are defined in this translation unit only)
+// ================================================================================================
+namespace mvdb {
+
+size_t select_state_bytes() { return sizeof(SelectState); }
+
+// scores[n] (score = -distance; -inf = row not selected) -> the k best (D = distance, I = index into scores +
+// label_offset), missing slots -1 / +FLT_MAX.  keys must hold pow2ceil(max(k, 2)) entries.
+int select_scores_topk(const float* scores, int64_t n, int k, int64_t label_offset, float* D, int64_t* I, void* state,
+                       uint64_t* keys, int device, hipStream_t s) {
+    SelectState* st = (SelectState*)state;
+    const int64_t k_eff = std::min<int64_t>(k, n);
+    const int64_t P = pow2ceil(std::max<int64_t>(k, 2));
+    const int sel_grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, device_cus(device) * 8));
+    hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, s, st, (uint64_t)k_eff);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(sel_grid), dim3(256), 0, s, scores, n, shift, st);
+        hipLaunchKernelGGL(radix_pick_kernel, dim3(1), dim3(256), 0, s, shift, st);
+    }
+    hipLaunchKernelGGL(radix_compact_kernel, dim3(sel_grid), dim3(256), 0, s, scores, n, st, keys);
+    if (P > k_eff)
+        hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)((P - k_eff + 255) / 256)), dim3(256), 0, s, keys, k_eff, P);
+    if (P <= 4096) {
+        hipLaunchKernelGGL(bitonic_sort_lds_kernel, dim3(1), dim3(1024), 0, s, keys, (int)P);
+    } else {
+        for (int64_t size = 2; size <= P; size <<= 1)
+            for (int64_t stride = size >> 1; stride > 0; stride >>= 1)
+                hipLaunchKernelGGL(bitonic_step_kernel, dim3((unsigned)((P / 2 + 255) / 256)), dim3(256), 0, s, keys, P,
+                                   size, stride);
+    }
+    hipLaunchKernelGGL(emit_sorted_kernel, dim3((k + 255) / 256), dim3(256), 0, s, keys, k, MVDB_METRIC_L2, label_offset,
+                       D, I, 1);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace mvdb

@@ -26,7 +26,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from ._dbcore import FilterAndRerankMixin, _IdIndex, _RowStore
+from ._dbcore import FilterAndRerankMixin, _IdIndex
 
 
 def _shard_number(file_name):
@@ -77,7 +77,7 @@ class ShardedVectorDatabase(FilterAndRerankMixin):
 
     @embeddings.setter
     def embeddings(self, value):
-        self._mat = None if value is None else _RowStore.adopt(value)
+        self._mat = None if value is None else self._row_store.adopt(value)
         if self.index is not None:
             self.index.reset()
         self._embeddings_changed = True
@@ -144,7 +144,7 @@ class ShardedVectorDatabase(FilterAndRerankMixin):
         self._ids = _IdIndex(ids)
         self._first_open = 0
         if pieces:
-            self._mat = _RowStore.adopt(np.concatenate(pieces, axis=0))
+            self._mat = self._row_store.adopt(np.concatenate(pieces, axis=0))
         if self._mat is not None and self._mat.n > 0:
             self.embedding_size = self._mat.d
             with self.lock:
