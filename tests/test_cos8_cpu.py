@@ -186,3 +186,87 @@ def test_autocut_distances_quirks(fake_index, tmp_path):
     assert ids == (5,)
     ids, dist, _ = db.find_most_similar(x[2], k=3, autocut=True)
     assert ids == [3] and isinstance(ids, list)     # 0 then a jump: everything after the zero is cut
+
+
+# ---- the case tables of the GPU tests (tests/cos8_cases.py) ----------------------------------------------------------
+import cos8_cases as C  # noqa: E402
+
+
+def test_expected_form_restates_the_dispatch():
+    assert len(C.all_scan_forms()) == 96 and len(C.all_mfma_forms()) == 2
+    assert [C.width_class(c) for c in (1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65, 256)] == \
+        [(1, 1), (2, 1), (4, 1), (4, 1), (8, 1), (8, 1), (16, 1), (16, 1), (32, 1), (32, 1), (64, 1), (64, 1), (64, 4), (64, 4)]
+    assert C.expected_form(512, 1, 10, "none") == ("scan", 32, 1, 1, 0, False)
+    assert C.expected_form(512, 7, 10, "excluded") == ("scan", 32, 1, 8, 2, False)
+    assert C.expected_form(512, 8, 10, "excluded") == ("mfma", 2)
+    assert C.expected_form(512, 8, 64, "none") == ("mfma", 0)
+    assert C.expected_form(512, 8, 65, "none") == ("scan", 32, 1, 8, 0, True)      # large k: never the matrix cores
+    assert C.expected_form(512, 33, 10, "list") == ("scan", 32, 1, 8, 1, False)    # a row list: never the matrix cores
+    assert C.expected_form(1024, 8, 10, "none") == ("mfma", 0)
+    assert C.expected_form(1025, 8, 10, "none") == ("scan", 64, 4, 4, 0, False)    # the queries no longer fit in LDS
+    assert C.expected_form(4096, 1, 200, "bitmap") == ("scan", 64, 4, 1, 2, True)
+    assert C.rowset_is_bitmap(800, 99, False) is False and C.rowset_is_bitmap(800, 100, False) is True
+    assert C.rowset_is_bitmap(800, 0, True) is True
+
+
+def test_case_table_reaches_every_kernel_form():
+    """A condition on the table: under expected_form the GPU cases launch all 96 instantiations of cos8_scan_kernel and
+    both of cos8_mfma_kernel, and the matrix-core cases cover, for every row and for the bitmap: an odd and an even chunk
+    count, rows of at most 8 K-steps and of more, k = 1 and k = 64."""
+    assert len(set(C.CASES)) == len(C.CASES)
+    forms = {}
+    for case in C.CASES:
+        n, d, nq, k, kind = case
+        assert kind in C.FILTER_KINDS and 1 <= d <= C.MAX_D and 1 <= k <= C.MAX_K and n % 2 == 1 and n > 2048
+        rows, excluded, keep = C.filter_rows(n, kind)
+        if kind != "none":       # the rows of the case really are stored the way expected_form assumes
+            assert C.rowset_is_bitmap(n, len(rows), excluded) == (C.FILTER_FORM[kind] == 2), case
+            assert len(keep) > 200, case
+        forms.setdefault(C.expected_form(d, nq, k, kind), []).append(case)
+    scan = {f for f in forms if f[0] == "scan"}
+    assert scan == C.all_scan_forms(), sorted(C.all_scan_forms() - scan)
+    assert len(scan) == 96
+    assert {f for f in forms if f[0] == "mfma"} == C.all_mfma_forms()
+    for F in (0, 2):
+        mf = forms[("mfma", F)]
+        chunks = [C.nchunk_of(d) for _, d, _, _, _ in mf]
+        strides = [16 * c for c in chunks]
+        ks = [k for _, _, _, k, _ in mf]
+        assert any(c % 2 == 1 for c in chunks) and any(c % 2 == 0 for c in chunks), (F, chunks)
+        assert any(s <= 256 for s in strides) and any(s > 256 for s in strides), (F, strides)
+        assert 1 in ks and 64 in ks, (F, ks)
+        assert {nq for _, _, nq, _, _ in mf} >= {8, 33, 70}       # one pass, a partial second pass, a partial third
+    # every d of the table's classes is used, both ends of each class, and the documented maximum
+    assert {d for _, d, _, _, _ in C.CASES} >= {d for dims in C.CLASS_DIMS for d in dims} | {C.MAX_D}
+    assert {k for _, _, _, k, _ in C.CASES} >= {1, 10, 64, 65, 200}
+
+
+@pytest.mark.parametrize("d", [1, 3, 17, 64, 1000, 4096])
+def test_special_rows_match_per_element_restatement(d):
+    x = C.special_rows(d, np.random.default_rng(d))
+    assert x.dtype == np.float32 and x.shape[1] == d
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        codes, a2 = O.quantize(x)
+        for i, row in enumerate(x):
+            want = O.quantize_scalar(row)
+            assert list(codes[i]) == want, (d, i)
+            assert a2[i] == sum(c * c for c in want)
+    for i in C.SPECIAL_ZERO_ROWS:
+        assert not codes[i].any(), (d, i)
+    assert (codes[7] == 127).all() and a2[7] == 127 * 127 * d            # x * 127f overflows: every code clamps
+    assert (codes[8] == -int(127 / np.sqrt(d))).all()                    # subnormals are kept, not flushed
+    assert codes[4].any() and codes[3].any() and codes[11].any()
+
+
+def test_kernel_census_lists_every_form():
+    """profiles/cos8_forms_kernel_census.txt is a kernel trace of the GPU file on the device: the symbols it saw are the
+    forms that expected_form() predicts, so the restatement of the dispatch above tells the truth."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "profiles", "cos8_forms_kernel_census.txt")) as f:
+        seen = set(re.findall(r"cos8_(?:scan|mfma)_kernel<[^>]*>", f.read()))
+    want = {"cos8_mfma_kernel<%d>" % f[1] for f in C.all_mfma_forms()}
+    want |= {"cos8_scan_kernel<%d, %d, %d, %d, %s>" % (f[1], f[2], f[3], f[4], "true" if f[5] else "false")
+             for f in C.all_scan_forms()}
+    assert len(want) == 98 and seen == want, sorted(seen ^ want)
