@@ -238,7 +238,9 @@ int mvdb_index_search_masked_device(const mvdb_index* idx, const float* q_dev, i
  * carries its bitmap, under which a BATCH of queries shares corpus passes where that beats one gathered scan per query (10M x
  * 512, 30 % of the rows: 64 queries 1.7 ms instead of 58 ms).  A set belongs to the index state it
  * was built against: rows appended later are not part of it; after a removal (rows renumbered) searching it fails with
- * MVDB_ERR_ARG. */
+ * MVDB_ERR_ARG.  A set also belongs to its INDEX: every search entry point that takes a row set refuses, with MVDB_ERR_ARG
+ * and without writing anything, a set that was created on another index object, even one of the same device, row count and
+ * removal history (its row numbers mean other rows there). */
 typedef struct mvdb_rowset mvdb_rowset;
 int mvdb_rowset_create(const mvdb_index* idx, const int64_t* rows_host, int64_t m, int excluded, mvdb_rowset** out);
 int64_t mvdb_rowset_size(const mvdb_rowset* rs);      /* rows selected */
@@ -253,6 +255,32 @@ int mvdb_index_search_rowset(const mvdb_index* idx, const float* q_host, int nq,
 int mvdb_index_search_rowset_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q,
                                     const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev,
                                     void* stream);
+
+/* A batch in which EVERY QUERY HAS ITS OWN ROW SET (a serving layer that collects the queries of many callers, each with
+ * its own filter): query i is searched under sets[i]; a NULL entry means every row.  Several queries may name the same set.
+ * Contract: row i of (D, I) is BIT FOR BIT what mvdb_index_search_rowset (mvdb_index_search for a NULL entry) returns for
+ * query i alone with nq = 1 on the default routing — not "identical away from fp32 near-ties" as the shared-pass batch
+ * contract above.  Labels are row numbers.  The shadow_single_query option does not apply to this entry point.
+ * Routing: all queries whose set is in LIST form share ONE gathered launch over work items (query, slice of its list) and
+ * one segmented merge that also maps positions to row numbers; a long list is cut into many items, so one large filter
+ * beside many small ones does not serialise the launch.  A query whose set is a BITMAP (mvdb_rowset_is_bitmap) or NULL is
+ * answered by the exact single-query scan straight into row i: callers with many such queries under one set should use
+ * mvdb_index_search_rowset / mvdb_index_search, which share corpus passes.  k > 64: every query takes the scores +
+ * radix-select route on its own list — correct, not fast.
+ * Every set is checked before anything is enqueued: one stale or foreign set fails the whole call with MVDB_ERR_ARG and
+ * nothing is written.  No reference counterpart (the reference answers one query per call). */
+int mvdb_index_search_grouped(const mvdb_index* idx, const float* q_host, int nq, int k, int normalize_q,
+                              const mvdb_rowset* const* sets, float* D_host, int64_t* I_host);
+/* Device-resident variant, under the contract of mvdb_index_search_device: enqueued on `stream`, one search at a time per
+ * (index, stream), capturable into a hipGraph after one eager call of the same shape (same sets) has sized the workspace;
+ * labels are row numbers + label_offset.  The item table travels through a pinned staging copy and an asynchronous copy on
+ * `stream`.  The call does not wait for the device: a stream's workspace keeps a ring of staging copies and takes one whose
+ * upload has already run, or adds one (a few KB); only with 64 grouped calls all still queued on one stream does a call wait
+ * for the oldest upload.  A CAPTURED call takes over a pinned staging copy of its own (left behind by the eager call of the
+ * same shape), which the graph re-reads at every replay: it is kept until the index is freed, one per capture. */
+int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q,
+                                     const mvdb_rowset* const* sets, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                                     void* stream);
 
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the

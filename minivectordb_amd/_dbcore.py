@@ -18,6 +18,7 @@ reference's ``list(set_of_rows)`` (vector_database.py:510) follows CPython's has
 """
 import bisect
 from array import array
+from collections import OrderedDict
 from operator import ge, gt, le, lt, ne
 
 import numpy as np
@@ -507,6 +508,8 @@ class FilterAndRerankMixin:
         # built against the previous rows: dropped, not closed — a search running outside the lock may still hold one
         # (its device memory goes when the last reference does)
         self.__dict__["_rowsets"] = {}
+        self.__dict__["_rowsets_each"] = OrderedDict()   # find_most_similar_each's own cache (bounded by bytes, not entries)
+        self.__dict__["_rowsets_each_bytes"] = 0
 
     _invalidate_filter_cache = _note_write
 
@@ -608,6 +611,160 @@ class FilterAndRerankMixin:
                     if len(cache) >= 16:  # a handful of filters in rotation; each holds device memory until its last user drops it
                         cache.clear()
                     cache[key] = (gen, index, len(wanted), rowset)
+        return rowset
+
+    # ---- a batch in which every query brings its own filter -------------------------------------------------
+    _EACH_FILTER_KEYS = ("metadata_filter", "exclude_filter", "or_filters")
+
+    def find_most_similar_each(self, embeddings, filters, k=5, autocut=False):
+        """Several queries, EACH UNDER ITS OWN FILTER, in one call (no reference counterpart; a serving layer that collects
+        the queries of many callers): ``filters[i]`` is None or a dict with any of ``metadata_filter``, ``exclude_filter``,
+        ``or_filters``, and element i of the returned list is what
+        ``find_most_similar(embeddings[i], k=k, autocut=autocut, **filters[i])`` returns.  Each distinct filter is evaluated
+        once; all queries whose rows live on the device as a row LIST share one gathered launch (`search_grouped`: bit for bit
+        the single call's arithmetic), unfiltered queries and queries under one dense (bitmap) set go through the batch
+        passes of `find_most_similar_batch`."""
+        queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
+        if queries.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like, one query per row")
+        filters = list(filters)
+        if len(filters) != queries.shape[0]:
+            raise ValueError(f"{len(filters)} filters for {queries.shape[0]} queries")
+        specs = []
+        for f in filters:
+            if f is None:
+                specs.append((None, None, None))
+                continue
+            if not isinstance(f, dict) or any(name not in self._EACH_FILTER_KEYS for name in f):
+                raise ValueError("a filter is None or a dict with any of metadata_filter, exclude_filter, or_filters")
+            specs.append(tuple(f.get(name) for name in self._EACH_FILTER_KEYS))
+        if queries.shape[0] == 0 or self._mat is None:
+            return [([], [], []) for _ in range(queries.shape[0])]
+        if queries.shape[1] != self._mat.d:
+            # before any filter is evaluated: the retry loop below would re-evaluate every distinct filter three times over
+            # before handing the index's own ValueError on
+            raise ValueError(f"query dimension {queries.shape[1]} != index dimension {self._mat.d}")
+        uids = self._ids.uids
+        out = []
+        for found in self._nearest_rows_each(queries, specs, k):
+            hits = []
+            for row, score in found:
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[row], score, self.metadata[row]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, autocut))
+        return out
+
+    def _nearest_rows_each(self, query, specs, k):
+        """_nearest_rows_many with one (metadata_filter, exclude_filter, or_filters) triple per query."""
+        nq = query.shape[0]
+        keys = []
+        for i, spec in enumerate(specs):
+            if not (spec[0] or spec[1] or spec[2]):
+                keys.append(None)            # unfiltered
+                continue
+            try:
+                keys.append(repr(spec))
+            except Exception:
+                keys.append(("unprintable", i))  # evaluated for this query alone, never cached
+        for attempt in range(3):
+            # one pass under the lock: device up to date, every DISTINCT filter evaluated (or found resident), generation captured
+            groups = OrderedDict()   # key -> [count, rowset, wanted, [queries]]
+            with self.lock:
+                if self._embeddings_changed:
+                    self._build_index()
+                index, n_rows = self.index, self._mat.n
+                gen = self.__dict__.get("_write_gen", 0)
+                cache = self.__dict__.get("_rowsets_each")
+                for i, key in enumerate(keys):
+                    group = groups.get(key)
+                    if group is None:
+                        hit = cache.get(key) if (cache and isinstance(key, str)) else None
+                        if hit is not None and hit[0] == gen and hit[1] is index:
+                            cache.move_to_end(key)
+                            group = [hit[2], hit[3], None, []]
+                        elif key is None:
+                            group = [self._row_count(), None, None, []]
+                        else:
+                            wanted = self._get_filtered_indices(*specs[i])
+                            group = [len(wanted), None, wanted, []]
+                        groups[key] = group
+                    group[3].append(i)
+            found = [[] for _ in range(nq)]
+            if index is None:
+                return found
+            try:
+                everything, listed = [], []   # queries over every row; (queries, rowset, count) of the list-form sets
+                for key, (count, rowset, wanted, members) in groups.items():
+                    if not count:
+                        continue
+                    if count == n_rows:
+                        everything.extend(members)
+                        continue
+                    if rowset is None:
+                        rowset = self._resident_rowset_each(index, wanted, key, gen, n_rows)
+                    if getattr(rowset, "is_bitmap", False):
+                        # a dense set: its queries share corpus passes under the bitmap (the existing batch route)
+                        scores, rows = index.search_rowset(query[members], min(k, count), rowset, normalize_q=True)
+                        self._scatter_hits(found, members, scores, rows)
+                    else:
+                        listed.append((members, rowset, count))
+                if everything:
+                    everything.sort()
+                    scores, rows = index.search(query[everything], min(k, n_rows), normalize_q=True)
+                    self._scatter_hits(found, everything, scores, rows)
+                if listed and hasattr(index, "search_grouped"):
+                    # ONE launch for every query under a row list; a query with fewer rows than the call's k gets -1 padding
+                    members = [i for group in listed for i in group[0]]
+                    sets = [group[1] for group in listed for _ in group[0]]
+                    take = min(k, max(group[2] for group in listed))
+                    scores, rows = index.search_grouped(query[members], take, sets, normalize_q=True)
+                    self._scatter_hits(found, members, scores, rows)
+                else:
+                    # an index without a grouped search (the int8 cosine index): one search per distinct filter
+                    for members, rowset, count in listed:
+                        scores, rows = index.search_rowset(query[members], min(k, count), rowset, normalize_q=True)
+                        self._scatter_hits(found, members, scores, rows)
+                return found
+            except ValueError:
+                # another thread deleted rows between the filters and the search: evaluate them again on the current rows
+                if attempt == 2:
+                    raise
+        return found
+
+    @staticmethod
+    def _scatter_hits(found, members, scores, rows):
+        for j, i in enumerate(members):
+            found[i] = [(int(r), s) for r, s in zip(rows[j], scores[j]) if r != -1]
+
+    def _resident_rowset_each(self, index, wanted, key, gen, n_rows):
+        """`_resident_rowset` for find_most_similar_each.  A batch with 50 tenants would empty the 16-entry cache of the
+        single-filter methods on every call, so this method keeps its own, bounded by DEVICE BYTES: least-recently-used sets go
+        once the sets held exceed 2 x 8 B x the current row count (a partition of the corpus into disjoint tenants costs
+        exactly 8 B x n as row lists; the factor 2 allows overlapping filters).  Dropped by the same `_note_write`; an evicted
+        set stays alive while a running call holds it."""
+        if wanted.gone is not None:
+            rowset = index.rowset(wanted.gone, excluded=True)
+        else:
+            rowset = index.rowset(wanted.rows)
+        if isinstance(key, str):
+            nbytes = (n_rows + 7) // 8 if getattr(rowset, "is_bitmap", False) else 8 * len(wanted)
+            bound = 2 * 8 * n_rows
+            with self.lock:
+                if self.__dict__.get("_write_gen", 0) == gen and self.index is index and nbytes <= bound:
+                    cache = self.__dict__.get("_rowsets_each")
+                    if cache is None:
+                        cache = self.__dict__["_rowsets_each"] = OrderedDict()
+                        self.__dict__["_rowsets_each_bytes"] = 0
+                    held = self.__dict__.get("_rowsets_each_bytes", 0)
+                    old = cache.pop(key, None)
+                    if old is not None:
+                        held -= old[4]
+                    while cache and held + nbytes > bound:
+                        held -= cache.popitem(last=False)[1][4]
+                    cache[key] = (gen, index, len(wanted), rowset, nbytes)
+                    self.__dict__["_rowsets_each_bytes"] = held + nbytes
         return rowset
 
     def _package(self, hits, autocut):

@@ -90,6 +90,9 @@ PROTOTYPES = {
     "mvdb_index_search_rowset": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_index_search_rowset_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                        ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_grouped_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                                        ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -339,6 +342,47 @@ class FlatIndex:
         """Device-pointer variant of search_rowset (labels: row numbers + label_offset); enqueues on `stream` and returns."""
         check(lib().mvdb_index_search_rowset_device(
             self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(bool(normalize_q)), rowset._h, int(label_offset),
+            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    @staticmethod
+    def _rowset_table(rowsets, nq):
+        """The `const mvdb_rowset* const*` argument of the grouped entry points: one handle per query, NULL = every row."""
+        rowsets = list(rowsets)
+        if len(rowsets) != nq:
+            raise ValueError(f"{len(rowsets)} row sets for {nq} queries")
+        table = (ctypes.c_void_p * nq)()
+        for i, rs in enumerate(rowsets):
+            if rs is not None:
+                if not rs._h:
+                    raise ValueError(f"row set {i} is closed")
+                table[i] = rs._h.value
+        return table
+
+    def search_grouped(self, q, k, rowsets, normalize_q=False, out=None):
+        """Every query under ITS OWN resident RowSet (None = every row): row i is bit for bit what search_rowset(q[i:i+1], k,
+        rowsets[i]) / search(q[i:i+1], k) returns.  List-form sets share one gathered launch; labels are row numbers.
+        out=(D, I): caller-owned result arrays (float32 / int64, [nq, k], C-contiguous)."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[1]} != index dimension {self.d}")
+        nq = q.shape[0]
+        table = self._rowset_table(rowsets, nq)
+        if out is None:
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+        else:
+            D, I = out
+            if (D.dtype != np.float32 or I.dtype != np.int64 or D.shape != (nq, k) or I.shape != (nq, k)
+                    or not D.flags.c_contiguous or not I.flags.c_contiguous):
+                raise ValueError("out must be C-contiguous (float32[nq, k], int64[nq, k])")
+        check(lib().mvdb_index_search_grouped(self._h, _ptr(q), nq, int(k), int(bool(normalize_q)), table, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_grouped_device(self, q_ptr, nq, k, rowsets, D_ptr, I_ptr, stream=0, normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_grouped (labels: row numbers + label_offset); enqueues on `stream` and returns."""
+        table = self._rowset_table(rowsets, int(nq))
+        check(lib().mvdb_index_search_grouped_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(bool(normalize_q)), table, int(label_offset),
             ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
 
     def search_masked(self, q, k, mask_words, normalize_q=False, labels="rows"):

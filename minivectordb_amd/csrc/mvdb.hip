@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "scan_kernels.hpp"
+#include "grouped_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
 #include "half_scan.hpp"
@@ -63,6 +64,8 @@ Knobs read_knobs() {
     k.disable_l2_cert = env_int("MVDB_DISABLE_L2_CERT", 0) != 0;
     k.disable_half_shadow = env_int("MVDB_DISABLE_HALF_SHADOW", 0) != 0;
     k.shadow_single_query = env_int("MVDB_SHADOW_SINGLE_QUERY", 0) != 0;
+    k.grouped_items_per_cu = env_int("MVDB_GROUPED_ITEMS_PER_CU", 0);
+    k.grouped_min_batches = std::max(1, env_int("MVDB_GROUPED_MIN_BATCHES", 4));
     if (const char* v = getenv("MVDB_COMPACT_BYTES"))
         if (*v) k.compact_bytes = std::max(1ll, atoll(v));
     k.compact_inplace = env_int("MVDB_COMPACT_INPLACE", 1) != 0;
@@ -206,6 +209,17 @@ struct Workspace {
     std::mutex use_mu;  // stream workspaces are shared by every host thread that names the stream: one search at a time
     bool captured = false;         // a search on this workspace has been captured into a hipGraph: its buffers are never freed
     std::vector<void*> retired;    // ... outgrown ones wait here until the workspace goes (common.hpp, RetireScope)
+    // grouped search (mvdb_index_search_grouped): the item table on the device, its pinned staging copy, and the event recorded
+    // behind the upload — the staging copy is rewritten only once the upload that reads it has run
+    DevBuf<char> gtab;
+    struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
+        PinnedBuf buf;
+        hipEvent_t ev = nullptr;
+        bool busy = false;
+    };
+    std::vector<GroupedStage*> gstage;  // a ring: a call takes a copy whose upload has run, or adds one (stage_grouped_table)
+    std::vector<void*> gpin_captured;  // a captured call's upload re-reads its staging copy at every replay: kept, never rewritten
+    PinnedBuf gpin_spare;              // ... allocated by the eager calls (nothing may be allocated while a stream is capturing)
 
     int init(int dev, hipStream_t s) {
         device = dev;
@@ -236,6 +250,16 @@ struct Workspace {
         relabel.release();
         nfail.release();
         pin.release();
+        gtab.release();
+        for (GroupedStage* g : gstage) {
+            g->buf.release();
+            if (g->ev) (void)hipEventDestroy(g->ev);
+            delete g;
+        }
+        gstage.clear();
+        gpin_spare.release();
+        for (void* p : gpin_captured) (void)hipHostFree(p);
+        gpin_captured.clear();
         for (void* old : retired) (void)hipFree(old);
         retired.clear();
         if (st) (void)hipFree(st);
@@ -245,7 +269,10 @@ struct Workspace {
 
 }  // namespace
 
+static std::atomic<uint64_t> g_index_serial{0};
+
 struct mvdb_index {
+    const uint64_t serial = ++g_index_serial;  // unique per index object of the process: resident row sets name their index by it
     int d = 0, d4 = 0, metric = 0, device = 0;
     int64_t ld = 0;
     float* X = nullptr;
@@ -2490,6 +2517,7 @@ static bool masked_batch_possible(const mvdb_index* idx, int nq, int k, int64_t 
 }
 
 struct mvdb_rowset {
+    uint64_t owner = 0;       // serial number of the index the set was built on (never reused, unlike an address)
     int device = 0;
     int64_t n_at_create = 0;  // the index's row count the set was built against
     uint64_t renumbered = 0;  // ... and its renumbering generation
@@ -2525,6 +2553,7 @@ int mvdb_rowset_create(const mvdb_index* idx, const int64_t* rows_host, int64_t 
     }
     DeviceGuard dg(idx->device);
     mvdb_rowset* rs = new mvdb_rowset();
+    rs->owner = idx->serial;
     rs->device = idx->device;
     rs->n_at_create = n;
     rs->renumbered = idx->renumbered;
@@ -2601,6 +2630,7 @@ static int rowset_check(const mvdb_index* idx, const mvdb_rowset* rs) {
     if (!rs) return fail(MVDB_ERR_ARG, "row set is NULL");
     // rows appended since the set was built are simply not part of it (the filter was evaluated before they arrived);
     // a SHRUNK index has renumbered its rows: the set is stale
+    if (rs->owner != idx->serial) return fail(MVDB_ERR_ARG, "the row set belongs to another index");
     if (rs->device != idx->device || rs->n_at_create > idx->n || rs->renumbered != idx->renumbered)
         return fail(MVDB_ERR_ARG, "the row set was built for another state of the index (%lld rows then, %lld now)",
                     (long long)rs->n_at_create, (long long)idx->n);
@@ -2679,6 +2709,267 @@ int mvdb_index_search_rowset_device(const mvdb_index* idx, const float* q_dev, i
         q = ws->q.p;
     }
     return rowset_search_core(idx, ws, q, nq, k, normalize_q, rs, label_offset, D_dev, I_dev);
+}
+
+}  // extern "C"
+
+// ---- grouped search: every query under its own row set (grouped_scan.hpp) ------------------------------------------------
+namespace {
+
+template <int G, int C, int U>
+int launch_grouped_gcu(int metric, const GroupedScanArgs& a, int nitems, hipStream_t s) {
+    constexpr bool kAlwaysFull = G == 32 && C > 1;  // (chosen for rows that fill it exactly: no lane-masked form, as launch_scan_inst)
+    const bool masked = !kAlwaysFull && a.d4 != G * C;
+    void (*kern)(GroupedScanArgs);
+    if constexpr (kAlwaysFull) {
+        kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, false> : grouped_scan_kernel<G, C, U, 1, false>;
+    } else {
+        if (masked) kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, true> : grouped_scan_kernel<G, C, U, 1, true>;
+        else kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, false> : grouped_scan_kernel<G, C, U, 1, false>;
+    }
+    prof_symbol("grouped_scan", "grouped_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, metric == MVDB_METRIC_IP ? 0 : 1,
+                masked ? "true" : "false");
+    int slot = prof_begin("grouped_scan", s);
+    hipLaunchKernelGGL(kern, dim3(nitems), dim3(kScanThreads), 0, s, a);
+    prof_end(slot, s);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// rows in flight per wave: what the row-list forms of launch_scan use (U does not enter the arithmetic)
+constexpr int grouped_u(int C) { return C <= 3 ? 4 : 1; }
+
+int launch_grouped(int metric, const GroupedScanArgs& a, int nitems, hipStream_t s) {
+    const Shape sh = choose_shape(a.d4);
+#define MVDB_GROUPED_CASE(G_, C_) \
+    if (sh.G == G_ && sh.C == C_) return launch_grouped_gcu<G_, C_, grouped_u(C_)>(metric, a, nitems, s);
+    MVDB_GROUPED_CASE(16, 1)
+    MVDB_GROUPED_CASE(32, 1)
+    MVDB_GROUPED_CASE(32, 3)
+    MVDB_GROUPED_CASE(64, 1)
+    MVDB_GROUPED_CASE(64, 2)
+    MVDB_GROUPED_CASE(64, 3)
+    MVDB_GROUPED_CASE(64, 4)
+    MVDB_GROUPED_CASE(64, 5)
+    MVDB_GROUPED_CASE(64, 6)
+    MVDB_GROUPED_CASE(64, 7)
+    MVDB_GROUPED_CASE(64, 8)
+    MVDB_GROUPED_CASE(64, 16)
+#undef MVDB_GROUPED_CASE
+    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+}
+
+// Cut the lists of the call's list-form queries into work items.  The rule:
+//   S = max(S_min, ceil(sum m_i / T)) rows per item, rounded up to whole block steps (4 waves x RB rows);
+//   T = CUs x items_per_cu — the launch fills the device when there is enough work;
+//   S_min = min_batches block steps — a short list is ONE item, and an item is never so short that the query load, the
+//           prologue and the block merge outweigh its rows;
+//   query i gets ceil(m_i / S) items of equal length (to a block step).
+// At most T + (number of list queries) items come out.
+void plan_grouped(const mvdb_index* idx, int nq, const mvdb_rowset* const* sets, std::vector<GroupedQuery>& queries,
+                  std::vector<GroupedItem>& items) {
+    const Shape sh = choose_shape(idx->d4);
+    const int64_t step = (int64_t)kScanWaves * (kWave / sh.G) * grouped_u(sh.C);  // rows one block takes per loop step
+    const int per_cu = idx->kn.grouped_items_per_cu > 0 ? idx->kn.grouped_items_per_cu : 4;  // swept on the device: DESIGN.md section 6c
+    const int64_t T = (int64_t)device_cus(idx->device) * per_cu;
+    int64_t sum = 0;
+    for (int i = 0; i < nq; ++i)
+        if (sets[i] && sets[i]->rows) sum += sets[i]->count;
+    int64_t S = std::max<int64_t>((int64_t)idx->kn.grouped_min_batches * step, (sum + T - 1) / T);
+    S = (S + step - 1) / step * step;
+    queries.resize((size_t)nq + 1);
+    items.clear();
+    for (int i = 0; i < nq; ++i) {
+        GroupedQuery& gq = queries[i];
+        gq.pad_ = 0;
+        gq.first_item = (int)items.size();
+        if (!(sets[i] && sets[i]->rows)) {  // bitmap or NULL: not part of the grouped launch
+            gq.rows = nullptr;
+            gq.m = -1;
+            continue;
+        }
+        const int64_t m = sets[i]->count;
+        gq.rows = m > 0 ? sets[i]->rows : nullptr;
+        gq.m = m;
+        if (m == 0) continue;
+        const int64_t pieces = (m + S - 1) / S;
+        const int64_t len = ((m + pieces - 1) / pieces + step - 1) / step * step;
+        for (int64_t b = 0; b < m; b += len)
+            items.push_back(GroupedItem{i, (uint32_t)b, (uint32_t)std::min(m, b + len), 0u});
+    }
+    queries[nq] = GroupedQuery{nullptr, -1, (int)items.size(), 0};
+}
+
+// The table reaches the device without a wait for the device: pinned staging + an asynchronous copy on the search's stream.
+// A staging copy may be rewritten only once the upload that reads it has run, and the device entry must not wait for
+// that: the workspace keeps a ring of copies, a call takes one whose upload has completed (hipEventQuery) or adds a new
+// one (a few KB each).  Only with kMaxGroupedStages uploads all still pending — that many whole searches queued on one
+// stream — does a call wait, for the oldest.
+constexpr size_t kMaxGroupedStages = 64;
+int stage_grouped_table(Workspace* ws, const std::vector<GroupedQuery>& queries, const std::vector<GroupedItem>& items,
+                        const GroupedQuery** q_dev, const GroupedItem** it_dev) {
+    const size_t qbytes = queries.size() * sizeof(GroupedQuery);
+    const size_t ibytes = items.size() * sizeof(GroupedItem);
+    const size_t bytes = qbytes + ibytes;
+    MVDB_TRY(ws->gtab.reserve(bytes));
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    const bool capturing = ws->stream && hipStreamIsCapturing(ws->stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
+    void* pin = nullptr;
+    Workspace::GroupedStage* slot = nullptr;
+    if (capturing) {
+        // the graph's upload node reads its staging copy at every replay: the call takes over the spare buffer an eager call
+        // of the same shape has left behind (allocation is not capturable)
+        if (ws->gpin_spare.cap < bytes)
+            return fail(MVDB_ERR_ARG, "a grouped search is being captured before an eager call of the same shape has sized the workspace");
+        pin = ws->gpin_spare.p;
+        ws->gpin_captured.push_back(pin);
+        ws->gpin_spare.p = nullptr;
+        ws->gpin_spare.cap = 0;
+    } else {
+        if (!ws->own_stream) MVDB_TRY(ws->gpin_spare.reserve(bytes));  // (caller streams only: the host entry's workspaces are never captured)
+        for (Workspace::GroupedStage* g : ws->gstage) {
+            if (g->busy && hipEventQuery(g->ev) == hipSuccess) g->busy = false;
+            if (!g->busy) {
+                slot = g;
+                break;
+            }
+        }
+        (void)hipGetLastError();  // (hipErrorNotReady of a pending upload is not an error)
+        if (!slot && ws->gstage.size() < kMaxGroupedStages) {
+            slot = new Workspace::GroupedStage();
+            ws->gstage.push_back(slot);
+        }
+        if (!slot) {
+            slot = ws->gstage.front();
+            MVDB_HIP(hipEventSynchronize(slot->ev));
+            slot->busy = false;
+            std::rotate(ws->gstage.begin(), ws->gstage.begin() + 1, ws->gstage.end());  // the oldest becomes the newest
+        }
+        MVDB_TRY(slot->buf.reserve(bytes));
+        pin = slot->buf.p;
+    }
+    memcpy(pin, queries.data(), qbytes);
+    if (ibytes) memcpy((char*)pin + qbytes, items.data(), ibytes);
+    MVDB_HIP(hipMemcpyAsync(ws->gtab.p, pin, bytes, hipMemcpyHostToDevice, ws->stream));
+    if (!capturing) {
+        if (!slot->ev) MVDB_HIP(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
+        MVDB_HIP(hipEventRecord(slot->ev, ws->stream));
+        slot->busy = true;
+    }
+    *q_dev = reinterpret_cast<const GroupedQuery*>(ws->gtab.p);
+    *it_dev = reinterpret_cast<const GroupedItem*>(ws->gtab.p + qbytes);
+    return 0;
+}
+
+int check_grouped_sets(const mvdb_index* idx, int nq, const mvdb_rowset* const* sets) {
+    if (!sets) return fail(MVDB_ERR_ARG, "sets is NULL");
+    for (int i = 0; i < nq; ++i)
+        if (sets[i]) MVDB_TRY(rowset_check(idx, sets[i]));
+    return 0;
+}
+
+// queries on the device (padded to ld), results to device buffers; every set has been checked
+int grouped_search_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int normalize_q,
+                        const mvdb_rowset* const* sets, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    KnobScope knobs(&idx->kn);
+    hipStream_t s = ws->stream;
+    bool any_list = false;
+    for (int i = 0; i < nq; ++i) any_list = any_list || (sets[i] && sets[i]->rows);
+    const bool fused = k <= kMaxFusedK;
+    if (fused && any_list) {
+        thread_local std::vector<GroupedQuery> queries;
+        thread_local std::vector<GroupedItem> items;
+        plan_grouped(idx, nq, sets, queries, items);
+        const GroupedQuery* q_tab = nullptr;
+        const GroupedItem* it_tab = nullptr;
+        MVDB_TRY(stage_grouped_table(ws, queries, items, &q_tab, &it_tab));
+        const int nitems = (int)items.size();
+        MVDB_TRY(ws->cand.reserve((size_t)std::max(nitems, 1) * k));
+        if (nitems > 0) {
+            GroupedScanArgs a;
+            a.X = idx->X;
+            a.ld = idx->ld;
+            a.d4 = idx->d4;
+            a.q = q;
+            a.normalize_q = normalize_q;
+            a.k = k;
+            a.items = it_tab;
+            a.queries = q_tab;
+            a.cand = ws->cand.p;
+            MVDB_TRY(launch_grouped(idx->metric, a, nitems, s));
+        }
+        MergeSegArgs mg;
+        mg.keys = ws->cand.p;
+        mg.queries = q_tab;
+        mg.k = k;
+        mg.metric = idx->metric;
+        mg.label_offset = label_offset;
+        mg.D = D_dev;
+        mg.I = I_dev;
+        int slot = prof_begin("grouped_merge", s);
+        hipLaunchKernelGGL(merge_keys_seg_kernel, dim3(nq), dim3(kMergeThreads), 0, s, mg);
+        prof_end(slot, s);
+        MVDB_HIP(hipGetLastError());
+    }
+    // bitmap and NULL sets (and every query when k is beyond the fused select): the exact single-query routes, row by row
+    for (int i = 0; i < nq; ++i) {
+        const mvdb_rowset* rs = sets[i];
+        if (fused && rs && rs->rows) continue;
+        const float* qi = q + (int64_t)i * idx->ld;
+        float* Di = D_dev + (int64_t)i * k;
+        int64_t* Ii = I_dev + (int64_t)i * k;
+        if (rs) MVDB_TRY(rowset_search_core(idx, ws, qi, 1, k, normalize_q, rs, label_offset, Di, Ii));
+        else MVDB_TRY(search_core(idx, ws, qi, 1, k, normalize_q, nullptr, 0, label_offset, Di, Ii, /*allow_split=*/false));
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_search_grouped(const mvdb_index* idx, const float* q_host, int nq, int k, int normalize_q,
+                              const mvdb_rowset* const* sets, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_search_args(idx, q_host, nq, k, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_grouped_sets(idx, nq, sets));
+    DeviceGuard dg(idx->device);
+    Workspace* ws = idx->acquire();
+    if (!ws) return MVDB_ERR_HIP;
+    int rc = 0;
+    do {
+        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
+        const size_t total = (size_t)nq * k;
+        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;
+        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
+        if ((rc = grouped_search_core(idx, ws, ws->q.p, nq, k, normalize_q, sets, 0, D_dev, ws->out.p))) break;
+        rc = fetch_results(ws, total, D_host, I_host);
+    } while (0);
+    idx->release(ws);
+    return rc;
+}
+
+int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q,
+                                     const mvdb_rowset* const* sets, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                                     void* stream) {
+    MVDB_TRY(check_search_args(idx, q_dev, nq, k, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_grouped_sets(idx, nq, sets));
+    DeviceGuard dg(idx->device);
+    Workspace* ws = idx->for_stream((hipStream_t)stream);
+    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
+    std::lock_guard<std::mutex> use(ws->use_mu);
+    note_capture(ws);
+    RetireScope keep(ws->captured ? &ws->retired : nullptr);
+    const float* q = q_dev;
+    if (idx->ld != idx->d) {
+        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
+                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
+        MVDB_HIP(hipGetLastError());
+        q = ws->q.p;
+    }
+    return grouped_search_core(idx, ws, q, nq, k, normalize_q, sets, label_offset, D_dev, I_dev);
 }
 
 int mvdb_merge_topk_device(int metric, int nlists, int nq, int k, const float* D_dev,
