@@ -282,6 +282,35 @@ int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, 
                                      const mvdb_rowset* const* sets, int64_t label_offset, float* D_dev, int64_t* I_dev,
                                      void* stream);
 
+/* RANGE SEARCH: every selected row whose score reaches a threshold, instead of the k best (faiss.IndexFlat.range_search
+ * beside search).  rs == NULL: every row; else the resident row set (list or bitmap).  cap: the most results per query the
+ * caller has room for, >= 0.
+ *   counts[i]  = number of selected rows whose score reaches the threshold (inner product: score >= threshold; L2: squared
+ *                distance <= threshold), WHATEVER cap is.  cap == 0 is a pure count; D / I may then be NULL.
+ *   counts[i] <= cap: row i of (D [nq,cap], I [nq,cap]) holds those rows best first, exact ties to the lower row (for an
+ *                unsorted row list: to the lower list position, as mvdb_index_search_rowset); labels are row numbers; the
+ *                tail is -1 / -FLT_MAX (inner product) or +FLT_MAX (L2) as everywhere.
+ *   counts[i] >  cap: row i holds only missing markers — the order in which the device appends results is not defined, so a
+ *                partial answer would not be reproducible; call again with cap >= counts[i].
+ * Bit identity: every returned score is bit for bit the score mvdb_index_search / mvdb_index_search_rowset returns for that
+ * (query, row) with nq = 1 on the default routing; row i equals the leading counts[i] entries of that call with
+ * k = counts[i], and entry counts[i] + 1 of a longer one, if there is one, is below the threshold.  Several queries of a call
+ * are answered one corpus pass each.
+ * A NaN threshold is MVDB_ERR_ARG; -inf (inner product) selects every row whose score is not NaN; rows with NaN scores never
+ * match.  A stale or foreign row set: MVDB_ERR_ARG before anything is enqueued, nothing written.  Empty index: counts 0.
+ * The host entry point reads the counts back before it sorts, so its sort and its copy are sized by the results, not by cap.
+ * Workspace: nq x (cap rounded up to a power of two) 8-byte keys — not nq x n scores.  No reference counterpart (the
+ * reference's autocut heuristic serves the same wish on a fixed k). */
+int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, float threshold, int normalize_q,
+                            const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host);
+/* Device-resident variant under the contract of mvdb_index_search_device: queries, counts and outputs in device memory,
+ * enqueued on `stream`, no synchronisation, one search at a time per (index, stream); labels are row numbers +
+ * label_offset.  Its sort is sized by cap (each block looks its query's count up on the device and sorts no more than that).
+ * Capturable into a hipGraph after one eager call of the same shape (same nq, cap, set) has sized the workspace. */
+int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, int nq, float threshold, int normalize_q,
+                                   const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev,
+                                   float* D_dev, int64_t* I_dev, void* stream);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be

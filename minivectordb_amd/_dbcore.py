@@ -613,6 +613,98 @@ class FilterAndRerankMixin:
                     cache[key] = (gen, index, len(wanted), rowset)
         return rowset
 
+    # ---- range search: everything at or above a score, instead of the k best --------------------------------
+    def find_all_similar(self, embedding, min_score, metadata_filter=None, exclude_filter=None, or_filters=None, limit=None):
+        """EVERY stored embedding whose score against `embedding` is at least `min_score` (cosine: rows and query are
+        normalised), best first, under the filters of ``find_most_similar`` — near-duplicate checks, retrieval with a relevance
+        floor instead of a fixed k, neighbourhoods of unknown size.  No reference counterpart (its ``autocut`` guesses such a
+        floor from a fixed k).  Returns ``(ids, distances, metadatas)`` packaged as ``find_most_similar`` does without
+        autocut; ids, scores and order are those of ``find_most_similar`` with k = the number of matches.  `limit`: only the
+        best `limit` of them."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        return self.find_all_similar_batch(query, min_score, metadata_filter, exclude_filter, or_filters, limit)[0]
+
+    def find_all_similar_batch(self, embeddings, min_score, metadata_filter=None, exclude_filter=None, or_filters=None,
+                               limit=None):
+        """Several queries under ONE filter: element i is what ``find_all_similar(embeddings[i], min_score, ...)`` returns.
+        Each query is its own pass over the selected rows (a range result is bit for bit the single query's)."""
+        queries = self._range_queries(embeddings)
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        if queries.shape[0] == 0 or self._mat is None:
+            return [([], [], []) for _ in range(queries.shape[0])]
+        uids = self._ids.uids
+        out = []
+        for found in self._range_rows_many(queries, min_score, metadata_filter, exclude_filter, or_filters):
+            hits = []
+            for row, score in (found if limit is None else found[:limit]):
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[row], score, self.metadata[row]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, False))
+        return out
+
+    def count_similar(self, embedding, min_score, metadata_filter=None, exclude_filter=None, or_filters=None):
+        """``len(find_all_similar(...)[0])`` without fetching a single result: one pass on the device, one integer back."""
+        query = self._range_queries(np.array([np.array(embedding, dtype=np.float32)]))
+        if self._mat is None:
+            return 0
+        return int(self._range_rows_many(query, min_score, metadata_filter, exclude_filter, or_filters, count_only=True)[0])
+
+    def _range_queries(self, embeddings):
+        queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
+        if queries.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like, one query per row")
+        if self._mat is not None and queries.shape[0] and queries.shape[1] != self._mat.d:
+            # before any filter is evaluated (the retry loop would evaluate it three times over before the index's own ValueError)
+            raise ValueError(f"query dimension {queries.shape[1]} != index dimension {self._mat.d}")
+        return queries
+
+    def _range_rows_many(self, query, min_score, metadata_filter, exclude_filter, or_filters, count_only=False):
+        """Device half of find_all_similar: per query [(row, score)] best first — or, count_only, the number of matches.  Lazy
+        device sync, filter evaluation, the resident row-set cache and the retry after a concurrent delete are
+        `_nearest_rows_many`'s."""
+        nq = query.shape[0]
+        min_score = float(min_score)
+        if min_score != min_score:
+            raise ValueError("min_score is NaN")
+        filtered = bool(metadata_filter or exclude_filter or or_filters)
+        key = None
+        if filtered:
+            try:
+                key = repr((metadata_filter, exclude_filter, or_filters))
+            except Exception:
+                key = None
+        for attempt in range(3):
+            with self.lock:
+                if self._embeddings_changed:
+                    self._build_index()
+                index, n_rows = self.index, self._mat.n
+                gen = self.__dict__.get("_write_gen", 0)
+                hit = self.__dict__.get("_rowsets", {}).get(key) if key is not None else None
+                if hit is not None and hit[0] == gen and hit[1] is index:
+                    count, rowset, wanted = hit[2], hit[3], None
+                else:
+                    wanted = self._get_filtered_indices(metadata_filter, exclude_filter, or_filters)
+                    count, rowset = len(wanted), None
+            if not count or index is None:
+                return [0] * nq if count_only else [[] for _ in range(nq)]
+            if not hasattr(index, "range_search"):
+                raise NotImplementedError(f"{type(index).__name__} has no range search")
+            try:
+                if count != n_rows and rowset is None:
+                    rowset = self._resident_rowset(index, wanted, key, gen)
+                if count_only:
+                    return [int(c) for c in index.range_count(query, min_score, rowset=rowset, normalize_q=True)]
+                lims, scores, rows = index.range_search(query, min_score, rowset=rowset, normalize_q=True)
+                break
+            except ValueError:
+                # another thread deleted rows between the filter and the search: evaluate the filter again on the current rows
+                if attempt == 2:
+                    raise
+        return [[(int(r), s) for r, s in zip(rows[lims[i]:lims[i + 1]], scores[lims[i]:lims[i + 1]])] for i in range(nq)]
+
     # ---- a batch in which every query brings its own filter -------------------------------------------------
     _EACH_FILTER_KEYS = ("metadata_filter", "exclude_filter", "or_filters")
 

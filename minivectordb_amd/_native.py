@@ -93,6 +93,10 @@ PROTOTYPES = {
     "mvdb_index_search_grouped": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_index_search_grouped_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                         ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_range_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_vp, ctypes.c_int64,
+                                               c_vp, c_vp, c_vp]),
+    "mvdb_index_range_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_vp,
+                                                      ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -424,6 +428,77 @@ class FlatIndex:
             self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(bool(normalize_q)), ctypes.c_void_p(rows_ptr), int(m),
             int(bool(map_labels)), int(label_offset), ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
             ctypes.c_void_p(stream)))
+
+    # ---- range search: every selected row at or above a threshold (include/mvdb.h "RANGE SEARCH") -------------------
+    RANGE_DEFAULT_CAP = 1024
+
+    def _range_queries(self, q):
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        return q
+
+    def range_search_raw(self, q, threshold, cap, rowset=None, normalize_q=False, out=None):
+        """One call of mvdb_index_range_search: (counts int64[nq], D float32[nq, cap], I int64[nq, cap]).  A query whose count
+        exceeds `cap` has a row of missing markers (-1); its count is still the true count.  out=(counts, D, I): caller-owned
+        arrays (D / I may be None with cap == 0)."""
+        q = self._range_queries(q)
+        nq, cap = q.shape[0], int(cap)
+        if out is None:
+            counts = np.empty(nq, dtype=np.int64)
+            D = np.empty((nq, cap), dtype=np.float32) if cap > 0 else None
+            I = np.empty((nq, cap), dtype=np.int64) if cap > 0 else None
+        else:
+            counts, D, I = out
+        check(lib().mvdb_index_range_search(
+            self._h, _ptr(q), nq, float(threshold), int(bool(normalize_q)), rowset._h if rowset is not None else None, cap,
+            _ptr(counts), _ptr(D) if D is not None else None, _ptr(I) if I is not None else None))
+        return counts, D, I
+
+    def range_count(self, q, threshold, rowset=None, normalize_q=False):
+        """int64[nq]: how many selected rows reach the threshold (inner product: score >= threshold; L2: squared distance
+        <= threshold)."""
+        return self.range_search_raw(q, threshold, 0, rowset, normalize_q)[0]
+
+    def range_search(self, q, threshold, rowset=None, normalize_q=False, cap=None):
+        """Every selected row that reaches the threshold, in faiss's range_search layout: (lims int64[nq + 1], D, I) with the
+        results of query i at [lims[i], lims[i + 1]), best first, ties to the lower row; labels are ROW NUMBERS.  Calls with
+        a capacity (`cap`, default 1024 per query) and once more, for the queries that overflowed only, with the largest
+        count seen."""
+        q = self._range_queries(q)
+        nq = q.shape[0]
+        cap = self.RANGE_DEFAULT_CAP if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        for _ in range(3):
+            counts, D, I = self.range_search_raw(q, threshold, cap, rowset, normalize_q)
+            lims = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum(counts, out=lims[1:])
+            Dout = np.empty(int(lims[-1]), dtype=np.float32)
+            Iout = np.empty(int(lims[-1]), dtype=np.int64)
+            over = np.flatnonzero(counts > cap)
+            for i in np.flatnonzero(counts <= cap):
+                Dout[lims[i]:lims[i + 1]] = D[i, :counts[i]]
+                Iout[lims[i]:lims[i + 1]] = I[i, :counts[i]]
+            if over.size:
+                c2, D2, I2 = self.range_search_raw(q[over], threshold, int(counts[over].max()), rowset, normalize_q)
+                if not np.array_equal(c2, counts[over]):
+                    continue   # rows were added or removed between the two calls: both again, on the index as it is now
+                for j, i in enumerate(over):
+                    Dout[lims[i]:lims[i + 1]] = D2[j, :c2[j]]
+                    Iout[lims[i]:lims[i + 1]] = I2[j, :c2[j]]
+            return lims, Dout, Iout
+        # the same error class as a row set outdated by a removal: callers that retry after a racing write retry this too
+        raise ValueError("the index kept changing between the two calls of a range search")
+
+    def range_search_device(self, q_ptr, nq, threshold, cap, counts_ptr, D_ptr, I_ptr, rowset=None, stream=0,
+                            normalize_q=False, label_offset=0):
+        """Device-pointer variant of range_search_raw (counts int64[nq], D float32[nq, cap], I int64[nq, cap] on the device;
+        labels: row numbers + label_offset); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_range_search_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), float(threshold), int(bool(normalize_q)),
+            rowset._h if rowset is not None else None, int(cap), int(label_offset), ctypes.c_void_p(counts_ptr),
+            ctypes.c_void_p(D_ptr) if D_ptr else None, ctypes.c_void_p(I_ptr) if I_ptr else None, ctypes.c_void_p(stream)))
 
 
 class RowSet:

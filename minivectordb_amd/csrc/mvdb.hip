@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "scan_kernels.hpp"
 #include "grouped_scan.hpp"
+#include "range_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
 #include "half_scan.hpp"
@@ -211,6 +212,8 @@ struct Workspace {
     std::vector<void*> retired;    // ... outgrown ones wait here until the workspace goes (common.hpp, RetireScope)
     // grouped search (mvdb_index_search_grouped): the item table on the device, its pinned staging copy, and the event recorded
     // behind the upload — the staging copy is rewritten only once the upload that reads it has run
+    DevBuf<uint64_t> rkeys;             // range search: [nq, segment] appended keys (range_scan.hpp)
+    DevBuf<unsigned long long> rcounts;  // ... and the host entry point's per-query counters
     DevBuf<char> gtab;
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
         PinnedBuf buf;
@@ -250,6 +253,8 @@ struct Workspace {
         relabel.release();
         nfail.release();
         pin.release();
+        rkeys.release();
+        rcounts.release();
         gtab.release();
         for (GroupedStage* g : gstage) {
             g->buf.release();
@@ -2709,6 +2714,263 @@ int mvdb_index_search_rowset_device(const mvdb_index* idx, const float* q_dev, i
         q = ws->q.p;
     }
     return rowset_search_core(idx, ws, q, nq, k, normalize_q, rs, label_offset, D_dev, I_dev);
+}
+
+}  // extern "C"
+
+// ---- range search: every selected row at or above a threshold (range_scan.hpp) ------------------------------------------
+namespace {
+
+template <int G, int C, int U, int METRIC, int SEL, bool MASKED>
+int launch_range_kern(const RangeScanArgs& a, int nq, int device, hipStream_t stream) {
+    void (*kern)(RangeScanArgs) = range_scan_kernel<G, C, U, METRIC, SEL, MASKED>;
+    // the grid of the single-query scan (launch_scan_kern): 2 resident blocks per CU, 3 for the one- and three-chunk shapes
+    const int occ_hw = cached_occupancy((const void*)kern, kScanThreads, 0, 4);
+    int occ = std::min(occ_hw, (C == 1 || C == 3) ? 3 : 2);
+    if (kn().scan_blocks_per_cu > 0) occ = std::min(occ_hw, kn().scan_blocks_per_cu);
+    constexpr int RB = (kWave / G) * U;
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * occ));
+    prof_symbol("ip_scan_range", "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
+    int slot = prof_begin("ip_scan_range", stream);
+    hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int G, int C, int U, int METRIC>
+int launch_range_sel(const RangeScanArgs& a, int nq, int device, hipStream_t s) {
+    constexpr bool kAlwaysFull = G == 32 && C > 1;  // (as launch_scan_inst: chosen for rows that fill the lanes exactly)
+    if constexpr (kAlwaysFull) {
+        if (a.mask) return launch_range_kern<G, C, U, METRIC, 2, false>(a, nq, device, s);
+        if (a.rows) return launch_range_kern<G, C, U, METRIC, 1, false>(a, nq, device, s);
+        return launch_range_kern<G, C, U, METRIC, 0, false>(a, nq, device, s);
+    } else {
+        const bool masked = a.d4 != G * C;
+        if (a.mask)
+            return masked ? launch_range_kern<G, C, U, METRIC, 2, true>(a, nq, device, s)
+                          : launch_range_kern<G, C, U, METRIC, 2, false>(a, nq, device, s);
+        // (row lists of the two- and three-chunk shapes are launch_range's own U = 4 forms: no U = 2 gather is instantiated)
+        if constexpr (!(G == 64 && (C == 2 || C == 3))) {
+            if (a.rows)
+                return masked ? launch_range_kern<G, C, U, METRIC, 1, true>(a, nq, device, s)
+                              : launch_range_kern<G, C, U, METRIC, 1, false>(a, nq, device, s);
+        }
+        return masked ? launch_range_kern<G, C, U, METRIC, 0, true>(a, nq, device, s)
+                      : launch_range_kern<G, C, U, METRIC, 0, false>(a, nq, device, s);
+    }
+}
+
+// the shapes and rows in flight of launch_scan: a score depends on (G, C, MASKED, METRIC) only, U follows the measured best
+int launch_range(int metric, const RangeScanArgs& a, int nq, int device, hipStream_t s) {
+    const Shape sh = choose_shape(a.d4);
+    const bool masked = a.d4 != sh.G * sh.C;
+    if (a.rows && sh.G == 64 && (sh.C == 2 || sh.C == 3)) {  // gathered two- and three-chunk rows: four rows in flight
+#define MVDB_RANGE_ROWS(C_, M_)                                                        \
+    (masked ? launch_range_kern<64, C_, 4, M_, 1, true>(a, nq, device, s) \
+            : launch_range_kern<64, C_, 4, M_, 1, false>(a, nq, device, s))
+        if (sh.C == 2) return metric == MVDB_METRIC_IP ? MVDB_RANGE_ROWS(2, 0) : MVDB_RANGE_ROWS(2, 1);
+        return metric == MVDB_METRIC_IP ? MVDB_RANGE_ROWS(3, 0) : MVDB_RANGE_ROWS(3, 1);
+#undef MVDB_RANGE_ROWS
+    }
+#define MVDB_RANGE_CASE(G_, C_, U_)                                                         \
+    if (sh.G == G_ && sh.C == C_)                                                           \
+        return metric == MVDB_METRIC_IP ? launch_range_sel<G_, C_, U_, 0>(a, nq, device, s) \
+                                        : launch_range_sel<G_, C_, U_, 1>(a, nq, device, s);
+    MVDB_RANGE_CASE(16, 1, 4)
+    MVDB_RANGE_CASE(32, 1, 4)
+    MVDB_RANGE_CASE(32, 3, 4)
+    MVDB_RANGE_CASE(64, 1, 4)
+    MVDB_RANGE_CASE(64, 2, 2)
+    MVDB_RANGE_CASE(64, 3, 2)
+    MVDB_RANGE_CASE(64, 4, 1)
+    MVDB_RANGE_CASE(64, 5, 1)
+    MVDB_RANGE_CASE(64, 6, 1)
+    MVDB_RANGE_CASE(64, 7, 1)
+    MVDB_RANGE_CASE(64, 8, 1)
+    MVDB_RANGE_CASE(64, 16, 1)
+#undef MVDB_RANGE_CASE
+    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+}
+
+constexpr int kRangeTile = 1024;  // queries of one range launch (a call of more is answered that many at a time)
+
+int check_range_args(const mvdb_index* idx, const void* q, int nq, float threshold, int64_t cap, const void* counts, const void* D,
+                     const void* I) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (!q || !counts) return fail(MVDB_ERR_ARG, "NULL buffer passed to range search");
+    if (nq <= 0) return fail(MVDB_ERR_ARG, "nq must be positive (got %d)", nq);
+    if (threshold != threshold) return fail(MVDB_ERR_ARG, "the threshold is NaN");
+    if (cap < 0) return fail(MVDB_ERR_ARG, "cap must not be negative (got %lld)", (long long)cap);
+    if (cap > 0 && (!D || !I)) return fail(MVDB_ERR_ARG, "D / I may be NULL only with cap == 0");
+    return 0;
+}
+
+// zero the counters and run the thresholded scan: counts[i] = passing rows of query i, keys[i * seg ...] the first `cap` of
+// them in no defined order.  *rows_out: the row list the keys' positions refer to (NULL: they are row numbers).
+int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int nq, float threshold, int normalize_q,
+                     const mvdb_rowset* rs, int64_t cap, int64_t seg, unsigned long long* counts, const int64_t** rows_out) {
+    KnobScope knobs(&idx->kn);
+    hipStream_t s = ws->stream;
+    MVDB_TRY(ws->rkeys.reserve((size_t)nq * (size_t)seg));
+    MVDB_HIP(hipMemsetAsync(counts, 0, (size_t)nq * sizeof(unsigned long long), s));
+    RangeScanArgs a;
+    a.X = idx->X;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.q = q;
+    a.normalize_q = normalize_q;
+    a.thr = idx->metric == MVDB_METRIC_IP ? threshold : -threshold;  // the key's score of an L2 row is -distance
+    a.rows = nullptr;
+    a.mask = nullptr;
+    a.n = idx->n;
+    if (rs) {
+        if (rs->mask) {
+            a.mask = rs->mask;
+            a.n = rs->count == 0 ? 0 : std::min<int64_t>(rs->n_at_create, idx->n);  // rows appended since are not part of the set
+        } else {
+            a.rows = rs->rows;
+            a.n = rs->count;
+        }
+    }
+    a.keys = ws->rkeys.p;
+    a.seg = seg;
+    a.cap = cap;
+    a.counts = counts;
+    *rows_out = a.rows;
+    if (a.n == 0) return 0;
+    return launch_range(idx->metric, a, nq, idx->device, s);
+}
+
+// sort the leading keys of every segment (descending) — P: a power of two >= every count that is to be sorted
+int range_sort_phase(Workspace* ws, int nq, int64_t seg, int64_t cap, int64_t P, const unsigned long long* counts) {
+    hipStream_t s = ws->stream;
+    const int L = (int)std::min<int64_t>(P, kRangeSortTile);
+    const dim3 tiles((unsigned)(P / L), (unsigned)nq);
+    hipLaunchKernelGGL(range_sort_lds_kernel, tiles, dim3(kRangeSortThreads), 0, s, ws->rkeys.p, seg, counts, cap, L, (int64_t)2, (int64_t)L);
+    for (int64_t size = 2 * (int64_t)L; size <= P; size <<= 1) {
+        for (int64_t stride = size >> 1; stride >= L; stride >>= 1)
+            hipLaunchKernelGGL(range_sort_step_kernel, dim3((unsigned)((P / 2 + 255) / 256), (unsigned)nq), dim3(256), 0, s, ws->rkeys.p, seg,
+                               counts, cap, size, stride);
+        hipLaunchKernelGGL(range_sort_lds_kernel, tiles, dim3(kRangeSortThreads), 0, s, ws->rkeys.p, seg, counts, cap, L, size, size);
+    }
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+int range_emit_phase(const mvdb_index* idx, Workspace* ws, int nq, int64_t seg, int64_t cap, int64_t width,
+                     const unsigned long long* counts, const int64_t* rows, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)nq), dim3(256), 0, ws->stream, ws->rkeys.p, seg,
+                       counts, cap, width, idx->metric, rows, label_offset, D_dev, I_dev);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// host entry point, one tile of queries already staged in ws->q
+int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshold, int normalize_q, const mvdb_rowset* rs,
+                    int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+    const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
+    MVDB_TRY(ws->rcounts.reserve((size_t)nq));
+    const int64_t* rows = nullptr;
+    MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, normalize_q, rs, cap, seg, ws->rcounts.p, &rows));
+    // the counts come back first: the sort and the copy are sized by what is there, not by the capacity
+    MVDB_TRY(ws->pin_out.reserve((size_t)nq * sizeof(unsigned long long)));
+    hipError_t e = hipMemcpyAsync(ws->pin_out.p, ws->rcounts.p, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) return fail(MVDB_ERR_HIP, "range search failed: %s", hipGetErrorString(e));
+    int64_t width = 0;
+    for (int i = 0; i < nq; ++i) {
+        counts_host[i] = (int64_t)((const unsigned long long*)ws->pin_out.p)[i];
+        if (counts_host[i] <= cap) width = std::max(width, counts_host[i]);
+    }
+    if (cap == 0) return 0;
+    const size_t total = (size_t)nq * (size_t)width;
+    if (width > 0) {
+        MVDB_TRY(ws->out.reserve(total + (total + 1) / 2));  // [I: total int64 | D: total fp32]
+        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
+        MVDB_TRY(range_sort_phase(ws, nq, seg, cap, pow2ceil(std::max<int64_t>(width, 2)), ws->rcounts.p));
+        MVDB_TRY(range_emit_phase(idx, ws, nq, seg, cap, width, ws->rcounts.p, rows, 0, D_dev, ws->out.p));
+        const size_t bytes = total * (sizeof(int64_t) + sizeof(float));
+        MVDB_TRY(ws->pin_out.reserve(bytes));
+        e = hipMemcpyAsync(ws->pin_out.p, ws->out.p, bytes, hipMemcpyDeviceToHost, ws->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+        if (e != hipSuccess) return fail(MVDB_ERR_HIP, "range search failed: %s", hipGetErrorString(e));
+    }
+    const int64_t* I_st = (const int64_t*)ws->pin_out.p;
+    const float* D_st = (const float*)((const char*)ws->pin_out.p + total * sizeof(int64_t));
+    const float missing = idx->metric == MVDB_METRIC_IP ? -3.402823466e+38f : 3.402823466e+38f;
+    for (int i = 0; i < nq; ++i) {
+        const int64_t have = counts_host[i] <= cap ? counts_host[i] : 0;  // an overflowed query: missing markers only
+        float* Dr = D_host + (size_t)i * cap;
+        int64_t* Ir = I_host + (size_t)i * cap;
+        if (have) {
+            memcpy(Ir, I_st + (size_t)i * width, (size_t)have * sizeof(int64_t));
+            memcpy(Dr, D_st + (size_t)i * width, (size_t)have * sizeof(float));
+        }
+        std::fill(Dr + have, Dr + cap, missing);
+        std::fill(Ir + have, Ir + cap, (int64_t)-1);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, float threshold, int normalize_q,
+                            const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_range_args(idx, q_host, nq, threshold, cap, counts_host, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    Workspace* ws = idx->acquire();
+    if (!ws) return MVDB_ERR_HIP;
+    int rc = 0;
+    for (int t0 = 0; t0 < nq && !rc; t0 += kRangeTile) {
+        const int take = std::min(kRangeTile, nq - t0);
+        if ((rc = stage_queries(idx, ws, q_host + (size_t)t0 * idx->d, take))) break;
+        rc = range_host_tile(idx, ws, take, threshold, normalize_q, rs, cap, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
+                             cap ? I_host + (size_t)t0 * cap : nullptr);
+    }
+    idx->release(ws);
+    return rc;
+}
+
+int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, int nq, float threshold, int normalize_q,
+                                   const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev, float* D_dev,
+                                   int64_t* I_dev, void* stream) {
+    MVDB_TRY(check_range_args(idx, q_dev, nq, threshold, cap, counts_dev, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    Workspace* ws = idx->for_stream((hipStream_t)stream);
+    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
+    std::lock_guard<std::mutex> use(ws->use_mu);
+    note_capture(ws);
+    RetireScope keep(ws->captured ? &ws->retired : nullptr);
+    const float* q = q_dev;
+    if (idx->ld != idx->d) {  // pad the dense queries to the row stride
+        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)), dim3(256), 0, ws->stream, ws->q.p, q_dev,
+                           (int64_t)nq, idx->d, idx->ld);
+        MVDB_HIP(hipGetLastError());
+        q = ws->q.p;
+    }
+    // Nothing below reads from the device: the sort is sized by the capacity (each block looks its query's count up and
+    // sorts no more than that), so the call may be captured once an eager call of the same shape has sized the workspace.
+    const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
+    for (int t0 = 0; t0 < nq; t0 += kRangeTile) {
+        const int take = std::min(kRangeTile, nq - t0);
+        unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + t0;
+        const int64_t* rows = nullptr;
+        MVDB_TRY(range_scan_phase(idx, ws, q + (size_t)t0 * idx->ld, take, threshold, normalize_q, rs, cap, seg, counts, &rows));
+        if (cap == 0) continue;
+        MVDB_TRY(range_sort_phase(ws, take, seg, cap, seg, counts));
+        MVDB_TRY(range_emit_phase(idx, ws, take, seg, cap, cap, counts, rows, label_offset, D_dev + (size_t)t0 * cap, I_dev + (size_t)t0 * cap));
+    }
+    return 0;
 }
 
 }  // extern "C"

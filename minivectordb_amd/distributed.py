@@ -540,3 +540,16 @@ class DistributedShardedVectorDatabase:
         Dg, Ig = self._searcher(search_k).search_device(q_dev, rows=rows, normalize_q=True)
         Dh, Ih = Dg.cpu().numpy(), Ig.cpu().numpy()
         return [self._package_row(Ih[i], Dh[i], autocut) for i in range(nq)]
+
+    # ---- range search: not across ranks -------------------------------------------------------------------------
+    _NO_RANGE = ("DistributedShardedVectorDatabase has no range search: the ranks would have to exchange results of "
+                 "variable length, which the packed top-k all-gather does not carry (use ShardedVectorDatabase on one device)")
+
+    def find_all_similar(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
+
+    def find_all_similar_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
+
+    def count_similar(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)

@@ -129,3 +129,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
                 distances = [distances[i] for i in range(len(distances)) if i not in remove]
                 metadatas = [metadatas[i] for i in range(len(metadatas)) if i not in remove]
         return ids, distances, metadatas
+
+    # ---- range search: not on the int8 cosine index --------------------------------------------------------------
+    _NO_RANGE = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: a range search over int8 cosine "
+                 "distances is not implemented (use ShardedVectorDatabase)")
+
+    def find_all_similar(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
+
+    def find_all_similar_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
+
+    def count_similar(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
