@@ -71,6 +71,13 @@ int mvdb_index_reload_env(mvdb_index* idx);
  *       re-scored in fp32, every result certified, uncertified queries re-run exactly — at about half the bytes per query
  *       (10M x 512: 2.84 -> 1.58 ms), for 2 more bytes per stored element.  Off by default: the single-query scan is the exact
  *       fp32 kernel the headline roofline is defined on.
+ *   "code8_single_query" (0 | 1, default 1): ONE unfiltered inner-product query over >= 500,000 unpadded rows of width
+ *       384 / 512 / 1024 is answered in two steps: a pass over an int8 code of the rows (1 byte per element, kept beside the
+ *       matrix: mvdb_index_code8_rows) keeps every row whose proven upper bound reaches a proven floor of the k-th best score,
+ *       then the exact fp32 kernel scores the kept rows.  D and I are bit for bit those of the exact scan (option 0).
+ *       "shadow_single_query" = 1 takes precedence.
+ *   "code8_capacity" (1 .. 65536, default 32768): most candidate rows a call of that route may keep; a call that keeps more (or fewer
+ *       than k) is answered by the full exact scan, enabled on the device.  Diagnostic: a small value forces that fallback.
  *   "half_shadow" (0 | 1, default 1): 0 = batches nominate from the fp32 rows (no second copy of the corpus).
  *   "compact_bytes" (> 0, default 512 MiB): staging buffer of mvdb_index_remove_rows. */
 int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value);
@@ -101,6 +108,26 @@ int mvdb_index_device(const mvdb_index* idx);
  * the exact fp32 passes (32 queries per corpus pass; until round 6 a second nomination generation read the fp32 rows).
  * No reference counterpart. */
 int64_t mvdb_index_shadow_rows(const mvdb_index* idx);
+
+/* Rows held in the index' int8 CODE (0: none): d int8 values, an fp32 scale and an fp32 bound of the coding residual per row
+ * (+25 % of the index's device memory at d = 512), the operand of the single-query prefilter (option "code8_single_query").
+ * Built by the first eligible single query (one blocking conversion pass and the allocations inside that call; never while the
+ * stream is being captured: such a call takes the exact scan), extended by add, dropped by remove_rows / reset / a
+ * re-allocation — the exact scan answers the next two eligible queries after the LATEST such change before the code is
+ * rebuilt (every delete restarts the count), so a workload that alternates deletes and queries never pays for builds.  An
+ * allocation failure leaves the exact scan in charge for the life of the index.  The build also fills the last row of the
+ * readable slack behind the matrix with NaN (the padding entry of the candidate list); no stored row is touched.
+ * No reference counterpart. */
+int64_t mvdb_index_code8_rows(const mvdb_index* idx);
+
+/* Diagnostics of the prefilter route, read from host-mapped words without synchronising (they lag by the calls in flight):
+ * calls that fell back to the full exact scan, the candidate rows of the latest call, calls served.  Any pointer may be NULL. */
+int mvdb_index_code8_counters(const mvdb_index* idx, long long* fallbacks, long long* last_candidates, long long* calls);
+
+/* The prefilter's margin: for a stored row x with |x| <= row_norm_bound whose code has residual bound r,
+ * and a query image of norm <= qnorm rounded with step qstep, the fp32 score the exact kernel computes lies within
+ * alpha * r + beta of the coded score.  Pure host arithmetic (no device needed). */
+int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta);
 
 /* Reserve device capacity for at least n rows in total (amortises repeated add). */
 int mvdb_index_reserve(mvdb_index* idx, int64_t n);

@@ -64,6 +64,9 @@ PROTOTYPES = {
     "mvdb_index_reset": (ctypes.c_int, [c_vp]),
     "mvdb_index_ntotal": (ctypes.c_int64, [c_vp]),
     "mvdb_index_shadow_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_index_code8_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_index_code8_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_code8_margin": (ctypes.c_int, [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp]),
     "mvdb_index_dim": (ctypes.c_int, [c_vp]),
     "mvdb_index_device": (ctypes.c_int, [c_vp]),
     "mvdb_index_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
@@ -260,6 +263,17 @@ class FlatIndex:
     def shadow_rows(self):
         """Rows in the fp16 shadow the batch passes stream (0: none yet / not applicable)."""
         return int(lib().mvdb_index_shadow_rows(self._h))
+
+    @property
+    def code8_rows(self):
+        """Rows in the int8 code the single-query prefilter streams (0: none yet / not applicable)."""
+        return int(lib().mvdb_index_code8_rows(self._h))
+
+    def code8_counters(self):
+        """(fallbacks, candidates of the latest call, calls) of the single-query prefilter route; lags by the calls in flight."""
+        v = [ctypes.c_longlong(0) for _ in range(3)]
+        check(lib().mvdb_index_code8_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def reset(self):
         check(lib().mvdb_index_reset(self._h))
@@ -747,3 +761,10 @@ def prof_read(name):
     ms = ctypes.c_double(0.0)
     check(lib().mvdb_prof_read(name.encode(), ctypes.byref(n), ctypes.byref(ms)))
     return n.value, ms.value
+
+
+def code8_margin(d, qnorm, qstep, row_norm_bound):
+    """(alpha, beta) of the int8 prefilter's margin alpha * r + beta (include/mvdb.h: mvdb_code8_margin)."""
+    a, b = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().mvdb_code8_margin(int(d), float(qnorm), float(qstep), float(row_norm_bound), ctypes.byref(a), ctypes.byref(b)))
+    return float(a.value), float(b.value)

@@ -83,6 +83,8 @@ struct Knobs {
          disable_l2_cert = false,    // MVDB_DISABLE_* (L2_CERT: L2 batches back on the exact fp32 kernels)
          disable_half_shadow = false;  // MVDB_DISABLE_HALF_SHADOW (index option half_shadow = 0): no fp16 shadow, batches on the exact fp32 passes
     bool shadow_single_query = false;  // MVDB_SHADOW_SINGLE_QUERY (1: single queries through the certified fp16-shadow pass too)
+    bool code8_single_query = true;    // index option code8_single_query: single queries over large inner-product indexes through the int8 prefilter
+    long long code8_capacity = 32768;  // index option code8_capacity: candidates the prefilter may hand to the exact re-score
     int grouped_items_per_cu = 0;      // MVDB_GROUPED_ITEMS_PER_CU: work items per CU the grouped launch aims at (0: the default of mvdb.hip plan_grouped; sweep in DESIGN.md section 6c)
     int grouped_min_batches = 4;       // MVDB_GROUPED_MIN_BATCHES: fewest row batches per wave of a work item
     long long compact_bytes = 512ll << 20;  // MVDB_COMPACT_BYTES: staging buffer of a row compaction (mvdb_index_remove_rows)

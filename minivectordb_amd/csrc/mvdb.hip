@@ -17,6 +17,7 @@
 #include "scan_kernels.hpp"
 #include "grouped_scan.hpp"
 #include "range_scan.hpp"
+#include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
 #include "half_scan.hpp"
@@ -215,6 +216,7 @@ struct Workspace {
     DevBuf<uint64_t> rkeys;             // range search: [nq, segment] appended keys (range_scan.hpp)
     DevBuf<unsigned long long> rcounts;  // ... and the host entry point's per-query counters
     DevBuf<char> gtab;
+    DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter, gate, seed results, candidates, row list
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
         PinnedBuf buf;
         hipEvent_t ev = nullptr;
@@ -256,6 +258,7 @@ struct Workspace {
         rkeys.release();
         rcounts.release();
         gtab.release();
+        c8.release();
         for (GroupedStage* g : gstage) {
             g->buf.release();
             if (g->ev) (void)hipEventDestroy(g->ev);
@@ -320,6 +323,21 @@ struct mvdb_index {
     mutable std::atomic<unsigned int> rf_seen{0};
     mutable std::atomic<int> rf_calls_left{0};
     mutable std::atomic<unsigned long long> sq_suspensions{0};
+    // int8 code of the rows (code8_scan.hpp): d codes + (scale, residual bound) per row beside the matrix,
+    // the operand of the single-query prefilter.  Lifecycle of the fp16 shadow: built by the first eligible single query, extended
+    // by add, emptied by whatever renumbers rows, freed with the matrix; built / read under shadow_mu by searches.
+    mutable int8_t* C8 = nullptr;
+    mutable float2* c8_ar = nullptr;
+    mutable int64_t* c8_seed = nullptr;        // the seed sample's rows (kCode8Seed, spread over [0, c8_rows))
+    mutable std::atomic<bool> c8_wanted{false};   // an eligible single query has asked for the code since the index was created / reset
+    mutable int64_t c8_cap = 0, c8_rows = 0;
+    mutable std::atomic<bool> c8_failed{false};
+    mutable std::atomic<int> c8_wait{0};       // single queries the exact scan still answers before a dropped code is rebuilt
+    mutable unsigned int* c8_ctr_dev = nullptr;   // [0] fallbacks, [1] calls
+    mutable PinnedBuf c8_stats;                   // host-mapped mirror: fallbacks, candidates of the latest call, calls
+    mutable std::atomic<unsigned int> c8_calls{0}, c8_window_calls{0}, c8_window_fail{0};
+    mutable std::atomic<int> c8_suspend_left{0};
+    mutable std::atomic<unsigned long long> c8_suspensions{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -389,6 +407,10 @@ struct KnobScope {
 };
 inline const Knobs& kn() { return *tls_kn; }
 
+// the profiling label of the scans a pass launches on its own behalf (the prefilter route's seed and re-score: "ip_scan" is
+// the label of the launch that reads the corpus)
+thread_local const char* tls_scan_label = nullptr;
+
 // ---- shape selection: G lanes per row, C chunks per lane, U rows in flight ----------------------
 struct Shape {
     int G, C;
@@ -439,7 +461,7 @@ int launch_scan_kern(const ScanArgs& a, int nq, int device, hipStream_t stream, 
     int64_t cap = (int64_t)device_cus(device) * occ;
     int nblocks = (int)std::max<int64_t>(1, std::min(want, cap));
     if (nblocks_out) *nblocks_out = nblocks;
-    const char* pname = MODE == kModeTopK ? "ip_scan" : "ip_scan_scores";
+    const char* pname = tls_scan_label ? tls_scan_label : MODE == kModeTopK ? "ip_scan" : "ip_scan_scores";
     prof_symbol(pname, "flat_scan_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", G, C, U, METRIC, MODE, NT ? "true" : "false", SEL,
                 MASKED ? "true" : "false", gated ? "true" : "false");
     int slot = prof_begin(pname, stream);
@@ -928,6 +950,9 @@ bool half_path_ok(const mvdb_index* idx) {
 
 const _Float16* ensure_shadow(const mvdb_index* idx, hipStream_t s, float xscale);
 const float* ensure_offsets(const mvdb_index* idx, hipStream_t s);
+bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, const uint64_t* mask_dev, int64_t n);
+int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                 bool* served);
 
 int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int nqpad, int k, int64_t n,
                      int64_t label_offset, float* D, int64_t* I, int* flag, int* failed, const uint32_t* mask = nullptr,
@@ -1159,6 +1184,14 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
     a.mask = mask_dev;
     a.cand = nullptr;
     a.scores = nullptr;
+
+    // ONE query over a large inner-product index: the int8 prefilter names the rows that can reach the top k, the exact kernel
+    // scores those (code8_search).  Not served (no code yet and the stream is capturing, allocation failed, suspended): below.
+    if (allow_split && code8_route_ok(idx, nq, k, rows_dev, mask_dev, n)) {
+        bool served = false;
+        MVDB_TRY(code8_search(idx, ws, a, k, label_offset, D_dev, I_dev, &served));
+        if (served) return 0;
+    }
 
     // Batches (2+ queries where the corpus buries the pass's fixed cost, half_min_nq), k <= 32, rows of known norm, a width the
     // fp16 kernels serve: ONE fp16 product over the shadow nominates, fp32 re-scores decide, a worst-case bound certifies
@@ -1816,6 +1849,268 @@ const float* ensure_offsets(const mvdb_index* idx, hipStream_t s) {
     return idx->Hn;
 }
 
+// ---- the int8 code of the rows and the single-query prefilter route (code8_scan.hpp) -------------------
+constexpr int64_t kCode8Seed = 131072;     // rows of the seed sample (exact scores: their k-th best is the prefilter's floor)
+constexpr int64_t kCode8MinRows = 500000;
+constexpr int64_t kCode8MaxCapacity = 65536;   // code8_list_kernel ranks by counting: quadratic in the candidates
+// A dropped code is rebuilt once the exact scan has answered this many single queries since the drop: the build moves about
+// 1.25 scans' worth of bytes (the matrix read once, a quarter of it written), a served query saves about 0.75 — two queries
+// pay for it, so a workload that alternates one delete and one query never builds.
+constexpr int kCode8RebuildAfter = 2;
+
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
+}
+
+// (count_rebuild: the rows changed under a code that was held or wanted — the wait starts again, whether or not a code is
+//  held right now: every delete of a delete / query alternation restarts it, so such a workload never builds)
+void drop_code8(const mvdb_index* idx, bool count_rebuild = true) {
+    if (idx->C8) (void)hipFree(idx->C8);
+    if (idx->c8_ar) (void)hipFree(idx->c8_ar);
+    if (idx->c8_seed) (void)hipFree(idx->c8_seed);
+    idx->C8 = nullptr;
+    idx->c8_ar = nullptr;
+    idx->c8_seed = nullptr;
+    idx->c8_cap = idx->c8_rows = 0;
+    if (count_rebuild && idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
+}
+// rows were renumbered: emptied, the allocation kept (invalidate_shadow)
+void invalidate_code8(const mvdb_index* idx) {
+    if (idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
+    idx->c8_rows = 0;
+}
+
+bool code8_dim(int d) { return d == 384 || d == 512 || d == 1024; }
+
+int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, int64_t n_after, hipStream_t s) {
+    if (rows > 0) {
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
+        hipLaunchKernelGGL(code8_build_kernel, dim3(grid), dim3(256), 0, s, (const float*)(idx->X + row0 * idx->ld), idx->ld, idx->d, rows,
+                           idx->C8 + row0 * idx->d, idx->c8_ar + row0);
+    }
+    hipLaunchKernelGGL(code8_seed_rows_kernel, dim3((unsigned)((kCode8Seed + 255) / 256)), dim3(256), 0, s, idx->c8_seed, kCode8Seed, n_after);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// The code for a single query on stream s (caller holds the index shared).  false: the exact scan serves this call.
+bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(idx->shadow_mu);
+    if (idx->C8 && idx->c8_rows == idx->n) return true;
+    if (idx->c8_failed || stream_capturing(s)) return false;
+    idx->c8_wanted.store(true);
+    if (idx->c8_wait.load(std::memory_order_relaxed) > 0) {
+        idx->c8_wait.fetch_sub(1, std::memory_order_relaxed);
+        return false;
+    }
+    if (idx->C8 && idx->c8_cap < idx->n) drop_code8(idx, false);
+    if (!idx->C8) {
+        const int64_t cap = std::max<int64_t>(idx->cap, idx->n);
+        // the padding row of the candidate list: the LAST row of the slack behind the matrix (kRowSlack rows that are read
+        // by the tiled kernels and never nominated), filled with NaN — no scan ever offers it; the matrix' rows are untouched
+        const size_t nan_floats = (size_t)idx->ld;
+        float* nan_row = idx->X + (idx->cap + kRowSlack - 1) * idx->ld;
+        bool ok = hipMalloc((void**)&idx->C8, (size_t)cap * idx->d) == hipSuccess &&
+                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess &&
+                  hipMalloc((void**)&idx->c8_seed, (size_t)kCode8Seed * sizeof(int64_t)) == hipSuccess;
+        if (ok && !idx->c8_ctr_dev) {
+            ok = hipMalloc((void**)&idx->c8_ctr_dev, 2 * sizeof(unsigned int)) == hipSuccess &&
+                 hipMemset(idx->c8_ctr_dev, 0, 2 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
+            if (ok) memset(idx->c8_stats.p, 0, 64);
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            drop_code8(idx, false);
+            idx->c8_failed = true;
+            return false;
+        }
+        idx->c8_cap = cap;
+        idx->c8_rows = 0;
+        hipLaunchKernelGGL(code8_fill_nan_kernel, dim3((unsigned)((nan_floats + 255) / 256)), dim3(256), 0, s, nan_row, (int64_t)nan_floats);
+    }
+    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, idx->n, s) != 0 || hipStreamSynchronize(s) != hipSuccess) {
+        drop_code8(idx, false);
+        idx->c8_failed = true;
+        return false;
+    }
+    idx->c8_rows = idx->n;
+    return true;
+}
+
+// One decision per call the route would serve: true = suspended, the exact scan answers (single_route_suspended's windows).
+bool code8_suspended(const mvdb_index* idx) {
+    if (idx->c8_suspend_left.load(std::memory_order_relaxed) > 0) {
+        idx->c8_suspend_left.fetch_sub(1, std::memory_order_relaxed);
+        return true;
+    }
+    const unsigned int calls = idx->c8_calls.fetch_add(1, std::memory_order_relaxed) + 1;
+    if (calls - idx->c8_window_calls.load(std::memory_order_relaxed) >= (unsigned int)kSingleWindow && idx->c8_stats.p) {
+        const unsigned int fails = *reinterpret_cast<volatile unsigned int*>(idx->c8_stats.p);
+        if ((fails - idx->c8_window_fail.load(std::memory_order_relaxed)) * 2 >= (unsigned int)kSingleWindow) {
+            idx->c8_suspend_left.store(kSingleSuspend, std::memory_order_relaxed);
+            idx->c8_suspensions.fetch_add(1, std::memory_order_relaxed);
+        }
+        idx->c8_window_calls.store(calls, std::memory_order_relaxed);
+        idx->c8_window_fail.store(fails, std::memory_order_relaxed);
+    }
+    return false;
+}
+
+bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, const uint64_t* mask_dev, int64_t n) {
+    if (nq != 1 || !idx->kn.code8_single_query || idx->kn.shadow_single_query) return false;
+    if (idx->metric != MVDB_METRIC_IP || rows_dev || mask_dev || k > kMaxFusedK) return false;
+    if (n != idx->n || n < kCode8MinRows || !code8_dim(idx->d) || idx->ld != idx->d) return false;
+    if (!(idx->row_norm_bound > 0.f) || !(idx->row_norm_bound < 1.0e30f) || idx->c8_failed) return false;
+    return true;
+}
+
+// the device-gated full exact scan of the route's fallback: the headline kernel's shape with GATED set
+template <int G, int C, int U>
+int launch_gated_ip_scan(const ScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
+    void (*kern)(ScanArgs) = flat_scan_kernel<G, C, U, 0, kModeTopK, true, 0, false, true>;
+    const int occ = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), (C == 1 || C == 3) ? 3 : 2);
+    constexpr int RB = (kWave / G) * U;
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * occ));
+    *nblocks_out = nblocks;
+    prof_symbol("ip_scan_code8_fallback", "flat_scan_kernel<%d, %d, %d, 0, 0, true, 0, false, true>", G, C, U);
+    int slot = prof_begin("ip_scan_code8_fallback", stream);
+    hipLaunchKernelGGL(kern, dim3(nblocks, 1), dim3(kScanThreads), 0, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int G, int U, bool MASKED>
+int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
+    constexpr int RB = (kWave / G) * U;
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
+    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), 2);  // flat_scan_kernel's grid: CUs x 2 blocks
+    if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+    prof_symbol("ip_scan", "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
+    int slot = prof_begin("ip_scan", stream);
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+struct ScanLabelScope {
+    const char* prev;
+    explicit ScanLabelScope(const char* l) : prev(tls_scan_label) { tls_scan_label = l; }
+    ~ScanLabelScope() { tls_scan_label = prev; }
+};
+
+int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                 bool* served) {
+    *served = false;
+    hipStream_t s = ws->stream;
+    const int d = idx->d;
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(idx->kn.code8_capacity, kCode8MaxCapacity));
+    // workspace layout (bytes): planes [2 d] | terms [16 floats] | counter | gate | seed D [64] | seed I [64] | candidates | list
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t o_planes = take((size_t)2 * d), o_par = take(16 * sizeof(float)), o_ctr = take(sizeof(unsigned long long)),
+                 o_gate = take(sizeof(int)), o_sd = take(kMaxFusedK * sizeof(float)), o_si = take(kMaxFusedK * sizeof(int64_t)),
+                 o_cand = take((size_t)cap * sizeof(uint32_t)), o_list = take((size_t)cap * sizeof(int64_t));
+    const size_t cand_keys = (size_t)scan_grid_upper_bound(idx->device) * k;
+    const bool capturing = stream_capturing(s);
+    if (capturing && (ws->c8.cap < off || ws->cand.cap < cand_keys)) return 0;  // nothing is allocated inside a capture
+    if (code8_suspended(idx)) return 0;
+    if (!ensure_code8(idx, s)) return 0;
+    MVDB_TRY(ws->c8.reserve(off));
+    MVDB_TRY(ws->cand.reserve(cand_keys));
+    char* base = ws->c8.p;
+    int8_t* qhi = reinterpret_cast<int8_t*>(base + o_planes);
+    int8_t* qlo = qhi + d;
+    float* par = reinterpret_cast<float*>(base + o_par);
+    unsigned long long* counter = reinterpret_cast<unsigned long long*>(base + o_ctr);
+    int* gate = reinterpret_cast<int*>(base + o_gate);
+    float* seedD = reinterpret_cast<float*>(base + o_sd);
+    int64_t* seedI = reinterpret_cast<int64_t*>(base + o_si);
+    uint32_t* cand = reinterpret_cast<uint32_t*>(base + o_cand);
+    int64_t* list = reinterpret_cast<int64_t*>(base + o_list);
+
+    hipLaunchKernelGGL(code8_query_kernel, dim3(1), dim3(256), 0, s, a0.q, d, a0.normalize_q, idx->row_norm_bound, qhi, qlo, par, counter);
+    MVDB_HIP(hipGetLastError());
+
+    auto merge = [&](int nlists, float* D, int64_t* I, int64_t lo, const int* g) {
+        MergeArgs ma;
+        ma.keys = ws->cand.p;
+        ma.nlists = nlists;
+        ma.k = k;
+        ma.metric = idx->metric;
+        ma.label_offset = lo;
+        ma.D = D;
+        ma.I = I;
+        ma.gate = g;
+        hipLaunchKernelGGL(merge_keys_kernel, dim3(1), dim3(kMergeThreads), 0, s, ma);
+    };
+    // 1. the floor: exact scores of the seed sample (the row-list form of the exact kernel), their k-th best
+    ScanArgs a = a0;
+    a.cand = ws->cand.p;
+    int nblocks = 0;
+    {
+        ScanLabelScope label("ip_scan_code8_seed");
+        a.rows = idx->c8_seed;
+        a.n = kCode8Seed;
+        MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
+        merge(nblocks, seedD, seedI, 0, nullptr);
+    }
+    // 2. the prefilter over the codes
+    Code8ScanArgs c;
+    c.codes = idx->C8;
+    c.ar = idx->c8_ar;
+    c.n = idx->n;
+    c.d = d;
+    c.qhi = qhi;
+    c.qlo = qlo;
+    c.par = par;
+    c.floor = seedD + (k - 1);
+    c.cand = cand;
+    c.cap = cap;
+    c.counter = counter;
+    if (d == 512) MVDB_TRY((launch_code8_scan<32, 4, false>(c, idx->device, s)));
+    else if (d == 1024) MVDB_TRY((launch_code8_scan<64, 4, false>(c, idx->device, s)));
+    else MVDB_TRY((launch_code8_scan<32, 4, true>(c, idx->device, s)));
+    // 3. candidates -> ascending row list, padded with the row of NaN in the matrix' slack
+    const int64_t pad = idx->cap + kRowSlack - 1;  // the NaN row in the matrix' slack (ensure_code8)
+    hipLaunchKernelGGL(code8_list_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, (const uint32_t*)cand,
+                       (const unsigned long long*)counter, cap, k, (const float*)par, pad, list, gate, idx->c8_ctr_dev,
+                       (volatile unsigned int*)idx->c8_stats.p);
+    MVDB_HIP(hipGetLastError());
+    // 4. the exact scores of the candidates: flat_scan_kernel's row-list form, ties by position = by row
+    {
+        ScanLabelScope label("ip_scan_code8_rescore");
+        a.rows = list;
+        a.n = cap;
+        MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
+        merge(nblocks, D_dev, I_dev, 0, nullptr);
+        hipLaunchKernelGGL(code8_relabel_kernel, dim3(1), dim3(64), 0, s, I_dev, k, (const int64_t*)list, label_offset);
+    }
+    // 5. fallback, enabled on the device: the full exact scan overwrites the result
+    a.rows = nullptr;
+    a.n = idx->n;
+    a.gate = gate;
+    a.gate_lo = 0;
+    if (d == 512) MVDB_TRY((launch_gated_ip_scan<64, 2, 2>(a, idx->device, s, &nblocks)));
+    else if (d == 1024) MVDB_TRY((launch_gated_ip_scan<64, 4, 1>(a, idx->device, s, &nblocks)));
+    else MVDB_TRY((launch_gated_ip_scan<32, 3, 4>(a, idx->device, s, &nblocks)));
+    merge(nblocks, D_dev, I_dev, label_offset, gate);
+    MVDB_HIP(hipGetLastError());
+    *served = true;
+    return 0;
+}
+
 int grow(mvdb_index* idx, int64_t need) {
     if (need <= idx->cap) return 0;
     int64_t cap = std::max<int64_t>(need, idx->cap + idx->cap / 2);
@@ -1823,6 +2118,7 @@ int grow(mvdb_index* idx, int64_t need) {
     // the fp16 shadow (50 % of the matrix's bytes) goes first: it is sized for the old capacity anyway (rebuilt by the next
     // batch search), and an add on a nearly full device must not fail for a copy that is about to be dropped
     drop_shadow(idx);
+    drop_code8(idx);
     float* nx = nullptr;
     MVDB_HIP(hipMalloc((void**)&nx, (size_t)(cap + kRowSlack) * idx->ld * sizeof(float)));
     if (idx->n > 0) {
@@ -1899,7 +2195,11 @@ int mvdb_index_create(int d, int metric, int device, mvdb_index** out) {
 int mvdb_index_reload_env(mvdb_index* idx) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
+    const bool code8 = idx->kn.code8_single_query;   // (options without an environment switch: kept)
+    const long long code8_cap = idx->kn.code8_capacity;
     idx->kn = read_knobs();
+    idx->kn.code8_single_query = code8;
+    idx->kn.code8_capacity = code8_cap;
     return 0;
 }
 
@@ -1913,13 +2213,21 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         idx->sq_suspend_left.store(0);   // a fresh start: the route probes again from its next call
         idx->sq_window_calls.store(idx->sq_calls.load());
         if (idx->sq_fail_host.p) idx->sq_window_fail.store(*reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p));
+    } else if (n == "code8_single_query") {
+        idx->kn.code8_single_query = value != 0;
+        idx->c8_suspend_left.store(0);
+        idx->c8_window_calls.store(idx->c8_calls.load());
+        if (idx->c8_stats.p) idx->c8_window_fail.store(*reinterpret_cast<volatile unsigned int*>(idx->c8_stats.p));
+    } else if (n == "code8_capacity") {  // diagnostic: a small candidate capacity makes calls take the fallback
+        if (value <= 0 || value > kCode8MaxCapacity) return fail(MVDB_ERR_ARG, "code8_capacity must lie in [1, %lld]", (long long)kCode8MaxCapacity);
+        idx->kn.code8_capacity = value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -1941,6 +2249,9 @@ int mvdb_index_free(mvdb_index* idx) {
         if (idx->rf_dev) (void)hipFree(idx->rf_dev);
         idx->rf_host.release();
         drop_shadow(idx);
+        drop_code8(idx);
+        if (idx->c8_ctr_dev) (void)hipFree(idx->c8_ctr_dev);
+        idx->c8_stats.release();
         for (Workspace* w : idx->free_ws) {
             w->destroy();
             delete w;
@@ -1966,6 +2277,7 @@ int mvdb_index_reset(mvdb_index* idx) {
     MVDB_TRY(quiesce(idx));
     idx->n = 0;
     drop_shadow(idx);
+    drop_code8(idx);
     idx->row_norm_bound = 0.f;
     idx->norm2_lo = INFINITY;
     idx->norm2_hi = 0.f;
@@ -1979,6 +2291,26 @@ int64_t mvdb_index_shadow_rows(const mvdb_index* idx) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
     return idx->Xh ? idx->xh_rows : 0;
 }
+int64_t mvdb_index_code8_rows(const mvdb_index* idx) {
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->shadow_mu);
+    return idx->C8 ? idx->c8_rows : 0;
+}
+int mvdb_index_code8_counters(const mvdb_index* idx, long long* fallbacks, long long* last_candidates, long long* calls) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    const volatile unsigned int* st = reinterpret_cast<const volatile unsigned int*>(idx->c8_stats.p);
+    if (fallbacks) *fallbacks = st ? (long long)st[0] : 0;
+    if (last_candidates) *last_candidates = st ? (long long)st[1] : 0;
+    if (calls) *calls = st ? (long long)st[2] : 0;
+    return 0;
+}
+int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta) {
+    if (d <= 0 || !alpha || !beta) return fail(MVDB_ERR_ARG, "mvdb_code8_margin: bad arguments");
+    const Code8Margin m = code8_margin(d, qnorm, qstep, row_norm_bound);
+    *alpha = m.alpha;
+    *beta = m.beta;
+    return 0;
+}
 int mvdb_index_dim(const mvdb_index* idx) { return idx ? idx->d : -1; }
 int mvdb_index_device(const mvdb_index* idx) { return idx ? idx->device : -1; }
 
@@ -1991,6 +2323,7 @@ int mvdb_index_reserve(mvdb_index* idx, int64_t n) {
     MVDB_TRY(quiesce(idx));
     // exact-size growth (no 1.5x slack): the caller knows the final size
     drop_shadow(idx);  // before the new matrix is allocated (see grow)
+    drop_code8(idx);
     float* nx = nullptr;
     MVDB_HIP(hipMalloc((void**)&nx, (size_t)(n + kRowSlack) * idx->ld * sizeof(float)));
     if (idx->n > 0) {
@@ -2076,6 +2409,20 @@ static int extend_shadow(mvdb_index* idx, int64_t n_new) {
     return 0;
 }
 
+// add: the code follows when it is there, complete and still fits (the rows are coded from the matrix, on the mutators' stream)
+static int extend_code8(mvdb_index* idx, int64_t n_new) {
+    if (!idx->C8) return 0;
+    if (idx->c8_cap < idx->n + n_new) {
+        drop_code8(idx);
+        return 0;
+    }
+    if (idx->c8_rows != idx->n) return 0;  // emptied by a delete: the next eligible query codes every row again
+    MVDB_TRY(code8_convert(idx, idx->n, n_new, idx->n + n_new, idx->mut));
+    MVDB_HIP(hipStreamSynchronize(idx->mut));
+    idx->c8_rows = idx->n + n_new;
+    return 0;
+}
+
 int mvdb_index_add(mvdb_index* idx, const float* x_host, int64_t n, int normalize) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
@@ -2100,6 +2447,7 @@ int mvdb_index_add(mvdb_index* idx, const float* x_host, int64_t n, int normaliz
     MVDB_HIP(hipStreamSynchronize(idx->mut));  // the caller's buffer is free again, the rows are in place
     MVDB_TRY(note_row_norms(idx, dst, n, normalize));
     MVDB_TRY(extend_shadow(idx, n));
+    MVDB_TRY(extend_code8(idx, n));
     idx->n += n;
     return 0;
 }
@@ -2134,6 +2482,7 @@ int mvdb_index_add_device(mvdb_index* idx, const float* x_dev, int64_t n, int no
     MVDB_HIP(hipStreamSynchronize(idx->mut));
     MVDB_TRY(note_row_norms(idx, dst, n, normalize));
     MVDB_TRY(extend_shadow(idx, n));
+    MVDB_TRY(extend_code8(idx, n));
     idx->n += n;
     return 0;
 }
@@ -2160,6 +2509,7 @@ int mvdb_index_add_synthetic(mvdb_index* idx, int64_t n, uint64_t seed, int64_t 
     MVDB_HIP(hipStreamSynchronize(idx->mut));
     MVDB_TRY(note_row_norms(idx, dst, n, normalize));
     MVDB_TRY(extend_shadow(idx, n));
+    MVDB_TRY(extend_code8(idx, n));
     idx->n += n;
     return 0;
 }
@@ -2201,6 +2551,7 @@ int mvdb_index_remove_rows(mvdb_index* idx, const int64_t* rows_host, int64_t m)
     MVDB_TRY(quiesce(idx));
     ++idx->renumbered;
     invalidate_shadow(idx);  // rows are renumbered: the next batch search rebuilds the shadow in the allocation it already has
+    invalidate_code8(idx);
     const int64_t n_new = idx->n - m;
     if (n_new == 0) {
         idx->n = 0;
