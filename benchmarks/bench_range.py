@@ -13,7 +13,16 @@ nq = 1 and 16.  Per cell, device buffers, hipEvents, medians of --reps after 3 w
      cells carry no scan-launch ratio
 
 Two runs: `--columns range --out A.jsonl` on this build, then `--columns parent --merge-from A.jsonl --out B.jsonl` with
-MVDB_LIBMVDB naming the parent commit's library (column b needs nothing this build adds); B holds the merged records."""
+MVDB_LIBMVDB naming the parent commit's library (column b needs nothing this build adds); B holds the merged records.
+
+`--batch`: the BATCH cells of the shared pass instead — 1M x 512 and 10M x 512, 8 / 32 / 128 / 256
+queries, thresholds for about 10 and about 1,000 passing rows per query and one dense cell (1 % of the rows).  Per cell, the same
+device call under option "range_shared" = 0 (one fp32 pass per query: the route every batch took before the shared pass
+existed, same kernels) and = 1 (the automatic rule), the nomination launch alone ("ip_scan_range_half"), and beside it the
+certified top-k call (k = 10) of the same (nq, n, d), which streams the same shadow.  The "per_query" column is THIS build
+with the route switched off, not the parent commit's library: the parent has no option to switch, and its range_scan_kernel
+lacks the two branches this build adds at the top of the kernel (the per-query threshold pointer and the device gate, both
+NULL on that column)."""
 import argparse
 import json
 import os
@@ -71,8 +80,75 @@ def cell_key(c):
     return (c["n"], c["target"], c["filter"], c["nq"])
 
 
+def batch_cells(args):
+    d = 512
+    stream = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(2026)
+    sd = 1.0 / np.sqrt(d)
+    sink = open(args.out, "w") if args.out else None
+    for n in args.rows:
+        idx = _native.FlatIndex(d)
+        idx.reserve(n)
+        idx.add_synthetic(n, 1234)
+        qh = rng.standard_normal((max(args.batch_nq), d), dtype=np.float32)
+        q = torch.from_numpy(qh).cuda()
+        for target in (10, 1_000, n // 100):
+            t = float(sd * statistics.NormalDist().inv_cdf(1.0 - target / n))
+            for nq in args.batch_nq:
+                idx.set_option("range_shared", 1)
+                counts = idx.range_count(qh[:nq], t, normalize_q=True)
+                cap = pow2ceil(int(counts.max()))
+                ct = torch.empty(nq, dtype=torch.int64, device="cuda")
+                D = torch.empty((nq, cap), dtype=torch.float32, device="cuda")
+                I = torch.empty((nq, cap), dtype=torch.int64, device="cuda")
+
+                def ranged():
+                    idx.range_search_device(q.data_ptr(), nq, t, cap, ct.data_ptr(), D.data_ptr(), I.data_ptr(), stream=stream,
+                                            normalize_q=True)
+
+                rec = {"bench": "range_batch", "n": n, "d": d, "target": target, "threshold": round(t, 6), "nq": nq,
+                       "counts_min": int(counts.min()), "counts_max": int(counts.max()), "cap": cap}
+                idx.set_option("range_shared", 0)
+                slow_reps = max(2, min(args.reps, int(2e9 // (n * nq)) or 2))     # (256 fp32 passes over 10M rows: 0.7 s a call)
+                rec["per_query_ms"] = round(timed_events(ranged, slow_reps, warm=1), 4)
+                ref = (ct.cpu().numpy().copy(), D.cpu().numpy().view(np.uint32).copy(), I.cpu().numpy().copy())
+                idx.set_option("range_shared", 1)
+                calls, fb0 = idx.range_counters()[:2]
+                rec["auto_ms"] = round(timed_events(ranged, args.reps), 4)
+                torch.cuda.synchronize()
+                after = idx.range_counters()
+                rec["auto_took_shared"] = after[0] > calls
+                rec["fallback_queries_per_call"] = round((after[1] - fb0) / (args.reps + 3), 2)
+                rec["candidates"] = after[2]
+                rec["identical"] = bool(np.array_equal(ct.cpu().numpy(), ref[0]) and np.array_equal(D.cpu().numpy().view(np.uint32), ref[1])
+                                        and np.array_equal(I.cpu().numpy(), ref[2]))
+                rec["speedup"] = round(rec["per_query_ms"] / rec["auto_ms"], 2)
+                if rec["auto_took_shared"]:
+                    for label, key in (("ip_scan_range_half", "nominate_launch_ms"), ("ip_scan_range_rescore", "rescore_launch_ms"),
+                                       ("ip_scan_range_fallback", "fallback_launch_ms")):
+                        ms, sym = launch_ms(ranged, label, args.reps)
+                        rec[key] = round(ms, 4) if ms is not None else None
+                    Dk = torch.empty((nq, 10), dtype=torch.float32, device="cuda")
+                    Ik = torch.empty((nq, 10), dtype=torch.int64, device="cuda")
+                    k10 = lambda: idx.search_device(q.data_ptr(), nq, 10, Dk.data_ptr(), Ik.data_ptr(), stream=stream, normalize_q=True)
+                    rec["topk10_device_ms"] = round(timed_events(k10, args.reps), 4)
+                    ms, sym = launch_ms(k10, "ip_scan_half", args.reps)
+                    rec["topk10_half_launch_ms"], rec["topk10_half_symbol"] = (round(ms, 4) if ms is not None else None), sym
+                line = json.dumps(rec)
+                print(line, flush=True)
+                if sink:
+                    sink.write(line + "\n")
+                    sink.flush()
+                del D, I
+                torch.cuda.empty_cache()
+        idx.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true", help="the batch cells of the shared pass")
+    ap.add_argument("--batch-nq", type=int, nargs="+", default=[8, 32, 128, 256])
     ap.add_argument("--rows", type=int, nargs="+", default=[10_000_000, 1_000_000])
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--reps", type=int, default=20)
@@ -80,6 +156,8 @@ def main():
     ap.add_argument("--merge-from", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.batch:
+        return batch_cells(args)
     if args.columns == "parent":
         for name in RANGE_SYMBOLS:          # the parent's library does not export them
             _native.PROTOTYPES.pop(name, None)

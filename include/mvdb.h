@@ -321,8 +321,19 @@ int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, 
  *                partial answer would not be reproducible; call again with cap >= counts[i].
  * Bit identity: every returned score is bit for bit the score mvdb_index_search / mvdb_index_search_rowset returns for that
  * (query, row) with nq = 1 on the default routing; row i equals the leading counts[i] entries of that call with
- * k = counts[i], and entry counts[i] + 1 of a longer one, if there is one, is below the threshold.  Several queries of a call
- * are answered one corpus pass each.
+ * k = counts[i], and entry counts[i] + 1 of a longer one, if there is one, is below the threshold.
+ * Corpus passes.  A single query, an L2 index and a list-form row set take one pass over the fp32 rows per query.
+ * A batch may share passes instead.  It is eligible if the index is inner product, the call names every row or a
+ * bitmap-form set, and the index's shape keeps an fp16 shadow (mvdb_index_shadow_rows).  Option "range_shared" decides:
+ * 0 never (the default: the route has not been timed yet), 1 from 33 queries on, 2 wherever the call
+ * is eligible.
+ * On the shared route one pass over the shadow per 128 / 256 queries names every row whose fp16 score is not provably below
+ * the query's threshold (band: mvdb_range_band).  The exact kernel re-scores those rows in the single-query scan's
+ * arithmetic and decides.  A query with more candidates than the route holds per query (option "range_candidates":
+ * 64 .. 2^20, 0 = default = max(2 cap rounded up to a power of two, 4096), at most 256 MiB of candidates per launch) is
+ * answered by its own fp32 pass, enabled on the device.  The results are the same bits on every route.  The route builds the
+ * shadow as a batch search does (first eligible call, never while the stream is capturing: such a call takes the per-query
+ * passes).
  * A NaN threshold is MVDB_ERR_ARG; -inf (inner product) selects every row whose score is not NaN; rows with NaN scores never
  * match.  A stale or foreign row set: MVDB_ERR_ARG before anything is enqueued, nothing written.  Empty index: counts 0.
  * The host entry point reads the counts back before it sorts, so its sort and its copy are sized by the results, not by cap.
@@ -337,6 +348,26 @@ int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, 
 int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, int nq, float threshold, int normalize_q,
                                    const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev,
                                    float* D_dev, int64_t* I_dev, void* stream);
+/* PER-QUERY THRESHOLDS: the contract of mvdb_index_range_search / _device word for word, with `threshold` read as
+ * thresholds[i] for query i (counts, cap, overflow markers, ties, labels, NaN rows, stale or foreign sets, the empty index,
+ * both metrics, capturability, routing).  A NaN entry of the HOST array is MVDB_ERR_ARG before anything is enqueued; the
+ * device variant cannot look: a NaN threshold there matches nothing (count 0). */
+int mvdb_index_range_search_each(const mvdb_index* idx, const float* q_host, int nq, const float* thresholds_host /*[nq]*/,
+                                 int normalize_q, const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host,
+                                 int64_t* I_host);
+int mvdb_index_range_search_each_device(const mvdb_index* idx, const float* q_dev, int nq, const float* thresholds_dev /*[nq]*/,
+                                        int normalize_q, const mvdb_rowset* rs, int64_t cap, int64_t label_offset,
+                                        int64_t* counts_dev, float* D_dev, int64_t* I_dev, void* stream);
+/* The band of the shared pass: for a query of norm qnorm and any stored row x, |x| <= row_norm_bound,
+ * the fp16 nomination score lies within the returned value of the fp32 score the exact scans compute (in the scans' own
+ * summation order, for the widths that keep a shadow).  Below 1e-3 * qnorm * row_norm_bound at d = 1024.  Pure host arithmetic
+ * (no device needed); linear in qnorm and in row_norm_bound. */
+double mvdb_range_band(int d, float qnorm, float row_norm_bound);
+/* Diagnostics of the shared pass, read without synchronising (the device-side words lag by the calls in flight): calls that
+ * took it, queries its fallback answered (running total), candidates held by the latest launch group of up to 1024 queries.
+ * Any pointer may be NULL. */
+int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries,
+                              long long* last_candidates);
 
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the

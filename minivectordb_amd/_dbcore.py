@@ -626,12 +626,15 @@ class FilterAndRerankMixin:
 
     def find_all_similar_batch(self, embeddings, min_score, metadata_filter=None, exclude_filter=None, or_filters=None,
                                limit=None):
-        """Several queries under ONE filter: element i is what ``find_all_similar(embeddings[i], min_score, ...)`` returns.
-        Each query is its own pass over the selected rows (a range result is bit for bit the single query's)."""
+        """Several queries under ONE filter: element i is what ``find_all_similar(embeddings[i], min_score, ...)`` returns —
+        `min_score` one number, or a sequence with one per query (``min_score[i]`` for query i; another length or a NaN entry
+        is a ValueError).  A range result is bit for bit the single query's, whichever corpus passes the index shares between
+        the queries of the batch."""
         queries = self._range_queries(embeddings)
         if limit is not None and limit < 0:
             raise ValueError("limit must not be negative")
         if queries.shape[0] == 0 or self._mat is None:
+            self._range_min_scores(min_score, queries.shape[0])   # a bad min_score is an error whatever the database holds
             return [([], [], []) for _ in range(queries.shape[0])]
         uids = self._ids.uids
         out = []
@@ -652,6 +655,30 @@ class FilterAndRerankMixin:
             return 0
         return int(self._range_rows_many(query, min_score, metadata_filter, exclude_filter, or_filters, count_only=True)[0])
 
+    def count_similar_batch(self, embeddings, min_score, metadata_filter=None, exclude_filter=None, or_filters=None):
+        """``[count_similar(e, min_score, ...) for e in embeddings]`` in one call on the device, nothing but the integers
+        back; `min_score` as in ``find_all_similar_batch``."""
+        queries = self._range_queries(embeddings)
+        if queries.shape[0] == 0 or self._mat is None:
+            self._range_min_scores(min_score, queries.shape[0])
+            return [0] * queries.shape[0]
+        return [int(c) for c in self._range_rows_many(queries, min_score, metadata_filter, exclude_filter, or_filters, count_only=True)]
+
+    @staticmethod
+    def _range_min_scores(min_score, nq):
+        """A scalar min_score as a Python float (what a single-threshold index call takes); a sequence as float32[nq]."""
+        if np.ndim(min_score) == 0:
+            min_score = float(min_score)
+            if min_score != min_score:
+                raise ValueError("min_score is NaN")
+            return min_score
+        scores = np.ascontiguousarray(min_score, dtype=np.float32)
+        if scores.ndim != 1 or scores.shape[0] != nq:
+            raise ValueError(f"min_score has {scores.size} entries for {nq} queries: pass one number or one per query")
+        if np.isnan(scores).any():
+            raise ValueError("min_score holds a NaN")
+        return scores
+
     def _range_queries(self, embeddings):
         queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
         if queries.ndim != 2:
@@ -666,9 +693,7 @@ class FilterAndRerankMixin:
         device sync, filter evaluation, the resident row-set cache and the retry after a concurrent delete are
         `_nearest_rows_many`'s."""
         nq = query.shape[0]
-        min_score = float(min_score)
-        if min_score != min_score:
-            raise ValueError("min_score is NaN")
+        min_score = self._range_min_scores(min_score, nq)
         filtered = bool(metadata_filter or exclude_filter or or_filters)
         key = None
         if filtered:

@@ -100,6 +100,12 @@ PROTOTYPES = {
                                                c_vp, c_vp, c_vp]),
     "mvdb_index_range_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_vp,
                                                       ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_range_search_each": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int64,
+                                                    c_vp, c_vp, c_vp]),
+    "mvdb_index_range_search_each_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
+                                                           ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_range_band": (ctypes.c_double, [ctypes.c_int, ctypes.c_float, ctypes.c_float]),
+    "mvdb_index_range_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -452,35 +458,60 @@ class FlatIndex:
             raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
         return q
 
+    @staticmethod
+    def _range_thresholds(threshold, nq):
+        """None for a scalar threshold; else float32[nq] (one threshold per query; a NaN entry or another length: ValueError)."""
+        if np.ndim(threshold) == 0:
+            return None
+        t = np.ascontiguousarray(threshold, dtype=np.float32)
+        if t.ndim != 1 or t.shape[0] != nq:
+            raise ValueError(f"{t.shape} thresholds for {nq} queries: pass a scalar or one per query")
+        if np.isnan(t).any():
+            raise ValueError("a threshold is NaN")
+        return t
+
+    def range_counters(self):
+        """(calls that took the shared pass, queries its fallback answered, candidates of the latest launch group)."""
+        v = [ctypes.c_longlong(0) for _ in range(3)]
+        check(lib().mvdb_index_range_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     def range_search_raw(self, q, threshold, cap, rowset=None, normalize_q=False, out=None):
-        """One call of mvdb_index_range_search: (counts int64[nq], D float32[nq, cap], I int64[nq, cap]).  A query whose count
-        exceeds `cap` has a row of missing markers (-1); its count is still the true count.  out=(counts, D, I): caller-owned
-        arrays (D / I may be None with cap == 0)."""
+        """One call of mvdb_index_range_search (scalar `threshold`) or mvdb_index_range_search_each (one per query): (counts
+        int64[nq], D float32[nq, cap], I int64[nq, cap]).  A query whose count exceeds `cap` has a row of missing markers (-1);
+        its count is still the true count.  out=(counts, D, I): caller-owned arrays (D / I may be None with cap == 0)."""
         q = self._range_queries(q)
         nq, cap = q.shape[0], int(cap)
+        each = self._range_thresholds(threshold, nq)
         if out is None:
             counts = np.empty(nq, dtype=np.int64)
             D = np.empty((nq, cap), dtype=np.float32) if cap > 0 else None
             I = np.empty((nq, cap), dtype=np.int64) if cap > 0 else None
         else:
             counts, D, I = out
+        if each is not None:
+            check(lib().mvdb_index_range_search_each(
+                self._h, _ptr(q), nq, _ptr(each), int(bool(normalize_q)), rowset._h if rowset is not None else None, cap,
+                _ptr(counts), _ptr(D) if D is not None else None, _ptr(I) if I is not None else None))
+            return counts, D, I
         check(lib().mvdb_index_range_search(
             self._h, _ptr(q), nq, float(threshold), int(bool(normalize_q)), rowset._h if rowset is not None else None, cap,
             _ptr(counts), _ptr(D) if D is not None else None, _ptr(I) if I is not None else None))
         return counts, D, I
 
     def range_count(self, q, threshold, rowset=None, normalize_q=False):
-        """int64[nq]: how many selected rows reach the threshold (inner product: score >= threshold; L2: squared distance
-        <= threshold)."""
+        """int64[nq]: how many selected rows reach the threshold — a scalar, or one per query — (inner product: score >=
+        threshold; L2: squared distance <= threshold)."""
         return self.range_search_raw(q, threshold, 0, rowset, normalize_q)[0]
 
     def range_search(self, q, threshold, rowset=None, normalize_q=False, cap=None):
         """Every selected row that reaches the threshold, in faiss's range_search layout: (lims int64[nq + 1], D, I) with the
         results of query i at [lims[i], lims[i + 1]), best first, ties to the lower row; labels are ROW NUMBERS.  Calls with
         a capacity (`cap`, default 1024 per query) and once more, for the queries that overflowed only, with the largest
-        count seen."""
+        count seen.  `threshold`: a scalar, or one per query."""
         q = self._range_queries(q)
         nq = q.shape[0]
+        each = self._range_thresholds(threshold, nq)
         cap = self.RANGE_DEFAULT_CAP if cap is None else int(cap)
         if cap < 0:
             raise ValueError("cap must not be negative")
@@ -495,7 +526,8 @@ class FlatIndex:
                 Dout[lims[i]:lims[i + 1]] = D[i, :counts[i]]
                 Iout[lims[i]:lims[i + 1]] = I[i, :counts[i]]
             if over.size:
-                c2, D2, I2 = self.range_search_raw(q[over], threshold, int(counts[over].max()), rowset, normalize_q)
+                c2, D2, I2 = self.range_search_raw(q[over], threshold if each is None else each[over], int(counts[over].max()),
+                                                   rowset, normalize_q)
                 if not np.array_equal(c2, counts[over]):
                     continue   # rows were added or removed between the two calls: both again, on the index as it is now
                 for j, i in enumerate(over):
@@ -506,9 +538,16 @@ class FlatIndex:
         raise ValueError("the index kept changing between the two calls of a range search")
 
     def range_search_device(self, q_ptr, nq, threshold, cap, counts_ptr, D_ptr, I_ptr, rowset=None, stream=0,
-                            normalize_q=False, label_offset=0):
+                            normalize_q=False, label_offset=0, thresholds_ptr=0):
         """Device-pointer variant of range_search_raw (counts int64[nq], D float32[nq, cap], I int64[nq, cap] on the device;
-        labels: row numbers + label_offset); enqueues on `stream` and returns."""
+        labels: row numbers + label_offset); enqueues on `stream` and returns.  `threshold`: a Python number, or
+        ``thresholds_ptr=`` the device address of float32[nq] (one per query; a NaN there matches nothing)."""
+        if thresholds_ptr:
+            check(lib().mvdb_index_range_search_each_device(
+                self._h, ctypes.c_void_p(q_ptr), int(nq), ctypes.c_void_p(thresholds_ptr), int(bool(normalize_q)),
+                rowset._h if rowset is not None else None, int(cap), int(label_offset), ctypes.c_void_p(counts_ptr),
+                ctypes.c_void_p(D_ptr) if D_ptr else None, ctypes.c_void_p(I_ptr) if I_ptr else None, ctypes.c_void_p(stream)))
+            return
         check(lib().mvdb_index_range_search_device(
             self._h, ctypes.c_void_p(q_ptr), int(nq), float(threshold), int(bool(normalize_q)),
             rowset._h if rowset is not None else None, int(cap), int(label_offset), ctypes.c_void_p(counts_ptr),
@@ -761,6 +800,11 @@ def prof_read(name):
     ms = ctypes.c_double(0.0)
     check(lib().mvdb_prof_read(name.encode(), ctypes.byref(n), ctypes.byref(ms)))
     return n.value, ms.value
+
+
+def range_band(d, qnorm, row_norm_bound):
+    """Bound of |fp16 nomination score - fp32 score of the exact scans| in the shared range pass (include/mvdb.h: mvdb_range_band)."""
+    return float(lib().mvdb_range_band(int(d), float(qnorm), float(row_norm_bound)))
 
 
 def code8_margin(d, qnorm, qstep, row_norm_bound):

@@ -85,6 +85,9 @@ struct Knobs {
     bool shadow_single_query = false;  // MVDB_SHADOW_SINGLE_QUERY (1: single queries through the certified fp16-shadow pass too)
     bool code8_single_query = true;    // index option code8_single_query: single queries over large inner-product indexes through the int8 prefilter
     long long code8_capacity = 32768;  // index option code8_capacity: candidates the prefilter may hand to the exact re-score
+    int range_shared = 0;              // index option range_shared: batches of a range search on the shared fp16 pass (0 never — the default until the
+                                       // route has been timed, DESIGN.md section 6e —, 1 by size, 2 wherever eligible)
+    long long range_candidates = 0;    // index option range_candidates: candidates per query that pass holds (0: max(2 cap rounded up to a power of two, 4096))
     int grouped_items_per_cu = 0;      // MVDB_GROUPED_ITEMS_PER_CU: work items per CU the grouped launch aims at (0: the default of mvdb.hip plan_grouped; sweep in DESIGN.md section 6c)
     int grouped_min_batches = 4;       // MVDB_GROUPED_MIN_BATCHES: fewest row batches per wave of a work item
     long long compact_bytes = 512ll << 20;  // MVDB_COMPACT_BYTES: staging buffer of a row compaction (mvdb_index_remove_rows)

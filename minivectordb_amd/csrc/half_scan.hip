@@ -24,6 +24,8 @@
 //   flat_scan_h16_kernel<KT, KS, WV, NST, DEPTH>   the pass itself, over the shadow: 128 / 256 queries per pass (32 per wave),
 //       d = 128 .. 1024; DEPTH = 32: the rescue launch, which walks a LIST of tiles (rescue_tiles_kernel: the tiles the main launches
 //       flagged for its refused queries — HalfScanArgs::tflags — or every tile).  Algorithmic bytes per launch = rows scanned x d x 2.
+//   range_nominate_h16_kernel<KT, KS, WV, NST>   the same pipeline for a RANGE batch (mvdb_index_range_search*): a fixed floor per
+//       query instead of lists, candidate rows appended to per-query segments.  Algorithmic bytes per launch = rows x d x 2.
 //   flat_scan_seed_kernel<KQ, SKB, NG, NST>   the first launch of every pass: one 32-row tile of the fp32 rows per block (K
 //       split over four waves, partial score tiles exchanged through LDS), every score dumped — it only produces the floors.
 // (Retired in round 6: the forms of the pass that converted the fp32 rows on the fly — flat_scan_hq_kernel and the main-launch
@@ -676,6 +678,205 @@ static int launch_h16(int d, int nqpad, const HalfScanArgs& a, int device, hipSt
     return fail(MVDB_ERR_ARG, "no fp16-shadow kernel for %d queries per pass at d = %d", nqpad, d);
 }
 
+// ---- range search: the pass against a fixed floor ------------------------------------------------------------------------
+// flat_scan_h16_kernel's pipeline (whole-tile or part-tile stages DMA'd into the swizzled fragment image, NST stages in flight,
+// one bare barrier per stage, the queries' fragments in registers), with another gate: no lists, no running threshold.  Query
+// q of the wave keeps ONE register, its floor f_q = threshold_q - band_q; a (row, query) pair is a candidate unless its score
+// is provably below — !(a < f_q), so a NaN floor or score admits — and the row bitmap is looked at only where some lane is
+// about to admit.  A lane reserves room for all the candidates of its 16 rows of the tile with ONE atomic add on the query's
+// counter and stores the row numbers that still fit.  Once a lane has seen the counter pass the capacity it stops admitting
+// (floor := +inf): the query is answered by the exact scan then and neither its candidates nor its count are used.
+// ALGORITHMIC bytes per launch = rows x d x 2 + 4 per candidate.  No LDS beyond the ring.
+// NACC chains per tile: the KT MFMAs of a tile are cut into NACC runs of KT / NACC, each run accumulates from zero (one fp32
+// chain holds at most 16 KT / NACC products) and the runs' partial tiles are added up in order — that is what keeps the
+// band's accumulation term from growing with d (half_range_eps).  Two chain accumulators in turns and the running total: 48
+// registers whatever NACC is (one accumulator per chain spilled at d = 896 / 1024); the fold of chain c - 2 sits behind the
+// first MFMA of chain c, off the matrix cores' critical path.  NACC = 1 up to d = 512: one chain of d products, as before.
+template <int KT, int KS, int WV, int NST, int NACC>
+__global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeArgs a) {
+    static_assert(KT % NACC == 0, "whole MFMAs per accumulator");
+    constexpr int K = KT * 16;
+    constexpr int NSTG = KT / KS;
+    constexpr int HSL = KS * 2;
+    constexpr int kStage = 32 * HSL * 16;
+    constexpr int NP = kStage / 1024;
+    constexpr int DPW = NP / WV;
+    static_assert(KT % KS == 0 && HSL % 16 == 0 && NP % WV == 0 && DPW >= 1, "shape");
+    static_assert((NST - 1) * DPW <= 63, "vmcnt is a 6-bit counter");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // NST stages
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int fr = lane & 31, fk = lane >> 5;
+
+    hs_h8 Q[KT];
+#pragma unroll
+    for (int kb = 0; kb < KT; ++kb)
+        Q[kb] = *reinterpret_cast<const hs_h8*>(a.qf + (int64_t)(wave * 32 + fr) * K + kb * 16 + fk * 8);
+    const int myq = wave * 32 + fr;
+    const bool live = myq < a.nq;
+    float fl = live ? a.floors[myq] : INFINITY;
+    float inv = a.qinv[myq];
+    // consume every global load here: the hand-placed vmcnt waits below are invisible to hipcc (see flat_scan_seed_kernel)
+#pragma unroll
+    for (int kb = 0; kb < KT; ++kb) asm volatile("" : "+v"(Q[kb]));
+    asm volatile("" : "+v"(fl), "+v"(inv));
+    bool open = live;  // this lane still admits
+    unsigned long long* const ctr = a.ccount + (live ? myq : 0);
+    uint32_t* const seg = a.cand + (int64_t)(live ? myq : 0) * a.ccap;
+    const unsigned long long ccap = (unsigned long long)a.ccap;
+
+    const int64_t ntiles = (a.n + 31) / 32;
+    const int64_t last = a.n - 1;
+    uint32_t voff[DPW];
+#pragma unroll
+    for (int i = 0; i < DPW; ++i) {
+        const int j = (wave * DPW + i) * 64 + lane;
+        const int row = j / HSL, ps = j % HSL;
+        voff[i] = (uint32_t)(row * (K * 2) + ((ps ^ (row & 15)) << 4));
+    }
+    const int64_t step = gridDim.x;
+    int64_t tile = blockIdx.x;
+    // stage c of the block's flat sequence = (tile + (c / NSTG) step, K part c % NSTG); tiles past the end are clamped (re-reads
+    // nobody consumes: the loop body is branch-free and every counted wait sees a full ring)
+    auto issue_stage = [&](int64_t base, int c, int buf) {
+        int64_t t = base + (int64_t)(c / NSTG) * step;
+        t = t < ntiles ? t : (base < ntiles ? base : 0);
+        const char* sbase = reinterpret_cast<const char*>(a.Xh) + (t * 32 * (int64_t)K + (c % NSTG) * KS * 16) * 2;
+        unsigned char* dst = smem + buf * kStage + wave * DPW * 1024;
+#pragma unroll
+        for (int i = 0; i < DPW; ++i)
+            __builtin_amdgcn_global_load_lds((hs_gbl_ptr)(sbase + voff[i]), (hs_lds_ptr)(dst + i * 1024), 16, 0, 2 /* nt */);
+    };
+    const int frow = fr * HSL * 16;
+    const int fsw = fr & 15;
+    constexpr int CH = KT / NACC;  // MFMAs per chain
+    hs_f16 cur[NACC > 1 ? 2 : 1], total;
+    auto gate = [&](int64_t m0) {
+        // acc[e] is row (e & 3) + 8 (e >> 2) + 4 fk of the tile, query fr
+        hs_f16 acc = cur[0];
+        if constexpr (NACC > 1) {   // the last two chains are still on their own
+            acc = total + cur[NACC & 1];
+            acc += cur[(NACC - 1) & 1];
+        }
+        uint32_t hit = 0u;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) hit |= (!(acc[e] * inv < fl) ? 1u : 0u) << ((e & 3) + 8 * (e >> 2));  // (the product is exact: a power of two)
+        if (__ballot(open && hit != 0u) == 0ull) return;
+        // slow path: rows past the corpus and rows outside the set drop out, what is left is admitted
+        const uint32_t mw = a.mask ? a.mask[m0 >> 5] : 0xffffffffu;  // the tile's 32 rows = one word of the bitmap
+        const int64_t left = last - m0;                              // >= 0: rows m0 .. m0 + left exist
+        const uint32_t inside = left >= 31 ? 0xffffffffu : (2u << (int)left) - 1u;
+        hit = open ? ((hit << (4 * fk)) & mw & inside) : 0u;
+        const int c = __popc(hit);
+        if (c) {
+            unsigned long long at = atomicAdd(ctr, (unsigned long long)c);
+            if (at + (unsigned long long)c > ccap) {
+                open = false;
+                fl = INFINITY;
+            }
+            while (hit) {
+                const int b = __ffs(hit) - 1;
+                hit &= hit - 1;
+                if (at < ccap) seg[at] = (uint32_t)(m0 + b);
+                ++at;
+            }
+        }
+    };
+
+    if (tile < ntiles) {
+#pragma unroll
+        for (int c = 0; c < NST - 1; ++c) issue_stage(tile, c, c);
+    }
+    int buf = 0;
+    while (tile < ntiles) {
+        const int64_t m0 = tile * 32;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) total[e] = 0.f;
+#pragma unroll
+        for (int sg = 0; sg < NSTG; ++sg) {
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * DPW) : "memory");  // this wave's pieces of the stage have landed
+            __builtin_amdgcn_s_barrier();  // everybody's have; and every wave is done reading the stage before
+            __builtin_amdgcn_sched_barrier(0);
+            const int abuf = buf == 0 ? NST - 1 : buf - 1;  // the look-ahead stage goes into the buffer of the stage before
+            issue_stage(tile, sg + NST - 1, abuf);
+            __builtin_amdgcn_sched_barrier(0);
+            const unsigned char* src = smem + buf * kStage + frow;
+            auto frag = [&](int kb) { return *reinterpret_cast<const hs_h8*>(src + (((2 * kb + fk) ^ fsw) << 4)); };
+            constexpr int AHEAD = KS < 6 ? KS : (KT >= 64 ? 3 : 6);  // (d = 1024: 256 registers of query fragments leave room for three)
+            hs_h8 f[AHEAD + 1];
+#pragma unroll
+            for (int u = 0; u < AHEAD; ++u) f[u] = frag(u);
+#pragma unroll
+            for (int kb = 0; kb < KS; ++kb) {
+                if (kb + AHEAD < KS) f[(kb + AHEAD) % (AHEAD + 1)] = frag(kb + AHEAD);
+                const int m = sg * KS + kb, c = m / CH;   // (compile-time after unrolling)
+                if (m % CH == 0) {
+                    if (c >= 2) total += cur[c & 1];      // chain c - 2, finished CH MFMAs ago
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) cur[c & 1][e] = 0.f;
+                }
+                cur[c & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[kb % (AHEAD + 1)], Q[sg * KS + kb], cur[c & 1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
+#pragma unroll
+            for (int kb = 0; kb < KS; ++kb) {
+                if (kb + AHEAD < KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the fragments are in registers before the buffer may be refilled)
+            buf = buf == NST - 1 ? 0 : buf + 1;
+        }
+        gate(m0);
+        tile += step;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped look-ahead DMAs must land before the LDS is released
+}
+
+template <int KT, int KS, int WV, int NST, int BPC = 1>
+static int launch_range_h16_inst(const HalfRangeArgs& a, int device, hipStream_t stream) {
+    constexpr int NACC = KT <= 32 ? 1 : KT / 8;   // d <= 512: one chain of d products; wider: chains of 128 (half_range_eps)
+    auto kern = range_nominate_h16_kernel<KT, KS, WV, NST, NACC>;
+    constexpr size_t lds = (size_t)NST * 32 * KS * 2 * 16;
+    static_assert(BPC * lds <= 160 * 1024, "LDS budget of a CU");
+    {
+        static std::mutex mu;
+        static std::map<int, bool> done;
+        std::lock_guard<std::mutex> lk(mu);
+        if (!done[device]) {
+            MVDB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            done[device] = true;
+        }
+    }
+    const int64_t ntiles = (a.n + 31) / 32;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * BPC));
+    prof_symbol("ip_scan_range_half", "range_nominate_h16_kernel<%d, %d, %d, %d, %d>", KT, KS, WV, NST, NACC);
+    int slot = prof_begin("ip_scan_range_half", stream);
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WV * 64), lds, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// the shapes of launch_h16 (the ring and the workgroups per CU measured for the certified pass: the stream is the same)
+int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream) {
+    const bool wide = nqpad == 256;
+    if ((nqpad != 128 && nqpad != 256) || a.n <= 0) return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass", nqpad);
+    switch (d) {
+        case 128: return wide ? launch_range_h16_inst<8, 8, 8, 4>(a, device, stream) : launch_range_h16_inst<8, 8, 4, 4, 2>(a, device, stream);
+        case 256: return wide ? launch_range_h16_inst<16, 16, 8, 4>(a, device, stream) : launch_range_h16_inst<16, 16, 4, 4, 2>(a, device, stream);
+        case 384: return wide ? launch_range_h16_inst<24, 24, 8, 4>(a, device, stream) : launch_range_h16_inst<24, 24, 4, 2, 2>(a, device, stream);
+        case 512: return wide ? launch_range_h16_inst<32, 32, 8, 3>(a, device, stream) : launch_range_h16_inst<32, 32, 4, 2, 2>(a, device, stream);
+        case 640: if (!wide) return launch_range_h16_inst<40, 40, 4, 3>(a, device, stream); break;
+        case 768: if (!wide) return launch_range_h16_inst<48, 48, 4, 3>(a, device, stream); break;
+        case 896: if (!wide) return launch_range_h16_inst<56, 56, 4, 2>(a, device, stream); break;
+        case 1024: if (!wide) return launch_range_h16_inst<64, 64, 4, 2>(a, device, stream); break;
+        default: break;
+    }
+    return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass at d = %d", nqpad, d);
+}
+
 // ---- the rescue pass (round 5) -----------------------------------------------------------------------------------------
 // A refused query is not an unknown one: half_certify_kernel has re-scored its 64 nominees exactly, and the k-th of those scores,
 // t, bounds the k-th result from below.  Every row of the top k therefore has an APPROXIMATE score >= t - margin - eps |q| =: f.
@@ -1020,6 +1221,29 @@ double half_eps(int d) {
     const double depth = ((d + 3) / 4 + 63) / 64 * 4 + 6;
     const double e_re = depth * u24 / (1.0 - depth * u24);
     return (e_op + e_uf + e_acc + e_re) * (1.0 + 4e-6) + 4.0 * u24;
+}
+
+// The band of the shared range pass: |a(x) - s(x)| per unit |q| max|x|, a(x) the nomination score of range_nominate_h16_kernel
+// and s(x) the fp32 score of the exact scans (range_scan_kernel / range_rescore_kernel = flat_scan_kernel's arithmetic).
+//   (1), (2) of half_eps: operand rounding and fp16 underflow, unchanged.
+//   (3) accumulation on the matrix cores: the kernel adds at most `chain` = min(d, 128 for d > 512) products into one fp32
+//       accumulator — in ANY order, every addition rounded or truncated (unit 2^-23) — and then the d / chain <= 8 partial sums
+//       in order: gamma(chain + 8), each chain's error relative to its own share of sum |q_i x_i|.
+//   (4) the other side is the SCAN's sum, not the certify kernel's: lane t of G takes C chunks (4 C fmaf), then log2 G butterfly
+//       additions — depth 4 C + log2 G, round to nearest.  For the shadow widths choose_shape gives (32, 1) (64, 1) (32, 3)
+//       (64, 2) (64, 3) (64, 3) (64, 4) (64, 4) at d = 128 ... 1024: depth <= 4 ceil(d / 128) + 6 (term (4) of half_eps,
+//       4 ceil(d / 256) + 6, is too small at d = 384).  This term does NOT cover other fp32 summation orders.
+//   Then |q| in fp32 and the floor's own arithmetic.
+static int half_range_chain(int d) { return d <= 512 ? d : 128; }
+double half_range_eps(int d) {
+    const double u11 = std::ldexp(1.0, -11), u23 = std::ldexp(1.0, -23), u24 = std::ldexp(1.0, -24);
+    const double e_op = 2.0 * u11 + u11 * u11;
+    const double e_uf = std::sqrt((double)d) * std::ldexp(1.0, -27) * (1.0 + u11) + d * std::ldexp(1.0, -56);
+    const double n = half_range_chain(d) + 8.0;
+    const double e_acc = n * u23 / (1.0 - n * u23) * (1.0 + u11) * (1.0 + u11);
+    const double depth = (d + 127) / 128 * 4 + 6;
+    const double e_scan = depth * u24 / (1.0 - depth * u24);
+    return (e_op + e_uf + e_acc + e_scan) * (1.0 + 1e-5) + 4.0 * u24;
 }
 
 // s_x = 2^(15 - e) with bound = m 2^e, m in [0.5, 1): every corpus element times s_x is below 2^15.

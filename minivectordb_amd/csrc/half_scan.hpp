@@ -121,11 +121,32 @@ int launch_rescue_tiles(const RescueTilesArgs& a, int slots, hipStream_t stream)
 int launch_half_rescue_certify(const HalfRescueArgs& a, hipStream_t stream);
 bool half_rescue_dim(int d);
 
+// ---- range search, shared pass (mvdb_index_range_search*, inner product): nomination against a FIXED per-query floor ----------
+// One launch streams the shadow once for up to 128 / 256 queries; a (row, query) pair whose nomination score is not provably
+// below floors[q] = threshold - band is a candidate: its row number goes to the query's candidate segment.  The counter keeps
+// counting past the capacity — only the store is suppressed — so a segment that overflowed is recognisable (count > ccap; its
+// count is then a lower bound only: a lane that has seen the overflow stops reporting).
+struct HalfRangeArgs {
+    const _Float16* Xh;   // the fp16 shadow, [n + slack][d]
+    const _Float16* qf;   // [nqpad][d] fp16 query images (half_queries_kernel)
+    const float* qinv;    // [nqpad]
+    const float* floors;  // [nq] admission floor per query (NaN / -inf: every row is a candidate)
+    int nq;
+    int64_t n;            // rows [0, n) may be candidates
+    const uint32_t* mask; // NULL, or one bit per row
+    uint32_t* cand;       // [nq][ccap] candidate rows, in no defined order
+    int64_t ccap;
+    unsigned long long* ccount;  // [nq] zeroed by the caller
+};
+int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream);
+
 // queries per corpus pass of the widest instantiation for dimension d (0: no kernel for this d)
 int half_max_queries(int d);
 // queries per pass the launcher will use for a chunk of `nq` queries (a multiple of 32 * d / 128)
 int half_chunk_queries(int d, int nq);
 double half_eps(int d);
+// per unit |q| max|x|: bound on |range nomination score - the fp32 score of the exact scans| (the band of the shared range pass)
+double half_range_eps(int d);
 float half_xscale(float row_norm_bound);
 
 int launch_half_queries(const float* q, int64_t ld, int d, int nq, int nqpad, float xscale, _Float16* qf, float* qnorm,

@@ -215,6 +215,9 @@ struct Workspace {
     // behind the upload — the staging copy is rewritten only once the upload that reads it has run
     DevBuf<uint64_t> rkeys;             // range search: [nq, segment] appended keys (range_scan.hpp)
     DevBuf<unsigned long long> rcounts;  // ... and the host entry point's per-query counters
+    DevBuf<uint32_t> rcand;              // range search, shared pass: [nq, capacity] candidate rows ...
+    DevBuf<unsigned long long> rccount;  // ... and their per-query counters
+    DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter, gate, seed results, candidates, row list
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -257,6 +260,9 @@ struct Workspace {
         pin.release();
         rkeys.release();
         rcounts.release();
+        rcand.release();
+        rccount.release();
+        rthr.release();
         gtab.release();
         c8.release();
         for (GroupedStage* g : gstage) {
@@ -338,6 +344,11 @@ struct mvdb_index {
     mutable std::atomic<unsigned int> c8_calls{0}, c8_window_calls{0}, c8_window_fail{0};
     mutable std::atomic<int> c8_suspend_left{0};
     mutable std::atomic<unsigned long long> c8_suspensions{0};
+    // range search, shared pass (range_shared_phase): a running count of queries its fallback answered, mirrored with the
+    // candidates of the latest launch group into host-mapped words; calls that took the route are counted on the host
+    mutable unsigned int* rg_ctr_dev = nullptr;
+    mutable PinnedBuf rg_stats;
+    mutable std::atomic<unsigned long long> rg_shared_calls{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -2197,9 +2208,13 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     const bool code8 = idx->kn.code8_single_query;   // (options without an environment switch: kept)
     const long long code8_cap = idx->kn.code8_capacity;
+    const int range_shared = idx->kn.range_shared;
+    const long long range_cand = idx->kn.range_candidates;
     idx->kn = read_knobs();
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
+    idx->kn.range_shared = range_shared;
+    idx->kn.range_candidates = range_cand;
     return 0;
 }
 
@@ -2221,13 +2236,19 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "code8_capacity") {  // diagnostic: a small candidate capacity makes calls take the fallback
         if (value <= 0 || value > kCode8MaxCapacity) return fail(MVDB_ERR_ARG, "code8_capacity must lie in [1, %lld]", (long long)kCode8MaxCapacity);
         idx->kn.code8_capacity = value;
+    } else if (n == "range_shared") {  // batches of a range search on the shared fp16 pass: 0 never, 1 by size, 2 wherever eligible
+        if (value < 0 || value > 2) return fail(MVDB_ERR_ARG, "range_shared must be 0, 1 or 2");
+        idx->kn.range_shared = (int)value;
+    } else if (n == "range_candidates") {  // candidates per query the shared pass holds (0: by cap); a small value forces the fallback
+        if (value != 0 && (value < 64 || value > (1ll << 20))) return fail(MVDB_ERR_ARG, "range_candidates must be 0 or lie in [64, 2^20]");
+        idx->kn.range_candidates = value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, range_shared, range_candidates, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2252,6 +2273,8 @@ int mvdb_index_free(mvdb_index* idx) {
         drop_code8(idx);
         if (idx->c8_ctr_dev) (void)hipFree(idx->c8_ctr_dev);
         idx->c8_stats.release();
+        if (idx->rg_ctr_dev) (void)hipFree(idx->rg_ctr_dev);
+        idx->rg_stats.release();
         for (Workspace* w : idx->free_ws) {
             w->destroy();
             delete w;
@@ -2303,6 +2326,18 @@ int mvdb_index_code8_counters(const mvdb_index* idx, long long* fallbacks, long 
     if (last_candidates) *last_candidates = st ? (long long)st[1] : 0;
     if (calls) *calls = st ? (long long)st[2] : 0;
     return 0;
+}
+int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries, long long* last_candidates) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    const volatile unsigned long long* st = reinterpret_cast<const volatile unsigned long long*>(idx->rg_stats.p);
+    if (shared_calls) *shared_calls = (long long)idx->rg_shared_calls.load();
+    if (fallback_queries) *fallback_queries = st ? (long long)st[0] : 0;
+    if (last_candidates) *last_candidates = st ? (long long)st[1] : 0;
+    return 0;
+}
+double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
+    if (d <= 0 || !(qnorm >= 0.f) || !(row_norm_bound >= 0.f)) return INFINITY;
+    return half_range_eps(d) * (double)qnorm * (double)row_norm_bound;
 }
 int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta) {
     if (d <= 0 || !alpha || !beta) return fail(MVDB_ERR_ARG, "mvdb_code8_margin: bad arguments");
@@ -3083,8 +3118,11 @@ int launch_range_kern(const RangeScanArgs& a, int nq, int device, hipStream_t st
     const int64_t nbatches = (a.n + RB - 1) / RB;
     const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * occ));
-    prof_symbol("ip_scan_range", "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
-    int slot = prof_begin("ip_scan_range", stream);
+    // (the gated launch of the shared pass runs under a label of its own: a profile tells the scans that were asked for from
+    //  the launches that return at once)
+    const char* label = a.gate_count ? "ip_scan_range_fallback" : "ip_scan_range";
+    prof_symbol(label, "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
+    int slot = prof_begin(label, stream);
     hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a);
     prof_end(slot, stream);
     MVDB_HIP(hipGetLastError());
@@ -3148,6 +3186,234 @@ int launch_range(int metric, const RangeScanArgs& a, int nq, int device, hipStre
 
 constexpr int kRangeTile = 1024;  // queries of one range launch (a call of more is answered that many at a time)
 
+// ---- the shared pass of a range batch (inner product): nomination over the fp16 shadow, exact re-score, gated fallback ----------
+template <int G, int C, int U>
+int launch_rescore_gcu(const RangeRescoreArgs& a, int nq, int device, hipStream_t s) {
+    constexpr bool kAlwaysFull = G == 32 && C > 1;
+    const bool masked = !kAlwaysFull && a.d4 != G * C;
+    void (*kern)(RangeRescoreArgs);
+    if constexpr (kAlwaysFull) {
+        kern = range_rescore_kernel<G, C, U, false>;
+    } else {
+        kern = masked ? range_rescore_kernel<G, C, U, true> : range_rescore_kernel<G, C, U, false>;
+    }
+    // blocks per query: enough for a full candidate segment at a few batches per wave, no more than the device holds at once
+    constexpr int RB = (kWave / G) * U;
+    const int64_t want = (a.ccap + (int64_t)RB * kScanWaves * 4 - 1) / ((int64_t)RB * kScanWaves * 4);
+    const int64_t room = std::max<int64_t>(1, (int64_t)device_cus(device) * 8 / nq);
+    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, room));
+    prof_symbol("ip_scan_range_rescore", "range_rescore_kernel<%d, %d, %d, %s>", G, C, U, masked ? "true" : "false");
+    int slot = prof_begin("ip_scan_range_rescore", s);
+    hipLaunchKernelGGL(kern, dim3(gx, nq), dim3(kScanThreads), 0, s, a);
+    prof_end(slot, s);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_rescore(const RangeRescoreArgs& a, int nq, int device, hipStream_t s) {
+    const Shape sh = choose_shape(a.d4);
+#define MVDB_RESCORE_CASE(G_, C_, U_) \
+    if (sh.G == G_ && sh.C == C_) return launch_rescore_gcu<G_, C_, U_>(a, nq, device, s);
+    MVDB_RESCORE_CASE(16, 1, 4)
+    MVDB_RESCORE_CASE(32, 1, 4)
+    MVDB_RESCORE_CASE(32, 3, 4)
+    MVDB_RESCORE_CASE(64, 1, 4)
+    MVDB_RESCORE_CASE(64, 2, 4)
+    MVDB_RESCORE_CASE(64, 3, 4)
+    MVDB_RESCORE_CASE(64, 4, 2)
+    MVDB_RESCORE_CASE(64, 5, 2)
+    MVDB_RESCORE_CASE(64, 6, 2)
+    MVDB_RESCORE_CASE(64, 7, 2)
+    MVDB_RESCORE_CASE(64, 8, 2)
+    MVDB_RESCORE_CASE(64, 16, 1)
+#undef MVDB_RESCORE_CASE
+    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+}
+
+// floors[i] = threshold_i - coef |q_i|, rounded down (a NaN or -inf floor admits every row: the query overflows or is decided
+// by the exact re-score)
+__global__ void range_floor_kernel(const float* __restrict__ thrs, float thr, const float* __restrict__ qnorm, float coef, int nq,
+                                   float* __restrict__ floors) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float t = thrs ? thrs[i] : thr;
+    floors[i] = nextafterf(t - coef * qnorm[i], -INFINITY);
+}
+
+// diagnostics of one launch group: queries whose candidates overflowed (added to the running count), candidates held
+__global__ __launch_bounds__(256) void range_stats_kernel(const unsigned long long* __restrict__ ccount, unsigned long long ccap, int nq,
+                                                          unsigned int* ctr, volatile unsigned long long* host) {
+    __shared__ unsigned long long sh[2][4];
+    unsigned long long nf = 0, nc = 0;
+    for (int i = threadIdx.x; i < nq; i += 256) {
+        const unsigned long long c = ccount[i];
+        nf += c > ccap;
+        nc += c > ccap ? 0ull : c;
+    }
+    for (int off = 32; off; off >>= 1) {
+        nf += __shfl_xor(nf, off);
+        nc += __shfl_xor(nc, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = nf;
+        sh[1][threadIdx.x >> 6] = nc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        nf = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+        nc = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+        const unsigned int total = atomicAdd(ctr, (unsigned int)nf) + (unsigned int)nf;
+        host[0] = total;
+        host[1] = nc;
+    }
+}
+
+// the route's own zeroing and query copy: kernels, so that a captured call holds kernel nodes only
+__global__ void range_zero_kernel(unsigned long long* __restrict__ a, unsigned long long* __restrict__ b, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        a[i] = 0ull;
+        b[i] = 0ull;
+    }
+}
+__global__ void range_copy_kernel(const float* __restrict__ src, int64_t n, float* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+__global__ void negate_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = -src[i];
+}
+
+// Fewest queries of a range call that take the shared pass (option range_shared = 1).  The certified top-k pass, whose cost
+// structure this pass shares — one stream of the shadow per 128 / 256 queries against one stream of the fp32 rows per query —
+// starts at 2 queries from 500k rows and at 8 from 100k (half_min_nq); those crossovers were measured for ANOTHER kernel, and
+// the batch cells of benchmarks/bench_range.py have not been timed yet.  Until they are, the rule keeps to the batches where
+// arithmetic alone decides: 33+ queries replace 33+ fp32 passes by one pass over half the bytes.
+int range_shared_min_nq(int64_t n) {
+    (void)n;
+    return 33;
+}
+
+// the counters of the route: allocated with the first call that takes it, never inside a capture
+bool ensure_range_stats(const mvdb_index* idx, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(idx->shadow_mu);
+    if (idx->rg_ctr_dev) return true;
+    if (stream_capturing(s)) return false;
+    unsigned int* p = nullptr;
+    if (hipMalloc((void**)&p, sizeof(unsigned int)) != hipSuccess || hipMemset(p, 0, sizeof(unsigned int)) != hipSuccess ||
+        idx->rg_stats.reserve(64) != 0) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        return false;
+    }
+    memset(idx->rg_stats.p, 0, 64);
+    idx->rg_ctr_dev = p;
+    return true;
+}
+
+// Does this launch group go through the shared pass?  Inner product, a batch, every row or a bitmap-form set, an index that
+// meets the certified pass's shadow conditions (half_path_ok: a width with a shadow kernel, unpadded rows, rows of known finite
+// norm), and a shadow that exists or may be built now (never while the stream is capturing).
+const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq, const mvdb_rowset* rs, int64_t n) {
+    const int mode = idx->kn.range_shared;
+    if (mode == 0 || nq < 2 || n <= 0 || idx->metric != MVDB_METRIC_IP || (rs && !rs->mask) || !half_path_ok(idx)) return nullptr;
+    if (mode == 1 && nq < range_shared_min_nq(n)) return nullptr;
+    {   // the band (half_range_eps) bounds the scan's sum by its depth, 4 C + log2 G <= 4 ceil(d / 128) + 6: hold the shape to it
+        const Shape sh = choose_shape(idx->d4);
+        int lg = 0;
+        while ((1 << lg) < sh.G) ++lg;
+        if (4 * sh.C + lg > (idx->d + 127) / 128 * 4 + 6) return nullptr;
+    }
+    const _Float16* Xh = ensure_shadow(idx, ws->stream, half_xscale(idx->row_norm_bound));
+    if (!Xh || !ensure_range_stats(idx, ws->stream)) return nullptr;
+    return Xh;
+}
+
+// The three stages on the call's stream, no host synchronisation: (a) per 128 / 256 queries one nomination launch over the
+// shadow against the floors threshold_i - band_i; (b) the exact re-score of the candidates appends the passing keys; (c) the
+// thresholded scan, enabled per query on the device, answers the queries whose candidates overflowed.  `a`: the arguments the
+// per-query route would launch with.
+int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh, RangeScanArgs a, int nq) {
+    hipStream_t s = ws->stream;
+    const int chunk = half_max_queries(idx->d);
+    int64_t ccap = idx->kn.range_candidates > 0 ? idx->kn.range_candidates : std::max<int64_t>(pow2ceil(std::max<int64_t>(2 * a.cap, 2)), 4096);
+    ccap = std::max<int64_t>(64, std::min<int64_t>(ccap, 1ll << 20));
+    ccap = std::min<int64_t>(ccap, (256ll << 20) / 4 / nq);  // the candidate workspace stays at or below 256 MiB (nq <= 1024: >= 65536)
+    MVDB_TRY(ws->rcand.reserve((size_t)nq * (size_t)ccap));
+    MVDB_TRY(ws->rccount.reserve((size_t)nq));
+    MVDB_TRY(ws->qsplit.reserve((size_t)std::max(2 * 128, chunk) * idx->d));
+    MVDB_TRY(ws->qnorm.reserve((size_t)std::max(256, 3 * chunk)));
+    hipLaunchKernelGGL(range_zero_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, a.counts, ws->rccount.p, nq);
+    MVDB_HIP(hipGetLastError());
+    // the nomination reads the queries as the certified pass does: normalised by the row normaliser where the call asks for
+    // it.  The re-score normalises inside its prologue (the scan's own arithmetic).  Both sum the squares per lane and over a
+    // butterfly — depth 4 C + log2 G <= 38 at the shadow widths — and multiply by 1 / sqrt: each image is within
+    // ((depth + 1) / 2 + 3) 2^-24 of the real-number one, the two within (depth + 7) 2^-24 of each other, element by element.
+    // The band carries (d + 8) 2^-24, which would cover sums of squares taken in ANY order
+    // (tests/test_range_batch_cpu.py: test_allowance_for_the_two_normalised_query_images).
+    const float* qsrc = a.q;
+    double extra = 0.0;
+    if (a.normalize_q) {
+        MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
+        const int64_t total = (int64_t)nq * idx->ld;
+        hipLaunchKernelGGL(range_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.q, total, ws->qn.p);
+        MVDB_HIP(hipGetLastError());
+        MVDB_TRY(normalize_range(idx, ws->qn.p, nq, s));
+        qsrc = ws->qn.p;
+        extra = (idx->d + 8.0) * std::ldexp(1.0, -24);
+    }
+    const float coef = (float)((half_range_eps(idx->d) + extra) * (double)idx->row_norm_bound * (1.0 + 1e-6));
+    const float xscale = half_xscale(idx->row_norm_bound);
+    _Float16* qf = reinterpret_cast<_Float16*>(ws->qsplit.p);
+    for (int c0 = 0; c0 < nq; c0 += chunk) {
+        const int take = std::min(chunk, nq - c0);
+        const int nqpad = half_chunk_queries(idx->d, take);
+        float* qnorm = ws->qnorm.p;
+        float* floors = qnorm + nqpad;
+        float* qinv = qnorm + 2 * nqpad;
+        MVDB_TRY(launch_half_queries(qsrc + (int64_t)c0 * idx->ld, idx->ld, idx->d, take, nqpad, xscale, qf, qnorm, qinv, s));
+        hipLaunchKernelGGL(range_floor_kernel, dim3((take + 255) / 256), dim3(256), 0, s, a.thrs ? a.thrs + c0 : nullptr, a.thr, qnorm,
+                           coef, take, floors);
+        MVDB_HIP(hipGetLastError());
+        HalfRangeArgs h;
+        h.Xh = Xh;
+        h.qf = qf;
+        h.qinv = qinv;
+        h.floors = floors;
+        h.nq = take;
+        h.n = a.n;
+        h.mask = reinterpret_cast<const uint32_t*>(a.mask);
+        h.cand = ws->rcand.p + (size_t)c0 * (size_t)ccap;
+        h.ccap = ccap;
+        h.ccount = ws->rccount.p + c0;
+        MVDB_TRY(launch_half_range(idx->d, nqpad, h, idx->device, s));
+    }
+    RangeRescoreArgs r;
+    r.X = a.X;
+    r.ld = a.ld;
+    r.d4 = a.d4;
+    r.q = a.q;
+    r.normalize_q = a.normalize_q;
+    r.thr = a.thr;
+    r.thrs = a.thrs;
+    r.cand = ws->rcand.p;
+    r.ccap = ccap;
+    r.ccount = ws->rccount.p;
+    r.keys = a.keys;
+    r.seg = a.seg;
+    r.cap = a.cap;
+    r.counts = a.counts;
+    MVDB_TRY(launch_rescore(r, nq, idx->device, s));
+    hipLaunchKernelGGL(range_stats_kernel, dim3(1), dim3(256), 0, s, ws->rccount.p, (unsigned long long)ccap, nq, idx->rg_ctr_dev,
+                       (volatile unsigned long long*)idx->rg_stats.p);
+    MVDB_HIP(hipGetLastError());
+    a.gate_count = ws->rccount.p;
+    a.gate_cap = (unsigned long long)ccap;
+    return launch_range(idx->metric, a, nq, idx->device, s);
+}
+
 int check_range_args(const mvdb_index* idx, const void* q, int nq, float threshold, int64_t cap, const void* counts, const void* D,
                      const void* I) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
@@ -3161,12 +3427,13 @@ int check_range_args(const mvdb_index* idx, const void* q, int nq, float thresho
 
 // zero the counters and run the thresholded scan: counts[i] = passing rows of query i, keys[i * seg ...] the first `cap` of
 // them in no defined order.  *rows_out: the row list the keys' positions refer to (NULL: they are row numbers).
-int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int nq, float threshold, int normalize_q,
-                     const mvdb_rowset* rs, int64_t cap, int64_t seg, unsigned long long* counts, const int64_t** rows_out) {
+// thrs: NULL, or the queries' own thresholds on the device in the units of the keys (L2: negated).  *shared: the launch group
+// took the shared pass.
+int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int nq, float threshold, const float* thrs, int normalize_q,
+                     const mvdb_rowset* rs, int64_t cap, int64_t seg, unsigned long long* counts, const int64_t** rows_out, bool* shared) {
     KnobScope knobs(&idx->kn);
     hipStream_t s = ws->stream;
     MVDB_TRY(ws->rkeys.reserve((size_t)nq * (size_t)seg));
-    MVDB_HIP(hipMemsetAsync(counts, 0, (size_t)nq * sizeof(unsigned long long), s));
     RangeScanArgs a;
     a.X = idx->X;
     a.ld = idx->ld;
@@ -3174,6 +3441,7 @@ int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int n
     a.q = q;
     a.normalize_q = normalize_q;
     a.thr = idx->metric == MVDB_METRIC_IP ? threshold : -threshold;  // the key's score of an L2 row is -distance
+    a.thrs = thrs;
     a.rows = nullptr;
     a.mask = nullptr;
     a.n = idx->n;
@@ -3191,6 +3459,13 @@ int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int n
     a.cap = cap;
     a.counts = counts;
     *rows_out = a.rows;
+    if (a.n > 0) {
+        if (const _Float16* Xh = range_shared_route(idx, ws, nq, rs, a.n)) {
+            *shared = true;
+            return range_shared_phase(idx, ws, Xh, a, nq);   // (zeroes the counters itself)
+        }
+    }
+    MVDB_HIP(hipMemsetAsync(counts, 0, (size_t)nq * sizeof(unsigned long long), s));
     if (a.n == 0) return 0;
     return launch_range(idx->metric, a, nq, idx->device, s);
 }
@@ -3220,12 +3495,12 @@ int range_emit_phase(const mvdb_index* idx, Workspace* ws, int nq, int64_t seg, 
 }
 
 // host entry point, one tile of queries already staged in ws->q
-int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshold, int normalize_q, const mvdb_rowset* rs,
-                    int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshold, const float* thrs, int normalize_q, const mvdb_rowset* rs,
+                    int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host, bool* shared) {
     const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
     MVDB_TRY(ws->rcounts.reserve((size_t)nq));
     const int64_t* rows = nullptr;
-    MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, normalize_q, rs, cap, seg, ws->rcounts.p, &rows));
+    MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, thrs, normalize_q, rs, cap, seg, ws->rcounts.p, &rows, shared));
     // the counts come back first: the sort and the copy are sized by what is there, not by the capacity
     MVDB_TRY(ws->pin_out.reserve((size_t)nq * sizeof(unsigned long long)));
     hipError_t e = hipMemcpyAsync(ws->pin_out.p, ws->rcounts.p, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream);
@@ -3270,28 +3545,48 @@ int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshol
 
 extern "C" {
 
-int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, float threshold, int normalize_q,
-                            const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+// thresholds_host: NULL (every query under `threshold`), or one per query
+static int range_search_host(const mvdb_index* idx, const float* q_host, int nq, float threshold, const float* thresholds_host,
+                             int normalize_q, const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
     MVDB_TRY(check_range_args(idx, q_host, nq, threshold, cap, counts_host, D_host, I_host));
+    if (thresholds_host)
+        for (int i = 0; i < nq; ++i)
+            if (thresholds_host[i] != thresholds_host[i]) return fail(MVDB_ERR_ARG, "threshold %d is NaN", i);
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     if (rs) MVDB_TRY(rowset_check(idx, rs));
     DeviceGuard dg(idx->device);
     Workspace* ws = idx->acquire();
     if (!ws) return MVDB_ERR_HIP;
     int rc = 0;
+    bool shared = false;
+    std::vector<float> tkeys;  // the thresholds in the units of the keys
     for (int t0 = 0; t0 < nq && !rc; t0 += kRangeTile) {
         const int take = std::min(kRangeTile, nq - t0);
         if ((rc = stage_queries(idx, ws, q_host + (size_t)t0 * idx->d, take))) break;
-        rc = range_host_tile(idx, ws, take, threshold, normalize_q, rs, cap, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
-                             cap ? I_host + (size_t)t0 * cap : nullptr);
+        const float* thrs = nullptr;
+        if (thresholds_host) {
+            tkeys.assign(thresholds_host + t0, thresholds_host + t0 + take);
+            if (idx->metric != MVDB_METRIC_IP)
+                for (float& v : tkeys) v = -v;
+            if ((rc = ws->rthr.reserve((size_t)take))) break;
+            // (pageable memory: the copy has left the host buffer when the call returns)
+            if (hipMemcpyAsync(ws->rthr.p, tkeys.data(), (size_t)take * sizeof(float), hipMemcpyHostToDevice, ws->stream) != hipSuccess) {
+                rc = fail(MVDB_ERR_HIP, "range search: the thresholds' upload failed");
+                break;
+            }
+            thrs = ws->rthr.p;
+        }
+        rc = range_host_tile(idx, ws, take, threshold, thrs, normalize_q, rs, cap, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
+                             cap ? I_host + (size_t)t0 * cap : nullptr, &shared);
     }
+    if (shared) idx->rg_shared_calls.fetch_add(1);
     idx->release(ws);
     return rc;
 }
 
-int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, int nq, float threshold, int normalize_q,
-                                   const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev, float* D_dev,
-                                   int64_t* I_dev, void* stream) {
+static int range_search_dev(const mvdb_index* idx, const float* q_dev, int nq, float threshold, const float* thresholds_dev,
+                            int normalize_q, const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev, float* D_dev,
+                            int64_t* I_dev, void* stream) {
     MVDB_TRY(check_range_args(idx, q_dev, nq, threshold, cap, counts_dev, D_dev, I_dev));
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     if (rs) MVDB_TRY(rowset_check(idx, rs));
@@ -3309,19 +3604,53 @@ int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, in
         MVDB_HIP(hipGetLastError());
         q = ws->q.p;
     }
+    const float* thrs = thresholds_dev;
+    if (thrs && idx->metric != MVDB_METRIC_IP) {  // the key's score of an L2 row is -distance
+        MVDB_TRY(ws->rthr.reserve((size_t)nq));
+        hipLaunchKernelGGL(negate_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ws->stream, thresholds_dev, nq, ws->rthr.p);
+        MVDB_HIP(hipGetLastError());
+        thrs = ws->rthr.p;
+    }
     // Nothing below reads from the device: the sort is sized by the capacity (each block looks its query's count up and
     // sorts no more than that), so the call may be captured once an eager call of the same shape has sized the workspace.
     const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
+    bool shared = false;
     for (int t0 = 0; t0 < nq; t0 += kRangeTile) {
         const int take = std::min(kRangeTile, nq - t0);
         unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + t0;
         const int64_t* rows = nullptr;
-        MVDB_TRY(range_scan_phase(idx, ws, q + (size_t)t0 * idx->ld, take, threshold, normalize_q, rs, cap, seg, counts, &rows));
+        MVDB_TRY(range_scan_phase(idx, ws, q + (size_t)t0 * idx->ld, take, threshold, thrs ? thrs + t0 : nullptr, normalize_q, rs, cap, seg,
+                                  counts, &rows, &shared));
         if (cap == 0) continue;
         MVDB_TRY(range_sort_phase(ws, take, seg, cap, seg, counts));
         MVDB_TRY(range_emit_phase(idx, ws, take, seg, cap, cap, counts, rows, label_offset, D_dev + (size_t)t0 * cap, I_dev + (size_t)t0 * cap));
     }
+    if (shared) idx->rg_shared_calls.fetch_add(1);
     return 0;
+}
+
+int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, float threshold, int normalize_q,
+                            const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+    return range_search_host(idx, q_host, nq, threshold, nullptr, normalize_q, rs, cap, counts_host, D_host, I_host);
+}
+
+int mvdb_index_range_search_each(const mvdb_index* idx, const float* q_host, int nq, const float* thresholds_host, int normalize_q,
+                                 const mvdb_rowset* rs, int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host) {
+    if (!thresholds_host) return fail(MVDB_ERR_ARG, "NULL buffer passed to range search");
+    return range_search_host(idx, q_host, nq, 0.f, thresholds_host, normalize_q, rs, cap, counts_host, D_host, I_host);
+}
+
+int mvdb_index_range_search_device(const mvdb_index* idx, const float* q_dev, int nq, float threshold, int normalize_q,
+                                   const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev, float* D_dev,
+                                   int64_t* I_dev, void* stream) {
+    return range_search_dev(idx, q_dev, nq, threshold, nullptr, normalize_q, rs, cap, label_offset, counts_dev, D_dev, I_dev, stream);
+}
+
+int mvdb_index_range_search_each_device(const mvdb_index* idx, const float* q_dev, int nq, const float* thresholds_dev, int normalize_q,
+                                        const mvdb_rowset* rs, int64_t cap, int64_t label_offset, int64_t* counts_dev, float* D_dev,
+                                        int64_t* I_dev, void* stream) {
+    if (!thresholds_dev) return fail(MVDB_ERR_ARG, "NULL buffer passed to range search");
+    return range_search_dev(idx, q_dev, nq, 0.f, thresholds_dev, normalize_q, rs, cap, label_offset, counts_dev, D_dev, I_dev, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,11 @@
 // atomicAdd per flush of up to 64 keys.  The counter keeps counting past the segment's capacity — only the store is
 // suppressed — so it always ends as the true count.  The order in which waves append is not defined: the segment is sorted
 // afterwards, and a segment that overflowed is reported as such, never as a partial answer.
+//
+// Batches.  A query may bring its own threshold (RangeScanArgs::thrs).  A batch over an inner-product index
+// that keeps an fp16 shadow shares corpus passes: half_scan.hip's range_nominate_h16_kernel names candidate rows per query,
+// range_rescore_kernel below scores them with this file's arithmetic and appends to the same segments, and range_scan_kernel
+// runs once more, enabled per query on the device (gate_count), for the queries whose candidates overflowed.
 #pragma once
 #include "scan_kernels.hpp"
 
@@ -29,6 +34,11 @@ struct RangeScanArgs {
     const float* q;        // [nq, ld] queries (device), zero padded
     int normalize_q;       // L2-normalise the query in the prologue
     float thr;             // a row passes iff its key score (IP: q.x, L2: -|q-x|^2) >= thr; NaN scores fail
+    const float* thrs = nullptr;  // NULL, or [nq]: query i's own threshold in place of thr (same units; a NaN entry matches nothing)
+    // the fallback launch of the shared pass (mvdb.hip: range_shared_phase): query i is scanned only if its candidate counter
+    // passed the capacity — every other block returns at once
+    const unsigned long long* gate_count = nullptr;
+    unsigned long long gate_cap = 0;
     const int64_t* rows;   // SEL 1: physical row of list position r
     const uint64_t* mask;  // SEL 2: bitmap over the physical rows
     uint64_t* keys;        // [nq, seg] appended keys: make_key(score, position)
@@ -47,6 +57,8 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(RangeScanArgs 
     const int t = lane % G;  // chunk lane within the row
     const int g = lane / G;  // row slot within the instruction
     const int qi = blockIdx.y;
+    if (a.gate_count && a.gate_count[qi] <= a.gate_cap) return;
+    const float thr = a.thrs ? a.thrs[qi] : a.thr;
 
     // ---- query -> registers (flat_scan_kernel's prologue, same operation order) ---------------
     f32x4 qv[C];
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(RangeScanArgs 
         for (int u = 0; u < U; ++u) {
             const int64_t r = row0 + (int64_t)u * RPI;
             // NaN fails the comparison; the key carries the position (row number, or position in the row list)
-            const bool pass = (t == 0) && (r < a.n) && (SEL != 2 || sel[u]) && (s[u] >= a.thr);
+            const bool pass = (t == 0) && (r < a.n) && (SEL != 2 || sel[u]) && (s[u] >= thr);
             if (__ballot(pass)) append(pass ? make_key(s[u], (uint32_t)r) : 0ull);
         }
     };
@@ -211,6 +223,147 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(RangeScanArgs 
             batch_rows(b, pr);
             load_batch(pr, x);
             consume_batch(b, x, all_rows);
+        }
+    }
+    if (nst) flush();
+}
+
+// ---- exact re-score of the shared pass's candidates (inner product) ---------------------------------------------------------
+// The nomination launches (half_scan.hip: range_nominate_h16_kernel) left, per query, a segment of candidate ROW NUMBERS and a
+// counter.  Work items are (query blockIdx.y, batch of its segment): the grid is fixed — gridDim.x blocks per query, looping
+// over the batches the query's counter says there are; a query without candidates, or one whose counter passed the capacity
+// (the gated range_scan_kernel answers it), costs its blocks one scalar load.  Per row this is range_scan_kernel's arithmetic
+// for the same (G, C, MASKED), metric 0 — lane t of the row's G lanes takes chunks t, t + G, ..., C x 4 fmaf in chunk order,
+// the G/2 ... 1 xor butterfly, the same fused query normalisation — so a score is bit for bit the single-query scan's; the
+// keys carry the ROW, and go to the segments the sort and the emit kernels read through the same staged append.
+struct RangeRescoreArgs {
+    const float* X;
+    int64_t ld;
+    int d4;
+    const float* q;        // [nq, ld] the fp32 queries
+    int normalize_q;
+    float thr;
+    const float* thrs;     // NULL, or [nq]
+    const uint32_t* cand;  // [nq][ccap]
+    int64_t ccap;
+    const unsigned long long* ccount;  // [nq]
+    uint64_t* keys;
+    int64_t seg;
+    int64_t cap;
+    unsigned long long* counts;
+};
+
+template <int G, int C, int U, bool MASKED>
+__global__ __launch_bounds__(kScanThreads) void range_rescore_kernel(RangeRescoreArgs a) {
+    constexpr int RPI = kWave / G;
+    constexpr int RB = RPI * U;
+    const int qi = blockIdx.y;
+    const unsigned long long have = a.ccount[qi];
+    if (have == 0 || have > (unsigned long long)a.ccap) return;
+    const int64_t m = (int64_t)have;
+    const int64_t nbatches = (m + RB - 1) / RB;
+    if ((int64_t)blockIdx.x * kScanWaves >= nbatches) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int t = lane % G;
+    const int g = lane / G;
+    const float thr = a.thrs ? a.thrs[qi] : a.thr;
+    const uint32_t* __restrict__ rows = a.cand + (int64_t)qi * a.ccap;
+
+    // ---- query -> registers (flat_scan_kernel's prologue, same operation order) ---------------
+    f32x4 qv[C];
+    bool cvalid[C];
+    const float* qptr = a.q + (int64_t)qi * a.ld;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int chunk = c * G + t;
+        cvalid[c] = !MASKED || chunk < a.d4;
+        qv[c] = cvalid[c] ? *reinterpret_cast<const f32x4*>(qptr + chunk * 4) : f32x4{0, 0, 0, 0};
+    }
+    if (a.normalize_q) {
+        float nr = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            nr += qv[c].x * qv[c].x + qv[c].y * qv[c].y + qv[c].z * qv[c].z + qv[c].w * qv[c].w;
+        nr = group_reduce_add<G>(nr);
+        if (nr > 0.f) {
+            const float inorm = 1.0f / sqrtf(nr);
+#pragma unroll
+            for (int c = 0; c < C; ++c) qv[c] *= inorm;
+        }
+    }
+
+    // ---- the wave's staged keys (range_scan_kernel's append path) -----------------------------------
+    uint64_t stage = 0;
+    int nst = 0;
+    uint64_t* const seg = a.keys + (int64_t)qi * a.seg;
+    unsigned long long* const ctr = a.counts + qi;
+    const unsigned long long cap = (unsigned long long)a.cap;
+    auto flush = [&]() {
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(ctr, (unsigned long long)nst);
+        base = readlane_u64(base, 0);
+        if (lane < nst && base + (unsigned long long)lane < cap) seg[base + lane] = stage;
+        nst = 0;
+    };
+    auto append = [&](uint64_t cand) {
+        uint64_t mm = __ballot(cand != 0ull);
+        while (mm) {
+            const int src = __ffsll((long long)mm) - 1;
+            mm &= mm - 1;
+            const uint64_t key = readlane_u64(cand, src);
+            if (lane == nst) stage = key;
+            if (++nst == kWave) flush();
+        }
+    };
+
+    const int64_t last = m - 1;
+    const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
+    for (int64_t b = (int64_t)blockIdx.x * kScanWaves + wave; b < nbatches; b += nwaves_total) {
+        const int64_t row0 = b * RB + g;
+        uint32_t pr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int64_t r = row0 + (int64_t)u * RPI;
+            r = r < last ? r : last;  // clamp: tail lanes re-read the segment's last candidate, result discarded
+            pr[u] = rows[r];
+        }
+        f32x4 x[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float* p = a.X + (int64_t)pr[u] * a.ld + t * 4;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const f32x4* src = reinterpret_cast<const f32x4*>(p + c * G * 4);
+                if (MASKED)
+                    x[u][c] = cvalid[c] ? __builtin_nontemporal_load(src) : f32x4{0, 0, 0, 0};
+                else
+                    x[u][c] = __builtin_nontemporal_load(src);
+            }
+        }
+        float s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float acc = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                acc = fmaf(x[u][c].x, qv[c].x, acc);
+                acc = fmaf(x[u][c].y, qv[c].y, acc);
+                acc = fmaf(x[u][c].z, qv[c].z, acc);
+                acc = fmaf(x[u][c].w, qv[c].w, acc);
+            }
+            s[u] = acc;
+        }
+#pragma unroll
+        for (int mm = G / 2; mm >= 1; mm >>= 1) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] += __shfl_xor(s[u], mm);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = row0 + (int64_t)u * RPI;
+            const bool pass = (t == 0) && (r < m) && (s[u] >= thr);
+            if (__ballot(pass)) append(pass ? make_key(s[u], pr[u]) : 0ull);
         }
     }
     if (nst) flush();

@@ -553,3 +553,6 @@ class DistributedShardedVectorDatabase:
 
     def count_similar(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RANGE)
+
+    def count_similar_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)

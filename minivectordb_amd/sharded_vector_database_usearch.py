@@ -142,3 +142,6 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
 
     def count_similar(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RANGE)
+
+    def count_similar_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RANGE)
