@@ -108,10 +108,15 @@ struct RetireScope {
     ~RetireScope() { tls_retire = prev; }
 };
 
+// The two buffer types own their memory: whatever holds one frees it by going away (with the owner's device current).
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t n) {
         if (n <= cap) return 0;
         if (p) {
@@ -135,6 +140,10 @@ struct DevBuf {
 struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;  // bytes
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
     int reserve(size_t n) {
         if (n <= cap) return 0;
         if (p) (void)hipHostFree(p);
@@ -149,6 +158,18 @@ struct PinnedBuf {
         if (p) (void)hipHostFree(p);
         p = nullptr;
         cap = 0;
+    }
+};
+
+// The stream a workspace created for itself (none for a caller's stream or the legacy default stream).  Declared as the FIRST
+// member of its workspace, so destroyed last: the workspace's buffers are freed before the stream they were used on goes.
+struct OwnedStream {
+    hipStream_t h = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() {
+        if (h) (void)hipStreamDestroy(h);
     }
 };
 

@@ -32,8 +32,8 @@ int64_t pow2_at_least(int64_t v) {
 }
 
 struct Cos8Workspace {
+    OwnedStream owned;       // (first: the buffers below are freed before it)
     hipStream_t stream = nullptr;
-    bool own_stream = false;
     DevBuf<float> q;         // host queries staged on the device
     DevBuf<int8_t> qcodes;   // [nq, stride]
     DevBuf<int32_t> qb2;     // [nq]
@@ -50,30 +50,17 @@ struct Cos8Workspace {
     int init(int device, hipStream_t s, bool own) {
         (void)device;
         if (own) {
-            MVDB_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            MVDB_HIP(hipStreamCreateWithFlags(&owned.h, hipStreamNonBlocking));
+            stream = owned.h;
         } else {
             stream = s;
         }
-        own_stream = own;
         MVDB_HIP(hipMalloc(&st, select_state_bytes()));
         return 0;
     }
-    void destroy() {
-        q.release();
-        qcodes.release();
-        qb2.release();
-        cand.release();
-        scores.release();
-        selkeys.release();
-        out.release();
-        pin.release();
-        pin_out.release();
+    ~Cos8Workspace() {   // (also of a workspace whose init() failed half-way)
         if (st) (void)hipFree(st);
-        st = nullptr;
         for (void* p : retired) (void)hipFree(p);
-        retired.clear();
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
     }
 };
 
@@ -115,7 +102,6 @@ Cos8Workspace* ws_for_stream(const mvdb_cos8* ix, hipStream_t s) {
     if (it != ix->by_stream.end()) return it->second;
     Cos8Workspace* ws = new Cos8Workspace();
     if (ws->init(ix->device, s, false) != 0) {
-        ws->destroy();
         delete ws;
         return nullptr;
     }
@@ -132,7 +118,6 @@ Cos8Workspace* ws_acquire(const mvdb_cos8* ix) {
     }
     Cos8Workspace* ws = new Cos8Workspace();
     if (ws->init(ix->device, nullptr, true) != 0) {
-        ws->destroy();
         delete ws;
         return nullptr;
     }
@@ -161,7 +146,6 @@ int quiesce(mvdb_cos8* ix) {
         }
         (void)hipGetLastError();
         if (e == hipErrorInvalidHandle || e == hipErrorInvalidResourceHandle || e == hipErrorContextIsDestroyed) {
-            it->second->destroy();
             delete it->second;
             it = ix->by_stream.erase(it);
         } else {
@@ -463,21 +447,13 @@ int mvdb_cos8_free(mvdb_cos8* ix) {
     {
         std::unique_lock<std::shared_mutex> lk(ix->mu);
         if (quiesce(ix) != 0) (void)hipDeviceSynchronize();
-        for (auto& kv : ix->by_stream) {
-            kv.second->destroy();
-            delete kv.second;
-        }
-        for (Cos8Workspace* ws : ix->pool) {
-            ws->destroy();
-            delete ws;
-        }
-        ix->stage.release();
-        ix->pin.release();
+        for (auto& kv : ix->by_stream) delete kv.second;
+        for (Cos8Workspace* ws : ix->pool) delete ws;
         if (ix->codes) (void)hipFree(ix->codes);
         if (ix->a2) (void)hipFree(ix->a2);
         if (ix->ms) (void)hipStreamDestroy(ix->ms);
     }
-    delete ix;
+    delete ix;  // (the staging buffers it owns go here, still on the index's device)
     return 0;
 }
 

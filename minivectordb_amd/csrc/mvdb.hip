@@ -184,6 +184,7 @@ void prof_end(int ticket, hipStream_t stream) {
 namespace {
 
 struct Workspace {
+    OwnedStream owned;  // (first: every buffer below is freed before the stream this workspace created for itself)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -233,51 +234,23 @@ struct Workspace {
         device = dev;
         if (s) {
             stream = s;
-            own_stream = false;
         } else {
-            MVDB_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            MVDB_HIP(hipStreamCreateWithFlags(&owned.h, hipStreamNonBlocking));
+            stream = owned.h;
             own_stream = true;
         }
         MVDB_HIP(hipMalloc((void**)&st, sizeof(SelectState)));
         return 0;
     }
-    void destroy() {
-        q.release();
-        qn.release();
-        cand.release();
-        out.release();
-        pin_out.release();
-        scores.release();
-        selkeys.release();
-        rows.release();
-        qsplit.release();
-        qnorm.release();
-        flags.release();
-        qfail.release();
-        requery.release();
-        relabel.release();
-        nfail.release();
-        pin.release();
-        rkeys.release();
-        rcounts.release();
-        rcand.release();
-        rccount.release();
-        rthr.release();
-        gtab.release();
-        c8.release();
+    // what is not a buffer (the buffers free themselves); also of a workspace whose init() failed half-way
+    ~Workspace() {
         for (GroupedStage* g : gstage) {
-            g->buf.release();
             if (g->ev) (void)hipEventDestroy(g->ev);
             delete g;
         }
-        gstage.clear();
-        gpin_spare.release();
         for (void* p : gpin_captured) (void)hipHostFree(p);
-        gpin_captured.clear();
         for (void* old : retired) (void)hipFree(old);
-        retired.clear();
         if (st) (void)hipFree(st);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -366,7 +339,6 @@ struct mvdb_index {
         }
         Workspace* w = new Workspace();
         if (w->init(device, nullptr)) {
-            w->destroy();
             delete w;
             return nullptr;
         }
@@ -380,11 +352,9 @@ struct mvdb_index {
         std::lock_guard<std::mutex> lk(ws_mu);
         if (!s) {
             if (!default_stream_ws) {
-                // legacy default stream: work is enqueued on stream 0 itself
+                // legacy default stream: work is enqueued on stream 0 itself (the workspace owns no stream: stream 0 is never destroyed)
                 Workspace* w = new Workspace();
                 w->device = device;
-                w->stream = nullptr;
-                w->own_stream = false;
                 if (hipMalloc((void**)&w->st, sizeof(SelectState)) != hipSuccess) {
                     delete w;
                     return nullptr;
@@ -397,7 +367,6 @@ struct mvdb_index {
         if (it != stream_ws.end()) return it->second;
         Workspace* w = new Workspace();
         if (w->init(device, s)) {
-            w->destroy();
             delete w;
             return nullptr;
         }
@@ -612,7 +581,6 @@ int quiesce(mvdb_index* idx) {
         }
         (void)hipGetLastError();
         if (e == hipErrorInvalidHandle || e == hipErrorInvalidResourceHandle || e == hipErrorContextIsDestroyed) {
-            it->second->destroy();
             delete it->second;
             it = idx->stream_ws.erase(it);
         } else {
@@ -1137,11 +1105,321 @@ __global__ __launch_bounds__(256) void mask_rank_kernel(int64_t* __restrict__ I,
     if (threadIdx.x == 0) I[blockIdx.x] = part[0];
 }
 
+// The queries a multi-query pass reads: the caller's, or their normalised copy in ws->qn.
+int normalized_queries(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq, int normalize_q, const float** qsrc) {
+    *qsrc = q_dev;
+    if (!normalize_q) return 0;
+    MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
+    MVDB_HIP(hipMemcpyAsync(ws->qn.p, q_dev, (size_t)nq * idx->ld * sizeof(float), hipMemcpyDeviceToDevice, ws->stream));
+    MVDB_TRY(normalize_range(idx, ws->qn.p, nq, ws->stream));
+    *qsrc = ws->qn.p;
+    return 0;
+}
+
+// Merge the per-block lists a scan left in ws->cand into the k results of `nq` queries (one block per query).  gate / gate_lo:
+// the device-side enable of an exact re-run (query b is merged iff *gate > gate_lo + b); need / per_pass / pass_stride: the
+// second enable, one word per pass of per_pass queries whose lists start pass_stride keys apart (scan_kernels.hpp: MergeArgs).
+int launch_merge(const mvdb_index* idx, Workspace* ws, int nq, int nlists, int k, int64_t label_offset, float* D, int64_t* I,
+                 const int* gate = nullptr, int gate_lo = 0, const int* need = nullptr, int per_pass = 0, int64_t pass_stride = 0) {
+    MergeArgs mg;
+    mg.keys = ws->cand.p;
+    mg.nlists = nlists;
+    mg.k = k;
+    mg.metric = idx->metric;
+    mg.label_offset = label_offset;
+    mg.D = D;
+    mg.I = I;
+    mg.gate = gate;
+    mg.gate_lo = gate_lo;
+    mg.need = need;
+    mg.per_pass = per_pass;
+    mg.pass_stride = pass_stride;
+    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(kMergeThreads), 0, ws->stream, mg);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
 constexpr int kCoreTile = 1024;      // queries search_core answers per pass over its workspace
 constexpr int64_t kShiftMaxRows = 8;           // most scattered deleted rows of a call the one-pass compaction takes (a run of any length qualifies)
 constexpr size_t kShiftSideBytes = 64u << 20;   // ... and the most its side copies may occupy
 constexpr size_t kTileFlagMaxBytes = 512u << 20;  // the most the certified pass's tile flags may occupy (queries of the call x tiles / 8)
 constexpr int kGatedPassGroup = 8;   // exact re-run passes (of 16 / 32 compact queries) one gated launch walks: one list buffer of that many
+
+// The certified batch pass (search_core's route for batches; half_scan.hip): ONE fp16 product over the shadow nominates, fp32
+// re-scores decide, a worst-case bound certifies; queries whose certificate is refused are re-run on the exact kernels,
+// enabled on the device.  `a`: the scan arguments of the call (the L2 re-run launches the single-query scan with them).
+// *answered: the leading queries of the call the pass took — the rest (fewer than the pass is worth) is the caller's;
+// *qsrc_out: the queries as the pass read them (normalised where the call asks for it).
+int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, const float* q_dev, int nq, int k, int normalize_q, int64_t n,
+                    int64_t label_offset, float* D_dev, int64_t* I_dev, const uint64_t* mask_dev, int* answered, const float** qsrc_out) {
+    hipStream_t s = ws->stream;
+    const uint32_t* mask32 = reinterpret_cast<const uint32_t*>(mask_dev);
+    const float* qsrc = nullptr;
+    MVDB_TRY(normalized_queries(idx, ws, q_dev, nq, normalize_q, &qsrc));
+    *qsrc_out = qsrc;
+    // chunk plan: 128 / 256 queries per pass while at least min_nq remain; what is left takes the exact passes
+    const int min_nq = half_min_nq(idx, n);
+    const int chunk = half_max_queries(idx->d);
+    std::vector<std::pair<int, int>> plan;  // (first query, count)
+    int q0 = 0;
+    // (L2 over rows of mixed norms: the pass nominates by q.x - |x|^2 / 2 with per-row offsets beside the shadow; rows of one
+    //  norm by inner product, which ranks like the distance then)
+    const bool ip_ranks = idx->metric == MVDB_METRIC_IP || l2_cert_ok(idx);
+    while (nq - q0 >= min_nq && (ip_ranks || l2_offsets_ok(idx, nq - q0, n))) {
+        plan.emplace_back(q0, std::min(nq - q0, chunk));
+        q0 += plan.back().second;
+    }
+    const int nchunks = (int)plan.size();
+    if (nchunks > 0) {
+        MVDB_TRY(ws->qsplit.reserve((size_t)std::max(2 * 128, chunk) * idx->d));
+        MVDB_TRY(ws->qnorm.reserve((size_t)std::max(256, 3 * chunk)));  // |q|, admission floors, 1 / scale
+        MVDB_TRY(ws->flags.reserve((size_t)std::max(nchunks, 64) + 32));  // + diagnostics counters in the last 32 slots
+        MVDB_TRY(ws->cand.reserve((size_t)std::max(128, chunk) * (scan_grid_upper_bound(idx->device) + 1) * kHalfKeep));
+        MVDB_TRY(ws->qfail.reserve((size_t)q0));
+        MVDB_TRY(ws->qfloor.reserve((size_t)2 * q0 + 128));  // [q0] per query | [q0 + 128] per compact slot
+        MVDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws->qfloor.p), 0xff800000u, (size_t)q0, s));  // -inf: no floor
+        MVDB_HIP(hipMemsetAsync(ws->flags.p, 0, (size_t)nchunks * sizeof(int), s));
+        MVDB_HIP(hipMemsetAsync(ws->qfail.p, 0, (size_t)q0 * sizeof(int), s));
+        // Tile flags (round 6): the main launches note, per query, which 32-row tiles came near its running threshold; should the
+        // query be refused, its rescue launch walks those tiles only (clustered 10M x 512, 256 per call: 2.6 % of the shadow).  Inner product, k <= 16 (the floors are 16th-best scores), from ~400k rows on (below, the rescue launch is
+        // short and the flags' memset is not), at most 512 MiB of flags — and only while the index has been refusing
+        // certificates (tile_flags_wanted): a corpus that certifies everything never pays for them.
+        const int64_t ntiles_all = (n + 31) / 32;
+        const int twords = (int)((ntiles_all + 31) / 32);
+        const bool tile_flags = idx->metric == MVDB_METRIC_IP && k <= kHalfKeep && ntiles_all >= idx->kn.tile_flag_min_tiles && tile_flags_wanted(idx) &&
+                                !idx->kn.disable_rescue && !idx->kn.disable_rerun_floor && half_rescue_dim(idx->d) &&
+                                (size_t)q0 * twords * sizeof(uint32_t) <= kTileFlagMaxBytes;
+        if (tile_flags) {
+            MVDB_TRY(ws->tflags.reserve((size_t)q0 * twords));
+            MVDB_HIP(hipMemsetAsync(ws->tflags.p, 0, (size_t)q0 * twords * sizeof(uint32_t), s));
+        }
+        bool flags_ok = tile_flags;  // ... and every chunk's main launches did write them (launch_half_pass decides per chunk)
+        for (int c = 0; c < nchunks; ++c) {
+            const int c0 = plan[c].first, take = plan[c].second;
+            bool wrote = false;
+            MVDB_TRY(launch_half_pass(idx, ws, qsrc + (int64_t)c0 * idx->ld, take, half_chunk_queries(idx->d, take), k, n, label_offset,
+                                      D_dev + (int64_t)c0 * k, I_dev + (int64_t)c0 * k, ws->flags.p + c, ws->qfail.p + c0, mask32,
+                                      ws->qfloor.p + c0, tile_flags ? ws->tflags.p + (size_t)c0 * twords : nullptr, twords, &wrote));
+            flags_ok = flags_ok && wrote;
+        }
+        // ---- uncertified queries: re-run on the exact kernels WITHOUT the host ever learning which they were ----------
+        // split_plan_kernel compacts the failed queries (ascending) and publishes their number nb; the exact passes below
+        // are launched unconditionally over the compact batch and enabled on the device: a launch whose query range
+        // starts at or beyond nb returns at once (a few microseconds each when every query certified — the usual case).
+        //   compact queries [0, 64): two 32-query fp32-MFMA passes (one corpus pass each: a handful of duplicate-heavy
+        //                            neighbourhoods in a batch cost about one pass);
+        //   the rest, in 128s:       the GEMM-tiled exact scan (a whole chunk failing: duplicate-heavy data).
+        // No stream synchronise, no device-to-host copy: the call can be captured into a hipGraph (after one eager call
+        // has sized the workspace) and an encoder -> search chain stays one enqueue.
+        unsigned long long* ctr = rerun_counter(idx->device);
+        if (!ctr) return fail(MVDB_ERR_OOM, "device allocation for the re-run counter failed");
+        const int R = q0;  // most queries that can fail
+        MVDB_TRY(ws->nfail.reserve(1));
+        MVDB_TRY(ws->relabel.reserve((size_t)R * (1 + k)));
+        MVDB_TRY(ws->requery.reserve((size_t)(R + 128) * idx->ld + (size_t)R * k));  // + one query tile of slack for the scans
+        int64_t* map = ws->relabel.p;
+        int64_t* It = map + R;
+        float* qc = ws->requery.p;
+        float* Dt = qc + (size_t)(R + 128) * idx->ld;
+        unsigned int *sq_dev = nullptr, *sq_host = nullptr;
+        if (nq == 1 && idx->kn.shadow_single_query) {  // the opt-in single-query route reports its refusals (single_route_suspended)
+            std::lock_guard<std::mutex> lk(idx->shadow_mu);
+            if (!idx->sq_fail_dev && hipMalloc((void**)&idx->sq_fail_dev, sizeof(unsigned int)) == hipSuccess) {
+                if (hipMemsetAsync(idx->sq_fail_dev, 0, sizeof(unsigned int), s) != hipSuccess || idx->sq_fail_host.reserve(64) != 0) {
+                    (void)hipFree(idx->sq_fail_dev);
+                    idx->sq_fail_dev = nullptr;
+                } else {
+                    *reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p) = 0u;
+                }
+            }
+            (void)hipGetLastError();
+            if (idx->sq_fail_dev && idx->sq_fail_host.p) {
+                sq_dev = idx->sq_fail_dev;
+                sq_host = reinterpret_cast<unsigned int*>(idx->sq_fail_host.p);
+            }
+        }
+        unsigned int* rf_dev = idx->rf_dev && idx->rf_host.p ? idx->rf_dev : nullptr;
+        hipLaunchKernelGGL(split_plan_kernel, dim3(1), dim3(64), 0, s, (const int*)ws->flags.p, nchunks, (const int*)ws->qfail.p, q0,
+                           map, ws->nfail.p, ctr, sq_dev, (volatile unsigned int*)sq_host, rf_dev,
+                           (volatile unsigned int*)(rf_dev ? idx->rf_host.p : nullptr));
+        {
+            const int64_t rows = R + 128, gtotal = rows * (idx->ld / 4);
+            const int ggrid = (int)std::min<int64_t>((gtotal + 255) / 256, (int64_t)device_cus(idx->device) * 8);
+            hipLaunchKernelGGL(gather_failed_kernel, dim3(ggrid), dim3(256), 0, s, qc, qsrc, (const int64_t*)map,
+                               (const int*)ws->nfail.p, rows, idx->ld, (const float*)ws->qfloor.p, ws->qfloor.p + q0);
+        }
+        MVDB_HIP(hipGetLastError());
+        const int per_pass = mfma_gated_queries(idx);
+        const int KB = idx->d / 16;
+        int off = 0;
+        // ---- the RESCUE pass (half_scan.hip): refused queries once more over the shadow, 128 at a time, every row above
+        // the query's floor — what the k-th exact score (L2: distance) of its nominees admits, less the nomination error —
+        // kept and re-scored in fp32; what it answers the exact passes skip.  need_per = compact queries per `need` word:
+        // the queries of one exact pass (inner product: a gated fp32-MFMA pass of 32 / 16), or 1 (L2: one gated scan each).
+        auto rescue = [&](int need_per, const int** need_out) -> int {
+            *need_out = nullptr;
+            const float xs = half_xscale(idx->row_norm_bound);
+            if (need_per <= 0 || kRescueQueries % need_per != 0 || !half_rescue_dim(idx->d) || idx->ld != idx->d || k > kRescueKeep ||
+                idx->kn.disable_rescue || idx->kn.disable_rerun_floor || !(xs > 0.f))
+                return 0;
+            const _Float16* Xh = ensure_shadow(idx, s, xs);
+            if (!Xh) return 0;
+            // (L2: the same nomination form the certified pass used — per-row offsets where the rows' norms differ)
+            const bool l2 = idx->metric == MVDB_METRIC_L2;
+            const float* hn = l2 && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? ensure_offsets(idx, s) : nullptr;
+            if (l2 && !l2_cert_ok(idx) && !hn) return 0;
+            const int grid_ub = device_cus(idx->device) * kRescueBlocksPerCu;  // the rescue launch: one or two workgroups per CU
+            const int slots = (R + kRescueQueries - 1) / kRescueQueries;
+            const size_t nneed = (size_t)(R + kRescueQueries) / need_per + 8;
+            const size_t nwords = nneed + slots;  // ... and the tile lists' lengths behind the need words (one memset)
+            MVDB_TRY(ws->need.reserve(nwords));
+            MVDB_TRY(ws->tlist.reserve((size_t)slots * ntiles_all));
+            MVDB_TRY(ws->cand.reserve((size_t)kRescueQueries * (grid_ub + 1) * kRescueKeep));
+            MVDB_TRY(ws->qsplit.reserve((size_t)2 * kRescueQueries * idx->d));
+            MVDB_TRY(ws->qnorm.reserve((size_t)3 * kRescueQueries));
+            MVDB_HIP(hipMemsetAsync(ws->need.p, 0, nwords * sizeof(int), s));
+            _Float16* qf = reinterpret_cast<_Float16*>(ws->qsplit.p);
+            float* qn2 = ws->qnorm.p;
+            float* qinv = qn2 + 2 * kRescueQueries;
+            float eps = (float)(half_eps(idx->d) * (double)idx->row_norm_bound * (1.0 + 1e-6));
+            if (hn) eps = (float)((double)eps + std::ldexp(1.0, -22) * (double)idx->row_norm_bound * (1.0 + 1e-6));  // (launch_half_pass: the subtraction)
+            {   // the launches' tile lists: what the refused queries' flags name (no flags: every tile)
+                RescueTilesArgs ta;
+                ta.tflags = flags_ok ? ws->tflags.p : nullptr;
+                ta.twords = twords;
+                ta.map = map;
+                ta.nfail = ws->nfail.p;
+                ta.seed_tiles = std::min<int64_t>(ntiles_all, device_cus(idx->device));  // (launch_half_pass: the seed launch's tiles)
+                ta.ntiles = ntiles_all;
+                ta.lists = ws->tlist.p;
+                ta.counts = ws->need.p + nneed;
+                ta.stats = ctr + 1;
+                MVDB_TRY(launch_rescue_tiles(ta, slots, s));
+            }
+            for (int off2 = 0; off2 < R; off2 += kRescueQueries) {
+                MVDB_TRY(launch_half_queries(qc + (int64_t)off2 * idx->ld, idx->ld, idx->d, kRescueQueries, kRescueQueries, xs, qf, qn2,
+                                             qinv, s));
+                HalfScanArgs ra;
+                ra.X = idx->X;
+                ra.n = n;
+                ra.ld = idx->ld;
+                ra.qf = qf;
+                ra.qinv = qinv;
+                ra.xscale = xs;
+                ra.nq = std::min(kRescueQueries, R - off2);  // (slots past the call's queries can never be live)
+                ra.mask = mask32;
+                ra.Xh = Xh;
+                ra.hn = hn;
+                ra.stats = nullptr;
+                ra.cand = ws->cand.p;
+                ra.tile0 = 0;
+                ra.tile1 = (n + 31) / 32;
+                ra.thr0 = ws->qfloor.p + q0 + off2;
+                ra.thr_eps = eps;
+                ra.thr_qn = qn2;
+                ra.gate = ws->nfail.p;
+                ra.gate_lo = off2;
+                ra.tile_list = ws->tlist.p + (size_t)(off2 / kRescueQueries) * ntiles_all;
+                ra.tile_count = ws->need.p + nneed + off2 / kRescueQueries;
+                int gx = 0;
+                MVDB_TRY(launch_half_rescue_scan(idx->d, ra, idx->device, s, &gx));
+                HalfRescueArgs rc;
+                rc.keys = ws->cand.p;
+                rc.nlists = gx;
+                rc.X = idx->X;
+                rc.ld = idx->ld;
+                rc.d4 = idx->d4;
+                rc.q = qc + (int64_t)off2 * idx->ld;
+                rc.k = k;
+                rc.label_offset = label_offset;
+                rc.D = Dt + (int64_t)off2 * k;
+                rc.I = It + (int64_t)off2 * k;
+                rc.gate = ws->nfail.p;
+                rc.gate_lo = off2;
+                rc.need = ws->need.p + off2 / need_per;
+                rc.per_pass = need_per;
+                rc.l2 = l2 ? 1 : 0;
+                MVDB_TRY(launch_half_rescue_certify(rc, s));
+            }
+            *need_out = ws->need.p;
+            return 0;
+        };
+        if (idx->metric == MVDB_METRIC_L2) {
+            // L2: the rescue pass, then — for what it could not hold — the exact single-query scan (sum (q - x)^2 directly),
+            // 32 compact queries per launch, each query's blocks enabled on the device (refused count and `need` word)
+            const int* need = nullptr;
+            MVDB_TRY(rescue(1, &need));
+            const int per = 32;
+            MVDB_TRY(ws->cand.reserve((size_t)per * scan_grid_upper_bound(idx->device) * k));
+            for (; off < R; off += per) {
+                const int take = std::min(per, R - off);
+                ScanArgs ga = a;
+                ga.q = qc + (int64_t)off * idx->ld;
+                ga.normalize_q = 0;
+                ga.cand = ws->cand.p;
+                ga.gate = ws->nfail.p;
+                ga.gate_lo = off;
+                ga.need = need ? need + off : nullptr;
+                int nblocks = 0;
+                MVDB_TRY(launch_scan(idx->metric, kModeTopK, ga, take, idx->device, s, &nblocks));
+                // (one `need` word per query: "pass" = query, its lists nblocks * k keys after the query before)
+                MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, Dt + (int64_t)off * k, It + (int64_t)off * k, ws->nfail.p, off,
+                                      need ? need + off : nullptr, need ? 1 : 0, need ? (int64_t)nblocks * k : 0));
+            }
+            off = R;
+        } else if (per_pass > 0 && !idx->kn.disable_mfma_scan) {
+            const int* need = nullptr;
+            MVDB_TRY(rescue(per_pass, &need));
+            MVDB_TRY(ws->cand.reserve((size_t)32 * scan_grid_upper_bound(idx->device) * k));
+            // (the GEMM scan keeps k <= 16 and takes no bitmap: those re-runs are all fp32-MFMA passes)
+            // every refused query through the gated fp32-MFMA pass, 32 at a time (launches beyond the refused count return at
+            // once).  Until round 5 the batch went to the 128-query GEMM-tiled scan after two such passes — 20-25 ms per 128
+            // queries at 10M x 512 where four MFMA passes take 14.
+            const int max_passes = (R + per_pass - 1) / per_pass;
+            {
+                // ONE launch walks up to kGatedPassGroup passes on the device (pass p: compact queries [p per_pass, ...); each
+                // enabled by the refused count and its `need` word), ONE merge launch covers the group's compact queries; the
+                // groups share one list buffer in stream order (so the lists are O(1) in the batch: 8 passes x 5 MB at k = 10)
+                const int64_t cand_stride = (int64_t)per_pass * scan_grid_upper_bound(idx->device) * k;
+                MVDB_TRY(ws->cand.reserve((size_t)std::min(max_passes, kGatedPassGroup) * cand_stride));
+                for (int p0 = 0; p0 < max_passes; p0 += kGatedPassGroup) {
+                    const int np = std::min(kGatedPassGroup, max_passes - p0), qoff = p0 * per_pass;
+                    MfmaScanArgs ma;
+                    ma.X = idx->X;
+                    ma.n = n;
+                    ma.ld = idx->ld;
+                    ma.q = qc + (int64_t)qoff * idx->ld;
+                    ma.nq = std::min(per_pass, R - qoff);
+                    ma.k = k;
+                    ma.cand = ws->cand.p;
+                    ma.mask = mask32;
+                    ma.thr0 = idx->kn.disable_rerun_floor ? nullptr : ws->qfloor.p + q0 + qoff;
+                    int nblocks = 0;
+                    MVDB_TRY(launch_mfma2_gated(KB, ma, idx->device, s, &nblocks, ws->nfail.p, qoff, need ? need + p0 : nullptr, np, per_pass,
+                                                R - qoff, cand_stride));
+                    MVDB_TRY(launch_merge(idx, ws, std::min(np * per_pass, R - qoff), nblocks, k, label_offset, Dt + (int64_t)qoff * k,
+                                          It + (int64_t)qoff * k, ws->nfail.p, qoff, need ? need + p0 : nullptr, per_pass, cand_stride));
+                }
+                off = R;
+            }
+        }
+        if (off < R && mask_dev) return fail(MVDB_ERR_ARG, "internal: bitmap re-run left to the GEMM scan");
+        if (off < R) MVDB_TRY(ws->cand.reserve((size_t)128 * scan_grid_upper_bound(idx->device) * k));
+        while (off < R) {
+            const int take = std::min(128, R - off);
+            int nblocks = 0;
+            MVDB_TRY(launch_gemm_scan(idx, qc + (int64_t)off * idx->ld, take, k, n, ws->cand.p, s, &nblocks, ws->nfail.p, off));
+            MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, Dt + (int64_t)off * k, It + (int64_t)off * k, ws->nfail.p, off));
+            off += take;
+        }
+        hipLaunchKernelGGL(scatter_failed_kernel, dim3((unsigned)(((int64_t)R * k + 255) / 256)), dim3(256), 0, s, (const float*)Dt,
+                           (const int64_t*)It, (const int64_t*)map, (const int*)ws->nfail.p, (int64_t)R, k, D_dev, I_dev);
+        MVDB_HIP(hipGetLastError());
+    }
+    *answered = q0;
+    return 0;
+}
+
 int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq, int k,
                 int normalize_q, const int64_t* rows_dev, int64_t m, int64_t label_offset,
                 float* D_dev, int64_t* I_dev, bool allow_split = true, const uint64_t* mask_dev = nullptr) {
@@ -1206,313 +1484,11 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
 
     // Batches (2+ queries where the corpus buries the pass's fixed cost, half_min_nq), k <= 32, rows of known norm, a width the
     // fp16 kernels serve: ONE fp16 product over the shadow nominates, fp32 re-scores decide, a worst-case bound certifies
-    // (half_scan.hip); queries whose certificate is refused are re-run below.
+    // (certified_batch); what it leaves — fewer queries than the pass is worth — takes the exact passes below.
     if (allow_split && split_path_ok(idx, nq, k, rows_dev, n) && ensure_shadow(idx, s, half_xscale(idx->row_norm_bound))) {
-        const float* qsrc = q_dev;
-        if (normalize_q) {
-            MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
-            MVDB_HIP(hipMemcpyAsync(ws->qn.p, q_dev, (size_t)nq * idx->ld * sizeof(float),
-                                    hipMemcpyDeviceToDevice, s));
-            MVDB_TRY(normalize_range(idx, ws->qn.p, nq, s));
-            qsrc = ws->qn.p;
-        }
-        // chunk plan: 128 / 256 queries per pass while at least min_nq remain; what is left takes the exact passes
-        const int min_nq = half_min_nq(idx, n);
-        const int chunk = half_max_queries(idx->d);
-        std::vector<std::pair<int, int>> plan;  // (first query, count)
         int q0 = 0;
-        // (L2 over rows of mixed norms: the pass nominates by q.x - |x|^2 / 2 with per-row offsets beside the shadow; rows of one
-        //  norm by inner product, which ranks like the distance then)
-        const bool ip_ranks = idx->metric == MVDB_METRIC_IP || l2_cert_ok(idx);
-        while (nq - q0 >= min_nq && (ip_ranks || l2_offsets_ok(idx, nq - q0, n))) {
-            plan.emplace_back(q0, std::min(nq - q0, chunk));
-            q0 += plan.back().second;
-        }
-        const int nchunks = (int)plan.size();
-        if (nchunks > 0) {
-            MVDB_TRY(ws->qsplit.reserve((size_t)std::max(2 * 128, chunk) * idx->d));
-            MVDB_TRY(ws->qnorm.reserve((size_t)std::max(256, 3 * chunk)));  // |q|, admission floors, 1 / scale
-            MVDB_TRY(ws->flags.reserve((size_t)std::max(nchunks, 64) + 32));  // + diagnostics counters in the last 32 slots
-            MVDB_TRY(ws->cand.reserve((size_t)std::max(128, chunk) * (scan_grid_upper_bound(idx->device) + 1) * kHalfKeep));
-            MVDB_TRY(ws->qfail.reserve((size_t)q0));
-            MVDB_TRY(ws->qfloor.reserve((size_t)2 * q0 + 128));  // [q0] per query | [q0 + 128] per compact slot
-            MVDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws->qfloor.p), 0xff800000u, (size_t)q0, s));  // -inf: no floor
-            MVDB_HIP(hipMemsetAsync(ws->flags.p, 0, (size_t)nchunks * sizeof(int), s));
-            MVDB_HIP(hipMemsetAsync(ws->qfail.p, 0, (size_t)q0 * sizeof(int), s));
-            // Tile flags (round 6): the main launches note, per query, which 32-row tiles came near its running threshold; should the
-            // query be refused, its rescue launch walks those tiles only (clustered 10M x 512, 256 per call: 2.6 % of the shadow).  Inner product, k <= 16 (the floors are 16th-best scores), from ~400k rows on (below, the rescue launch is
-            // short and the flags' memset is not), at most 512 MiB of flags — and only while the index has been refusing
-            // certificates (tile_flags_wanted): a corpus that certifies everything never pays for them.
-            const int64_t ntiles_all = (n + 31) / 32;
-            const int twords = (int)((ntiles_all + 31) / 32);
-            const bool tile_flags = idx->metric == MVDB_METRIC_IP && k <= kHalfKeep && ntiles_all >= idx->kn.tile_flag_min_tiles && tile_flags_wanted(idx) &&
-                                    !idx->kn.disable_rescue && !idx->kn.disable_rerun_floor && half_rescue_dim(idx->d) &&
-                                    (size_t)q0 * twords * sizeof(uint32_t) <= kTileFlagMaxBytes;
-            if (tile_flags) {
-                MVDB_TRY(ws->tflags.reserve((size_t)q0 * twords));
-                MVDB_HIP(hipMemsetAsync(ws->tflags.p, 0, (size_t)q0 * twords * sizeof(uint32_t), s));
-            }
-            bool flags_ok = tile_flags;  // ... and every chunk's main launches did write them (launch_half_pass decides per chunk)
-            for (int c = 0; c < nchunks; ++c) {
-                const int c0 = plan[c].first, take = plan[c].second;
-                bool wrote = false;
-                MVDB_TRY(launch_half_pass(idx, ws, qsrc + (int64_t)c0 * idx->ld, take, half_chunk_queries(idx->d, take), k, n, label_offset,
-                                          D_dev + (int64_t)c0 * k, I_dev + (int64_t)c0 * k, ws->flags.p + c, ws->qfail.p + c0, mask32,
-                                          ws->qfloor.p + c0, tile_flags ? ws->tflags.p + (size_t)c0 * twords : nullptr, twords, &wrote));
-                flags_ok = flags_ok && wrote;
-            }
-            // ---- uncertified queries: re-run on the exact kernels WITHOUT the host ever learning which they were ----------
-            // split_plan_kernel compacts the failed queries (ascending) and publishes their number nb; the exact passes below
-            // are launched unconditionally over the compact batch and enabled on the device: a launch whose query range
-            // starts at or beyond nb returns at once (a few microseconds each when every query certified — the usual case).
-            //   compact queries [0, 64): two 32-query fp32-MFMA passes (one corpus pass each: a handful of duplicate-heavy
-            //                            neighbourhoods in a batch cost about one pass);
-            //   the rest, in 128s:       the GEMM-tiled exact scan (a whole chunk failing: duplicate-heavy data).
-            // No stream synchronise, no device-to-host copy: the call can be captured into a hipGraph (after one eager call
-            // has sized the workspace) and an encoder -> search chain stays one enqueue.
-            unsigned long long* ctr = rerun_counter(idx->device);
-            if (!ctr) return fail(MVDB_ERR_OOM, "device allocation for the re-run counter failed");
-            const int R = q0;  // most queries that can fail
-            MVDB_TRY(ws->nfail.reserve(1));
-            MVDB_TRY(ws->relabel.reserve((size_t)R * (1 + k)));
-            MVDB_TRY(ws->requery.reserve((size_t)(R + 128) * idx->ld + (size_t)R * k));  // + one query tile of slack for the scans
-            int64_t* map = ws->relabel.p;
-            int64_t* It = map + R;
-            float* qc = ws->requery.p;
-            float* Dt = qc + (size_t)(R + 128) * idx->ld;
-            unsigned int *sq_dev = nullptr, *sq_host = nullptr;
-            if (nq == 1 && idx->kn.shadow_single_query) {  // the opt-in single-query route reports its refusals (single_route_suspended)
-                std::lock_guard<std::mutex> lk(idx->shadow_mu);
-                if (!idx->sq_fail_dev && hipMalloc((void**)&idx->sq_fail_dev, sizeof(unsigned int)) == hipSuccess) {
-                    if (hipMemsetAsync(idx->sq_fail_dev, 0, sizeof(unsigned int), s) != hipSuccess || idx->sq_fail_host.reserve(64) != 0) {
-                        (void)hipFree(idx->sq_fail_dev);
-                        idx->sq_fail_dev = nullptr;
-                    } else {
-                        *reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p) = 0u;
-                    }
-                }
-                (void)hipGetLastError();
-                if (idx->sq_fail_dev && idx->sq_fail_host.p) {
-                    sq_dev = idx->sq_fail_dev;
-                    sq_host = reinterpret_cast<unsigned int*>(idx->sq_fail_host.p);
-                }
-            }
-            unsigned int* rf_dev = idx->rf_dev && idx->rf_host.p ? idx->rf_dev : nullptr;
-            hipLaunchKernelGGL(split_plan_kernel, dim3(1), dim3(64), 0, s, (const int*)ws->flags.p, nchunks, (const int*)ws->qfail.p, q0,
-                               map, ws->nfail.p, ctr, sq_dev, (volatile unsigned int*)sq_host, rf_dev,
-                               (volatile unsigned int*)(rf_dev ? idx->rf_host.p : nullptr));
-            {
-                const int64_t rows = R + 128, gtotal = rows * (idx->ld / 4);
-                const int ggrid = (int)std::min<int64_t>((gtotal + 255) / 256, (int64_t)device_cus(idx->device) * 8);
-                hipLaunchKernelGGL(gather_failed_kernel, dim3(ggrid), dim3(256), 0, s, qc, qsrc, (const int64_t*)map,
-                                   (const int*)ws->nfail.p, rows, idx->ld, (const float*)ws->qfloor.p, ws->qfloor.p + q0);
-            }
-            MVDB_HIP(hipGetLastError());
-            const int per_pass = mfma_gated_queries(idx);
-            const int KB = idx->d / 16;
-            int off = 0;
-            // ---- the RESCUE pass (half_scan.hip): refused queries once more over the shadow, 128 at a time, every row above
-            // the query's floor — what the k-th exact score (L2: distance) of its nominees admits, less the nomination error —
-            // kept and re-scored in fp32; what it answers the exact passes skip.  need_per = compact queries per `need` word:
-            // the queries of one exact pass (inner product: a gated fp32-MFMA pass of 32 / 16), or 1 (L2: one gated scan each).
-            auto rescue = [&](int need_per, const int** need_out) -> int {
-                *need_out = nullptr;
-                const float xs = half_xscale(idx->row_norm_bound);
-                if (need_per <= 0 || kRescueQueries % need_per != 0 || !half_rescue_dim(idx->d) || idx->ld != idx->d || k > kRescueKeep ||
-                    idx->kn.disable_rescue || idx->kn.disable_rerun_floor || !(xs > 0.f))
-                    return 0;
-                const _Float16* Xh = ensure_shadow(idx, s, xs);
-                if (!Xh) return 0;
-                // (L2: the same nomination form the certified pass used — per-row offsets where the rows' norms differ)
-                const bool l2 = idx->metric == MVDB_METRIC_L2;
-                const float* hn = l2 && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? ensure_offsets(idx, s) : nullptr;
-                if (l2 && !l2_cert_ok(idx) && !hn) return 0;
-                const int grid_ub = device_cus(idx->device) * kRescueBlocksPerCu;  // the rescue launch: one or two workgroups per CU
-                const int slots = (R + kRescueQueries - 1) / kRescueQueries;
-                const size_t nneed = (size_t)(R + kRescueQueries) / need_per + 8;
-                const size_t nwords = nneed + slots;  // ... and the tile lists' lengths behind the need words (one memset)
-                MVDB_TRY(ws->need.reserve(nwords));
-                MVDB_TRY(ws->tlist.reserve((size_t)slots * ntiles_all));
-                MVDB_TRY(ws->cand.reserve((size_t)kRescueQueries * (grid_ub + 1) * kRescueKeep));
-                MVDB_TRY(ws->qsplit.reserve((size_t)2 * kRescueQueries * idx->d));
-                MVDB_TRY(ws->qnorm.reserve((size_t)3 * kRescueQueries));
-                MVDB_HIP(hipMemsetAsync(ws->need.p, 0, nwords * sizeof(int), s));
-                _Float16* qf = reinterpret_cast<_Float16*>(ws->qsplit.p);
-                float* qn2 = ws->qnorm.p;
-                float* qinv = qn2 + 2 * kRescueQueries;
-                float eps = (float)(half_eps(idx->d) * (double)idx->row_norm_bound * (1.0 + 1e-6));
-                if (hn) eps = (float)((double)eps + std::ldexp(1.0, -22) * (double)idx->row_norm_bound * (1.0 + 1e-6));  // (launch_half_pass: the subtraction)
-                {   // the launches' tile lists: what the refused queries' flags name (no flags: every tile)
-                    RescueTilesArgs ta;
-                    ta.tflags = flags_ok ? ws->tflags.p : nullptr;
-                    ta.twords = twords;
-                    ta.map = map;
-                    ta.nfail = ws->nfail.p;
-                    ta.seed_tiles = std::min<int64_t>(ntiles_all, device_cus(idx->device));  // (launch_half_pass: the seed launch's tiles)
-                    ta.ntiles = ntiles_all;
-                    ta.lists = ws->tlist.p;
-                    ta.counts = ws->need.p + nneed;
-                    ta.stats = ctr + 1;
-                    MVDB_TRY(launch_rescue_tiles(ta, slots, s));
-                }
-                for (int off2 = 0; off2 < R; off2 += kRescueQueries) {
-                    MVDB_TRY(launch_half_queries(qc + (int64_t)off2 * idx->ld, idx->ld, idx->d, kRescueQueries, kRescueQueries, xs, qf, qn2,
-                                                 qinv, s));
-                    HalfScanArgs ra;
-                    ra.X = idx->X;
-                    ra.n = n;
-                    ra.ld = idx->ld;
-                    ra.qf = qf;
-                    ra.qinv = qinv;
-                    ra.xscale = xs;
-                    ra.nq = std::min(kRescueQueries, R - off2);  // (slots past the call's queries can never be live)
-                    ra.mask = mask32;
-                    ra.Xh = Xh;
-                    ra.hn = hn;
-                    ra.stats = nullptr;
-                    ra.cand = ws->cand.p;
-                    ra.tile0 = 0;
-                    ra.tile1 = (n + 31) / 32;
-                    ra.thr0 = ws->qfloor.p + q0 + off2;
-                    ra.thr_eps = eps;
-                    ra.thr_qn = qn2;
-                    ra.gate = ws->nfail.p;
-                    ra.gate_lo = off2;
-                    ra.tile_list = ws->tlist.p + (size_t)(off2 / kRescueQueries) * ntiles_all;
-                    ra.tile_count = ws->need.p + nneed + off2 / kRescueQueries;
-                    int gx = 0;
-                    MVDB_TRY(launch_half_rescue_scan(idx->d, ra, idx->device, s, &gx));
-                    HalfRescueArgs rc;
-                    rc.keys = ws->cand.p;
-                    rc.nlists = gx;
-                    rc.X = idx->X;
-                    rc.ld = idx->ld;
-                    rc.d4 = idx->d4;
-                    rc.q = qc + (int64_t)off2 * idx->ld;
-                    rc.k = k;
-                    rc.label_offset = label_offset;
-                    rc.D = Dt + (int64_t)off2 * k;
-                    rc.I = It + (int64_t)off2 * k;
-                    rc.gate = ws->nfail.p;
-                    rc.gate_lo = off2;
-                    rc.need = ws->need.p + off2 / need_per;
-                    rc.per_pass = need_per;
-                    rc.l2 = l2 ? 1 : 0;
-                    MVDB_TRY(launch_half_rescue_certify(rc, s));
-                }
-                *need_out = ws->need.p;
-                return 0;
-            };
-            if (idx->metric == MVDB_METRIC_L2) {
-                // L2: the rescue pass, then — for what it could not hold — the exact single-query scan (sum (q - x)^2 directly),
-                // 32 compact queries per launch, each query's blocks enabled on the device (refused count and `need` word)
-                const int* need = nullptr;
-                MVDB_TRY(rescue(1, &need));
-                const int per = 32;
-                MVDB_TRY(ws->cand.reserve((size_t)per * scan_grid_upper_bound(idx->device) * k));
-                for (; off < R; off += per) {
-                    const int take = std::min(per, R - off);
-                    ScanArgs ga = a;
-                    ga.q = qc + (int64_t)off * idx->ld;
-                    ga.normalize_q = 0;
-                    ga.cand = ws->cand.p;
-                    ga.gate = ws->nfail.p;
-                    ga.gate_lo = off;
-                    ga.need = need ? need + off : nullptr;
-                    int nblocks = 0;
-                    MVDB_TRY(launch_scan(idx->metric, kModeTopK, ga, take, idx->device, s, &nblocks));
-                    MergeArgs mg;
-                    mg.keys = ws->cand.p;
-                    mg.nlists = nblocks;
-                    mg.k = k;
-                    mg.metric = idx->metric;
-                    mg.label_offset = label_offset;
-                    mg.D = Dt + (int64_t)off * k;
-                    mg.I = It + (int64_t)off * k;
-                    mg.gate = ws->nfail.p;
-                    mg.gate_lo = off;
-                    if (need) {   // one word per query: "pass" = query, its lists nblocks * k keys after the query before
-                        mg.need = need + off;
-                        mg.per_pass = 1;
-                        mg.pass_stride = (int64_t)nblocks * k;
-                    }
-                    hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
-                    MVDB_HIP(hipGetLastError());
-                }
-                off = R;
-            } else if (per_pass > 0 && !idx->kn.disable_mfma_scan) {
-                const int* need = nullptr;
-                MVDB_TRY(rescue(per_pass, &need));
-                MVDB_TRY(ws->cand.reserve((size_t)32 * scan_grid_upper_bound(idx->device) * k));
-                // (the GEMM scan keeps k <= 16 and takes no bitmap: those re-runs are all fp32-MFMA passes)
-                // every refused query through the gated fp32-MFMA pass, 32 at a time (launches beyond the refused count return at
-                // once).  Until round 5 the batch went to the 128-query GEMM-tiled scan after two such passes — 20-25 ms per 128
-                // queries at 10M x 512 where four MFMA passes take 14.
-                const int max_passes = (R + per_pass - 1) / per_pass;
-                {
-                    // ONE launch walks up to kGatedPassGroup passes on the device (pass p: compact queries [p per_pass, ...); each
-                    // enabled by the refused count and its `need` word), ONE merge launch covers the group's compact queries; the
-                    // groups share one list buffer in stream order (so the lists are O(1) in the batch: 8 passes x 5 MB at k = 10)
-                    const int64_t cand_stride = (int64_t)per_pass * scan_grid_upper_bound(idx->device) * k;
-                    MVDB_TRY(ws->cand.reserve((size_t)std::min(max_passes, kGatedPassGroup) * cand_stride));
-                    for (int p0 = 0; p0 < max_passes; p0 += kGatedPassGroup) {
-                        const int np = std::min(kGatedPassGroup, max_passes - p0), qoff = p0 * per_pass;
-                        MfmaScanArgs ma;
-                        ma.X = idx->X;
-                        ma.n = n;
-                        ma.ld = idx->ld;
-                        ma.q = qc + (int64_t)qoff * idx->ld;
-                        ma.nq = std::min(per_pass, R - qoff);
-                        ma.k = k;
-                        ma.cand = ws->cand.p;
-                        ma.mask = mask32;
-                        ma.thr0 = idx->kn.disable_rerun_floor ? nullptr : ws->qfloor.p + q0 + qoff;
-                        int nblocks = 0;
-                        MVDB_TRY(launch_mfma2_gated(KB, ma, idx->device, s, &nblocks, ws->nfail.p, qoff, need ? need + p0 : nullptr, np, per_pass,
-                                                    R - qoff, cand_stride));
-                        MergeArgs mg;
-                        mg.keys = ws->cand.p;
-                        mg.nlists = nblocks;
-                        mg.k = k;
-                        mg.metric = idx->metric;
-                        mg.label_offset = label_offset;
-                        mg.D = Dt + (int64_t)qoff * k;
-                        mg.I = It + (int64_t)qoff * k;
-                        mg.gate = ws->nfail.p;
-                        mg.gate_lo = qoff;
-                        mg.need = need ? need + p0 : nullptr;
-                        mg.per_pass = per_pass;
-                        mg.pass_stride = cand_stride;
-                        hipLaunchKernelGGL(merge_keys_kernel, dim3(std::min(np * per_pass, R - qoff)), dim3(kMergeThreads), 0, s, mg);
-                        MVDB_HIP(hipGetLastError());
-                    }
-                    off = R;
-                }
-            }
-            if (off < R && mask_dev) return fail(MVDB_ERR_ARG, "internal: bitmap re-run left to the GEMM scan");
-            if (off < R) MVDB_TRY(ws->cand.reserve((size_t)128 * scan_grid_upper_bound(idx->device) * k));
-            while (off < R) {
-                const int take = std::min(128, R - off);
-                int nblocks = 0;
-                MVDB_TRY(launch_gemm_scan(idx, qc + (int64_t)off * idx->ld, take, k, n, ws->cand.p, s, &nblocks, ws->nfail.p, off));
-                MergeArgs mg;
-                mg.keys = ws->cand.p;
-                mg.nlists = nblocks;
-                mg.k = k;
-                mg.metric = idx->metric;
-                mg.label_offset = label_offset;
-                mg.D = Dt + (int64_t)off * k;
-                mg.I = It + (int64_t)off * k;
-                mg.gate = ws->nfail.p;
-                mg.gate_lo = off;
-                hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
-                MVDB_HIP(hipGetLastError());
-                off += take;
-            }
-            hipLaunchKernelGGL(scatter_failed_kernel, dim3((unsigned)(((int64_t)R * k + 255) / 256)), dim3(256), 0, s, (const float*)Dt,
-                               (const int64_t*)It, (const int64_t*)map, (const int*)ws->nfail.p, (int64_t)R, k, D_dev, I_dev);
-            MVDB_HIP(hipGetLastError());
-        }
+        const float* qsrc = nullptr;
+        MVDB_TRY(certified_batch(idx, ws, a, q_dev, nq, k, normalize_q, n, label_offset, D_dev, I_dev, mask_dev, &q0, &qsrc));
         if (q0 == nq) return 0;
         return search_core(idx, ws, qsrc + (int64_t)q0 * idx->ld, nq - q0, k, 0, rows_dev, m, label_offset,
                            D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k, false, mask_dev);
@@ -1520,13 +1496,8 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
 
     if (masked_batch) {
         // ---- bitmap-selected rows, 2+ queries: staged fp32-MFMA passes of up to 32 (d <= 512) / 16 queries, exact ----------
-        const float* qsrc = q_dev;
-        if (normalize_q) {
-            MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
-            MVDB_HIP(hipMemcpyAsync(ws->qn.p, q_dev, (size_t)nq * idx->ld * sizeof(float), hipMemcpyDeviceToDevice, s));
-            MVDB_TRY(normalize_range(idx, ws->qn.p, nq, s));
-            qsrc = ws->qn.p;
-        }
+        const float* qsrc = nullptr;
+        MVDB_TRY(normalized_queries(idx, ws, q_dev, nq, normalize_q, &qsrc));
         const int per_pass = mfma_gated_queries(idx);
         MVDB_TRY(ws->cand.reserve((size_t)32 * scan_grid_upper_bound(idx->device) * k));
         for (int q0 = 0; q0 < nq; q0 += per_pass) {
@@ -1544,16 +1515,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
             int slot = prof_begin("ip_scan_mfma_masked", s);
             MVDB_TRY(launch_mfma2_gated(idx->d / 16, ma, idx->device, s, &nblocks, nullptr, 0));
             prof_end(slot, s);
-            MergeArgs mg;
-            mg.keys = ws->cand.p;
-            mg.nlists = nblocks;
-            mg.k = k;
-            mg.metric = idx->metric;
-            mg.label_offset = label_offset;
-            mg.D = D_dev + (int64_t)q0 * k;
-            mg.I = I_dev + (int64_t)q0 * k;
-            hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
-            MVDB_HIP(hipGetLastError());
+            MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
         }
         return 0;
     }
@@ -1561,14 +1523,8 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
     // Large batches are cut into chunks: >= 104 queries left -> one 128-query GEMM-tiled launch (compute-
     // bound, 13.7 ms at 10M x 512), fewer -> 32-query MFMA passes (4.0 ms each); measured crossover ~100.
     if (gemm_path_ok(idx, nq, k, restricted)) {
-        const float* qsrc = q_dev;
-        if (normalize_q) {
-            MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
-            MVDB_HIP(hipMemcpyAsync(ws->qn.p, q_dev, (size_t)nq * idx->ld * sizeof(float),
-                                    hipMemcpyDeviceToDevice, s));
-            MVDB_TRY(normalize_range(idx, ws->qn.p, nq, s));
-            qsrc = ws->qn.p;
-        }
+        const float* qsrc = nullptr;
+        MVDB_TRY(normalized_queries(idx, ws, q_dev, nq, normalize_q, &qsrc));
         MVDB_TRY(ws->cand.reserve((size_t)128 * scan_grid_upper_bound(idx->device) * k));
         const int min_nq = gemm_min_nq(idx, k);
         int q0 = 0;
@@ -1576,16 +1532,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
             const int take = std::min(nq - q0, 128);
             int nblocks = 0;
             MVDB_TRY(launch_gemm_scan(idx, qsrc + (int64_t)q0 * idx->ld, take, k, n, ws->cand.p, s, &nblocks));
-            MergeArgs mg;
-            mg.keys = ws->cand.p;
-            mg.nlists = nblocks;
-            mg.k = k;
-            mg.metric = idx->metric;
-            mg.label_offset = label_offset;
-            mg.D = D_dev + (int64_t)q0 * k;
-            mg.I = I_dev + (int64_t)q0 * k;
-            hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
-            MVDB_HIP(hipGetLastError());
+            MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
             q0 += take;
         }
         if (q0 == nq) return 0;
@@ -1596,14 +1543,8 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
 
     if (mfma_path_ok(idx, nq, k, restricted)) {
         // ---- several queries per corpus pass on the fp32 matrix cores ---------------------------
-        const float* qsrc = q_dev;
-        if (normalize_q) {
-            MVDB_TRY(ws->qn.reserve((size_t)nq * idx->ld));
-            MVDB_HIP(hipMemcpyAsync(ws->qn.p, q_dev, (size_t)nq * idx->ld * sizeof(float),
-                                    hipMemcpyDeviceToDevice, s));
-            MVDB_TRY(normalize_range(idx, ws->qn.p, nq, s));
-            qsrc = ws->qn.p;
-        }
+        const float* qsrc = nullptr;
+        MVDB_TRY(normalized_queries(idx, ws, q_dev, nq, normalize_q, &qsrc));
         const int grid_ub = scan_grid_upper_bound(idx->device);
         MVDB_TRY(ws->cand.reserve((size_t)32 * grid_ub * k));
         for (int q0 = 0; q0 < nq;) {
@@ -1631,16 +1572,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
                 MVDB_TRY(launch_mfma2<1>(KB, ma, idx->device, s, &nblocks, idx->metric));  // LDS-DMA staged, coalesced
             else
                 MVDB_TRY(launch_mfma_ng<1>(KB, ma, idx->device, s, &nblocks));
-            MergeArgs mg;
-            mg.keys = ws->cand.p;
-            mg.nlists = nblocks;
-            mg.k = k;
-            mg.metric = idx->metric;
-            mg.label_offset = label_offset;
-            mg.D = D_dev + (int64_t)q0 * k;
-            mg.I = I_dev + (int64_t)q0 * k;
-            hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
-            MVDB_HIP(hipGetLastError());
+            MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
             q0 += take;
         }
         return 0;
@@ -1651,17 +1583,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
         a.cand = ws->cand.p;
         int nblocks = 0;
         MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, nq, idx->device, s, &nblocks));
-        MergeArgs ma;
-        ma.keys = ws->cand.p;
-        ma.nlists = nblocks;
-        ma.k = k;
-        ma.metric = idx->metric;
-        ma.label_offset = label_offset;
-        ma.D = D_dev;
-        ma.I = I_dev;
-        hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(kMergeThreads), 0, s, ma);
-        MVDB_HIP(hipGetLastError());
-        return 0;
+        return launch_merge(idx, ws, nq, nblocks, k, label_offset, D_dev, I_dev);
     }
 
     // ---- large k: scores -> radix select -> sort ------------------------------------------------------
@@ -1705,42 +1627,113 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
     return 0;
 }
 
-// Stage host queries [nq,d] into ws->q (padded to ld) on ws->stream.
-int stage_queries(const mvdb_index* idx, Workspace* ws, const float* q_host, int nq) {
-    const size_t elems = (size_t)nq * idx->ld;
-    MVDB_TRY(ws->q.reserve(elems));
-    MVDB_TRY(ws->pin.reserve(elems * sizeof(float)));
-    float* st = (float*)ws->pin.p;
-    if (idx->ld == idx->d) {
-        memcpy(st, q_host, elems * sizeof(float));
-    } else {
-        memset(st, 0, elems * sizeof(float));
-        for (int i = 0; i < nq; ++i)
-            memcpy(st + (size_t)i * idx->ld, q_host + (size_t)i * idx->d, idx->d * sizeof(float));
-    }
-    MVDB_HIP(hipMemcpyAsync(ws->q.p, st, elems * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+// Copy `bytes` from the device to ws->pin_out on the workspace's stream and wait for them ("<what> failed: ..." otherwise).
+int copy_back(Workspace* ws, const void* src, size_t bytes, const char* what) {
+    MVDB_TRY(ws->pin_out.reserve(bytes));
+    hipError_t e = hipMemcpyAsync(ws->pin_out.p, src, bytes, hipMemcpyDeviceToHost, ws->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) return fail(MVDB_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return 0;
 }
 
-// Host API epilogue: results sit packed in ws->out ([I | D]); one async D2H into pinned staging, sync, unpack.
-int fetch_results(Workspace* ws, size_t total, float* D_host, int64_t* I_host) {
-    const size_t bytes = total * (sizeof(int64_t) + sizeof(float));
-    MVDB_TRY(ws->pin_out.reserve(bytes));
-    hipError_t e = hipMemcpyAsync(ws->pin_out.p, ws->out.p, bytes, hipMemcpyDeviceToHost, ws->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-    if (e != hipSuccess) return fail(MVDB_ERR_HIP, "search failed: %s", hipGetErrorString(e));
-    memcpy(I_host, ws->pin_out.p, total * sizeof(int64_t));
-    memcpy(D_host, (const char*)ws->pin_out.p + total * sizeof(int64_t), total * sizeof(float));
-    return 0;
-}
+// A host-pointer entry point's workspace: one of the index's own (private stream), given back on every path.  The caller
+// holds idx->mu shared, has made the index's device current and checks `ws` (NULL: mvdb_index::acquire failed).
+struct HostCall {
+    const mvdb_index* const idx;
+    Workspace* const ws;
+    explicit HostCall(const mvdb_index* i) : idx(i), ws(i->acquire()) {}
+    HostCall(const HostCall&) = delete;
+    HostCall& operator=(const HostCall&) = delete;
+    ~HostCall() {
+        if (ws) idx->release(ws);
+    }
+    // host queries [nq, d] into ws->q (padded to ld) on ws->stream
+    int stage(const float* q_host, int nq) {
+        const size_t elems = (size_t)nq * idx->ld;
+        MVDB_TRY(ws->q.reserve(elems));
+        MVDB_TRY(ws->pin.reserve(elems * sizeof(float)));
+        float* st = (float*)ws->pin.p;
+        if (idx->ld == idx->d) {
+            memcpy(st, q_host, elems * sizeof(float));
+        } else {
+            memset(st, 0, elems * sizeof(float));
+            for (int i = 0; i < nq; ++i)
+                memcpy(st + (size_t)i * idx->ld, q_host + (size_t)i * idx->d, idx->d * sizeof(float));
+        }
+        MVDB_HIP(hipMemcpyAsync(ws->q.p, st, elems * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        return 0;
+    }
+    // the call's results on the device, packed in ws->out: [I: total int64 | D: total fp32] -> ONE copy back
+    int results(size_t total, float** D_dev, int64_t** I_dev) {
+        MVDB_TRY(ws->out.reserve(total + (total + 1) / 2));
+        *I_dev = ws->out.p;
+        *D_dev = reinterpret_cast<float*>(ws->out.p + total);
+        return 0;
+    }
+    // epilogue: one async D2H into pinned staging, sync, unpack
+    int fetch(size_t total, float* D_host, int64_t* I_host) {
+        MVDB_TRY(copy_back(ws, ws->out.p, total * (sizeof(int64_t) + sizeof(float)), "search"));
+        memcpy(I_host, ws->pin_out.p, total * sizeof(int64_t));
+        memcpy(D_host, (const char*)ws->pin_out.p + total * sizeof(int64_t), total * sizeof(float));
+        return 0;
+    }
+};
 
 // A search being captured into a hipGraph: from now on this workspace keeps every buffer it outgrows (RetireScope), so a
-// later, larger eager call on the same stream cannot free memory the graph still names.
-void note_capture(Workspace* ws) {
+// later, larger eager call on the same stream cannot free memory the graph still names.  Returns ws->captured.
+bool note_capture(Workspace* ws) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (ws->stream && !ws->captured && hipStreamIsCapturing(ws->stream, &st) == hipSuccess &&
         st == hipStreamCaptureStatusActive)
         ws->captured = true;
+    return ws->captured;
+}
+
+// A device-pointer entry point's prologue (the caller holds idx->mu shared and has made the index's device current): the
+// stream's workspace, held for the call (one search at a time per stream workspace), the capture rule, and the queries
+// padded to the row stride.  `rc` is checked before `ws` / `q` are used.
+// Nothing a device entry point does behind this synchronises the stream or reads from the device: the call may be captured
+// into a hipGraph once an eager call of the same shape has sized the stream's workspace (allocation is not capturable).
+struct StreamCall {
+    Workspace* const ws;
+    std::unique_lock<std::mutex> use;
+    RetireScope keep;
+    const float* q;  // the queries at stride ld
+    int rc;
+    StreamCall(const mvdb_index* idx, void* stream, const float* q_dev, int nq)
+        : ws(idx->for_stream((hipStream_t)stream)),
+          use(ws ? std::unique_lock<std::mutex>(ws->use_mu) : std::unique_lock<std::mutex>()),
+          keep(ws && note_capture(ws) ? &ws->retired : nullptr),
+          q(q_dev),
+          rc(ws ? pad(idx, q_dev, nq) : fail(MVDB_ERR_HIP, "workspace allocation failed")) {}
+
+  private:
+    int pad(const mvdb_index* idx, const float* q_dev, int nq) {
+        if (idx->ld == idx->d) return 0;
+        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)), dim3(256), 0, ws->stream, ws->q.p, q_dev,
+                           (int64_t)nq, idx->d, idx->ld);
+        MVDB_HIP(hipGetLastError());
+        q = ws->q.p;
+        return 0;
+    }
+};
+
+// Branch-free min / max (and strict ascent) of a host row list: vectorises; a list can hold millions of rows.
+struct RowRange {
+    int64_t lo = 0, hi = -1;
+    bool sorted = true;  // strictly ascending
+};
+RowRange row_range(const int64_t* rows, int64_t m) {
+    RowRange r;
+    if (m <= 0) return r;
+    r.lo = r.hi = rows[0];
+    for (int64_t i = 1; i < m; ++i) {
+        r.lo = rows[i] < r.lo ? rows[i] : r.lo;
+        r.hi = rows[i] > r.hi ? rows[i] : r.hi;
+        r.sorted &= rows[i] > rows[i - 1];
+    }
+    return r;
 }
 
 int check_search_args(const mvdb_index* idx, const void* q, int nq, int k, const void* D,
@@ -2054,18 +2047,6 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     hipLaunchKernelGGL(code8_query_kernel, dim3(1), dim3(256), 0, s, a0.q, d, a0.normalize_q, idx->row_norm_bound, qhi, qlo, par, counter);
     MVDB_HIP(hipGetLastError());
 
-    auto merge = [&](int nlists, float* D, int64_t* I, int64_t lo, const int* g) {
-        MergeArgs ma;
-        ma.keys = ws->cand.p;
-        ma.nlists = nlists;
-        ma.k = k;
-        ma.metric = idx->metric;
-        ma.label_offset = lo;
-        ma.D = D;
-        ma.I = I;
-        ma.gate = g;
-        hipLaunchKernelGGL(merge_keys_kernel, dim3(1), dim3(kMergeThreads), 0, s, ma);
-    };
     // 1. the floor: exact scores of the seed sample (the row-list form of the exact kernel), their k-th best
     ScanArgs a = a0;
     a.cand = ws->cand.p;
@@ -2075,7 +2056,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         a.rows = idx->c8_seed;
         a.n = kCode8Seed;
         MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
-        merge(nblocks, seedD, seedI, 0, nullptr);
+        MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, 0, seedD, seedI));
     }
     // 2. the prefilter over the codes
     Code8ScanArgs c;
@@ -2105,7 +2086,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         a.rows = list;
         a.n = cap;
         MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
-        merge(nblocks, D_dev, I_dev, 0, nullptr);
+        MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, 0, D_dev, I_dev));
         hipLaunchKernelGGL(code8_relabel_kernel, dim3(1), dim3(64), 0, s, I_dev, k, (const int64_t*)list, label_offset);
     }
     // 5. fallback, enabled on the device: the full exact scan overwrites the result
@@ -2116,8 +2097,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     if (d == 512) MVDB_TRY((launch_gated_ip_scan<64, 2, 2>(a, idx->device, s, &nblocks)));
     else if (d == 1024) MVDB_TRY((launch_gated_ip_scan<64, 4, 1>(a, idx->device, s, &nblocks)));
     else MVDB_TRY((launch_gated_ip_scan<32, 3, 4>(a, idx->device, s, &nblocks)));
-    merge(nblocks, D_dev, I_dev, label_offset, gate);
-    MVDB_HIP(hipGetLastError());
+    MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, label_offset, D_dev, I_dev, gate));
     *served = true;
     return 0;
 }
@@ -2258,38 +2238,22 @@ long long mvdb_index_single_route_suspensions(const mvdb_index* idx) {
 
 int mvdb_index_free(mvdb_index* idx) {
     if (!idx) return 0;
+    DeviceGuard dg(idx->device);  // every free below, the members' own included, runs on the index's device
     {
         std::unique_lock<std::shared_mutex> lk(idx->mu);
-        DeviceGuard dg(idx->device);
         (void)quiesce(idx);
         if (idx->mut) (void)hipStreamDestroy(idx->mut);
-        if (idx->normmax) (void)hipFree(idx->normmax);
-        if (idx->ctmp) (void)hipFree(idx->ctmp);
-        if (idx->sq_fail_dev) (void)hipFree(idx->sq_fail_dev);
-        idx->sq_fail_host.release();
-        if (idx->rf_dev) (void)hipFree(idx->rf_dev);
-        idx->rf_host.release();
+        void* words[] = {idx->normmax, idx->ctmp, idx->sq_fail_dev, idx->rf_dev, idx->c8_ctr_dev, idx->rg_ctr_dev};
+        for (void* p : words)
+            if (p) (void)hipFree(p);
         drop_shadow(idx);
         drop_code8(idx);
-        if (idx->c8_ctr_dev) (void)hipFree(idx->c8_ctr_dev);
-        idx->c8_stats.release();
-        if (idx->rg_ctr_dev) (void)hipFree(idx->rg_ctr_dev);
-        idx->rg_stats.release();
-        for (Workspace* w : idx->free_ws) {
-            w->destroy();
-            delete w;
-        }
-        for (auto& kv : idx->stream_ws) {
-            kv.second->destroy();
-            delete kv.second;
-        }
-        if (idx->default_stream_ws) {
-            idx->default_stream_ws->destroy();
-            delete idx->default_stream_ws;
-        }
+        for (Workspace* w : idx->free_ws) delete w;
+        for (auto& kv : idx->stream_ws) delete kv.second;
+        delete idx->default_stream_ws;
         if (idx->X) (void)hipFree(idx->X);
     }
-    delete idx;
+    delete idx;  // (the host-mapped mirrors it owns go here)
     return 0;
 }
 
@@ -2699,19 +2663,15 @@ int mvdb_index_search(const mvdb_index* idx, const float* q_host, int nq, int k,
     MVDB_TRY(check_search_args(idx, q_host, nq, k, D_host, I_host));
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
-    do {
-        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
-        const size_t total = (size_t)nq * k;
-        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;  // total int64 + total fp32
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
-        if ((rc = search_core(idx, ws, ws->q.p, nq, k, normalize_q, nullptr, 0, 0, D_dev, ws->out.p))) break;
-        rc = fetch_results(ws, total, D_host, I_host);
-    } while (0);
-    idx->release(ws);
-    return rc;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(search_core(idx, call.ws, call.ws->q.p, nq, k, normalize_q, nullptr, 0, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
 }
 
 int mvdb_index_search_subset(const mvdb_index* idx, const float* q_host, int nq, int k,
@@ -2721,42 +2681,26 @@ int mvdb_index_search_subset(const mvdb_index* idx, const float* q_host, int nq,
     if (m < 0) return fail(MVDB_ERR_ARG, "negative subset size");
     if (m > 0 && !rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
-    {   // range check as a branch-free min/max reduction (vectorises; the list can hold millions of rows)
-        int64_t lo = 0, hi = -1;
-        if (m > 0) {
-            lo = hi = rows_host[0];
-            for (int64_t i = 1; i < m; ++i) {
-                lo = rows_host[i] < lo ? rows_host[i] : lo;
-                hi = rows_host[i] > hi ? rows_host[i] : hi;
-            }
-        }
-        if (m > 0 && (lo < 0 || hi >= idx->n))
-            return fail(MVDB_ERR_ARG, "subset row %lld out of range [0,%lld)", (long long)(lo < 0 ? lo : hi),
-                        (long long)idx->n);
-    }
+    const RowRange rr = row_range(rows_host, m);
+    if (m > 0 && (rr.lo < 0 || rr.hi >= idx->n))
+        return fail(MVDB_ERR_ARG, "subset row %lld out of range [0,%lld)", (long long)(rr.lo < 0 ? rr.lo : rr.hi),
+                    (long long)idx->n);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
-    do {
-        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
-        const size_t total = (size_t)nq * k;
-        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
-        if ((rc = ws->rows.reserve((size_t)std::max<int64_t>(m, 1)))) break;
-        if (m > 0) {
-            hipError_t e = hipMemcpyAsync(ws->rows.p, rows_host, (size_t)m * sizeof(int64_t),
-                                          hipMemcpyHostToDevice, ws->stream);
-            if (e != hipSuccess) {
-                rc = fail(MVDB_ERR_HIP, "subset upload failed: %s", hipGetErrorString(e));
-                break;
-            }
-        }
-        if ((rc = search_core(idx, ws, ws->q.p, nq, k, normalize_q, ws->rows.p, m, 0, D_dev, ws->out.p))) break;
-        rc = fetch_results(ws, total, D_host, I_host);
-    } while (0);
-    idx->release(ws);
-    return rc;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* ws = call.ws;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(ws->rows.reserve((size_t)std::max<int64_t>(m, 1)));
+    if (m > 0) {
+        hipError_t e = hipMemcpyAsync(ws->rows.p, rows_host, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ws->stream);
+        if (e != hipSuccess) return fail(MVDB_ERR_HIP, "subset upload failed: %s", hipGetErrorString(e));
+    }
+    MVDB_TRY(search_core(idx, ws, ws->q.p, nq, k, normalize_q, ws->rows.p, m, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
 }
 
 int mvdb_index_search_device(const mvdb_index* idx, const float* q_dev, int nq, int k,
@@ -2765,23 +2709,10 @@ int mvdb_index_search_device(const mvdb_index* idx, const float* q_dev, int nq, 
     MVDB_TRY(check_search_args(idx, q_dev, nq, k, D_dev, I_dev));
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {  // pad the dense queries to the row stride
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
-                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
-    // Nothing below synchronises the stream or reads from the device (certification failures of the batch passes are
-    // re-run by device-gated launches): the call may be captured into a hipGraph once an eager call of the same shape
-    // has sized the stream's workspace (allocation is not capturable).
-    return search_core(idx, ws, q, nq, k, normalize_q, nullptr, 0, label_offset, D_dev, I_dev);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    // (certification failures of the batch passes are re-run by device-gated launches: nothing here reads from the device)
+    return search_core(idx, call.ws, call.q, nq, k, normalize_q, nullptr, 0, label_offset, D_dev, I_dev);
 }
 
 __global__ void map_subset_labels_kernel(int64_t* I, int64_t total, const int64_t* __restrict__ rows,
@@ -2801,22 +2732,12 @@ int mvdb_index_search_subset_device(const mvdb_index* idx, const float* q_dev, i
     if (m > 0 && !rows_dev) return fail(MVDB_ERR_ARG, "rows is NULL");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
-                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    Workspace* ws = call.ws;
     // m == 0: search_core's empty-corpus branch needs a non-NULL row list to take the subset meaning
     const int64_t* rows = m > 0 ? rows_dev : reinterpret_cast<const int64_t*>(ws->st);
-    MVDB_TRY(search_core(idx, ws, q, nq, k, normalize_q, rows, m, map_labels ? 0 : label_offset, D_dev, I_dev));
+    MVDB_TRY(search_core(idx, ws, call.q, nq, k, normalize_q, rows, m, map_labels ? 0 : label_offset, D_dev, I_dev));
     if (map_labels && m > 0) {
         const int64_t total = (int64_t)nq * k;
         hipLaunchKernelGGL(map_subset_labels_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ws->stream,
@@ -2843,20 +2764,10 @@ int mvdb_index_search_masked_device(const mvdb_index* idx, const float* q_dev, i
     if (labels != 0 && labels != 1) return fail(MVDB_ERR_ARG, "labels must be 0 (positions) or 1 (row numbers)");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
-                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
-    MVDB_TRY(search_core(idx, ws, q, nq, k, normalize_q, nullptr, 0, labels == 1 ? label_offset : 0, D_dev, I_dev, true, mask_dev));
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    Workspace* ws = call.ws;
+    MVDB_TRY(search_core(idx, ws, call.q, nq, k, normalize_q, nullptr, 0, labels == 1 ? label_offset : 0, D_dev, I_dev, true, mask_dev));
     return finish_mask_labels(idx, ws, nq, k, mask_dev, labels, I_dev);
 }
 
@@ -2867,30 +2778,24 @@ int mvdb_index_search_masked(const mvdb_index* idx, const float* q_host, int nq,
     if (labels != 0 && labels != 1) return fail(MVDB_ERR_ARG, "labels must be 0 (positions) or 1 (row numbers)");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
-    do {
-        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
-        const size_t total = (size_t)nq * k;
-        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
-        const size_t words = (size_t)((idx->n + 63) / 64);
-        if ((rc = ws->rows.reserve(std::max<size_t>(words, 1)))) break;  // 8-byte words: the row-list buffer serves
-        uint64_t* mask_dev = reinterpret_cast<uint64_t*>(ws->rows.p);
-        if (words) {
-            hipError_t e = hipMemcpyAsync(mask_dev, mask_host, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream);
-            if (e != hipSuccess) {
-                rc = fail(MVDB_ERR_HIP, "mask upload failed: %s", hipGetErrorString(e));
-                break;
-            }
-        }
-        if ((rc = search_core(idx, ws, ws->q.p, nq, k, normalize_q, nullptr, 0, 0, D_dev, ws->out.p, true, mask_dev))) break;
-        if ((rc = finish_mask_labels(idx, ws, nq, k, mask_dev, labels, ws->out.p))) break;
-        rc = fetch_results(ws, total, D_host, I_host);
-    } while (0);
-    idx->release(ws);
-    return rc;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* ws = call.ws;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    const size_t words = (size_t)((idx->n + 63) / 64);
+    MVDB_TRY(ws->rows.reserve(std::max<size_t>(words, 1)));  // 8-byte words: the row-list buffer serves
+    uint64_t* mask_dev = reinterpret_cast<uint64_t*>(ws->rows.p);
+    if (words) {
+        hipError_t e = hipMemcpyAsync(mask_dev, mask_host, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream);
+        if (e != hipSuccess) return fail(MVDB_ERR_HIP, "mask upload failed: %s", hipGetErrorString(e));
+    }
+    MVDB_TRY(search_core(idx, ws, ws->q.p, nq, k, normalize_q, nullptr, 0, 0, D_dev, I_dev, true, mask_dev));
+    MVDB_TRY(finish_mask_labels(idx, ws, nq, k, mask_dev, labels, I_dev));
+    return call.fetch(total, D_host, I_host);
 }
 
 // ---- resident row sets: a filter's rows uploaded ONCE, searched many times ---------------------------------------------
@@ -2929,19 +2834,10 @@ int mvdb_rowset_create(const mvdb_index* idx, const int64_t* rows_host, int64_t 
     if (m > 0 && !rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     const int64_t n = idx->n;
-    bool sorted = true;
-    {
-        int64_t lo = 0, hi = -1, prev = -1;
-        for (int64_t i = 0; i < m; ++i) {
-            const int64_t r = rows_host[i];
-            lo = (i == 0 || r < lo) ? r : lo;
-            hi = (i == 0 || r > hi) ? r : hi;
-            sorted &= r > prev;
-            prev = r;
-        }
-        if (m > 0 && (lo < 0 || hi >= n))
-            return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)(lo < 0 ? lo : hi), (long long)n);
-    }
+    const RowRange rr = row_range(rows_host, m);
+    if (m > 0 && (rr.lo < 0 || rr.hi >= n))
+        return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)(rr.lo < 0 ? rr.lo : rr.hi), (long long)n);
+    const bool sorted = rr.sorted;
     DeviceGuard dg(idx->device);
     mvdb_rowset* rs = new mvdb_rowset();
     rs->owner = idx->serial;
@@ -3065,19 +2961,15 @@ int mvdb_index_search_rowset(const mvdb_index* idx, const float* q_host, int nq,
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     MVDB_TRY(rowset_check(idx, rs));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
-    do {
-        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
-        const size_t total = (size_t)nq * k;
-        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
-        if ((rc = rowset_search_core(idx, ws, ws->q.p, nq, k, normalize_q, rs, 0, D_dev, ws->out.p))) break;
-        rc = fetch_results(ws, total, D_host, I_host);
-    } while (0);
-    idx->release(ws);
-    return rc;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(rowset_search_core(idx, call.ws, call.ws->q.p, nq, k, normalize_q, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
 }
 
 int mvdb_index_search_rowset_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q,
@@ -3086,20 +2978,10 @@ int mvdb_index_search_rowset_device(const mvdb_index* idx, const float* q_dev, i
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     MVDB_TRY(rowset_check(idx, rs));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
-                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
-    return rowset_search_core(idx, ws, q, nq, k, normalize_q, rs, label_offset, D_dev, I_dev);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    Workspace* ws = call.ws;
+    return rowset_search_core(idx, ws, call.q, nq, k, normalize_q, rs, label_offset, D_dev, I_dev);
 }
 
 }  // extern "C"
@@ -3495,17 +3377,15 @@ int range_emit_phase(const mvdb_index* idx, Workspace* ws, int nq, int64_t seg, 
 }
 
 // host entry point, one tile of queries already staged in ws->q
-int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshold, const float* thrs, int normalize_q, const mvdb_rowset* rs,
+int range_host_tile(const mvdb_index* idx, HostCall& call, int nq, float threshold, const float* thrs, int normalize_q, const mvdb_rowset* rs,
                     int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host, bool* shared) {
+    Workspace* ws = call.ws;
     const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
     MVDB_TRY(ws->rcounts.reserve((size_t)nq));
     const int64_t* rows = nullptr;
     MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, thrs, normalize_q, rs, cap, seg, ws->rcounts.p, &rows, shared));
     // the counts come back first: the sort and the copy are sized by what is there, not by the capacity
-    MVDB_TRY(ws->pin_out.reserve((size_t)nq * sizeof(unsigned long long)));
-    hipError_t e = hipMemcpyAsync(ws->pin_out.p, ws->rcounts.p, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, ws->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-    if (e != hipSuccess) return fail(MVDB_ERR_HIP, "range search failed: %s", hipGetErrorString(e));
+    MVDB_TRY(copy_back(ws, ws->rcounts.p, (size_t)nq * sizeof(unsigned long long), "range search"));
     int64_t width = 0;
     for (int i = 0; i < nq; ++i) {
         counts_host[i] = (int64_t)((const unsigned long long*)ws->pin_out.p)[i];
@@ -3514,15 +3394,12 @@ int range_host_tile(const mvdb_index* idx, Workspace* ws, int nq, float threshol
     if (cap == 0) return 0;
     const size_t total = (size_t)nq * (size_t)width;
     if (width > 0) {
-        MVDB_TRY(ws->out.reserve(total + (total + 1) / 2));  // [I: total int64 | D: total fp32]
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
+        float* D_dev = nullptr;
+        int64_t* I_dev = nullptr;
+        MVDB_TRY(call.results(total, &D_dev, &I_dev));
         MVDB_TRY(range_sort_phase(ws, nq, seg, cap, pow2ceil(std::max<int64_t>(width, 2)), ws->rcounts.p));
-        MVDB_TRY(range_emit_phase(idx, ws, nq, seg, cap, width, ws->rcounts.p, rows, 0, D_dev, ws->out.p));
-        const size_t bytes = total * (sizeof(int64_t) + sizeof(float));
-        MVDB_TRY(ws->pin_out.reserve(bytes));
-        e = hipMemcpyAsync(ws->pin_out.p, ws->out.p, bytes, hipMemcpyDeviceToHost, ws->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-        if (e != hipSuccess) return fail(MVDB_ERR_HIP, "range search failed: %s", hipGetErrorString(e));
+        MVDB_TRY(range_emit_phase(idx, ws, nq, seg, cap, width, ws->rcounts.p, rows, 0, D_dev, I_dev));
+        MVDB_TRY(copy_back(ws, ws->out.p, total * (sizeof(int64_t) + sizeof(float)), "range search"));
     }
     const int64_t* I_st = (const int64_t*)ws->pin_out.p;
     const float* D_st = (const float*)((const char*)ws->pin_out.p + total * sizeof(int64_t));
@@ -3555,32 +3432,31 @@ static int range_search_host(const mvdb_index* idx, const float* q_host, int nq,
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     if (rs) MVDB_TRY(rowset_check(idx, rs));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* ws = call.ws;
     bool shared = false;
     std::vector<float> tkeys;  // the thresholds in the units of the keys
-    for (int t0 = 0; t0 < nq && !rc; t0 += kRangeTile) {
+    auto tile = [&](int t0) -> int {
         const int take = std::min(kRangeTile, nq - t0);
-        if ((rc = stage_queries(idx, ws, q_host + (size_t)t0 * idx->d, take))) break;
+        MVDB_TRY(call.stage(q_host + (size_t)t0 * idx->d, take));
         const float* thrs = nullptr;
         if (thresholds_host) {
             tkeys.assign(thresholds_host + t0, thresholds_host + t0 + take);
             if (idx->metric != MVDB_METRIC_IP)
                 for (float& v : tkeys) v = -v;
-            if ((rc = ws->rthr.reserve((size_t)take))) break;
+            MVDB_TRY(ws->rthr.reserve((size_t)take));
             // (pageable memory: the copy has left the host buffer when the call returns)
-            if (hipMemcpyAsync(ws->rthr.p, tkeys.data(), (size_t)take * sizeof(float), hipMemcpyHostToDevice, ws->stream) != hipSuccess) {
-                rc = fail(MVDB_ERR_HIP, "range search: the thresholds' upload failed");
-                break;
-            }
+            if (hipMemcpyAsync(ws->rthr.p, tkeys.data(), (size_t)take * sizeof(float), hipMemcpyHostToDevice, ws->stream) != hipSuccess)
+                return fail(MVDB_ERR_HIP, "range search: the thresholds' upload failed");
             thrs = ws->rthr.p;
         }
-        rc = range_host_tile(idx, ws, take, threshold, thrs, normalize_q, rs, cap, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
-                             cap ? I_host + (size_t)t0 * cap : nullptr, &shared);
-    }
-    if (shared) idx->rg_shared_calls.fetch_add(1);
-    idx->release(ws);
+        return range_host_tile(idx, call, take, threshold, thrs, normalize_q, rs, cap, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
+                               cap ? I_host + (size_t)t0 * cap : nullptr, &shared);
+    };
+    int rc = 0;
+    for (int t0 = 0; t0 < nq && !rc; t0 += kRangeTile) rc = tile(t0);
+    if (shared) idx->rg_shared_calls.fetch_add(1);  // (a call that failed behind the shared pass counts too)
     return rc;
 }
 
@@ -3591,19 +3467,10 @@ static int range_search_dev(const mvdb_index* idx, const float* q_dev, int nq, f
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     if (rs) MVDB_TRY(rowset_check(idx, rs));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {  // pad the dense queries to the row stride
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)), dim3(256), 0, ws->stream, ws->q.p, q_dev,
-                           (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    Workspace* ws = call.ws;
+    const float* q = call.q;
     const float* thrs = thresholds_dev;
     if (thrs && idx->metric != MVDB_METRIC_IP) {  // the key's score of an L2 row is -distance
         MVDB_TRY(ws->rthr.reserve((size_t)nq));
@@ -3876,19 +3743,15 @@ int mvdb_index_search_grouped(const mvdb_index* idx, const float* q_host, int nq
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     MVDB_TRY(check_grouped_sets(idx, nq, sets));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->acquire();
-    if (!ws) return MVDB_ERR_HIP;
-    int rc = 0;
-    do {
-        if ((rc = stage_queries(idx, ws, q_host, nq))) break;
-        const size_t total = (size_t)nq * k;
-        if ((rc = ws->out.reserve(total + (total + 1) / 2))) break;
-        float* D_dev = reinterpret_cast<float*>(ws->out.p + total);
-        if ((rc = grouped_search_core(idx, ws, ws->q.p, nq, k, normalize_q, sets, 0, D_dev, ws->out.p))) break;
-        rc = fetch_results(ws, total, D_host, I_host);
-    } while (0);
-    idx->release(ws);
-    return rc;
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(grouped_search_core(idx, call.ws, call.ws->q.p, nq, k, normalize_q, sets, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
 }
 
 int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q,
@@ -3898,20 +3761,10 @@ int mvdb_index_search_grouped_device(const mvdb_index* idx, const float* q_dev, 
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     MVDB_TRY(check_grouped_sets(idx, nq, sets));
     DeviceGuard dg(idx->device);
-    Workspace* ws = idx->for_stream((hipStream_t)stream);
-    if (!ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
-    std::lock_guard<std::mutex> use(ws->use_mu);
-    note_capture(ws);
-    RetireScope keep(ws->captured ? &ws->retired : nullptr);
-    const float* q = q_dev;
-    if (idx->ld != idx->d) {
-        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((int64_t)nq * idx->ld + 255) / 256)),
-                           dim3(256), 0, ws->stream, ws->q.p, q_dev, (int64_t)nq, idx->d, idx->ld);
-        MVDB_HIP(hipGetLastError());
-        q = ws->q.p;
-    }
-    return grouped_search_core(idx, ws, q, nq, k, normalize_q, sets, label_offset, D_dev, I_dev);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    Workspace* ws = call.ws;
+    return grouped_search_core(idx, ws, call.q, nq, k, normalize_q, sets, label_offset, D_dev, I_dev);
 }
 
 int mvdb_merge_topk_device(int metric, int nlists, int nq, int k, const float* D_dev,

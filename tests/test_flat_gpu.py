@@ -1953,3 +1953,41 @@ def test_rescue_launches_skip_tiles_no_refused_query_flagged(native, monkeypatch
         ok, msg = flat.adjudicate(src, q[i], k, D[i], I[i], tol=1e-4, tie_eps=4e-6)
         assert ok, (i, msg)
     idx.close()
+
+
+def test_freeing_an_index_returns_its_device_memory(native, monkeypatch):
+    """Every buffer a search workspace holds is freed with its index.  One cycle: a fresh index of 400,000 x 256 normalised rows
+    answers 1,024 queries (k = 10) — one whole tile of search_core's queries through the certified pass, tile flags kept
+    (MVDB_TILE_FLAGS=1, MVDB_TILE_FLAG_MIN_TILES=1) and the rescue pass set up — and is closed.  The call asks for, among others,
+        tflags  1,024 queries x ceil(ceil(400,000 / 32) / 32) = 1,024 x 391 words of 4 bytes          = 1,601,536 bytes
+        tlist   ceil(1,024 / 128) = 8 rescue launches x 12,500 tiles x 4 bytes                        =   400,000 bytes
+        qfloor  (2 x 1,024 + 128) floats, need (1,024 + 128) / 32 + 8 + 8 words                       — a few KB,
+    the four buffers a hand-kept release list once forgot: at least 2.0 MB lost per cycle (the allocator's slack and granularity
+    only add to it), 32 MB over 16 cycles.  Bound: the free device memory drops by less than 16 MB — half of that — over 16 cycles.
+    The card may be shared, so three rounds are measured and the smallest drop counts: a leak shows in every round, a
+    neighbour's allocation only in the round it lands in."""
+    import torch
+    monkeypatch.setenv("MVDB_TILE_FLAGS", "1")
+    monkeypatch.setenv("MVDB_TILE_FLAG_MIN_TILES", "1")
+    n, d, nq, k = 400_000, 256, 1024, 10
+    q = flat.synth(nq, d, 5678)
+    flat.normalize_l2(q)
+
+    def cycle():
+        idx = native.FlatIndex(d)
+        idx.reserve(n)
+        idx.add_synthetic(n, 1234, normalize=True)
+        D, I = idx.search(q, k)
+        idx.close()
+        return I
+
+    I = cycle()   # warm-up: the runtime's one-time allocations, the process-wide re-run counter
+    assert (I >= 0).all()
+    drops = []
+    for _ in range(3):
+        before = torch.cuda.mem_get_info(0)[0]
+        for _ in range(16):
+            cycle()
+        drops.append(before - torch.cuda.mem_get_info(0)[0])
+    print("free device memory lost over 16 create / search / free cycles, per round:", drops)
+    assert min(drops) < 16e6, drops
