@@ -163,6 +163,33 @@ int mvdb_index_get_rows(const mvdb_index* idx, int64_t row0, int64_t n, float* o
  *                                                minivectordb/vector_database.py:126, :139-152 */
 int mvdb_index_remove_rows(mvdb_index* idx, const int64_t* rows_host, int64_t m);
 
+/* Overwrite the m listed stored rows with x[m,d]; row numbers, ntotal, capacity and every device pointer stay as they are.
+ * rows_host: each in [0, ntotal), any order; a duplicate, an out-of-range row or a NULL pointer with m > 0 is MVDB_ERR_ARG and
+ * leaves the index untouched (the list is a host array: it is checked before anything is enqueued).  m == 0: no-op, returns 0.
+ * Takes the index exclusively and waits for its enqueued searches, as add does; works on the mutators' stream; returns when
+ * the rows are in place (the caller's buffers are free again).
+ * Afterwards no search can tell the index from one built by add of the final rows in the same order:
+ *   - the fp32 row is, bit for bit, what add(..., normalize) writes for that input (the same normalisation arithmetic, a
+ *     zero-norm row left alone, the padding up to the row stride zeroed);
+ *   - the fp16 shadow, the |x|^2/2 offsets and the int8 code, where present and covering the row, get what their converters
+ *     write for the stored row (the same device code as add's, driven by the list).  Nothing is dropped or rebuilt:
+ *     mvdb_index_shadow_rows, mvdb_index_code8_rows and the counters read the same before and after, the wait before a dropped
+ *     code is rebuilt is not restarted, nothing is reallocated.  A derived store that is absent or was emptied by a delete is
+ *     left as it is;
+ *   - rows are not renumbered: resident row sets (list and bitmap form) stay valid and mean the same row numbers; a graph
+ *     captured on a caller's stream stays replayable and sees the new rows.
+ * The norm bounds only ever widen, as with add: they are updated from the new rows and never narrowed for the rows that went
+ * away (a non-finite new row leaves the bound non-finite, as a raw add does).  One consequence: if the widened bound moves the
+ * shadow's scale, the shadow is emptied exactly as add does it and the next batch search converts in place.
+ * Cost: proportional to m * d, never to ntotal; host rows go through a bounded staging buffer (32 MiB, kept by the index) in
+ * chunks, a fixed number of launches per chunk.  No reference counterpart (it raises on a duplicate id). */
+int mvdb_index_set_rows(mvdb_index* idx, const int64_t* rows_host, const float* x_host, int64_t m, int normalize);
+
+/* Same, the new rows already in device memory (x_dev[m,d], dense, same GPU; complete, or ordered before the legacy stream, as
+ * for mvdb_index_add_device).  The row numbers are still a host array. */
+int mvdb_index_set_rows_device(mvdb_index* idx, const int64_t* rows_host, const float* x_dev /*[m,d] dense, same GPU*/, int64_t m,
+                               int normalize);
+
 /* k nearest rows for nq queries.  q_host[nq,d], D_host[nq,k], I_host[nq,k].
  * normalize_q != 0 L2-normalises each query on the device first.
  * Every path returns exact-fp32 scores of the exact top-k.  Which pass answers a call (csrc/mvdb.hip: search_core):
@@ -473,6 +500,13 @@ int mvdb_cos8_get_codes(const mvdb_cos8* ix, int64_t row0, int64_t n, int8_t* co
 
 /* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
 int mvdb_cos8_remove_rows(mvdb_cos8* ix, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows with the quantised x[m,d] (x_host: uploaded in chunks; x_dev: dense, same GPU).  Codes
+ * and a2 are what add gives for the same input (one quantisation rule).  rows_host is a host array, each row in [0, ntotal),
+ * any order; a duplicate, an out-of-range row or a NULL pointer with m > 0 is MVDB_ERR_ARG and leaves the index untouched;
+ * m == 0 returns 0.  Exclusive like add; rows are not renumbered, so resident row sets stay valid; nothing is reallocated. */
+int mvdb_cos8_set_rows(mvdb_cos8* ix, const int64_t* rows_host, const float* x_host, int64_t m);
+int mvdb_cos8_set_rows_device(mvdb_cos8* ix, const int64_t* rows_host, const float* x_dev, int64_t m);
 
 /* k nearest rows for nq fp32 queries (quantised on the device by the same rule): q_host[nq,d], D_host[nq,k] distances,
  * I_host[nq,k] row numbers. */

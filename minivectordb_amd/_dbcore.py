@@ -180,6 +180,24 @@ class _RowStore:
             self.synced -= len(dev)
         self._cache = None
 
+    def replace(self, rows, vectors, index):
+        """Overwrite the stacked rows `rows` (distinct) with vectors[len(rows), d]: the rows the device holds through ONE
+        `index.set_rows` (normalised there, as `flush` has them normalised), the rows still waiting for a build in their host
+        block.  Nothing moves and no host copy of a synced row is kept.  The device goes first: if it refuses, nothing changed."""
+        rows = np.asarray(rows, dtype=np.int64)
+        vectors = np.asarray(vectors, dtype=np.float32)
+        on_device = rows < self.synced
+        if on_device.any():
+            index.set_rows(rows[on_device], vectors[on_device], normalize=True)
+        if not on_device.all():
+            starts = np.cumsum([0] + [b.shape[0] for b in self.pending])
+            for r, v in zip(rows[~on_device] - self.synced, vectors[~on_device]):
+                b = int(np.searchsorted(starts, r, side="right")) - 1
+                if not self.pending[b].flags.writeable:
+                    self.pending[b] = self.pending[b].copy()
+                self.pending[b][r - starts[b]] = v
+        self._cache = None
+
     def row(self, r, index):
         """A fresh copy of stacked row r (the reference hands out a view of an array that every write REPLACES, so
         an earlier result never changes under the caller, vector_database.py:72,104,126)."""
@@ -413,6 +431,38 @@ class _ValueIndex:
             entry = self.keys.get(key)
             if entry is not None:
                 entry[1].pop(handle, None)   # (hashable values: the dead handle is filtered out at query time)
+
+
+    def note_update(self, handle, old, new):
+        """The metadata of a LIVE handle is replaced (update_embedding).  `note_delete` alone would not do: it leaves a
+        hashable value's handle in place and relies on the handle being dead.  The handle leaves the slots of the old dict and
+        enters those of the new one at its sorted position (handle arrays stay ascending: `_IdIndex.rows_of`)."""
+        for key, field in old.items():
+            entry = self.keys.get(key)
+            if entry is None:
+                continue
+            entry[1].pop(handle, None)
+            try:
+                slot = entry[0].get(field)
+            except TypeError:
+                continue
+            if slot is not None:
+                at = bisect.bisect_left(slot, handle)
+                if at < len(slot) and slot[at] == handle:
+                    del slot[at]
+                if not len(slot):
+                    del entry[0][field]
+        for key, field in new.items():
+            entry = self.keys.get(key)
+            if entry is None:
+                continue   # built when a filter first names the key
+            try:
+                slot = entry[0].get(field)
+                if slot is None:
+                    slot = entry[0][field] = array('q')
+                bisect.insort(slot, handle)
+            except TypeError:
+                entry[1][handle] = field
 
 
 class FilterAndRerankMixin:
@@ -1031,3 +1081,76 @@ class FilterAndRerankMixin:
         if steepest > 0.2:
             return list(range(drops.index(steepest) + 1, len(score_list)))
         return []
+
+
+class UpdateMixin:
+    """``update_embedding`` / ``update_embeddings_batch`` of the database classes that write (no reference counterpart: the
+    reference raises on a duplicate id, and so does ``store_embedding`` here).  The id keeps its row, its handle and its
+    place in its shard file; the embedding is overwritten where it lives (`_RowStore.replace`: the device row through
+    ``set_rows``, which keeps every derived store of the index in step), the metadata dict is REPLACED, not merged.
+
+    Needs what FilterAndRerankMixin needs; a class that persists per id overrides `_persist_update`."""
+
+    def update_embedding(self, unique_id, embedding=None, metadata_dict=None):
+        self.update_embeddings_batch([unique_id], None if embedding is None else [embedding],
+                                     None if metadata_dict is None else [metadata_dict])
+
+    def update_embeddings_batch(self, unique_ids, embeddings=None, metadata_dicts=None):
+        """None means "keep"; both None is a ValueError.  All-or-nothing: every check runs before anything changes."""
+        unique_ids = list(unique_ids)
+        if embeddings is None and metadata_dicts is None:
+            raise ValueError("Nothing to update: pass embeddings, metadata, or both.")
+        with self.lock:
+            if embeddings is not None and len(embeddings) != len(unique_ids):
+                raise ValueError("Number of unique IDs must match number of embeddings.")
+            if metadata_dicts is not None and len(metadata_dicts) != len(unique_ids):
+                raise ValueError("Metadata dictionaries must be provided for all unique IDs.")
+            if any(uid not in self._ids for uid in unique_ids):
+                raise ValueError("Unique ID does not exist.")
+            if len(set(unique_ids)) != len(unique_ids):
+                raise ValueError("Unique ID listed more than once.")
+            if metadata_dicts is not None:
+                metadata_dicts = list(metadata_dicts)
+                if any(not isinstance(m, dict) for m in metadata_dicts):
+                    raise ValueError("Metadata must be a dictionary.")
+            vectors = None
+            if embeddings is not None and unique_ids:
+                if isinstance(embeddings, np.ndarray) and embeddings.ndim == 2:
+                    vectors = np.array(embeddings, dtype=np.float32)
+                else:
+                    rows = [np.array(e, dtype=np.float32) for e in embeddings]
+                    if any(v.ndim != 1 or v.shape[0] != self._mat.d for v in rows):
+                        raise ValueError(f"Embedding size must be {self._mat.d}.")
+                    vectors = np.stack(rows)
+                if vectors.shape[1] != self._mat.d:
+                    raise ValueError(f"Embedding size must be {self._mat.d}.")
+            if not unique_ids:
+                return
+            rows = [self._ids.row(uid) for uid in unique_ids]
+            if vectors is not None:
+                # Row numbers and filter results stay as they are, so the cached row sets and `_write_gen` stay too: a set a
+                # concurrent search builds from rows it read before this call still names the right rows.  That search sees
+                # either the old rows or the new ones — the index takes set_rows exclusively — and the two-call range search
+                # notices counts that moved between its calls and runs both again.
+                self._mat.replace(rows, vectors, self.index)
+            if metadata_dicts is not None:
+                values = self._live_value_index()
+                inverted = self.inverted_index
+                for uid, row, new in zip(unique_ids, rows, metadata_dicts):
+                    old = self.metadata[row]
+                    if values is not None:
+                        values.note_update(self._ids.handle[uid], old, new)
+                    for key in old:
+                        holders = inverted.get(key)
+                        if holders is not None:
+                            holders.discard(uid)
+                            if not holders:
+                                del inverted[key]
+                    self.metadata[row] = new
+                    for key in new:
+                        inverted[key].add(uid)
+                self._note_write()   # filter results moved: cached row sets go, as after a store
+            self._persist_update(unique_ids, vectors, metadata_dicts)
+
+    def _persist_update(self, unique_ids, vectors, metadata_dicts):
+        """Per-id storage of the class (shard files); nothing for a class that persists as a whole."""

@@ -75,6 +75,8 @@ PROTOTYPES = {
     "mvdb_index_add_synthetic": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int]),
     "mvdb_index_get_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
     "mvdb_index_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_index_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int]),
+    "mvdb_index_set_rows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int]),
     "mvdb_index_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int64, c_vp, c_vp, c_vp]),
@@ -137,6 +139,8 @@ PROTOTYPES = {
     "mvdb_cos8_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
     "mvdb_cos8_get_codes": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
     "mvdb_cos8_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_cos8_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_cos8_set_rows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
     "mvdb_cos8_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "mvdb_cos8_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp,
                                                c_vp]),
@@ -322,6 +326,22 @@ class FlatIndex:
     def remove_rows(self, rows):
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         check(lib().mvdb_index_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x, normalize=False):
+        """Overwrite the stored rows `rows` (distinct, each in [0, ntotal)) with x[len(rows), d] in place: nothing is
+        renumbered, dropped or rebuilt (include/mvdb.h: mvdb_index_set_rows)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if rows.ndim != 1 or x.ndim != 2 or x.shape[1] != self.d or x.shape[0] != rows.shape[0]:
+            raise ValueError(f"expected [m] rows and [m,{self.d}] float32, got {rows.shape} and {x.shape}")
+        check(lib().mvdb_index_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0], int(bool(normalize))))
+
+    def set_rows_device(self, rows, x_ptr, m, normalize=False):
+        """Same, the new rows in device memory ([m, d] dense float32 at x_ptr); the row numbers stay a host array."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        check(lib().mvdb_index_set_rows_device(self._h, _ptr(rows), ctypes.c_void_p(x_ptr), int(m), int(bool(normalize))))
 
     def search(self, q, k, normalize_q=False):
         q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
@@ -641,6 +661,20 @@ class Cos8Index:
     def remove_rows(self, rows):
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         check(lib().mvdb_cos8_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x, normalize=None):
+        """Overwrite the stored rows `rows` (distinct, each in [0, ntotal)) with the codes of x[len(rows), d], in place."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        x = self._rows2d(x)
+        if rows.ndim != 1 or x.shape[0] != rows.shape[0]:
+            raise ValueError(f"expected [m] rows and [m,{self.d}] float32, got {rows.shape} and {x.shape}")
+        check(lib().mvdb_cos8_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_device(self, rows, x_ptr, m):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        check(lib().mvdb_cos8_set_rows_device(self._h, _ptr(rows), ctypes.c_void_p(x_ptr), int(m)))
 
     def _out(self, nq, k):
         return np.empty((nq, int(k)), dtype=np.float32), np.empty((nq, int(k)), dtype=np.int64)

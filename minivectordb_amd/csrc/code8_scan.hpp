@@ -52,13 +52,18 @@ constexpr float kCode8Tiny = 1e-15f;  // a row (a query) whose largest |element|
 // ---- build: rows [0, n) of X -> codes, (a, r) ------------------------------------------------------------------------------------
 // One wave per row.  a = max|x| / 127, c = rint(x / a); r = sqrt(sum (x - a c)^2) rounded up.  A row with a non-finite element
 // gets zero codes and r = +inf: it is always a candidate and the exact kernel treats it as it always has.
+// list == NULL: rows [0, n) behind the three pointers.  list != NULL (set_rows): the n stored rows list[0 .. n), the pointers
+// at row 0; a listed row at or above `limit` (not coded yet) is skipped.
 __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restrict__ X, int64_t ld, int d, int64_t n,
-                                                          int8_t* __restrict__ codes, float2* __restrict__ ar) {
+                                                          int8_t* __restrict__ codes, float2* __restrict__ ar,
+                                                          const int64_t* __restrict__ list, int64_t limit) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
     const int d4 = d / 4;
-    for (int64_t row = wave0; row < n; row += nw) {
+    for (int64_t i = wave0; i < n; i += nw) {
+        const int64_t row = list ? list[i] : i;
+        if (list && row >= limit) continue;
         const f32x4* src = reinterpret_cast<const f32x4*>(X + row * ld);
         float mx = 0.f;
         bool bad = false;

@@ -74,6 +74,7 @@ struct mvdb_cos8 {
     uint64_t gen = 0;  // bumped when rows are renumbered (remove_rows / reset)
     hipStream_t ms = nullptr;  // mutators' private stream
     DevBuf<float> stage;
+    DevBuf<int64_t> stage_rows;  // set_rows: the row numbers of the staged chunk
     PinnedBuf pin;
     mutable std::shared_mutex mu;
     mutable std::mutex ws_mu;
@@ -515,6 +516,61 @@ int mvdb_cos8_add_device(mvdb_cos8* ix, const float* x_dev, int64_t n) {
     MVDB_HIP(hipStreamSynchronize(ix->ms));
     ix->n += n;
     return 0;
+}
+
+// ---- set_rows: stored rows overwritten in place ---------------------------------------------------------------------------------
+namespace {
+int set_rows_entry(mvdb_cos8* ix, const int64_t* rows_host, const float* x, bool x_on_device, int64_t m) {
+    if (!ix) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (m < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (m == 0) return 0;
+    if (!rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
+    if (!x) return fail(MVDB_ERR_ARG, "x is NULL");
+    DeviceGuard g(ix->device);
+    std::unique_lock<std::shared_mutex> lk(ix->mu);
+    {   // validate first, write after
+        std::vector<int64_t> v(rows_host, rows_host + m);
+        std::sort(v.begin(), v.end());
+        for (int64_t i = 0; i < m; ++i) {
+            if (v[i] < 0 || v[i] >= ix->n)
+                return fail(MVDB_ERR_ARG, "row %lld out of range [0, %lld)", (long long)v[i], (long long)ix->n);
+            if (i && v[i] == v[i - 1]) return fail(MVDB_ERR_ARG, "row %lld listed twice", (long long)v[i]);
+        }
+    }
+    MVDB_TRY(quiesce(ix));
+    // chunks of at most 64 MiB of rows (mvdb_cos8_add's staging): the row numbers travel with them
+    const int64_t chunk = std::min<int64_t>(m, std::max<int64_t>(1, (64ll << 20) / ((int64_t)ix->d * 4)));
+    MVDB_TRY(ix->stage_rows.reserve((size_t)chunk));
+    if (!x_on_device) {
+        MVDB_TRY(ix->stage.reserve((size_t)chunk * ix->d));
+        MVDB_TRY(ix->pin.reserve((size_t)chunk * ix->d * sizeof(float)));
+    }
+    for (int64_t i0 = 0; i0 < m; i0 += chunk) {
+        const int64_t rows = std::min(chunk, m - i0);
+        const size_t bytes = (size_t)rows * ix->d * sizeof(float);
+        MVDB_HIP(hipStreamSynchronize(ix->ms));  // the staging buffers are reused
+        MVDB_HIP(hipMemcpyAsync(ix->stage_rows.p, rows_host + i0, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ix->ms));
+        const float* src = x + i0 * ix->d;
+        if (!x_on_device) {
+            memcpy(ix->pin.p, src, bytes);
+            MVDB_HIP(hipMemcpyAsync(ix->stage.p, ix->pin.p, bytes, hipMemcpyHostToDevice, ix->ms));
+            src = ix->stage.p;
+        }
+        hipLaunchKernelGGL(cos8_quantize_list_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ix->ms, src,
+                           (const int64_t*)ix->stage_rows.p, rows, ix->d, ix->stride, ix->codes, ix->a2);
+        MVDB_HIP(hipGetLastError());
+    }
+    MVDB_HIP(hipStreamSynchronize(ix->ms));
+    return 0;
+}
+}  // namespace
+
+int mvdb_cos8_set_rows(mvdb_cos8* ix, const int64_t* rows_host, const float* x_host, int64_t m) {
+    return set_rows_entry(ix, rows_host, x_host, false, m);
+}
+
+int mvdb_cos8_set_rows_device(mvdb_cos8* ix, const int64_t* rows_host, const float* x_dev, int64_t m) {
+    return set_rows_entry(ix, rows_host, x_dev, true, m);
 }
 
 int mvdb_cos8_get_codes(const mvdb_cos8* ix, int64_t row0, int64_t n, int8_t* codes_host, int32_t* a2_host) {

@@ -62,6 +62,16 @@ __global__ __launch_bounds__(256) void cos8_quantize_kernel(const float* __restr
     a2[r] = cos8_quantize_row(x + r * d, d, stride, codes + r * stride);
 }
 
+// set_rows: staged row i -> the stored row rows[i] (distinct rows: checked on the host).  The same rule, the same thread per row.
+__global__ __launch_bounds__(256) void cos8_quantize_list_kernel(const float* __restrict__ x, const int64_t* __restrict__ rows,
+                                                                 int64_t m, int d, int stride, int8_t* __restrict__ codes,
+                                                                 int32_t* __restrict__ a2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int64_t r = rows[i];
+    a2[r] = cos8_quantize_row(x + i * d, d, stride, codes + r * stride);
+}
+
 // The distance, once.
 __device__ __forceinline__ float cos8_distance(int32_t ab, int32_t a2, int32_t b2) {
     if (a2 == 0 && b2 == 0) return 0.0f;

@@ -570,13 +570,19 @@ __global__ __launch_bounds__(WV * 64) void flat_scan_h16_kernel(HalfScanArgs a) 
 }
 
 // fp32 rows -> the shadow: Xh[r][c] = fp16(s_x X[r][c]) (RNE; s_x a power of two: the product is exact) — the values
-// the on-the-fly conversion of rounds 3 - 5 produced
+// the on-the-fly conversion of rounds 3 - 5 produced.  list == NULL: rows [0, n) of X into rows [0, n) of Xh (both pointers
+// at the first row).  list != NULL (set_rows): the n stored rows list[0 .. n), X and Xh at row 0; a listed row at or above
+// `limit` (not converted yet) is skipped.
 __global__ __launch_bounds__(256) void half_shadow_kernel(const float* __restrict__ X, int64_t ld, int d, int64_t n, float xscale,
-                                                          _Float16* __restrict__ Xh) {
+                                                          _Float16* __restrict__ Xh, const int64_t* __restrict__ list, int64_t limit) {
     const int64_t total = n * (int64_t)(d / 4);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = i / (d / 4);
+        int64_t r = i / (d / 4);
         const int c = (int)(i % (d / 4)) * 4;
+        if (list) {
+            r = list[r];
+            if (r >= limit) continue;
+        }
         const hs_f4 v = *reinterpret_cast<const hs_f4*>(X + r * ld + c);
         union {
             hs_h2 p[2];
@@ -588,20 +594,24 @@ __global__ __launch_bounds__(256) void half_shadow_kernel(const float* __restric
     }
 }
 
-int launch_half_shadow(const float* X, int64_t ld, int d, int64_t n, float xscale, _Float16* Xh, int device, hipStream_t stream) {
+int launch_half_shadow(const float* X, int64_t ld, int d, int64_t n, float xscale, _Float16* Xh, int device, hipStream_t stream,
+                       const int64_t* list_dev, int64_t limit) {
     if (n <= 0) return 0;
     const int64_t total = n * (int64_t)(d / 4);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)device_cus(device) * 16));
-    hipLaunchKernelGGL(half_shadow_kernel, dim3(grid), dim3(256), 0, stream, X, ld, d, n, xscale, Xh);
+    hipLaunchKernelGGL(half_shadow_kernel, dim3(grid), dim3(256), 0, stream, X, ld, d, n, xscale, Xh, list_dev, limit);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
 
 // Hn[r] = |x_r|^2 / 2: a wave per row, every lane sums its 16-byte pieces with fmas, butterfly over the lanes
+// (list / limit: as half_shadow_kernel)
 __global__ __launch_bounds__(256) void half_norms_kernel(const float* __restrict__ X, int64_t ld, int d4, int64_t n,
-                                                         float* __restrict__ Hn) {
+                                                         float* __restrict__ Hn, const int64_t* __restrict__ list, int64_t limit) {
     const int lane = threadIdx.x & 63;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * 4) {
+        const int64_t r = list ? list[i] : i;
+        if (list && r >= limit) continue;
         const hs_f4* xr = reinterpret_cast<const hs_f4*>(X + r * ld);
         float s = 0.f;
         for (int c = lane; c < d4; c += 64) {
@@ -616,10 +626,11 @@ __global__ __launch_bounds__(256) void half_norms_kernel(const float* __restrict
     }
 }
 
-int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, int device, hipStream_t stream) {
+int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, int device, hipStream_t stream,
+                      const int64_t* list_dev, int64_t limit) {
     if (n <= 0) return 0;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)device_cus(device) * 16));
-    hipLaunchKernelGGL(half_norms_kernel, dim3(grid), dim3(256), 0, stream, X, ld, (d + 3) / 4, n, Hn);
+    hipLaunchKernelGGL(half_norms_kernel, dim3(grid), dim3(256), 0, stream, X, ld, (d + 3) / 4, n, Hn, list_dev, limit);
     MVDB_HIP(hipGetLastError());
     return 0;
 }

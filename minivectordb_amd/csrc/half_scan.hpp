@@ -154,10 +154,14 @@ int launch_half_queries(const float* q, int64_t ld, int d, int nq, int nqpad, fl
 // seed: one tile per block over [tile0, tile1), every score dumped ([nq, blocks, 32] keys); *nblocks_out = blocks
 int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, const Knobs& kn, int device, hipStream_t stream, int* nblocks_out);
 int launch_half_certify(const HalfCertifyArgs& a, int nq, hipStream_t stream);
-// the fp16 shadow of rows [0, n) of X (ld floats per row) into Xh (d halves per row); dimensions the shadow kernels serve
-int launch_half_shadow(const float* X, int64_t ld, int d, int64_t n, float xscale, _Float16* Xh, int device, hipStream_t stream);
+// the fp16 shadow of rows [0, n) of X (ld floats per row) into Xh (d halves per row); dimensions the shadow kernels serve.
+// list_dev (set_rows): the n stored rows it names instead, X and Xh at row 0, rows at or above `limit` skipped
+int launch_half_shadow(const float* X, int64_t ld, int d, int64_t n, float xscale, _Float16* Xh, int device, hipStream_t stream,
+                       const int64_t* list_dev = nullptr, int64_t limit = 0);
 bool half_shadow_dim(int d);
 // Hn[r] = |X[r]|^2 / 2 for rows [0, n) (fp32; a wave per row, lane-strided fmas + butterfly: relative error < 2^-18 for d <= 4096)
-int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, int device, hipStream_t stream);
+// (list_dev / limit: as launch_half_shadow)
+int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, int device, hipStream_t stream,
+                      const int64_t* list_dev = nullptr, int64_t limit = 0);
 
 }  // namespace mvdb

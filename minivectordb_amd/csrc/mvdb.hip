@@ -274,6 +274,8 @@ struct mvdb_index {
     unsigned int* normmax = nullptr;  // 4-byte scratch of note_row_norms (raw adds)
     float* ctmp = nullptr;            // bounded staging buffer of mvdb_index_remove_rows (kept once a delete has run)
     size_t ctmp_bytes = 0;
+    DevBuf<float> set_stage;          // bounded staging of mvdb_index_set_rows (kept once an update has run): one chunk of new
+    DevBuf<int64_t> set_list;         // rows at the matrix' stride, and the row numbers they go to
     // fp16 shadow of the rows (half_scan.hip: flat_scan_h16_kernel): built by the first batch search that can use it, extended
     // by add, emptied (allocation kept) by whatever renumbers rows or changes the scale, freed with the matrix.  Searches (shared lock) build / read it under
     // shadow_mu; mutators (exclusive lock, searches quiesced) edit it directly.
@@ -1891,7 +1893,7 @@ int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, int64_t n_a
     if (rows > 0) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
         hipLaunchKernelGGL(code8_build_kernel, dim3(grid), dim3(256), 0, s, (const float*)(idx->X + row0 * idx->ld), idx->ld, idx->d, rows,
-                           idx->C8 + row0 * idx->d, idx->c8_ar + row0);
+                           idx->C8 + row0 * idx->d, idx->c8_ar + row0, (const int64_t*)nullptr, (int64_t)0);
     }
     hipLaunchKernelGGL(code8_seed_rows_kernel, dim3((unsigned)((kCode8Seed + 255) / 256)), dim3(256), 0, s, idx->c8_seed, kCode8Seed, n_after);
     MVDB_HIP(hipGetLastError());
@@ -2341,8 +2343,9 @@ int mvdb_index_reserve(mvdb_index* idx, int64_t n) {
 }
 
 // Keeps idx->row_norm_bound >= |row| for every stored row: 1 for rows normalised on the device, one
-// extra read of the new rows otherwise (non-finite rows leave the bound non-finite).
-static int note_row_norms(mvdb_index* idx, const float* dst, int64_t n, int normalize) {
+// extra read of the new rows otherwise (non-finite rows leave the bound non-finite).  The new rows are [0, n) behind dst, or
+// (set_rows) the n stored rows list_dev names, dst at row 0.  The bounds only ever widen.
+static int note_row_norms(mvdb_index* idx, const float* dst, int64_t n, int normalize, const int64_t* list_dev = nullptr) {
     const bool l2 = idx->metric == MVDB_METRIC_L2;
     if (normalize && !l2) {
         // |row| after normalize_rows_kernel: |x| / sqrt(fl(|x|^2)) with an fp32 sum of depth <= 4 * 16 + 6 (d <= 4096),
@@ -2360,9 +2363,9 @@ static int note_row_norms(mvdb_index* idx, const float* dst, int64_t n, int norm
     if (e == hipSuccess) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)device_cus(idx->device) * 16));
         if (l2)
-            hipLaunchKernelGGL(row_norm2_range_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d4, dmax);
+            hipLaunchKernelGGL(row_norm2_range_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d4, dmax, list_dev);
         else
-            hipLaunchKernelGGL(max_row_norm2_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d4, dmax);
+            hipLaunchKernelGGL(max_row_norm2_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d4, dmax, list_dev);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(bits, dmax, sizeof(bits), hipMemcpyDeviceToHost, idx->mut);
@@ -2511,6 +2514,97 @@ int mvdb_index_add_synthetic(mvdb_index* idx, int64_t n, uint64_t seed, int64_t 
     MVDB_TRY(extend_code8(idx, n));
     idx->n += n;
     return 0;
+}
+
+// ---- set_rows: stored rows overwritten in place (contract: mvdb.h) -----------------------------------------------------------
+constexpr size_t kSetStageBytes = 32u << 20;   // one chunk of staged rows: at most this many bytes (and at least one row)
+
+// every row in [0, n), none twice; nothing is enqueued before this has passed
+static int check_row_list(const int64_t* rows_host, int64_t m, int64_t n) {
+    std::vector<int64_t> v(rows_host, rows_host + m);
+    std::sort(v.begin(), v.end());
+    for (int64_t i = 0; i < m; ++i) {
+        if (v[i] < 0 || v[i] >= n) return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)v[i], (long long)n);
+        if (i && v[i] == v[i - 1]) return fail(MVDB_ERR_ARG, "row %lld listed twice", (long long)v[i]);
+    }
+    return 0;
+}
+
+// Caller holds the index exclusively, searches quiesced.  Per chunk of at most kSetStageBytes: the row numbers and the new rows
+// go to the staging buffers (at the matrix' stride, padding zero), scatter_rows_kernel writes them over the stored rows, and
+// each derived store that covers a listed row is converted from the stored row by the kernel that add uses, in its list form.
+// A fixed number of launches per chunk; nothing here is proportional to idx->n.
+static int set_rows_core(mvdb_index* idx, const int64_t* rows_host, const float* x, bool x_on_device, int64_t m, int normalize) {
+    const size_t row_bytes = (size_t)idx->ld * sizeof(float);
+    const int64_t chunk = std::min<int64_t>(m, std::max<int64_t>(1, (int64_t)(kSetStageBytes / row_bytes)));
+    MVDB_TRY(idx->set_stage.reserve((size_t)chunk * idx->ld));
+    MVDB_TRY(idx->set_list.reserve((size_t)chunk));
+    float* S = idx->set_stage.p;
+    int64_t* L = idx->set_list.p;
+    const Shape sh = choose_shape(idx->d4);
+    const int rpi = 64 / sh.G;
+    const int64_t cus = device_cus(idx->device);
+    const bool padded = idx->ld != idx->d;
+    if (x_on_device) MVDB_HIP(hipStreamSynchronize(nullptr));  // (mvdb_index_add_device's join with the legacy stream)
+    // the shadow at the scale it was built with: should the widened bound ask for another one, it is invalidated below
+    const bool shadow = idx->Xh && idx->xh_rows > 0;
+    const bool offsets = idx->Hn && idx->hn_rows > 0;
+    const bool code = idx->C8 && idx->c8_rows > 0;
+    for (int64_t i0 = 0; i0 < m; i0 += chunk) {
+        const int64_t rows = std::min(chunk, m - i0);
+        const float* src = x + i0 * idx->d;
+        MVDB_HIP(hipMemcpyAsync(L, rows_host + i0, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, idx->mut));
+        if (!padded) {
+            MVDB_HIP(hipMemcpyAsync(S, src, (size_t)rows * row_bytes, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, idx->mut));
+        } else if (x_on_device) {
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows * idx->ld + 255) / 256, cus * 16));
+            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, S, src, rows, idx->d, idx->ld);
+        } else {
+            MVDB_HIP(hipMemsetAsync(S, 0, (size_t)rows * row_bytes, idx->mut));
+            MVDB_HIP(hipMemcpy2DAsync(S, row_bytes, src, idx->d * sizeof(float), idx->d * sizeof(float), (size_t)rows, hipMemcpyHostToDevice,
+                                      idx->mut));
+        }
+        const int64_t waves = (rows + rpi - 1) / rpi;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, cus * 8));
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, idx->X, (const float*)S, (const int64_t*)L, rows, idx->ld,
+                           idx->d4, (int)(idx->ld / 4), sh.G, normalize);
+        MVDB_HIP(hipGetLastError());
+        if (shadow)
+            MVDB_TRY(launch_half_shadow(idx->X, idx->ld, idx->d, rows, idx->xh_scale, idx->Xh, idx->device, idx->mut, L, idx->xh_rows));
+        if (offsets) MVDB_TRY(launch_half_norms(idx->X, idx->ld, idx->d, rows, idx->Hn, idx->device, idx->mut, L, idx->hn_rows));
+        if (code) {
+            const int g8 = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, cus * 16));
+            hipLaunchKernelGGL(code8_build_kernel, dim3(g8), dim3(256), 0, idx->mut, (const float*)idx->X, idx->ld, idx->d, rows, idx->C8,
+                               idx->c8_ar, (const int64_t*)L, idx->c8_rows);
+            MVDB_HIP(hipGetLastError());
+        }
+        // (waits for the chunk: the staging buffers are free again, and so is the caller's part of x)
+        MVDB_TRY(note_row_norms(idx, idx->X, rows, normalize, L));
+        MVDB_HIP(hipStreamSynchronize(idx->mut));
+    }
+    if (idx->Xh && idx->xh_rows > 0 && half_xscale(idx->row_norm_bound) != idx->xh_scale) invalidate_shadow(idx);  // (extend_shadow's rule)
+    return 0;
+}
+
+static int set_rows_entry(mvdb_index* idx, const int64_t* rows_host, const float* x, bool x_on_device, int64_t m, int normalize) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (m < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (m == 0) return 0;
+    if (!rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
+    if (!x) return fail(MVDB_ERR_ARG, "x is NULL");
+    std::unique_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_row_list(rows_host, m, idx->n));
+    DeviceGuard dg(idx->device);
+    MVDB_TRY(quiesce(idx));
+    return set_rows_core(idx, rows_host, x, x_on_device, m, normalize);
+}
+
+int mvdb_index_set_rows(mvdb_index* idx, const int64_t* rows_host, const float* x_host, int64_t m, int normalize) {
+    return set_rows_entry(idx, rows_host, x_host, false, m, normalize);
+}
+
+int mvdb_index_set_rows_device(mvdb_index* idx, const int64_t* rows_host, const float* x_dev, int64_t m, int normalize) {
+    return set_rows_entry(idx, rows_host, x_dev, true, m, normalize);
 }
 
 int mvdb_index_get_rows(const mvdb_index* idx, int64_t row0, int64_t n, float* out_host) {

@@ -8,6 +8,19 @@ namespace mvdb {
 typedef float f32x4u __attribute__((ext_vector_type(4)));
 
 // ---- faiss.normalize_L2 on device rows (reference: minivectordb/vector_database.py:45) --------
+// The arithmetic of one row, once: lane t of a G-lane group sums the squares of its 16-byte pieces in index order, the group
+// folds by xor shuffles.  normalize_rows_kernel (add) and scatter_rows_kernel (set_rows) both call it and scale by the same
+// 1 / sqrtf(nr), so a row written by either holds the same bits.
+__device__ __forceinline__ float group_row_norm2(const float* __restrict__ row, int d4, int t, int G) {
+    float nr = 0.f;
+    for (int c = t; c < d4; c += G) {
+        const f32x4u v = *reinterpret_cast<const f32x4u*>(row + c * 4);
+        nr += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+    for (int m = G >> 1; m >= 1; m >>= 1) nr += __shfl_xor(nr, m);
+    return nr;
+}
+
 // One group of G lanes (runtime power of two <= 64) per row; pass 1 sums squares, pass 2 re-reads
 // the row (L1/L2 hit: a row is <= 16 KiB) and scales it.  Zero-norm rows stay untouched, as in
 // faiss fvec_renorm_L2 (`if (nr > 0)`).  HBM-bound: 1 read + 1 write of n*ld*4 bytes.
@@ -23,12 +36,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(float* __restrict__
         const int64_t r = r0 + g;
         const bool rv = r < n;
         float* row = X + (rv ? r : n - 1) * ld;
-        float nr = 0.f;
-        for (int c = t; c < d4; c += G) {
-            const f32x4u v = *reinterpret_cast<const f32x4u*>(row + c * 4);
-            nr += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-        for (int m = G >> 1; m >= 1; m >>= 1) nr += __shfl_xor(nr, m);
+        const float nr = group_row_norm2(row, d4, t, G);
         if (rv && nr > 0.f) {
             const float inorm = 1.0f / sqrtf(nr);
             for (int c = t; c < d4; c += G) {
@@ -40,24 +48,62 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(float* __restrict__
     }
 }
 
+// ---- set_rows: staged rows into the stored rows a list names ------------------------------------------------------------
+// X[rows[i], :] = S[i, :] for i < m, normalised on the way when `normalize` is set (normalize_rows_kernel's arithmetic: the
+// same sum, the same 1 / sqrtf, a zero-norm row copied as it is).  S has the matrix' stride (padding already zero), so whole
+// 16-byte pieces move and the padding of the stored row is rewritten with zeros.  One G-lane group per row, as above; the
+// rows of the list are distinct (checked on the host), so no two groups write the same row.  Moves m * ld * 8 bytes.
+__global__ __launch_bounds__(256) void scatter_rows_kernel(float* __restrict__ X, const float* __restrict__ S,
+                                                           const int64_t* __restrict__ rows, int64_t m, int64_t ld, int d4,
+                                                           int ld4, int G, int normalize) {
+    const int lane = threadIdx.x & 63;
+    const int t = lane & (G - 1);
+    const int g = lane / G;
+    const int rpi = 64 / G;
+    const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t i0 = gw * rpi; i0 < m; i0 += nw * rpi) {
+        const int64_t i = i0 + g;
+        const bool rv = i < m;
+        const float* src = S + (rv ? i : m - 1) * ld;
+        const float nr = normalize ? group_row_norm2(src, d4, t, G) : 0.f;
+        if (!rv) continue;
+        float* dst = X + rows[i] * ld;
+        const bool scale = normalize && nr > 0.f;
+        const float inorm = scale ? 1.0f / sqrtf(nr) : 1.0f;
+        for (int c = t; c < ld4; c += G) {
+            f32x4u v = *reinterpret_cast<const f32x4u*>(src + c * 4);
+            if (scale) v *= inorm;
+            *reinterpret_cast<f32x4u*>(dst + c * 4) = v;
+        }
+    }
+}
+
+// |row|^2 by one wave: lane-strided 16-byte pieces, butterfly (the sum both norm kernels below report)
+__device__ __forceinline__ float wave_row_norm2(const float* __restrict__ row, int d4, int lane) {
+    float nr = 0.f;
+    for (int c = lane; c < d4; c += 64) {
+        const f32x4u v = *reinterpret_cast<const f32x4u*>(row + c * 4);
+        nr += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+    for (int m = 32; m >= 1; m >>= 1) nr += __shfl_xor(nr, m);
+    return nr;
+}
+
 // max over rows of |row|^2 (raw adds: the split-precision batch pass needs a row-norm bound).  One
 // wave per row; atomicMax on the bit pattern (non-negative floats order like their bits; a NaN row
 // leaves a NaN pattern behind, which disables that pass).
+// (list: NULL = rows [0, n) of X; else the n stored rows list[0 .. n) — set_rows)
 __global__ __launch_bounds__(256) void max_row_norm2_kernel(const float* __restrict__ X, int64_t n, int64_t ld,
-                                                            int d4, unsigned int* __restrict__ out) {
+                                                            int d4, unsigned int* __restrict__ out,
+                                                            const int64_t* __restrict__ list = nullptr) {
     const int lane = threadIdx.x & 63;
     const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     float best = 0.f;
     bool bad = false;
     for (int64_t r = gw; r < n; r += nw) {
-        const float* row = X + r * ld;
-        float nr = 0.f;
-        for (int c = lane; c < d4; c += 64) {
-            const f32x4u v = *reinterpret_cast<const f32x4u*>(row + c * 4);
-            nr += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-        for (int m = 32; m >= 1; m >>= 1) nr += __shfl_xor(nr, m);
+        const float nr = wave_row_norm2(X + (list ? list[r] : r) * ld, d4, lane);
         bad |= !(nr >= 0.f);  // NaN
         best = fmaxf(best, nr);
     }
@@ -67,20 +113,15 @@ __global__ __launch_bounds__(256) void max_row_norm2_kernel(const float* __restr
 // min AND max over rows of |row|^2: out[0] = max (as above), out[1] = min (atomicMin on the bit pattern; the caller sets it
 // to +inf first).  The L2 metric's certified batch passes nominate by inner product and need both ends of the norm range.
 __global__ __launch_bounds__(256) void row_norm2_range_kernel(const float* __restrict__ X, int64_t n, int64_t ld,
-                                                              int d4, unsigned int* __restrict__ out) {
+                                                              int d4, unsigned int* __restrict__ out,
+                                                              const int64_t* __restrict__ list = nullptr) {
     const int lane = threadIdx.x & 63;
     const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     float hi = 0.f, lo = INFINITY;
     bool bad = false;
     for (int64_t r = gw; r < n; r += nw) {
-        const float* row = X + r * ld;
-        float nr = 0.f;
-        for (int c = lane; c < d4; c += 64) {
-            const f32x4u v = *reinterpret_cast<const f32x4u*>(row + c * 4);
-            nr += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-        for (int m = 32; m >= 1; m >>= 1) nr += __shfl_xor(nr, m);
+        const float nr = wave_row_norm2(X + (list ? list[r] : r) * ld, d4, lane);
         bad |= !(nr >= 0.f);  // NaN
         hi = fmaxf(hi, nr);
         lo = fminf(lo, nr);

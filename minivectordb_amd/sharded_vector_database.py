@@ -26,7 +26,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from ._dbcore import FilterAndRerankMixin, _IdIndex
+from ._dbcore import FilterAndRerankMixin, UpdateMixin, _IdIndex
 
 
 def _shard_number(file_name):
@@ -47,7 +47,7 @@ def shard_files_for_rank(storage_dir, rank, world):
     return files[start:start + base + (1 if rank < rem else 0)]
 
 
-class ShardedVectorDatabase(FilterAndRerankMixin):
+class ShardedVectorDatabase(UpdateMixin, FilterAndRerankMixin):
     def __init__(self, storage_dir='db_shards', shard_size=5000, device=0, fast_single_query=False):
         """storage_dir, shard_size: as in the reference (sharded_vector_database.py:9).  device, fast_single_query: see
         VectorDatabase."""
@@ -294,6 +294,35 @@ class ShardedVectorDatabase(FilterAndRerankMixin):
 
             # stacked rows, ids, metadata, inverted index, device matrix: only what belongs to the doomed ids moves
             self._expel(unique_ids)
+
+    # ---- update in place (no reference counterpart) ----------------------------------------------------------
+    def _persist_update(self, unique_ids, vectors, metadata_dicts):
+        """Rewrite only the shard files that own an updated id: the raw embedding in place in ``shard['embeddings']``, the
+        metadata and the shard's inverted index as a delete followed by a store of the same id would leave them."""
+        by_shard = defaultdict(list)
+        for at, uid in enumerate(unique_ids):
+            by_shard[self.inverse_box_item_map[uid]].append(at)
+        for shard_id, members in by_shard.items():
+            shard = self._read_shard(shard_id)
+            place = {uid: pos for pos, uid in enumerate(shard['unique_ids'])}
+            if vectors is not None and not shard['embeddings'].flags.writeable:
+                shard['embeddings'] = np.array(shard['embeddings'])
+            for at in members:
+                uid = unique_ids[at]
+                pos = place[uid]
+                if vectors is not None:
+                    shard['embeddings'][pos] = vectors[at]
+                if metadata_dicts is not None:
+                    for key in shard['metadata'][pos]:
+                        holders = shard['inverted_index'].get(key)
+                        if holders is not None:
+                            holders.discard(uid)
+                            if not holders:
+                                del shard['inverted_index'][key]
+                    shard['metadata'][pos] = metadata_dicts[at]
+                    for key in metadata_dicts[at]:
+                        shard['inverted_index'][key].add(uid)
+            self._write_shard(shard_id, shard)
 
     # ---- search (sharded_vector_database.py:598-662) --------------------------------------------------------
     def find_most_similar(self, embedding, metadata_filter=None, exclude_filter=None, or_filters=None, k=5,

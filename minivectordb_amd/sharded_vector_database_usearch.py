@@ -80,6 +80,16 @@ class _HostRows:
         self._blocks = [np.delete(self._matrix(), rows, axis=0)]
         self._n = self._blocks[0].shape[0]
 
+    def replace(self, rows, vectors, index):
+        """Overwrite the stacked rows `rows` (distinct): the codes of the rows already flushed through ONE
+        `Cos8Index.set_rows`, then the host matrix.  The device goes first: if it refuses, nothing changed."""
+        rows = np.asarray(rows, dtype=np.int64)
+        vectors = np.asarray(vectors, dtype=np.float32)
+        on_device = rows < self.synced
+        if on_device.any():
+            index.set_rows(rows[on_device], vectors[on_device])
+        self._matrix()[rows] = vectors
+
     def row(self, r, index=None):
         return self._matrix()[r].copy()
 

@@ -26,10 +26,10 @@ import threading
 from collections import defaultdict
 import numpy as np
 
-from ._dbcore import FilterAndRerankMixin, _IdIndex, _RowStore
+from ._dbcore import FilterAndRerankMixin, UpdateMixin, _IdIndex, _RowStore
 
 
-class VectorDatabase(FilterAndRerankMixin):
+class VectorDatabase(UpdateMixin, FilterAndRerankMixin):
     def __init__(self, storage_file='db.pkl', device=0, fast_single_query=False):
         """storage_file: as in the reference (vector_database.py:8).  device: HIP device ordinal.  fast_single_query: every
         find_most_similar call (one query) nominates over an fp16 copy of the rows and is re-scored and certified in fp32 — the
