@@ -97,6 +97,8 @@ Knobs read_knobs();
 
 // hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once per (kernel, dynamic LDS) and remembered
 int cached_occupancy(const void* kern, int threads, size_t lds, int dflt);
+// hipFuncAttributeMaxDynamicSharedMemorySize >= lds for `kern`, set once per (kernel, device); `device` is the current device
+int ensure_dynamic_lds(const void* kern, size_t lds, int device);
 
 // A search captured into a hipGraph bakes its workspace pointers into the graph.  While a retire list is installed
 // (RetireScope: searches on a workspace that has been captured once), a buffer that must grow is NOT freed — it goes on

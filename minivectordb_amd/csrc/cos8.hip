@@ -248,18 +248,6 @@ int launch_scan(const Cos8ScanArgs& a, int Q, int F, bool scores, dim3 grid, hip
 constexpr int kCos8MfmaMinNq = 8;
 bool mfma_pass_ok(const mvdb_cos8* ix, int nq, int F) { return nq >= kCos8MfmaMinNq && ix->nchunk <= 64 && F != 1; }
 
-// Dynamic LDS above the default limit must be allowed per kernel, once.
-int allow_lds(const void* kern, size_t bytes) {
-    static std::mutex mu;
-    static std::map<const void*, size_t> allowed;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& have = allowed[kern];
-    if (bytes <= have || bytes <= 65536) return 0;
-    MVDB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    have = bytes;
-    return 0;
-}
-
 int queries_per_pass(const mvdb_cos8* ix, int nq) { return nq == 1 ? 1 : (ix->nchunk > 64 ? 4 : 8); }
 
 // Everything on stream s, no synchronisation.  q_dev: dense fp32 [nq, d].
@@ -319,10 +307,10 @@ int search_core(const mvdb_cos8* ix, Cos8Workspace* ws, const float* q_dev, int 
         const size_t lds = (size_t)kCos8MfmaQ * cos8_mfma_lds_stride(ix->stride) +
                            (size_t)(kCos8Threads / kWave) * kCos8MfmaQ * k * sizeof(uint64_t);
         if (F == 2) {
-            MVDB_TRY(allow_lds((const void*)cos8_mfma_kernel<2>, lds));
+            MVDB_TRY(ensure_dynamic_lds((const void*)cos8_mfma_kernel<2>, lds, ix->device));
             hipLaunchKernelGGL(cos8_mfma_kernel<2>, mgrid, dim3(kCos8Threads), lds, s, a);
         } else {
-            MVDB_TRY(allow_lds((const void*)cos8_mfma_kernel<0>, lds));
+            MVDB_TRY(ensure_dynamic_lds((const void*)cos8_mfma_kernel<0>, lds, ix->device));
             hipLaunchKernelGGL(cos8_mfma_kernel<0>, mgrid, dim3(kCos8Threads), lds, s, a);
         }
         MVDB_HIP(hipGetLastError());

@@ -32,8 +32,6 @@
 //  forms of the K-split kernel, ~700 lines — an index without a shadow answers its batches on the exact fp32 passes.)
 #include <cmath>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 #include "common.hpp"
@@ -639,54 +637,65 @@ int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, i
 // (160 - 256 registers of query fragments)
 bool half_shadow_dim(int d) { return d == 128 || d == 256 || d == 384 || d == 512 || d == 640 || d == 768 || d == 896 || d == 1024; }
 
-template <int KT, int KS, int WV, int NST, int BPC = 1>
-static int launch_h16_inst(const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
-    auto kern = flat_scan_h16_kernel<KT, KS, WV, NST>;
-    constexpr size_t lds = (size_t)NST * 32 * KS * 2 * 16;
-    static_assert(BPC * (lds + WV * 32 * kHalfKeep * 8) <= 160 * 1024, "LDS budget of a CU");
-    {
-        static std::mutex mu;
-        static std::map<int, bool> done;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done[device]) {
-            MVDB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done[device] = true;
-        }
-    }
-    const int64_t ntiles = a.tile1 - a.tile0;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * BPC));
-    *nblocks_out = nblocks;
-    // (a launch without admission floors is the seed of an L2 pass over the shadow, mvdb.hip: launch_half_pass)
-    const char* pname = a.thr0 ? "ip_scan_half" : "ip_scan_half_seed";
-    prof_symbol(pname, "flat_scan_h16_kernel<%d, %d, %d, %d, %d>", KT, KS, WV, NST, kHalfKeep);
-    int slot = prof_begin(pname, stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WV * 64), lds, stream, a);
+// One launch of a kernel that streams through a ring in dynamic LDS: the attribute that admits `lds` bytes, a grid of one block
+// per tile up to `per_cu` workgroups per CU (*nblocks_out, where asked for), the profiling bracket.  symbol...: the format and the
+// arguments of prof_symbol.
+template <typename Args, typename... Sym>
+static int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int threads, int64_t ntiles, int per_cu, int device, hipStream_t stream,
+                       int* nblocks_out, const char* label, Sym... symbol) {
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * per_cu));
+    if (nblocks_out) *nblocks_out = nblocks;
+    prof_symbol(label, symbol...);
+    int slot = prof_begin(label, stream);
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, a);
     prof_end(slot, stream);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
 
-// main launches over the shadow.  A stage = a whole 32-row tile (KS = KT: 16 / 24 / 32 KiB at d = 256 / 384 / 512: one barrier
-// per tile).  256 queries per pass: eight waves (two per SIMD), a ring of 3 - 4 tiles.  128 queries per pass: four waves and
-// TWO workgroups per CU — the second workgroup's waves issue MFMAs while the first's sit at their barrier or in the gate —,
-// 2 - 4 tiles per ring.  Sweep at 10M x 512 (profiles/r04_h16_variants.txt): 128 queries 66.5k q/s with one workgroup per CU
-// (KS 16, ring of 6), 72.3k with two (KS 32, ring of 2); 256 queries 89.2k (KS 16, ring of 6) -> 92.1k (KS 32, ring of 3);
-// DMA pieces spread between the MFMAs: +-1 %; 8-KiB stages: -5 %.
-static int launch_h16(int d, int nqpad, const HalfScanArgs& a, int device, hipStream_t stream, int* nb) {
+// The shapes of the launches that stream the whole shadow: the certified pass's main launches and the shared pass of a batch range
+// search (the ring and the workgroups per CU were measured for the former: the stream is the same).  A stage = a whole 32-row tile
+// (KS = KT: 16 / 24 / 32 KiB at d = 256 / 384 / 512: one barrier per tile).  256 queries per pass: eight waves (two per SIMD), a
+// ring of 3 - 4 tiles.  128 queries per pass: four waves and TWO workgroups per CU — the second workgroup's waves issue MFMAs while
+// the first's sit at their barrier or in the gate —, 2 - 4 tiles per ring; d = 640 .. 1024: one workgroup per CU.  Sweep at
+// 10M x 512 (profiles/r04_h16_variants.txt): 128 queries 66.5k q/s with one workgroup per CU (KS 16, ring of 6), 72.3k with two
+// (KS 32, ring of 2); 256 queries 89.2k (KS 16, ring of 6) -> 92.1k (KS 32, ring of 3); DMA pieces spread between the MFMAs: +-1 %;
+// 8-KiB stages: -5 %.
+template <int KT_, int KS_, int WV_, int NST_, int BPC_ = 1>
+struct H16Shape {
+    static constexpr int KT = KT_, KS = KS_, WV = WV_, NST = NST_, BPC = BPC_;
+    static constexpr size_t kLds = (size_t)NST * 32 * KS * 2 * 16;  // the ring: NST stages
+};
+// launch(H16Shape<...>{}) for the shape of (d, nqpad); what: "" or "range ", for the message where there is none
+template <typename Launch>
+static int with_h16_shape(int d, int nqpad, const char* what, Launch launch) {
     const bool wide = nqpad == 256;
-    if (nqpad != 128 && nqpad != 256) return fail(MVDB_ERR_ARG, "no fp16-shadow kernel for %d queries per pass", nqpad);
+    if (nqpad != 128 && nqpad != 256) return fail(MVDB_ERR_ARG, "no fp16-shadow %skernel for %d queries per pass", what, nqpad);
     switch (d) {
-        case 128: return wide ? launch_h16_inst<8, 8, 8, 4>(a, device, stream, nb) : launch_h16_inst<8, 8, 4, 4, 2>(a, device, stream, nb);
-        case 256: return wide ? launch_h16_inst<16, 16, 8, 4>(a, device, stream, nb) : launch_h16_inst<16, 16, 4, 4, 2>(a, device, stream, nb);
-        case 384: return wide ? launch_h16_inst<24, 24, 8, 4>(a, device, stream, nb) : launch_h16_inst<24, 24, 4, 2, 2>(a, device, stream, nb);
-        case 512: return wide ? launch_h16_inst<32, 32, 8, 3>(a, device, stream, nb) : launch_h16_inst<32, 32, 4, 2, 2>(a, device, stream, nb);
-        case 640: if (!wide) return launch_h16_inst<40, 40, 4, 3>(a, device, stream, nb); break;
-        case 768: if (!wide) return launch_h16_inst<48, 48, 4, 3>(a, device, stream, nb); break;
-        case 896: if (!wide) return launch_h16_inst<56, 56, 4, 2>(a, device, stream, nb); break;
-        case 1024: if (!wide) return launch_h16_inst<64, 64, 4, 2>(a, device, stream, nb); break;
+        case 128: return wide ? launch(H16Shape<8, 8, 8, 4>{}) : launch(H16Shape<8, 8, 4, 4, 2>{});
+        case 256: return wide ? launch(H16Shape<16, 16, 8, 4>{}) : launch(H16Shape<16, 16, 4, 4, 2>{});
+        case 384: return wide ? launch(H16Shape<24, 24, 8, 4>{}) : launch(H16Shape<24, 24, 4, 2, 2>{});
+        case 512: return wide ? launch(H16Shape<32, 32, 8, 3>{}) : launch(H16Shape<32, 32, 4, 2, 2>{});
+        case 640: if (!wide) return launch(H16Shape<40, 40, 4, 3>{}); break;
+        case 768: if (!wide) return launch(H16Shape<48, 48, 4, 3>{}); break;
+        case 896: if (!wide) return launch(H16Shape<56, 56, 4, 2>{}); break;
+        case 1024: if (!wide) return launch(H16Shape<64, 64, 4, 2>{}); break;
         default: break;
     }
-    return fail(MVDB_ERR_ARG, "no fp16-shadow kernel for %d queries per pass at d = %d", nqpad, d);
+    return fail(MVDB_ERR_ARG, "no fp16-shadow %skernel for %d queries per pass at d = %d", what, nqpad, d);
+}
+
+// main launches over the shadow
+static int launch_h16(int d, int nqpad, const HalfScanArgs& a, int device, hipStream_t stream, int* nb) {
+    return with_h16_shape(d, nqpad, "", [&](auto shape) {
+        using S = decltype(shape);
+        static_assert(S::BPC * (S::kLds + S::WV * 32 * kHalfKeep * 8) <= 160 * 1024, "LDS budget of a CU");
+        // (a launch without admission floors is the seed of an L2 pass over the shadow, mvdb.hip: launch_half_pass)
+        return launch_ring(flat_scan_h16_kernel<S::KT, S::KS, S::WV, S::NST>, a, S::kLds, S::WV * 64, a.tile1 - a.tile0, S::BPC, device, stream, nb,
+                           a.thr0 ? "ip_scan_half" : "ip_scan_half_seed", "flat_scan_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV, S::NST,
+                           kHalfKeep);
+    });
 }
 
 // ---- range search: the pass against a fixed floor ------------------------------------------------------------------------
@@ -845,47 +854,15 @@ __global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeAr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped look-ahead DMAs must land before the LDS is released
 }
 
-template <int KT, int KS, int WV, int NST, int BPC = 1>
-static int launch_range_h16_inst(const HalfRangeArgs& a, int device, hipStream_t stream) {
-    constexpr int NACC = KT <= 32 ? 1 : KT / 8;   // d <= 512: one chain of d products; wider: chains of 128 (half_range_eps)
-    auto kern = range_nominate_h16_kernel<KT, KS, WV, NST, NACC>;
-    constexpr size_t lds = (size_t)NST * 32 * KS * 2 * 16;
-    static_assert(BPC * lds <= 160 * 1024, "LDS budget of a CU");
-    {
-        static std::mutex mu;
-        static std::map<int, bool> done;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done[device]) {
-            MVDB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done[device] = true;
-        }
-    }
-    const int64_t ntiles = (a.n + 31) / 32;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * BPC));
-    prof_symbol("ip_scan_range_half", "range_nominate_h16_kernel<%d, %d, %d, %d, %d>", KT, KS, WV, NST, NACC);
-    int slot = prof_begin("ip_scan_range_half", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WV * 64), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
-}
-
-// the shapes of launch_h16 (the ring and the workgroups per CU measured for the certified pass: the stream is the same)
 int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream) {
-    const bool wide = nqpad == 256;
-    if ((nqpad != 128 && nqpad != 256) || a.n <= 0) return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass", nqpad);
-    switch (d) {
-        case 128: return wide ? launch_range_h16_inst<8, 8, 8, 4>(a, device, stream) : launch_range_h16_inst<8, 8, 4, 4, 2>(a, device, stream);
-        case 256: return wide ? launch_range_h16_inst<16, 16, 8, 4>(a, device, stream) : launch_range_h16_inst<16, 16, 4, 4, 2>(a, device, stream);
-        case 384: return wide ? launch_range_h16_inst<24, 24, 8, 4>(a, device, stream) : launch_range_h16_inst<24, 24, 4, 2, 2>(a, device, stream);
-        case 512: return wide ? launch_range_h16_inst<32, 32, 8, 3>(a, device, stream) : launch_range_h16_inst<32, 32, 4, 2, 2>(a, device, stream);
-        case 640: if (!wide) return launch_range_h16_inst<40, 40, 4, 3>(a, device, stream); break;
-        case 768: if (!wide) return launch_range_h16_inst<48, 48, 4, 3>(a, device, stream); break;
-        case 896: if (!wide) return launch_range_h16_inst<56, 56, 4, 2>(a, device, stream); break;
-        case 1024: if (!wide) return launch_range_h16_inst<64, 64, 4, 2>(a, device, stream); break;
-        default: break;
-    }
-    return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass at d = %d", nqpad, d);
+    if (a.n <= 0) return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass", nqpad);
+    return with_h16_shape(d, nqpad, "range ", [&](auto shape) {
+        using S = decltype(shape);
+        constexpr int NACC = S::KT <= 32 ? 1 : S::KT / 8;   // d <= 512: one chain of d products; wider: chains of 128 (half_range_eps)
+        static_assert(S::BPC * S::kLds <= 160 * 1024, "LDS budget of a CU");
+        return launch_ring(range_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC, device,
+                           stream, nullptr, "ip_scan_range_half", "range_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV, S::NST, NACC);
+    });
 }
 
 // ---- the rescue pass (round 5) -----------------------------------------------------------------------------------------
@@ -899,28 +876,11 @@ int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipS
 // block inside the band) raises the query's `need` word and its 32-query exact pass runs as before.
 template <int KT, int KS, int NST, int BPC>
 static int launch_h16_rescue_inst(const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
-    auto kern = flat_scan_h16_kernel<KT, KS, 4, NST, kRescueKeep>;
-    constexpr size_t lds = (size_t)NST * 32 * KS * 2 * 16;
+    constexpr size_t lds = H16Shape<KT, KS, 4, NST>::kLds;
     static_assert(BPC * (lds + 4 * 32 * kRescueKeep * 8) <= 160 * 1024, "LDS budget of a CU");
     static_assert(BPC <= kRescueBlocksPerCu, "mvdb.hip sizes the lists by kRescueBlocksPerCu");
-    {
-        static std::mutex mu;
-        static std::map<int, bool> done;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done[device]) {
-            MVDB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done[device] = true;
-        }
-    }
-    const int64_t ntiles = a.tile1 - a.tile0;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * BPC));
-    *nblocks_out = nblocks;
-    prof_symbol("ip_scan_rescue", "flat_scan_h16_kernel<%d, %d, 4, %d, %d>", KT, KS, NST, kRescueKeep);
-    int slot = prof_begin("ip_scan_rescue", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return launch_ring(flat_scan_h16_kernel<KT, KS, 4, NST, kRescueKeep>, a, lds, 256, a.tile1 - a.tile0, BPC, device, stream, nblocks_out,
+                       "ip_scan_rescue", "flat_scan_h16_kernel<%d, %d, 4, %d, %d>", KT, KS, NST, kRescueKeep);
 }
 // The rescue launches' tile lists: thread w of slot s = blockIdx.y ORs word w of the flag rows of the slot's refused queries, adds
 // the seed's tiles, drops the bits past the last tile and appends the set bits to the slot's list (order: as the atomics fall).
@@ -1294,27 +1254,10 @@ int launch_half_queries(const float* q, int64_t ld, int d, int nq, int nqpad, fl
 // through LDS), every score dumped: [nq][blocks][32] keys.  It only has to produce the first admission floors.
 template <int KQ, int NG, int NST>
 static int launch_seed_inst(const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
-    auto kern = flat_scan_seed_kernel<KQ, 2, NG, NST>;
     constexpr size_t lds = (size_t)4 * NST * HsStage<2>::kBytes + (size_t)4 * 3 * 4096;
     static_assert(lds + 128 <= 160 * 1024, "LDS budget of a CU");
-    {
-        static std::mutex mu;
-        static std::map<int, bool> done;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done[device]) {
-            MVDB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done[device] = true;
-        }
-    }
-    const int64_t ntiles = a.tile1 - a.tile0;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device)));
-    *nblocks_out = nblocks;
-    prof_symbol("ip_scan_half_seed", "flat_scan_seed_kernel<%d, 2, %d, %d>", KQ, NG, NST);
-    int slot = prof_begin("ip_scan_half_seed", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return launch_ring(flat_scan_seed_kernel<KQ, 2, NG, NST>, a, lds, 256, a.tile1 - a.tile0, 1, device, stream, nblocks_out, "ip_scan_half_seed",
+                       "flat_scan_seed_kernel<%d, 2, %d, %d>", KQ, NG, NST);
 }
 
 template <int KQ>
@@ -1326,8 +1269,7 @@ static int launch_seed_kq(int nqpad, const HalfScanArgs& a, int device, hipStrea
 }
 
 // seed = true: the seed launch (fp32 rows); else a main launch over the fp16 shadow a.Xh (which the caller has ensured)
-int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, const Knobs& kn, int device, hipStream_t stream, int* nblocks_out) {
-    (void)kn;
+int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
     if (!seed) {
         if (!a.Xh || !half_shadow_dim(d)) return fail(MVDB_ERR_ARG, "internal: the certified pass needs the fp16 shadow (d = %d)", d);
         return launch_h16(d, nqpad, a, device, stream, nblocks_out);

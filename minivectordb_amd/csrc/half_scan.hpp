@@ -152,7 +152,7 @@ float half_xscale(float row_norm_bound);
 int launch_half_queries(const float* q, int64_t ld, int d, int nq, int nqpad, float xscale, _Float16* qf, float* qnorm,
                         float* qinv, hipStream_t stream);
 // seed: one tile per block over [tile0, tile1), every score dumped ([nq, blocks, 32] keys); *nblocks_out = blocks
-int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, const Knobs& kn, int device, hipStream_t stream, int* nblocks_out);
+int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out);
 int launch_half_certify(const HalfCertifyArgs& a, int nq, hipStream_t stream);
 // the fp16 shadow of rows [0, n) of X (ld floats per row) into Xh (d halves per row); dimensions the shadow kernels serve.
 // list_dev (set_rows): the n stored rows it names instead, X and Xh at row 0, rows at or above `limit` skipped

@@ -89,6 +89,22 @@ int cached_occupancy(const void* kern, int threads, size_t lds, int dflt) {
     return nb;
 }
 
+// Raises a kernel's dynamic-LDS limit once per (kernel, device): the attribute is per device, and one process may
+// hold indexes on several GPUs.  No size is exempt: kernels with 32 KiB of static lists on top of a 32 - 48 KiB ring
+// (half_scan.hip) have always had it set.
+int ensure_dynamic_lds(const void* kern, size_t lds, int device) {
+    if (lds == 0) return 0;
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> done;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = done[{kern, device}];
+    if (lds > have) {
+        MVDB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        have = lds;
+    }
+    return 0;
+}
+
 void set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -501,21 +517,6 @@ int launch_scan_rows(int metric, int mode, const ScanArgs& a, int nq, int device
 
 // Grid size the scan will use for (shape, n): needed up front to size the candidate buffer.
 int scan_grid_upper_bound(int device) { return device_cus(device) * 8; }
-
-// Raises a kernel's dynamic-LDS limit once per (kernel, device): the attribute is per device, and one process may
-// hold indexes on several GPUs.
-int ensure_dynamic_lds(const void* kern, size_t lds, int device) {
-    if (lds <= 48 * 1024) return 0;
-    static std::mutex mu;
-    static std::map<std::pair<const void*, int>, size_t> done;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& have = done[{kern, device}];
-    if (lds > have) {
-        MVDB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        have = lds;
-    }
-    return 0;
-}
 
 int launch_scan(int metric, int mode, const ScanArgs& a, int nq, int device, hipStream_t s,
                 int* nblocks) {
@@ -979,10 +980,10 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     const bool l2off = hn != nullptr;
     if (l2off) {
         a.hn = hn;
-        MVDB_TRY(launch_half_scan(idx->d, nqpad, false, a, idx->kn, idx->device, stream, &gx));
+        MVDB_TRY(launch_half_scan(idx->d, nqpad, false, a, idx->device, stream, &gx));
         hipLaunchKernelGGL(phase_fold_kernel, dim3(nq), dim3(1024), 0, stream, cand, gx, (const uint64_t*)nullptr, seed_keys, floors);
     } else {
-        MVDB_TRY(launch_half_scan(idx->d, nqpad, true, a, idx->kn, idx->device, stream, &gx));
+        MVDB_TRY(launch_half_scan(idx->d, nqpad, true, a, idx->device, stream, &gx));
         hipLaunchKernelGGL(phase_fold_kernel, dim3(nq), dim3(1024), 0, stream, cand, 2 * gx, (const uint64_t*)nullptr,
                            seed_keys, floors);
     }
@@ -1029,7 +1030,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     for (size_t p = ends.size(); p-- > 0;) {
         a.tile0 = covered;
         a.tile1 = ends[p];
-        MVDB_TRY(launch_half_scan(idx->d, nqpad, false, a, idx->kn, idx->device, stream, &gx));
+        MVDB_TRY(launch_half_scan(idx->d, nqpad, false, a, idx->device, stream, &gx));
         covered = ends[p];
         if (p > 0) {
             hipLaunchKernelGGL(phase_fold_kernel, dim3(nq), dim3(1024), 0, stream, cand, gx, seed_keys, seed_keys, floors);

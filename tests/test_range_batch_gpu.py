@@ -381,3 +381,48 @@ def test_against_the_float64_oracle(gpu):
         assert must <= got <= may, (i, len(must), len(got), len(may))
         assert (np.abs(D[lims[i]:lims[i + 1]] - s64[i][I[lims[i]:lims[i + 1]]]) <= tol).all()
     idx.close()
+
+
+@pytest.mark.parametrize("d", [384, 640, 768, 896])
+def test_shadow_widths_batch_search_and_range_against_the_oracle(gpu, monkeypatch, d):
+    """The widths of the fp16-shadow kernels that the shapes above leave out, 130 queries over 4,999 rows: one 256-query pass up
+    to d = 512, two 128-query passes above; a ragged last tile; fewer tiles (157) than workgroups x ring depth, so every block's
+    look-ahead runs past its last tile.  (The certified search of so small a corpus is nominated by its seed launch alone; the
+    range pass streams the shadow.)  Search: float64 adjudication of every query and distances within 1e-4 of the fp32 oracle's.
+    Range: every row at or above t + (d + 8) 2^-24 in float64 is returned, none below t - that (unit rows, unit queries)."""
+    from minivectordb_amd import _native
+    monkeypatch.setenv("MVDB_SPLIT_SCAN_MIN_NQ", "24")               # read when the index is created
+    n, nq, k = 4_999, 130, 10
+    x = flat.synth(n, d, 1234)
+    flat.normalize_l2(x)
+    q = flat.synth(nq, d, 777)
+    flat.normalize_l2(q)
+    idx = _native.FlatIndex(d)
+    idx.add(x)
+    _native.prof_enable(True)
+    try:
+        _native.prof_read("ip_scan_half_seed")
+        D, I = idx.search(q, k)
+        assert _native.prof_read("ip_scan_half_seed")[0] >= 1, "the certified pass did not run"
+    finally:
+        _native.prof_enable(False)
+    Do, Io = flat.flat_search(x, q, k)
+    for i in range(nq):
+        ok, msg = flat.adjudicate(x, q[i], k, D[i], I[i], tol=1e-4)
+        assert ok, f"query {i}: {msg}"
+    np.testing.assert_allclose(D, Do, atol=1e-4, rtol=0)
+
+    idx.set_option("range_shared", 2)
+    s64 = q.astype(np.float64) / np.linalg.norm(q.astype(np.float64), axis=1, keepdims=True) @ x.astype(np.float64).T
+    thr = np.sort(s64, axis=1)[np.arange(nq), -np.array([(3, 40, 400)[i % 3] for i in range(nq)])].astype(np.float32)
+    tol = (d + 8) * 2.0 ** -24
+    before = idx.range_counters()[0]
+    lims, Dr, Ir = idx.range_search(q, thr, normalize_q=True)
+    assert idx.range_counters()[0] > before and lims[-1] > 40 * (nq // 3)
+    for i in range(nq):
+        got = set(Ir[lims[i]:lims[i + 1]].tolist())
+        must = set(np.flatnonzero(s64[i] >= float(thr[i]) + tol).tolist())
+        may = set(np.flatnonzero(s64[i] >= float(thr[i]) - tol).tolist())
+        assert must <= got <= may, (i, len(must), len(got), len(may))
+        assert (np.abs(Dr[lims[i]:lims[i + 1]] - s64[i][Ir[lims[i]:lims[i + 1]]]) <= tol).all()
+    idx.close()
