@@ -218,6 +218,18 @@ int mvdb_index_set_rows_device(mvdb_index* idx, const int64_t* rows_host, const 
  * norm-range certificate) or, for ANY norms, by q.x - |x|^2 / 2 with per-row offsets beside the shadow, also under a bitmap;
  * else on the fp32 matrix cores as |q|^2 + |x|^2 - 2 q.x (d % 128 == 0, d <= 768; differences of the two forms are at the
  * rounding level of the norms).
+ * NON-FINITE ROWS AND QUERIES (NaN, +/-inf, -0.0) — one contract for every route of this call and of its subset, masked and
+ * row-set forms:
+ *   - The key score of a row is q.x for IP and -sum (q_j - x_j)^2 for L2.  NaN arises only where IEEE arithmetic on the
+ *     DIRECT form gives it: a NaN element, inf * 0, inf - inf.
+ *   - A row whose key score is NaN is never a result, on any route and at any k.
+ *   - Rows scoring +inf come first and rows scoring -inf come after every finite row.  Within equal scores, +/-inf included,
+ *     the lower row (or lower position in a row list) comes first.
+ *   - Slots beyond the non-NaN rows are I = -1, D = -FLT_MAX (IP) / +FLT_MAX (L2).  This holds whether the shortfall comes from
+ *     k > n, from the selection or from NaN rows.
+ *   - normalize_q follows fvec_renorm_L2 literally: nr > 0 false leaves the query as it is, and nr = inf multiplies by 0.
+ *   - A score that overflows to +/-inf from FINITE elements is outside the contract.  It depends on summation order and on
+ *     fused multiply-add.
  * Replaces faiss.normalize_L2(embedding) + index.search(embedding, search_k)
  *                                                minivectordb/vector_database.py:475, :497
  *                                                minivectordb/sharded_vector_database.py:604, :626 */

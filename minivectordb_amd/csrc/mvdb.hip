@@ -638,7 +638,9 @@ int launch_mfma2_gated_inst(const MfmaScanArgs& a, int device, hipStream_t strea
 template <int KB, int NG, int SKB>
 int launch_mfma2_inst(const MfmaScanArgs& a, int device, hipStream_t stream, int* nblocks_out, int metric = MVDB_METRIC_IP) {
     // the L2 form exists where it fits the registers (mfma_path_ok / two_groups route L2 batches accordingly)
-    constexpr bool kL2Form = KB <= 48 && !(KB == 32 && NG == 2);
+    // (d = 768 with 1-KiB stages: the L2 epilogue's non-finite cases do not fit beside 192 registers of query fragments and
+    //  64 of staged row — launch_mfma2 gives L2 the 512-B stages there)
+    constexpr bool kL2Form = KB <= 48 && !(KB == 32 && NG == 2) && !(KB == 48 && SKB == 16);
     auto kern = flat_scan_mfma2_kernel<KB, NG, SKB, 0>;
     if (metric == MVDB_METRIC_L2) {
         if constexpr (kL2Form)
@@ -679,8 +681,8 @@ int launch_mfma2(int KB, const MfmaScanArgs& a, int device, hipStream_t s, int* 
         // query fragments leave one wave per SIMD, like two groups at d = 512
         case 40: if (NG == 1) return launch_mfma2_inst<40, 1, 8>(a, device, s, nb, metric);   // (d = 640 / 896: round 6 — the exact pass
                  break;                                                                      //  behind the rescue tier at those widths)
-        case 48: if (NG == 1) return deep ? launch_mfma2_inst<48, 1, 16>(a, device, s, nb, metric)
-                                          : launch_mfma2_inst<48, 1, 8>(a, device, s, nb, metric);
+        case 48: if (NG == 1) return deep && metric != MVDB_METRIC_L2 ? launch_mfma2_inst<48, 1, 16>(a, device, s, nb, metric)
+                                                                      : launch_mfma2_inst<48, 1, 8>(a, device, s, nb, metric);
                  break;
         case 56: if (NG == 1) return launch_mfma2_inst<56, 1, 8>(a, device, s, nb, metric);
                  break;
@@ -1624,7 +1626,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
         }
         hipLaunchKernelGGL(emit_sorted_kernel, dim3((k + 255) / 256), dim3(256), 0, s,
                            ws->selkeys.p, k, idx->metric, label_offset, D_dev + (int64_t)qi * k,
-                           I_dev + (int64_t)qi * k, mask_dev ? 1 : 0);
+                           I_dev + (int64_t)qi * k, 0);
         MVDB_HIP(hipGetLastError());
     }
     return 0;

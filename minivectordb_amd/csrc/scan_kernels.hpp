@@ -59,7 +59,7 @@ __device__ __forceinline__ float group_reduce_add(float v) {
 // SEL    : 0 every row; 1 rows[] indirection (compile-time, so the identity path carries no branch and — crucially —
 //          no `s_waitcnt vmcnt(0)` between the row loads of a batch); 2 bitmap (a.mask): rows in corpus order, the bit of
 //          each row of the NEXT batch fetched behind the current batch's row loads; a clear bit only keeps the row out of
-//          the top-k gate (and writes -inf in score mode) — dense filters (exclude-filters keep most rows) then cost one
+//          the top-k gate (and writes kNotCandidate in score mode) — dense filters (exclude-filters keep most rows) then cost one
 //          full scan instead of a gather that is slower than the scan it avoids.
 // MASKED : the row has fewer than G*C chunks (lanes with chunk >= d4 load nothing).  When the row
 //          fills every lane the loads are unconditional: no exec-mask branches in the loop.
@@ -186,8 +186,11 @@ __global__ __launch_bounds__(kScanThreads) void flat_scan_kernel(ScanArgs a) {
             for (int u = 0; u < U; ++u) {
                 const int64_t r = row0 + (int64_t)u * RPI;
                 if (t == 0 && r < a.n) {
+                    // a row that is no candidate — its score is NaN, or its bit is clear — carries kNotCandidate, which no
+                    // candidate can: the select orders it behind every real score, -inf included, and the emitter drops it
                     const float v = s[u];
-                    a.scores[(int64_t)qi * a.n + r] = (v == v && (SEL != 2 || sel[u])) ? v : -INFINITY;
+                    reinterpret_cast<uint32_t*>(a.scores)[(int64_t)qi * a.n + r] =
+                        (v == v && (SEL != 2 || sel[u])) ? __float_as_uint(v) : kNotCandidate;
                 }
             }
         } else {

@@ -112,7 +112,7 @@ __device__ __forceinline__ void flat_scan_mfma_body(const MfmaScanArgs& a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {  // padded query slots never pass the gate
             thr[g][r] = (g * 16 + 4 * (lane >> 4) + r) < a.nq ? -INFINITY : INFINITY;
-            thr_row[g][r] = 0u;
+            thr_row[g][r] = kNoFloorRow;  // no floor: a row scoring -inf enters while the list has room (topk_device.hpp)
             floor0[g][r] = -INFINITY;
         }
 
@@ -218,7 +218,7 @@ __device__ __forceinline__ void flat_scan_mfma2_body(const MfmaScanArgs& a) {
             const int qi = g * 16 + 4 * (lane >> 4) + r;
             floor0[g][r] = qi < a.nq && a.thr0 ? a.thr0[qi] : -INFINITY;   // (a floor carries row 0: nothing ties its way past it)
             thr[g][r] = qi < a.nq ? floor0[g][r] : INFINITY;
-            thr_row[g][r] = 0u;
+            thr_row[g][r] = floor_row(floor0[g][r]);
         }
     // METRIC 1 (squared L2 by |q|^2 + |x|^2 - 2 q.x; the lists keep -distance as everywhere): |q|^2 of the four queries
     // whose scores this lane's accumulator registers hold — query g 16 + 4 (lane >> 4) + r
@@ -335,7 +335,41 @@ __device__ __forceinline__ void flat_scan_mfma2_body(const MfmaScanArgs& a) {
 #pragma unroll
             for (int g = 0; g < NG; ++g)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[g][r] = (2.f * acc[g][r] - xs) - qn[g][r];  // -(|q|^2 + |x|^2 - 2 q.x)
+                for (int r = 0; r < 4; ++r) {
+                    float v = (2.f * acc[g][r] - xs) - qn[g][r];  // -(|q|^2 + |x|^2 - 2 q.x)
+                    // An infinite element makes |x|^2 or |q|^2 +inf and the expansion inf - inf: the score is then what the direct
+                    // form sum (q_j - x_j)^2 gives — the contract of every route.  One side infinite: every term
+                    // of the other is finite, the distance is +inf (NaN if the other side holds a NaN: inf + NaN).
+                    if (xs == INFINITY || qn[g][r] == INFINITY) v = -(xs + qn[g][r]);
+                    acc[g][r] = v;
+                }
+            // Both infinite: only the elements tell (inf - inf in ONE column is NaN, anything else +inf), so the wave scores
+            // such a (row, query) pair directly from memory, 64 elements at a time — a row AND a query with an infinite
+            // element, off every measured path.  Wave-uniform control flow, wave-uniform addresses.
+            if (__ballot(xs == INFINITY)) {
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        uint64_t both = __ballot(xs == INFINITY && qn[g][r] == INFINITY);
+                        while (both) {
+                            const int src = __ffsll((long long)both) - 1;
+                            both &= both - 1;
+                            const int64_t srow = tile * 16 + (src & 15);
+                            const float* xp = a.X + (srow <= last ? srow : last) * a.ld;
+                            const float* qp = a.q + (int64_t)(g * 16 + 4 * (src >> 4) + r) * a.ld;
+                            float dsum = 0.f;
+#pragma unroll 1
+                            for (int j = lane; j < KB * 16; j += 64) {
+                                const float t = qp[j] - xp[j];
+                                dsum = fmaf(t, t, dsum);
+                            }
+#pragma unroll
+                            for (int m = 32; m >= 1; m >>= 1) dsum += __shfl_xor(dsum, m);
+                            if (lane == src) acc[g][r] = -dsum;
+                        }
+                    }
+            }
         }
         mfma_tile_select<NG>(acc, thr, thr_row, tile * 16 + fr <= last && ((mw >> ((int)(tile & 1) * 16 + fr)) & 1u), (uint32_t)(tile * 16 + fr), a.nq, k,
                              mylists, lane, floor0);
@@ -416,7 +450,7 @@ __device__ __forceinline__ void flat_scan_gemm_body(const GemmScanArgs& a) {
 
     // thresholds of this lane's two queries (query = n0 + wn*64 + j*32 + fr)
     float thr[2];
-    uint32_t thr_row[2] = {0u, 0u};
+    uint32_t thr_row[2] = {kNoFloorRow, kNoFloorRow};  // no floor: rows scoring -inf enter while the list has room
 #pragma unroll
     for (int j = 0; j < 2; ++j) thr[j] = (n0 + wn * 64 + j * 32 + fr) < a.nq ? -INFINITY : INFINITY;
 

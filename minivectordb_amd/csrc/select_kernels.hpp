@@ -5,7 +5,9 @@
 // tests/test_sharded_multithreaded_operations.py:65-68), so large k must work; it is not the
 // bandwidth path (the score vector is 4 B per row against ld*4 B per row of corpus).
 //
-//   1. flat_scan_kernel<MODE = kModeScores> writes scores[n]
+//   1. flat_scan_kernel<MODE = kModeScores> writes scores[n]; a row that is no candidate (NaN score, bit clear under a
+//      bitmap) gets kNotCandidate, whose keys sort behind every candidate's: when fewer than k candidates exist the select
+//      picks some of them, last, and emit_sorted_kernel turns them into missing results
 //   2. 8 x (radix_hist_kernel, radix_pick_kernel): MSB-first 8-bit radix select of the k-th
 //      largest 64-bit key (score image << 32 | ~row) — keys are unique, so the answer is exact
 //      and ties resolve to the lower row number
@@ -128,14 +130,18 @@ __global__ void zero_tail_kernel(uint64_t* keys, int64_t from, int64_t to) {
     if (i < to) keys[i] = 0;
 }
 
-// drop_unselected: bitmap-selected search — rows outside the mask were written with score -inf and are not results
+// A key whose upper word is 0 belongs to a row that was no candidate (kNotCandidate in the score vector: its score was NaN, or
+// its bit in the search's bitmap clear) or is the zero padding behind the k_eff selected keys: such a slot is a missing result.
+// Candidates scoring -inf are results like any other and come last.
+// drop_neg_inf: the int8 cosine index's score vectors (cos8_kernels.hpp) mark "not selected" with -inf, which no cosine
+// distance is; the flat index passes 0.
 __global__ void emit_sorted_kernel(const uint64_t* __restrict__ keys, int k, int metric,
                                    int64_t label_offset, float* __restrict__ D,
-                                   int64_t* __restrict__ I, int drop_unselected) {
+                                   int64_t* __restrict__ I, int drop_neg_inf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;
     const uint64_t key = keys[i];
-    if (key && !(drop_unselected && key_score(key) == -INFINITY)) {
+    if ((key >> 32) != 0 && !(drop_neg_inf && key_score(key) == -INFINITY)) {
         const float s = key_score(key);
         D[i] = metric == 0 ? s : -s;
         I[i] = label_offset + (int64_t)key_row(key);

@@ -4,7 +4,11 @@
 // Larger key == better candidate: higher score first, then LOWER row number — the deterministic
 // restatement of faiss' (score, id) heap ordering used by IndexFlatIP.search
 // (reference call site: minivectordb/vector_database.py:497).  Key 0 is the "empty slot" sentinel:
-// every real key is > 0 because the image of any non-NaN float is > 0.
+// the image of every non-NaN float is >= 0x007FFFFF (that of -inf), so every key made from one is > 0.
+// NaN has no place in the order: the image of a positive NaN lies ABOVE that of +inf (0xFFC00000 for the
+// default NaN: it would come first in every list) and that of a negative NaN below that of -inf, down to
+// 0 for the all-ones pattern.  Nothing here keeps a NaN out: the gate in front of every make_key does
+// (`s >= thr_score`, beats_key, `v == v` — comparisons a NaN fails), and a score that is NaN must fail it.
 //
 // A wave keeps its best k <= 64 keys SORTED DESCENDING, one per lane (lane i = i-th best).  Rows
 // are admitted through a threshold gate (the k-th best so far), so after warm-up almost no row
@@ -17,6 +21,10 @@ namespace mvdb {
 
 constexpr int kWave = 64;
 constexpr int kMaxFusedK = 64;  // fused select keeps one candidate per lane
+// Score-vector marker of the k > 64 route (scan_kernels.hpp kModeScores -> select_kernels.hpp): "this row is no candidate".
+// The one bit pattern whose image is 0 — a NaN, which no candidate's score is once the `v == v` gate has spoken — so its keys
+// (0 << 32 | ~row) sort behind every candidate's, -inf included, and are told from them by their upper word alone.
+constexpr uint32_t kNotCandidate = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t f2ord(float f) {
     uint32_t u = __float_as_uint(f);
@@ -94,6 +102,11 @@ __device__ __forceinline__ bool l2_certified(float rk, float u, float eps_q, flo
 // that the key order then refused — 64 queries over 1M identical rows took 21.8 ms instead of 0.33
 // (benchmarks/ties_probe.py).  A floor (no list key behind the score) carries row 0: nothing ties its way past a floor —
 // floors come from rows of earlier phases, i.e. lower rows.
+// The one exception is "no floor at all" (-inf while the list is not full): it carries kNoFloorRow, the row after every row, so
+// that a row scoring -inf — one infinite element of the wrong sign — still enters a list that has room, as it does on the
+// single-query scan (`s >= thr_score`).  NaN fails both comparisons whatever the threshold.
+constexpr uint32_t kNoFloorRow = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t floor_row(float floor0) { return floor0 == -INFINITY ? kNoFloorRow : 0u; }
 __device__ __forceinline__ bool beats_key(float s, uint32_t row, float thr, uint32_t thr_row) {
     return s > thr || (s == thr && row < thr_row);
 }
@@ -101,7 +114,7 @@ __device__ __forceinline__ void set_threshold(uint64_t kth, float floor0, float&
     const float ks = kth ? key_score(kth) : -INFINITY;
     const bool from_list = kth != 0ull && ks >= floor0;
     thr = from_list ? ks : floor0;
-    thr_row = from_list ? key_row(kth) : 0u;
+    thr_row = from_list ? key_row(kth) : floor_row(floor0);
 }
 
 // wave-cooperative sorted insert into an LDS list; returns the list's new k-th key

@@ -91,16 +91,15 @@ def key_scores_f64(x, q, rows, metric, normalize_q):
 ODD_ROWS = np.array([7, 8, 9])   # the rows spike() gives a non-finite element
 
 
-def reference(idx, q1, rs, k, metric, normalize_q, nan_set):
-    """The single-query top-k of the existing path, nq = 1, without the rows whose score is NaN (the k > 64 route lists them
-    with score -inf; k is raised by their number so that k real entries remain where there are that many) and without
-    missing markers."""
-    kk = int(k + len(nan_set))
+def reference(idx, q1, rs, k, metric, normalize_q):
+    """The single-query top-k of the existing path, nq = 1, without missing markers.  Rows whose score is NaN are in no top-k
+    list at any k, and rows scoring -inf are listed last, under a bitmap too: the range result is
+    compared with it as it stands."""
     if rs is None:
-        D, I = idx.search(q1[None], kk, normalize_q=normalize_q)
+        D, I = idx.search(q1[None], int(k), normalize_q=normalize_q)
     else:
-        D, I = idx.search_rowset(q1[None], kk, rs, normalize_q=normalize_q)
-    keep = np.array([r >= 0 and int(r) not in nan_set for r in I[0]])
+        D, I = idx.search_rowset(q1[None], int(k), rs, normalize_q=normalize_q)
+    keep = I[0] >= 0
     return D[0][keep], I[0][keep]
 
 
@@ -110,18 +109,9 @@ def check_query(idx, x, q1, rs, rows, t, got_D, got_I, metric, normalize_q, what
     ip = metric == flat.METRIC_IP
     assert (got_D >= t).all() if ip else (got_D <= t).all(), what
     assert not (set(got_I.tolist()) & nan_set), what                  # rows with NaN scores never match
-    if rs is not None and rs.is_bitmap:
-        # the k > 64 route under a bitmap cannot tell a row that scores -inf from a row outside the set and drops both: such
-        # rows (they only pass a threshold of -inf) are checked against the float64 restatement instead, lowest row first
-        tail = got_D == (-np.inf if ip else np.inf)
-        assert not tail.any() or tail[np.argmax(tail):].all(), what   # ... they come last
-        assert got_I[tail].tolist() == (rows[s64 == -np.inf].tolist() if tail.any() else []), what
-        got_D, got_I = got_D[~tail], got_I[~tail]
     count = len(got_D)
-    Dw, Iw = reference(idx, q1, rs, count + 8, metric, normalize_q, nan_set)
-    if rs is not None and rs.is_bitmap:    # (the k <= 64 route does list such rows under a bitmap: dropped on this side too)
-        worst = Dw == (-np.inf if ip else np.inf)
-        Dw, Iw = Dw[~worst], Iw[~worst]
+    Dw, Iw = reference(idx, q1, rs, count + 8, metric, normalize_q)
+    assert not (set(Iw.tolist()) & nan_set), what                     # ... and are in no top-k list either
     assert len(Dw) >= count, (what, len(Dw), count)
     same = (got_I == Iw[:count]) & (got_D.view(np.uint32) == Dw[:count].view(np.uint32))
     if not same.all():
@@ -161,8 +151,7 @@ def test_range_is_bit_identical_to_the_top_k_path(gpu, d, metric):
                 # stored scores to aim at: each query's 20th and 37th best (NaN / inf queries have none)
                 top = []
                 for i in range(NQ):
-                    s64 = key_scores_f64(x, q[i], rows, metric, normalize_q)
-                    top.append(reference(idx, q[i], rs, 64, metric, normalize_q, set(rows[np.isnan(s64)].tolist()))[0])
+                    top.append(reference(idx, q[i], rs, 64, metric, normalize_q)[0])
                 aims = [float(t[19]) for t in top if len(t) > 36 and np.isfinite(t[19])]
                 shared = float(np.median(aims))
                 # above every finite score (rows 8 and 9 score +-inf against most queries: only the all-zero query 6 and the
