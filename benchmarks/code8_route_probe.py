@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""The single-query int8 route beside the exact fp32 scan, in ONE process and on one corpus.
+
+Per configuration one JSON line: the prefilter launch's own mean duration (the library's `ip_scan` timer), its true rate on
+N (d + 8) bytes, the wall time per query, and whether (D, I) of the first queries equal the exact scan's bit for bit.  The
+last line is the exact scan (`code8_single_query = 0`): its launch time and rate on N d 4 bytes.
+
+  python3 benchmarks/code8_route_probe.py                              # 10M x 512, the grid the library picks
+  python3 benchmarks/code8_route_probe.py --blocks 2,3,4               # MVDB_SCAN_BLOCKS_PER_CU swept in-process
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 benchmarks/code8_route_probe.py --timers 0
+      (one trace session with both kernels: 200 route steps, then 40 exact scans; --timers 0 keeps the library's event
+       pairs out of the stream, so the gaps in the trace are the route's own)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=512)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--exact-steps", type=int, default=40)
+    ap.add_argument("--blocks", default="0", help="comma list of MVDB_SCAN_BLOCKS_PER_CU values (0 = the library's choice)")
+    ap.add_argument("--timers", type=int, default=1, help="0: no per-launch event timers (for runs under a tracer)")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from minivectordb_amd import _native as native
+
+    n, d, k = args.rows, args.dim, args.k
+    W, K = args.warmup, args.steps
+    dev = torch.device("cuda", 0)
+    idx = native.FlatIndex(d, device=0)
+    idx.reserve(n)
+    idx.add_synthetic(n, 1234, normalize=True)
+    nqs = W + K
+    queries = torch.empty((nqs, d), dtype=torch.float32, device=dev)
+    native.check(native.lib().mvdb_synth_fill_device(queries.data_ptr(), nqs, d, 5678, 0, 1, 0, torch.cuda.current_stream().cuda_stream))
+    D = torch.empty((1, k), dtype=torch.float32, device=dev)
+    I = torch.empty((1, k), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(first, count):
+        for i in range(first, first + count):
+            idx.search_device(queries[i].data_ptr(), 1, k, D.data_ptr(), I.data_ptr(), stream)
+        torch.cuda.synchronize()
+
+    def results(count):
+        out = []
+        for i in range(W, W + count):
+            run(i, 1)
+            out.append((D.cpu().numpy().view(np.uint32).copy(), I.cpu().numpy().copy()))
+        return out
+
+    def measure(steps, bytes_per_launch, label):
+        run(0, W)
+        native.prof_read("ip_scan")
+        native.prof_enable(bool(args.timers))
+        t0 = time.perf_counter()
+        run(W, steps)
+        dt = time.perf_counter() - t0
+        native.prof_enable(False)
+        launches, ms = native.prof_read("ip_scan")
+        avg = ms / max(launches, 1)
+        rec = dict(label, rows=n, dim=d, k=k, steps=steps, kernel=native.prof_symbol("ip_scan"), launches=launches,
+                   launch_ms=round(avg, 5), true_bytes_per_launch=bytes_per_launch,
+                   true_tb_per_s=round(bytes_per_launch / (avg * 1e-3) / 1e12, 4) if avg > 0 else None,
+                   ms_per_query=round(dt / steps * 1e3, 5))
+        return rec
+
+    idx.set_option("code8_single_query", 0)
+    want = results(8)
+    idx.set_option("code8_single_query", 1)
+    run(0, 3)   # the third eligible query builds the code
+    for blocks in args.blocks.split(","):
+        os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = blocks if int(blocks) > 0 else ""
+        idx.reload_env()
+        got = results(8)
+        same = all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(got, want))
+        rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks)})
+        fb, cand, calls = idx.code8_counters()
+        rec.update(bit_equal_exact_scan=bool(same), fallbacks=fb, last_candidates=cand)
+        print(json.dumps(rec), flush=True)
+    os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = ""
+    idx.reload_env()
+    idx.set_option("code8_single_query", 0)
+    if args.exact_steps > 0:
+        print(json.dumps(measure(args.exact_steps, n * d * 4, {"route": "exact"})), flush=True)
+    idx.close()
+
+
+if __name__ == "__main__":
+    main()

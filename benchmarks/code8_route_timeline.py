@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""Per-launch durations and the gaps between launches of the single-query int8 route, from a rocprofv3 kernel trace
+(`--kernel-trace --output-format csv`, the directory or the *_kernel_trace.csv itself) of `code8_route_probe.py --timers 0`
+or of `bench.py`.  A step is the run of dispatches from one `code8_query_kernel` to the next; only steps with the most
+common number of launches are averaged (the first ones build the code).  Prints one JSON object:
+launches in order with their mean / median duration, the mean gap before each, their sums, the mean step span, and the
+mean duration of the exact scan's launches (steps with `code8_single_query = 0`) where the trace has them.
+
+usage: code8_route_timeline.py <trace dir or csv> [git-head]"""
+import collections
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+
+
+def main():
+    src = sys.argv[1]
+    head = sys.argv[2] if len(sys.argv) > 2 else None
+    if os.path.isdir(src):
+        src = glob.glob(os.path.join(src, "**", "*_kernel_trace.csv"), recursive=True)[0]
+    rows = []
+    for r in csv.DictReader(open(src)):
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
+    rows.sort()
+    steps, cur = [], None
+    for r in rows:
+        if "code8_query_kernel" in r[2]:
+            cur = []
+            steps.append(cur)
+        elif cur is not None and "flat_scan_kernel<64, 2, 2, 0, 0, true, 0, false, false>" in r[2]:
+            cur = None   # the exact scans behind the route steps
+        if cur is not None:
+            cur.append(r)
+    common = collections.Counter(len(s) for s in steps).most_common(1)[0][0]
+    steps = [s for s in steps if len(s) == common][5:]
+    launches = []
+    for j in range(common):
+        dur = [s[j][1] - s[j][0] for s in steps]
+        gap = [s[j][0] - s[j - 1][1] for s in steps] if j else [0]
+        launches.append({"kernel": steps[0][j][2].split("(")[0], "mean_us": round(statistics.mean(dur) / 1e3, 3),
+                         "median_us": round(statistics.median(dur) / 1e3, 3), "gap_before_mean_us": round(statistics.mean(gap) / 1e3, 3)})
+    exact = [r[1] - r[0] for r in rows if "flat_scan_kernel<64, 2, 2, 0, 0, true, 0, false, false>" in r[2]]
+    out = {"git_head": head, "steps_averaged": len(steps), "launches_per_step": common, "launches": launches,
+           "sum_of_launches_us": round(sum(l["mean_us"] for l in launches), 3),
+           "sum_of_gaps_us": round(sum(l["gap_before_mean_us"] for l in launches), 3),
+           "step_span_mean_us": round(statistics.mean(s[-1][1] - s[0][0] for s in steps) / 1e3, 3),
+           "exact_scan_launches": len(exact),
+           "exact_scan_mean_us": round(statistics.mean(exact) / 1e3, 3) if exact else None,
+           "exact_scan_median_us": round(statistics.median(exact) / 1e3, 3) if exact else None}
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()

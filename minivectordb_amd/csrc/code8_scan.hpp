@@ -10,7 +10,7 @@
 //
 // Shape of the work (flat_scan_kernel's): G lanes share a row, one 16-byte chunk each (d = 512: G = 32, two rows per
 // wave-instruction), U row groups in flight per wave, non-temporal loads, a persistent grid, no branch between the loads of a
-// batch.  Per 16 bytes: eight v_dot4_i32_i8, then a log2(G)-step integer butterfly.
+// batch.  Per 16 bytes: eight v_dot4_i32_i8; per batch one halving reduction of the U sums and one epilogue (code8_reduce).
 #pragma once
 #include "scan_kernels.hpp"
 
@@ -216,12 +216,59 @@ struct Code8ScanArgs {
     unsigned long long* counter;  // zeroed by the prologue; keeps counting past cap
 };
 
+// lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
+// LDS-crossbar trip, no address register); 4 and 16 are ds_swizzle's bit mode; 32 crosses the halves of the wave.
+template <int M>
+__device__ __forceinline__ int lane_xor(int v) {
+    if constexpr (M == 1)
+        return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);   // quad_perm [1, 0, 3, 2]
+    else if constexpr (M == 2)
+        return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);   // quad_perm [2, 3, 0, 1]
+    else if constexpr (M == 8)
+        return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);  // row_ror:8
+    else if constexpr (M == 4 || M == 16)
+        return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1F);           // bit mode: and 0x1F, or 0, xor M
+    else
+        return __shfl_xor(v, M);
+}
+
+// U per-lane partial sums T[0 .. U) -> ONE total per lane: the sum over the G lanes of a row group of T[ue], ue the
+// bit reversal of (t & (U - 1)) in log2(U) bits.  A halving step sends the half of the values the partner keeps and keeps
+// the other half: U - 1 exchanges, then log2(G / U) for the single value left — U - 1 + log2(G / U) cross-lane
+// operations where a butterfly per value takes U log2(G).  Integer sums: any order gives the same bits.
+template <int G, int U, int M = 1>
+__device__ __forceinline__ int code8_reduce(int (&T)[U], int t) {
+    if constexpr (M < U) {
+        constexpr int H = U / (2 * M);   // values left after this step
+        const bool hi = (t & M) != 0;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const int send = hi ? T[j] : T[j + H];
+            const int keep = hi ? T[j + H] : T[j];
+            T[j] = keep + lane_xor<M>(send);
+        }
+        return code8_reduce<G, U, M * 2>(T, t);
+    } else if constexpr (M < G) {
+        T[0] += lane_xor<M>(T[0]);
+        return code8_reduce<G, U, M * 2>(T, t);
+    } else {
+        return T[0];
+    }
+}
+
+// One wave takes batches of RB = (64 / G) U consecutive rows, U KiB of codes (d = 16 G; 768 U bytes at d = 384).  Per batch:
+// U 16-byte loads per lane at one base per batch + a lane offset that never changes + u row-group strides, ONE 8-byte load of
+// (a, r) (lane (g, t) reads the entry of the row whose total code8_reduce leaves in it), 8 U v_dot4_i32_i8, the reduction
+// above, and ONE epilogue + ballot for the RB rows of the batch (lanes t < U hold one row each).  Full batches run in a loop
+// without a row clamp or a row test; the one partial batch at the end of the index is done by the wave whose turn it is,
+// with both.
 template <int G, int U, bool MASKED>
 __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
     constexpr int RB = RPI * U;
+    static_assert(U >= 2 && U <= 8 && (U & (U - 1)) == 0 && U <= G, "code8_reduce halves U down to one value inside a row group");
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = lane % G;
     const int g = lane / G;
     const bool valid = !MASKED || t * 16 < a.d;
@@ -245,8 +292,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         if (lane < nst && base + (unsigned long long)lane < cap) a.cand[base + lane] = stage;
         nst = 0;
     };
-    auto append = [&](bool pass, uint32_t row) {
-        uint64_t m = __ballot(pass);
+    auto append = [&](uint64_t m, uint32_t row) {
         while (m) {
             const int src = __ffsll((long long)m) - 1;
             m &= m - 1;
@@ -256,27 +302,14 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         }
     };
 
-    const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
-    const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
-    const int64_t nbatches = (a.n + RB - 1) / RB;
-    const int64_t last = a.n - 1;
-
-    for (int64_t b = gw; b < nbatches; b += nwaves_total) {
-        const int64_t row0 = b * RB + g;
-        i32x4 x[U];
-        float2 sr[U];
+    // the row of the batch whose total this lane ends up with (code8_reduce), and whether it is the lane that reports it
+    int ue = 0;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int64_t r = row0 + (int64_t)u * RPI;
-            r = r < last ? r : last;  // clamp: tail lanes re-read the last row, result discarded
-            const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + r * (int64_t)a.d + t * 16);
-            if (MASKED)
-                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
-            else
-                x[u] = __builtin_nontemporal_load(src);
-            sr[u] = a.ar[r];
-        }
-        int T[U];
+    for (int m = 1, h = U / 2; m < U; m <<= 1, h >>= 1) ue += (t & m) ? h : 0;
+    const int erow = ue * RPI + g;
+    const uint64_t elanes = __ballot(t < U);
+
+    auto scores = [&](const i32x4 (&x)[U], int (&T)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             int hi = 0, lo = 0;
@@ -287,22 +320,65 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             }
             T[u] = hi * 256 + lo;
         }
-#pragma unroll
-        for (int m = G / 2; m >= 1; m >>= 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) T[u] += __shfl_xor(T[u], m);
-        }
+    };
+    // every lane evaluates the predicate (its (a, r) load is issued with the batch's code loads, not behind a lane test);
+    // `mine` keeps the bits of the lanes that report a row
+    auto epilogue = [&](int tot, float2 sr, uint64_t mine, int64_t r) {
+        const float s = ((float)tot * qstep) * sr.x;
+        float m = fmaf(alpha, sr.y, beta);
+        m = fmaf(fabsf(s) + m, 2.4e-7f, m);   // the rounding of s + m itself
+        const float ub = s + m;
+        // NaN (0 * inf: a zero query against a row of unbounded residual) passes
+        const uint64_t pass = __ballot(!(ub < floor)) & mine;
+        if (pass) append(pass, (uint32_t)r);
+    };
+
+    const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
+    const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
+    const int64_t nfull = a.n / RB;
+    const int64_t batch_bytes = (int64_t)RB * a.d;
+    const int64_t group_bytes = (int64_t)RPI * a.d;
+    const int lane_off = g * a.d + t * 16;
+
+    auto load = [&](i32x4 (&x)[U], float2& sr, int64_t b) {
+        const int8_t* base = a.codes + b * batch_bytes + lane_off;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t r = row0 + (int64_t)u * RPI;
-            const float s = ((float)T[u] * qstep) * sr[u].x;
-            float m = fmaf(alpha, sr[u].y, beta);
-            m = fmaf(fabsf(s) + m, 2.4e-7f, m);   // the rounding of s + m itself
-            const float ub = s + m;
-            // NaN (0 * inf: a zero query against a row of unbounded residual) passes
-            const bool pass = (t == 0) && (r < a.n) && !(ub < floor);
-            if (__ballot(pass)) append(pass, (uint32_t)r);
+            const i32x4* src = reinterpret_cast<const i32x4*>(base + u * group_bytes);
+            if (MASKED)
+                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
+            else
+                x[u] = __builtin_nontemporal_load(src);
         }
+        sr = a.ar[b * RB + erow];
+    };
+    for (int64_t b = gw; b < nfull; b += nwaves_total) {
+        i32x4 x[U];
+        float2 sr;
+        load(x, sr, b);
+        int T[U];
+        scores(x, T);
+        epilogue(code8_reduce<G, U>(T, t), sr, elanes, b * RB + erow);
+    }
+    // the partial batch behind the full ones: rows past the end re-read the last row, their result is discarded
+    if (nfull * RB < a.n && nfull % nwaves_total == gw) {
+        const int64_t last = a.n - 1;
+        i32x4 x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int64_t r = nfull * RB + (int64_t)u * RPI + g;
+            r = r < last ? r : last;
+            const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + r * (int64_t)a.d + t * 16);
+            if (MASKED)
+                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
+            else
+                x[u] = __builtin_nontemporal_load(src);
+        }
+        const int64_t r = nfull * RB + erow;
+        const float2 sr = a.ar[r < last ? r : last];
+        int T[U];
+        scores(x, T);
+        epilogue(code8_reduce<G, U>(T, t), sr, __ballot(t < U && r < a.n), r);
     }
     if (nst) flush();
 }

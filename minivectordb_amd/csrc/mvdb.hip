@@ -1998,7 +1998,8 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
     constexpr int RB = (kWave / G) * U;
     const int64_t nbatches = (a.n + RB - 1) / RB;
     const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
-    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), 2);  // flat_scan_kernel's grid: CUs x 2 blocks
+    // CUs x 2 blocks: measured for this kernel (3 and 4 blocks per CU are 3 - 7 % slower at every served shape)
+    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), 2);
     if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
     prof_symbol("ip_scan", "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
@@ -2076,9 +2077,10 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.cand = cand;
     c.cap = cap;
     c.counter = counter;
+    // (U per shape: measured)
     if (d == 512) MVDB_TRY((launch_code8_scan<32, 4, false>(c, idx->device, s)));
     else if (d == 1024) MVDB_TRY((launch_code8_scan<64, 4, false>(c, idx->device, s)));
-    else MVDB_TRY((launch_code8_scan<32, 4, true>(c, idx->device, s)));
+    else MVDB_TRY((launch_code8_scan<32, 8, true>(c, idx->device, s)));
     // 3. candidates -> ascending row list, padded with the row of NaN in the matrix' slack
     const int64_t pad = idx->cap + kRowSlack - 1;  // the NaN row in the matrix' slack (ensure_code8)
     hipLaunchKernelGGL(code8_list_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, (const uint32_t*)cand,
