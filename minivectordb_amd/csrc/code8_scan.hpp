@@ -4,7 +4,8 @@
 // of |x_i - a_i c_i|.  One pass over the codes (1 byte per element instead of 4) computes s~_i = q~ . (a_i c_i) exactly in
 // integers (q~: the query rounded to 16 / 15 bits, held as two int8 planes) and keeps every row whose upper bound
 // u_i = s~_i + m_i reaches a floor that is proven to lie at or below the final k-th best score.  The kept rows — a few
-// thousand of 10M — are then scored by flat_scan_kernel's row-list form: the bits of (D, I) are the full scan's.
+// thousand of 10M — are then scored by code8_rescore_kernel with flat_scan_kernel's arithmetic: the bits of (D, I) are the full scan's.
+// The floor is the k-th best LOWER bound s~_i - m_i of a sample of rows (code8_seed_kernel): one launch in front of the pass.
 //
 // Roofline: HBM.  Algorithmic bytes per launch = n * (d + 8): every code once, 8 bytes of (a, r) per row.
 //
@@ -114,19 +115,10 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
     }
 }
 
-// rows of the seed sample: S rows spread evenly over [0, n) (n >= S: distinct, ascending)
-__global__ void code8_seed_rows_kernel(int64_t* __restrict__ rows, int64_t S, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < S) rows[i] = (i * n) / S;
-}
-// (the padding row of the candidate list)
-__global__ void code8_fill_nan_kernel(float* __restrict__ p, int64_t count) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) p[i] = __uint_as_float(0x7FC00000u);
-}
-
-// ---- prologue: the query -> two int8 planes + the margin's terms; zeroes the candidate counter ---------------------------------
+// ---- prologue: the query -> two int8 planes + the margin's terms; zeroes the call's counter words ------------------------------
 // par[0] = qstep, par[1] = alpha, par[2] = beta, par[3] = 1 when the query's norm is not finite (the call falls back)
+// counter[0]: the candidate counter; counter[1]: the two 32-bit arrival tickets of code8_seed_kernel and code8_rescore_kernel
+// (kCode8SeedTicket, kCode8RescoreTicket) — zeroed here on EVERY call, whatever an earlier call left in them
 __global__ __launch_bounds__(256) void code8_query_kernel(const float* __restrict__ q, int d, int normalize_q, float row_norm_bound,
                                                           int8_t* __restrict__ qhi, int8_t* __restrict__ qlo, float* __restrict__ par,
                                                           unsigned long long* __restrict__ counter) {
@@ -197,7 +189,8 @@ __global__ __launch_bounds__(256) void code8_query_kernel(const float* __restric
         par[1] = m.alpha;
         par[2] = m.beta;
         par[3] = nonfinite ? 1.f : 0.f;
-        *counter = 0ull;
+        counter[0] = 0ull;
+        counter[1] = 0ull;
     }
 }
 
@@ -210,7 +203,7 @@ struct Code8ScanArgs {
     const int8_t* qhi;     // [d] the query's high / low planes (code8_query_kernel)
     const int8_t* qlo;
     const float* par;      // qstep, alpha, beta
-    const float* floor;    // a proven lower bound of the final k-th best score (the seed sample's exact k-th best)
+    const float* floor;    // a proven lower bound of the final k-th best score (code8_seed_kernel: the sample's k-th best lower bound)
     uint32_t* cand;        // [cap] appended rows, in no order
     int64_t cap;
     unsigned long long* counter;  // zeroed by the prologue; keeps counting past cap
@@ -383,57 +376,377 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     if (nst) flush();
 }
 
-// ---- candidates -> the ascending row list of the exact re-score -------------------------------------------------------------------
-// Thread i ranks candidate i among the count candidates (rows are distinct: the rank is its place in ascending order) and
-// writes it there; places from the count on get `pad`, the row of NaN in the matrix' slack that no scan ever offers.  The call falls back to the full
-// exact scan (*gate = 1; the list is all padding) when the candidates overflowed the capacity, are fewer than k, or the query's
-// norm is not finite.  stats (host-mapped): [0] fallbacks so far, [1] candidates of the latest call, [2] calls so far.
-__global__ __launch_bounds__(256) void code8_list_kernel(const uint32_t* __restrict__ cand, const unsigned long long* __restrict__ counter,
-                                                         int64_t cap, int k, const float* __restrict__ par, int64_t pad,
-                                                         int64_t* __restrict__ rows, int* __restrict__ gate, unsigned int* __restrict__ ctr_dev,
-                                                         volatile unsigned int* stats) {
-    __shared__ uint32_t sh[256];
-    const unsigned long long count = *counter;
-    const bool fallback = count > (unsigned long long)cap || count < (unsigned long long)k || par[3] != 0.f;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *gate = fallback ? 1 : 0;
-        // (searches of one index on several streams run this concurrently: atomic)
-        const unsigned int fb = atomicAdd(&ctr_dev[0], fallback ? 1u : 0u) + (fallback ? 1u : 0u);
-        const unsigned int calls = atomicAdd(&ctr_dev[1], 1u) + 1u;
-        if (stats) {
-            stats[0] = fb;
-            stats[1] = (unsigned int)(count > 0xFFFFFFFFull ? 0xFFFFFFFFull : count);
-            stats[2] = calls;
-        }
-    }
-    const int64_t cnt = fallback ? 0 : (int64_t)count;
-    if ((int64_t)blockIdx.x * 256 >= cnt) {
-        if (i < cap) rows[i] = pad;
-        return;
-    }
-    const uint32_t mine = i < cnt ? cand[i] : 0xFFFFFFFFu;
-    int rank = 0;
-    for (int64_t base = 0; base < cnt; base += 256) {
-        const int64_t j = base + threadIdx.x;
-        sh[threadIdx.x] = j < cnt ? cand[j] : 0xFFFFFFFFu;
-        __syncthreads();
-#pragma unroll 8
-        for (int e = 0; e < 256; ++e) rank += sh[e] < mine ? 1 : 0;
-        __syncthreads();
-    }
-    if (i < cnt)
-        rows[rank] = (int64_t)mine;
-    else if (i < cap)
-        rows[i] = pad;
+// ---- hand-off of block lists to the last block to arrive ------------------------------------------------------------------------
+// Both kernels below end the same way: every block leaves its sorted k-list in global memory, takes a ticket, and the block
+// that draws the last ticket merges all lists.  Nothing waits for anything: a block that is not last returns.
+//   producer: the list is stored with agent-scope atomic 8-byte stores (write-through), the storing wave drains them
+//             (s_waitcnt vmcnt(0)), __syncthreads(), then ONE lane: agent-scope release fence, drain, relaxed ticket fetch_add
+//             (the fences order it: an acq_rel add would write back and invalidate a second time in every block);
+//   consumer: the lane that drew the last ticket does ONE agent-scope acquire fence and drains it, __syncthreads(), then every
+//             wave reads the lists with agent-scope atomic loads (vector loads that bypass this CU's L1; never the scalar path).
+// The ticket word is zeroed by code8_query_kernel on every call; the last arriver also leaves it at zero.
+__device__ __forceinline__ void code8_store_list(uint64_t* lists, int64_t at, uint64_t key) {
+    __hip_atomic_store(lists + at, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint64_t code8_load_list(uint64_t* lists, int64_t at) {
+    return __hip_atomic_load(lists + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// positions of the row list -> row numbers (the re-score's keys carry positions)
-__global__ void code8_relabel_kernel(int64_t* __restrict__ I, int k, const int64_t* __restrict__ rows, int64_t label_offset) {
-    const int i = threadIdx.x;
-    if (i < k) {
-        const int64_t p = I[i];
-        I[i] = p >= 0 ? rows[p] + label_offset : -1;
+// Called by every thread of the block after wave 0 stored the block's list.  `expected`: the blocks that take a ticket.
+// sh: the block's LDS array (block_merge_topk's; at least one word), free for reuse when this returns.
+// sh must not be live across this call: sh[0] carries the "I am last" word (block_merge_topk's reads of sh end before the
+// first barrier here, and its next writes come after the last one).
+__device__ __forceinline__ bool code8_last_arriver(unsigned int* ticket, unsigned int expected, uint64_t* sh) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (every wave: only wave 0 has list stores in flight)
+    __syncthreads();                                    // the list is drained; wave 0 has finished reading sh
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int seen = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = seen == expected - 1u;
+        if (last) {
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        sh[0] = last ? 1ull : 0ull;
+    }
+    __syncthreads();
+    const bool last = sh[0] != 0ull;
+    __syncthreads();   // every wave has read the word before the merge below writes sh again
+    return last;
+}
+
+// The waves of the block share the nlists k-lists out (merge_keys_kernel's walk: UNROLL x 64 keys per wave and step, loaded
+// before any is offered), merge into wave 0's list.  Few lists: short steps, so that every wave has a share.
+template <int UNROLL>
+__device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, uint64_t* lists, int64_t total, int nwaves) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    for (int64_t base = (int64_t)wave * kWave * UNROLL; base < total; base += (int64_t)nwaves * kWave * UNROLL) {
+        uint64_t c[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const int64_t i = base + j * kWave + lane;
+            c[j] = i < total ? code8_load_list(lists, i) : 0ull;
+        }
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) tk.offer(c[j]);
+    }
+}
+__device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists, int nlists, int k, uint64_t* sh, int nwaves) {
+    const int64_t total = (int64_t)nlists * k;
+    tk.init(k);
+    if (total <= (int64_t)nwaves * kWave * 4)
+        code8_offer_lists<2>(tk, lists, total, nwaves);
+    else
+        code8_offer_lists<kMergeUnroll>(tk, lists, total, nwaves);
+    block_merge_topk(tk, sh, nwaves);
+}
+
+// ---- the floor: lower bounds of a sample of rows, from the codes -----------------------------------------------------------------
+// The sample: rows (i * n) / kCode8Seed, i in [0, kCode8Seed) (n >= kCode8Seed: distinct, ascending).  For each, the coded score
+// s~ and the margin m exactly as code8_scan_kernel's epilogue forms them, then lb = s~ - m in fp32: the exact kernel's score
+// of the row is >= lb (the lower half of the route's bound).  floor = the k-th best lb: k distinct rows score at least that, so
+// the final k-th best score does — the unchanged prefilter predicate !(ub < floor) keeps every row of the final top-k
+// (DESIGN.md section 4.1b).  Fewer than k lower bounds (or a k-th of -inf): floor = -FLT_MAX, everything passes, the call
+// falls back.  A NaN lb (0 * inf) fails the gate and never enters a list.
+// Roofline: latency of the gather; bytes = kCode8Seed * (d + 8).
+constexpr int64_t kCode8Seed = 131072;
+constexpr int kCode8SeedMaxThreads = 1024;
+constexpr int kCode8SeedThreads = 512;   // one block of this many per CU: measured
+
+struct Code8SeedArgs {
+    const int8_t* codes;
+    const float2* ar;
+    int64_t n;
+    int d;
+    const int8_t* qhi;
+    const int8_t* qlo;
+    const float* par;
+    int k;
+    uint64_t* lists;        // [gridDim.x, k]
+    unsigned int* ticket;   // zeroed by code8_query_kernel
+    float* floor;
+};
+
+template <int G, int U, bool MASKED>
+__global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8SeedArgs a) {
+    constexpr int RPI = kWave / G;
+    constexpr int RB = RPI * U;
+    static_assert(U >= 2 && U <= 8 && (U & (U - 1)) == 0 && U <= G, "code8_reduce halves U down to one value inside a row group");
+    static_assert(kCode8Seed % RB == 0, "the sample is whole batches");
+    __shared__ uint64_t sh[(kCode8SeedMaxThreads / kWave - 1) * kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwaves = blockDim.x >> 6;
+    const int t = lane % G;
+    const int g = lane / G;
+    const bool valid = !MASKED || t * 16 < a.d;
+
+    i32x4 qh = {0, 0, 0, 0}, ql = {0, 0, 0, 0};
+    if (valid) {
+        qh = *reinterpret_cast<const i32x4*>(a.qhi + t * 16);
+        ql = *reinterpret_cast<const i32x4*>(a.qlo + t * 16);
+    }
+    const float qstep = a.par[0], alpha = a.par[1], beta = a.par[2];
+
+    int ue = 0;
+#pragma unroll
+    for (int m = 1, h = U / 2; m < U; m <<= 1, h >>= 1) ue += (t & m) ? h : 0;
+    const int erow = ue * RPI + g;
+    const bool reports = t < U;
+
+    WaveTopK tk;
+    tk.init(a.k);
+
+    const int64_t n = a.n;
+    auto sample_row = [&](int64_t i) { return (i * n) / kCode8Seed; };
+    auto load = [&](i32x4 (&x)[U], float2& sr, int64_t& er, int64_t b) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = sample_row(b * RB + (int64_t)u * RPI + g);
+            const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + r * (int64_t)a.d + t * 16);
+            if (MASKED)
+                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
+            else
+                x[u] = __builtin_nontemporal_load(src);
+        }
+        er = sample_row(b * RB + erow);
+        sr = a.ar[er];
+    };
+    auto consume = [&](const i32x4 (&x)[U], float2 sr, int64_t er) {
+        int T[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int hi = 0, lo = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                hi = __builtin_amdgcn_sdot4(x[u][j], qh[j], hi, false);
+                lo = __builtin_amdgcn_sdot4(x[u][j], ql[j], lo, false);
+            }
+            T[u] = hi * 256 + lo;
+        }
+        const int tot = code8_reduce<G, U>(T, t);
+        const float s = ((float)tot * qstep) * sr.x;
+        float m = fmaf(alpha, sr.y, beta);
+        m = fmaf(fabsf(s) + m, 2.4e-7f, m);
+        const float lb = s - m;
+        const bool pass = reports && lb >= tk.thr_score;   // NaN fails
+        if (__ballot(pass)) tk.offer(pass ? make_key(lb, (uint32_t)er) : 0ull);
+    };
+
+    // the next batch's loads are issued before this batch is consumed: a gathered row is a fresh DRAM page
+    const int64_t nb = kCode8Seed / RB;
+    const int64_t stride = (int64_t)gridDim.x * nwaves;
+    int64_t b = (int64_t)blockIdx.x * nwaves + wave;
+    if (b < nb) {
+        i32x4 x[U];
+        float2 sr;
+        int64_t er;
+        load(x, sr, er, b);
+        for (; b < nb; b += stride) {
+            i32x4 xn[U];
+            float2 srn = sr;
+            int64_t ern = er;
+            const int64_t bn = b + stride;
+            if (bn < nb) load(xn, srn, ern, bn);
+            consume(x, sr, er);
+            if (bn < nb) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) x[u] = xn[u];
+            }
+            sr = srn;
+            er = ern;
+        }
+    }
+
+    block_merge_topk(tk, sh, nwaves);
+    if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
+    if (!code8_last_arriver(a.ticket, gridDim.x, sh)) return;
+    code8_merge_lists(tk, a.lists, (int)gridDim.x, a.k, sh, nwaves);
+    if (wave == 0) {
+        const uint64_t kth = readlane_u64(tk.key, a.k - 1);
+        if (lane == 0) *a.floor = kth ? fmaxf(key_score(kth), -3.402823466e+38f) : -3.402823466e+38f;
+    }
+}
+
+// ---- the exact re-score of the candidates, in one launch -------------------------------------------------------------------------
+// Decides the fallback as the route always has (the candidates overflowed the capacity, are fewer than k, or the query's norm
+// is not finite: *gate = 1 and nothing is written to D or I — the gated exact scan behind this launch answers the call), else
+// scores the candidates straight from cand[], in the order the prefilter appended them, and keeps make_key(score, ROW): the
+// key order (score descending, row ascending) is the exact scan's tie rule, so no sorted list, no padding and no relabelling
+// are needed.  stats (host-mapped): [0] fallbacks so far, [1] candidates of the latest call, [2] calls so far.
+// The arithmetic restates flat_scan_kernel<G, C, ...>'s for the shape choose_shape picks (the same prologue, the same fmaf
+// chain over chunks c then .x .y .z .w, the same xor butterfly): the scores are the exact scan's bit for bit.
+// The grid is fixed at launch; the blocks that work are the first `active`, derived from the count (kCode8RescoreRows per
+// block, clamped to the grid); the others return without a ticket.  The last active block to arrive merges and writes (D, I).
+constexpr int kCode8RescoreRows = 32;   // measured
+
+struct Code8RescoreArgs {
+    const float* X;
+    int64_t ld;
+    int d4;
+    const float* q;
+    int normalize_q;
+    int k;
+    const uint32_t* cand;
+    const unsigned long long* counter;
+    int64_t cap;
+    const float* par;
+    int rows_per_block;
+    uint64_t* lists;        // [gridDim.x, k]
+    unsigned int* ticket;   // zeroed by code8_query_kernel
+    int* gate;
+    unsigned int* ctr_dev;  // [0] fallbacks, [1] calls
+    volatile unsigned int* stats;
+    int64_t label_offset;
+    float* D;
+    int64_t* I;
+};
+
+template <int G, int C, int U, bool MASKED>
+__global__ __launch_bounds__(kScanThreads) void code8_rescore_kernel(Code8RescoreArgs a) {
+    constexpr int RPI = kWave / G;
+    constexpr int RB = RPI * U;
+    __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
+    const unsigned long long count = *a.counter;
+    const bool fallback = count > (unsigned long long)a.cap || count < (unsigned long long)a.k || a.par[3] != 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *a.gate = fallback ? 1 : 0;
+        // (searches of one index on several streams run this concurrently: atomic)
+        const unsigned int fb = atomicAdd(&a.ctr_dev[0], fallback ? 1u : 0u) + (fallback ? 1u : 0u);
+        const unsigned int calls = atomicAdd(&a.ctr_dev[1], 1u) + 1u;
+        if (a.stats) {
+            a.stats[0] = fb;
+            a.stats[1] = (unsigned int)(count > 0xFFFFFFFFull ? 0xFFFFFFFFull : count);
+            a.stats[2] = calls;
+        }
+    }
+    if (fallback) return;
+    const int64_t cnt = (int64_t)count;   // k <= cnt <= cap
+    int64_t want = (cnt + a.rows_per_block - 1) / a.rows_per_block;
+    const int active = (int)(want < (int64_t)gridDim.x ? want : (int64_t)gridDim.x);   // >= 1
+    if ((int)blockIdx.x >= active) return;
+
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int t = lane % G;
+    const int g = lane / G;
+
+    // ---- query -> registers (flat_scan_kernel's prologue) -------------------------------------------
+    f32x4 qv[C];
+    bool cvalid[C];
+    const float* qptr = a.q;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int chunk = c * G + t;
+        cvalid[c] = !MASKED || chunk < a.d4;
+        qv[c] = cvalid[c] ? *reinterpret_cast<const f32x4*>(qptr + chunk * 4) : f32x4{0, 0, 0, 0};
+    }
+    if (a.normalize_q) {
+        float nr = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            nr += qv[c].x * qv[c].x + qv[c].y * qv[c].y + qv[c].z * qv[c].z + qv[c].w * qv[c].w;
+        nr = group_reduce_add<G>(nr);
+        if (nr > 0.f) {
+            const float inorm = 1.0f / sqrtf(nr);
+#pragma unroll
+            for (int c = 0; c < C; ++c) qv[c] *= inorm;
+        }
+    }
+
+    WaveTopK tk;
+    tk.init(a.k);
+
+    const int64_t nwaves_total = (int64_t)active * kScanWaves;
+    const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
+    const int64_t nbatches = (cnt + RB - 1) / RB;
+    const int64_t last = cnt - 1;
+
+    auto batch_rows = [&](int64_t b, uint32_t (&pr)[U]) {
+        const int64_t i0 = b * RB + g;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int64_t i = i0 + (int64_t)u * RPI;
+            i = i < last ? i : last;  // clamp: tail lanes re-read the last candidate, result discarded
+            pr[u] = a.cand[i];
+        }
+    };
+    auto load_batch = [&](const uint32_t (&pr)[U], f32x4 (&x)[U][C]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float* p = a.X + (int64_t)pr[u] * a.ld + t * 4;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const f32x4* src = reinterpret_cast<const f32x4*>(p + c * G * 4);
+                if (MASKED)
+                    x[u][c] = cvalid[c] ? __builtin_nontemporal_load(src) : f32x4{0, 0, 0, 0};
+                else
+                    x[u][c] = __builtin_nontemporal_load(src);
+            }
+        }
+    };
+    auto consume_batch = [&](int64_t b, f32x4 (&x)[U][C], const uint32_t (&pr)[U]) {
+        const int64_t i0 = b * RB + g;
+        float s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float acc = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                acc = fmaf(x[u][c].x, qv[c].x, acc);
+                acc = fmaf(x[u][c].y, qv[c].y, acc);
+                acc = fmaf(x[u][c].z, qv[c].z, acc);
+                acc = fmaf(x[u][c].w, qv[c].w, acc);
+            }
+            s[u] = acc;
+        }
+#pragma unroll
+        for (int m = G / 2; m >= 1; m >>= 1) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] += __shfl_xor(s[u], m);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + (int64_t)u * RPI;
+            // gate on the score alone (NaN fails); exact 64-bit order decided inside offer()
+            const bool pass = (t == 0) && (i < cnt) && (s[u] >= tk.thr_score);
+            if (__ballot(pass)) tk.offer(pass ? make_key(s[u], pr[u]) : 0ull);
+        }
+    };
+
+    // the candidate ids of the NEXT batch are fetched behind this batch's row loads (flat_scan_kernel's SUBSET loop)
+    uint32_t pr[U], pn[U];
+    if (gw < nbatches) batch_rows(gw, pr);
+    for (int64_t b = gw; b < nbatches; b += nwaves_total) {
+        f32x4 x[U][C];
+        load_batch(pr, x);
+        const int64_t bn = b + nwaves_total;
+        batch_rows(bn < nbatches ? bn : b, pn);
+        consume_batch(b, x, pr);
+#pragma unroll
+        for (int u = 0; u < U; ++u) pr[u] = pn[u];
+    }
+
+    block_merge_topk(tk, sh, kScanWaves);
+    if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
+    if (!code8_last_arriver(a.ticket, (unsigned int)active, sh)) return;
+    code8_merge_lists(tk, a.lists, active, a.k, sh, kScanWaves);
+    if (wave == 0 && lane < a.k) {
+        const uint64_t key = tk.key;
+        float d;
+        int64_t id;
+        if (key) {
+            d = key_score(key);
+            id = a.label_offset + (int64_t)key_row(key);
+        } else {  // faiss convention for missing results (merge_keys_kernel's)
+            d = -3.402823466e+38f;
+            id = -1;
+        }
+        a.D[lane] = d;
+        a.I[lane] = id;
     }
 }
 

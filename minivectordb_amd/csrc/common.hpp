@@ -92,6 +92,9 @@ struct Knobs {
     int grouped_min_batches = 4;       // MVDB_GROUPED_MIN_BATCHES: fewest row batches per wave of a work item
     long long compact_bytes = 512ll << 20;  // MVDB_COMPACT_BYTES: staging buffer of a row compaction (mvdb_index_remove_rows)
     bool compact_inplace = true;            // MVDB_COMPACT_INPLACE (0: a few deleted rows take the staging path too)
+    int code8_seed_blocks = 0;         // MVDB_CODE8_SEED_BLOCKS: tuning hook, grid of code8_seed_kernel (0: one block per CU)
+    int code8_seed_threads = 0;        // MVDB_CODE8_SEED_THREADS: tuning hook, 256 | 512 | 1024 threads per block of it (0: 512)
+    int code8_rescore_rows = 0;        // MVDB_CODE8_RESCORE_ROWS: tuning hook, candidates per active block of code8_rescore_kernel (0: 32)
 };
 Knobs read_knobs();
 

@@ -71,6 +71,9 @@ Knobs read_knobs() {
     if (const char* v = getenv("MVDB_COMPACT_BYTES"))
         if (*v) k.compact_bytes = std::max(1ll, atoll(v));
     k.compact_inplace = env_int("MVDB_COMPACT_INPLACE", 1) != 0;
+    k.code8_seed_blocks = env_int("MVDB_CODE8_SEED_BLOCKS", 0);
+    k.code8_seed_threads = env_int("MVDB_CODE8_SEED_THREADS", 0);
+    k.code8_rescore_rows = env_int("MVDB_CODE8_RESCORE_ROWS", 0);
     return k;
 }
 
@@ -236,7 +239,7 @@ struct Workspace {
     DevBuf<unsigned long long> rccount;  // ... and their per-query counters
     DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
     DevBuf<char> gtab;
-    DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter, gate, seed results, candidates, row list
+    DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and tickets, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
         PinnedBuf buf;
         hipEvent_t ev = nullptr;
@@ -325,7 +328,6 @@ struct mvdb_index {
     // by add, emptied by whatever renumbers rows, freed with the matrix; built / read under shadow_mu by searches.
     mutable int8_t* C8 = nullptr;
     mutable float2* c8_ar = nullptr;
-    mutable int64_t* c8_seed = nullptr;        // the seed sample's rows (kCode8Seed, spread over [0, c8_rows))
     mutable std::atomic<bool> c8_wanted{false};   // an eligible single query has asked for the code since the index was created / reset
     mutable int64_t c8_cap = 0, c8_rows = 0;
     mutable std::atomic<bool> c8_failed{false};
@@ -405,10 +407,6 @@ struct KnobScope {
 };
 inline const Knobs& kn() { return *tls_kn; }
 
-// the profiling label of the scans a pass launches on its own behalf (the prefilter route's seed and re-score: "ip_scan" is
-// the label of the launch that reads the corpus)
-thread_local const char* tls_scan_label = nullptr;
-
 // ---- shape selection: G lanes per row, C chunks per lane, U rows in flight ----------------------
 struct Shape {
     int G, C;
@@ -459,7 +457,7 @@ int launch_scan_kern(const ScanArgs& a, int nq, int device, hipStream_t stream, 
     int64_t cap = (int64_t)device_cus(device) * occ;
     int nblocks = (int)std::max<int64_t>(1, std::min(want, cap));
     if (nblocks_out) *nblocks_out = nblocks;
-    const char* pname = tls_scan_label ? tls_scan_label : MODE == kModeTopK ? "ip_scan" : "ip_scan_scores";
+    const char* pname = MODE == kModeTopK ? "ip_scan" : "ip_scan_scores";
     prof_symbol(pname, "flat_scan_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", G, C, U, METRIC, MODE, NT ? "true" : "false", SEL,
                 MASKED ? "true" : "false", gated ? "true" : "false");
     int slot = prof_begin(pname, stream);
@@ -1859,9 +1857,11 @@ const float* ensure_offsets(const mvdb_index* idx, hipStream_t s) {
 }
 
 // ---- the int8 code of the rows and the single-query prefilter route (code8_scan.hpp) -------------------
-constexpr int64_t kCode8Seed = 131072;     // rows of the seed sample (exact scores: their k-th best is the prefilter's floor)
-constexpr int64_t kCode8MinRows = 500000;
-constexpr int64_t kCode8MaxCapacity = 65536;   // code8_list_kernel ranks by counting: quadratic in the candidates
+constexpr int64_t kCode8MinRows = 500000;      // (>= kCode8Seed, code8_scan.hpp: the rows of the floor's sample are distinct)
+static_assert(kCode8MinRows >= kCode8Seed, "the seed sample takes distinct rows");
+// the most candidates a call may hand to the re-score: code8_rescore_kernel's grid is sized for it (kCode8RescoreRows per
+// block), and a query that keeps more than this of the index is better served by the exact scan anyway
+constexpr int64_t kCode8MaxCapacity = 65536;
 // A dropped code is rebuilt once the exact scan has answered this many single queries since the drop: the build moves about
 // 1.25 scans' worth of bytes (the matrix read once, a quarter of it written), a served query saves about 0.75 — two queries
 // pay for it, so a workload that alternates one delete and one query never builds.
@@ -1877,10 +1877,8 @@ bool stream_capturing(hipStream_t s) {
 void drop_code8(const mvdb_index* idx, bool count_rebuild = true) {
     if (idx->C8) (void)hipFree(idx->C8);
     if (idx->c8_ar) (void)hipFree(idx->c8_ar);
-    if (idx->c8_seed) (void)hipFree(idx->c8_seed);
     idx->C8 = nullptr;
     idx->c8_ar = nullptr;
-    idx->c8_seed = nullptr;
     idx->c8_cap = idx->c8_rows = 0;
     if (count_rebuild && idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
 }
@@ -1892,13 +1890,12 @@ void invalidate_code8(const mvdb_index* idx) {
 
 bool code8_dim(int d) { return d == 384 || d == 512 || d == 1024; }
 
-int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, int64_t n_after, hipStream_t s) {
+int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t s) {
     if (rows > 0) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
         hipLaunchKernelGGL(code8_build_kernel, dim3(grid), dim3(256), 0, s, (const float*)(idx->X + row0 * idx->ld), idx->ld, idx->d, rows,
                            idx->C8 + row0 * idx->d, idx->c8_ar + row0, (const int64_t*)nullptr, (int64_t)0);
     }
-    hipLaunchKernelGGL(code8_seed_rows_kernel, dim3((unsigned)((kCode8Seed + 255) / 256)), dim3(256), 0, s, idx->c8_seed, kCode8Seed, n_after);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
@@ -1916,13 +1913,8 @@ bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
     if (idx->C8 && idx->c8_cap < idx->n) drop_code8(idx, false);
     if (!idx->C8) {
         const int64_t cap = std::max<int64_t>(idx->cap, idx->n);
-        // the padding row of the candidate list: the LAST row of the slack behind the matrix (kRowSlack rows that are read
-        // by the tiled kernels and never nominated), filled with NaN — no scan ever offers it; the matrix' rows are untouched
-        const size_t nan_floats = (size_t)idx->ld;
-        float* nan_row = idx->X + (idx->cap + kRowSlack - 1) * idx->ld;
         bool ok = hipMalloc((void**)&idx->C8, (size_t)cap * idx->d) == hipSuccess &&
-                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess &&
-                  hipMalloc((void**)&idx->c8_seed, (size_t)kCode8Seed * sizeof(int64_t)) == hipSuccess;
+                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess;
         if (ok && !idx->c8_ctr_dev) {
             ok = hipMalloc((void**)&idx->c8_ctr_dev, 2 * sizeof(unsigned int)) == hipSuccess &&
                  hipMemset(idx->c8_ctr_dev, 0, 2 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
@@ -1936,9 +1928,8 @@ bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
         }
         idx->c8_cap = cap;
         idx->c8_rows = 0;
-        hipLaunchKernelGGL(code8_fill_nan_kernel, dim3((unsigned)((nan_floats + 255) / 256)), dim3(256), 0, s, nan_row, (int64_t)nan_floats);
     }
-    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, idx->n, s) != 0 || hipStreamSynchronize(s) != hipSuccess) {
+    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, s) != 0 || hipStreamSynchronize(s) != hipSuccess) {
         drop_code8(idx, false);
         idx->c8_failed = true;
         return false;
@@ -2010,11 +2001,38 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
     return 0;
 }
 
-struct ScanLabelScope {
-    const char* prev;
-    explicit ScanLabelScope(const char* l) : prev(tls_scan_label) { tls_scan_label = l; }
-    ~ScanLabelScope() { tls_scan_label = prev; }
-};
+// The floor's launch.  The gather is bound by latency, the last block's merge by inserts: wide blocks keep the lists few.
+// (grid shapes measured: DESIGN.md section 4.1b)
+template <int G, int U, bool MASKED>
+int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream) {
+    void (*kern)(Code8SeedArgs) = code8_seed_kernel<G, U, MASKED>;
+    int threads = kn().code8_seed_threads;   // (tuning hooks, as scan_blocks_per_cu: 0 = the measured defaults)
+    if (threads != 256 && threads != 512 && threads != 1024) threads = kCode8SeedThreads;
+    constexpr int64_t nbatches = kCode8Seed / ((kWave / G) * U);
+    const int64_t want = (nbatches + threads / kWave - 1) / (threads / kWave);
+    int64_t blocks = kn().code8_seed_blocks > 0 ? kn().code8_seed_blocks : device_cus(device);
+    blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, want), scan_grid_upper_bound(device)));
+    prof_symbol("ip_scan_code8_seed", "code8_seed_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
+    int slot = prof_begin("ip_scan_code8_seed", stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// The re-score's launch: a grid for the whole capacity, of which the kernel uses what the count asks for.
+template <int G, int C, int U, bool MASKED>
+int launch_code8_rescore(const Code8RescoreArgs& a, int device, hipStream_t stream) {
+    void (*kern)(Code8RescoreArgs) = code8_rescore_kernel<G, C, U, MASKED>;
+    const int64_t want = (a.cap + a.rows_per_block - 1) / a.rows_per_block;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * 4));
+    prof_symbol("ip_scan_code8_rescore", "code8_rescore_kernel<%d, %d, %d, %s>", G, C, U, MASKED ? "true" : "false");
+    int slot = prof_begin("ip_scan_code8_rescore", stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kScanThreads), 0, stream, a);
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
 
 int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
                  bool* served) {
@@ -2022,16 +2040,16 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     hipStream_t s = ws->stream;
     const int d = idx->d;
     const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(idx->kn.code8_capacity, kCode8MaxCapacity));
-    // workspace layout (bytes): planes [2 d] | terms [16 floats] | counter | gate | seed D [64] | seed I [64] | candidates | list
+    // workspace layout (bytes): planes [2 d] | terms [16 floats] | counter, tickets [2 x 8] | gate | floor | candidates
+    // (the block lists of the seed and re-score launches, and of the gated fallback scan, go through ws->cand in turn)
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t at = off;
         off += (bytes + 255) / 256 * 256;
         return at;
     };
-    const size_t o_planes = take((size_t)2 * d), o_par = take(16 * sizeof(float)), o_ctr = take(sizeof(unsigned long long)),
-                 o_gate = take(sizeof(int)), o_sd = take(kMaxFusedK * sizeof(float)), o_si = take(kMaxFusedK * sizeof(int64_t)),
-                 o_cand = take((size_t)cap * sizeof(uint32_t)), o_list = take((size_t)cap * sizeof(int64_t));
+    const size_t o_planes = take((size_t)2 * d), o_par = take(16 * sizeof(float)), o_ctr = take(2 * sizeof(unsigned long long)),
+                 o_gate = take(sizeof(int)), o_floor = take(sizeof(float)), o_cand = take((size_t)cap * sizeof(uint32_t));
     const size_t cand_keys = (size_t)scan_grid_upper_bound(idx->device) * k;
     const bool capturing = stream_capturing(s);
     if (capturing && (ws->c8.cap < off || ws->cand.cap < cand_keys)) return 0;  // nothing is allocated inside a capture
@@ -2044,27 +2062,32 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     int8_t* qlo = qhi + d;
     float* par = reinterpret_cast<float*>(base + o_par);
     unsigned long long* counter = reinterpret_cast<unsigned long long*>(base + o_ctr);
+    unsigned int* tickets = reinterpret_cast<unsigned int*>(counter + 1);   // [0] the seed launch's, [1] the re-score's
     int* gate = reinterpret_cast<int*>(base + o_gate);
-    float* seedD = reinterpret_cast<float*>(base + o_sd);
-    int64_t* seedI = reinterpret_cast<int64_t*>(base + o_si);
+    float* floor = reinterpret_cast<float*>(base + o_floor);
     uint32_t* cand = reinterpret_cast<uint32_t*>(base + o_cand);
-    int64_t* list = reinterpret_cast<int64_t*>(base + o_list);
 
+    // 1. the query's planes and margin terms; zeroes the candidate counter and both tickets
     hipLaunchKernelGGL(code8_query_kernel, dim3(1), dim3(256), 0, s, a0.q, d, a0.normalize_q, idx->row_norm_bound, qhi, qlo, par, counter);
     MVDB_HIP(hipGetLastError());
 
-    // 1. the floor: exact scores of the seed sample (the row-list form of the exact kernel), their k-th best
-    ScanArgs a = a0;
-    a.cand = ws->cand.p;
-    int nblocks = 0;
-    {
-        ScanLabelScope label("ip_scan_code8_seed");
-        a.rows = idx->c8_seed;
-        a.n = kCode8Seed;
-        MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
-        MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, 0, seedD, seedI));
-    }
-    // 2. the prefilter over the codes
+    // 2. the floor: the k-th best LOWER bound of the seed sample, from the codes
+    Code8SeedArgs sd;
+    sd.codes = idx->C8;
+    sd.ar = idx->c8_ar;
+    sd.n = idx->n;
+    sd.d = d;
+    sd.qhi = qhi;
+    sd.qlo = qlo;
+    sd.par = par;
+    sd.k = k;
+    sd.lists = ws->cand.p;
+    sd.ticket = tickets;
+    sd.floor = floor;
+    if (d == 512) MVDB_TRY((launch_code8_seed<32, 4, false>(sd, idx->device, s)));
+    else if (d == 1024) MVDB_TRY((launch_code8_seed<64, 4, false>(sd, idx->device, s)));
+    else MVDB_TRY((launch_code8_seed<32, 8, true>(sd, idx->device, s)));
+    // 3. the prefilter over the codes
     Code8ScanArgs c;
     c.codes = idx->C8;
     c.ar = idx->c8_ar;
@@ -2073,7 +2096,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.qhi = qhi;
     c.qlo = qlo;
     c.par = par;
-    c.floor = seedD + (k - 1);
+    c.floor = floor;
     c.cand = cand;
     c.cap = cap;
     c.counter = counter;
@@ -2081,22 +2104,35 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     if (d == 512) MVDB_TRY((launch_code8_scan<32, 4, false>(c, idx->device, s)));
     else if (d == 1024) MVDB_TRY((launch_code8_scan<64, 4, false>(c, idx->device, s)));
     else MVDB_TRY((launch_code8_scan<32, 8, true>(c, idx->device, s)));
-    // 3. candidates -> ascending row list, padded with the row of NaN in the matrix' slack
-    const int64_t pad = idx->cap + kRowSlack - 1;  // the NaN row in the matrix' slack (ensure_code8)
-    hipLaunchKernelGGL(code8_list_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, (const uint32_t*)cand,
-                       (const unsigned long long*)counter, cap, k, (const float*)par, pad, list, gate, idx->c8_ctr_dev,
-                       (volatile unsigned int*)idx->c8_stats.p);
-    MVDB_HIP(hipGetLastError());
-    // 4. the exact scores of the candidates: flat_scan_kernel's row-list form, ties by position = by row
-    {
-        ScanLabelScope label("ip_scan_code8_rescore");
-        a.rows = list;
-        a.n = cap;
-        MVDB_TRY(launch_scan(idx->metric, kModeTopK, a, 1, idx->device, s, &nblocks));
-        MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, 0, D_dev, I_dev));
-        hipLaunchKernelGGL(code8_relabel_kernel, dim3(1), dim3(64), 0, s, I_dev, k, (const int64_t*)list, label_offset);
-    }
+    // 4. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
+    Code8RescoreArgs r;
+    r.X = a0.X;
+    r.ld = a0.ld;
+    r.d4 = a0.d4;
+    r.q = a0.q;
+    r.normalize_q = a0.normalize_q;
+    r.k = k;
+    r.cand = cand;
+    r.counter = counter;
+    r.cap = cap;
+    r.par = par;
+    r.rows_per_block = kn().code8_rescore_rows > 0 ? kn().code8_rescore_rows : kCode8RescoreRows;   // (tuning hook)
+    r.lists = ws->cand.p;
+    r.ticket = tickets + 1;
+    r.gate = gate;
+    r.ctr_dev = idx->c8_ctr_dev;
+    r.stats = (volatile unsigned int*)idx->c8_stats.p;
+    r.label_offset = label_offset;
+    r.D = D_dev;
+    r.I = I_dev;
+    // (the exact scan's shape per width, choose_shape: the arithmetic is restated for exactly these)
+    if (d == 512) MVDB_TRY((launch_code8_rescore<64, 2, 4, false>(r, idx->device, s)));
+    else if (d == 1024) MVDB_TRY((launch_code8_rescore<64, 4, 2, false>(r, idx->device, s)));
+    else MVDB_TRY((launch_code8_rescore<32, 3, 4, false>(r, idx->device, s)));
     // 5. fallback, enabled on the device: the full exact scan overwrites the result
+    ScanArgs a = a0;
+    a.cand = ws->cand.p;
+    int nblocks = 0;
     a.rows = nullptr;
     a.n = idx->n;
     a.gate = gate;
@@ -2424,7 +2460,7 @@ static int extend_code8(mvdb_index* idx, int64_t n_new) {
         return 0;
     }
     if (idx->c8_rows != idx->n) return 0;  // emptied by a delete: the next eligible query codes every row again
-    MVDB_TRY(code8_convert(idx, idx->n, n_new, idx->n + n_new, idx->mut));
+    MVDB_TRY(code8_convert(idx, idx->n, n_new, idx->mut));
     MVDB_HIP(hipStreamSynchronize(idx->mut));
     idx->c8_rows = idx->n + n_new;
     return 0;
