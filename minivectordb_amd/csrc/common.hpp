@@ -8,6 +8,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mvdb.h"
@@ -56,6 +57,19 @@ void prof_end(int slot, hipStream_t stream);
 // while profiling is on: remember which kernel instantiation a label's launches run (mvdb_prof_symbol; bench.py checks
 // the committed PMC profile against it)
 void prof_symbol(const char* label, const char* fmt, ...);
+// One launch inside its profiling bracket: the symbol of `label` (symbol...: the format and the arguments of prof_symbol; none:
+// the label records no symbol), the event pair around launch() on `stream`, and the launch's error.  launch() enqueues the
+// kernel; one that brackets launches of its own returns their status, and a failure ends the call there.
+template <typename Launch, typename... Sym>
+int profiled_launch(const char* label, hipStream_t stream, Launch launch, Sym... symbol) {
+    if constexpr (sizeof...(Sym) > 0) prof_symbol(label, symbol...);
+    const int slot = prof_begin(label, stream);
+    if constexpr (std::is_void_v<decltype(launch())>) launch();
+    else MVDB_TRY(launch());
+    prof_end(slot, stream);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
 
 // Every MVDB_* tuning / A-B hook of the SEARCH path.  The environment is read ONCE per index — at mvdb_index_create, and
 // again only when the caller asks (mvdb_index_reload_env: A/B runs and tests that flip a hook inside one process) — never on

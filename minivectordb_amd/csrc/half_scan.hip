@@ -638,7 +638,7 @@ int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, i
 bool half_shadow_dim(int d) { return d == 128 || d == 256 || d == 384 || d == 512 || d == 640 || d == 768 || d == 896 || d == 1024; }
 
 // One launch of a kernel that streams through a ring in dynamic LDS: the attribute that admits `lds` bytes, a grid of one block
-// per tile up to `per_cu` workgroups per CU (*nblocks_out, where asked for), the profiling bracket.  symbol...: the format and the
+// per tile up to `per_cu` workgroups per CU (*nblocks_out, where asked for), the profiling bracket (profiled_launch).  symbol...: the format and the
 // arguments of prof_symbol.
 template <typename Args, typename... Sym>
 static int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int threads, int64_t ntiles, int per_cu, int device, hipStream_t stream,
@@ -646,12 +646,7 @@ static int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int thread
     MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * per_cu));
     if (nblocks_out) *nblocks_out = nblocks;
-    prof_symbol(label, symbol...);
-    int slot = prof_begin(label, stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return profiled_launch(label, stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, a); }, symbol...);
 }
 
 // The shapes of the launches that stream the whole shadow: the certified pass's main launches and the shared pass of a batch range

@@ -411,7 +411,7 @@ inline const Knobs& kn() { return *tls_kn; }
 struct Shape {
     int G, C;
 };
-Shape choose_shape(int d4) {
+constexpr Shape choose_shape(int d4) {
     // one chunk per lane, 16 / 32 / 64 lanes per row (rows of up to 64 / 128 / 256 floats; the 1-, 2-, 4- and 8-lane
     // shapes of rounds 1 - 4 served rows of <= 4, 8 and 32 floats only: 84 instantiations for toy widths)
     if (d4 <= 64) return {d4 <= 16 ? 16 : d4 <= 32 ? 32 : 64, 1};  // (rows of <= 16 floats ride the 16-lane shape, lanes masked)
@@ -425,125 +425,150 @@ Shape choose_shape(int d4) {
 }
 constexpr int kMaxC = 16;  // d <= 4096
 
-template <int G, int C, int U, int METRIC, int MODE, bool NT, int SEL, bool MASKED>
-int launch_scan_kern(const ScanArgs& a, int nq, int device, hipStream_t stream, int* nblocks_out) {
-    void (*kern)(ScanArgs) = flat_scan_kernel<G, C, U, METRIC, MODE, NT, SEL, MASKED>;
+// The exact scans are instantiated for the twelve shapes choose_shape returns.  launch(ScanShape<G, C>{}) for rows of d4 chunks:
+// this is the one table of them (flat_scan_kernel, range_scan_kernel, range_rescore_kernel, grouped_scan_kernel and the
+// candidate re-score of the int8 route all take their (G, C) from here).
+template <int G_, int C_>
+struct ScanShape {
+    static constexpr int G = G_, C = C_;
+};
+int unsupported_shape(int d4) { return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", d4); }
+template <typename Launch>
+int with_scan_shape(int d4, Launch launch) {
+    const Shape sh = choose_shape(d4);
+    if (sh.G == 16 && sh.C == 1) return launch(ScanShape<16, 1>{});
+    if (sh.G == 32 && sh.C == 1) return launch(ScanShape<32, 1>{});
+    if (sh.G == 32 && sh.C == 3) return launch(ScanShape<32, 3>{});
+    if (sh.G == 64) switch (sh.C) {
+            case 1: return launch(ScanShape<64, 1>{});
+            case 2: return launch(ScanShape<64, 2>{});
+            case 3: return launch(ScanShape<64, 3>{});
+            case 4: return launch(ScanShape<64, 4>{});
+            case 5: return launch(ScanShape<64, 5>{});
+            case 6: return launch(ScanShape<64, 6>{});
+            case 7: return launch(ScanShape<64, 7>{});
+            case 8: return launch(ScanShape<64, 8>{});
+            case 16: return launch(ScanShape<64, 16>{});
+            default: break;
+        }
+    return unsupported_shape(d4);
+}
+
+// ---- rows in flight per wave, U: three policies over the table (a score does not depend on U) ---------------------------------
+// (Rounds 1 - 2 carried run-time tuning hooks here — MVDB_SCAN_VARIANT, MVDB_SCAN_U: other rows-in-flight counts per shape,
+//  17 more shapes x 24 kernels each; the sweeps they served are in profiles/r01_sweep_scan_variants.txt.  Removed in round 3:
+//  they were 40 % of this code object, which a process loads whole before its first search.)
+// Streaming scans (every row, or the rows of a bitmap): about four independent 16-B loads per lane (scan_resident_blocks has the
+// measurement), so 4 rows of one chunk, 2 of two or three, 1 beyond; the three exact chunks on 32 lanes keep 4.
+constexpr int stream_u(int G, int C) { return C == 1 || G == 32 ? 4 : C <= 3 ? 2 : 1; }
+// Row-list (gather) scans of two- and three-chunk rows keep FOUR rows in flight per wave (the streaming scan: two): a
+// gathered row is a fresh DRAM page, so more rows must be outstanding to cover its latency — 10M x 512 rows resident,
+// ids on the device: 10 % of the rows 5.74 -> 6.23 TB/s of rows touched, 50 % 6.37 -> 6.78, 99 % 6.54 -> 6.95.
+// The grouped launch gathers too: its rows in flight are these (plan_grouped sizes its work items by them).
+constexpr int gather_u(int G, int C) { return C <= 3 ? 4 : 1; }
+// The exact re-scores of candidate rows (a range batch's shared pass, the int8 route): gathers too, 4 rows up to three
+// chunks, 2 up to eight, 1 at sixteen.  (No sweep of these is on record: they are the values both re-score launchers were written with.)
+constexpr int rescore_u(int G, int C) { return C <= 3 ? 4 : C <= 8 ? 2 : 1; }
+
+// ---- runtime -> compile-time switches of a shape's kernels: subset indirection, lane masking ----------------------------------
+// launch(ScanForm<SEL, MASKED>{}): SEL 0 every row, 1 a row list, 2 a bitmap; MASKED where the row does not fill G x C chunks.
+template <int SEL_, bool MASKED_>
+struct ScanForm {
+    static constexpr int SEL = SEL_;
+    static constexpr bool MASKED = MASKED_;
+};
+template <int G, int C, typename Launch>
+int with_scan_form(int d4, bool row_list, bool bitmap, Launch launch) {
+    auto sel = [&](auto masked) {
+        constexpr bool M = decltype(masked)::value;
+        if (bitmap) return launch(ScanForm<2, M>{});  // bitmap-selected rows (mvdb_index_search_masked)
+        if (row_list) return launch(ScanForm<1, M>{});
+        return launch(ScanForm<0, M>{});
+    };
+    // (32 lanes x 3 / 5 / 7 chunks are chosen for rows that fill them exactly: their lane-masked forms are never instantiated)
+    constexpr bool kAlwaysFull = G == 32 && C > 1;
+    if constexpr (!kAlwaysFull) {
+        if (d4 != G * C) return sel(std::true_type{});
+    }
+    return sel(std::false_type{});
+}
+
+// ---- grids ------------------------------------------------------------------------------------------------------------------
+// A row scan: RB = (64 / G) U rows per wave-batch, batches -> waves -> blocks, at most per_cu resident blocks per CU.
+int scan_grid(int64_t n, int RB, int per_cu, int device) {
+    const int64_t nbatches = (n + RB - 1) / RB;
+    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+}
+// The fp32-MFMA passes: one 16-row tile per wave at a time.
+int mfma_tile_grid(int64_t n, int per_cu, int device) {
+    const int64_t ntiles = (n + 15) / 16;
+    const int64_t want = (ntiles + kScanWaves - 1) / kScanWaves;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+}
+// Resident blocks per CU of the exact row scans (flat_scan_kernel, range_scan_kernel) at C chunks per lane; knob: the launch
+// honours MVDB_SCAN_BLOCKS_PER_CU.
+int scan_resident_blocks(const void* kern, int C, bool knob = true) {
+    const int occ_hw = cached_occupancy(kern, kScanThreads, 0, 4);  // blocks per CU this instantiation sustains
+    // measured on MI355X (round-1 sweep, profiles/r01_sweep_scan_variants.txt, 10M x 512): with ~4
+    // independent 16-B loads per lane, 2 resident blocks (8 waves) per CU reach 7.21-7.24 TB/s; more
+    // waves or more loads in flight per lane are 2-4 % slower, 1 block per CU is latency-starved
+    // (gpurun_out/sweep_dims.log: the one- and three-chunk shapes — d = 64 / 256 / 384 — prefer U = 4 with
+    //  3 resident blocks: 7.0-7.1 TB/s vs 6.5-6.9 at 2)
+    const int cap_env = knob ? kn().scan_blocks_per_cu : 0;  // tuning hook
+    return std::min(occ_hw, cap_env > 0 ? cap_env : (C == 1 || C == 3) ? 3 : 2);
+}
+
+// the widths of the int8 prefilter (code8_scan.hpp) and the exact-scan shapes they have
+constexpr int kCode8Dims[] = {384, 512, 1024};
+bool code8_dim(int d) { return std::find(std::begin(kCode8Dims), std::end(kCode8Dims), d) != std::end(kCode8Dims); }
+constexpr bool code8_shape(int G, int C) {
+    for (int d : kCode8Dims)
+        if (choose_shape(d / 4).G == G && choose_shape(d / 4).C == C) return true;
+    return false;
+}
+
+// label: the profiling label where the launch has one of its own (the int8 route's fallback scan)
+template <int G, int C, int U, int METRIC, int MODE, int SEL, bool MASKED>
+int launch_scan_kern(const ScanArgs& a, int nq, int device, hipStream_t stream, int* nblocks_out, const char* label = nullptr,
+                     bool knob = true) {
+    void (*kern)(ScanArgs) = flat_scan_kernel<G, C, U, METRIC, MODE, true, SEL, MASKED>;
     bool gated = false;
     // device-gated exact re-run of an L2 batch's queries: over the whole index (SEL 0) and under a bitmap (SEL 2 — round-4
-    // advisor finding: without the gated instantiation every query of a certified masked L2 batch paid a full masked scan)
-    if constexpr (METRIC == 1 && MODE == kModeTopK && (SEL == 0 || SEL == 2)) {
+    // advisor finding: without the gated instantiation every query of a certified masked L2 batch paid a full masked scan);
+    // and the int8 route's fallback: the headline kernel's shape with GATED set, at that route's widths
+    if constexpr ((METRIC == 1 && MODE == kModeTopK && (SEL == 0 || SEL == 2)) ||
+                  (METRIC == 0 && MODE == kModeTopK && SEL == 0 && !MASKED && code8_shape(G, C))) {
         if (a.gate) {
-            kern = flat_scan_kernel<G, C, U, METRIC, MODE, NT, SEL, MASKED, true>;
+            kern = flat_scan_kernel<G, C, U, METRIC, MODE, true, SEL, MASKED, true>;
             gated = true;
         }
     }
     if (a.gate && !gated) return fail(MVDB_ERR_ARG, "internal: a device-gated scan was requested for a kernel form that has no gated instantiation");
-    const int occ_hw = cached_occupancy((const void*)kern, kScanThreads, 0, 4);  // blocks per CU this instantiation sustains
-    int occ;
-    {
-        const int nb = occ_hw;
-        // measured on MI355X (round-1 sweep, profiles/r01_sweep_scan_variants.txt, 10M x 512): with ~4
-        // independent 16-B loads per lane, 2 resident blocks (8 waves) per CU reach 7.21-7.24 TB/s; more
-        // waves or more loads in flight per lane are 2-4 % slower, 1 block per CU is latency-starved
-        // (gpurun_out/sweep_dims.log: the one- and three-chunk shapes — d = 64 / 256 / 384 — prefer U = 4 with
-        //  3 resident blocks: 7.0-7.1 TB/s vs 6.5-6.9 at 2)
-        occ = std::min(nb, (C == 1 || C == 3) ? 3 : 2);
-        const int cap_env = kn().scan_blocks_per_cu;  // tuning hook
-        if (cap_env > 0) occ = std::min(occ_hw, cap_env);
-    }
-    constexpr int RB = (kWave / G) * U;
-    const int64_t nbatches = (a.n + RB - 1) / RB;
-    int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
-    int64_t cap = (int64_t)device_cus(device) * occ;
-    int nblocks = (int)std::max<int64_t>(1, std::min(want, cap));
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C, knob), device);
     if (nblocks_out) *nblocks_out = nblocks;
-    const char* pname = MODE == kModeTopK ? "ip_scan" : "ip_scan_scores";
-    prof_symbol(pname, "flat_scan_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", G, C, U, METRIC, MODE, NT ? "true" : "false", SEL,
-                MASKED ? "true" : "false", gated ? "true" : "false");
-    int slot = prof_begin(pname, stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
-}
-
-// runtime -> compile-time switches: subset indirection, lane masking
-template <int G, int C, int U, int METRIC, int MODE, bool NT = true>
-int launch_scan_inst(const ScanArgs& a, int nq, int device, hipStream_t s, int* nb) {
-    // (32 lanes x 3 / 5 / 7 chunks are chosen for rows that fill them exactly: their lane-masked forms are never instantiated)
-    constexpr bool kAlwaysFull = G == 32 && C > 1;
-    const bool masked = !kAlwaysFull && a.d4 != G * C;
-    if constexpr (kAlwaysFull) {
-        if (a.mask) return launch_scan_kern<G, C, U, METRIC, MODE, NT, 2, false>(a, nq, device, s, nb);
-        if (a.rows) return launch_scan_kern<G, C, U, METRIC, MODE, NT, 1, false>(a, nq, device, s, nb);
-        return launch_scan_kern<G, C, U, METRIC, MODE, NT, 0, false>(a, nq, device, s, nb);
-    }
-    if (a.mask) {  // bitmap-selected rows (mvdb_index_search_masked)
-        if (masked) return launch_scan_kern<G, C, U, METRIC, MODE, NT, 2, true>(a, nq, device, s, nb);
-        return launch_scan_kern<G, C, U, METRIC, MODE, NT, 2, false>(a, nq, device, s, nb);
-    }
-    if (a.rows) {
-        if (masked) return launch_scan_kern<G, C, U, METRIC, MODE, NT, 1, true>(a, nq, device, s, nb);
-        return launch_scan_kern<G, C, U, METRIC, MODE, NT, 1, false>(a, nq, device, s, nb);
-    }
-    if (masked) return launch_scan_kern<G, C, U, METRIC, MODE, NT, 0, true>(a, nq, device, s, nb);
-    return launch_scan_kern<G, C, U, METRIC, MODE, NT, 0, false>(a, nq, device, s, nb);
-}
-
-template <int G, int C, int U>
-int launch_scan_gcu(int metric, int mode, const ScanArgs& a, int nq, int device, hipStream_t s,
-                    int* nb) {
-    if (metric == MVDB_METRIC_IP) {
-        if (mode == kModeTopK) return launch_scan_inst<G, C, U, 0, kModeTopK>(a, nq, device, s, nb);
-        return launch_scan_inst<G, C, U, 0, kModeScores>(a, nq, device, s, nb);
-    }
-    if (mode == kModeTopK) return launch_scan_inst<G, C, U, 1, kModeTopK>(a, nq, device, s, nb);
-    return launch_scan_inst<G, C, U, 1, kModeScores>(a, nq, device, s, nb);
-}
-
-// the row-list (SEL 1) forms of a shape only: the gather variants of the two- and three-chunk shapes exist for nothing else
-template <int G, int C, int U>
-int launch_scan_rows(int metric, int mode, const ScanArgs& a, int nq, int device, hipStream_t s, int* nb) {
-    const bool masked = a.d4 != G * C;
-#define MVDB_ROWS_CASE(M, MD)                                                                              \
-    (masked ? launch_scan_kern<G, C, U, M, MD, true, 1, true>(a, nq, device, s, nb) \
-            : launch_scan_kern<G, C, U, M, MD, true, 1, false>(a, nq, device, s, nb))
-    if (metric == MVDB_METRIC_IP) return mode == kModeTopK ? MVDB_ROWS_CASE(0, kModeTopK) : MVDB_ROWS_CASE(0, kModeScores);
-    return mode == kModeTopK ? MVDB_ROWS_CASE(1, kModeTopK) : MVDB_ROWS_CASE(1, kModeScores);
-#undef MVDB_ROWS_CASE
+    return profiled_launch(label ? label : MODE == kModeTopK ? "ip_scan" : "ip_scan_scores", stream,
+                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           "flat_scan_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", G, C, U, METRIC, MODE, "true", SEL, MASKED ? "true" : "false",
+                           gated ? "true" : "false");
 }
 
 // Grid size the scan will use for (shape, n): needed up front to size the candidate buffer.
 int scan_grid_upper_bound(int device) { return device_cus(device) * 8; }
 
-int launch_scan(int metric, int mode, const ScanArgs& a, int nq, int device, hipStream_t s,
-                int* nblocks) {
-    const Shape sh = choose_shape(a.d4);
-    // (Rounds 1 - 2 carried run-time tuning hooks here — MVDB_SCAN_VARIANT, MVDB_SCAN_U: other rows-in-flight counts per shape,
-    //  17 more shapes x 24 kernels each; the sweeps they served are in profiles/r01_sweep_scan_variants.txt.  Removed in round 3:
-    //  they were 40 % of this code object, which a process loads whole before its first search.)
-    // Row-list (gather) scans of two- and three-chunk rows keep FOUR rows in flight per wave (the streaming scan: two): a
-    // gathered row is a fresh DRAM page, so more rows must be outstanding to cover its latency — 10M x 512 rows resident,
-    // ids on the device: 10 % of the rows 5.74 -> 6.23 TB/s of rows touched, 50 % 6.37 -> 6.78, 99 % 6.54 -> 6.95.
-    if (a.rows && sh.G == 64 && sh.C == 2) return launch_scan_rows<64, 2, 4>(metric, mode, a, nq, device, s, nblocks);
-    if (a.rows && sh.G == 64 && sh.C == 3) return launch_scan_rows<64, 3, 4>(metric, mode, a, nq, device, s, nblocks);
-#define MVDB_SCAN_CASE(G_, C_, U_) \
-    if (sh.G == G_ && sh.C == C_) return launch_scan_gcu<G_, C_, U_>(metric, mode, a, nq, device, s, nblocks);
-    MVDB_SCAN_CASE(16, 1, 4)
-    MVDB_SCAN_CASE(32, 1, 4)
-    MVDB_SCAN_CASE(32, 3, 4)
-    MVDB_SCAN_CASE(64, 1, 4)
-    MVDB_SCAN_CASE(64, 2, 2)
-    MVDB_SCAN_CASE(64, 3, 2)
-    MVDB_SCAN_CASE(64, 4, 1)
-    MVDB_SCAN_CASE(64, 5, 1)
-    MVDB_SCAN_CASE(64, 6, 1)
-    MVDB_SCAN_CASE(64, 7, 1)
-    MVDB_SCAN_CASE(64, 8, 1)
-    MVDB_SCAN_CASE(64, 16, 1)
-#undef MVDB_SCAN_CASE
-    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)",
-                a.d4);
+int launch_scan(int metric, int mode, const ScanArgs& a, int nq, int device, hipStream_t s, int* nblocks) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);  // a row list: the gather policy
+            if (metric == MVDB_METRIC_IP)
+                return mode == kModeTopK ? launch_scan_kern<S::G, S::C, U, 0, kModeTopK, F::SEL, F::MASKED>(a, nq, device, s, nblocks)
+                                         : launch_scan_kern<S::G, S::C, U, 0, kModeScores, F::SEL, F::MASKED>(a, nq, device, s, nblocks);
+            return mode == kModeTopK ? launch_scan_kern<S::G, S::C, U, 1, kModeTopK, F::SEL, F::MASKED>(a, nq, device, s, nblocks)
+                                     : launch_scan_kern<S::G, S::C, U, 1, kModeScores, F::SEL, F::MASKED>(a, nq, device, s, nblocks);
+        });
+    });
 }
 
 __global__ void fill_missing_kernel(float* D, int64_t* I, int64_t total, int metric) {
@@ -602,15 +627,8 @@ int launch_mfma_inst(const MfmaScanArgs& a, int device, hipStream_t stream, int*
     MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
     int nb = cached_occupancy((const void*)kern, kScanThreads, lds, 1);
     nb = std::min(nb, kn().mfma_blocks_per_cu > 0 ? kn().mfma_blocks_per_cu : 4);
-    const int64_t ntiles = (a.n + 15) / 16;
-    const int64_t want = (ntiles + kScanWaves - 1) / kScanWaves;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * nb));
-    *nblocks_out = nblocks;
-    int slot = prof_begin("ip_scan_mfma", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
+    return profiled_launch("ip_scan_mfma", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a); });
 }
 
 template <int KB, int NG, int SKB>
@@ -621,16 +639,11 @@ int launch_mfma2_gated_inst(const MfmaScanArgs& a, int device, hipStream_t strea
     MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
     int nb = cached_occupancy((const void*)kern, kScanThreads, lds, 1);
     nb = std::min(nb, kn().mfma_blocks_per_cu > 0 ? kn().mfma_blocks_per_cu : 2);
-    const int64_t ntiles = (a.n + 15) / 16;
-    const int64_t want = (ntiles + kScanWaves - 1) / kScanWaves;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * nb));
-    *nblocks_out = nblocks;
-    prof_symbol("ip_scan_rerun", "flat_scan_mfma2_gated_kernel<%d, %d, %d, %s>", KB, NG, SKB, a.mask ? "true" : "false");
-    int slot = prof_begin("ip_scan_rerun", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a, gate, gate_lo, need, npasses, per_pass, rtot, cand_stride);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
+    return profiled_launch(
+        "ip_scan_rerun", stream,
+        [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a, gate, gate_lo, need, npasses, per_pass, rtot, cand_stride); },
+        "flat_scan_mfma2_gated_kernel<%d, %d, %d, %s>", KB, NG, SKB, a.mask ? "true" : "false");
 }
 
 template <int KB, int NG, int SKB>
@@ -650,16 +663,9 @@ int launch_mfma2_inst(const MfmaScanArgs& a, int device, hipStream_t stream, int
     MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
     int nb = cached_occupancy((const void*)kern, kScanThreads, lds, 1);
     nb = std::min(nb, kn().mfma_blocks_per_cu > 0 ? kn().mfma_blocks_per_cu : 2);
-    const int64_t ntiles = (a.n + 15) / 16;
-    const int64_t want = (ntiles + kScanWaves - 1) / kScanWaves;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * nb));
-    *nblocks_out = nblocks;
-    prof_symbol("ip_scan_mfma", "flat_scan_mfma2_kernel<%d, %d, %d, %d>", KB, NG, SKB, metric == MVDB_METRIC_L2 ? 1 : 0);
-    int slot = prof_begin("ip_scan_mfma", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
+    return profiled_launch("ip_scan_mfma", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a); },
+                           "flat_scan_mfma2_kernel<%d, %d, %d, %d>", KB, NG, SKB, metric == MVDB_METRIC_L2 ? 1 : 0);
 }
 
 template <int NG>
@@ -775,11 +781,7 @@ int launch_gemm_scan(const mvdb_index* idx, const float* q, int nq, int k, int64
         MVDB_HIP(hipGetLastError());
         return 0;
     }
-    int slot = prof_begin("ip_scan_gemm", stream);
-    hipLaunchKernelGGL(flat_scan_gemm_kernel, dim3(gx, qtiles), dim3(256), lds, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return profiled_launch("ip_scan_gemm", stream, [&] { hipLaunchKernelGGL(flat_scan_gemm_kernel, dim3(gx, qtiles), dim3(256), lds, stream, a); });
 }
 
 // Chunks that held an uncertified query, counted ON THE DEVICE (split_plan_kernel): the host never reads a certification
@@ -1515,9 +1517,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
             ma.cand = ws->cand.p;
             ma.mask = mask32;
             int nblocks = 0;
-            int slot = prof_begin("ip_scan_mfma_masked", s);
-            MVDB_TRY(launch_mfma2_gated(idx->d / 16, ma, idx->device, s, &nblocks, nullptr, 0));
-            prof_end(slot, s);
+            MVDB_TRY(profiled_launch("ip_scan_mfma_masked", s, [&] { return launch_mfma2_gated(idx->d / 16, ma, idx->device, s, &nblocks, nullptr, 0); }));
             MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
         }
         return 0;
@@ -1888,8 +1888,6 @@ void invalidate_code8(const mvdb_index* idx) {
     idx->c8_rows = 0;
 }
 
-bool code8_dim(int d) { return d == 384 || d == 512 || d == 1024; }
-
 int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t s) {
     if (rows > 0) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
@@ -1965,40 +1963,40 @@ bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_de
     return true;
 }
 
-// the device-gated full exact scan of the route's fallback: the headline kernel's shape with GATED set
-template <int G, int C, int U>
-int launch_gated_ip_scan(const ScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
-    void (*kern)(ScanArgs) = flat_scan_kernel<G, C, U, 0, kModeTopK, true, 0, false, true>;
-    const int occ = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), (C == 1 || C == 3) ? 3 : 2);
-    constexpr int RB = (kWave / G) * U;
-    const int64_t nbatches = (a.n + RB - 1) / RB;
-    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * occ));
-    *nblocks_out = nblocks;
-    prof_symbol("ip_scan_code8_fallback", "flat_scan_kernel<%d, %d, %d, 0, 0, true, 0, false, true>", G, C, U);
-    int slot = prof_begin("ip_scan_code8_fallback", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks, 1), dim3(kScanThreads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+// What is specific to the codes: (G, U, MASKED) of code8_seed_kernel / code8_scan_kernel per width (U per shape: measured,
+// DESIGN.md section 4.1b).  launch(Code8Shape<...>{}) for d; the exact-scan shapes of the route come from with_scan_shape.
+template <int G_, int U_, bool MASKED_>
+struct Code8Shape {
+    static constexpr int G = G_, U = U_;
+    static constexpr bool MASKED = MASKED_;
+};
+template <typename Launch>
+int with_code8_shape(int d, Launch launch) {
+    switch (d) {
+        case 384: return launch(Code8Shape<32, 8, true>{});
+        case 512: return launch(Code8Shape<32, 4, false>{});
+        case 1024: return launch(Code8Shape<64, 4, false>{});
+        default: return fail(MVDB_ERR_ARG, "internal: no int8 prefilter kernel for d = %d", d);
+    }
+}
+// launch(ScanShape<G, C>{}) for the exact-scan shape of one of the route's widths: nothing is instantiated for the other shapes
+template <typename Launch>
+int with_code8_exact_shape(int d4, Launch launch) {
+    return with_scan_shape(d4, [&](auto shape) {
+        if constexpr (code8_shape(decltype(shape)::G, decltype(shape)::C)) return launch(shape);
+        else return fail(MVDB_ERR_ARG, "internal: no int8 prefilter kernel for rows of %d 16-byte chunks", d4);
+    });
 }
 
 template <int G, int U, bool MASKED>
 int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
     void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
-    constexpr int RB = (kWave / G) * U;
-    const int64_t nbatches = (a.n + RB - 1) / RB;
-    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
     // CUs x 2 blocks: measured for this kernel (3 and 4 blocks per CU are 3 - 7 % slower at every served shape)
     int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), 2);
     if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
-    prof_symbol("ip_scan", "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
-    int slot = prof_begin("ip_scan", stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, per_cu, device);
+    return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
+                           "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 
 // The floor's launch.  The gather is bound by latency, the last block's merge by inserts: wide blocks keep the lists few.
@@ -2012,12 +2010,8 @@ int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream) {
     const int64_t want = (nbatches + threads / kWave - 1) / (threads / kWave);
     int64_t blocks = kn().code8_seed_blocks > 0 ? kn().code8_seed_blocks : device_cus(device);
     blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, want), scan_grid_upper_bound(device)));
-    prof_symbol("ip_scan_code8_seed", "code8_seed_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
-    int slot = prof_begin("ip_scan_code8_seed", stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return profiled_launch("ip_scan_code8_seed", stream, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, a); },
+                           "code8_seed_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 
 // The re-score's launch: a grid for the whole capacity, of which the kernel uses what the count asks for.
@@ -2026,12 +2020,8 @@ int launch_code8_rescore(const Code8RescoreArgs& a, int device, hipStream_t stre
     void (*kern)(Code8RescoreArgs) = code8_rescore_kernel<G, C, U, MASKED>;
     const int64_t want = (a.cap + a.rows_per_block - 1) / a.rows_per_block;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * 4));
-    prof_symbol("ip_scan_code8_rescore", "code8_rescore_kernel<%d, %d, %d, %s>", G, C, U, MASKED ? "true" : "false");
-    int slot = prof_begin("ip_scan_code8_rescore", stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kScanThreads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
+    return profiled_launch("ip_scan_code8_rescore", stream, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kScanThreads), 0, stream, a); },
+                           "code8_rescore_kernel<%d, %d, %d, %s>", G, C, U, MASKED ? "true" : "false");
 }
 
 int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
@@ -2084,9 +2074,10 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     sd.lists = ws->cand.p;
     sd.ticket = tickets;
     sd.floor = floor;
-    if (d == 512) MVDB_TRY((launch_code8_seed<32, 4, false>(sd, idx->device, s)));
-    else if (d == 1024) MVDB_TRY((launch_code8_seed<64, 4, false>(sd, idx->device, s)));
-    else MVDB_TRY((launch_code8_seed<32, 8, true>(sd, idx->device, s)));
+    MVDB_TRY(with_code8_shape(d, [&](auto cs) {
+        using K = decltype(cs);
+        return launch_code8_seed<K::G, K::U, K::MASKED>(sd, idx->device, s);
+    }));
     // 3. the prefilter over the codes
     Code8ScanArgs c;
     c.codes = idx->C8;
@@ -2100,10 +2091,10 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.cand = cand;
     c.cap = cap;
     c.counter = counter;
-    // (U per shape: measured)
-    if (d == 512) MVDB_TRY((launch_code8_scan<32, 4, false>(c, idx->device, s)));
-    else if (d == 1024) MVDB_TRY((launch_code8_scan<64, 4, false>(c, idx->device, s)));
-    else MVDB_TRY((launch_code8_scan<32, 8, true>(c, idx->device, s)));
+    MVDB_TRY(with_code8_shape(d, [&](auto cs) {
+        using K = decltype(cs);
+        return launch_code8_scan<K::G, K::U, K::MASKED>(c, idx->device, s);
+    }));
     // 4. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
     Code8RescoreArgs r;
     r.X = a0.X;
@@ -2125,10 +2116,11 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     r.label_offset = label_offset;
     r.D = D_dev;
     r.I = I_dev;
-    // (the exact scan's shape per width, choose_shape: the arithmetic is restated for exactly these)
-    if (d == 512) MVDB_TRY((launch_code8_rescore<64, 2, 4, false>(r, idx->device, s)));
-    else if (d == 1024) MVDB_TRY((launch_code8_rescore<64, 4, 2, false>(r, idx->device, s)));
-    else MVDB_TRY((launch_code8_rescore<32, 3, 4, false>(r, idx->device, s)));
+    // (the exact scan's shape: the arithmetic is restated for exactly that; the route serves unpadded rows that fill it)
+    MVDB_TRY(with_code8_exact_shape(a0.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return launch_code8_rescore<S::G, S::C, rescore_u(S::G, S::C), false>(r, idx->device, s);
+    }));
     // 5. fallback, enabled on the device: the full exact scan overwrites the result
     ScanArgs a = a0;
     a.cand = ws->cand.p;
@@ -2137,9 +2129,11 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     a.n = idx->n;
     a.gate = gate;
     a.gate_lo = 0;
-    if (d == 512) MVDB_TRY((launch_gated_ip_scan<64, 2, 2>(a, idx->device, s, &nblocks)));
-    else if (d == 1024) MVDB_TRY((launch_gated_ip_scan<64, 4, 1>(a, idx->device, s, &nblocks)));
-    else MVDB_TRY((launch_gated_ip_scan<32, 3, 4>(a, idx->device, s, &nblocks)));
+    MVDB_TRY(with_code8_exact_shape(a.d4, [&](auto shape) {   // (the fallback has never honoured MVDB_SCAN_BLOCKS_PER_CU)
+        using S = decltype(shape);
+        return launch_scan_kern<S::G, S::C, stream_u(S::G, S::C), 0, kModeTopK, 0, false>(a, 1, idx->device, s, &nblocks, "ip_scan_code8_fallback",
+                                                                                            /*knob=*/false);
+    }));
     MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, label_offset, D_dev, I_dev, gate));
     *served = true;
     return 0;
@@ -3128,123 +3122,54 @@ template <int G, int C, int U, int METRIC, int SEL, bool MASKED>
 int launch_range_kern(const RangeScanArgs& a, int nq, int device, hipStream_t stream) {
     void (*kern)(RangeScanArgs) = range_scan_kernel<G, C, U, METRIC, SEL, MASKED>;
     // the grid of the single-query scan (launch_scan_kern): 2 resident blocks per CU, 3 for the one- and three-chunk shapes
-    const int occ_hw = cached_occupancy((const void*)kern, kScanThreads, 0, 4);
-    int occ = std::min(occ_hw, (C == 1 || C == 3) ? 3 : 2);
-    if (kn().scan_blocks_per_cu > 0) occ = std::min(occ_hw, kn().scan_blocks_per_cu);
-    constexpr int RB = (kWave / G) * U;
-    const int64_t nbatches = (a.n + RB - 1) / RB;
-    const int64_t want = (nbatches + kScanWaves - 1) / kScanWaves;
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * occ));
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
     // (the gated launch of the shared pass runs under a label of its own: a profile tells the scans that were asked for from
     //  the launches that return at once)
-    const char* label = a.gate_count ? "ip_scan_range_fallback" : "ip_scan_range";
-    prof_symbol(label, "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
-    int slot = prof_begin(label, stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a);
-    prof_end(slot, stream);
-    MVDB_HIP(hipGetLastError());
-    return 0;
-}
-
-template <int G, int C, int U, int METRIC>
-int launch_range_sel(const RangeScanArgs& a, int nq, int device, hipStream_t s) {
-    constexpr bool kAlwaysFull = G == 32 && C > 1;  // (as launch_scan_inst: chosen for rows that fill the lanes exactly)
-    if constexpr (kAlwaysFull) {
-        if (a.mask) return launch_range_kern<G, C, U, METRIC, 2, false>(a, nq, device, s);
-        if (a.rows) return launch_range_kern<G, C, U, METRIC, 1, false>(a, nq, device, s);
-        return launch_range_kern<G, C, U, METRIC, 0, false>(a, nq, device, s);
-    } else {
-        const bool masked = a.d4 != G * C;
-        if (a.mask)
-            return masked ? launch_range_kern<G, C, U, METRIC, 2, true>(a, nq, device, s)
-                          : launch_range_kern<G, C, U, METRIC, 2, false>(a, nq, device, s);
-        // (row lists of the two- and three-chunk shapes are launch_range's own U = 4 forms: no U = 2 gather is instantiated)
-        if constexpr (!(G == 64 && (C == 2 || C == 3))) {
-            if (a.rows)
-                return masked ? launch_range_kern<G, C, U, METRIC, 1, true>(a, nq, device, s)
-                              : launch_range_kern<G, C, U, METRIC, 1, false>(a, nq, device, s);
-        }
-        return masked ? launch_range_kern<G, C, U, METRIC, 0, true>(a, nq, device, s)
-                      : launch_range_kern<G, C, U, METRIC, 0, false>(a, nq, device, s);
-    }
+    return profiled_launch(a.gate_count ? "ip_scan_range_fallback" : "ip_scan_range", stream,
+                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
 }
 
 // the shapes and rows in flight of launch_scan: a score depends on (G, C, MASKED, METRIC) only, U follows the measured best
 int launch_range(int metric, const RangeScanArgs& a, int nq, int device, hipStream_t s) {
-    const Shape sh = choose_shape(a.d4);
-    const bool masked = a.d4 != sh.G * sh.C;
-    if (a.rows && sh.G == 64 && (sh.C == 2 || sh.C == 3)) {  // gathered two- and three-chunk rows: four rows in flight
-#define MVDB_RANGE_ROWS(C_, M_)                                                        \
-    (masked ? launch_range_kern<64, C_, 4, M_, 1, true>(a, nq, device, s) \
-            : launch_range_kern<64, C_, 4, M_, 1, false>(a, nq, device, s))
-        if (sh.C == 2) return metric == MVDB_METRIC_IP ? MVDB_RANGE_ROWS(2, 0) : MVDB_RANGE_ROWS(2, 1);
-        return metric == MVDB_METRIC_IP ? MVDB_RANGE_ROWS(3, 0) : MVDB_RANGE_ROWS(3, 1);
-#undef MVDB_RANGE_ROWS
-    }
-#define MVDB_RANGE_CASE(G_, C_, U_)                                                         \
-    if (sh.G == G_ && sh.C == C_)                                                           \
-        return metric == MVDB_METRIC_IP ? launch_range_sel<G_, C_, U_, 0>(a, nq, device, s) \
-                                        : launch_range_sel<G_, C_, U_, 1>(a, nq, device, s);
-    MVDB_RANGE_CASE(16, 1, 4)
-    MVDB_RANGE_CASE(32, 1, 4)
-    MVDB_RANGE_CASE(32, 3, 4)
-    MVDB_RANGE_CASE(64, 1, 4)
-    MVDB_RANGE_CASE(64, 2, 2)
-    MVDB_RANGE_CASE(64, 3, 2)
-    MVDB_RANGE_CASE(64, 4, 1)
-    MVDB_RANGE_CASE(64, 5, 1)
-    MVDB_RANGE_CASE(64, 6, 1)
-    MVDB_RANGE_CASE(64, 7, 1)
-    MVDB_RANGE_CASE(64, 8, 1)
-    MVDB_RANGE_CASE(64, 16, 1)
-#undef MVDB_RANGE_CASE
-    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);
+            return metric == MVDB_METRIC_IP ? launch_range_kern<S::G, S::C, U, 0, F::SEL, F::MASKED>(a, nq, device, s)
+                                            : launch_range_kern<S::G, S::C, U, 1, F::SEL, F::MASKED>(a, nq, device, s);
+        });
+    });
 }
 
 constexpr int kRangeTile = 1024;  // queries of one range launch (a call of more is answered that many at a time)
 
 // ---- the shared pass of a range batch (inner product): nomination over the fp16 shadow, exact re-score, gated fallback ----------
-template <int G, int C, int U>
-int launch_rescore_gcu(const RangeRescoreArgs& a, int nq, int device, hipStream_t s) {
-    constexpr bool kAlwaysFull = G == 32 && C > 1;
-    const bool masked = !kAlwaysFull && a.d4 != G * C;
-    void (*kern)(RangeRescoreArgs);
-    if constexpr (kAlwaysFull) {
-        kern = range_rescore_kernel<G, C, U, false>;
-    } else {
-        kern = masked ? range_rescore_kernel<G, C, U, true> : range_rescore_kernel<G, C, U, false>;
-    }
-    // blocks per query: enough for a full candidate segment at a few batches per wave, no more than the device holds at once
-    constexpr int RB = (kWave / G) * U;
-    const int64_t want = (a.ccap + (int64_t)RB * kScanWaves * 4 - 1) / ((int64_t)RB * kScanWaves * 4);
-    const int64_t room = std::max<int64_t>(1, (int64_t)device_cus(device) * 8 / nq);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, room));
-    prof_symbol("ip_scan_range_rescore", "range_rescore_kernel<%d, %d, %d, %s>", G, C, U, masked ? "true" : "false");
-    int slot = prof_begin("ip_scan_range_rescore", s);
-    hipLaunchKernelGGL(kern, dim3(gx, nq), dim3(kScanThreads), 0, s, a);
-    prof_end(slot, s);
-    MVDB_HIP(hipGetLastError());
-    return 0;
-}
+// Reached through range_shared_route only, which holds the index to the shadow's widths with unpadded rows (half_path_ok:
+// d = 128, 256, ..., 1024): rows of 32 x 1, 64 x 1, 32 x 3 and 64 x 2 / 3 / 4 chunks.  No other shape has a re-score kernel.
+constexpr bool rescore_shape(int G, int C) { return G >= 32 && C <= 4; }
 
 int launch_rescore(const RangeRescoreArgs& a, int nq, int device, hipStream_t s) {
-    const Shape sh = choose_shape(a.d4);
-#define MVDB_RESCORE_CASE(G_, C_, U_) \
-    if (sh.G == G_ && sh.C == C_) return launch_rescore_gcu<G_, C_, U_>(a, nq, device, s);
-    MVDB_RESCORE_CASE(16, 1, 4)
-    MVDB_RESCORE_CASE(32, 1, 4)
-    MVDB_RESCORE_CASE(32, 3, 4)
-    MVDB_RESCORE_CASE(64, 1, 4)
-    MVDB_RESCORE_CASE(64, 2, 4)
-    MVDB_RESCORE_CASE(64, 3, 4)
-    MVDB_RESCORE_CASE(64, 4, 2)
-    MVDB_RESCORE_CASE(64, 5, 2)
-    MVDB_RESCORE_CASE(64, 6, 2)
-    MVDB_RESCORE_CASE(64, 7, 2)
-    MVDB_RESCORE_CASE(64, 8, 2)
-    MVDB_RESCORE_CASE(64, 16, 1)
-#undef MVDB_RESCORE_CASE
-    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        if constexpr (!rescore_shape(S::G, S::C)) {
+            return unsupported_shape(a.d4);
+        } else {
+            constexpr int U = rescore_u(S::G, S::C);
+            return with_scan_form<S::G, S::C>(a.d4, false, false, [&](auto form) {
+                constexpr bool MASKED = decltype(form)::MASKED;
+                void (*kern)(RangeRescoreArgs) = range_rescore_kernel<S::G, S::C, U, MASKED>;
+                // blocks per query: enough for a full candidate segment at a few batches per wave, no more than the device holds at once
+                constexpr int RB = (kWave / S::G) * U;
+                const int64_t want = (a.ccap + (int64_t)RB * kScanWaves * 4 - 1) / ((int64_t)RB * kScanWaves * 4);
+                const int64_t room = std::max<int64_t>(1, (int64_t)device_cus(device) * 8 / nq);
+                const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, room));
+                return profiled_launch("ip_scan_range_rescore", s, [&] { hipLaunchKernelGGL(kern, dim3(gx, nq), dim3(kScanThreads), 0, s, a); },
+                                       "range_rescore_kernel<%d, %d, %d, %s>", S::G, S::C, U, MASKED ? "true" : "false");
+            });
+        }
+    });
 }
 
 // floors[i] = threshold_i - coef |q_i|, rounded down (a NaN or -inf floor admits every row: the query overflows or is decided
@@ -3660,47 +3585,18 @@ int mvdb_index_range_search_each_device(const mvdb_index* idx, const float* q_de
 // ---- grouped search: every query under its own row set (grouped_scan.hpp) ------------------------------------------------
 namespace {
 
-template <int G, int C, int U>
-int launch_grouped_gcu(int metric, const GroupedScanArgs& a, int nitems, hipStream_t s) {
-    constexpr bool kAlwaysFull = G == 32 && C > 1;  // (chosen for rows that fill it exactly: no lane-masked form, as launch_scan_inst)
-    const bool masked = !kAlwaysFull && a.d4 != G * C;
-    void (*kern)(GroupedScanArgs);
-    if constexpr (kAlwaysFull) {
-        kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, false> : grouped_scan_kernel<G, C, U, 1, false>;
-    } else {
-        if (masked) kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, true> : grouped_scan_kernel<G, C, U, 1, true>;
-        else kern = metric == MVDB_METRIC_IP ? grouped_scan_kernel<G, C, U, 0, false> : grouped_scan_kernel<G, C, U, 1, false>;
-    }
-    prof_symbol("grouped_scan", "grouped_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, metric == MVDB_METRIC_IP ? 0 : 1,
-                masked ? "true" : "false");
-    int slot = prof_begin("grouped_scan", s);
-    hipLaunchKernelGGL(kern, dim3(nitems), dim3(kScanThreads), 0, s, a);
-    prof_end(slot, s);
-    MVDB_HIP(hipGetLastError());
-    return 0;
-}
-
-// rows in flight per wave: what the row-list forms of launch_scan use (U does not enter the arithmetic)
-constexpr int grouped_u(int C) { return C <= 3 ? 4 : 1; }
-
+// rows in flight per wave: the gather policy, what the row-list forms of launch_scan use (U does not enter the arithmetic)
 int launch_grouped(int metric, const GroupedScanArgs& a, int nitems, hipStream_t s) {
-    const Shape sh = choose_shape(a.d4);
-#define MVDB_GROUPED_CASE(G_, C_) \
-    if (sh.G == G_ && sh.C == C_) return launch_grouped_gcu<G_, C_, grouped_u(C_)>(metric, a, nitems, s);
-    MVDB_GROUPED_CASE(16, 1)
-    MVDB_GROUPED_CASE(32, 1)
-    MVDB_GROUPED_CASE(32, 3)
-    MVDB_GROUPED_CASE(64, 1)
-    MVDB_GROUPED_CASE(64, 2)
-    MVDB_GROUPED_CASE(64, 3)
-    MVDB_GROUPED_CASE(64, 4)
-    MVDB_GROUPED_CASE(64, 5)
-    MVDB_GROUPED_CASE(64, 6)
-    MVDB_GROUPED_CASE(64, 7)
-    MVDB_GROUPED_CASE(64, 8)
-    MVDB_GROUPED_CASE(64, 16)
-#undef MVDB_GROUPED_CASE
-    return fail(MVDB_ERR_ARG, "dimension with %d 16-byte chunks per row is not supported (d <= 4096)", a.d4);
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        constexpr int U = gather_u(S::G, S::C);
+        return with_scan_form<S::G, S::C>(a.d4, false, false, [&](auto form) {
+            constexpr bool MASKED = decltype(form)::MASKED;
+            void (*kern)(GroupedScanArgs) = metric == MVDB_METRIC_IP ? grouped_scan_kernel<S::G, S::C, U, 0, MASKED> : grouped_scan_kernel<S::G, S::C, U, 1, MASKED>;
+            return profiled_launch("grouped_scan", s, [&] { hipLaunchKernelGGL(kern, dim3(nitems), dim3(kScanThreads), 0, s, a); },
+                                   "grouped_scan_kernel<%d, %d, %d, %d, %s>", S::G, S::C, U, metric == MVDB_METRIC_IP ? 0 : 1, MASKED ? "true" : "false");
+        });
+    });
 }
 
 // Cut the lists of the call's list-form queries into work items.  The rule:
@@ -3713,7 +3609,7 @@ int launch_grouped(int metric, const GroupedScanArgs& a, int nitems, hipStream_t
 void plan_grouped(const mvdb_index* idx, int nq, const mvdb_rowset* const* sets, std::vector<GroupedQuery>& queries,
                   std::vector<GroupedItem>& items) {
     const Shape sh = choose_shape(idx->d4);
-    const int64_t step = (int64_t)kScanWaves * (kWave / sh.G) * grouped_u(sh.C);  // rows one block takes per loop step
+    const int64_t step = (int64_t)kScanWaves * (kWave / sh.G) * gather_u(sh.G, sh.C);  // rows one block takes per loop step
     const int per_cu = idx->kn.grouped_items_per_cu > 0 ? idx->kn.grouped_items_per_cu : 4;  // swept on the device: DESIGN.md section 6c
     const int64_t T = (int64_t)device_cus(idx->device) * per_cu;
     int64_t sum = 0;
@@ -3850,10 +3746,7 @@ int grouped_search_core(const mvdb_index* idx, Workspace* ws, const float* q, in
         mg.label_offset = label_offset;
         mg.D = D_dev;
         mg.I = I_dev;
-        int slot = prof_begin("grouped_merge", s);
-        hipLaunchKernelGGL(merge_keys_seg_kernel, dim3(nq), dim3(kMergeThreads), 0, s, mg);
-        prof_end(slot, s);
-        MVDB_HIP(hipGetLastError());
+        MVDB_TRY(profiled_launch("grouped_merge", s, [&] { hipLaunchKernelGGL(merge_keys_seg_kernel, dim3(nq), dim3(kMergeThreads), 0, s, mg); }));
     }
     // bitmap and NULL sets (and every query when k is beyond the fused select): the exact single-query routes, row by row
     for (int i = 0; i < nq; ++i) {
