@@ -452,12 +452,17 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * When enabled, every launch of the dominant kernels is bracketed by hipEvents on the launch
  * stream.  mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "encoder") and returns the number of launches and their summed duration. */
+ * "encoder") and returns the number of launches and their summed duration.
+ * Turning profiling on while it was off forgets the symbols recorded so far (mvdb_prof_symbol): after it, a label under which
+ * nothing has been launched since reads "", not the symbol of an earlier bracket. */
 int mvdb_prof_enable(int on);
 int mvdb_prof_read(const char* name, int64_t* launches, double* total_ms);
 /* The kernel instantiation last launched under label `name` while profiling was on, as rocprofv3 prints it
  * ("flat_scan_kernel<64, 2, 2, 0, 0, true, 0, false>"; "" if none): bench.py refuses a committed PMC profile whose kernel
- * differs from what the timed run launched. */
+ * differs from what the timed run launched.  The ops of an encoder forward record theirs with the grid, the block and the LDS
+ * bytes — "gemm_x3_dma_kernel<EPI_BIAS_QKV, 64, 3, 4, 64, 1, 0> grid=(18,2,1) block=256 lds=49152 sel=0" — under enc_pack,
+ * enc_embed, enc_qkv, enc_qkv_epi, enc_attn, enc_ctx_split, enc_wo, enc_ln1, enc_ffn1, enc_ffn1_epi, enc_ffn2, enc_ln2, enc_pool,
+ * and the second GEMM of a (256-row form, fallback) pair under <label>_fallback (tests/test_encoder_launch_table_gpu.py). */
 int mvdb_prof_symbol(const char* name, char* out, int len);
 
 /* Number of chunks (up to 256 queries) of the certified batch passes that held a query which failed certification — those
@@ -564,7 +569,11 @@ typedef struct mvdb_encoder_cfg {
 
 /* Weight table: device pointers (fp32, PyTorch nn.Linear layout [out,in]) in the order given by
  * mvdb_encoder_weight_name(i) for i in [0, mvdb_encoder_weight_count(cfg)). The encoder keeps
- * the pointers (the caller — a torch state_dict — owns the memory). */
+ * the pointers (the caller — a torch state_dict — owns the memory).
+ * mvdb_encoder_create reads every MVDB_* switch of the encoder (docs/DESIGN_NOTES.md, the switch list) into the encoder: a
+ * switch set afterwards does not reach it, one process can hold encoders created under different switches, and no forward
+ * reads the environment.  (Earlier builds read most of them once per PROCESS, at the first launch that consulted them.)
+ * Per process still: MVDB_WALK_LOCK and MVDB_WALK_LOCK_DIR, the per-device gate all encoders share. */
 int mvdb_encoder_weight_count(const mvdb_encoder_cfg* cfg);
 const char* mvdb_encoder_weight_name(const mvdb_encoder_cfg* cfg, int i);
 int mvdb_encoder_create(const mvdb_encoder_cfg* cfg, const void* const* weight_ptrs_dev, int device,
@@ -604,7 +613,7 @@ int mvdb_encoder_walks(const mvdb_encoder* enc, int B, int S);
  * resident.  It is guarded three ways (csrc/encoder.hip "Walking launches ..."): one such launch at a time per device inside
  * a process (whatever encoder, stream or host thread); an advisory flock on /dev/shm/mvdb_walk_<GPU UUID>.lock across
  * processes (MVDB_WALK_LOCK=0 switches it off, MVDB_WALK_LOCK_DIR moves it); and BOUNDED waits inside the kernel: no wait
- * outlasts MVDB_WALK_DEADLINE_US (default 20000, read when the encoder first walks) — the launch then abandons itself, fills
+ * outlasts MVDB_WALK_DEADLINE_US (default 20000, read when the encoder is created) — the launch then abandons itself, fills
  * `out` with NaN, raises the overflow word above and counts itself.  mvdb_encoder_forward notices that behind its own stream
  * wait and re-runs the forward on the per-op kernels within the same call; a caller of mvdb_encoder_forward_device sees the
  * overflow word (or `aborts` here) behind ITS stream wait and calls again.  After an abandoned launch the next 256 forwards of
@@ -624,7 +633,7 @@ int mvdb_encoder_gemm_tile_form(int64_t tokens, int n, int compute_units);
  * K (0: not split): a K-step of the GEMM is a latency step — one barrier and one DMA round trip — so while the 64 x 128 tiles of
  * a batch leave CUs idle, K is cut into min(8, (k / 32) / 4, compute_units / tiles) planes (snapped to 2 / 3 / 4 / 6 / 8), summed in
  * plane order by the LayerNorm / image kernel behind the GEMM.  The same rule on the host, from the padded token count; exported
- * so that it is testable without a GPU (tests/test_encoder_tiles.py).  MVDB_GEMM_X3_SPLITK* environment switches: csrc/encoder.hip. */
+ * so that it is testable without a GPU (tests/test_encoder_tiles.py).  MVDB_GEMM_X3_SPLITK* environment switches: csrc/encoder.hip; this function, which has no encoder, reads them at the call. */
 int mvdb_encoder_splitk_planes(int64_t tokens, int n, int k, int compute_units);
 
 #ifdef __cplusplus

@@ -777,6 +777,7 @@ def normalize_l2(x, device=0):
 
 
 def prof_enable(on=True):
+    """Profiling brackets on / off; off -> on forgets the symbols recorded so far (prof_symbol)."""
     check(lib().mvdb_prof_enable(int(bool(on))))
 
 
@@ -813,7 +814,8 @@ def half_max_queries(d):
 
 
 def encoder_splitk_planes(tokens, n, k, compute_units=256):
-    """Planes a small batch's [tokens, n] = A [tokens, k] W^T GEMM of the encoder is split into over K (0: not split)."""
+    """Planes a small batch's [tokens, n] = A [tokens, k] W^T GEMM of the encoder is split into over K (0: not split); the
+    MVDB_GEMM_X3_SPLITK* switches are read at the call (an encoder reads them when it is created)."""
     return int(lib().mvdb_encoder_splitk_planes(int(tokens), int(n), int(k), int(compute_units)))
 
 

@@ -5,6 +5,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -69,6 +70,12 @@ int profiled_launch(const char* label, hipStream_t stream, Launch launch, Sym...
     prof_end(slot, stream);
     MVDB_HIP(hipGetLastError());
     return 0;
+}
+
+// The one reader of the integer MVDB_* switches (read_knobs here, read_encoder_knobs in encoder.hip): unset or empty is `dflt`.
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
 }
 
 // Every MVDB_* tuning / A-B hook of the SEARCH path.  The environment is read ONCE per index — at mvdb_index_create, and

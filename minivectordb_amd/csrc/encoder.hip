@@ -31,10 +31,12 @@
 
 #include <cerrno>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <map>
 #include <tuple>
+#include <utility>
 
 #include "common.hpp"
 
@@ -2424,6 +2426,61 @@ struct LayerW {
 constexpr int kSplitKMax = 8;
 inline int64_t x3_plane_floats(int cus) { return (int64_t)cus * 64 * 128 + 64 * 1024; }
 
+// Every MVDB_* tuning / A-B hook of the ENCODER: one line per switch — its name, its default, its spelling, its meaning.
+// read_encoder_knobs() reads the environment (constructing the table does); an encoder does so ONCE, at mvdb_encoder_create —
+// so that one process can hold encoders of several kinds — and never on a path a forward takes.  (Per process instead:
+// MVDB_WALK_LOCK and MVDB_WALK_LOCK_DIR, which belong to the per-device gate all encoders share, and the two switches of the
+// ablation build.)  Defaults are the measured best; the measurements stand with the rules that use them.
+// Three spellings beside env_int's, each switch keeping its own: on unless the value starts with 0; on for a leading 1 only;
+// atoi of whatever is set (set but empty: 0).
+inline const char* env_str(const char* name) { const char* v = getenv(name); return v ? v : ""; }
+inline bool env_not0(const char* name) { const char* v = getenv(name); return !(v && *v == '0'); }
+inline bool env_is1(const char* name) { const char* v = getenv(name); return v && *v == '1'; }
+inline int env_raw_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+struct EncoderKnobs {
+    // the exact-fp32 GEMMs (launch_gemm)
+    int gemm_big_tile_rounds = env_int("MVDB_GEMM_BIG_TILE_ROUNDS", 3);
+    bool gemm_big_bk32 = env_is1("MVDB_GEMM_BIG_BK32");
+    bool gemm_small_bk32 = env_not0("MVDB_GEMM_SMALL_BK32");
+    bool gemm_dma = env_not0("MVDB_GEMM_DMA");
+    // the split-precision GEMMs (x3_plan)
+    bool x3_spread_small = env_not0("MVDB_GEMM_X3_SPREAD_SMALL");  // the DMA instructions of the 64- / 128-row forms between the MFMAs (0: one burst)
+    bool x3_spread = env_not0("MVDB_GEMM_X3_SPREAD");              // the same for the persistent 256-row forms
+    bool x3_persist = env_not0("MVDB_GEMM_X3_PERSIST");            // 0: the 256-row forms as one workgroup per tile
+    bool x3_bn64 = env_not0("MVDB_GEMM_X3_BN64");                  // 0: no 64 x 64 tiles
+    int x3_bm128w4 = env_raw_int("MVDB_GEMM_X3_BM128W4", -1);      // -1: 128 x 128 tiles by the tile count; 1 always, 0 never (set: no 256-row forms)
+    int x3_many = env_int("MVDB_GEMM_X3_MANY", 2);                 // 128 x 128 tiles from this many tiles per CU
+    int x3_big = env_raw_int("MVDB_GEMM_X3_BIG", -1);              // -1: the 256-row forms by x3_big_form; 1 wherever N allows, 0 never
+    // ... with bias + residual + LayerNorm in the epilogue (launch_gemm_x3_ln)
+    int ln_fused = env_int("MVDB_GEMM_LN_FUSED", 1);               // 0 never, 1 by batch size, 2 always
+    bool ln_spread = env_not0("MVDB_GEMM_LN_SPREAD");
+    bool ln_persist = env_not0("MVDB_GEMM_LN_PERSIST");            // 0: one band per workgroup
+    int ln_bm = env_int("MVDB_GEMM_LN_BM", 0);                     // 32 | 64 | 128: rows per workgroup; otherwise by batch size
+    // ... split over K (x3_splitk_parts)
+    bool splitk = env_not0("MVDB_GEMM_X3_SPLITK");
+    bool splitk_wide = env_not0("MVDB_GEMM_X3_SPLITK_WIDE");       // 0: QKV / FFN1 of the wide shapes unsplit
+    int splitk_parts = env_int("MVDB_GEMM_X3_SPLITK_PARTS", 0);    // >= 2: that many planes
+    int splitk_minsteps = std::max(1, env_int("MVDB_GEMM_X3_SPLITK_MINSTEPS", 4));
+    // attention (launch_attention)
+    bool attn_valu = env_str("MVDB_ENCODER_ATTENTION")[0] == 'v';  // =valu: the thread-per-query VALU kernel (A/B reference)
+    bool attn_x3 = env_not0("MVDB_ATTENTION_X3");                  // 0: the fp32 MFMA kernel in the split-precision mode too
+    bool attn_img = env_not0("MVDB_ATTENTION_IMG");                // 0: fp32 qkv + attention_x3_kernel, which splits K / V per workgroup
+    bool attn_x3_short = env_not0("MVDB_ATTENTION_X3_SHORT");      // 0: no one-wave workgroups for S <= 32
+    int attn_x3_wide_from = env_int("MVDB_ATTENTION_X3_WIDE_FROM", 128);  // longer sequences run eight-wave workgroups
+    // the forward
+    int split = env_raw_int("MVDB_ENCODER_SPLIT", 1);              // 0: never two lanes
+    bool graph = env_not0("MVDB_ENCODER_GRAPH");                   // 0: plain launches
+    // the layer-walking launch
+    bool walk = env_not0("MVDB_ENCODER_WALK");                     // 0: the per-op kernels
+    bool walk_roles = env_not0("MVDB_WALK_ROLES");                 // 0: every phase based at workgroup 0, the form before role placement
+    bool walk_pinned = env_not0("MVDB_WALK_PINNED");               // 0: the host entry stages ids / mask / out through device buffers
+    int walk_planes = std::max(1, env_int("MVDB_WALK_PLANES", INT_MAX));  // A/B: most workgroups (= partial planes) of the FFN phase
+    int walk_grid = env_int("MVDB_WALK_GRID", 0);                  // A/B: workgroups of the launch (0: by shape, launch_walk)
+    // no wait of a launch outlasts this (default 20 ms >> the 0.25 - 2.4 ms of a forward, << anything a watchdog would notice)
+    long long walk_deadline_us = *env_str("MVDB_WALK_DEADLINE_US") ? atoll(env_str("MVDB_WALK_DEADLINE_US")) : 20000;
+};
+inline EncoderKnobs read_encoder_knobs() { return EncoderKnobs(); }
+
 struct GraphKey {
     int B, S, compute;
     const void *ids, *mask, *out;
@@ -2440,10 +2497,7 @@ struct mvdb_encoder {
         graphs.clear();
     }
     int device = 0;
-    // A/B switches, read from the environment when the encoder is created (so that one process can hold encoders of both
-    // kinds): MVDB_GEMM_LN_FUSED (0 never, 1 by batch size, 2 always), MVDB_ATTENTION_IMG (0: fp32 qkv + per-tile split)
-    int opt_ln_fused = 1;
-    bool opt_img_attn = true;
+    const EncoderKnobs kn = read_encoder_knobs();  // the switches as the environment had them when the encoder was created
     const float *word = nullptr, *pos = nullptr, *type = nullptr, *embg = nullptr, *embb = nullptr;
     std::vector<LayerW> layers;
     std::vector<float*> owned;  // fused qkv weights / biases
@@ -2481,9 +2535,6 @@ struct mvdb_encoder {
     int64_t stage_cap = 0, out_cap = 0;
     hipStream_t stream = nullptr;
     // small batches (<= walk::kTmax token slots): the layer-walking persistent launch (encoder_walk.hpp)
-    int opt_walk = 1;                       // MVDB_ENCODER_WALK as read when the encoder was created (0: the per-op kernels)
-    int opt_walk_roles = 1;                 // MVDB_WALK_ROLES (0: every phase based at workgroup 0, the form before role placement)
-    int opt_walk_pinned = 1;                // MVDB_WALK_PINNED (0: the host entry stages ids / mask / out through device buffers)
     walk::LayerPtrs* walk_layers = nullptr; // device copy of the per-layer weight pointers
     float *walk_x = nullptr, *walk_x1 = nullptr, *walk_qkv = nullptr, *walk_pl = nullptr, *walk_h = nullptr;
     unsigned int* walk_bar = nullptr;
@@ -2493,7 +2544,7 @@ struct mvdb_encoder {
     hipEvent_t walk_done = nullptr;            // recorded behind every forward of the device entry: the next one — on whatever
                                                // stream — waits for it (forwards share the staging buffers, the workspace and the
                                                // walking launch's phase counters: two resident walking grids would never finish)
-    int walk_np3 = 0, walk_grid = 0, walk_grid_env = 0;
+    int walk_np3 = 0, walk_grid = 0;
     // bounded waits (encoder_walk.hpp, Args::deadline): launches abandoned so far, on the device and mirrored into host-mapped
     // memory; calls still to be served by the per-op kernels after an abandoned launch (the GPU is being shared with
     // something that keeps the launch's workgroups from all being resident: do not pay the deadline on every call)
@@ -2584,163 +2635,211 @@ int ensure_ws(mvdb_encoder* e, int B, int S) {
     return 0;
 }
 
+// ---- the launch bracket of a forward ----------------------------------------------------------------------------------------
+// Every launch of a forward goes through enqueue(): while profiling is on it records, under the op's label (enc_pack, enc_embed,
+// enc_qkv[_epi], enc_attn, enc_ctx_split, enc_wo, enc_ln1, enc_ffn1[_epi], enc_ffn2, enc_ln2, enc_pool; <label>_fallback for
+// the second GEMM of a pair), WHICH instantiation ran on which grid — tests/test_encoder_launch_table_gpu.py pins them.  No
+// event pairs: a forward is captured into a graph.
+struct KernelName {
+    char s[96];
+};
+KernelName kname(const char* fmt, ...) {  // the instantiation as the source writes it; formatted only while profiling is on
+    KernelName n;
+    n.s[0] = 0;
+    if (!prof_enabled()) return n;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(n.s, sizeof(n.s), fmt, ap);
+    va_end(ap);
+    return n;
+}
+const char* epi_name(int epi) {
+    static const char* const names[] = {"EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RESIDUAL", "EPI_BIAS_QKV", "EPI_PARTIAL"};
+    return names[epi];
+}
+constexpr const char* bool_name(bool b) { return b ? "true" : "false"; }
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+template <typename... P, typename... A>
+void enqueue(const char* label, const KernelName& name, void (*kern)(P...), dim3 grid, int block, size_t lds, hipStream_t s, A... args) {
+    prof_symbol(label, "%s grid=(%u,%u,%u) block=%d lds=%d", name.s, grid.x, grid.y, grid.z, block, (int)lds);
+    hipLaunchKernelGGL(kern, grid, dim3(block), lds, s, static_cast<P>(args)...);
+}
+
+// One forward on one lane: what every launcher is called with, and the forms that are decided once per forward (enqueue_lane)
+struct LaneCall {
+    mvdb_encoder* e;
+    mvdb_encoder::Lane& w;
+    int B, S, compute;
+    hipStream_t s;
+    int64_t Tmax;     // padded token slots: all the host knows (Tptr: the packed count, on the device)
+    const int* Tptr;
+    float* xp;        // compute = 2: every GEMM input is a (hi | lo) fp16 image written by its producer — x by the LayerNorms (beside
+                      // the fp32 x the residuals and the pooling read), the context by the attention kernel, the GELU output by
+                      // FFN1's epilogue
+    int cus;
+    bool img_attn, ln_fused;
+    int qkv_parts, wo_parts, ffn1_parts, ffn2_parts;
+};
+// C[T][N] = epilogue(A[T][K] W[N][K]^T + bias (+ R)), in either mode: A / W in fp32, or (compute = 2) A's (hi | lo) image —
+// [T][K / 32][hi 32 | lo 32], the bytes of a [T][K] fp32 matrix — and Wp, W's, scaled by 1 / Wp_is
+struct Gemm {
+    const float *A, *W;
+    const _Float16* Wp;
+    float Wp_is;
+    const float *bias, *R;
+    float* C;
+    int N, K;
+    int qcols = 0;  // EPI_BIAS_QKV: the first qcols columns (Q) times qscale
+    float qscale = 1.f;
+};
+
+// ---- compute = 0: the exact-fp32 GEMMs ---------------------------------------------------------------------------------------
 template <int EPI>
-void launch_gemm(const float* A, const float* W, const float* bias, const float* R, float* C,
-                 const int* Tptr, int64_t Tmax, int N, int K, int cus, hipStream_t s) {
-    const int64_t big = (int64_t)((N + 127) / 128) * ((Tmax + 127) / 128);
+void launch_gemm(const char* label, const LaneCall& c, const Gemm& g) {
+    const EncoderKnobs& kn = c.e->kn;
+    const int N = g.N, K = g.K, cus = c.cus;
+    const int64_t Tmax = c.Tmax;
     // 128x128 tiles only when they fill the chip's resident slots (2 blocks per CU) several times over;
     // otherwise the last, partly filled round dominates (T = 8192: 576-768 tiles = 1.1-1.5 rounds) and
     // 64x64 tiles (4x the blocks) are faster despite their lower per-block reuse.
-    static const int rounds = []() {
-        const char* v = getenv("MVDB_GEMM_BIG_TILE_ROUNDS");
-        return v && *v ? atoi(v) : 3;
-    }();
-    static const bool big_bk32 = []() {
-        const char* v = getenv("MVDB_GEMM_BIG_BK32");
-        return v && *v == '1';
-    }();
-    static const bool small_bk32 = []() {
-        const char* v = getenv("MVDB_GEMM_SMALL_BK32");
-        return !(v && *v == '0');
-    }();
-    static const bool use_dma = []() {
-        const char* v = getenv("MVDB_GEMM_DMA");
-        return !(v && *v == '0');
-    }();
-    if (use_dma && K % 32 == 0 && big < (int64_t)rounds * 2 * cus) {
+    const bool big = (int64_t)((N + 127) / 128) * ((Tmax + 127) / 128) >= (int64_t)kn.gemm_big_tile_rounds * 2 * cus;
+    const dim3 grid = big ? dim3((N + 127) / 128, (unsigned)((Tmax + 127) / 128)) : dim3((N + 63) / 64, (unsigned)((Tmax + 63) / 64));
+    if (kn.gemm_dma && K % 32 == 0 && !big) {
         // 64x64 tiles, LDS-DMA staged, three 16-KiB stages: 3 blocks per CU — T = 8192: 9 / 12 / 3 tiles per CU for
         // N = 1152 / 1536 / 384, whole rounds in every GEMM (the register-staged kernel fits 4 blocks: 2.25 rounds
         // at N = 1152).  Measured 4.12 vs 4.26 ms per forward at B = 256, S = 32.  With 128x128 tiles (96 KiB of LDS,
         // one block per CU) it loses to the register-staged kernel (81 vs 67 ms at S = 512): not used there.
-        constexpr int lds = 3 * 128 * 128;
-        dim3 grid((N + 63) / 64, (unsigned)((Tmax + 63) / 64));
-        hipLaunchKernelGGL((gemm_f32_dma_kernel<EPI, 1>), grid, dim3(256), lds, s, A, W, bias, R, C, Tptr, N, K);
+        enqueue(label, kname("gemm_f32_dma_kernel<%s, 1>", epi_name(EPI)), gemm_f32_dma_kernel<EPI, 1>, grid, 256, 3 * 128 * 128, c.s, g.A,
+                g.W, g.bias, g.R, g.C, c.Tptr, N, K);
         return;
     }
-    if (big >= (int64_t)rounds * 2 * cus) {
-        dim3 grid((N + 127) / 128, (unsigned)((Tmax + 127) / 128));
-        if (K % 32 == 0 && big_bk32)
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<EPI, 2, 32>), grid, dim3(256), 0, s, A, W, bias, R, C, Tptr, N, K);
-        else
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<EPI, 2, 16>), grid, dim3(256), 0, s, A, W, bias, R, C, Tptr, N, K);
-    } else {
-        dim3 grid((N + 63) / 64, (unsigned)((Tmax + 63) / 64));
-        // 64x64 tiles do 8 MFMAs per wave and 16-deep step: step twice as deep to halve the barriers
-        if (K % 32 == 0 && small_bk32)
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<EPI, 1, 32>), grid, dim3(256), 0, s, A, W, bias, R, C, Tptr, N, K);
-        else
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<EPI, 1, 16>), grid, dim3(256), 0, s, A, W, bias, R, C, Tptr, N, K);
-    }
+    // 64x64 tiles do 8 MFMAs per wave and 16-deep step: step twice as deep to halve the barriers
+    const bool bk32 = K % 32 == 0 && (big ? kn.gemm_big_bk32 : kn.gemm_small_bk32);
+    auto kern = big ? (bk32 ? gemm_f32_mfma_kernel<EPI, 2, 32> : gemm_f32_mfma_kernel<EPI, 2, 16>)
+                    : (bk32 ? gemm_f32_mfma_kernel<EPI, 1, 32> : gemm_f32_mfma_kernel<EPI, 1, 16>);
+    enqueue(label, kname("gemm_f32_mfma_kernel<%s, %d, %d>", epi_name(EPI), big ? 2 : 1, bk32 ? 32 : 16), kern, grid, 256, 0, c.s, g.A, g.W,
+            g.bias, g.R, g.C, c.Tptr, N, K);
 }
 
-// compute = 2: LDS-DMA kernel, 64 x 128 tiles, three stages, two workgroups per CU — measured best at every shape
-// (B = 256: S = 32 2.68 ms vs 3.04 with 128-row tiles for the wide GEMMs, 3.15 register-staged; S = 512 43.8 ms vs
-// 55.7 / 45.3; rings of 2, 4 or 6 stages, i.e. 3 or 1 workgroups per CU: within 1 %)
-// Raises a kernel's dynamic-LDS limit once per (kernel, device).
-int x3_set_lds(const void* kern, int lds, int device) {
-    static std::mutex mu;
-    static std::map<std::pair<const void*, int>, int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    int& have = done[{kern, device}];
-    if (lds > have) {
-        MVDB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        have = lds;
-    }
-    return 0;
-}
-
+// ---- compute = 2: the split-precision GEMMs -----------------------------------------------------------------------------------
 // Timing ablations of the split-precision GEMMs (DBG template parameter: 1 no fragment reads / MFMAs, 2 no DMA, 3 no
 // epilogue, 4 no K loop; results invalid) exist only in builds with -DMVDB_X3_ABLATE (make ABLATE=1), selected at run time
 // by MVDB_GEMM_X3_DBG; the normal build instantiates the real kernels only.
 #ifdef MVDB_X3_ABLATE
+int x3_dbg() {
+    static const int dbg = []() { const char* v = getenv("MVDB_GEMM_X3_DBG"); return v ? atoi(v) : 0; }();
+    return dbg;
+}
 #define X3_KERN(...)                                                                                                  \
-    (dbg == 1 ? gemm_x3_dma_kernel<__VA_ARGS__, 1> : dbg == 2 ? gemm_x3_dma_kernel<__VA_ARGS__, 2> :                 \
-     dbg == 3 ? gemm_x3_dma_kernel<__VA_ARGS__, 3> : dbg == 4 ? gemm_x3_dma_kernel<__VA_ARGS__, 4> :                 \
-     dbg == 5 ? gemm_x3_dma_kernel<__VA_ARGS__, 5> : gemm_x3_dma_kernel<__VA_ARGS__, 0>)
+    (x3_dbg() == 1 ? gemm_x3_dma_kernel<__VA_ARGS__, 1> : x3_dbg() == 2 ? gemm_x3_dma_kernel<__VA_ARGS__, 2> :       \
+     x3_dbg() == 3 ? gemm_x3_dma_kernel<__VA_ARGS__, 3> : x3_dbg() == 4 ? gemm_x3_dma_kernel<__VA_ARGS__, 4> :       \
+     x3_dbg() == 5 ? gemm_x3_dma_kernel<__VA_ARGS__, 5> : gemm_x3_dma_kernel<__VA_ARGS__, 0>)
 #define X3_BIG_KERN(...)                                                                                              \
-    (dbg == 1 ? gemm_x3_big_kernel<__VA_ARGS__, 1> : dbg == 2 ? gemm_x3_big_kernel<__VA_ARGS__, 2> :                 \
-     dbg == 7 ? gemm_x3_big_kernel<__VA_ARGS__, 7> :                                                                  \
-     dbg == 3 ? gemm_x3_big_kernel<__VA_ARGS__, 3> : dbg == 4 ? gemm_x3_big_kernel<__VA_ARGS__, 4> :                 \
-     dbg == 5 ? gemm_x3_big_kernel<__VA_ARGS__, 5> : dbg == 6 ? gemm_x3_big_kernel<__VA_ARGS__, 6> : gemm_x3_big_kernel<__VA_ARGS__, 0>)
+    (x3_dbg() == 1 ? gemm_x3_big_kernel<__VA_ARGS__, 1> : x3_dbg() == 2 ? gemm_x3_big_kernel<__VA_ARGS__, 2> :       \
+     x3_dbg() == 7 ? gemm_x3_big_kernel<__VA_ARGS__, 7> :                                                             \
+     x3_dbg() == 3 ? gemm_x3_big_kernel<__VA_ARGS__, 3> : x3_dbg() == 4 ? gemm_x3_big_kernel<__VA_ARGS__, 4> :       \
+     x3_dbg() == 5 ? gemm_x3_big_kernel<__VA_ARGS__, 5> : x3_dbg() == 6 ? gemm_x3_big_kernel<__VA_ARGS__, 6> : gemm_x3_big_kernel<__VA_ARGS__, 0>)
 #define X3_LN_KERN(...)                                                                                               \
-    (dbg == 1 ? gemm_x3_ln_kernel<__VA_ARGS__, 1> : dbg == 2 ? gemm_x3_ln_kernel<__VA_ARGS__, 2> :                   \
-     dbg == 3 ? gemm_x3_ln_kernel<__VA_ARGS__, 3> : dbg == 4 ? gemm_x3_ln_kernel<__VA_ARGS__, 4> : gemm_x3_ln_kernel<__VA_ARGS__, 0>)
+    (x3_dbg() == 1 ? gemm_x3_ln_kernel<__VA_ARGS__, 1> : x3_dbg() == 2 ? gemm_x3_ln_kernel<__VA_ARGS__, 2> :         \
+     x3_dbg() == 3 ? gemm_x3_ln_kernel<__VA_ARGS__, 3> : x3_dbg() == 4 ? gemm_x3_ln_kernel<__VA_ARGS__, 4> : gemm_x3_ln_kernel<__VA_ARGS__, 0>)
 #else
+constexpr int x3_dbg() { return 0; }
 #define X3_KERN(...) gemm_x3_dma_kernel<__VA_ARGS__, 0>
 #define X3_BIG_KERN(...) gemm_x3_big_kernel<__VA_ARGS__, 0>
 #define X3_LN_KERN(...) gemm_x3_ln_kernel<__VA_ARGS__, 0>
 #endif
 
-template <int EPI>
-int launch_gemm_x3(const float* Aimg, const _Float16* Wp, float inv_wscale, const float* bias, const float* R, float* C,
-                   const int* Tptr, int64_t Tmax, int N, int K, int device, hipStream_t s, int qcols = 0, float qscale = 1.f) {
-    const _Float16* A = reinterpret_cast<const _Float16*>(Aimg);  // [T][K / 32][hi 32 | lo 32]: the bytes of a [T][K] fp32 matrix
-    static const int dbg = []() { const char* v = getenv("MVDB_GEMM_X3_DBG"); return v ? atoi(v) : 0; }();
-    (void)dbg;
-    static const bool spread_small = []() { const char* v = getenv("MVDB_GEMM_X3_SPREAD_SMALL"); return !(v && *v == '0'); }();
-    auto kern = spread_small ? X3_KERN(EPI, 64, 3, 4, 128, 1) : X3_KERN(EPI, 64, 3, 4, 128, 0);
-    constexpr int lds = 3 * (64 * 128 + 128 * 128);
-    MVDB_TRY(x3_set_lds((const void*)kern, lds, device));
-    dim3 grid((N + 127) / 128, (unsigned)((Tmax + 63) / 64));
-    // Enough 128 x 128 tiles to fill every resident slot (two workgroups per CU) at least once: 128 x 128 tiles on FOUR
-    // waves — wave tile 64 x 64, 8 fragment reads per 12 MFMAs where the 32 x 64 wave tile of the default needs 12, and a
-    // third less L2 -> LDS traffic per output —, two stages (64 KiB), two workgroups per CU.  e5-small, S = 512: 29.3 ms
-    // per forward vs 33.1 with the default tiles and 32.2 with 128 x 128 tiles on eight waves of 32 x 64
-    // (MVDB_GEMM_X3_W8=1).  The threshold (MVDB_GEMM_X3_MANY, in units of the CU count, counted on the padded batch):
-    // at 2 an e5-large-shaped forward (H = 1024, 24 layers) of 256 x 32 tokens takes 16.7 ms against 18.3 at 8, 17.4 at 3
-    // (ragged: 12.9 / 12.9 / 12.5); e5-small at T = 8192 — QKV and FFN1 qualify, 1.1 / 1.5 rounds — is within the
-    // run-to-run spread either way (1.97 vs 1.99 ms, ragged 1.64 vs 1.62).  Forcing them onto the N = 384 GEMMs as well
-    // (192 tiles) costs a ragged batch 30 %.
-    static const int big4env = []() { const char* v = getenv("MVDB_GEMM_X3_BM128W4"); return v ? atoi(v) : -1; }();
-    static const bool w8 = []() { const char* v = getenv("MVDB_GEMM_X3_W8"); return v && *v == '1'; }();
-    static const int many_x = []() { const char* v = getenv("MVDB_GEMM_X3_MANY"); return v && *v ? atoi(v) : 2; }();
-    const bool many = (int64_t)((N + 127) / 128) * ((Tmax + 127) / 128) >= (int64_t)many_x * device_cus(device);
+// The forms of gemm_x3_dma_kernel / gemm_x3_big_kernel a GEMM can run on (tile rows x columns, stages of the ring, waves):
+enum X3Form {
+    X3_DEFAULT,      // 64 x 128, 3 stages, 4 waves, two workgroups per CU — measured best at every shape before the forms below
+                     // (B = 256: S = 32 2.68 ms vs 3.04 with 128-row tiles for the wide GEMMs, 3.15 register-staged; S = 512
+                     // 43.8 ms vs 55.7 / 45.3; rings of 2, 4 or 6 stages, i.e. 3 or 1 workgroups per CU: within 1 %)
+    X3_FEW_TILES,    // 64 x 64, 3 stages, 4 waves
+    X3_MANY_TILES,   // 128 x 128, 2 stages (64 KiB), 4 waves: wave tile 64 x 64, two workgroups per CU
+    X3_PERSIST_256,  // 256 x 256, one persistent eight-wave workgroup per CU walking the tile list (gemm_x3_big_kernel)
+    X3_PERSIST_192,  // 256 x 192, the same
+    X3_TILE_256,     // 256 x 256, 2 stages, 8 waves, one tile per workgroup
+    X3_TILE_192,     // 256 x 192, the same
+};
+template <int BM_, int NST_, int WAVES_, int BN_, int SPREAD_, bool PERSISTENT_ = false>
+struct X3Shape {
+    static constexpr int BM = BM_, NST = NST_, WAVES = WAVES_, BN = BN_, SPREAD = SPREAD_;
+    static constexpr bool PERSISTENT = PERSISTENT_;
+    static constexpr int lds = NST * (BM + BN) * 128, threads = WAVES * 64;
+};
+// The one table of the instantiated forms: launch(X3Shape<...>{}) for `form`; spread: the DMA instructions issued between the
+// MFMAs (the forms that have both variants)
+template <typename Launch>
+int with_x3_form(X3Form form, bool spread, Launch launch) {
+    switch (form) {
+        case X3_DEFAULT: return spread ? launch(X3Shape<64, 3, 4, 128, 1>{}) : launch(X3Shape<64, 3, 4, 128, 0>{});
+        case X3_FEW_TILES: return launch(X3Shape<64, 3, 4, 64, 1>{});
+        case X3_MANY_TILES: return spread ? launch(X3Shape<128, 2, 4, 128, 1>{}) : launch(X3Shape<128, 2, 4, 128, 0>{});
+        case X3_PERSIST_256: return spread ? launch(X3Shape<256, 2, 8, 256, 1, true>{}) : launch(X3Shape<256, 2, 8, 256, 0, true>{});
+        case X3_PERSIST_192: return spread ? launch(X3Shape<256, 2, 8, 192, 1, true>{}) : launch(X3Shape<256, 2, 8, 192, 0, true>{});
+        case X3_TILE_256: return launch(X3Shape<256, 2, 8, 256, 0>{});
+        case X3_TILE_192: return launch(X3Shape<256, 2, 8, 192, 0>{});
+    }
+    return fail(MVDB_ERR_ARG, "internal: no split-precision GEMM form %d", (int)form);
+}
+
+// One launch of a split-precision GEMM: everything a launch needs follows from the shape's type.  sel_bn != 0: one of a pair,
+// the kernel decides from the packed token count whether it does the work (x3_big_form).
+template <int EPI, typename Shape>
+int launch_x3(const char* label, const LaneCall& c, Shape, dim3 grid, int sel_bn, const Gemm& g) {
+    auto kern = []() {
+        if constexpr (Shape::PERSISTENT) return X3_BIG_KERN(EPI, Shape::BN, Shape::SPREAD);
+        else return X3_KERN(EPI, Shape::BM, Shape::NST, Shape::WAVES, Shape::BN, Shape::SPREAD);
+    }();
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, Shape::lds, c.e->device));
+    if (Shape::PERSISTENT)
+        prof_symbol(label, "gemm_x3_big_kernel<%s, %d, %d, %d> grid=(%u,%u,%u) block=%d lds=%d sel=%d", epi_name(EPI), Shape::BN, Shape::SPREAD,
+                    x3_dbg(), grid.x, grid.y, grid.z, Shape::threads, Shape::lds, sel_bn);
+    else
+        prof_symbol(label, "gemm_x3_dma_kernel<%s, %d, %d, %d, %d, %d, %d> grid=(%u,%u,%u) block=%d lds=%d sel=%d", epi_name(EPI), Shape::BM,
+                    Shape::NST, Shape::WAVES, Shape::BN, Shape::SPREAD, x3_dbg(), grid.x, grid.y, grid.z, Shape::threads, Shape::lds, sel_bn);
+    hipLaunchKernelGGL(kern, grid, dim3(Shape::threads), Shape::lds, c.s, reinterpret_cast<const _Float16*>(g.A), g.Wp, g.Wp_is, g.bias, g.R,
+                       g.C, c.Tptr, g.N, g.K, sel_bn, c.cus, g.qcols, g.qscale);
+    return 0;
+}
+
+// The rule: which form(s) a [Tmax, N] GEMM runs on — one launch, or the 256-row form and its fallback as a pair (the padded
+// batch could qualify; the packed token count, known only on the device, decides which of the two does the work).
+struct X3Launch {
+    X3Form form;
+    bool spread;
+    dim3 grid;
+    int sel_bn;
+};
+struct X3Plan {
+    int n = 0;
+    X3Launch launch[2];
+    void add(X3Form form, bool spread, dim3 grid, int sel_bn) { launch[n++] = X3Launch{form, spread, grid, sel_bn}; }
+};
+X3Plan x3_plan(int64_t Tmax, int N, int cus, const EncoderKnobs& kn) {
+    X3Plan plan;
     // N a multiple of 256 and whole rounds of 256 x 256 tiles: ONE workgroup of eight waves per CU on a 256 x 256 tile (wave
     // tile 64 x 128: 24 fragment reads per 48 MFMAs; two 64-KiB stages) — half the L2 -> LDS bytes per output of two
     // 128 x 128 workgroups.  PMC on the e5-large shape at 256 x 512 tokens: matrix cores 61 % busy in the QKV GEMM, 60 %
     // in the N = 1024 ones, 53 % in FFN1 (GELU epilogue).  Forward of that shape (24 layers): 294.9 -> 265.2 ms (ragged
     // 189.4 -> 177.9), S = 256 137.0 -> 122.9, S = 128 66.8 -> 60.2 (ragged 45.0 -> 46.4), S = 64 33.7 -> 29.8; at S = 32 its
     // 384 / 128 tiles per GEMM are 1.5 / 0.5 rounds of the 256 CUs and it loses (16.6 -> 17.9 ms, ragged 12.9 -> 16.8) — hence
-    // the rule: at least one round, and either >= 4 rounds or a last round that is >= 85 % full (counted on the padded
-    // batch).  MVDB_GEMM_X3_BIG: 1 forces it wherever N % 256 == 0 or N % 192 == 0, 0 disables it.
-    static const int big8env = []() { const char* v = getenv("MVDB_GEMM_X3_BIG"); return v ? atoi(v) : -1; }();
-    // N % 256 != 0 but N % 192 == 0 (every GEMM of a 384-wide model): the same form on 256 x 192 tiles (wave tile 64 x 96)
+    // the rule (x3_big_form): at least one round, and either >= 4 rounds or a last round that is >= 85 % full (counted on the
+    // padded batch).  MVDB_GEMM_X3_BIG: 1 forces it wherever N % 256 == 0 or N % 192 == 0 — one launch, no fallback —, 0 disables it.
+    // N % 256 != 0 but N % 192 == 0 (every GEMM of a 384-wide model): the same form on 256 x 192 tiles (wave tile 64 x 96).
+    // By default one persistent workgroup per CU walks the tile list; MVDB_GEMM_X3_PERSIST=0: one workgroup per tile.
     const int bign = N % 256 == 0 ? 256 : N % 192 == 0 ? 192 : 0;
-    const int cus = device_cus(device);
-    // forced (1): unconditional; default: launched as a pair with the fallback below when the padded batch could qualify
-    const bool big_pair = bign != 0 && big8env < 0 && x3_big_form(Tmax, N, bign, cus);
     int sel_bn = 0;  // the fallback's selector
-    if (!w8 && big4env < 0 && bign != 0 && (big8env == 1 || big_pair)) {
-        const dim3 gridb(N / bign, (unsigned)((Tmax + 255) / 256));
-        const int sel_big = big8env == 1 ? 0 : bign;
-        // one persistent workgroup per CU walking the tile list (gemm_x3_big_kernel); MVDB_GEMM_X3_PERSIST=0: one workgroup per tile
-        static const bool persist = []() { const char* v = getenv("MVDB_GEMM_X3_PERSIST"); return !(v && *v == '0'); }();
-        if (persist) {
-            const unsigned gp = (unsigned)std::min<int64_t>((int64_t)gridb.x * gridb.y, cus);
-            static const bool spread = []() { const char* v = getenv("MVDB_GEMM_X3_SPREAD"); return !(v && *v == '0'); }();
-            if (bign == 256) {
-                auto kernp = spread ? X3_BIG_KERN(EPI, 256, 1) : X3_BIG_KERN(EPI, 256, 0);
-                constexpr int ldsp = 2 * (256 * 128 + 256 * 128);
-                MVDB_TRY(x3_set_lds((const void*)kernp, ldsp, device));
-                hipLaunchKernelGGL(kernp, dim3(gp), dim3(512), ldsp, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_big, cus, qcols, qscale);
-            } else {
-                auto kernp = spread ? X3_BIG_KERN(EPI, 192, 1) : X3_BIG_KERN(EPI, 192, 0);
-                constexpr int ldsp = 2 * (256 * 128 + 192 * 128);
-                MVDB_TRY(x3_set_lds((const void*)kernp, ldsp, device));
-                hipLaunchKernelGGL(kernp, dim3(gp), dim3(512), ldsp, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_big, cus, qcols, qscale);
-            }
-        } else if (bign == 256) {
-            auto kernb = X3_KERN(EPI, 256, 2, 8, 256, 0);
-            constexpr int ldsb = 2 * (256 * 128 + 256 * 128);
-            MVDB_TRY(x3_set_lds((const void*)kernb, ldsb, device));
-            hipLaunchKernelGGL(kernb, gridb, dim3(512), ldsb, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_big, cus, qcols, qscale);
-        } else {
-            auto kernc = X3_KERN(EPI, 256, 2, 8, 192, 0);
-            constexpr int ldsc = 2 * (256 * 128 + 192 * 128);
-            MVDB_TRY(x3_set_lds((const void*)kernc, ldsc, device));
-            hipLaunchKernelGGL(kernc, gridb, dim3(512), ldsc, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_big, cus, qcols, qscale);
-        }
-        if (big8env == 1) return 0;
+    if (kn.x3_bm128w4 < 0 && bign != 0 && (kn.x3_big == 1 || (kn.x3_big < 0 && x3_big_form(Tmax, N, bign, cus)))) {
+        const dim3 tiles(N / bign, (unsigned)((Tmax + 255) / 256));
+        const int sel_big = kn.x3_big == 1 ? 0 : bign;
+        if (kn.x3_persist)
+            plan.add(bign == 256 ? X3_PERSIST_256 : X3_PERSIST_192, kn.x3_spread, dim3((unsigned)std::min<int64_t>((int64_t)tiles.x * tiles.y, cus)), sel_big);
+        else
+            plan.add(bign == 256 ? X3_TILE_256 : X3_TILE_192, false, tiles, sel_big);
+        if (kn.x3_big == 1) return plan;
         sel_bn = -bign;  // the fallback runs only where the packed token count rules the 256-row form out
     }
     // (Tried in round 3 and dropped: the persistent eight-wave kernel on 128 x 192 / 128 x 256 tiles (wave tile 32 x 96 / 32 x 128) for
@@ -2748,35 +2847,41 @@ int launch_gemm_x3(const float* Aimg, const _Float16* Wp, float inv_wscale, cons
     // (Tried in round 3 and dropped: 128 x 192 tiles on four waves, two 40-KiB stages, TWO workgroups per CU so that one
     // workgroup's stores run under the other's K loop — S = 512 forward 26.7 ms vs 25.9 with the 256-row forms, S = 32 2.01
     // vs 1.96: the epilogue is not what the 256-row forms wait for.)
-    if (!w8 && (big4env >= 0 ? big4env == 1 : many)) {
-        auto kern4 = spread_small ? X3_KERN(EPI, 128, 2, 4, 128, 1) : X3_KERN(EPI, 128, 2, 4, 128, 0);
-        constexpr int lds4 = 2 * (128 * 128 + 128 * 128);
-        MVDB_TRY(x3_set_lds((const void*)kern4, lds4, device));
-        dim3 grid4((N + 127) / 128, (unsigned)((Tmax + 127) / 128));
-        hipLaunchKernelGGL(kern4, grid4, dim3(256), lds4, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_bn, cus, qcols, qscale);
-        return 0;
-    }
-    if (w8) {
-        auto kern8 = X3_KERN(EPI, 128, 3, 8, 128, 0);
-        constexpr int lds8 = 3 * (128 * 128 + 128 * 128);
-        MVDB_TRY(x3_set_lds((const void*)kern8, lds8, device));
-        dim3 grid8((N + 127) / 128, (unsigned)((Tmax + 127) / 128));
-        hipLaunchKernelGGL(kern8, grid8, dim3(512), lds8, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_bn, cus, qcols, qscale);
-        return 0;
+    // (Tried and dropped: 128 x 128 tiles on eight waves of 32 x 64, three stages — e5-small, S = 512: 32.2 ms vs 29.3 on four waves.)
+    // Enough 128 x 128 tiles to fill every resident slot (two workgroups per CU) at least once: 128 x 128 tiles on FOUR
+    // waves — wave tile 64 x 64, 8 fragment reads per 12 MFMAs where the 32 x 64 wave tile of the default needs 12, and a
+    // third less L2 -> LDS traffic per output —, two stages (64 KiB), two workgroups per CU.  e5-small, S = 512: 29.3 ms
+    // per forward vs 33.1 with the default tiles.  The threshold (MVDB_GEMM_X3_MANY, in units of the CU count, counted on the
+    // padded batch): at 2 an e5-large-shaped forward (H = 1024, 24 layers) of 256 x 32 tokens takes 16.7 ms against 18.3 at 8,
+    // 17.4 at 3 (ragged: 12.9 / 12.9 / 12.5); e5-small at T = 8192 — QKV and FFN1 qualify, 1.1 / 1.5 rounds — is within the
+    // run-to-run spread either way (1.97 vs 1.99 ms, ragged 1.64 vs 1.62).  Forcing them onto the N = 384 GEMMs as well
+    // (192 tiles) costs a ragged batch 30 %.
+    const dim3 tiles128((N + 127) / 128, (unsigned)((Tmax + 127) / 128));
+    if (kn.x3_bm128w4 >= 0 ? kn.x3_bm128w4 == 1 : (int64_t)tiles128.x * tiles128.y >= (int64_t)kn.x3_many * cus) {
+        plan.add(X3_MANY_TILES, kn.x3_spread_small, tiles128, sel_bn);
+        return plan;
     }
     // Few tiles (one long sentence, a handful of short ones): 64 x 64 tiles, twice the workgroups — a K-step of a 64 x 128 tile is
     // 12 MFMAs per wave (~0.33 us), and with a quarter of the CUs busy that, not the memory system, is what the GEMM takes
-    static const bool bn64 = []() { const char* v = getenv("MVDB_GEMM_X3_BN64"); return !(v && *v == '0'); }();
     // (one workgroup per CU at most; up to 1.5 / 2 per CU measured: +-2 %, benchmarks/mid_batch_probe.py)
-    if (bn64 && sel_bn == 0 && N % 64 == 0 && (int64_t)grid.x * grid.y * 2 <= cus) {
-        auto kern64 = X3_KERN(EPI, 64, 3, 4, 64, 1);
-        constexpr int lds64 = 3 * (64 * 128 + 64 * 128);
-        MVDB_TRY(x3_set_lds((const void*)kern64, lds64, device));
-        dim3 grid64(N / 64, (unsigned)((Tmax + 63) / 64));
-        hipLaunchKernelGGL(kern64, grid64, dim3(256), lds64, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, 0, cus, qcols, qscale);
-        return 0;
+    const dim3 tiles((N + 127) / 128, (unsigned)((Tmax + 63) / 64));
+    if (kn.x3_bn64 && sel_bn == 0 && N % 64 == 0 && (int64_t)tiles.x * tiles.y * 2 <= cus)
+        plan.add(X3_FEW_TILES, true, dim3(N / 64, tiles.y), 0);
+    else
+        plan.add(X3_DEFAULT, kn.x3_spread_small, tiles, sel_bn);
+    return plan;
+}
+
+// C = epilogue(A W^T): the launch(es) of x3_plan; the fallback of a pair is recorded under <label>_fallback
+template <int EPI>
+int launch_gemm_x3(const char* label, const LaneCall& c, const Gemm& g) {
+    const X3Plan plan = x3_plan(c.Tmax, g.N, c.cus, c.e->kn);
+    char fallback[48];
+    snprintf(fallback, sizeof(fallback), "%s_fallback", label);
+    for (int i = 0; i < plan.n; ++i) {
+        const X3Launch& l = plan.launch[i];
+        MVDB_TRY(with_x3_form(l.form, l.spread, [&](auto shape) { return launch_x3<EPI>(i ? fallback : label, c, shape, l.grid, l.sel_bn, g); }));
     }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, A, Wp, inv_wscale, bias, R, C, Tptr, N, K, sel_bn, cus, qcols, qscale);
     return 0;
 }
 
@@ -2784,59 +2889,48 @@ int launch_gemm_x3(const float* Aimg, const _Float16* Wp, float inv_wscale, cons
 bool x3_ln_fusable(int H) { return H % 128 == 0 && H <= 512; }
 
 template <int BM, int WM, int TN>
-int launch_gemm_x3_ln_inst(const _Float16* A, const _Float16* Wp, float inv_wscale, const float* bias, const float* gamma,
-                           const float* beta, float eps, float* X, float* Xp, const int* Tptr, int64_t Tmax, int K, int device,
-                           hipStream_t s) {
+int launch_gemm_x3_ln_inst(const char* label, const LaneCall& c, const Gemm& g, const float* gamma, const float* beta) {
+    const EncoderKnobs& kn = c.e->kn;
     constexpr int kStage = (BM + 128 * TN) * 128;
     constexpr int NST = 3 * kStage <= 160 * 1024 ? 3 : 2;
     static_assert(2 * kStage <= 160 * 1024, "two stages must fit the CU's LDS");
-    static const int dbg = []() { const char* v = getenv("MVDB_GEMM_X3_DBG"); return v ? atoi(v) : 0; }();
-    (void)dbg;
-    static const bool spread = []() { const char* v = getenv("MVDB_GEMM_LN_SPREAD"); return !(v && *v == '0'); }();
-    auto kern = spread ? X3_LN_KERN(BM, WM, TN, NST, 1) : X3_LN_KERN(BM, WM, TN, NST, 0);
+    auto kern = kn.ln_spread ? X3_LN_KERN(BM, WM, TN, NST, 1) : X3_LN_KERN(BM, WM, TN, NST, 0);
     constexpr int lds = NST * kStage + 2 * 4 * BM * 4;  // the ring + the row statistics
     static_assert(lds <= 160 * 1024, "LDS budget of a CU");
-    MVDB_TRY(x3_set_lds((const void*)kern, lds, device));
-    // two-stage forms: persistent, one workgroup per CU (a multiple of the row bands would leave a last round part full anyway)
-    const int64_t bands = (Tmax + BM - 1) / BM;
-    static const bool persist = []() { const char* v = getenv("MVDB_GEMM_LN_PERSIST"); return !(v && *v == '0'); }();  // 0: one band per workgroup (A/B)
-    const unsigned grid = (unsigned)(NST == 2 && persist ? std::min<int64_t>(bands, device_cus(device)) : bands);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * 256), lds, s, A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, K);
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, c.e->device));
+    // two-stage forms: persistent, one workgroup per CU (a multiple of the row bands would leave a last round part full anyway);
+    // MVDB_GEMM_LN_PERSIST=0: one band per workgroup (A/B)
+    const int64_t bands = (c.Tmax + BM - 1) / BM;
+    const unsigned grid = (unsigned)(NST == 2 && kn.ln_persist ? std::min<int64_t>(bands, c.cus) : bands);
+    enqueue(label, kname("gemm_x3_ln_kernel<%d, %d, %d, %d, %d, %d>", BM, WM, TN, NST, (int)kn.ln_spread, x3_dbg()), kern, dim3(grid), WM * 256,
+            lds, c.s, reinterpret_cast<const _Float16*>(g.A), g.Wp, g.Wp_is, g.bias, gamma, beta, c.e->cfg.ln_eps, c.w.x, c.xp, c.Tptr, g.K);
     return 0;
 }
 
-template <int TN>
-int launch_gemm_x3_ln_tn(int bm, const _Float16* A, const _Float16* Wp, float inv_wscale, const float* bias, const float* gamma,
-                         const float* beta, float eps, float* X, float* Xp, const int* Tptr, int64_t Tmax, int K, int device,
-                         hipStream_t s) {
-    // (H = 512 at 128 rows: two 80-KiB stages are the whole LDS, no room for the row statistics behind them: 64 rows there)
-    if constexpr (TN < 4)
-        if (bm == 128) return launch_gemm_x3_ln_inst<128, 2, TN>(A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-    if (bm == 128) bm = 64;
-    if (bm == 64) return launch_gemm_x3_ln_inst<64, 2, TN>(A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-    return launch_gemm_x3_ln_inst<32, 1, TN>(A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-}
-
-// X (in: the residual rows; out: LayerNorm(A W^T + bias + X), fp32) and Xp (out: its (hi | lo) image); N = H = 128 TN.
+// x (in: the residual rows; out: LayerNorm(A W^T + bias + x), fp32) and xp (out: its (hi | lo) image); N = H = 128 TN.
 // Rows per workgroup: the largest of 128 / 64 / 32 that still gives every CU a workgroup (counted on the padded batch) —
 // a workgroup streams ALL of W whatever its height, so taller tiles mean less L2 -> LDS traffic per output row, but at
 // T = 8192 only 32-row tiles reach all 256 CUs.  MVDB_GEMM_LN_BM overrides.
-int launch_gemm_x3_ln(const float* Aimg, const _Float16* Wp, float inv_wscale, const float* bias, const float* gamma,
-                      const float* beta, float eps, float* X, float* Xp, const int* Tptr, int64_t Tmax, int H, int K, int device,
-                      hipStream_t s) {
-    const _Float16* A = reinterpret_cast<const _Float16*>(Aimg);
-    static const int bm_env = []() { const char* v = getenv("MVDB_GEMM_LN_BM"); return v && *v ? atoi(v) : 0; }();
-    const int cus = device_cus(device);
-    int bm = (Tmax + 127) / 128 >= cus ? 128 : (Tmax + 63) / 64 >= cus ? 64 : 32;
-    if (bm_env == 32 || bm_env == 64 || bm_env == 128) bm = bm_env;
-    switch (H / 128) {
-        case 1: return launch_gemm_x3_ln_tn<1>(bm, A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-        case 2: return launch_gemm_x3_ln_tn<2>(bm, A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-        case 3: return launch_gemm_x3_ln_tn<3>(bm, A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-        case 4: return launch_gemm_x3_ln_tn<4>(bm, A, Wp, inv_wscale, bias, gamma, beta, eps, X, Xp, Tptr, Tmax, K, device, s);
-        default: return fail(MVDB_ERR_ARG, "no LayerNorm-fused GEMM for H = %d", H);
+int launch_gemm_x3_ln(const char* label, const LaneCall& c, const Gemm& g, const float* gamma, const float* beta) {
+    const int ln_bm = c.e->kn.ln_bm;
+    const int bm = ln_bm == 32 || ln_bm == 64 || ln_bm == 128 ? ln_bm : (c.Tmax + 127) / 128 >= c.cus ? 128 : (c.Tmax + 63) / 64 >= c.cus ? 64 : 32;
+    auto with_tn = [&](auto tn) {
+        constexpr int TN = decltype(tn)::value;
+        auto inst = [&](auto bmc, auto wm) { return launch_gemm_x3_ln_inst<decltype(bmc)::value, decltype(wm)::value, TN>(label, c, g, gamma, beta); };
+        // (H = 512 at 128 rows: two 80-KiB stages are the whole LDS, no room for the row statistics behind them: 64 rows there)
+        if constexpr (TN < 4)
+            if (bm == 128) return inst(Int<128>{}, Int<2>{});
+        return bm >= 64 ? inst(Int<64>{}, Int<2>{}) : inst(Int<32>{}, Int<1>{});
+    };
+    switch (g.N / 128) {
+        case 1: return with_tn(Int<1>{});
+        case 2: return with_tn(Int<2>{});
+        case 3: return with_tn(Int<3>{});
+        case 4: return with_tn(Int<4>{});
+        default: return fail(MVDB_ERR_ARG, "no LayerNorm-fused GEMM for H = %d", g.N);
     }
 }
+
 
 // one tensor: max|w| -> power-of-two scale with max|w| * scale in [2^13, 2^14) -> interleaved (hi | lo) fp16 pieces
 int make_interleaved(mvdb_encoder* e, const float* src, int64_t n, _Float16** out, float* inv_scale, unsigned int* scratch,
@@ -2896,90 +2990,97 @@ int ensure_x3_weights(mvdb_encoder* e, hipStream_t s) {
 // sentence (profiles/r06_long_sentence_chain.txt): e5-small 256 tokens 0.71 -> 0.65 ms, large 129 tokens 2.22 -> 2.02; batches
 // of 32 - 64 short sentences (benchmarks/mid_batch_probe.py): e5-small 64 x 32 tokens 0.92 -> 0.78 ms, large 32 x 32 3.93 -> 3.20.
 // MVDB_GEMM_X3_SPLITK_PARTS=3 forces three planes (A/B), MVDB_GEMM_X3_SPLITK=0 switches the split off.
-int x3_splitk_parts(int64_t Tmax, int N, int K, int cus) {
-    static const bool on = []() { const char* v = getenv("MVDB_GEMM_X3_SPLITK"); return !(v && *v == '0'); }();
-    static const int forced = []() { const char* v = getenv("MVDB_GEMM_X3_SPLITK_PARTS"); return v && *v ? atoi(v) : 0; }();
-    static const int min_steps = []() { const char* v = getenv("MVDB_GEMM_X3_SPLITK_MINSTEPS"); return v && *v ? std::max(1, atoi(v)) : 4; }();
-    if (!on) return 0;
+int x3_splitk_parts(int64_t Tmax, int N, int K, int cus, const EncoderKnobs& kn) {
+    if (!kn.splitk) return 0;
     const int64_t tiles = ((Tmax + 63) / 64) * ((N + 127) / 128);
-    int64_t parts = std::min<int64_t>({(int64_t)kSplitKMax, (int64_t)(K / 32 / min_steps), (int64_t)cus / std::max<int64_t>(tiles, 1)});
-    if (forced >= 2) parts = std::min<int64_t>({(int64_t)forced, (int64_t)kSplitKMax, (int64_t)(K / 32)});
+    int64_t parts = std::min<int64_t>({(int64_t)kSplitKMax, (int64_t)(K / 32 / kn.splitk_minsteps), (int64_t)cus / std::max<int64_t>(tiles, 1)});
+    if (kn.splitk_parts >= 2) parts = std::min<int64_t>({(int64_t)kn.splitk_parts, (int64_t)kSplitKMax, (int64_t)(K / 32)});
     if (parts < 2 || parts * Tmax * N > x3_plane_floats(cus)) return 0;
     return parts == 5 ? 4 : parts == 7 ? 6 : (int)parts;
 }
+// ... worth its extra launch (~5 us) for QKV / FFN1 where the GEMM walks many K-steps: K >= 768 (the wide shapes) and three planes or more
+int x3_splitk_parts_wide(int64_t Tmax, int N, int K, int cus, const EncoderKnobs& kn) {
+    if (!kn.splitk_wide || K < 768 || N % 64) return 0;
+    const int parts = x3_splitk_parts(Tmax, N, K, cus, kn);
+    return parts >= 3 ? parts : 0;
+}
 
-int launch_gemm_x3_splitk(const float* Aimg, const _Float16* Wp, float inv_wscale, float* planes, const int* Tptr, int64_t Tmax,
-                          int N, int K, int parts, int device, hipStream_t s) {
-    const _Float16* A = reinterpret_cast<const _Float16*>(Aimg);
-    auto kern = gemm_x3_dma_kernel<EPI_PARTIAL, 64, 3, 4, 128, 1, 0>;
-    constexpr int lds = 3 * (64 * 128 + 128 * 128);
-    MVDB_TRY(x3_set_lds((const void*)kern, lds, device));
-    dim3 grid((N + 127) / 128, (unsigned)((Tmax + 63) / 64), (unsigned)parts);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, A, Wp, inv_wscale, (const float*)nullptr, (const float*)nullptr, planes, Tptr, N, K,
-                       0, device_cus(device), (int)Tmax, 1.f);
-    return 0;
+// the planes: the default form with the bare partial sum as its epilogue, one grid layer per plane
+int launch_gemm_x3_splitk(const char* label, const LaneCall& c, const Gemm& g, int parts) {
+    const dim3 grid((g.N + 127) / 128, (unsigned)((c.Tmax + 63) / 64), (unsigned)parts);
+    return launch_x3<EPI_PARTIAL>(label, c, X3Shape<64, 3, 4, 128, 1>{}, grid, 0,
+                                  Gemm{g.A, nullptr, g.Wp, g.Wp_is, nullptr, nullptr, c.w.planes, g.N, g.K, (int)c.Tmax, 1.f});
+}
+
+// The plane counts the epilogues of a split-K GEMM have an unrolled form for: launch(Int<NP>{}); false: `parts` is none of them
+template <typename Launch>
+bool with_planes(int parts, Launch launch) {
+    switch (parts) {
+        case 2: launch(Int<2>{}); return true;
+        case 3: launch(Int<3>{}); return true;
+        case 4: launch(Int<4>{}); return true;
+        case 6: launch(Int<6>{}); return true;
+        case 8: launch(Int<8>{}); return true;
+        default: return false;
+    }
 }
 
 // the planes of a split-K QKV / FFN1 GEMM -> bias (+ query scale / GELU) -> (hi | lo) image (partials_image_kernel)
 template <int EPI>
-int launch_partials_image(const float* planes, int parts, const float* bias, const int* seq_start, int B, int64_t Tmax, int N, int qcols,
-                          float qscale, float* Cimg, hipStream_t s) {
-    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((Tmax + 3) / 4));
-    const int64_t plane = Tmax * N;
-#define MVDB_PI(NPV) hipLaunchKernelGGL((partials_image_kernel<EPI, NPV>), grid, dim3(256), 0, s, planes, plane, bias, seq_start, B, N, qcols, qscale, Cimg)
-    switch (parts) {
-        case 2: MVDB_PI(2); break;
-        case 3: MVDB_PI(3); break;
-        case 4: MVDB_PI(4); break;
-        case 6: MVDB_PI(6); break;
-        case 8: MVDB_PI(8); break;
-        default: return fail(MVDB_ERR_ARG, "internal: no partials_image_kernel for %d planes", parts);
-    }
-#undef MVDB_PI
+int launch_partials_image(const char* label, const LaneCall& c, const Gemm& g, int parts) {
+    const dim3 grid((unsigned)((g.N + 255) / 256), (unsigned)((c.Tmax + 3) / 4));
+    const bool known = with_planes(parts, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        enqueue(label, kname("partials_image_kernel<%s, %d>", epi_name(EPI), NP), partials_image_kernel<EPI, NP>, grid, 256, 0, c.s, c.w.planes,
+                c.Tmax * g.N, g.bias, c.w.seq_start, c.B, g.N, g.qcols, g.qscale, g.C);
+    });
+    if (!known) return fail(MVDB_ERR_ARG, "internal: no partials_image_kernel for %d planes", parts);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
-// ... worth its extra launch (~5 us) where the GEMM walks many K-steps: K >= 768 (the wide shapes) and three planes or more
-int x3_splitk_parts_wide(int64_t Tmax, int N, int K, int cus) {
-    static const bool on = []() { const char* v = getenv("MVDB_GEMM_X3_SPLITK_WIDE"); return !(v && *v == '0'); }();
-    if (!on || K < 768 || N % 64) return 0;
-    const int parts = x3_splitk_parts(Tmax, N, K, cus);
-    return parts >= 3 ? parts : 0;
+
+// ---- the row kernels: one row per wave, VPT values per lane -------------------------------------------------------------------
+// launch(Int<VPT>{}) for rows of `vpt` 64-value chunks (1 ... 16; H <= 1024)
+template <typename Launch, int... V>
+void with_vpt_of(int vpt, Launch& launch, std::integer_sequence<int, V...>) {
+    (void)(... || (vpt == V + 1 && (launch(Int<V + 1>{}), true)));
+}
+template <typename Launch>
+void with_vpt(int vpt, Launch launch) {
+    with_vpt_of(vpt >= 1 && vpt <= 16 ? vpt : 16, launch, std::make_integer_sequence<int, 16>{});
+}
+
+// x = LayerNorm(sum of the planes of a split-K GEMM + bias + x), and its (hi | lo) image
+template <int VPT>
+void launch_ln_partials(const char* label, const LaneCall& c, int parts, const float* bias, const float* gamma, const float* beta) {
+    const int H = c.e->cfg.hidden;
+    auto form = [&](auto full, auto np) {
+        constexpr bool FULL = decltype(full)::value;
+        constexpr int NP = decltype(np)::value;
+        enqueue(label, kname("ln_partials_kernel<%d, %s, %d>", VPT, bool_name(FULL), NP), ln_partials_kernel<VPT, FULL, NP>,
+                dim3((unsigned)((c.Tmax + 3) / 4)), 256, 0, c.s, c.w.planes, parts, c.Tmax * H, bias, c.w.seq_start, c.B, gamma, beta,
+                c.e->cfg.ln_eps, H, c.w.x, c.xp);
+    };
+    // unrolled over the planes: three everywhere; 2 / 4 / 6 / 8 only for branch-free rows at the widths of the reference's models
+    // (H = 384 / 768 / 1024); NP = 0: the loop over `parts`
+    auto rows = [&](auto full) {
+        constexpr bool all = decltype(full)::value && (VPT == 6 || VPT == 12 || VPT == 16);
+        const bool unrolled = with_planes(parts, [&](auto np) {
+            if constexpr (decltype(np)::value == 3 || all) form(full, np);
+            else form(full, Int<0>{});
+        });
+        if (!unrolled) form(full, Int<0>{});
+    };
+    if (H == VPT * 64) rows(std::true_type{});  // branch-free rows (384, 1024, ...)
+    else rows(std::false_type{});
 }
 
 template <int VPT>
-void launch_ln_partials(const float* planes, int parts, int64_t plane, const float* bias, const int* seq_start, int B, const float* g,
-                        const float* b, float eps, int H, float* x, float* xp, int64_t Tmax, hipStream_t s) {
-    const dim3 grid((unsigned)((Tmax + 3) / 4));
-#define MVDB_LNP(FULLV, NPV)                                                                                                          \
-    hipLaunchKernelGGL((ln_partials_kernel<VPT, FULLV, NPV>), grid, dim3(256), 0, s, planes, parts, plane, bias, seq_start, B, g, b, \
-                       eps, H, x, xp)
-    if (H == VPT * 64) {
-        if (parts == 3) { MVDB_LNP(true, 3); return; }
-        // (the other unrolled forms only at the widths of the reference's models: H = 384 / 768 / 1024)
-        if constexpr (VPT == 6 || VPT == 12 || VPT == 16) {
-            if (parts == 2) { MVDB_LNP(true, 2); return; }
-            if (parts == 4) { MVDB_LNP(true, 4); return; }
-            if (parts == 6) { MVDB_LNP(true, 6); return; }
-            if (parts == 8) { MVDB_LNP(true, 8); return; }
-        }
-        MVDB_LNP(true, 0);
-    } else {
-        if (parts == 3) MVDB_LNP(false, 3);
-        else MVDB_LNP(false, 0);
-    }
-#undef MVDB_LNP
-}
-
-template <int VPT>
-void launch_ln(const float* y, const int* seq_start, int B, const float* g, const float* b, float eps,
-               int H, float* x, float* xp, int64_t Tmax, hipStream_t s) {
-    if (H == VPT * 64)  // branch-free rows (384, 1024, ...)
-        hipLaunchKernelGGL((ln_kernel<VPT, true>), dim3((unsigned)((Tmax + 3) / 4)), dim3(256), 0, s, y, seq_start, B,
-                           g, b, eps, H, x, xp);
-    else
-        hipLaunchKernelGGL((ln_kernel<VPT, false>), dim3((unsigned)((Tmax + 3) / 4)), dim3(256), 0, s, y, seq_start, B,
-                           g, b, eps, H, x, xp);
+void launch_ln(const char* label, const LaneCall& c, const float* gamma, const float* beta) {
+    const int H = c.e->cfg.hidden;
+    const bool full = H == VPT * 64;  // branch-free rows (384, 1024, ...)
+    enqueue(label, kname("ln_kernel<%d, %s>", VPT, bool_name(full)), full ? ln_kernel<VPT, true> : ln_kernel<VPT, false>,
+            dim3((unsigned)((c.Tmax + 3) / 4)), 256, 0, c.s, c.w.y, c.w.seq_start, c.B, gamma, beta, c.e->cfg.ln_eps, H, c.w.x, c.xp);
 }
 
 
@@ -3103,7 +3204,7 @@ constexpr int kWalkSlots = 64;
 int walk_max_slots(const mvdb_encoder_cfg&) { return kWalkSlots; }
 bool walk_eligible(const mvdb_encoder* e, int B, int S) {
     const mvdb_encoder_cfg& c = e->cfg;
-    return e->opt_walk && (int64_t)B * S <= walk_max_slots(c) && c.hidden % 16 == 0 && c.intermediate % 16 == 0 && c.hidden <= 1024;
+    return e->kn.walk && (int64_t)B * S <= walk_max_slots(c) && c.hidden % 16 == 0 && c.intermediate % 16 == 0 && c.hidden <= 1024;
 }
 
 int ensure_walk(mvdb_encoder* e) {
@@ -3111,15 +3212,7 @@ int ensure_walk(mvdb_encoder* e) {
     const mvdb_encoder_cfg& c = e->cfg;
     const int64_t H = c.hidden, F = c.intermediate;
     const int cus = device_cus(e->device);
-    e->walk_np3 = (int)std::min<int64_t>(std::min<int64_t>(F / 16, walk::kMaxPlanes), cus);
-    {
-        const char* v = getenv("MVDB_WALK_PLANES");  // A/B: workgroups (= partial planes) of the FFN phase
-        if (v && *v) e->walk_np3 = std::max(1, std::min(e->walk_np3, atoi(v)));
-    }
-    {
-        const char* v = getenv("MVDB_WALK_GRID");    // A/B: workgroups of the launch (0: by shape, launch_walk)
-        e->walk_grid_env = v && *v ? atoi(v) : 0;
-    }
+    e->walk_np3 = std::max(1, std::min((int)std::min<int64_t>(std::min<int64_t>(F / 16, walk::kMaxPlanes), cus), e->kn.walk_planes));
     std::vector<walk::LayerPtrs> lp;
     for (const LayerW& L : e->layers)
         lp.push_back(walk::LayerPtrs{L.wqkv, L.bqkv, L.wo, L.bo, L.ln1g, L.ln1b, L.w1, L.b1, L.w2, L.b2, L.ln2g, L.ln2b});
@@ -3135,12 +3228,7 @@ int ensure_walk(mvdb_encoder* e) {
     MVDB_HIP(hipMemset(e->walk_aborts, 0, sizeof(unsigned int)));
     MVDB_HIP(hipHostMalloc((void**)&e->walk_aborts_host, sizeof(unsigned int), hipHostMallocMapped));
     *e->walk_aborts_host = 0u;
-    {
-        // no wait of a launch outlasts this (default 20 ms >> the 0.25 - 2.4 ms of a forward, << anything a watchdog would notice)
-        const char* v = getenv("MVDB_WALK_DEADLINE_US");
-        const long long us = v && *v ? atoll(v) : 20000;
-        e->walk_deadline = (unsigned int)std::min<long long>(std::max<long long>(us, 0) * 100, 0x7fffffffLL);  // s_memrealtime: 100 MHz
-    }
+    e->walk_deadline = (unsigned int)std::min<long long>(std::max<long long>(e->kn.walk_deadline_us, 0) * 100, 0x7fffffffLL);  // s_memrealtime: 100 MHz
     walk::LayerPtrs* dev = nullptr;
     MVDB_TRY(dev_alloc(&dev, (int64_t)lp.size()));
     MVDB_HIP(hipMemcpy(dev, lp.data(), lp.size() * sizeof(walk::LayerPtrs), hipMemcpyHostToDevice));
@@ -3151,7 +3239,7 @@ int ensure_walk(mvdb_encoder* e) {
 template <int MT, int HC, int RH>
 int launch_walk_inst(mvdb_encoder* e, const walk::Args& a, size_t lds, int grid, hipStream_t s) {
     auto kern = walk::encoder_walk_kernel<MT, HC, RH>;
-    MVDB_TRY(x3_set_lds((const void*)kern, (int)lds, e->device));
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, e->device));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(walk::kThreads), lds, s, a);
     MVDB_HIP(hipGetLastError());
     return 0;
@@ -3207,7 +3295,7 @@ int launch_walk(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B,
     const int cus = device_cus(e->device);
     int grid = std::min(cus, std::max<int>({16, 3 * c.hidden / 16 * rh, e->walk_np3 * rh}));  // one workgroup per CU: all resident
     if (hc == 8) grid = cus;  // wide shapes: FFN1 has F / 16 column units, FFN2 (H / 16) x 4 (encoder_walk.hpp): every CU
-    if (e->walk_grid_env > 0) grid = std::min(cus, std::max(e->walk_grid_env, e->walk_np3));
+    if (e->kn.walk_grid > 0) grid = std::min(cus, std::max(e->kn.walk_grid, e->walk_np3));
     e->walk_grid = grid;
     a.nsplit = std::max(1, std::min(std::max(grid, 96) / std::max(1, B * c.heads * rh), std::max(1, ntiles / walk::kWaves)));
     // Role placement (encoder_walk.hpp "ROLES"): rows | QKV | attention side by side, the FFN over the QKV / attention workgroups
@@ -3217,7 +3305,7 @@ int launch_walk(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B,
     a.off_rows = a.off_qkv = a.off_attn = a.off_ffn = 0;
     // (A/B on the host clock, `profiles/r05_walk_roles_ab.txt`: 5 - 7 us per forward at <= 32 slots; at 64 slots the grid would
     //  grow to every CU and the forward LOSES 15 us: roles are placed up to 32 slots only)
-    if (hc != 8 && rh == 1 && !e->walk_grid_env && e->opt_walk_roles) {
+    if (hc != 8 && rh == 1 && !e->kn.walk_grid && e->kn.walk_roles) {
         const int r = std::min(slots, cus), q = 3 * c.hidden / 16 * rh, at = B * c.heads * a.nsplit * rh, f = e->walk_np3 * rh;
         grid = std::min(cus, std::max({16, r + q + at, r + f}));
         a.off_qkv = r % grid;
@@ -3240,73 +3328,125 @@ int launch_walk(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B,
     return fail(MVDB_ERR_ARG, "no walker instantiation for this shape");
 }
 
+// ---- the ops of a layer ---------------------------------------------------------------------------------------------------
+enum AttnFamily { ATTN_VALU, ATTN_MFMA, ATTN_X3, ATTN_X3I };
+// MVDB_ENCODER_ATTENTION=valu: the thread-per-query VALU kernel (A/B reference); exact mode: the fp32 MFMA kernel; split-precision
+// mode: Q / K / V as (hi | lo) images straight from the QKV GEMM's epilogue (Q pre-scaled) and attention_x3i_kernel on them —
+// MVDB_ATTENTION_IMG=0 keeps the fp32 qkv + attention_x3_kernel (splits K / V per workgroup) as the A/B reference
+AttnFamily attention_family(const EncoderKnobs& kn, int compute) {
+    if (kn.attn_valu) return ATTN_VALU;
+    if (compute != 2 || !kn.attn_x3) return ATTN_MFMA;
+    return kn.attn_img ? ATTN_X3I : ATTN_X3;
+}
+
+template <int HD>
+void launch_attention_hd(AttnFamily family, int waves, const mvdb_encoder* e, mvdb_encoder::Lane& w, int B, int S, hipStream_t s) {
+    const int H = e->cfg.hidden;
+    const float scale = 1.0f / sqrtf((float)HD);
+    // one wave: a workgroup per (sentence, head); eight waves: 256 queries per workgroup; else ATT_Q queries
+    const dim3 grid(waves == 1 ? 1 : waves == 8 ? (S + 255) / 256 : (S + ATT_Q - 1) / ATT_Q, e->cfg.heads, B);
+    auto x3 = [&](auto wv) {
+        constexpr int WV = decltype(wv)::value;
+        if (family == ATTN_X3I)
+            enqueue("enc_attn", kname("attention_x3i_kernel<%d, %d>", HD, WV), attention_x3i_kernel<HD, WV>, grid, WV * 64, 0, s, w.qkv, w.seq_start, H, w.ctx);
+        else
+            enqueue("enc_attn", kname("attention_x3_kernel<%d, %d>", HD, WV), attention_x3_kernel<HD, WV>, grid, WV * 64, 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
+    };
+    if (family == ATTN_VALU)
+        enqueue("enc_attn", kname("attention_kernel<%d>", HD), attention_kernel<HD>, grid, ATT_Q, 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
+    else if (family == ATTN_MFMA)
+        enqueue("enc_attn", kname("attention_mfma_kernel<%d>", HD), attention_mfma_kernel<HD>, grid, 256, 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
+    else if (waves == 1) x3(Int<1>{});
+    else if (waves == 8) x3(Int<8>{});
+    else x3(Int<4>{});
+}
+
+// qkv -> ctx.  Returns whether ctx is the (hi | lo) image the split-precision GEMMs read (the split-precision families) or fp32.
+// Waves per workgroup of those families: one for S <= 32 (MVDB_ATTENTION_X3_SHORT); eight for sequences longer than
+// MVDB_ATTENTION_X3_WIDE_FROM — each K / V tile is loaded and split for twice as many queries: e5-small, B = 256: S = 512
+// 28.9 -> 27.7 ms per forward (ragged 19.4 -> 18.6), S = 256 13.4 -> 13.0; sixteen waves (one workgroup per (sentence, head) at
+// S = 512) add nothing: 27.4 vs 27.3, ragged 18.6 vs 18.3 —; four otherwise, as the fp32 kernels always.
+bool launch_attention(const mvdb_encoder* e, mvdb_encoder::Lane& w, int B, int S, int compute, hipStream_t s) {
+    const EncoderKnobs& kn = e->kn;
+    const AttnFamily family = attention_family(kn, compute);
+    const bool x3 = family == ATTN_X3 || family == ATTN_X3I;
+    const int waves = !x3 ? 4 : S <= 32 && kn.attn_x3_short ? 1 : S > kn.attn_x3_wide_from ? 8 : 4;
+    if (e->cfg.hidden / e->cfg.heads == 32) launch_attention_hd<32>(family, waves, e, w, B, S, s);
+    else launch_attention_hd<64>(family, waves, e, w, B, S, s);
+    return x3;
+}
+
+// a split-precision GEMM whose output is an image: in one launch, or — small batch, K >= 768 (x3_splitk_parts_wide) — split
+// over K into planes, then bias (+ query scale / GELU) + image as a launch of its own under `epi_label`
+template <int EPI>
+int launch_gemm_x3_image(const char* label, const char* epi_label, const LaneCall& c, const Gemm& g, int parts) {
+    if (!parts) return launch_gemm_x3<EPI>(label, c, g);
+    MVDB_TRY(launch_gemm_x3_splitk(label, c, g, parts));
+    return launch_partials_image<EPI>(epi_label, c, g, parts);
+}
+
+int launch_qkv(const LaneCall& c, const LayerW& L) {
+    const int H = c.e->cfg.hidden;
+    Gemm g{c.compute == 2 ? c.xp : c.w.x, L.wqkv, L.wqkv_p, L.wqkv_is, L.bqkv, nullptr, c.w.qkv, 3 * H, H};
+    if (c.compute != 2) launch_gemm<EPI_BIAS>("enc_qkv", c, g);
+    else if (!c.img_attn) MVDB_TRY(launch_gemm_x3<EPI_BIAS>("enc_qkv", c, g));
+    else {
+        g.qcols = H;  // Q pre-scaled, for the exp2 softmax
+        g.qscale = 1.0f / sqrtf((float)(H / c.e->cfg.heads)) * kLog2e;
+        MVDB_TRY(launch_gemm_x3_image<EPI_BIAS_QKV>("enc_qkv", "enc_qkv_epi", c, g, c.qkv_parts));
+    }
+    return 0;
+}
+
+int launch_ffn1(const LaneCall& c, const LayerW& L) {
+    const Gemm g{c.compute == 2 ? c.xp : c.w.x, L.w1, L.w1_p, L.w1_is, L.b1, nullptr, c.w.ffn, c.e->cfg.intermediate, c.e->cfg.hidden};
+    if (c.compute != 2) launch_gemm<EPI_BIAS_GELU>("enc_ffn1", c, g);
+    else MVDB_TRY(launch_gemm_x3_image<EPI_BIAS_GELU>("enc_ffn1", "enc_ffn1_epi", c, g, c.ffn1_parts));
+    return 0;
+}
+
+// x = LayerNorm(A W^T + bias + x) for one of the two N = H GEMMs of a layer (g.R = x, g.C = y): the LayerNorm in the GEMM's
+// epilogue; or, small batches, the GEMM split over K into `parts` planes and ln_partials_kernel; or the GEMM into y and ln_kernel
+int launch_proj_ln(const char* label, const char* ln_label, const LaneCall& c, const Gemm& g, const float* gamma, const float* beta, int parts) {
+    if (c.ln_fused) return launch_gemm_x3_ln(label, c, g, gamma, beta);
+    if (parts) MVDB_TRY(launch_gemm_x3_splitk(label, c, g, parts));
+    else if (c.compute == 2) MVDB_TRY(launch_gemm_x3<EPI_BIAS_RESIDUAL>(label, c, g));
+    else launch_gemm<EPI_BIAS_RESIDUAL>(label, c, g);
+    with_vpt((g.N + 63) / 64, [&](auto vpt) {
+        if (parts) launch_ln_partials<decltype(vpt)::value>(ln_label, c, parts, g.bias, gamma, beta);
+        else launch_ln<decltype(vpt)::value>(ln_label, c, gamma, beta);
+    });
+    return 0;
+}
+
+
 // Enqueue every kernel of one forward on `s` (no allocation, no host sync: capturable in a hipGraph).
 int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, const int32_t* mask, int B, int S,
                  int compute, float* out, float* hidden, hipStream_t s, bool clear_flag = false) {
-    const mvdb_encoder_cfg& c = e->cfg;
-    const int H = c.hidden, F = c.intermediate, hd = H / c.heads;
+    const mvdb_encoder_cfg& cfg = e->cfg;
+    const EncoderKnobs& kn = e->kn;
+    const int H = cfg.hidden, F = cfg.intermediate;
     const int64_t Tmax = (int64_t)B * S;
-    const int vpt = (H + 63) / 64;
-    const int* Tptr = w.seq_start + B;
+    const int cus = device_cus(e->device);
 
     if (clear_flag && B <= kPackSmallB) {
-        hipLaunchKernelGGL(pack_small_kernel, dim3(1), dim3(256), 0, s, mask, ids, B, S, c.position_offset, c.vocab_size, w.rank, w.count,
-                           w.seq_start, w.tok_id, w.tok_pos, w.tok_src, e->overflow_flag);
+        enqueue("enc_pack", kname("pack_small_kernel"), pack_small_kernel, dim3(1), 256, 0, s, mask, ids, B, S, cfg.position_offset, cfg.vocab_size,
+                w.rank, w.count, w.seq_start, w.tok_id, w.tok_pos, w.tok_src, e->overflow_flag);
     } else {
         if (clear_flag) MVDB_HIP(hipMemsetAsync(e->overflow_flag, 0, sizeof(unsigned int), s));  // (a memset node of the captured graph)
-        hipLaunchKernelGGL(seq_rank_kernel, dim3(B), dim3(64), 0, s, mask, S, w.rank, w.count);
-        hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(256), 0, s, w.count, B, w.seq_start);
-        hipLaunchKernelGGL(pack_fill_kernel, dim3(B), dim3(256), 0, s, ids, w.rank, w.seq_start, S,
-                           c.position_offset, c.vocab_size, w.tok_id, w.tok_pos, w.tok_src);
+        enqueue("enc_pack", kname("seq_rank_kernel"), seq_rank_kernel, dim3(B), 64, 0, s, mask, S, w.rank, w.count);
+        enqueue("enc_pack", kname("seq_scan_kernel"), seq_scan_kernel, dim3(1), 256, 0, s, w.count, B, w.seq_start);
+        enqueue("enc_pack", kname("pack_fill_kernel"), pack_fill_kernel, dim3(B), 256, 0, s, ids, w.rank, w.seq_start, S, cfg.position_offset,
+                cfg.vocab_size, w.tok_id, w.tok_pos, w.tok_src);
     }
-    const dim3 rowgrid((unsigned)((Tmax + 3) / 4));
-    // compute = 2: every GEMM input is a (hi | lo) fp16 image written by its producer — x by the LayerNorms (beside the
-    // fp32 x the residuals and the pooling read), the context by the attention kernel, the GELU output by FFN1's epilogue
-    float* xp = compute == 2 ? w.xp : nullptr;
-#define MVDB_VPT_SWITCH(CALL)                                      \
-    switch (vpt) {                                                 \
-        case 1: CALL(1); break;  case 2: CALL(2); break;           \
-        case 3: CALL(3); break;  case 4: CALL(4); break;           \
-        case 5: CALL(5); break;  case 6: CALL(6); break;           \
-        case 7: CALL(7); break;  case 8: CALL(8); break;           \
-        case 9: CALL(9); break;  case 10: CALL(10); break;         \
-        case 11: CALL(11); break; case 12: CALL(12); break;        \
-        case 13: CALL(13); break; case 14: CALL(14); break;        \
-        case 15: CALL(15); break; default: CALL(16); break;        \
-    }
-#define EMBED_CALL(V)                                                                                  \
-    hipLaunchKernelGGL(embed_ln_kernel<V>, rowgrid, dim3(256), 0, s, w.tok_id, w.tok_pos, w.seq_start, \
-                       B, e->word, e->pos, e->type, e->embg, e->embb, c.ln_eps, H, w.x, xp)
-    MVDB_VPT_SWITCH(EMBED_CALL)
-#undef EMBED_CALL
+    LaneCall c{e, w, B, S, compute, s, Tmax, w.seq_start + B, compute == 2 ? w.xp : nullptr, cus};
+    with_vpt((H + 63) / 64, [&](auto vpt) {
+        constexpr int VPT = decltype(vpt)::value;
+        enqueue("enc_embed", kname("embed_ln_kernel<%d>", VPT), embed_ln_kernel<VPT>, dim3((unsigned)((Tmax + 3) / 4)), 256, 0, s, w.tok_id, w.tok_pos,
+                w.seq_start, B, e->word, e->pos, e->type, e->embg, e->embb, cfg.ln_eps, H, w.x, c.xp);
+    });
 
-    const float scale = 1.0f / sqrtf((float)hd);
-    const int cus = device_cus(e->device);
-    static const bool attn_valu = []() {
-        const char* v = getenv("MVDB_ENCODER_ATTENTION");
-        return v && v[0] == 'v';
-    }();
-    static const bool x3_attention = []() {
-        const char* v = getenv("MVDB_ATTENTION_X3");
-        return !(v && *v == '0');
-    }();
-    // sequences longer than this run 256-query workgroups (eight waves): each K / V tile is loaded and split for twice as
-    // many queries — e5-small, B = 256: S = 512 28.9 -> 27.7 ms per forward (ragged 19.4 -> 18.6), S = 256 13.4 -> 13.0; sixteen
-    // waves (one workgroup per (sentence, head) at S = 512) add nothing: 27.4 vs 27.3, ragged 18.6 vs 18.3
-    static const int x3_wide_from = []() {
-        const char* v = getenv("MVDB_ATTENTION_X3_WIDE_FROM");
-        return v && *v ? atoi(v) : 128;
-    }();
-    static const bool x3_short = []() {
-        const char* v = getenv("MVDB_ATTENTION_X3_SHORT");
-        return !(v && *v == '0');
-    }();
-
-    const dim3 agrid((S + ATT_Q - 1) / ATT_Q, c.heads, B);
-    const bool ctx_is_image = compute == 2 && x3_attention && !attn_valu;
-    // Q / K / V as (hi | lo) images straight from the QKV GEMM's epilogue (Q pre-scaled), attention_x3i_kernel on them:
-    // MVDB_ATTENTION_IMG=0 keeps the fp32 qkv + attention_x3_kernel (splits K / V per workgroup) as the A/B reference
-    const bool img_attn = ctx_is_image && e->opt_img_attn;  // MVDB_ATTENTION_IMG as read when the encoder was created
+    c.img_attn = attention_family(kn, compute) == ATTN_X3I;
     // bias + residual + LayerNorm in the epilogue of the N = H GEMMs (MVDB_GEMM_LN_FUSED=0: separate ln_kernel launches;
     // =2: at every batch size).  A row-owning workgroup streams ALL of W and there is one workgroup per CU, so the fused
     // kernel needs rows: measured on e5-small, B = 256 (full / ragged batch, ms per forward, fused vs GEMM + ln_kernel):
@@ -3314,128 +3454,36 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
     // S = 256 11.85 / 8.50 vs 12.73 / 8.30, S = 512 25.6 / 17.0 vs 27.1 / 18.1 — ahead on full batches from S = 64, on
     // ragged ones (64 % of the token slots filled; the row count per workgroup is chosen from the PADDED count, the only
     // one the host knows) only at S = 512.  Default: from 128 token slots per CU.
-    const int ln_env = e->opt_ln_fused;  // MVDB_GEMM_LN_FUSED as read when the encoder was created
-    const bool ln_fused = compute == 2 && x3_ln_fusable(H) && ln_env != 0 && (ln_env == 2 || Tmax >= 128 * (int64_t)cus);
-    const int ffn2_parts = compute == 2 && !ln_fused ? x3_splitk_parts(Tmax, H, F, cus) : 0;
-    const int wo_parts = compute == 2 && !ln_fused ? x3_splitk_parts(Tmax, H, H, cus) : 0;
-    // QKV and FFN1 the same way on the wide shapes (K = H >= 768: 32 K-steps), their epilogues as a launch of their own
-    const int qkv_parts = compute == 2 ? x3_splitk_parts_wide(Tmax, 3 * H, H, cus) : 0;
-    const int ffn1_parts = compute == 2 ? x3_splitk_parts_wide(Tmax, F, H, cus) : 0;
+    c.ln_fused = compute == 2 && x3_ln_fusable(H) && kn.ln_fused != 0 && (kn.ln_fused == 2 || Tmax >= 128 * (int64_t)cus);
+    // small batches: the N = H GEMMs split over K (x3_splitk_parts); QKV and FFN1 the same way on the wide shapes (K = H >= 768:
+    // 32 K-steps), their epilogues as a launch of their own
+    c.wo_parts = compute == 2 && !c.ln_fused ? x3_splitk_parts(Tmax, H, H, cus, kn) : 0;
+    c.ffn2_parts = compute == 2 && !c.ln_fused ? x3_splitk_parts(Tmax, H, F, cus, kn) : 0;
+    c.qkv_parts = compute == 2 ? x3_splitk_parts_wide(Tmax, 3 * H, H, cus, kn) : 0;
+    c.ffn1_parts = compute == 2 ? x3_splitk_parts_wide(Tmax, F, H, cus, kn) : 0;
     for (const LayerW& L : e->layers) {
-        if (compute == 2 && img_attn && qkv_parts) {   // small batch, K >= 768: split over K, then bias + query scale + image
-            MVDB_TRY(launch_gemm_x3_splitk(xp, L.wqkv_p, L.wqkv_is, w.planes, Tptr, Tmax, 3 * H, H, qkv_parts, e->device, s));
-            MVDB_TRY(launch_partials_image<EPI_BIAS_QKV>(w.planes, qkv_parts, L.bqkv, w.seq_start, B, Tmax, 3 * H, H, scale * kLog2e, w.qkv, s));
-        } else if (compute == 2 && img_attn)
-            MVDB_TRY(launch_gemm_x3<EPI_BIAS_QKV>(xp, L.wqkv_p, L.wqkv_is, L.bqkv, nullptr, w.qkv, Tptr, Tmax, 3 * H, H, e->device, s,
-                                                  H, scale * kLog2e));
-        else if (compute == 2)
-            MVDB_TRY(launch_gemm_x3<EPI_BIAS>(xp, L.wqkv_p, L.wqkv_is, L.bqkv, nullptr, w.qkv, Tptr, Tmax, 3 * H, H, e->device, s));
-        else
-            launch_gemm<EPI_BIAS>(w.x, L.wqkv, L.bqkv, nullptr, w.qkv, Tptr, Tmax, 3 * H, H, cus, s);
-        if (attn_valu) {  // MVDB_ENCODER_ATTENTION=valu: the thread-per-query VALU kernel (A/B reference)
-            if (hd == 32)
-                hipLaunchKernelGGL(attention_kernel<32>, agrid, dim3(ATT_Q), 0, s, w.qkv, w.seq_start, H, scale,
-                                   w.ctx);
-            else
-                hipLaunchKernelGGL(attention_kernel<64>, agrid, dim3(ATT_Q), 0, s, w.qkv, w.seq_start, H, scale,
-                                   w.ctx);
-        } else if (img_attn) {
-            if (S <= 32 && x3_short) {  // one wave per (sentence, head)
-                const dim3 sgrid(1, c.heads, B);
-                if (hd == 32)
-                    hipLaunchKernelGGL((attention_x3i_kernel<32, 1>), sgrid, dim3(64), 0, s, w.qkv, w.seq_start, H, w.ctx);
-                else
-                    hipLaunchKernelGGL((attention_x3i_kernel<64, 1>), sgrid, dim3(64), 0, s, w.qkv, w.seq_start, H, w.ctx);
-            } else if (S > x3_wide_from) {  // eight waves = 256 queries per workgroup share each K / V tile
-                const dim3 wgrid((S + 255) / 256, c.heads, B);
-                if (hd == 32)
-                    hipLaunchKernelGGL((attention_x3i_kernel<32, 8>), wgrid, dim3(512), 0, s, w.qkv, w.seq_start, H, w.ctx);
-                else
-                    hipLaunchKernelGGL((attention_x3i_kernel<64, 8>), wgrid, dim3(512), 0, s, w.qkv, w.seq_start, H, w.ctx);
-            } else if (hd == 32)
-                hipLaunchKernelGGL((attention_x3i_kernel<32, 4>), agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, w.ctx);
-            else
-                hipLaunchKernelGGL((attention_x3i_kernel<64, 4>), agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, w.ctx);
-        } else if (compute == 2 && x3_attention) {
-            if (S <= 32 && x3_short) {  // one wave per (sentence, head)
-                const dim3 sgrid(1, c.heads, B);
-                if (hd == 32)
-                    hipLaunchKernelGGL((attention_x3_kernel<32, 1>), sgrid, dim3(64), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-                else
-                    hipLaunchKernelGGL((attention_x3_kernel<64, 1>), sgrid, dim3(64), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-            } else if (S > x3_wide_from) {  // eight waves = 256 queries per workgroup: each K / V tile is loaded and split for twice as many queries
-                const dim3 wgrid((S + 255) / 256, c.heads, B);
-                if (hd == 32)
-                    hipLaunchKernelGGL((attention_x3_kernel<32, 8>), wgrid, dim3(512), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-                else
-                    hipLaunchKernelGGL((attention_x3_kernel<64, 8>), wgrid, dim3(512), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-            } else if (hd == 32)
-                hipLaunchKernelGGL(attention_x3_kernel<32>, agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-            else
-                hipLaunchKernelGGL(attention_x3_kernel<64>, agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, scale, w.ctx);
-        } else if (hd == 32) {
-            hipLaunchKernelGGL(attention_mfma_kernel<32>, agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, scale,
-                               w.ctx);
-        } else {
-            hipLaunchKernelGGL(attention_mfma_kernel<64>, agrid, dim3(256), 0, s, w.qkv, w.seq_start, H, scale,
-                               w.ctx);
+        MVDB_TRY(launch_qkv(c, L));
+        const float* ctx = w.ctx;
+        if (!launch_attention(e, w, B, S, compute, s) && compute == 2) {  // an fp32 attention kernel ran (A/B switches): split its output into the image form
+            const int64_t n = Tmax * H;
+            enqueue("enc_ctx_split", kname("f32_split_interleave_kernel"), f32_split_interleave_kernel, dim3((unsigned)((n + 255) / 256)), 256, 0, s,
+                    w.ctx, reinterpret_cast<_Float16*>(w.ffn), n, 1.0f);
+            ctx = w.ffn;
         }
-        if (compute == 2) {
-            const float* ctx_img = w.ctx;
-            if (!ctx_is_image) {  // an fp32 attention kernel ran (A/B switches): split its output into the image form
-                const int64_t n = Tmax * H;
-                hipLaunchKernelGGL(f32_split_interleave_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.ctx,
-                                   reinterpret_cast<_Float16*>(w.ffn), n, 1.0f);
-                ctx_img = w.ffn;
-            }
-            if (ln_fused)
-                MVDB_TRY(launch_gemm_x3_ln(ctx_img, L.wo_p, L.wo_is, L.bo, L.ln1g, L.ln1b, c.ln_eps, w.x, xp, Tptr, Tmax, H, H, e->device, s));
-            else if (wo_parts)  // small batch, long K (H >= 768): split over K like FFN2 (attention is done with qkv)
-                MVDB_TRY(launch_gemm_x3_splitk(ctx_img, L.wo_p, L.wo_is, w.planes, Tptr, Tmax, H, H, wo_parts, e->device, s));
-            else
-                MVDB_TRY(launch_gemm_x3<EPI_BIAS_RESIDUAL>(ctx_img, L.wo_p, L.wo_is, L.bo, w.x, w.y, Tptr, Tmax, H, H, e->device, s));
-        }
-        else
-            launch_gemm<EPI_BIAS_RESIDUAL>(w.ctx, L.wo, L.bo, w.x, w.y, Tptr, Tmax, H, H, cus, s);
-#define LN1_CALL(V) launch_ln<V>(w.y, w.seq_start, B, L.ln1g, L.ln1b, c.ln_eps, H, w.x, xp, Tmax, s)
-#define LN1P_CALL(V) launch_ln_partials<V>(w.planes, wo_parts, Tmax * H, L.bo, w.seq_start, B, L.ln1g, L.ln1b, c.ln_eps, H, w.x, xp, Tmax, s)
-        if (!ln_fused && wo_parts) { MVDB_VPT_SWITCH(LN1P_CALL) }
-        else if (!ln_fused) { MVDB_VPT_SWITCH(LN1_CALL) }
-#undef LN1P_CALL
-#undef LN1_CALL
-        if (compute == 2) {
-            if (ffn1_parts) {
-                MVDB_TRY(launch_gemm_x3_splitk(xp, L.w1_p, L.w1_is, w.planes, Tptr, Tmax, F, H, ffn1_parts, e->device, s));
-                MVDB_TRY(launch_partials_image<EPI_BIAS_GELU>(w.planes, ffn1_parts, L.b1, w.seq_start, B, Tmax, F, 0, 1.f, w.ffn, s));
-            } else
-                MVDB_TRY(launch_gemm_x3<EPI_BIAS_GELU>(xp, L.w1_p, L.w1_is, L.b1, nullptr, w.ffn, Tptr, Tmax, F, H, e->device, s));
-            if (ln_fused)
-                MVDB_TRY(launch_gemm_x3_ln(w.ffn, L.w2_p, L.w2_is, L.b2, L.ln2g, L.ln2b, c.ln_eps, w.x, xp, Tptr, Tmax, H, F, e->device, s));
-            else if (ffn2_parts)  // small batch: split over K into planes
-                MVDB_TRY(launch_gemm_x3_splitk(w.ffn, L.w2_p, L.w2_is, w.planes, Tptr, Tmax, H, F, ffn2_parts, e->device, s));
-            else
-                MVDB_TRY(launch_gemm_x3<EPI_BIAS_RESIDUAL>(w.ffn, L.w2_p, L.w2_is, L.b2, w.x, w.y, Tptr, Tmax, H, F, e->device, s));
-        } else {
-            launch_gemm<EPI_BIAS_GELU>(w.x, L.w1, L.b1, nullptr, w.ffn, Tptr, Tmax, F, H, cus, s);
-            launch_gemm<EPI_BIAS_RESIDUAL>(w.ffn, L.w2, L.b2, w.x, w.y, Tptr, Tmax, H, F, cus, s);
-        }
-#define LN2_CALL(V) launch_ln<V>(w.y, w.seq_start, B, L.ln2g, L.ln2b, c.ln_eps, H, w.x, xp, Tmax, s)
-#define LN2P_CALL(V) launch_ln_partials<V>(w.planes, ffn2_parts, Tmax * H, L.b2, w.seq_start, B, L.ln2g, L.ln2b, c.ln_eps, H, w.x, xp, Tmax, s)
-        if (!ln_fused && ffn2_parts) { MVDB_VPT_SWITCH(LN2P_CALL) }
-        else if (!ln_fused) { MVDB_VPT_SWITCH(LN2_CALL) }
-#undef LN2P_CALL
-#undef LN2_CALL
+        MVDB_TRY(launch_proj_ln("enc_wo", "enc_ln1", c, Gemm{ctx, L.wo, L.wo_p, L.wo_is, L.bo, w.x, w.y, H, H}, L.ln1g, L.ln1b, c.wo_parts));
+        MVDB_TRY(launch_ffn1(c, L));
+        MVDB_TRY(launch_proj_ln("enc_ffn2", "enc_ln2", c, Gemm{w.ffn, L.w2, L.w2_p, L.w2_is, L.b2, w.x, w.y, H, F}, L.ln2g, L.ln2b, c.ffn2_parts));
     }
-#undef MVDB_VPT_SWITCH
     // (w.y is free here: chunk partials of sentences longer than kPoolChunk tokens)
-    hipLaunchKernelGGL(pool_norm_kernel, dim3(B, (S + kPoolChunk - 1) / kPoolChunk), dim3(256), 0, s, w.x, w.seq_start, H, c.pooling, out,
-                       e->overflow_flag, w.y, w.pool_ctr);
+    enqueue("enc_pool", kname("pool_norm_kernel"), pool_norm_kernel, dim3(B, (S + kPoolChunk - 1) / kPoolChunk), 256, 0, s, w.x, w.seq_start, H,
+            cfg.pooling, out, e->overflow_flag, w.y, w.pool_ctr);
     if (hidden)
-        hipLaunchKernelGGL(unpack_hidden_kernel, dim3((unsigned)Tmax), dim3(256), 0, s, w.x, w.rank,
-                           w.seq_start, S, H, hidden);
+        enqueue("enc_hidden", kname("unpack_hidden_kernel"), unpack_hidden_kernel, dim3((unsigned)Tmax), 256, 0, s, w.x, w.rank, w.seq_start, S, H,
+                hidden);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
+
 
 // One forward: the whole batch on lane 0, or — exact mode, >= 64 sentences and >= 32768 token slots — two halves on
 // two streams (fork / join by events, capturable into one hipGraph): the halves are independent, so one half's kernel
@@ -3443,11 +3491,7 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
 // 43.9 ms; at S = 32 (T = 8192) it gains nothing (4.09 vs 4.06 ms) and costs 6 % on a ragged batch: not used there.
 int enqueue_forward(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B, int S, int compute,
                     float* out, float* hidden, hipStream_t s) {
-    static const int split_mode = []() {
-        const char* v = getenv("MVDB_ENCODER_SPLIT");
-        return v ? atoi(v) : 1;
-    }();
-    const bool split = split_mode && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;
+    const bool split = e->kn.split && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;
     if (!split) return enqueue_lane(e, e->lane[0], ids, mask, B, S, compute, out, hidden, s, true);  // (clears the overflow word)
     MVDB_HIP(hipMemsetAsync(e->overflow_flag, 0, sizeof(unsigned int), s));  // (a memset node of the captured graph)
     const int b0 = B / 2, b1 = B - b0;
@@ -3520,11 +3564,8 @@ int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B
     if (e->ws_gen != gen_before) e->drop_graphs();  // workspace moved: captured pointers are stale
 
     // ~90 short launches per forward: replay them as ONE hipGraph per (shape, buffers) instead of paying
-    // the host launch path per kernel (the S = 32 forward is launch-bound otherwise)
-    static const bool use_graph = []() {
-        const char* v = getenv("MVDB_ENCODER_GRAPH");
-        return !(v && *v == '0');
-    }();
+    // the host launch path per kernel (the S = 32 forward is launch-bound otherwise); MVDB_ENCODER_GRAPH=0: plain launches
+    const bool use_graph = e->kn.graph;
     // the caller is capturing `s` into a graph of its own (e.g. encoder -> search as ONE graph): plain launches join it
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool outer_capture = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
@@ -3615,26 +3656,16 @@ int mvdb_encoder_create(const mvdb_encoder_cfg* cfg, const void* const* w, int d
         if (!w[i]) return fail(MVDB_ERR_ARG, "weight %d (%s) is NULL", i, mvdb_encoder_weight_name(cfg, i));
     MVDB_TRY(ensure_device(device));
     DeviceGuard dg(device);
-    mvdb_encoder* e = new mvdb_encoder();
+    mvdb_encoder* e = new mvdb_encoder();  // (reads the switches: EncoderKnobs)
     e->cfg = *cfg;
     e->device = device;
-    {
-        const char* v = getenv("MVDB_GEMM_LN_FUSED");
-        e->opt_ln_fused = v && *v ? atoi(v) : 1;
-        v = getenv("MVDB_ATTENTION_IMG");
-        e->opt_img_attn = !(v && *v == '0');
-        v = getenv("MVDB_ENCODER_WALK");
-        e->opt_walk = !(v && *v == '0');
-        v = getenv("MVDB_WALK_ROLES");
-        e->opt_walk_roles = !(v && *v == '0');
-        v = getenv("MVDB_WALK_PINNED");
-        e->opt_walk_pinned = !(v && *v == '0');
 #ifdef MVDB_X3_ABLATE
-        v = getenv("MVDB_LN_SKIP_X");
+    {
+        const char* v = getenv("MVDB_LN_SKIP_X");
         const int skip = v && *v == '1';
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ln_skip_x), &skip, sizeof(int));
-#endif
     }
+#endif
     e->word = (const float*)w[0];
     e->pos = (const float*)w[1];
     e->type = (const float*)w[2];
@@ -3706,7 +3737,7 @@ int mvdb_encoder_walks(const mvdb_encoder* e, int B, int S) {
 
 int mvdb_encoder_splitk_planes(int64_t tokens, int n, int k, int compute_units) {
     if (tokens <= 0 || n <= 0 || k <= 0 || compute_units <= 0) return 0;
-    return x3_splitk_parts(tokens, n, k, compute_units);
+    return x3_splitk_parts(tokens, n, k, compute_units, read_encoder_knobs());
 }
 
 int mvdb_encoder_gemm_tile_form(int64_t tokens, int n, int compute_units) {
@@ -3817,7 +3848,7 @@ int mvdb_encoder_forward(mvdb_encoder* e, const int32_t* ids_host, const int32_t
     };
     const unsigned int aborts_before = e->walk_aborts_host ? *e->walk_aborts_host : 0u;
     bool walked = false;
-    if (tokens <= kPinSlots && e->opt_walk_pinned) {
+    if (tokens <= kPinSlots && e->kn.walk_pinned) {
         // ONE sentence per call (extract_embeddings truncates at 512 tokens, embedding_model.py:64,77): the kernels read the ids
         // and the mask from host-mapped memory and write the embedding there — no copy engine work at all around the forward
         // (two H2D copies, a memset and a D2H copy before: ~20 us of a 0.27 ms call).  The walking launch up to its 128 token

@@ -36,10 +36,6 @@ int launch_merge_di_sort(int metric, int nlists, int nq, int k, const float* D, 
 static thread_local char g_err[512] = "";
 thread_local std::vector<void*>* tls_retire = nullptr;
 
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
 Knobs read_knobs() {
     Knobs k;
     k.scan_blocks_per_cu = env_int("MVDB_SCAN_BLOCKS_PER_CU", 0);
@@ -3882,6 +3878,7 @@ int mvdb_rescue_tile_stats(int64_t* listed, int64_t* total) {
 
 int mvdb_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (on && !g_prof_on) g_prof_sym.clear();  // off -> on: a label that launches nothing from here on reads ""
     g_prof_on = on != 0;
     return 0;
 }

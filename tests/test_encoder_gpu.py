@@ -85,22 +85,41 @@ def test_split_precision_kernel_variants_match_golden(i, switches, gpu, monkeypa
                                  {"MVDB_GEMM_X3_SPLITK": "0"}, {"MVDB_GEMM_X3_SPLITK_PARTS": "3", "MVDB_GEMM_X3_SPLITK_WIDE": "0"}],
                          ids=["persistent-256-row-tiles-forced", "one-tile-per-workgroup-256-row-tiles-forced", "dma-burst",
                               "ffn2-unsplit-at-small-batches", "three-split-k-planes-as-in-round-5"])
-def test_gemm_tile_forms_match_golden_in_a_fresh_process(env, gpu):
-    """The tile-form switches of the split-precision GEMMs are read once per process: a child pytest runs every split-mode
-    golden case with (a) the persistent 256-row kernel FORCED onto batches it would never be chosen for (fewer tiles than
-    CUs, a last row band of a few rows), (b) its one-tile-per-workgroup predecessor, (c) the LDS-DMA instructions issued as
-    one burst per K-step instead of between the MFMAs, (d) FFN2 unsplit at small batches (round 4: by default it runs split
-    over K there — which every golden case of the parent process exercises), (e) round 5's split-K rule (three planes, QKV /
-    FFN1 of the wide shapes unsplit) beside round 6's (as many planes as leave each four K-steps: the parent process)."""
-    import os
-    import subprocess
-    import sys
-    child_env = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-q", "-x", "-m", "gpu", "-k",
-                        "test_encoder_matches_transformers_golden and fp16x3"], env=child_env, capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-500:]
+@pytest.mark.parametrize("i", range(len(CASES)))
+def test_gemm_tile_forms_match_golden_in_a_fresh_process(i, env, gpu, monkeypatch):
+    """The tile-form switches of the split-precision GEMMs are read when an encoder is created (once per process until the
+    launchers got one switch table: this test then ran a child pytest per switch set; it keeps its name): a fresh encoder
+    in THIS process runs every split-mode golden case with (a) the persistent 256-row kernel FORCED onto batches it would never
+    be chosen for (fewer tiles than CUs, a last row band of a few rows), (b) its one-tile-per-workgroup predecessor, (c) the
+    LDS-DMA instructions issued as one burst per K-step instead of between the MFMAs, (d) FFN2 unsplit at small batches (round
+    4: by default it runs split over K there — which every golden case of the other tests exercises), (e) round 5's split-K
+    rule (three planes, QKV / FFN1 of the wide shapes unsplit) beside round 6's (as many planes as leave each four K-steps: the
+    other tests).  The assertions of test_encoder_matches_transformers_golden, at its tolerances."""
+    import torch
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)  # read when the encoder is created
+    c = CASES[i]
+    cfg = E.make_config(c["name"])
+    w = E.make_weights(cfg, c["wseed"])
+    enc = _model(cfg, w)
+    emb = enc.forward(c["ids"], c["mask"], compute=2)
+    np.testing.assert_allclose(emb, c["emb"], atol=2e-5, rtol=0)
+    dev = torch.device("cuda", 0)
+    out, hidden = enc.forward_device(torch.from_numpy(c["ids"]).to(dev), torch.from_numpy(c["mask"]).to(dev), compute=2,
+                                     want_hidden=True)
+    torch.cuda.synchronize()
+    np.testing.assert_allclose(out.cpu().numpy(), emb, atol=0, rtol=0)  # host and device entry points agree
+    hidden = hidden.cpu().numpy()
+    m = c["mask"].astype(bool)
+    if c["hidden_valid"] is not None:
+        np.testing.assert_allclose(hidden[m], c["hidden_valid"], atol=1e-4, rtol=0)
+    assert not hidden[~m].any()
+    enc.close()
+    if c["cls_emb"] is not None:
+        from minivectordb_amd.embedding_model import GpuEncoder
+        encc = GpuEncoder(cfg, {k: torch.from_numpy(v) for k, v in w.items()}, device=0, pooling="cls")
+        np.testing.assert_allclose(encc.forward(c["ids"], c["mask"], compute=2), c["cls_emb"], atol=2e-5, rtol=0)
+        encc.close()
 
 
 def test_batch_composition_does_not_change_a_row(gpu, monkeypatch):
