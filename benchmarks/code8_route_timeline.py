@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-launch durations and the gaps between launches of the single-query int8 route, from a rocprofv3 kernel trace
 (`--kernel-trace --output-format csv`, the directory or the *_kernel_trace.csv itself) of `code8_route_probe.py --timers 0`
-or of `bench.py`.  A step is the run of dispatches from one `code8_query_kernel` to the next; only steps with the most
+or of `bench.py`.  A step is the run of dispatches from one floor launch (`code8_seed_kernel`; in traces of builds that
+still had the one-block prologue, `code8_query_kernel`) to the next; only steps with the most
 common number of launches are averaged (the first ones build the code).  Prints one JSON object:
 launches in order with their mean / median duration, the mean gap before each, their sums, the mean step span, and the
 mean duration of the exact scan's launches (steps with `code8_single_query = 0`) where the trace has them.
@@ -25,9 +26,10 @@ def main():
     for r in csv.DictReader(open(src)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
+    first = "code8_query_kernel" if any("code8_query_kernel" in r[2] for r in rows) else "code8_seed_kernel"
     steps, cur = [], None
     for r in rows:
-        if "code8_query_kernel" in r[2]:
+        if first in r[2]:
             cur = []
             steps.append(cur)
         elif cur is not None and "flat_scan_kernel<64, 2, 2, 0, 0, true, 0, false, false>" in r[2]:

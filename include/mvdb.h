@@ -110,7 +110,8 @@ int mvdb_index_device(const mvdb_index* idx);
 int64_t mvdb_index_shadow_rows(const mvdb_index* idx);
 
 /* Rows held in the index' int8 CODE (0: none): d int8 values, an fp32 scale and an fp32 bound of the coding residual per row
- * (+25 % of the index's device memory at d = 512), the operand of the single-query prefilter (option "code8_single_query").
+ * (+25 % of the index's device memory at d = 512, and a fixed 131,072 x (d + 8) bytes for a second, contiguous copy of the
+ * sampled rows the route takes its floor from), the operand of the single-query prefilter (option "code8_single_query").
  * Built by the first eligible single query (one blocking conversion pass and the allocations inside that call; never while the
  * stream is being captured: such a call takes the exact scan), extended by add, dropped by remove_rows / reset / a
  * re-allocation — the exact scan answers the next two eligible queries after the LATEST such change before the code is

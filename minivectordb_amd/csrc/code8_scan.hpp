@@ -115,83 +115,106 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
     }
 }
 
-// ---- prologue: the query -> two int8 planes + the margin's terms; zeroes the call's counter words ------------------------------
+// ---- prologue: the query -> two int8 planes + the margin's terms -------------------------------------------------------------------
 // par[0] = qstep, par[1] = alpha, par[2] = beta, par[3] = 1 when the query's norm is not finite (the call falls back)
-// counter[0]: the candidate counter; counter[1]: the two 32-bit arrival tickets of code8_seed_kernel and code8_rescore_kernel
-// (kCode8SeedTicket, kCode8RescoreTicket) — zeroed here on EVERY call, whatever an earlier call left in them
-__global__ __launch_bounds__(256) void code8_query_kernel(const float* __restrict__ q, int d, int normalize_q, float row_norm_bound,
-                                                          int8_t* __restrict__ qhi, int8_t* __restrict__ qlo, float* __restrict__ par,
-                                                          unsigned long long* __restrict__ counter) {
-    __shared__ float shf[256];
-    __shared__ double shd[256];
+// Run by every block of code8_seed_kernel, all threads of the block calling it.  The query is read ONCE: the first
+// kCode8QueryThreads threads hold up to kCode8MaxDim / kCode8QueryThreads elements each and leave their partial sums in LDS;
+// every wave then reduces the kCode8QueryThreads partials itself, in the order of a halving tree over them (t with t + 128,
+// then t + 64, then the xor butterfly of a wave: float addition commutes, so every lane ends with the tree's bits) — an order
+// that depends on neither the block's size nor the wave, so every block holds the same bits, and three barriers in all.
+// qhi / qlo [d]: the block's LDS, complete for every thread when this returns; par: every thread's own copy.
+constexpr int kCode8QueryThreads = 256;
+constexpr int kCode8MaxDim = 1024;
+
+struct Code8QueryShared {
+    float nr[kCode8QueryThreads];
+    float mx[kCode8QueryThreads];
+    double n2[kCode8QueryThreads];
+};
+
+template <typename T, typename Op>
+__device__ __forceinline__ T code8_query_reduce(const T* part, Op op) {
+    const int lane = threadIdx.x & 63;
+    T v = op(op(part[lane], part[lane + 128]), op(part[lane + 64], part[lane + 192]));
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = op(v, __shfl_xor(v, m));
+    return v;
+}
+
+__device__ __forceinline__ void code8_query_image(const float* __restrict__ q, int d, int normalize_q, float row_norm_bound, int8_t* qhi,
+                                                  int8_t* qlo, float (&par)[4], Code8QueryShared& sh) {
+    constexpr int NT = kCode8QueryThreads;
+    constexpr int E = kCode8MaxDim / NT;
+    static_assert(NT == 256, "code8_query_reduce restates a halving tree over 256 partials");
     const int tid = threadIdx.x;
-    auto block_sum_f = [&](float v) {
-        shf[tid] = v;
-        __syncthreads();
-        for (int s = 128; s >= 1; s >>= 1) {
-            if (tid < s) shf[tid] += shf[tid + s];
-            __syncthreads();
-        }
-        const float out = shf[0];
-        __syncthreads();
-        return out;
-    };
-    float nr = 0.f;
-    for (int j = tid; j < d; j += 256) nr = fmaf(q[j], q[j], nr);
-    nr = block_sum_f(nr);
-    const float inorm = (normalize_q && nr > 0.f) ? 1.0f / sqrtf(nr) : 1.0f;
-    float mx = 0.f;
-    double n2 = 0.0;
-    bool bad = false;
-    for (int j = tid; j < d; j += 256) {
-        const float v = q[j] * inorm;
-        bad = bad || !(fabsf(v) <= 3.402823466e+38f);
-        mx = fmaxf(mx, fabsf(v));
-        n2 += (double)v * (double)v;
+    const bool on = tid < NT;
+    float qv[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) qv[e] = (on && tid + e * NT < d) ? q[tid + e * NT] : 0.f;
+    if (on) {
+        float nr = 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (tid + e * NT < d) nr = fmaf(qv[e], qv[e], nr);
+        sh.nr[tid] = nr;
     }
-    shd[tid] = n2;
-    shf[tid] = bad ? INFINITY : mx;
     __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) {
-            shd[tid] += shd[tid + s];
-            shf[tid] = fmaxf(shf[tid], shf[tid + s]);
+    const float nr = code8_query_reduce(sh.nr, [](float x, float y) { return x + y; });
+    const float inorm = (normalize_q && nr > 0.f) ? 1.0f / sqrtf(nr) : 1.0f;
+    if (on) {
+        float mx = 0.f;
+        double n2 = 0.0;
+        bool bad = false;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            if (tid + e * NT < d) {
+                const float v = qv[e] * inorm;
+                bad = bad || !(fabsf(v) <= 3.402823466e+38f);
+                mx = fmaxf(mx, fabsf(v));
+                n2 += (double)v * (double)v;
+            }
         }
-        __syncthreads();
+        sh.n2[tid] = n2;
+        sh.mx[tid] = bad ? INFINITY : mx;
     }
-    mx = shf[0];
-    const double qn_d = sqrt(shd[0]) * (1.0 + 1e-6);
+    __syncthreads();
+    const float mx = code8_query_reduce(sh.mx, [](float x, float y) { return fmaxf(x, y); });
+    const double n2 = code8_query_reduce(sh.n2, [](double x, double y) { return x + y; });
+    const double qn_d = sqrt(n2) * (1.0 + 1e-6);
     const bool nonfinite = !(mx <= 3.402823466e+38f) || !(qn_d <= 3.0e38);
     const float qn = nonfinite ? 0.f : (float)qn_d;
     const int qmax = code8_qmax(d);
     const bool tiny = nonfinite || mx < kCode8Tiny;
     const float qstep = tiny ? 0.f : mx / (float)qmax;
-    for (int j = tid; j < d; j += 256) {
-        int Q = 0;
-        if (!tiny) {
-            float cf = rintf((q[j] * inorm) / qstep);
-            cf = fminf(fmaxf(cf, -(float)qmax), (float)qmax);
-            Q = (int)cf;
+    if (on) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int j = tid + e * NT;
+            if (j < d) {
+                int Q = 0;
+                if (!tiny) {
+                    float cf = rintf((qv[e] * inorm) / qstep);
+                    cf = fminf(fmaxf(cf, -(float)qmax), (float)qmax);
+                    Q = (int)cf;
+                }
+                const int lo = ((Q + 128) & 255) - 128;
+                const int hi = (Q - lo) >> 8;
+                qhi[j] = (int8_t)hi;
+                qlo[j] = (int8_t)lo;
+            }
         }
-        const int lo = ((Q + 128) & 255) - 128;
-        const int hi = (Q - lo) >> 8;
-        qhi[j] = (int8_t)hi;
-        qlo[j] = (int8_t)lo;
     }
-    if (tid == 0) {
-        // a query coded as zero: all of it is "rounding error" (dq = qn)
-        Code8Margin m = code8_margin(d, qn, qstep, row_norm_bound);
-        if (tiny && !nonfinite) {
-            m.alpha = qn * 1.00001f;
-            m.beta = fmaf(qn * 1.00001f, row_norm_bound, 1e-30f) * 1.00001f;
-        }
-        par[0] = qstep;
-        par[1] = m.alpha;
-        par[2] = m.beta;
-        par[3] = nonfinite ? 1.f : 0.f;
-        counter[0] = 0ull;
-        counter[1] = 0ull;
+    // a query coded as zero: all of it is "rounding error" (dq = qn)
+    Code8Margin m = code8_margin(d, qn, qstep, row_norm_bound);
+    if (tiny && !nonfinite) {
+        m.alpha = qn * 1.00001f;
+        m.beta = fmaf(qn * 1.00001f, row_norm_bound, 1e-30f) * 1.00001f;
     }
+    par[0] = qstep;
+    par[1] = m.alpha;
+    par[2] = m.beta;
+    par[3] = nonfinite ? 1.f : 0.f;
+    __syncthreads();
 }
 
 // ---- the prefilter scan ---------------------------------------------------------------------------------------------------------
@@ -200,13 +223,13 @@ struct Code8ScanArgs {
     const float2* ar;      // [n] (a, r)
     int64_t n;
     int d;                 // bytes per row (a multiple of 16)
-    const int8_t* qhi;     // [d] the query's high / low planes (code8_query_kernel)
+    const int8_t* qhi;     // [d] the query's high / low planes (code8_query_image, left by code8_seed_kernel's block 0)
     const int8_t* qlo;
     const float* par;      // qstep, alpha, beta
     const float* floor;    // a proven lower bound of the final k-th best score (code8_seed_kernel: the sample's k-th best lower bound)
     uint32_t* cand;        // [cap] appended rows, in no order
     int64_t cap;
-    unsigned long long* counter;  // zeroed by the prologue; keeps counting past cap
+    unsigned long long* counter;  // zeroed by code8_seed_kernel's block 0; keeps counting past cap
 };
 
 // lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
@@ -384,7 +407,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
 //             (the fences order it: an acq_rel add would write back and invalidate a second time in every block);
 //   consumer: the lane that drew the last ticket does ONE agent-scope acquire fence and drains it, __syncthreads(), then every
 //             wave reads the lists with agent-scope atomic loads (vector loads that bypass this CU's L1; never the scalar path).
-// The ticket word is zeroed by code8_query_kernel on every call; the last arriver also leaves it at zero.
+// The last arriver leaves the ticket word at zero; the re-score's is also zeroed by code8_seed_kernel's block 0 on every call.
 __device__ __forceinline__ void code8_store_list(uint64_t* lists, int64_t at, uint64_t key) {
     __hip_atomic_store(lists + at, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -394,7 +417,7 @@ __device__ __forceinline__ uint64_t code8_load_list(uint64_t* lists, int64_t at)
 
 // Called by every thread of the block after wave 0 stored the block's list.  `expected`: the blocks that take a ticket.
 // sh: the block's LDS array (block_merge_topk's; at least one word), free for reuse when this returns.
-// sh must not be live across this call: sh[0] carries the "I am last" word (block_merge_topk's reads of sh end before the
+// sh must not be live across this call: sh[0] carries the "I am last" word (code8_block_merge's reads of sh end before the
 // first barrier here, and its next writes come after the last one).
 __device__ __forceinline__ bool code8_last_arriver(unsigned int* ticket, unsigned int expected, uint64_t* sh) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (every wave: only wave 0 has list stores in flight)
@@ -417,12 +440,56 @@ __device__ __forceinline__ bool code8_last_arriver(unsigned int* ticket, unsigne
     return last;
 }
 
+// The bar of a set of sorted k-lists: the best k-th key any of them holds.  That list alone has k keys at or above the bar, so
+// no key below it is among the k best of the union: such keys are dropped before the inserts, which are serial (about
+// 0.1 us each) and would otherwise take most keys of most lists — every list holds the best of its own rows.  0 (no list is
+// full) drops nothing.  Keys are distinct (score, row): the k best of the union are the same keys with and without the bar.
+__device__ __forceinline__ uint64_t code8_wave_max(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t code8_lists_bar(uint64_t* lists, int nlists, int k) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint64_t bar = 0ull;
+    for (int l = lane; l < nlists; l += kWave) {
+        const uint64_t v = code8_load_list(lists, (int64_t)l * k + (k - 1));
+        bar = v > bar ? v : bar;
+    }
+    return code8_wave_max(bar);
+}
+// block_merge_topk with the bar of the waves' lists: the sorted lists of all waves of the block into wave 0's list.
+// sh must hold (nwaves - 1) * 64 keys.  Must be called by every thread of the block.
+__device__ __forceinline__ void code8_block_merge(WaveTopK& tk, uint64_t* sh, int nwaves) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    if (wave > 0) sh[(wave - 1) * kWave + lane] = tk.key;
+    __syncthreads();
+    if (wave == 0) {
+        uint64_t bar = tk.thr;
+        for (int w = 0; w < nwaves - 1; ++w) {
+            const uint64_t v = sh[w * kWave + tk.k - 1];
+            bar = v > bar ? v : bar;
+        }
+        for (int w = 0; w < nwaves - 1; ++w) {
+            const uint64_t c = sh[w * kWave + lane];
+            tk.offer(c >= bar ? c : 0ull);
+        }
+    }
+}
+
 // The waves of the block share the nlists k-lists out (merge_keys_kernel's walk: UNROLL x 64 keys per wave and step, loaded
 // before any is offered), merge into wave 0's list.  Few lists: short steps, so that every wave has a share.
 template <int UNROLL>
-__device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, uint64_t* lists, int64_t total, int nwaves) {
+__device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, uint64_t* lists, int nlists, int k, int nwaves) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
+    const int64_t total = (int64_t)nlists * k;
+    uint64_t bar = 0ull;
+    bool have_bar = false;
     for (int64_t base = (int64_t)wave * kWave * UNROLL; base < total; base += (int64_t)nwaves * kWave * UNROLL) {
         uint64_t c[UNROLL];
 #pragma unroll
@@ -430,18 +497,21 @@ __device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, uint64_t* lists,
             const int64_t i = base + j * kWave + lane;
             c[j] = i < total ? code8_load_list(lists, i) : 0ull;
         }
+        // (every wave for itself, behind its first keys' loads: one round trip for both, no barrier)
+        if (!have_bar) bar = code8_lists_bar(lists, nlists, k);
+        have_bar = true;
 #pragma unroll
-        for (int j = 0; j < UNROLL; ++j) tk.offer(c[j]);
+        for (int j = 0; j < UNROLL; ++j) tk.offer(c[j] >= bar ? c[j] : 0ull);
     }
 }
 __device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists, int nlists, int k, uint64_t* sh, int nwaves) {
     const int64_t total = (int64_t)nlists * k;
     tk.init(k);
     if (total <= (int64_t)nwaves * kWave * 4)
-        code8_offer_lists<2>(tk, lists, total, nwaves);
+        code8_offer_lists<2>(tk, lists, nlists, k, nwaves);
     else
-        code8_offer_lists<kMergeUnroll>(tk, lists, total, nwaves);
-    block_merge_topk(tk, sh, nwaves);
+        code8_offer_lists<kMergeUnroll>(tk, lists, nlists, k, nwaves);
+    code8_block_merge(tk, sh, nwaves);
 }
 
 // ---- the floor: lower bounds of a sample of rows, from the codes -----------------------------------------------------------------
@@ -451,25 +521,55 @@ __device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists,
 // the final k-th best score does — the unchanged prefilter predicate !(ub < floor) keeps every row of the final top-k
 // (DESIGN.md section 4.1b).  Fewer than k lower bounds (or a k-th of -inf): floor = -FLT_MAX, everything passes, the call
 // falls back.  A NaN lb (0 * inf) fails the gate and never enters a list.
-// Roofline: latency of the gather; bytes = kCode8Seed * (d + 8).
+//
+// The index keeps the sample's codes and (a, r) a second time, slot i at i, in one allocation (kCode8Seed * (d + 8) bytes:
+// the codes, then the (a, r) entries); code8_sample_kernel gathers it whenever the code it copies was written (the rule:
+// code8_sample_gather in mvdb.hip).  The floor's launch streams that copy exactly as code8_scan_kernel streams the code.
+// Roofline: HBM; bytes = kCode8Seed * (d + 8).
 constexpr int64_t kCode8Seed = 131072;
 constexpr int kCode8SeedMaxThreads = 1024;
 constexpr int kCode8SeedThreads = 512;   // one block of this many per CU: measured
 
+__host__ __device__ inline int64_t code8_sample_row(int64_t slot, int64_t n) { return (slot * n) / kCode8Seed; }
+inline size_t code8_sample_bytes(int d) { return (size_t)kCode8Seed * ((size_t)d + sizeof(float2)); }
+
+// One thread per 16-byte chunk of a slot's codes; the thread of a slot's first chunk also copies its (a, r).
+__global__ __launch_bounds__(256) void code8_sample_kernel(const int8_t* __restrict__ codes, const float2* __restrict__ ar, int64_t n, int d,
+                                                           int8_t* __restrict__ scodes, float2* __restrict__ sar) {
+    const int d16 = d / 16;
+    const int64_t total = kCode8Seed * d16;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t slot = j / d16;
+        const int c = (int)(j - slot * d16);
+        const int64_t row = code8_sample_row(slot, n);
+        reinterpret_cast<i32x4*>(scodes + slot * d)[c] = reinterpret_cast<const i32x4*>(codes + row * d)[c];
+        if (c == 0) sar[slot] = ar[row];
+    }
+}
+
 struct Code8SeedArgs {
-    const int8_t* codes;
-    const float2* ar;
-    int64_t n;
+    const int8_t* scodes;   // [kCode8Seed, d] the stored sample (code8_sample_kernel)
+    const float2* sar;      // [kCode8Seed]
     int d;
-    const int8_t* qhi;
-    const int8_t* qlo;
-    const float* par;
+    const float* q;         // the query as the caller gave it
+    int normalize_q;
+    float row_norm_bound;
+    int8_t* qhi;            // out (block 0): the planes and the terms, for the prefilter and the re-score
+    int8_t* qlo;
+    float* par;
+    unsigned long long* counter;   // out (block 0): the candidate counter, zeroed
+    unsigned int* rescore_ticket;  // out (block 0): zeroed
     int k;
     uint64_t* lists;        // [gridDim.x, k]
-    unsigned int* ticket;   // zeroed by code8_query_kernel
+    unsigned int* ticket;   // this launch's own: see below
     float* floor;
 };
 
+// Every block computes the query's image itself (code8_query_image: the same bits in every block) and takes the planes from
+// LDS; block 0 also leaves the image and the zeroed counter words in the workspace for the launches behind this one.
+// The launch's own ticket cannot be zeroed by the launch that counts on it.  It is zero when the workspace is allocated
+// (code8_search), and every launch leaves it at zero: every block of the grid takes exactly one ticket — there is no path
+// from the kernel's entry to code8_last_arriver that returns — so the gridDim.x-th arriver exists and writes the zero back.
 template <int G, int U, bool MASKED>
 __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8SeedArgs a) {
     constexpr int RPI = kWave / G;
@@ -477,6 +577,8 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
     static_assert(U >= 2 && U <= 8 && (U & (U - 1)) == 0 && U <= G, "code8_reduce halves U down to one value inside a row group");
     static_assert(kCode8Seed % RB == 0, "the sample is whole batches");
     __shared__ uint64_t sh[(kCode8SeedMaxThreads / kWave - 1) * kWave];
+    __shared__ Code8QueryShared shq;
+    __shared__ __attribute__((aligned(16))) int8_t splanes[2 * kCode8MaxDim];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
@@ -484,38 +586,63 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
     const int g = lane / G;
     const bool valid = !MASKED || t * 16 < a.d;
 
-    i32x4 qh = {0, 0, 0, 0}, ql = {0, 0, 0, 0};
-    if (valid) {
-        qh = *reinterpret_cast<const i32x4*>(a.qhi + t * 16);
-        ql = *reinterpret_cast<const i32x4*>(a.qlo + t * 16);
-    }
-    const float qstep = a.par[0], alpha = a.par[1], beta = a.par[2];
-
     int ue = 0;
 #pragma unroll
     for (int m = 1, h = U / 2; m < U; m <<= 1, h >>= 1) ue += (t & m) ? h : 0;
     const int erow = ue * RPI + g;
     const bool reports = t < U;
 
-    WaveTopK tk;
-    tk.init(a.k);
-
-    const int64_t n = a.n;
-    auto sample_row = [&](int64_t i) { return (i * n) / kCode8Seed; };
-    auto load = [&](i32x4 (&x)[U], float2& sr, int64_t& er, int64_t b) {
+    // code8_scan_kernel's load over the stored sample: one base per batch + the constant lane offset + u row-group strides
+    const int64_t batch_bytes = (int64_t)RB * a.d;
+    const int64_t group_bytes = (int64_t)RPI * a.d;
+    const int lane_off = g * a.d + t * 16;
+    auto load = [&](i32x4 (&x)[U], float2& sr, int64_t b) {
+        const int8_t* base = a.scodes + b * batch_bytes + lane_off;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t r = sample_row(b * RB + (int64_t)u * RPI + g);
-            const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + r * (int64_t)a.d + t * 16);
+            const i32x4* src = reinterpret_cast<const i32x4*>(base + u * group_bytes);
             if (MASKED)
                 x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
             else
                 x[u] = __builtin_nontemporal_load(src);
         }
-        er = sample_row(b * RB + erow);
-        sr = a.ar[er];
+        sr = a.sar[b * RB + erow];
     };
-    auto consume = [&](const i32x4 (&x)[U], float2 sr, int64_t er) {
+
+    // the wave's first batch does not depend on the query: its loads are in flight while the image is computed
+    const int64_t nb = kCode8Seed / RB;
+    const int64_t stride = (int64_t)gridDim.x * nwaves;
+    int64_t b = (int64_t)blockIdx.x * nwaves + wave;
+    i32x4 x[U];
+    float2 sr = make_float2(0.f, 0.f);
+    if (b < nb) load(x, sr, b);
+
+    float par[4];
+    code8_query_image(a.q, a.d, a.normalize_q, a.row_norm_bound, splanes, splanes + kCode8MaxDim, par, shq);
+    if (blockIdx.x == 0) {
+        for (int j = threadIdx.x; j < a.d; j += blockDim.x) {
+            a.qhi[j] = splanes[j];
+            a.qlo[j] = splanes[kCode8MaxDim + j];
+        }
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a.par[j] = par[j];
+            *a.counter = 0ull;
+            *a.rescore_ticket = 0u;
+        }
+    }
+    i32x4 qh = {0, 0, 0, 0}, ql = {0, 0, 0, 0};
+    if (valid) {
+        qh = *reinterpret_cast<const i32x4*>(splanes + t * 16);
+        ql = *reinterpret_cast<const i32x4*>(splanes + kCode8MaxDim + t * 16);
+    }
+    const float qstep = par[0], alpha = par[1], beta = par[2];
+
+    WaveTopK tk;
+    tk.init(a.k);
+
+    // (the key's row is the SLOT: only the scores decide the floor)
+    auto consume = [&](const i32x4 (&x)[U], float2 sr, int64_t b) {
         int T[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -533,35 +660,24 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
         m = fmaf(fabsf(s) + m, 2.4e-7f, m);
         const float lb = s - m;
         const bool pass = reports && lb >= tk.thr_score;   // NaN fails
-        if (__ballot(pass)) tk.offer(pass ? make_key(lb, (uint32_t)er) : 0ull);
+        if (__ballot(pass)) tk.offer(pass ? make_key(lb, (uint32_t)(b * RB + erow)) : 0ull);
     };
 
-    // the next batch's loads are issued before this batch is consumed: a gathered row is a fresh DRAM page
-    const int64_t nb = kCode8Seed / RB;
-    const int64_t stride = (int64_t)gridDim.x * nwaves;
-    int64_t b = (int64_t)blockIdx.x * nwaves + wave;
-    if (b < nb) {
-        i32x4 x[U];
-        float2 sr;
-        int64_t er;
-        load(x, sr, er, b);
-        for (; b < nb; b += stride) {
-            i32x4 xn[U];
-            float2 srn = sr;
-            int64_t ern = er;
-            const int64_t bn = b + stride;
-            if (bn < nb) load(xn, srn, ern, bn);
-            consume(x, sr, er);
-            if (bn < nb) {
+    // the next batch's loads are issued before this batch is consumed
+    for (; b < nb; b += stride) {
+        i32x4 xn[U];
+        float2 srn = sr;
+        const int64_t bn = b + stride;
+        if (bn < nb) load(xn, srn, bn);
+        consume(x, sr, b);
+        if (bn < nb) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) x[u] = xn[u];
-            }
-            sr = srn;
-            er = ern;
+            for (int u = 0; u < U; ++u) x[u] = xn[u];
         }
+        sr = srn;
     }
 
-    block_merge_topk(tk, sh, nwaves);
+    code8_block_merge(tk, sh, nwaves);
     if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
     if (!code8_last_arriver(a.ticket, gridDim.x, sh)) return;
     code8_merge_lists(tk, a.lists, (int)gridDim.x, a.k, sh, nwaves);
@@ -596,7 +712,7 @@ struct Code8RescoreArgs {
     const float* par;
     int rows_per_block;
     uint64_t* lists;        // [gridDim.x, k]
-    unsigned int* ticket;   // zeroed by code8_query_kernel
+    unsigned int* ticket;   // zeroed by code8_seed_kernel's block 0
     int* gate;
     unsigned int* ctr_dev;  // [0] fallbacks, [1] calls
     volatile unsigned int* stats;
@@ -730,7 +846,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_rescore_kernel(Code8Rescor
         for (int u = 0; u < U; ++u) pr[u] = pn[u];
     }
 
-    block_merge_topk(tk, sh, kScanWaves);
+    code8_block_merge(tk, sh, kScanWaves);
     if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
     if (!code8_last_arriver(a.ticket, (unsigned int)active, sh)) return;
     code8_merge_lists(tk, a.lists, active, a.k, sh, kScanWaves);

@@ -326,6 +326,9 @@ struct mvdb_index {
     mutable float2* c8_ar = nullptr;
     mutable std::atomic<bool> c8_wanted{false};   // an eligible single query has asked for the code since the index was created / reset
     mutable int64_t c8_cap = 0, c8_rows = 0;
+    // the stored copy of the floor's sample (code8_sample_kernel; the rule: code8_sample_gather): codes, then (a, r) entries
+    mutable int8_t* c8_samp = nullptr;
+    mutable int64_t c8_samp_n = 0;   // the row count the copy was gathered for, after the last write to the code; 0 = stale
     mutable std::atomic<bool> c8_failed{false};
     mutable std::atomic<int> c8_wait{0};       // single queries the exact scan still answers before a dropped code is rebuilt
     mutable unsigned int* c8_ctr_dev = nullptr;   // [0] fallbacks, [1] calls
@@ -517,6 +520,7 @@ int scan_resident_blocks(const void* kern, int C, bool knob = true) {
 
 // the widths of the int8 prefilter (code8_scan.hpp) and the exact-scan shapes they have
 constexpr int kCode8Dims[] = {384, 512, 1024};
+static_assert(kCode8Dims[2] <= kCode8MaxDim, "code8_seed_kernel holds the query's planes in LDS");
 bool code8_dim(int d) { return std::find(std::begin(kCode8Dims), std::end(kCode8Dims), d) != std::end(kCode8Dims); }
 constexpr bool code8_shape(int G, int C) {
     for (int d : kCode8Dims)
@@ -1873,15 +1877,17 @@ bool stream_capturing(hipStream_t s) {
 void drop_code8(const mvdb_index* idx, bool count_rebuild = true) {
     if (idx->C8) (void)hipFree(idx->C8);
     if (idx->c8_ar) (void)hipFree(idx->c8_ar);
+    if (idx->c8_samp) (void)hipFree(idx->c8_samp);
     idx->C8 = nullptr;
     idx->c8_ar = nullptr;
-    idx->c8_cap = idx->c8_rows = 0;
+    idx->c8_samp = nullptr;
+    idx->c8_cap = idx->c8_rows = idx->c8_samp_n = 0;
     if (count_rebuild && idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
 }
 // rows were renumbered: emptied, the allocation kept (invalidate_shadow)
 void invalidate_code8(const mvdb_index* idx) {
     if (idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
-    idx->c8_rows = 0;
+    idx->c8_rows = idx->c8_samp_n = 0;
 }
 
 int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t s) {
@@ -1894,10 +1900,29 @@ int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t
     return 0;
 }
 
+// The stored copy of the floor's sample.  It is VALID iff the code is complete (c8_rows == n) and the copy was gathered for
+// this n after the last write to the code (c8_samp_n == n): code8_sample_valid is the only test, this function the only
+// writer.  Every writer of the code calls it behind its code8_build_kernel launch, on the same stream, with the row count the
+// index will have (ensure_code8: a build; extend_code8: add, where n moves and with it every slot; set_rows_core: rows
+// rewritten in place — a captured graph of the route stays valid across that, so the copy follows eagerly); the paths that
+// empty or free the code (invalidate_code8, drop_code8) mark it stale or free it with the code.  Nothing here runs inside a
+// stream capture: ensure_code8 refuses before it gets here, the mutators run on idx->mut.
+int code8_sample_gather(const mvdb_index* idx, int64_t n, hipStream_t s) {
+    idx->c8_samp_n = 0;
+    const int64_t chunks = kCode8Seed * (idx->d / 16);
+    const int grid = (int)std::min<int64_t>((chunks + 255) / 256, (int64_t)device_cus(idx->device) * 16);
+    hipLaunchKernelGGL(code8_sample_kernel, dim3(grid), dim3(256), 0, s, (const int8_t*)idx->C8, (const float2*)idx->c8_ar, n, idx->d,
+                       idx->c8_samp, reinterpret_cast<float2*>(idx->c8_samp + kCode8Seed * idx->d));
+    MVDB_HIP(hipGetLastError());
+    idx->c8_samp_n = n;
+    return 0;
+}
+bool code8_sample_valid(const mvdb_index* idx) { return idx->c8_samp && idx->c8_rows == idx->n && idx->c8_samp_n == idx->n; }
+
 // The code for a single query on stream s (caller holds the index shared).  false: the exact scan serves this call.
 bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    if (idx->C8 && idx->c8_rows == idx->n) return true;
+    if (idx->C8 && code8_sample_valid(idx)) return true;   // (complete code AND a current copy of the floor's sample)
     if (idx->c8_failed || stream_capturing(s)) return false;
     idx->c8_wanted.store(true);
     if (idx->c8_wait.load(std::memory_order_relaxed) > 0) {
@@ -1908,7 +1933,8 @@ bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
     if (!idx->C8) {
         const int64_t cap = std::max<int64_t>(idx->cap, idx->n);
         bool ok = hipMalloc((void**)&idx->C8, (size_t)cap * idx->d) == hipSuccess &&
-                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess;
+                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess &&
+                  hipMalloc((void**)&idx->c8_samp, code8_sample_bytes(idx->d)) == hipSuccess;
         if (ok && !idx->c8_ctr_dev) {
             ok = hipMalloc((void**)&idx->c8_ctr_dev, 2 * sizeof(unsigned int)) == hipSuccess &&
                  hipMemset(idx->c8_ctr_dev, 0, 2 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
@@ -1923,7 +1949,8 @@ bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
         idx->c8_cap = cap;
         idx->c8_rows = 0;
     }
-    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, s) != 0 || hipStreamSynchronize(s) != hipSuccess) {
+    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, s) != 0 || code8_sample_gather(idx, idx->n, s) != 0 ||
+        hipStreamSynchronize(s) != hipSuccess) {
         drop_code8(idx, false);
         idx->c8_failed = true;
         return false;
@@ -1995,7 +2022,7 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
                            "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 
-// The floor's launch.  The gather is bound by latency, the last block's merge by inserts: wide blocks keep the lists few.
+// The floor's launch.  The stored sample streams; the last block's merge is bound by inserts: wide blocks keep the lists few.
 // (grid shapes measured: DESIGN.md section 4.1b)
 template <int G, int U, bool MASKED>
 int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream) {
@@ -2041,9 +2068,12 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     if (capturing && (ws->c8.cap < off || ws->cand.cap < cand_keys)) return 0;  // nothing is allocated inside a capture
     if (code8_suspended(idx)) return 0;
     if (!ensure_code8(idx, s)) return 0;
+    const bool fresh = ws->c8.cap < off;
     MVDB_TRY(ws->c8.reserve(off));
     MVDB_TRY(ws->cand.reserve(cand_keys));
     char* base = ws->c8.p;
+    // a new workspace: the floor launch's ticket starts at zero; from then on every launch leaves it there (code8_seed_kernel)
+    if (fresh) MVDB_HIP(hipMemsetAsync(base + o_ctr, 0, 2 * sizeof(unsigned long long), s));
     int8_t* qhi = reinterpret_cast<int8_t*>(base + o_planes);
     int8_t* qlo = qhi + d;
     float* par = reinterpret_cast<float*>(base + o_par);
@@ -2053,19 +2083,20 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     float* floor = reinterpret_cast<float*>(base + o_floor);
     uint32_t* cand = reinterpret_cast<uint32_t*>(base + o_cand);
 
-    // 1. the query's planes and margin terms; zeroes the candidate counter and both tickets
-    hipLaunchKernelGGL(code8_query_kernel, dim3(1), dim3(256), 0, s, a0.q, d, a0.normalize_q, idx->row_norm_bound, qhi, qlo, par, counter);
-    MVDB_HIP(hipGetLastError());
-
-    // 2. the floor: the k-th best LOWER bound of the seed sample, from the codes
+    // 1. the query's planes and margin terms (every block; block 0 leaves them here and zeroes the candidate counter and the
+    //    re-score's ticket), and the floor: the k-th best LOWER bound of the seed sample, from its stored copy
     Code8SeedArgs sd;
-    sd.codes = idx->C8;
-    sd.ar = idx->c8_ar;
-    sd.n = idx->n;
+    sd.scodes = idx->c8_samp;
+    sd.sar = reinterpret_cast<const float2*>(idx->c8_samp + kCode8Seed * d);
     sd.d = d;
+    sd.q = a0.q;
+    sd.normalize_q = a0.normalize_q;
+    sd.row_norm_bound = idx->row_norm_bound;
     sd.qhi = qhi;
     sd.qlo = qlo;
     sd.par = par;
+    sd.counter = counter;
+    sd.rescore_ticket = tickets + 1;
     sd.k = k;
     sd.lists = ws->cand.p;
     sd.ticket = tickets;
@@ -2074,7 +2105,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         using K = decltype(cs);
         return launch_code8_seed<K::G, K::U, K::MASKED>(sd, idx->device, s);
     }));
-    // 3. the prefilter over the codes
+    // 2. the prefilter over the codes
     Code8ScanArgs c;
     c.codes = idx->C8;
     c.ar = idx->c8_ar;
@@ -2091,7 +2122,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         using K = decltype(cs);
         return launch_code8_scan<K::G, K::U, K::MASKED>(c, idx->device, s);
     }));
-    // 4. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
+    // 3. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
     Code8RescoreArgs r;
     r.X = a0.X;
     r.ld = a0.ld;
@@ -2117,7 +2148,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         using S = decltype(shape);
         return launch_code8_rescore<S::G, S::C, rescore_u(S::G, S::C), false>(r, idx->device, s);
     }));
-    // 5. fallback, enabled on the device: the full exact scan overwrites the result
+    // 4. fallback, enabled on the device: the full exact scan overwrites the result
     ScanArgs a = a0;
     a.cand = ws->cand.p;
     int nblocks = 0;
@@ -2451,6 +2482,7 @@ static int extend_code8(mvdb_index* idx, int64_t n_new) {
     }
     if (idx->c8_rows != idx->n) return 0;  // emptied by a delete: the next eligible query codes every row again
     MVDB_TRY(code8_convert(idx, idx->n, n_new, idx->mut));
+    MVDB_TRY(code8_sample_gather(idx, idx->n + n_new, idx->mut));   // n moves: every slot of the floor's sample does
     MVDB_HIP(hipStreamSynchronize(idx->mut));
     idx->c8_rows = idx->n + n_new;
     return 0;
@@ -2608,6 +2640,8 @@ static int set_rows_core(mvdb_index* idx, const int64_t* rows_host, const float*
             hipLaunchKernelGGL(code8_build_kernel, dim3(g8), dim3(256), 0, idx->mut, (const float*)idx->X, idx->ld, idx->d, rows, idx->C8,
                                idx->c8_ar, (const int64_t*)L, idx->c8_rows);
             MVDB_HIP(hipGetLastError());
+            // a listed row may be one of the floor's sample: the whole copy is gathered again (a fixed 131,072 rows)
+            if (code8_sample_valid(idx)) MVDB_TRY(code8_sample_gather(idx, idx->n, idx->mut));
         }
         // (waits for the chunk: the staging buffers are free again, and so is the caller's part of x)
         MVDB_TRY(note_row_norms(idx, idx->X, rows, normalize, L));
