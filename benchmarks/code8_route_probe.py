@@ -2,11 +2,15 @@
 """The single-query int8 route beside the exact fp32 scan, in ONE process and on one corpus.
 
 Per configuration one JSON line: the prefilter launch's own mean duration (the library's `ip_scan` timer), its true rate on
-N (d + 8) bytes, the wall time per query, and whether (D, I) of the first queries equal the exact scan's bit for bit.  The
-last line is the exact scan (`code8_single_query = 0`): its launch time and rate on N d 4 bytes.
+its own bytes — N (3 d / 4 + 8) for the high plane and (a, r), plus d / 4 for every row whose low plane it fetched (the rows
+its first stage could not reject: `refined_per_query`) — the wall time per query, the candidates of the timed queries
+(min / median / max), and whether (D, I) of the first queries equal the exact scan's bit for bit.  The last line is the exact
+scan (`code8_single_query = 0`): its launch time and rate on N d 4 bytes.  (Run from a checkout from before the two planes —
+this file copied into its benchmarks/ — the index has no count of refined rows and the launch is rated on N (d + 8).)
 
   python3 benchmarks/code8_route_probe.py                              # 10M x 512, the grid the library picks
   python3 benchmarks/code8_route_probe.py --blocks 2,3,4               # MVDB_SCAN_BLOCKS_PER_CU swept in-process
+  python3 benchmarks/code8_route_probe.py --family positive            # the all-positive corpus (or: clustered)
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 benchmarks/code8_route_probe.py --timers 0
       (one trace session with both kernels: 200 route steps, then 40 exact scans; --timers 0 keeps the library's event
        pairs out of the stream, so the gaps in the trace are the route's own)
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--exact-steps", type=int, default=40)
     ap.add_argument("--blocks", default="0", help="comma list of MVDB_SCAN_BLOCKS_PER_CU values (0 = the library's choice)")
+    ap.add_argument("--family", default="zero_mean", choices=["zero_mean", "positive", "clustered"], help="the synthetic corpus and its queries")
     ap.add_argument("--timers", type=int, default=1, help="0: no per-launch event timers (for runs under a tracer)")
     args = ap.parse_args()
 
@@ -37,14 +42,15 @@ def main():
     from minivectordb_amd import _native as native
 
     n, d, k = args.rows, args.dim, args.k
+    flag = {"zero_mean": 0, "positive": 1 << 56, "clustered": 2 << 56}[args.family]   # (oracle.flat.SYNTH_*)
     W, K = args.warmup, args.steps
     dev = torch.device("cuda", 0)
     idx = native.FlatIndex(d, device=0)
     idx.reserve(n)
-    idx.add_synthetic(n, 1234, normalize=True)
+    idx.add_synthetic(n, 1234 | flag, normalize=True)
     nqs = W + K
     queries = torch.empty((nqs, d), dtype=torch.float32, device=dev)
-    native.check(native.lib().mvdb_synth_fill_device(queries.data_ptr(), nqs, d, 5678, 0, 1, 0, torch.cuda.current_stream().cuda_stream))
+    native.check(native.lib().mvdb_synth_fill_device(queries.data_ptr(), nqs, d, 5678 | flag, 0, 1, 0, torch.cuda.current_stream().cuda_stream))
     D = torch.empty((1, k), dtype=torch.float32, device=dev)
     I = torch.empty((1, k), dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
@@ -61,14 +67,20 @@ def main():
             out.append((D.cpu().numpy().view(np.uint32).copy(), I.cpu().numpy().copy()))
         return out
 
+    planes = hasattr(idx, "code8_refined")
+
     def measure(steps, bytes_per_launch, label):
         run(0, W)
         native.prof_read("ip_scan")
+        refined = idx.code8_refined() if planes else 0
         native.prof_enable(bool(args.timers))
         t0 = time.perf_counter()
         run(W, steps)
         dt = time.perf_counter() - t0
         native.prof_enable(False)
+        if label["route"] == "code8" and planes:
+            label = dict(label, refined_per_query=round((idx.code8_refined() - refined) / steps, 1))
+            bytes_per_launch = n * (d // 4 * 3 + 8) + int(label["refined_per_query"] * (d // 4))
         launches, ms = native.prof_read("ip_scan")
         avg = ms / max(launches, 1)
         rec = dict(label, rows=n, dim=d, k=k, steps=steps, kernel=native.prof_symbol("ip_scan"), launches=launches,
@@ -88,7 +100,12 @@ def main():
         same = all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(got, want))
         rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks)})
         fb, cand, calls = idx.code8_counters()
-        rec.update(bit_equal_exact_scan=bool(same), fallbacks=fb, last_candidates=cand)
+        cands = []
+        for i in range(W, W + min(K, 32)):
+            run(i, 1)
+            cands.append(idx.code8_counters()[1])
+        rec.update(bit_equal_exact_scan=bool(same), fallbacks=fb, last_candidates=cand, family=args.family,
+                   candidates_min_median_max=[int(min(cands)), float(np.median(cands)), int(max(cands))], candidates=cands)
         print(json.dumps(rec), flush=True)
     os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = ""
     idx.reload_env()

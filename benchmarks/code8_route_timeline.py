@@ -7,7 +7,11 @@ common number of launches are averaged (the first ones build the code).  Prints 
 launches in order with their mean / median duration, the mean gap before each, their sums, the mean step span, and the
 mean duration of the exact scan's launches (steps with `code8_single_query = 0`) where the trace has them.
 
-usage: code8_route_timeline.py <trace dir or csv> [git-head]"""
+With the corpus' shape the prefilter launch (`code8_scan_kernel`) is also rated on its own streamed bytes: N (3 d / 4 + 8) — the
+high plane of the code and (a, r) — for a build with the two planes (`planes` = 1, the default), N (d + 8) for a build from
+before them (`planes` = 0).  The low plane of the refined rows (d / 4 bytes each, a few thousand rows) is not in the figure.
+
+usage: code8_route_timeline.py <trace dir or csv> [git-head [rows dim [planes]]]"""
 import collections
 import csv
 import glob
@@ -52,6 +56,14 @@ def main():
            "exact_scan_launches": len(exact),
            "exact_scan_mean_us": round(statistics.mean(exact) / 1e3, 3) if exact else None,
            "exact_scan_median_us": round(statistics.median(exact) / 1e3, 3) if exact else None}
+    if len(sys.argv) > 4:
+        n, d = int(sys.argv[3]), int(sys.argv[4])
+        planes = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+        nbytes = n * (d // 4 * 3 + 8) if planes else n * (d + 8)
+        pre = [l for l in launches if "code8_scan_kernel" in l["kernel"]]
+        if pre:
+            out.update(prefilter_streamed_bytes=nbytes, prefilter_mean_us=pre[0]["mean_us"],
+                       prefilter_tb_per_s=round(nbytes / (pre[0]["mean_us"] * 1e-6) / 1e12, 4))
     print(json.dumps(out, indent=1))
 
 

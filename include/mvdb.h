@@ -109,7 +109,9 @@ int mvdb_index_device(const mvdb_index* idx);
  * No reference counterpart. */
 int64_t mvdb_index_shadow_rows(const mvdb_index* idx);
 
-/* Rows held in the index' int8 CODE (0: none): d int8 values, an fp32 scale and an fp32 bound of the coding residual per row
+/* Rows held in the index' int8 CODE (0: none): d int8 values per row, stored as two planes in the same d bytes — the top 6
+ * bits of every code (3 d / 4 bytes per row, the plane the prefilter streams) and the low 2 bits (d / 4 bytes per row, fetched
+ * only for the rows the first plane cannot reject: mvdb_code8_pack) — an fp32 scale and an fp32 bound of the coding residual
  * (+25 % of the index's device memory at d = 512, and a fixed 131,072 x (d + 8) bytes for a second, contiguous copy of the
  * sampled rows the route takes its floor from), the operand of the single-query prefilter (option "code8_single_query").
  * Built by the first eligible single query (one blocking conversion pass and the allocations inside that call; never while the
@@ -129,6 +131,20 @@ int mvdb_index_code8_counters(const mvdb_index* idx, long long* fallbacks, long 
  * and a query image of norm <= qnorm rounded with step qstep, the fp32 score the exact kernel computes lies within
  * alpha * r + beta of the coded score.  Pure host arithmetic (no device needed). */
 int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta);
+
+/* The two planes of the code: the d int8 codes of one row (d a multiple of 16) <-> the 3 d / 4 bytes
+ * of its high plane (the top 6 bits of every code) and the d / 4 bytes of its low plane (the low 2 bits).  The very functions
+ * the device code packs and unpacks 16-code chunks with.  Pure host arithmetic (no device needed). */
+int mvdb_code8_pack(int d, const int8_t* codes, uint8_t* high, uint8_t* low);
+int mvdb_code8_unpack(int d, const uint8_t* high, const uint8_t* low, int8_t* codes);
+
+/* Diagnostic: how the prefilter's launch shares n rows of width d (384 / 512 / 1024) out on `device`: wave w of `waves`
+ * takes the batches w, w + waves, ... of rows_per_batch consecutive rows.  Tests plant rows by it. */
+int mvdb_code8_scan_geometry(int d, int64_t n, int device, int* rows_per_batch, int* waves);
+
+/* Diagnostic: the rows whose low plane the prefilter has fetched (the rows its first stage could not reject), summed over
+ * all calls on this index since the code's counters were allocated.  Reads a device word: synchronises with the device. */
+int mvdb_index_code8_refined(const mvdb_index* idx, long long* rows);
 
 /* Reserve device capacity for at least n rows in total (amortises repeated add). */
 int mvdb_index_reserve(mvdb_index* idx, int64_t n);

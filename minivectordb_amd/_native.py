@@ -67,6 +67,10 @@ PROTOTYPES = {
     "mvdb_index_code8_rows": (ctypes.c_int64, [c_vp]),
     "mvdb_index_code8_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mvdb_code8_margin": (ctypes.c_int, [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp]),
+    "mvdb_code8_pack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_code8_unpack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_index_code8_refined": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_code8_scan_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_dim": (ctypes.c_int, [c_vp]),
     "mvdb_index_device": (ctypes.c_int, [c_vp]),
     "mvdb_index_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
@@ -284,6 +288,12 @@ class FlatIndex:
         v = [ctypes.c_longlong(0) for _ in range(3)]
         check(lib().mvdb_index_code8_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def code8_refined(self):
+        """Rows whose low plane the prefilter has fetched, over all calls so far (diagnostic; synchronises with the device)."""
+        v = ctypes.c_longlong(0)
+        check(lib().mvdb_index_code8_refined(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     def reset(self):
         check(lib().mvdb_index_reset(self._h))
@@ -848,3 +858,32 @@ def code8_margin(d, qnorm, qstep, row_norm_bound):
     a, b = ctypes.c_float(0), ctypes.c_float(0)
     check(lib().mvdb_code8_margin(int(d), float(qnorm), float(qstep), float(row_norm_bound), ctypes.byref(a), ctypes.byref(b)))
     return float(a.value), float(b.value)
+
+
+def code8_pack(codes):
+    """The (high, low) planes of one row of int8 codes, as uint8 arrays of 3 d / 4 and d / 4 bytes (include/mvdb.h: mvdb_code8_pack)."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    d = codes.shape[0]
+    high = np.empty(d // 4 * 3, np.uint8)
+    low = np.empty(d // 4, np.uint8)
+    check(lib().mvdb_code8_pack(int(d), codes.ctypes.data, high.ctypes.data, low.ctypes.data))
+    return high, low
+
+
+def code8_unpack(high, low):
+    """The int8 codes of one row from its two planes (include/mvdb.h: mvdb_code8_unpack)."""
+    high = np.ascontiguousarray(high, dtype=np.uint8)
+    low = np.ascontiguousarray(low, dtype=np.uint8)
+    d = low.shape[0] * 4
+    assert high.shape[0] == d // 4 * 3
+    codes = np.empty(d, np.int8)
+    check(lib().mvdb_code8_unpack(int(d), high.ctypes.data, low.ctypes.data, codes.ctypes.data))
+    return codes
+
+
+def code8_scan_geometry(d, n, device=0):
+    """(rows per batch, waves) of the prefilter's launch over n rows of width d: wave w takes batches w, w + waves, ...
+    (include/mvdb.h: mvdb_code8_scan_geometry)."""
+    rb, waves = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().mvdb_code8_scan_geometry(int(d), int(n), int(device), ctypes.byref(rb), ctypes.byref(waves)))
+    return int(rb.value), int(waves.value)

@@ -7,11 +7,18 @@
 // thousand of 10M — are then scored by code8_rescore_kernel with flat_scan_kernel's arithmetic: the bits of (D, I) are the full scan's.
 // The floor is the k-th best LOWER bound s~_i - m_i of a sample of rows (code8_seed_kernel): one launch in front of the pass.
 //
-// Roofline: HBM.  Algorithmic bytes per launch = n * (d + 8): every code once, 8 bytes of (a, r) per row.
+// The codes are stored as two planes in the same d bytes per row: the top 6 bits of every code (3 d / 4 bytes) and the low 2
+// bits (d / 4 bytes).  The pass streams the first plane only, bounds what the missing bits can add, and fetches the second
+// plane for the few rows that bound cannot reject: for those the integer sum is completed, so what is kept is what a pass
+// over whole codes keeps.
 //
-// Shape of the work (flat_scan_kernel's): G lanes share a row, one 16-byte chunk each (d = 512: G = 32, two rows per
-// wave-instruction), U row groups in flight per wave, non-temporal loads, a persistent grid, no branch between the loads of a
-// batch.  Per 16 bytes: eight v_dot4_i32_i8; per batch one halving reduction of the U sums and one epilogue (code8_reduce).
+// Roofline: HBM.  Algorithmic bytes per launch = n * (3 d / 4 + 8) + (rows refined) * d / 4: the high plane once, 8 bytes of
+// (a, r) per row, the low plane of the rows the first stage cannot reject.
+//
+// Shape of the work (flat_scan_kernel's): G lanes share a row, one 16-code chunk (12 bytes) each (d = 512: G = 32, two rows
+// per wave-instruction), U row groups in flight per wave, non-temporal loads, a persistent grid, no branch between the loads
+// of a batch.  Per chunk: nine and / shift / or, eight v_dot4_i32_i8; per batch one halving reduction of the U sums and one
+// epilogue (code8_reduce).
 #pragma once
 #include "scan_kernels.hpp"
 
@@ -45,18 +52,81 @@ __host__ __device__ inline Code8Margin code8_margin(int d, float qnorm, float qs
     m.beta = (float)(B * (dq + kap * (qn + dq) + (gam * (1.0 + eta) + eta) * qn) * up + 1e-30);
     return m;
 }
-// most |Q| of the rounded query: 127 * 256 where d * 127 * |Q| fits an int32 (d <= 512), 127 * 128 up to d = 1024
+// most |Q| of the rounded query: 127 * 256 where d * 127 * |Q| fits an int32 (d <= 512), 127 * 128 up to d = 1024.
+// The prefilter's first stage sums Q_j (H_j + 3 [Q_j > 0]) and Q_j H_j, H_j = c_j & ~3 (below): every factor lies in
+// [-128, 127], and d * 128 * qmax = 2,130,706,432 < 2^31 at both values, so those sums fit an int32 as well.
 __host__ __device__ inline int code8_qmax(int d) { return d <= 512 ? 32512 : 16256; }
 
 constexpr float kCode8Tiny = 1e-15f;  // a row (a query) whose largest |element| is below this is coded as zero: r = |x| bound
 
+// ---- the two planes of the code ---------------------------------------------------------------------------------------------------
+// The d int8 codes of a row are stored as two planes in the same d bytes.  A 16-code chunk t — the dwords A, B, C, D of the
+// codes 16 t .. 16 t + 15 — becomes
+//   12 bytes of the HIGH plane (row stride 3 d / 4, chunk t at 12 t): A', B', C' = A, B, C with the low 2 bits of every byte
+//      replaced by bits 7:6, 5:4, 3:2 of the matching byte of D — `x & 0xFCFCFCFC` is (c & ~3) of A, B, C as int8 dwords, and
+//      three and / shift / or give D & 0xFCFCFCFC;
+//   one dword of the LOW plane (row stride d / 4, chunk t at 4 t): the low 2 bits of A, B, C, D at bit pairs 0, 2, 4, 6 of
+//      every byte — `(l >> 2 i) & 0x03030303` is (c & 3) of dword i.
+// The low plane of an index lies behind its high plane at byte offset capacity * 3 d / 4 (capacity, not row count: add into
+// reserved space moves nothing).  c = (c & ~3) + (c & 3) with 0 <= (c & 3) <= 3 in two's complement: -127 = -128 + 1.
+constexpr uint32_t kCode8HiMask = 0xFCFCFCFCu, kCode8LoMask = 0x03030303u;
+__host__ __device__ inline int code8_high_stride(int d) { return d / 4 * 3; }
+__host__ __device__ inline int code8_low_stride(int d) { return d / 4; }
+__host__ __device__ inline size_t code8_low_offset(int64_t cap, int d) { return (size_t)cap * (size_t)code8_high_stride(d); }
+
+__host__ __device__ inline void code8_pack_chunk(const uint32_t (&c)[4], uint32_t (&h)[3], uint32_t& l) {
+    h[0] = (c[0] & kCode8HiMask) | ((c[3] >> 6) & kCode8LoMask);
+    h[1] = (c[1] & kCode8HiMask) | ((c[3] >> 4) & kCode8LoMask);
+    h[2] = (c[2] & kCode8HiMask) | ((c[3] >> 2) & kCode8LoMask);
+    l = (c[0] & kCode8LoMask) | ((c[1] & kCode8LoMask) << 2) | ((c[2] & kCode8LoMask) << 4) | ((c[3] & kCode8LoMask) << 6);
+}
+// (c & ~3) of the 16 codes, from the high plane alone
+__host__ __device__ inline void code8_unpack_high(const uint32_t (&h)[3], uint32_t (&c)[4]) {
+    c[0] = h[0] & kCode8HiMask;
+    c[1] = h[1] & kCode8HiMask;
+    c[2] = h[2] & kCode8HiMask;
+    c[3] = ((h[0] & kCode8LoMask) << 6) | ((h[1] & kCode8LoMask) << 4) | ((h[2] & kCode8LoMask) << 2);
+}
+// (c & 3) of the 16 codes
+__host__ __device__ inline void code8_unpack_low(uint32_t l, uint32_t (&c)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = (l >> (2 * i)) & kCode8LoMask;
+}
+__host__ __device__ inline void code8_unpack_chunk(const uint32_t (&h)[3], uint32_t l, uint32_t (&c)[4]) {
+    uint32_t lo[4];
+    code8_unpack_high(h, c);
+    code8_unpack_low(l, lo);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] |= lo[i];
+}
+// d codes of one row <-> its d * 3 / 4 high-plane bytes and d / 4 low-plane bytes (host: mvdb_code8_pack / mvdb_code8_unpack)
+inline void code8_pack_row(int d, const int8_t* codes, uint8_t* high, uint8_t* low) {
+    for (int t = 0; t < d / 16; ++t) {
+        uint32_t c[4], h[3], l;
+        memcpy(c, codes + 16 * t, 16);
+        code8_pack_chunk(c, h, l);
+        memcpy(high + 12 * t, h, 12);
+        memcpy(low + 4 * t, &l, 4);
+    }
+}
+inline void code8_unpack_row(int d, const uint8_t* high, const uint8_t* low, int8_t* codes) {
+    for (int t = 0; t < d / 16; ++t) {
+        uint32_t c[4], h[3], l;
+        memcpy(h, high + 12 * t, 12);
+        memcpy(&l, low + 4 * t, 4);
+        code8_unpack_chunk(h, l, c);
+        memcpy(codes + 16 * t, c, 16);
+    }
+}
+
 // ---- build: rows [0, n) of X -> codes, (a, r) ------------------------------------------------------------------------------------
 // One wave per row.  a = max|x| / 127, c = rint(x / a); r = sqrt(sum (x - a c)^2) rounded up.  A row with a non-finite element
 // gets zero codes and r = +inf: it is always a candidate and the exact kernel treats it as it always has.
-// list == NULL: rows [0, n) behind the three pointers.  list != NULL (set_rows): the n stored rows list[0 .. n), the pointers
+// list == NULL: rows [0, n) behind the four pointers.  list != NULL (set_rows): the n stored rows list[0 .. n), the pointers
 // at row 0; a listed row at or above `limit` (not coded yet) is skipped.
+// The codes go out as the two planes: a lane holds one dword of codes, the four lanes of a quad hold a 16-code chunk.
 __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restrict__ X, int64_t ld, int d, int64_t n,
-                                                          int8_t* __restrict__ codes, float2* __restrict__ ar,
+                                                          uint8_t* __restrict__ high, uint8_t* __restrict__ low, float2* __restrict__ ar,
                                                           const int64_t* __restrict__ list, int64_t limit) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -83,7 +153,9 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
         const bool tiny = mx < kCode8Tiny;
         const float a = (anybad || tiny) ? 0.f : mx / 127.0f;
         float r2 = 0.f;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(codes + row * (int64_t)d);
+        uint32_t* hdst = reinterpret_cast<uint32_t*>(high + row * (int64_t)code8_high_stride(d));
+        uint32_t* ldst = reinterpret_cast<uint32_t*>(low + row * (int64_t)code8_low_stride(d));
+        // (d is a multiple of 16: the lanes of a quad run the same iterations)
         for (int c = lane; c < d4; c += 64) {
             uint32_t word = 0;
             if (a > 0.f) {
@@ -97,7 +169,15 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
                     word |= ((uint32_t)(uint8_t)(int8_t)(int)cf) << (8 * j);
                 }
             }
-            dst[c] = word;
+            uint32_t chunk[4], h[3], l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) chunk[j] = (uint32_t)__shfl((int)word, (lane & ~3) + j);
+            code8_pack_chunk(chunk, h, l);
+            const int part = lane & 3;
+            if (part < 3)
+                hdst[3 * (c >> 2) + part] = part == 0 ? h[0] : part == 1 ? h[1] : h[2];
+            else
+                ldst[c >> 2] = l;
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) r2 += __shfl_xor(r2, m);
@@ -219,10 +299,12 @@ __device__ __forceinline__ void code8_query_image(const float* __restrict__ q, i
 
 // ---- the prefilter scan ---------------------------------------------------------------------------------------------------------
 struct Code8ScanArgs {
-    const int8_t* codes;   // [n, d]
+    const uint8_t* high;   // [n, 3 d / 4] the high plane: streamed
+    const uint8_t* low;    // [n, d / 4] the low plane: gathered for the rows the first stage cannot reject
     const float2* ar;      // [n] (a, r)
     int64_t n;
-    int d;                 // bytes per row (a multiple of 16)
+    int d;                 // codes per row (a multiple of 16)
+    int hstride;           // bytes per row of the high plane (code8_high_stride)
     const int8_t* qhi;     // [d] the query's high / low planes (code8_query_image, left by code8_seed_kernel's block 0)
     const int8_t* qlo;
     const float* par;      // qstep, alpha, beta
@@ -230,6 +312,7 @@ struct Code8ScanArgs {
     uint32_t* cand;        // [cap] appended rows, in no order
     int64_t cap;
     unsigned long long* counter;  // zeroed by code8_seed_kernel's block 0; keeps counting past cap
+    unsigned long long* survivors;  // diagnostic, never zeroed: the rows the first stage could not reject, over all calls
 };
 
 // lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
@@ -272,12 +355,21 @@ __device__ __forceinline__ int code8_reduce(int (&T)[U], int t) {
     }
 }
 
-// One wave takes batches of RB = (64 / G) U consecutive rows, U KiB of codes (d = 16 G; 768 U bytes at d = 384).  Per batch:
-// U 16-byte loads per lane at one base per batch + a lane offset that never changes + u row-group strides, ONE 8-byte load of
-// (a, r) (lane (g, t) reads the entry of the row whose total code8_reduce leaves in it), 8 U v_dot4_i32_i8, the reduction
-// above, and ONE epilogue + ballot for the RB rows of the batch (lanes t < U hold one row each).  Full batches run in a loop
-// without a row clamp or a row test; the one partial batch at the end of the index is done by the wave whose turn it is,
-// with both.
+// One wave takes batches of RB = (64 / G) U consecutive rows, 0.75 U KiB of the high plane (d = 16 G; 576 U bytes at d = 384).
+// Per batch: U 12-byte loads per lane at one base per batch + a lane offset that never changes + u row-group strides, ONE
+// 8-byte load of (a, r) (lane (g, t) reads the entry of the row whose total code8_reduce leaves in it), the unpacking of
+// (c & ~3) (code8_unpack_high), 8 U v_dot4_i32_i8, the reduction above, and ONE epilogue + ballot for the RB rows of the
+// batch (lanes t < U hold one row each).  Full batches run in a loop without a row clamp or a row test; the one partial batch
+// at the end of the index is done by the wave whose turn it is, with both.
+//
+// Two stages.  With H = c & ~3 the loop has T6 = Q . H, and the row's integer sum is T = T6 + Q . (c & 3) with
+// T6 - 3 N <= T <= T6 + 3 P, P (N) the sum of the positive (the magnitudes of the negative) Q_j.  Stage 1 evaluates the
+// predicate at the upper end (stage1 below: it passes every row the predicate passes at T — DESIGN.md section 4.1b) and
+// STAGES the (row, T6) pairs it cannot reject, one per lane.  When 64 are staged, and once at the wave's end, refine() gathers
+// the low plane of the staged rows — batches of RB staged rows, lane t the dword of chunk t, U gathers in flight — completes
+// T, and runs the predicate itself on T: what is appended is what the one-plane prefilter appended, row for row.
+typedef int i32x3 __attribute__((ext_vector_type(3), aligned(4)));
+
 template <int G, int U, bool MASKED>
 __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
@@ -296,6 +388,25 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     }
     const float qstep = a.par[0], alpha = a.par[1], beta = a.par[2];
     const float floor = *a.floor;
+
+    // 3 P and 3 N of the query, from the lane's planes (a masked lane holds zeros); at most 3 d qmax < 2^26
+    int p3 = 0, n3 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int Q = ((qh[j] << (24 - 8 * b)) >> 24) * 256 + ((ql[j] << (24 - 8 * b)) >> 24);
+            p3 += Q > 0 ? Q : 0;
+            n3 += Q < 0 ? -Q : 0;
+        }
+    }
+#pragma unroll
+    for (int m = G / 2; m >= 1; m >>= 1) {
+        p3 += __shfl_xor(p3, m);
+        n3 += __shfl_xor(n3, m);
+    }
+    p3 = __builtin_amdgcn_readfirstlane(p3) * 3;
+    n3 = __builtin_amdgcn_readfirstlane(n3) * 3;
 
     // the wave's staged rows (range_scan_kernel's append path)
     uint32_t stage = 0;
@@ -325,20 +436,24 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     const int erow = ue * RPI + g;
     const uint64_t elanes = __ballot(t < U);
 
-    auto scores = [&](const i32x4 (&x)[U], int (&T)[U]) {
+    // (c & ~3) of the lane's chunks against the query's planes: T6
+    auto scores = [&](const i32x3 (&x)[U], int (&T)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+            const uint32_t h[3] = {(uint32_t)x[u].x, (uint32_t)x[u].y, (uint32_t)x[u].z};
+            uint32_t c[4];
+            code8_unpack_high(h, c);
             int hi = 0, lo = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                hi = __builtin_amdgcn_sdot4(x[u][j], qh[j], hi, false);
-                lo = __builtin_amdgcn_sdot4(x[u][j], ql[j], lo, false);
+                hi = __builtin_amdgcn_sdot4((int)c[j], qh[j], hi, false);
+                lo = __builtin_amdgcn_sdot4((int)c[j], ql[j], lo, false);
             }
             T[u] = hi * 256 + lo;
         }
     };
-    // every lane evaluates the predicate (its (a, r) load is issued with the batch's code loads, not behind a lane test);
-    // `mine` keeps the bits of the lanes that report a row
+    // THE predicate, on the row's integer sum.  Every lane evaluates it (its (a, r) load is issued with the batch's loads, not
+    // behind a lane test); `mine` keeps the bits of the lanes that report a row
     auto epilogue = [&](int tot, float2 sr, uint64_t mine, int64_t r) {
         const float s = ((float)tot * qstep) * sr.x;
         float m = fmaf(alpha, sr.y, beta);
@@ -349,44 +464,113 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         if (pass) append(pass, (uint32_t)r);
     };
 
+    // ---- stage 2: the staged (row, T6) pairs -> T -> the predicate ----
+    uint32_t srow = 0;
+    int st6 = 0, ns1 = 0;
+    unsigned long long nrefined = 0;   // (the diagnostic count: one atomic per wave, at its end)
+    const int lstride4 = a.d / 16;   // dwords per row of the low plane
+    auto refine = [&]() {
+        nrefined += (unsigned long long)ns1;
+        for (int base = 0; base < ns1; base += RB) {
+            // staged entries past the last re-read the last one, their result is discarded
+            uint32_t lw[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                int e = base + u * RPI + g;
+                e = e < ns1 - 1 ? e : ns1 - 1;
+                const uint32_t row = (uint32_t)__shfl((int)srow, e);
+                const uint32_t* src = reinterpret_cast<const uint32_t*>(a.low) + (int64_t)row * lstride4 + t;
+                if (MASKED)
+                    lw[u] = valid ? *src : 0u;
+                else
+                    lw[u] = *src;
+            }
+            const int e = base + erow;
+            const int ec = e < ns1 - 1 ? e : ns1 - 1;
+            const uint32_t row = (uint32_t)__shfl((int)srow, ec);
+            const int t6 = __shfl(st6, ec);
+            const float2 sr = a.ar[row];
+            int T[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                uint32_t c[4];
+                code8_unpack_low(lw[u], c);
+                int hi = 0, lo = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    hi = __builtin_amdgcn_sdot4((int)c[j], qh[j], hi, false);
+                    lo = __builtin_amdgcn_sdot4((int)c[j], ql[j], lo, false);
+                }
+                T[u] = hi * 256 + lo;
+            }
+            epilogue(t6 + code8_reduce<G, U>(T, t), sr, __ballot(t < U && e < ns1), row);
+        }
+        ns1 = 0;
+    };
+    // ---- stage 1: the predicate at the upper end of what the low plane can make of T6 ----
+    // s(T) is monotone in T (the conversion and the two products by qstep, a >= 0 round monotonically): sl <= s(T) <= su, so
+    // |s(T)| <= max(|sl|, |su|), the margin formed from that is >= the predicate's, and su + it is >= the predicate's bound, bit
+    // for bit (fp32 + and fma are monotone in every operand) — or NaN, which passes.  The lower end saturates at INT_MIN: still
+    // <= T, which fits (code8_qmax).
+    auto stage1 = [&](int t6, float2 sr, uint64_t mine, int64_t r) {
+        const int tl = (t6 > INT_MIN + n3 ? t6 : INT_MIN + n3) - n3;
+        const float su = ((float)(t6 + p3) * qstep) * sr.x;
+        const float sl = ((float)tl * qstep) * sr.x;
+        float m = fmaf(alpha, sr.y, beta);
+        m = fmaf(fmaxf(fabsf(su), fabsf(sl)) + m, 2.4e-7f, m);
+        const float ub = su + m;
+        uint64_t pass = __ballot(!(ub < floor)) & mine;
+        while (pass) {
+            const int src = __ffsll((long long)pass) - 1;
+            pass &= pass - 1;
+            const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)r, src);
+            const int w = __builtin_amdgcn_readlane(t6, src);
+            if (lane == ns1) {
+                srow = v;
+                st6 = w;
+            }
+            if (++ns1 == kWave) refine();
+        }
+    };
+
     const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
     const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
     const int64_t nfull = a.n / RB;
-    const int64_t batch_bytes = (int64_t)RB * a.d;
-    const int64_t group_bytes = (int64_t)RPI * a.d;
-    const int lane_off = g * a.d + t * 16;
+    const int64_t batch_bytes = (int64_t)RB * a.hstride;
+    const int64_t group_bytes = (int64_t)RPI * a.hstride;
+    const int lane_off = g * a.hstride + t * 12;
 
-    auto load = [&](i32x4 (&x)[U], float2& sr, int64_t b) {
-        const int8_t* base = a.codes + b * batch_bytes + lane_off;
+    auto load = [&](i32x3 (&x)[U], float2& sr, int64_t b) {
+        const uint8_t* base = a.high + b * batch_bytes + lane_off;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const i32x4* src = reinterpret_cast<const i32x4*>(base + u * group_bytes);
+            const i32x3* src = reinterpret_cast<const i32x3*>(base + u * group_bytes);
             if (MASKED)
-                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
+                x[u] = valid ? __builtin_nontemporal_load(src) : i32x3{0, 0, 0};
             else
                 x[u] = __builtin_nontemporal_load(src);
         }
         sr = a.ar[b * RB + erow];
     };
     for (int64_t b = gw; b < nfull; b += nwaves_total) {
-        i32x4 x[U];
+        i32x3 x[U];
         float2 sr;
         load(x, sr, b);
         int T[U];
         scores(x, T);
-        epilogue(code8_reduce<G, U>(T, t), sr, elanes, b * RB + erow);
+        stage1(code8_reduce<G, U>(T, t), sr, elanes, b * RB + erow);
     }
     // the partial batch behind the full ones: rows past the end re-read the last row, their result is discarded
     if (nfull * RB < a.n && nfull % nwaves_total == gw) {
         const int64_t last = a.n - 1;
-        i32x4 x[U];
+        i32x3 x[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             int64_t r = nfull * RB + (int64_t)u * RPI + g;
             r = r < last ? r : last;
-            const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + r * (int64_t)a.d + t * 16);
+            const i32x3* src = reinterpret_cast<const i32x3*>(a.high + r * (int64_t)a.hstride + t * 12);
             if (MASKED)
-                x[u] = valid ? __builtin_nontemporal_load(src) : i32x4{0, 0, 0, 0};
+                x[u] = valid ? __builtin_nontemporal_load(src) : i32x3{0, 0, 0};
             else
                 x[u] = __builtin_nontemporal_load(src);
         }
@@ -394,8 +578,10 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         const float2 sr = a.ar[r < last ? r : last];
         int T[U];
         scores(x, T);
-        epilogue(code8_reduce<G, U>(T, t), sr, __ballot(t < U && r < a.n), r);
+        stage1(code8_reduce<G, U>(T, t), sr, __ballot(t < U && r < a.n), r);
     }
+    if (ns1) refine();
+    if (nrefined && lane == 0) atomicAdd(a.survivors, nrefined);
     if (nst) flush();
 }
 
@@ -524,7 +710,8 @@ __device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists,
 //
 // The index keeps the sample's codes and (a, r) a second time, slot i at i, in one allocation (kCode8Seed * (d + 8) bytes:
 // the codes, then the (a, r) entries); code8_sample_kernel gathers it whenever the code it copies was written (the rule:
-// code8_sample_gather in mvdb.hip).  The floor's launch streams that copy exactly as code8_scan_kernel streams the code.
+// code8_sample_gather in mvdb.hip).  The copy is plain int8, d bytes per slot (put together from the two planes): the floor's
+// launch streams it in 16-byte chunks, batch by batch as code8_scan_kernel streams the high plane.
 // Roofline: HBM; bytes = kCode8Seed * (d + 8).
 constexpr int64_t kCode8Seed = 131072;
 constexpr int kCode8SeedMaxThreads = 1024;
@@ -533,16 +720,22 @@ constexpr int kCode8SeedThreads = 512;   // one block of this many per CU: measu
 __host__ __device__ inline int64_t code8_sample_row(int64_t slot, int64_t n) { return (slot * n) / kCode8Seed; }
 inline size_t code8_sample_bytes(int d) { return (size_t)kCode8Seed * ((size_t)d + sizeof(float2)); }
 
-// One thread per 16-byte chunk of a slot's codes; the thread of a slot's first chunk also copies its (a, r).
-__global__ __launch_bounds__(256) void code8_sample_kernel(const int8_t* __restrict__ codes, const float2* __restrict__ ar, int64_t n, int d,
-                                                           int8_t* __restrict__ scodes, float2* __restrict__ sar) {
+// One thread per 16-code chunk of a slot: the chunk's 12 + 4 bytes of the two planes are put together again — the stored
+// sample is plain int8, d bytes per slot.  The thread of a slot's first chunk also copies its (a, r).
+__global__ __launch_bounds__(256) void code8_sample_kernel(const uint8_t* __restrict__ high, const uint8_t* __restrict__ low,
+                                                           const float2* __restrict__ ar, int64_t n, int d, int8_t* __restrict__ scodes,
+                                                           float2* __restrict__ sar) {
     const int d16 = d / 16;
     const int64_t total = kCode8Seed * d16;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t slot = j / d16;
         const int c = (int)(j - slot * d16);
         const int64_t row = code8_sample_row(slot, n);
-        reinterpret_cast<i32x4*>(scodes + slot * d)[c] = reinterpret_cast<const i32x4*>(codes + row * d)[c];
+        const uint32_t* hsrc = reinterpret_cast<const uint32_t*>(high + row * code8_high_stride(d)) + 3 * c;
+        const uint32_t h[3] = {hsrc[0], hsrc[1], hsrc[2]};
+        uint32_t w[4];
+        code8_unpack_chunk(h, reinterpret_cast<const uint32_t*>(low + row * code8_low_stride(d))[c], w);
+        reinterpret_cast<i32x4*>(scodes + slot * d)[c] = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
         if (c == 0) sar[slot] = ar[row];
     }
 }

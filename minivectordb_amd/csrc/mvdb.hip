@@ -322,7 +322,7 @@ struct mvdb_index {
     // int8 code of the rows (code8_scan.hpp): d codes + (scale, residual bound) per row beside the matrix,
     // the operand of the single-query prefilter.  Lifecycle of the fp16 shadow: built by the first eligible single query, extended
     // by add, emptied by whatever renumbers rows, freed with the matrix; built / read under shadow_mu by searches.
-    mutable int8_t* C8 = nullptr;
+    mutable uint8_t* C8 = nullptr;   // two planes: [c8_cap, 3 d / 4] high, then [c8_cap, d / 4] low (c8_low)
     mutable float2* c8_ar = nullptr;
     mutable std::atomic<bool> c8_wanted{false};   // an eligible single query has asked for the code since the index was created / reset
     mutable int64_t c8_cap = 0, c8_rows = 0;
@@ -331,7 +331,7 @@ struct mvdb_index {
     mutable int64_t c8_samp_n = 0;   // the row count the copy was gathered for, after the last write to the code; 0 = stale
     mutable std::atomic<bool> c8_failed{false};
     mutable std::atomic<int> c8_wait{0};       // single queries the exact scan still answers before a dropped code is rebuilt
-    mutable unsigned int* c8_ctr_dev = nullptr;   // [0] fallbacks, [1] calls
+    mutable unsigned int* c8_ctr_dev = nullptr;   // [0] fallbacks, [1] calls, [2..3] one 64-bit word: rows refined (code8_scan_kernel)
     mutable PinnedBuf c8_stats;                   // host-mapped mirror: fallbacks, candidates of the latest call, calls
     mutable std::atomic<unsigned int> c8_calls{0}, c8_window_calls{0}, c8_window_fail{0};
     mutable std::atomic<int> c8_suspend_left{0};
@@ -1890,11 +1890,15 @@ void invalidate_code8(const mvdb_index* idx) {
     idx->c8_rows = idx->c8_samp_n = 0;
 }
 
+// the low plane lies behind the high plane of the whole CAPACITY: add into reserved space moves nothing
+uint8_t* c8_low(const mvdb_index* idx) { return idx->C8 + code8_low_offset(idx->c8_cap, idx->d); }
+
 int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t s) {
     if (rows > 0) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
         hipLaunchKernelGGL(code8_build_kernel, dim3(grid), dim3(256), 0, s, (const float*)(idx->X + row0 * idx->ld), idx->ld, idx->d, rows,
-                           idx->C8 + row0 * idx->d, idx->c8_ar + row0, (const int64_t*)nullptr, (int64_t)0);
+                           idx->C8 + row0 * code8_high_stride(idx->d), c8_low(idx) + row0 * code8_low_stride(idx->d), idx->c8_ar + row0,
+                           (const int64_t*)nullptr, (int64_t)0);
     }
     MVDB_HIP(hipGetLastError());
     return 0;
@@ -1911,7 +1915,7 @@ int code8_sample_gather(const mvdb_index* idx, int64_t n, hipStream_t s) {
     idx->c8_samp_n = 0;
     const int64_t chunks = kCode8Seed * (idx->d / 16);
     const int grid = (int)std::min<int64_t>((chunks + 255) / 256, (int64_t)device_cus(idx->device) * 16);
-    hipLaunchKernelGGL(code8_sample_kernel, dim3(grid), dim3(256), 0, s, (const int8_t*)idx->C8, (const float2*)idx->c8_ar, n, idx->d,
+    hipLaunchKernelGGL(code8_sample_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)idx->C8, (const uint8_t*)c8_low(idx), (const float2*)idx->c8_ar, n, idx->d,
                        idx->c8_samp, reinterpret_cast<float2*>(idx->c8_samp + kCode8Seed * idx->d));
     MVDB_HIP(hipGetLastError());
     idx->c8_samp_n = n;
@@ -1936,8 +1940,8 @@ bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
                   hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess &&
                   hipMalloc((void**)&idx->c8_samp, code8_sample_bytes(idx->d)) == hipSuccess;
         if (ok && !idx->c8_ctr_dev) {
-            ok = hipMalloc((void**)&idx->c8_ctr_dev, 2 * sizeof(unsigned int)) == hipSuccess &&
-                 hipMemset(idx->c8_ctr_dev, 0, 2 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
+            ok = hipMalloc((void**)&idx->c8_ctr_dev, 4 * sizeof(unsigned int)) == hipSuccess &&
+                 hipMemset(idx->c8_ctr_dev, 0, 4 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
             if (ok) memset(idx->c8_stats.p, 0, 64);
         }
         if (!ok) {
@@ -1986,19 +1990,20 @@ bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_de
     return true;
 }
 
-// What is specific to the codes: (G, U, MASKED) of code8_seed_kernel / code8_scan_kernel per width (U per shape: measured,
-// DESIGN.md section 4.1b).  launch(Code8Shape<...>{}) for d; the exact-scan shapes of the route come from with_scan_shape.
-template <int G_, int U_, bool MASKED_>
+// What is specific to the codes: (G, U, MASKED) of code8_seed_kernel per width, and for code8_scan_kernel — whose loads are
+// 12 bytes per lane, not 16 — its own U and blocks per CU (SCAN_U, SCAN_BLOCKS).  All measured per shape: DESIGN.md section
+// 4.1b.  launch(Code8Shape<...>{}) for d; the exact-scan shapes of the route come from with_scan_shape.
+template <int G_, int U_, bool MASKED_, int SCAN_U_, int SCAN_BLOCKS_>
 struct Code8Shape {
-    static constexpr int G = G_, U = U_;
+    static constexpr int G = G_, U = U_, SCAN_U = SCAN_U_, SCAN_BLOCKS = SCAN_BLOCKS_;
     static constexpr bool MASKED = MASKED_;
 };
 template <typename Launch>
 int with_code8_shape(int d, Launch launch) {
     switch (d) {
-        case 384: return launch(Code8Shape<32, 8, true>{});
-        case 512: return launch(Code8Shape<32, 4, false>{});
-        case 1024: return launch(Code8Shape<64, 4, false>{});
+        case 384: return launch(Code8Shape<32, 8, true, 8, 4>{});
+        case 512: return launch(Code8Shape<32, 4, false, 8, 2>{});
+        case 1024: return launch(Code8Shape<64, 4, false, 8, 2>{});
         default: return fail(MVDB_ERR_ARG, "internal: no int8 prefilter kernel for d = %d", d);
     }
 }
@@ -2011,13 +2016,19 @@ int with_code8_exact_shape(int d4, Launch launch) {
     });
 }
 
-template <int G, int U, bool MASKED>
+// the prefilter's grid: CUs x BLOCKS blocks, BLOCKS per shape from the sweep of this kernel (Code8Shape::SCAN_BLOCKS;
+// profiles/code8_planes_sweep.jsonl: U = 8 with 2 blocks per CU at d = 512 and 1024, with 4 at d = 384)
+template <int G, int U, bool MASKED, int BLOCKS>
+int code8_scan_blocks(int64_t n, int device) {
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
+    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), BLOCKS);
+    if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
+    return scan_grid(n, (kWave / G) * U, per_cu, device);
+}
+template <int G, int U, bool MASKED, int BLOCKS>
 int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
     void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
-    // CUs x 2 blocks: measured for this kernel (3 and 4 blocks per CU are 3 - 7 % slower at every served shape)
-    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), 2);
-    if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
-    const int nblocks = scan_grid(a.n, (kWave / G) * U, per_cu, device);
+    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS>(a.n, device);
     return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
                            "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
@@ -2107,10 +2118,12 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     }));
     // 2. the prefilter over the codes
     Code8ScanArgs c;
-    c.codes = idx->C8;
+    c.high = idx->C8;
+    c.low = c8_low(idx);
     c.ar = idx->c8_ar;
     c.n = idx->n;
     c.d = d;
+    c.hstride = code8_high_stride(d);
     c.qhi = qhi;
     c.qlo = qlo;
     c.par = par;
@@ -2118,9 +2131,10 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.cand = cand;
     c.cap = cap;
     c.counter = counter;
+    c.survivors = reinterpret_cast<unsigned long long*>(idx->c8_ctr_dev + 2);
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
-        return launch_code8_scan<K::G, K::U, K::MASKED>(c, idx->device, s);
+        return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
     }));
     // 3. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
     Code8RescoreArgs r;
@@ -2366,6 +2380,36 @@ int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, lo
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
     if (d <= 0 || !(qnorm >= 0.f) || !(row_norm_bound >= 0.f)) return INFINITY;
     return half_range_eps(d) * (double)qnorm * (double)row_norm_bound;
+}
+int mvdb_index_code8_refined(const mvdb_index* idx, long long* rows) {
+    if (!idx || !rows) return fail(MVDB_ERR_ARG, "mvdb_index_code8_refined: bad arguments");
+    *rows = 0;
+    if (!idx->c8_ctr_dev) return 0;
+    DeviceGuard dg(idx->device);
+    unsigned long long v = 0;
+    MVDB_HIP(hipMemcpy(&v, idx->c8_ctr_dev + 2, sizeof(v), hipMemcpyDeviceToHost));
+    *rows = (long long)v;
+    return 0;
+}
+int mvdb_code8_scan_geometry(int d, int64_t n, int device, int* rows_per_batch, int* waves) {
+    if (!code8_dim(d) || n <= 0 || !rows_per_batch || !waves) return fail(MVDB_ERR_ARG, "mvdb_code8_scan_geometry: bad arguments");
+    DeviceGuard dg(device);
+    return with_code8_shape(d, [&](auto cs) {
+        using K = decltype(cs);
+        *rows_per_batch = (kWave / K::G) * K::SCAN_U;
+        *waves = code8_scan_blocks<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(n, device) * kScanWaves;
+        return 0;
+    });
+}
+int mvdb_code8_pack(int d, const int8_t* codes, uint8_t* high, uint8_t* low) {
+    if (d <= 0 || d % 16 || !codes || !high || !low) return fail(MVDB_ERR_ARG, "mvdb_code8_pack: bad arguments");
+    code8_pack_row(d, codes, high, low);
+    return 0;
+}
+int mvdb_code8_unpack(int d, const uint8_t* high, const uint8_t* low, int8_t* codes) {
+    if (d <= 0 || d % 16 || !codes || !high || !low) return fail(MVDB_ERR_ARG, "mvdb_code8_unpack: bad arguments");
+    code8_unpack_row(d, high, low, codes);
+    return 0;
 }
 int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta) {
     if (d <= 0 || !alpha || !beta) return fail(MVDB_ERR_ARG, "mvdb_code8_margin: bad arguments");
@@ -2638,7 +2682,7 @@ static int set_rows_core(mvdb_index* idx, const int64_t* rows_host, const float*
         if (code) {
             const int g8 = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, cus * 16));
             hipLaunchKernelGGL(code8_build_kernel, dim3(g8), dim3(256), 0, idx->mut, (const float*)idx->X, idx->ld, idx->d, rows, idx->C8,
-                               idx->c8_ar, (const int64_t*)L, idx->c8_rows);
+                               c8_low(idx), idx->c8_ar, (const int64_t*)L, idx->c8_rows);
             MVDB_HIP(hipGetLastError());
             // a listed row may be one of the floor's sample: the whole copy is gathered again (a fixed 131,072 rows)
             if (code8_sample_valid(idx)) MVDB_TRY(code8_sample_gather(idx, idx->n, idx->mut));
