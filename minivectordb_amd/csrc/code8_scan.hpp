@@ -5,7 +5,8 @@
 // integers (q~: the query rounded to 16 / 15 bits, held as two int8 planes) and keeps every row whose upper bound
 // u_i = s~_i + m_i reaches a floor that is proven to lie at or below the final k-th best score.  The kept rows — a few
 // thousand of 10M — are then scored by code8_rescore_kernel with flat_scan_kernel's arithmetic: the bits of (D, I) are the full scan's.
-// The floor is the k-th best LOWER bound s~_i - m_i of a sample of rows (code8_seed_kernel): one launch in front of the pass.
+// The floor is the k-th best LOWER bound s~_i - m_i of a sample of rows: code8_seed_kernel, one launch in front of the pass,
+// leaves one sorted k-list per block, and every block of the pass merges them at its head.
 //
 // The codes are stored as two planes in the same d bytes per row: the top 6 bits of every code (3 d / 4 bytes) and the low 2
 // bits (d / 4 bytes).  The pass streams the first plane only, bounds what the missing bits can add, and fetches the second
@@ -297,6 +298,115 @@ __device__ __forceinline__ void code8_query_image(const float* __restrict__ q, i
     __syncthreads();
 }
 
+// ---- block lists: merged at the head of the next launch ---------------------------------------------------------------------------
+// code8_seed_kernel and code8_rescore_kernel end when every block has stored its sorted k-list; the launch behind them on the
+// stream merges the lists before anything else (code8_scan_kernel: every block, for the floor; code8_finish_kernel: its one
+// block, for (D, I)).  The kernel boundary orders the stores and makes them visible: plain stores, plain vector loads.
+//
+// The bar of a set of sorted k-lists: the best k-th key any of them holds.  That list alone has k keys at or above the bar, so
+// no key below it is among the k best of the union: such keys are dropped before the inserts, which are serial (about
+// 0.1 us each) and would otherwise take most keys of most lists — every list holds the best of its own rows.  0 (no list is
+// full) drops nothing.  Keys are distinct (score, row): the k best of the union are the same keys with and without the bar,
+// in whatever order the lists are walked.
+__device__ __forceinline__ uint64_t code8_wave_max(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint64_t o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t code8_lists_bar(const uint64_t* lists, int nlists, int k) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint64_t bar = 0ull, top = 0ull;
+    for (int l = lane; l < nlists; l += kWave) {
+        const uint64_t v = lists[(int64_t)l * k + (k - 1)];
+        const uint64_t f = lists[(int64_t)l * k];
+        bar = v > bar ? v : bar;
+        top = f > top ? f : top;
+    }
+    bar = code8_wave_max(bar);
+    // The second bar, for many lists: every lane holds the best key of the lists it read — 64 keys of 64 disjoint sets of
+    // lists — and the union holds k distinct keys at or above the k-th best of those.  Only a lower bound of that key is
+    // needed: the largest T with k lanes whose key's upper word (the score's image) reaches T, found bit by bit; T << 32 is at
+    // or below those k keys.  With the lists of 256 blocks it leaves a dozen keys to insert where the first bar leaves a third.
+    const uint32_t hi = (uint32_t)(top >> 32);
+    uint32_t T = 0u;
+#pragma unroll
+    for (int b = 31; b >= 0; --b) {
+        const uint32_t c = T | (1u << b);
+        if (__popcll(__ballot(hi >= c)) >= k) T = c;
+    }
+    const uint64_t bar2 = (uint64_t)T << 32;
+    return bar2 > bar ? bar2 : bar;
+}
+// block_merge_topk with the bar of the waves' lists: the sorted lists of all waves of the block into wave 0's list.
+// sh must hold (nwaves - 1) * 64 keys.  Must be called by every thread of the block.
+__device__ __forceinline__ void code8_block_merge(WaveTopK& tk, uint64_t* sh, int nwaves) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    if (wave > 0) sh[(wave - 1) * kWave + lane] = tk.key;
+    __syncthreads();
+    if (wave == 0) {
+        uint64_t bar = tk.thr;
+        for (int w = 0; w < nwaves - 1; ++w) {
+            const uint64_t v = sh[w * kWave + tk.k - 1];
+            bar = v > bar ? v : bar;
+        }
+        for (int w = 0; w < nwaves - 1; ++w) {
+            const uint64_t c = sh[w * kWave + lane];
+            tk.offer(c >= bar ? c : 0ull);
+        }
+    }
+}
+
+// The waves of the block share the nlists k-lists out (merge_keys_kernel's walk: UNROLL x 64 keys per wave and step, loaded
+// before any is offered), merge into wave 0's list.  Few lists: short steps, so that every wave has a share.
+template <int UNROLL>
+__device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, const uint64_t* lists, int nlists, int k, int nwaves) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int64_t total = (int64_t)nlists * k;
+    uint64_t bar = 0ull;
+    bool have_bar = false;
+    for (int64_t base = (int64_t)wave * kWave * UNROLL; base < total; base += (int64_t)nwaves * kWave * UNROLL) {
+        uint64_t c[UNROLL];
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) {
+            const int64_t i = base + j * kWave + lane;
+            c[j] = i < total ? lists[i] : 0ull;
+        }
+        // (every wave for itself, behind its first keys' loads: one round trip for both, no barrier)
+        if (!have_bar) bar = code8_lists_bar(lists, nlists, k);
+        have_bar = true;
+#pragma unroll
+        for (int j = 0; j < UNROLL; ++j) tk.offer(c[j] >= bar ? c[j] : 0ull);
+    }
+}
+// Must be called by every thread of the block; sh as code8_block_merge's.  Wave 0's list holds the k best keys of the union.
+__device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, const uint64_t* lists, int nlists, int k, uint64_t* sh, int nwaves) {
+    const int64_t total = (int64_t)nlists * k;
+    tk.init(k);
+    if (total <= (int64_t)nwaves * kWave * 4)
+        code8_offer_lists<2>(tk, lists, nlists, k, nwaves);
+    else
+        code8_offer_lists<kMergeUnroll>(tk, lists, nlists, k, nwaves);
+    code8_block_merge(tk, sh, nwaves);
+}
+// The floor of the prefilter, from the lists code8_seed_kernel's blocks left: the k-th best key of their union, -FLT_MAX
+// with fewer than k keys (or a k-th of -inf).  Every thread of the block calls it and gets the same bits — in every block,
+// whatever the number of lists: the k-th best of a set of distinct keys.  sh as code8_block_merge's; *word: one LDS float.
+__device__ __forceinline__ float code8_lists_floor(const uint64_t* lists, int nlists, int k, uint64_t* sh, float* word, int nwaves) {
+    WaveTopK tk;
+    code8_merge_lists(tk, lists, nlists, k, sh, nwaves);
+    if (threadIdx.x < kWave) {
+        const uint64_t kth = readlane_u64(tk.key, k - 1);
+        if (threadIdx.x == 0) *word = kth ? fmaxf(key_score(kth), -3.402823466e+38f) : -3.402823466e+38f;
+    }
+    __syncthreads();
+    return *word;
+}
+
 // ---- the prefilter scan ---------------------------------------------------------------------------------------------------------
 struct Code8ScanArgs {
     const uint8_t* high;   // [n, 3 d / 4] the high plane: streamed
@@ -308,7 +418,10 @@ struct Code8ScanArgs {
     const int8_t* qhi;     // [d] the query's high / low planes (code8_query_image, left by code8_seed_kernel's block 0)
     const int8_t* qlo;
     const float* par;      // qstep, alpha, beta
-    const float* floor;    // a proven lower bound of the final k-th best score (code8_seed_kernel: the sample's k-th best lower bound)
+    const uint64_t* lists; // [nlists, k] the sorted k-lists of code8_seed_kernel's blocks: lower bounds of the seed sample
+    int nlists;
+    int k;
+    float* floor;          // out (block 0, for the probes): the floor every block derives from the lists (code8_lists_floor)
     uint32_t* cand;        // [cap] appended rows, in no order
     int64_t cap;
     unsigned long long* counter;  // zeroed by code8_seed_kernel's block 0; keeps counting past cap
@@ -387,7 +500,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         ql = *reinterpret_cast<const i32x4*>(a.qlo + t * 16);
     }
     const float qstep = a.par[0], alpha = a.par[1], beta = a.par[2];
-    const float floor = *a.floor;
+    float floor = 0.f;   // (set below, behind the first batch's loads, before anything reads it)
 
     // 3 P and 3 N of the query, from the lane's planes (a masked lane holds zeros); at most 3 d qmax < 2^26
     int p3 = 0, n3 = 0;
@@ -552,7 +665,26 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         }
         sr = a.ar[b * RB + erow];
     };
-    for (int64_t b = gw; b < nfull; b += nwaves_total) {
+    // The head: the floor, merged by every block from the lists the seed launch's blocks left (the same bits in every block:
+    // code8_lists_floor).  The wave's first batch depends on neither the floor nor the merge: its loads are issued first.
+    __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
+    __shared__ float sfloor;
+    int64_t b = gw;
+    const bool head = b < nfull;
+    i32x3 x0[U];
+    float2 sr0 = make_float2(0.f, 0.f);
+    if (head) load(x0, sr0, b);
+    // (wave-uniform: held in a scalar register, so that the loop's compare takes it as an SGPR operand)
+    floor = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)__float_as_uint(code8_lists_floor(a.lists, a.nlists, a.k, sh, &sfloor, kScanWaves))));
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.floor = floor;
+    if (head) {
+        int T[U];
+        scores(x0, T);
+        stage1(code8_reduce<G, U>(T, t), sr0, elanes, b * RB + erow);
+        b += nwaves_total;
+    }
+    for (; b < nfull; b += nwaves_total) {
         i32x3 x[U];
         float2 sr;
         load(x, sr, b);
@@ -585,121 +717,6 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     if (nst) flush();
 }
 
-// ---- hand-off of block lists to the last block to arrive ------------------------------------------------------------------------
-// Both kernels below end the same way: every block leaves its sorted k-list in global memory, takes a ticket, and the block
-// that draws the last ticket merges all lists.  Nothing waits for anything: a block that is not last returns.
-//   producer: the list is stored with agent-scope atomic 8-byte stores (write-through), the storing wave drains them
-//             (s_waitcnt vmcnt(0)), __syncthreads(), then ONE lane: agent-scope release fence, drain, relaxed ticket fetch_add
-//             (the fences order it: an acq_rel add would write back and invalidate a second time in every block);
-//   consumer: the lane that drew the last ticket does ONE agent-scope acquire fence and drains it, __syncthreads(), then every
-//             wave reads the lists with agent-scope atomic loads (vector loads that bypass this CU's L1; never the scalar path).
-// The last arriver leaves the ticket word at zero; the re-score's is also zeroed by code8_seed_kernel's block 0 on every call.
-__device__ __forceinline__ void code8_store_list(uint64_t* lists, int64_t at, uint64_t key) {
-    __hip_atomic_store(lists + at, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t code8_load_list(uint64_t* lists, int64_t at) {
-    return __hip_atomic_load(lists + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Called by every thread of the block after wave 0 stored the block's list.  `expected`: the blocks that take a ticket.
-// sh: the block's LDS array (block_merge_topk's; at least one word), free for reuse when this returns.
-// sh must not be live across this call: sh[0] carries the "I am last" word (code8_block_merge's reads of sh end before the
-// first barrier here, and its next writes come after the last one).
-__device__ __forceinline__ bool code8_last_arriver(unsigned int* ticket, unsigned int expected, uint64_t* sh) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (every wave: only wave 0 has list stores in flight)
-    __syncthreads();                                    // the list is drained; wave 0 has finished reading sh
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int seen = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = seen == expected - 1u;
-        if (last) {
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        sh[0] = last ? 1ull : 0ull;
-    }
-    __syncthreads();
-    const bool last = sh[0] != 0ull;
-    __syncthreads();   // every wave has read the word before the merge below writes sh again
-    return last;
-}
-
-// The bar of a set of sorted k-lists: the best k-th key any of them holds.  That list alone has k keys at or above the bar, so
-// no key below it is among the k best of the union: such keys are dropped before the inserts, which are serial (about
-// 0.1 us each) and would otherwise take most keys of most lists — every list holds the best of its own rows.  0 (no list is
-// full) drops nothing.  Keys are distinct (score, row): the k best of the union are the same keys with and without the bar.
-__device__ __forceinline__ uint64_t code8_wave_max(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint64_t o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t code8_lists_bar(uint64_t* lists, int nlists, int k) {
-    const int lane = threadIdx.x & (kWave - 1);
-    uint64_t bar = 0ull;
-    for (int l = lane; l < nlists; l += kWave) {
-        const uint64_t v = code8_load_list(lists, (int64_t)l * k + (k - 1));
-        bar = v > bar ? v : bar;
-    }
-    return code8_wave_max(bar);
-}
-// block_merge_topk with the bar of the waves' lists: the sorted lists of all waves of the block into wave 0's list.
-// sh must hold (nwaves - 1) * 64 keys.  Must be called by every thread of the block.
-__device__ __forceinline__ void code8_block_merge(WaveTopK& tk, uint64_t* sh, int nwaves) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    if (wave > 0) sh[(wave - 1) * kWave + lane] = tk.key;
-    __syncthreads();
-    if (wave == 0) {
-        uint64_t bar = tk.thr;
-        for (int w = 0; w < nwaves - 1; ++w) {
-            const uint64_t v = sh[w * kWave + tk.k - 1];
-            bar = v > bar ? v : bar;
-        }
-        for (int w = 0; w < nwaves - 1; ++w) {
-            const uint64_t c = sh[w * kWave + lane];
-            tk.offer(c >= bar ? c : 0ull);
-        }
-    }
-}
-
-// The waves of the block share the nlists k-lists out (merge_keys_kernel's walk: UNROLL x 64 keys per wave and step, loaded
-// before any is offered), merge into wave 0's list.  Few lists: short steps, so that every wave has a share.
-template <int UNROLL>
-__device__ __forceinline__ void code8_offer_lists(WaveTopK& tk, uint64_t* lists, int nlists, int k, int nwaves) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int64_t total = (int64_t)nlists * k;
-    uint64_t bar = 0ull;
-    bool have_bar = false;
-    for (int64_t base = (int64_t)wave * kWave * UNROLL; base < total; base += (int64_t)nwaves * kWave * UNROLL) {
-        uint64_t c[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) {
-            const int64_t i = base + j * kWave + lane;
-            c[j] = i < total ? code8_load_list(lists, i) : 0ull;
-        }
-        // (every wave for itself, behind its first keys' loads: one round trip for both, no barrier)
-        if (!have_bar) bar = code8_lists_bar(lists, nlists, k);
-        have_bar = true;
-#pragma unroll
-        for (int j = 0; j < UNROLL; ++j) tk.offer(c[j] >= bar ? c[j] : 0ull);
-    }
-}
-__device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists, int nlists, int k, uint64_t* sh, int nwaves) {
-    const int64_t total = (int64_t)nlists * k;
-    tk.init(k);
-    if (total <= (int64_t)nwaves * kWave * 4)
-        code8_offer_lists<2>(tk, lists, nlists, k, nwaves);
-    else
-        code8_offer_lists<kMergeUnroll>(tk, lists, nlists, k, nwaves);
-    code8_block_merge(tk, sh, nwaves);
-}
-
 // ---- the floor: lower bounds of a sample of rows, from the codes -----------------------------------------------------------------
 // The sample: rows (i * n) / kCode8Seed, i in [0, kCode8Seed) (n >= kCode8Seed: distinct, ascending).  For each, the coded score
 // s~ and the margin m exactly as code8_scan_kernel's epilogue forms them, then lb = s~ - m in fp32: the exact kernel's score
@@ -707,6 +724,8 @@ __device__ __forceinline__ void code8_merge_lists(WaveTopK& tk, uint64_t* lists,
 // the final k-th best score does — the unchanged prefilter predicate !(ub < floor) keeps every row of the final top-k
 // (DESIGN.md section 4.1b).  Fewer than k lower bounds (or a k-th of -inf): floor = -FLT_MAX, everything passes, the call
 // falls back.  A NaN lb (0 * inf) fails the gate and never enters a list.
+// This launch ends when every block has stored the k best lower bounds of its share of the sample; the k-th best of their
+// union is taken by the prefilter's blocks (code8_lists_floor).
 //
 // The index keeps the sample's codes and (a, r) a second time, slot i at i, in one allocation (kCode8Seed * (d + 8) bytes:
 // the codes, then the (a, r) entries); code8_sample_kernel gathers it whenever the code it copies was written (the rule:
@@ -751,18 +770,13 @@ struct Code8SeedArgs {
     int8_t* qlo;
     float* par;
     unsigned long long* counter;   // out (block 0): the candidate counter, zeroed
-    unsigned int* rescore_ticket;  // out (block 0): zeroed
     int k;
-    uint64_t* lists;        // [gridDim.x, k]
-    unsigned int* ticket;   // this launch's own: see below
-    float* floor;
+    uint64_t* lists;        // out: [gridDim.x, k] every block's sorted k-list (slots it does not fill: 0)
 };
 
 // Every block computes the query's image itself (code8_query_image: the same bits in every block) and takes the planes from
-// LDS; block 0 also leaves the image and the zeroed counter words in the workspace for the launches behind this one.
-// The launch's own ticket cannot be zeroed by the launch that counts on it.  It is zero when the workspace is allocated
-// (code8_search), and every launch leaves it at zero: every block of the grid takes exactly one ticket — there is no path
-// from the kernel's entry to code8_last_arriver that returns — so the gridDim.x-th arriver exists and writes the zero back.
+// LDS; block 0 also leaves the image and the zeroed candidate counter in the workspace for the launches behind this one.
+// Every block of the grid stores a list — there is no path from the kernel's entry to the store that returns.
 template <int G, int U, bool MASKED>
 __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8SeedArgs a) {
     constexpr int RPI = kWave / G;
@@ -821,7 +835,6 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
 #pragma unroll
             for (int j = 0; j < 4; ++j) a.par[j] = par[j];
             *a.counter = 0ull;
-            *a.rescore_ticket = 0u;
         }
     }
     i32x4 qh = {0, 0, 0, 0}, ql = {0, 0, 0, 0};
@@ -871,13 +884,7 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
     }
 
     code8_block_merge(tk, sh, nwaves);
-    if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
-    if (!code8_last_arriver(a.ticket, gridDim.x, sh)) return;
-    code8_merge_lists(tk, a.lists, (int)gridDim.x, a.k, sh, nwaves);
-    if (wave == 0) {
-        const uint64_t kth = readlane_u64(tk.key, a.k - 1);
-        if (lane == 0) *a.floor = kth ? fmaxf(key_score(kth), -3.402823466e+38f) : -3.402823466e+38f;
-    }
+    if (wave == 0 && lane < a.k) a.lists[(int64_t)blockIdx.x * a.k + lane] = tk.key;
 }
 
 // ---- the exact re-score of the candidates, in one launch -------------------------------------------------------------------------
@@ -889,7 +896,9 @@ __global__ __launch_bounds__(kCode8SeedMaxThreads) void code8_seed_kernel(Code8S
 // The arithmetic restates flat_scan_kernel<G, C, ...>'s for the shape choose_shape picks (the same prologue, the same fmaf
 // chain over chunks c then .x .y .z .w, the same xor butterfly): the scores are the exact scan's bit for bit.
 // The grid is fixed at launch; the blocks that work are the first `active`, derived from the count (kCode8RescoreRows per
-// block, clamped to the grid); the others return without a ticket.  The last active block to arrive merges and writes (D, I).
+// block, clamped to the grid); the others return at once.  Every active block ends with the store of its sorted k-list, and
+// block 0 leaves `active` (0: the call falls back) in the workspace: code8_finish_kernel, the route's last launch, merges
+// exactly those lists and writes (D, I).
 constexpr int kCode8RescoreRows = 32;   // measured
 
 struct Code8RescoreArgs {
@@ -904,14 +913,11 @@ struct Code8RescoreArgs {
     int64_t cap;
     const float* par;
     int rows_per_block;
-    uint64_t* lists;        // [gridDim.x, k]
-    unsigned int* ticket;   // zeroed by code8_seed_kernel's block 0
+    uint64_t* lists;        // out: [active, k]
+    int* active;            // out (block 0): the lists this call stored
     int* gate;
     unsigned int* ctr_dev;  // [0] fallbacks, [1] calls
     volatile unsigned int* stats;
-    int64_t label_offset;
-    float* D;
-    int64_t* I;
 };
 
 template <int G, int C, int U, bool MASKED>
@@ -921,8 +927,12 @@ __global__ __launch_bounds__(kScanThreads) void code8_rescore_kernel(Code8Rescor
     __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
     const unsigned long long count = *a.counter;
     const bool fallback = count > (unsigned long long)a.cap || count < (unsigned long long)a.k || a.par[3] != 0.f;
+    const int64_t cnt = (int64_t)count;   // no fallback: k <= cnt <= cap
+    const int64_t want = (cnt + a.rows_per_block - 1) / a.rows_per_block;
+    const int active = fallback ? 0 : (int)(want < (int64_t)gridDim.x ? want : (int64_t)gridDim.x);   // no fallback: >= 1
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *a.gate = fallback ? 1 : 0;
+        *a.active = active;
         // (searches of one index on several streams run this concurrently: atomic)
         const unsigned int fb = atomicAdd(&a.ctr_dev[0], fallback ? 1u : 0u) + (fallback ? 1u : 0u);
         const unsigned int calls = atomicAdd(&a.ctr_dev[1], 1u) + 1u;
@@ -932,10 +942,6 @@ __global__ __launch_bounds__(kScanThreads) void code8_rescore_kernel(Code8Rescor
             a.stats[2] = calls;
         }
     }
-    if (fallback) return;
-    const int64_t cnt = (int64_t)count;   // k <= cnt <= cap
-    int64_t want = (cnt + a.rows_per_block - 1) / a.rows_per_block;
-    const int active = (int)(want < (int64_t)gridDim.x ? want : (int64_t)gridDim.x);   // >= 1
     if ((int)blockIdx.x >= active) return;
 
     const int lane = threadIdx.x & (kWave - 1);
@@ -1040,9 +1046,36 @@ __global__ __launch_bounds__(kScanThreads) void code8_rescore_kernel(Code8Rescor
     }
 
     code8_block_merge(tk, sh, kScanWaves);
-    if (wave == 0 && lane < a.k) code8_store_list(a.lists, (int64_t)blockIdx.x * a.k + lane, tk.key);
-    if (!code8_last_arriver(a.ticket, (unsigned int)active, sh)) return;
-    code8_merge_lists(tk, a.lists, active, a.k, sh, kScanWaves);
+    if (wave == 0 && lane < a.k) a.lists[(int64_t)blockIdx.x * a.k + lane] = tk.key;
+}
+
+// ---- the route's last launch: the block lists of this call -> (D, I) ---------------------------------------------------------------
+// One block.  *gate set (the call fell back): the `fallback_lists` lists the gated exact scan left — its grid, known to the
+// host; else the `*active` lists code8_rescore_kernel's blocks left.  Both went through the same buffer, the scan's behind
+// the re-score's: the count that is read is the one THIS call wrote, so lists of an earlier call with more blocks, or of the
+// seed launch, are never merged.  Merged with the bar and the walk of code8_merge_lists; labels and missing slots as
+// merge_keys_kernel writes them.
+constexpr int kCode8FinishThreads = 1024;
+
+struct Code8FinishArgs {
+    const uint64_t* lists;
+    const int* gate;
+    const int* active;
+    int fallback_lists;
+    int k;
+    int64_t label_offset;
+    float* D;
+    int64_t* I;
+};
+
+__global__ __launch_bounds__(kCode8FinishThreads) void code8_finish_kernel(Code8FinishArgs a) {
+    constexpr int NW = kCode8FinishThreads / kWave;
+    __shared__ uint64_t sh[(NW - 1) * kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int nlists = *a.gate != 0 ? a.fallback_lists : *a.active;
+    WaveTopK tk;
+    code8_merge_lists(tk, a.lists, nlists, a.k, sh, NW);
     if (wave == 0 && lane < a.k) {
         const uint64_t key = tk.key;
         float d;

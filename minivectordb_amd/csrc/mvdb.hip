@@ -235,7 +235,7 @@ struct Workspace {
     DevBuf<unsigned long long> rccount;  // ... and their per-query counters
     DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
     DevBuf<char> gtab;
-    DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and tickets, gate, floor, candidates
+    DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
         PinnedBuf buf;
         hipEvent_t ev = nullptr;
@@ -2033,10 +2033,10 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
                            "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 
-// The floor's launch.  The stored sample streams; the last block's merge is bound by inserts: wide blocks keep the lists few.
-// (grid shapes measured: DESIGN.md section 4.1b)
+// The floor's launch.  The stored sample streams; every block leaves one list, which every block of the prefilter merges.
+// (grid shapes measured: DESIGN.md section 4.1b)  *nlists: the lists the launch leaves — its grid.
 template <int G, int U, bool MASKED>
-int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream) {
+int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream, int* nlists) {
     void (*kern)(Code8SeedArgs) = code8_seed_kernel<G, U, MASKED>;
     int threads = kn().code8_seed_threads;   // (tuning hooks, as scan_blocks_per_cu: 0 = the measured defaults)
     if (threads != 256 && threads != 512 && threads != 1024) threads = kCode8SeedThreads;
@@ -2044,6 +2044,7 @@ int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream) {
     const int64_t want = (nbatches + threads / kWave - 1) / (threads / kWave);
     int64_t blocks = kn().code8_seed_blocks > 0 ? kn().code8_seed_blocks : device_cus(device);
     blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, want), scan_grid_upper_bound(device)));
+    *nlists = (int)blocks;
     return profiled_launch("ip_scan_code8_seed", stream, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, a); },
                            "code8_seed_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
@@ -2064,7 +2065,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     hipStream_t s = ws->stream;
     const int d = idx->d;
     const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(idx->kn.code8_capacity, kCode8MaxCapacity));
-    // workspace layout (bytes): planes [2 d] | terms [16 floats] | counter, tickets [2 x 8] | gate | floor | candidates
+    // workspace layout (bytes): planes [2 d] | terms [16 floats] | counter, active lists [2 x 8] | gate | floor | candidates
     // (the block lists of the seed and re-score launches, and of the gated fallback scan, go through ws->cand in turn)
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -2079,23 +2080,20 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     if (capturing && (ws->c8.cap < off || ws->cand.cap < cand_keys)) return 0;  // nothing is allocated inside a capture
     if (code8_suspended(idx)) return 0;
     if (!ensure_code8(idx, s)) return 0;
-    const bool fresh = ws->c8.cap < off;
     MVDB_TRY(ws->c8.reserve(off));
     MVDB_TRY(ws->cand.reserve(cand_keys));
     char* base = ws->c8.p;
-    // a new workspace: the floor launch's ticket starts at zero; from then on every launch leaves it there (code8_seed_kernel)
-    if (fresh) MVDB_HIP(hipMemsetAsync(base + o_ctr, 0, 2 * sizeof(unsigned long long), s));
     int8_t* qhi = reinterpret_cast<int8_t*>(base + o_planes);
     int8_t* qlo = qhi + d;
     float* par = reinterpret_cast<float*>(base + o_par);
     unsigned long long* counter = reinterpret_cast<unsigned long long*>(base + o_ctr);
-    unsigned int* tickets = reinterpret_cast<unsigned int*>(counter + 1);   // [0] the seed launch's, [1] the re-score's
+    int* active = reinterpret_cast<int*>(counter + 1);   // the lists the re-score launch of this call stored
     int* gate = reinterpret_cast<int*>(base + o_gate);
     float* floor = reinterpret_cast<float*>(base + o_floor);
     uint32_t* cand = reinterpret_cast<uint32_t*>(base + o_cand);
 
-    // 1. the query's planes and margin terms (every block; block 0 leaves them here and zeroes the candidate counter and the
-    //    re-score's ticket), and the floor: the k-th best LOWER bound of the seed sample, from its stored copy
+    // 1. the query's planes and margin terms (every block; block 0 leaves them here and zeroes the candidate counter), and
+    //    per block the k best LOWER bounds of its share of the seed sample, from its stored copy
     Code8SeedArgs sd;
     sd.scodes = idx->c8_samp;
     sd.sar = reinterpret_cast<const float2*>(idx->c8_samp + kCode8Seed * d);
@@ -2107,16 +2105,14 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     sd.qlo = qlo;
     sd.par = par;
     sd.counter = counter;
-    sd.rescore_ticket = tickets + 1;
     sd.k = k;
     sd.lists = ws->cand.p;
-    sd.ticket = tickets;
-    sd.floor = floor;
+    int seed_lists = 0;
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
-        return launch_code8_seed<K::G, K::U, K::MASKED>(sd, idx->device, s);
+        return launch_code8_seed<K::G, K::U, K::MASKED>(sd, idx->device, s, &seed_lists);
     }));
-    // 2. the prefilter over the codes
+    // 2. the floor — the k-th best of those lower bounds, merged by every block at its head — and the prefilter over the codes
     Code8ScanArgs c;
     c.high = idx->C8;
     c.low = c8_low(idx);
@@ -2127,6 +2123,9 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.qhi = qhi;
     c.qlo = qlo;
     c.par = par;
+    c.lists = ws->cand.p;
+    c.nlists = seed_lists;
+    c.k = k;
     c.floor = floor;
     c.cand = cand;
     c.cap = cap;
@@ -2136,7 +2135,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         using K = decltype(cs);
         return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
     }));
-    // 3. the fallback decision and the exact scores of the candidates, ties by row: (D, I)
+    // 3. the fallback decision and the exact scores of the candidates, ties by row: one sorted k-list per active block
     Code8RescoreArgs r;
     r.X = a0.X;
     r.ld = a0.ld;
@@ -2150,19 +2149,16 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     r.par = par;
     r.rows_per_block = kn().code8_rescore_rows > 0 ? kn().code8_rescore_rows : kCode8RescoreRows;   // (tuning hook)
     r.lists = ws->cand.p;
-    r.ticket = tickets + 1;
+    r.active = active;
     r.gate = gate;
     r.ctr_dev = idx->c8_ctr_dev;
     r.stats = (volatile unsigned int*)idx->c8_stats.p;
-    r.label_offset = label_offset;
-    r.D = D_dev;
-    r.I = I_dev;
     // (the exact scan's shape: the arithmetic is restated for exactly that; the route serves unpadded rows that fill it)
     MVDB_TRY(with_code8_exact_shape(a0.d4, [&](auto shape) {
         using S = decltype(shape);
         return launch_code8_rescore<S::G, S::C, rescore_u(S::G, S::C), false>(r, idx->device, s);
     }));
-    // 4. fallback, enabled on the device: the full exact scan overwrites the result
+    // 4. fallback, enabled on the device: the full exact scan leaves its block lists where the re-score's would be
     ScanArgs a = a0;
     a.cand = ws->cand.p;
     int nblocks = 0;
@@ -2175,7 +2171,18 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
         return launch_scan_kern<S::G, S::C, stream_u(S::G, S::C), 0, kModeTopK, 0, false>(a, 1, idx->device, s, &nblocks, "ip_scan_code8_fallback",
                                                                                             /*knob=*/false);
     }));
-    MVDB_TRY(launch_merge(idx, ws, 1, nblocks, k, label_offset, D_dev, I_dev, gate));
+    // 5. (D, I) from the lists of this call: the exact scan's where the gate is set, else the re-score's
+    Code8FinishArgs f;
+    f.lists = ws->cand.p;
+    f.gate = gate;
+    f.active = active;
+    f.fallback_lists = nblocks;
+    f.k = k;
+    f.label_offset = label_offset;
+    f.D = D_dev;
+    f.I = I_dev;
+    hipLaunchKernelGGL(code8_finish_kernel, dim3(1), dim3(kCode8FinishThreads), 0, s, f);
+    MVDB_HIP(hipGetLastError());
     *served = true;
     return 0;
 }
