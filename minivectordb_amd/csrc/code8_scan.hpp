@@ -729,7 +729,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
 //
 // The index keeps the sample's codes and (a, r) a second time, slot i at i, in one allocation (kCode8Seed * (d + 8) bytes:
 // the codes, then the (a, r) entries); code8_sample_kernel gathers it whenever the code it copies was written (the rule:
-// code8_sample_gather in mvdb.hip).  The copy is plain int8, d bytes per slot (put together from the two planes): the floor's
+// Code8Store::gather_sample in mvdb.hip).  The copy is plain int8, d bytes per slot (put together from the two planes): the floor's
 // launch streams it in 16-byte chunks, batch by batch as code8_scan_kernel streams the high plane.
 // Roofline: HBM; bytes = kCode8Seed * (d + 8).
 constexpr int64_t kCode8Seed = 131072;

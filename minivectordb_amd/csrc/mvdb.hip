@@ -8,12 +8,14 @@
 #include <cmath>
 #include <cstdlib>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <tuple>
 #include <vector>
 #include <shared_mutex>
 
 #include "common.hpp"
+#include "index_state.hpp"
 #include "scan_kernels.hpp"
 #include "grouped_scan.hpp"
 #include "range_scan.hpp"
@@ -198,6 +200,61 @@ void prof_end(int ticket, hipStream_t stream) {
 // ================================================================================================
 namespace {
 
+// The one capture test: nothing allocates or synchronises while it holds.
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
+}
+
+// A device allocation of EXACTLY the bytes asked for (the matrix and the stores derived from it: DevBuf's padding of a
+// quarter would be gigabytes), freed at once when it is replaced or goes — never parked on tls_retire: nothing captured
+// names these through a workspace.
+template <typename T>
+struct DevMem {
+    T* p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { release(); }
+    hipError_t alloc(size_t bytes) {
+        release();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+};
+
+// `words` device words that kernels count in, plus a 64-byte host-mapped mirror they copy the counts to, which host code
+// reads without a sync.  Both or neither: a failed ensure leaves the counter empty, which is no error — the kernels take
+// NULL for "do not count" and the readers see zeros.
+struct MirroredCounter {
+    DevMem<unsigned int> words;
+    PinnedBuf host;
+    // Never called while a stream is capturing (it allocates).  zero_on: the stream whose later work counts here, the zeroing
+    // is enqueued on it; none: zeroed before ensure returns.
+    bool ensure(int n, const hipStream_t* zero_on = nullptr) {
+        if (words.p) return true;
+        const size_t bytes = (size_t)n * sizeof(unsigned int);
+        if (words.alloc(bytes) != hipSuccess ||
+            (zero_on ? hipMemsetAsync(words.p, 0, bytes, *zero_on) : hipMemset(words.p, 0, bytes)) != hipSuccess || host.reserve(64) != 0) {
+            (void)hipGetLastError();
+            words.release();
+            return false;
+        }
+        memset(host.p, 0, 64);
+        return true;
+    }
+    unsigned int* dev() const { return words.p; }
+    template <typename W = unsigned int>
+    volatile W* mirror() const { return words.p ? reinterpret_cast<volatile W*>(host.p) : nullptr; }
+    template <typename W = unsigned int>
+    W read(int i) const { return words.p ? mirror<W>()[i] : W(0); }
+};
+
 struct Workspace {
     OwnedStream owned;  // (first: every buffer below is freed before the stream this workspace created for itself)
     int device = 0;
@@ -273,11 +330,78 @@ struct Workspace {
 
 static std::atomic<uint64_t> g_index_serial{0};
 
+// ---- the two stores derived from the matrix ------------------------------------------------------------------------------
+// Searches (index held shared) build and read them under mvdb_index::shadow_mu; mutators (index held exclusively, searches
+// quiesced) edit them directly.  What each event does to each store — the operations below are the only writers:
+//
+//   event                        | fp16 shadow (+ L2 offsets)                     | int8 code (+ floor sample)
+//   -----------------------------+------------------------------------------------+------------------------------------------------
+//   create                       | none; built by the first batch search that can | none; built by the first eligible single query
+//                                | use it (ensure), offsets by the first L2 pass  | (ensure sets `wanted`), with the sample
+//   add that fits                | extend: new rows converted; emptied instead if | extend: new rows coded and the sample gathered
+//                                | incomplete or the bound moved the scale;       | again; left alone if incomplete (emptied by a
+//                                | offsets catch up in ensure_offsets             | delete); nothing if none is held
+//   add that reallocates (grow)  | drop, before the new matrix is allocated       | drop; wait restarts if wanted
+//   reserve that reallocates     | as grow (nothing if the capacity suffices)     | as grow
+//   set_rows                     | listed rows below `rows` converted in place    | listed rows below `rows` coded in place; the
+//                                | (offsets: below `hn_rows`)                     | sample, if valid, gathered again per chunk
+//   set_rows that moves the scale| invalidate, after the rows are written         | (as set_rows)
+//   remove_rows                  | invalidate: emptied, allocation kept           | invalidate: emptied, sample stale, allocation
+//                                |                                                | kept; wait restarts if wanted, held or not
+//   reset                        | drop                                           | drop; wait restarts, `wanted` stays set
+//   free                         | freed with the index                           | freed with the index
+//   build failure                | drop, `failed` set: not tried again until a    | drop (wait untouched), `failed` set: NOTHING
+//                                | drop, an invalidate or an add without a shadow | clears it, the route is off for this index
+//                                | clears it                                      |
+//   capture                      | ensure builds nothing: a complete shadow is    | ensure builds nothing: a complete code with a
+//                                | used, else the fp32 passes serve               | valid sample is used, else the exact scan serves
+//
+// (`failed` of both is read by routing code that holds only the shared lock and written under shadow_mu: atomic.)
+namespace {
+
+struct ShadowStore {   // half_scan.hip: flat_scan_h16_kernel
+    DevMem<_Float16> Xh;
+    int64_t cap = 0, rows = 0;  // rows allocated (+ kRowSlack behind them) / rows converted
+    float scale = 0.f;
+    std::atomic<bool> failed{false};
+    DevMem<float> Hn;  // L2 over rows of mixed norms: |x_r|^2 / 2 of rows [0, hn_rows) (+ zeroed slack), dies with Xh
+    int64_t hn_rows = 0;
+
+    void drop();
+    void invalidate();
+    int extend(mvdb_index* idx, int64_t n_new);
+    const _Float16* ensure(const mvdb_index* idx, hipStream_t s, float xscale);
+    const float* ensure_offsets(const mvdb_index* idx, hipStream_t s);
+};
+
+struct Code8Store {   // code8_scan.hpp; DESIGN.md section 4.1b: d codes + (scale, residual bound) per row, the operand of the single-query prefilter
+    DevMem<uint8_t> C8;  // two planes: [cap, 3 d / 4] high, then [cap, d / 4] low (low())
+    DevMem<float2> ar;
+    DevMem<int8_t> samp;  // the stored copy of the floor's sample (code8_sample_kernel; the rule: gather_sample): codes, then (a, r) entries
+    int64_t cap = 0, rows = 0;
+    int64_t samp_n = 0;   // the row count the copy was gathered for, after the last write to the code; 0 = stale
+    std::atomic<bool> wanted{false};  // an eligible single query has asked for the code since the index was created
+    std::atomic<bool> failed{false};
+    std::atomic<int> wait{0};  // single queries the exact scan still answers before a dropped code is rebuilt
+
+    void drop(bool count_rebuild = true);
+    void invalidate();
+    int extend(mvdb_index* idx, int64_t n_new);
+    bool ensure(const mvdb_index* idx, hipStream_t s);
+    // the low plane lies behind the high plane of the whole CAPACITY: add into reserved space moves nothing
+    uint8_t* low(int d) const { return C8.p + code8_low_offset(cap, d); }
+    int build(const mvdb_index* idx, int64_t row0, int64_t n, hipStream_t s, const int64_t* list_dev = nullptr);
+    int gather_sample(const mvdb_index* idx, int64_t n, hipStream_t s);
+    bool sample_valid(int64_t n) const { return samp.p && rows == n && samp_n == n; }
+};
+
+}  // namespace
+
 struct mvdb_index {
     const uint64_t serial = ++g_index_serial;  // unique per index object of the process: resident row sets name their index by it
     int d = 0, d4 = 0, metric = 0, device = 0;
     int64_t ld = 0;
-    float* X = nullptr;
+    DevMem<float> X;
     int64_t n = 0, cap = 0;
     float row_norm_bound = 0.f;  // upper bound of |row| over the stored rows (INFINITY: unknown, raw adds)
     float norm2_lo = INFINITY, norm2_hi = 0.f;  // L2 metric only: bounds of |row|^2 over the stored rows (true values inside)
@@ -286,60 +410,31 @@ struct mvdb_index {
     Knobs kn;                    // the MVDB_* hooks as read at creation (mvdb_index_reload_env re-reads)
     hipStream_t mut = nullptr;   // the mutators' own non-blocking stream: add / remove_rows never touch the legacy stream,
                                  // so work other libraries have in flight on the device (an encoder forward) is not stalled
-    unsigned int* normmax = nullptr;  // 4-byte scratch of note_row_norms (raw adds)
-    float* ctmp = nullptr;            // bounded staging buffer of mvdb_index_remove_rows (kept once a delete has run)
+    DevMem<unsigned int> normmax;     // 8-byte scratch of note_row_norms (raw adds)
+    DevMem<float> ctmp;               // bounded staging buffer of mvdb_index_remove_rows (kept once a delete has run)
     size_t ctmp_bytes = 0;
     DevBuf<float> set_stage;          // bounded staging of mvdb_index_set_rows (kept once an update has run): one chunk of new
     DevBuf<int64_t> set_list;         // rows at the matrix' stride, and the row numbers they go to
-    // fp16 shadow of the rows (half_scan.hip: flat_scan_h16_kernel): built by the first batch search that can use it, extended
-    // by add, emptied (allocation kept) by whatever renumbers rows or changes the scale, freed with the matrix.  Searches (shared lock) build / read it under
-    // shadow_mu; mutators (exclusive lock, searches quiesced) edit it directly.
-    mutable std::mutex shadow_mu;
-    mutable _Float16* Xh = nullptr;
-    mutable int64_t xh_cap = 0, xh_rows = 0;   // rows allocated (+ kRowSlack behind them) / rows converted
-    mutable float xh_scale = 0.f;
-    mutable std::atomic<bool> xh_failed{false};  // allocation failed: not retried until the index changes (read by routing code
-                                                 // that holds only the shared lock, written under shadow_mu: atomic)
-    mutable float* Hn = nullptr;               // L2 over rows of mixed norms: |x_r|^2 / 2 of rows [0, hn_rows) (+ zeroed slack), dies with Xh
-    mutable int64_t hn_rows = 0;
-    // The opt-in single-query route over the shadow costs MORE than the exact scan when its certificate is refused (the
-    // nomination pass, then the exact scan anyway: 0.59 against 0.31 ms per query on a clustered 1M x 512 corpus,
-    // BENCH certified_passes_on_unfriendly_data).  The device keeps a running count of refused single-query certificates and
-    // mirrors it into a host-mapped word; the routing looks at windows of 32 such calls and, when half of a window was
-    // refused, sends the next 512 single queries straight to the exact scan before it probes again.  No synchronisation: the
-    // word lags by the calls in flight, which a heuristic can afford.
-    mutable unsigned int* sq_fail_dev = nullptr;
-    mutable PinnedBuf sq_fail_host;
-    mutable std::atomic<unsigned int> sq_calls{0}, sq_window_calls{0}, sq_window_fail{0};
-    mutable std::atomic<int> sq_suspend_left{0};
-    // adaptive tile flags (search_core): a running count of refused certificates of ANY certified call, mirrored into a
-    // host-mapped word; the certified pass keeps tile flags only while that count has been moving
-    mutable unsigned int* rf_dev = nullptr;
-    mutable PinnedBuf rf_host;
+    mutable std::mutex shadow_mu;     // (the event x store table above)
+    mutable ShadowStore shadow;
+    mutable Code8Store code;
+    // the opt-in single-query route over the shadow (index_state.hpp: RouteWindow): refused single-query certificates,
+    // counted from the first opted-in single query on (search_core)
+    mutable MirroredCounter sq_fail;
+    mutable RouteWindow sq_route;
+    // adaptive tile flags (search_core): a running count of refused certificates of ANY certified call, created with the
+    // shadow; the certified pass keeps tile flags only while that count has been moving
+    mutable MirroredCounter rf;
     mutable std::atomic<unsigned int> rf_seen{0};
     mutable std::atomic<int> rf_calls_left{0};
-    mutable std::atomic<unsigned long long> sq_suspensions{0};
-    // int8 code of the rows (code8_scan.hpp): d codes + (scale, residual bound) per row beside the matrix,
-    // the operand of the single-query prefilter.  Lifecycle of the fp16 shadow: built by the first eligible single query, extended
-    // by add, emptied by whatever renumbers rows, freed with the matrix; built / read under shadow_mu by searches.
-    mutable uint8_t* C8 = nullptr;   // two planes: [c8_cap, 3 d / 4] high, then [c8_cap, d / 4] low (c8_low)
-    mutable float2* c8_ar = nullptr;
-    mutable std::atomic<bool> c8_wanted{false};   // an eligible single query has asked for the code since the index was created / reset
-    mutable int64_t c8_cap = 0, c8_rows = 0;
-    // the stored copy of the floor's sample (code8_sample_kernel; the rule: code8_sample_gather): codes, then (a, r) entries
-    mutable int8_t* c8_samp = nullptr;
-    mutable int64_t c8_samp_n = 0;   // the row count the copy was gathered for, after the last write to the code; 0 = stale
-    mutable std::atomic<bool> c8_failed{false};
-    mutable std::atomic<int> c8_wait{0};       // single queries the exact scan still answers before a dropped code is rebuilt
-    mutable unsigned int* c8_ctr_dev = nullptr;   // [0] fallbacks, [1] calls, [2..3] one 64-bit word: rows refined (code8_scan_kernel)
-    mutable PinnedBuf c8_stats;                   // host-mapped mirror: fallbacks, candidates of the latest call, calls
-    mutable std::atomic<unsigned int> c8_calls{0}, c8_window_calls{0}, c8_window_fail{0};
-    mutable std::atomic<int> c8_suspend_left{0};
-    mutable std::atomic<unsigned long long> c8_suspensions{0};
-    // range search, shared pass (range_shared_phase): a running count of queries its fallback answered, mirrored with the
-    // candidates of the latest launch group into host-mapped words; calls that took the route are counted on the host
-    mutable unsigned int* rg_ctr_dev = nullptr;
-    mutable PinnedBuf rg_stats;
+    // the int8 route, created with the code.  Device words: [0] fallbacks, [1] calls, [2..3] one 64-bit word: rows refined
+    // (code8_scan_kernel); mirror: fallbacks, candidates of the latest call, calls
+    mutable MirroredCounter c8_ctr;
+    mutable RouteWindow c8_route;
+    // range search, shared pass (range_shared_phase), created by the first call that takes it: a running count of queries its
+    // fallback answered, mirrored with the candidates of the latest launch group as 64-bit words; calls that took the route
+    // are counted on the host
+    mutable MirroredCounter rg_ctr;
     mutable std::atomic<unsigned long long> rg_shared_calls{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
@@ -759,7 +854,7 @@ bool gemm_path_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev)
 int launch_gemm_scan(const mvdb_index* idx, const float* q, int nq, int k, int64_t n, uint64_t* cand,
                      hipStream_t stream, int* nblocks_out, const int* gate = nullptr, int gate_lo = 0) {
     GemmScanArgs a;
-    a.X = idx->X;
+    a.X = idx->X.p;
     a.n = n;
     a.ld = idx->ld;
     a.K = idx->d;
@@ -820,7 +915,7 @@ bool half_path_ok(const mvdb_index* idx);
 int half_min_nq(const mvdb_index* idx, int64_t n);
 bool l2_offsets_ok(const mvdb_index* idx, int nq, int64_t n) {
     return idx->metric == MVDB_METRIC_L2 && !idx->kn.disable_l2_cert && half_shadow_dim(idx->d) && idx->ld == idx->d &&
-           !idx->kn.disable_half_shadow && !idx->xh_failed && half_path_ok(idx) && nq >= half_min_nq(idx, n);
+           !idx->kn.disable_half_shadow && !idx->shadow.failed && half_path_ok(idx) && nq >= half_min_nq(idx, n);
 }
 
 // Fewest queries of a call that go to the certified passes.  Where the fp16 nomination pass streams the SHADOW of the rows
@@ -838,8 +933,8 @@ constexpr int kTileFlagCalls = 1024;
 bool tile_flags_wanted(const mvdb_index* idx) {
     if (idx->kn.disable_tile_skip || idx->kn.tile_flags_mode == 0) return false;
     if (idx->kn.tile_flags_mode == 1) return true;
-    if (!idx->rf_dev || !idx->rf_host.p) return false;
-    const unsigned int v = *reinterpret_cast<volatile unsigned int*>(idx->rf_host.p);
+    if (!idx->rf.dev()) return false;
+    const unsigned int v = idx->rf.read(0);
     if (v != idx->rf_seen.load(std::memory_order_relaxed)) {
         idx->rf_seen.store(v, std::memory_order_relaxed);
         idx->rf_calls_left.store(kTileFlagCalls, std::memory_order_relaxed);
@@ -850,29 +945,10 @@ bool tile_flags_wanted(const mvdb_index* idx) {
 }
 
 thread_local bool tls_single_suspended = false;  // decided once per search (search_core), read by every routing question of that call
-constexpr int kSingleWindow = 32, kSingleSuspend = 512;
-// One decision per single-query search that asks for the shadow route: true = this call takes the exact scan.
-bool single_route_suspended(const mvdb_index* idx) {
-    if (idx->sq_suspend_left.load(std::memory_order_relaxed) > 0) {
-        idx->sq_suspend_left.fetch_sub(1, std::memory_order_relaxed);
-        return true;
-    }
-    const unsigned int calls = idx->sq_calls.fetch_add(1, std::memory_order_relaxed) + 1;
-    if (calls - idx->sq_window_calls.load(std::memory_order_relaxed) >= (unsigned int)kSingleWindow && idx->sq_fail_host.p) {
-        const unsigned int fails = *reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p);
-        if ((fails - idx->sq_window_fail.load(std::memory_order_relaxed)) * 2 >= (unsigned int)kSingleWindow) {
-            idx->sq_suspend_left.store(kSingleSuspend, std::memory_order_relaxed);
-            idx->sq_suspensions.fetch_add(1, std::memory_order_relaxed);
-        }
-        idx->sq_window_calls.store(calls, std::memory_order_relaxed);
-        idx->sq_window_fail.store(fails, std::memory_order_relaxed);
-    }
-    return false;
-}
 
 int half_min_nq(const mvdb_index* idx, int64_t n) {
     if (idx->kn.split_scan_min_nq >= 0) return idx->kn.split_scan_min_nq;
-    if (half_shadow_dim(idx->d) && idx->ld == idx->d && !idx->kn.disable_half_shadow && !idx->xh_failed) {
+    if (half_shadow_dim(idx->d) && idx->ld == idx->d && !idx->kn.disable_half_shadow && !idx->shadow.failed) {
         // (opt-in, MVDB_SHADOW_SINGLE_QUERY=1: ONE query too — 10M x 512: 2.86 -> ~1.6 ms per query, certified like any batch; off
         //  by default: the single-query scan is the headline's exact fp32 kernel and its roofline is defined on the fp32 bytes)
         if (n >= 500000) return idx->kn.shadow_single_query && !tls_single_suspended ? 1 : 2;
@@ -928,12 +1004,10 @@ __global__ __launch_bounds__(1024) void phase_fold_kernel(const uint64_t* __rest
 // (the pass streams the fp16 SHADOW of the rows: an index that may not keep one — option half_shadow = 0, or the shadow's
 //  allocation failed — answers its batches on the exact fp32 passes)
 bool half_path_ok(const mvdb_index* idx) {
-    if (idx->kn.disable_half_scan || idx->kn.disable_half_shadow || idx->xh_failed) return false;
+    if (idx->kn.disable_half_scan || idx->kn.disable_half_shadow || idx->shadow.failed) return false;
     return half_max_queries(idx->d) > 0 && half_shadow_dim(idx->d) && idx->ld == idx->d && half_xscale(idx->row_norm_bound) > 0.f;
 }
 
-const _Float16* ensure_shadow(const mvdb_index* idx, hipStream_t s, float xscale);
-const float* ensure_offsets(const mvdb_index* idx, hipStream_t s);
 bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, const uint64_t* mask_dev, int64_t n);
 int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
                  bool* served);
@@ -950,7 +1024,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     const float xscale = half_xscale(idx->row_norm_bound);
     MVDB_TRY(launch_half_queries(q, idx->ld, idx->d, nq, nqpad, xscale, qf, qnorm, qinv, stream));
     HalfScanArgs a;
-    a.X = idx->X;
+    a.X = idx->X.p;
     a.n = n;
     a.ld = idx->ld;
     a.qf = qf;
@@ -958,7 +1032,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     a.xscale = xscale;
     a.nq = nq;
     a.mask = mask;
-    a.Xh = ensure_shadow(idx, stream, xscale);
+    a.Xh = idx->shadow.ensure(idx, stream, xscale);
     a.stats = idx->kn.split_stats ? reinterpret_cast<unsigned int*>(ws->flags.p) + (ws->flags.cap - 32) : nullptr;
     if (a.stats) MVDB_HIP(hipMemsetAsync(a.stats, 0, 8, stream));
     const int64_t ntiles = (n + 31) / 32;
@@ -977,7 +1051,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     // certificate): rows are nominated by q.x - |x|^2 / 2 with the per-row offsets kept beside the shadow (section 4.3e); the
     // seed is then the shadow kernel itself without a floor — one tile per block, its 16 best per query — because the fp32
     // seed kernel knows no offsets.
-    const float* hn = idx->metric == MVDB_METRIC_L2 && a.Xh && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? ensure_offsets(idx, stream)
+    const float* hn = idx->metric == MVDB_METRIC_L2 && a.Xh && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? idx->shadow.ensure_offsets(idx, stream)
                                                                                                           : nullptr;
     const bool l2off = hn != nullptr;
     if (l2off) {
@@ -1046,7 +1120,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     c.nlists = last_lists;
     c.base = seed_keys;
     c.thr0 = floors;
-    c.X = idx->X;
+    c.X = idx->X.p;
     c.ld = idx->ld;
     c.d4 = idx->d4;
     c.q = q;
@@ -1226,27 +1300,18 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
         int64_t* It = map + R;
         float* qc = ws->requery.p;
         float* Dt = qc + (size_t)(R + 128) * idx->ld;
-        unsigned int *sq_dev = nullptr, *sq_host = nullptr;
-        if (nq == 1 && idx->kn.shadow_single_query) {  // the opt-in single-query route reports its refusals (single_route_suspended)
+        unsigned int* sq_dev = nullptr;
+        volatile unsigned int* sq_host = nullptr;
+        if (nq == 1 && idx->kn.shadow_single_query) {  // the opt-in single-query route reports its refusals (sq_route)
             std::lock_guard<std::mutex> lk(idx->shadow_mu);
-            if (!idx->sq_fail_dev && hipMalloc((void**)&idx->sq_fail_dev, sizeof(unsigned int)) == hipSuccess) {
-                if (hipMemsetAsync(idx->sq_fail_dev, 0, sizeof(unsigned int), s) != hipSuccess || idx->sq_fail_host.reserve(64) != 0) {
-                    (void)hipFree(idx->sq_fail_dev);
-                    idx->sq_fail_dev = nullptr;
-                } else {
-                    *reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p) = 0u;
-                }
+            if (idx->sq_fail.dev() || (!stream_capturing(s) && idx->sq_fail.ensure(1, &s))) {
+                sq_dev = idx->sq_fail.dev();
+                sq_host = idx->sq_fail.mirror();
             }
-            (void)hipGetLastError();
-            if (idx->sq_fail_dev && idx->sq_fail_host.p) {
-                sq_dev = idx->sq_fail_dev;
-                sq_host = reinterpret_cast<unsigned int*>(idx->sq_fail_host.p);
-            }
+            (void)hipGetLastError();  // (unconditional, as the clear behind rf's creation: ShadowStore::ensure)
         }
-        unsigned int* rf_dev = idx->rf_dev && idx->rf_host.p ? idx->rf_dev : nullptr;
         hipLaunchKernelGGL(split_plan_kernel, dim3(1), dim3(64), 0, s, (const int*)ws->flags.p, nchunks, (const int*)ws->qfail.p, q0,
-                           map, ws->nfail.p, ctr, sq_dev, (volatile unsigned int*)sq_host, rf_dev,
-                           (volatile unsigned int*)(rf_dev ? idx->rf_host.p : nullptr));
+                           map, ws->nfail.p, ctr, sq_dev, sq_host, idx->rf.dev(), idx->rf.mirror());
         {
             const int64_t rows = R + 128, gtotal = rows * (idx->ld / 4);
             const int ggrid = (int)std::min<int64_t>((gtotal + 255) / 256, (int64_t)device_cus(idx->device) * 8);
@@ -1267,11 +1332,11 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
             if (need_per <= 0 || kRescueQueries % need_per != 0 || !half_rescue_dim(idx->d) || idx->ld != idx->d || k > kRescueKeep ||
                 idx->kn.disable_rescue || idx->kn.disable_rerun_floor || !(xs > 0.f))
                 return 0;
-            const _Float16* Xh = ensure_shadow(idx, s, xs);
+            const _Float16* Xh = idx->shadow.ensure(idx, s, xs);
             if (!Xh) return 0;
             // (L2: the same nomination form the certified pass used — per-row offsets where the rows' norms differ)
             const bool l2 = idx->metric == MVDB_METRIC_L2;
-            const float* hn = l2 && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? ensure_offsets(idx, s) : nullptr;
+            const float* hn = l2 && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? idx->shadow.ensure_offsets(idx, s) : nullptr;
             if (l2 && !l2_cert_ok(idx) && !hn) return 0;
             const int grid_ub = device_cus(idx->device) * kRescueBlocksPerCu;  // the rescue launch: one or two workgroups per CU
             const int slots = (R + kRescueQueries - 1) / kRescueQueries;
@@ -1305,7 +1370,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
                 MVDB_TRY(launch_half_queries(qc + (int64_t)off2 * idx->ld, idx->ld, idx->d, kRescueQueries, kRescueQueries, xs, qf, qn2,
                                              qinv, s));
                 HalfScanArgs ra;
-                ra.X = idx->X;
+                ra.X = idx->X.p;
                 ra.n = n;
                 ra.ld = idx->ld;
                 ra.qf = qf;
@@ -1331,7 +1396,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
                 HalfRescueArgs rc;
                 rc.keys = ws->cand.p;
                 rc.nlists = gx;
-                rc.X = idx->X;
+                rc.X = idx->X.p;
                 rc.ld = idx->ld;
                 rc.d4 = idx->d4;
                 rc.q = qc + (int64_t)off2 * idx->ld;
@@ -1390,7 +1455,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
                 for (int p0 = 0; p0 < max_passes; p0 += kGatedPassGroup) {
                     const int np = std::min(kGatedPassGroup, max_passes - p0), qoff = p0 * per_pass;
                     MfmaScanArgs ma;
-                    ma.X = idx->X;
+                    ma.X = idx->X.p;
                     ma.n = n;
                     ma.ld = idx->ld;
                     ma.q = qc + (int64_t)qoff * idx->ld;
@@ -1439,7 +1504,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
                                  D_dev + (int64_t)t0 * k, I_dev + (int64_t)t0 * k, allow_split, mask_dev));
         return 0;
     }
-    if (allow_split) tls_single_suspended = nq == 1 && idx->kn.shadow_single_query && single_route_suspended(idx);
+    if (allow_split) tls_single_suspended = nq == 1 && idx->kn.shadow_single_query && idx->sq_route.suspended(idx->sq_fail.mirror());
     // row list: its m entries; bitmap: the first m rows when the caller says how many rows the bitmap covers (a resident
     // row set built before later appends), else every row
     const int64_t n = rows_dev ? m : (mask_dev && m > 0 ? std::min<int64_t>(m, idx->n) : idx->n);
@@ -1467,7 +1532,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
         return 0;
     }
     ScanArgs a;
-    a.X = idx->X;
+    a.X = idx->X.p;
     a.n = n;
     a.ld = idx->ld;
     a.d4 = idx->d4;
@@ -1490,7 +1555,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
     // Batches (2+ queries where the corpus buries the pass's fixed cost, half_min_nq), k <= 32, rows of known norm, a width the
     // fp16 kernels serve: ONE fp16 product over the shadow nominates, fp32 re-scores decide, a worst-case bound certifies
     // (certified_batch); what it leaves — fewer queries than the pass is worth — takes the exact passes below.
-    if (allow_split && split_path_ok(idx, nq, k, rows_dev, n) && ensure_shadow(idx, s, half_xscale(idx->row_norm_bound))) {
+    if (allow_split && split_path_ok(idx, nq, k, rows_dev, n) && idx->shadow.ensure(idx, s, half_xscale(idx->row_norm_bound))) {
         int q0 = 0;
         const float* qsrc = nullptr;
         MVDB_TRY(certified_batch(idx, ws, a, q_dev, nq, k, normalize_q, n, label_offset, D_dev, I_dev, mask_dev, &q0, &qsrc));
@@ -1508,7 +1573,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
         for (int q0 = 0; q0 < nq; q0 += per_pass) {
             const int take = std::min(per_pass, nq - q0);
             MfmaScanArgs ma;
-            ma.X = idx->X;
+            ma.X = idx->X.p;
             ma.n = n;
             ma.ld = idx->ld;
             ma.q = qsrc + (int64_t)q0 * idx->ld;
@@ -1558,7 +1623,7 @@ int search_core(const mvdb_index* idx, Workspace* ws, const float* q_dev, int nq
             const bool two_groups = left > 16 && idx->d <= (idx->metric == MVDB_METRIC_IP ? 512 : 384) && (idx->kn.mfma_ng2 >= 0 ? idx->kn.mfma_ng2 != 0 : staged);
             const int take = two_groups ? std::min(left, 32) : std::min(left, 16);
             MfmaScanArgs ma;
-            ma.X = idx->X;
+            ma.X = idx->X.p;
             ma.n = n;
             ma.ld = idx->ld;
             ma.q = qsrc + (int64_t)q0 * idx->ld;
@@ -1685,10 +1750,7 @@ struct HostCall {
 // A search being captured into a hipGraph: from now on this workspace keeps every buffer it outgrows (RetireScope), so a
 // later, larger eager call on the same stream cannot free memory the graph still names.  Returns ws->captured.
 bool note_capture(Workspace* ws) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ws->stream && !ws->captured && hipStreamIsCapturing(ws->stream, &st) == hipSuccess &&
-        st == hipStreamCaptureStatusActive)
-        ws->captured = true;
+    if (!ws->captured && stream_capturing(ws->stream)) ws->captured = true;
     return ws->captured;
 }
 
@@ -1752,108 +1814,113 @@ int check_search_args(const mvdb_index* idx, const void* q, int nq, int k, const
 // are read, scored and never nominated) so that their DMA issue needs no per-lane bounds handling.
 constexpr int64_t kRowSlack = 32;
 
-void drop_shadow(const mvdb_index* idx) {
-    if (idx->Xh) (void)hipFree(idx->Xh);
-    if (idx->Hn) (void)hipFree(idx->Hn);
-    idx->Hn = nullptr;
-    idx->hn_rows = 0;
-    idx->Xh = nullptr;
-    idx->xh_cap = idx->xh_rows = 0;
-    idx->xh_scale = 0.f;
-    idx->xh_failed = false;
+// Grid of the utility kernels that give a wave to a row (four waves per block), at most per_cu blocks per CU.
+int row_grid(int device, int64_t rows, int per_cu = 16) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(device) * per_cu));
+}
+
+// ---- the fp16 shadow (the event x store table: above mvdb_index) ------------------------------------------------------------
+void ShadowStore::drop() {
+    Xh.release();
+    Hn.release();
+    cap = rows = hn_rows = 0;
+    scale = 0.f;
+    failed = false;
 }
 
 // The rows changed their numbers or their scale but the allocation still fits: the shadow is emptied, not freed — hipFree waits
 // for the whole device and the next batch search would allocate the same bytes again — and rebuilt in place on demand.
-void invalidate_shadow(const mvdb_index* idx) {
-    idx->xh_rows = 0;
-    idx->hn_rows = 0;
-    idx->xh_failed = false;
+void ShadowStore::invalidate() {
+    rows = hn_rows = 0;
+    failed = false;
 }
 
 // The shadow for a batch search on stream s (caller holds the index shared): the existing one if it covers the rows at
 // this scale, else built here — once: 10M x 512 convert in ~5 ms — and published after a wait for s, so that searches on
 // other streams find complete data.  NULL (the fp32 path serves): no kernel for d, switched off, allocation failed, or the
 // stream is being captured (a build allocates and synchronises).
-const _Float16* ensure_shadow(const mvdb_index* idx, hipStream_t s, float xscale) {
+const _Float16* ShadowStore::ensure(const mvdb_index* idx, hipStream_t s, float xscale) {
     if (!half_shadow_dim(idx->d) || idx->ld != idx->d || idx->kn.disable_half_shadow || !(xscale > 0.f)) return nullptr;
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    if (idx->Xh && idx->xh_scale == xscale && idx->xh_rows == idx->n) return idx->Xh;
-    if (idx->xh_failed) return nullptr;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive) return nullptr;
+    if (Xh.p && scale == xscale && rows == idx->n) return Xh.p;
+    if (failed || stream_capturing(s)) return nullptr;
     // (a stale shadow can only be one whose rows are a prefix at another scale or count: mutators drop or extend it while no
     //  search is in flight, so nobody else is reading what is rebuilt here)
-    if (idx->Xh && idx->xh_cap < idx->n) drop_shadow(idx);
-    if (idx->Xh && idx->xh_scale != xscale) {   // another scale: every row is converted again, into the same allocation
-        invalidate_shadow(idx);
-        idx->xh_scale = xscale;
+    if (Xh.p && cap < idx->n) drop();
+    if (Xh.p && scale != xscale) {   // another scale: every row is converted again, into the same allocation
+        invalidate();
+        scale = xscale;
     }
-    if (!idx->Xh) {
-        _Float16* p = nullptr;
-        const int64_t cap = std::max<int64_t>(idx->cap, idx->n);
-        if (hipMalloc((void**)&p, (size_t)(cap + kRowSlack) * idx->d * sizeof(_Float16)) != hipSuccess) {
+    if (!Xh.p) {
+        const int64_t want = std::max<int64_t>(idx->cap, idx->n);
+        if (Xh.alloc((size_t)(want + kRowSlack) * idx->d * sizeof(_Float16)) != hipSuccess) {
             (void)hipGetLastError();
-            idx->xh_failed = true;
+            failed = true;
             return nullptr;
         }
-        idx->Xh = p;
-        idx->xh_cap = cap;
-        idx->xh_rows = 0;
-        idx->xh_scale = xscale;
-        // (with the shadow — never inside a capture, once per index —: the refusal count and its host-mapped mirror, tile_flags_wanted)
-        if (!idx->rf_dev && hipMalloc((void**)&idx->rf_dev, sizeof(unsigned int)) == hipSuccess) {
-            if (hipMemset(idx->rf_dev, 0, sizeof(unsigned int)) != hipSuccess || idx->rf_host.reserve(64) != 0) {
-                (void)hipFree(idx->rf_dev);
-                idx->rf_dev = nullptr;
-            } else {
-                *reinterpret_cast<volatile unsigned int*>(idx->rf_host.p) = 0u;
-            }
-        }
-        (void)hipGetLastError();
+        cap = want;
+        rows = 0;
+        scale = xscale;
+        (void)idx->rf.ensure(1);  // (with the shadow — never inside a capture, once per index —: the refusal count of tile_flags_wanted)
+        (void)hipGetLastError();  // (unconditional on purpose: without it the GPU suite, run in order, met a stale HIP error at a later launch check)
     }
-    if (launch_half_shadow(idx->X + idx->xh_rows * idx->ld, idx->ld, idx->d, idx->n - idx->xh_rows, xscale,
-                           idx->Xh + idx->xh_rows * idx->d, idx->device, s) != 0 ||
+    if (launch_half_shadow(idx->X.p + rows * idx->ld, idx->ld, idx->d, idx->n - rows, xscale, Xh.p + rows * idx->d, idx->device, s) != 0 ||
         hipStreamSynchronize(s) != hipSuccess) {
-        drop_shadow(idx);
-        idx->xh_failed = true;
+        drop();
+        failed = true;
         return nullptr;
     }
-    idx->xh_rows = idx->n;
-    return idx->Xh;
+    rows = idx->n;
+    return Xh.p;
 }
 
 // L2 over rows of mixed norms (launch_half_pass: l2off): |x_r|^2 / 2 of the shadow's rows, 4 bytes per row beside it (+ zeroed
 // slack: the kernel fetches a whole tile's offsets), built on first use and caught up after appends here; dropped with the
 // shadow.  NULL: no complete shadow, allocation failed, or the stream is being captured before the array exists (the pass
 // then nominates by inner product and the norm-range certificate sends what it cannot certify to the exact kernels).
-const float* ensure_offsets(const mvdb_index* idx, hipStream_t s) {
+const float* ShadowStore::ensure_offsets(const mvdb_index* idx, hipStream_t s) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    if (!idx->Xh || idx->xh_rows != idx->n) return nullptr;
-    if (idx->Hn && idx->hn_rows == idx->n) return idx->Hn;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive) return nullptr;
-    if (!idx->Hn) {
-        float* h = nullptr;
-        const size_t bytes = (size_t)(idx->xh_cap + kRowSlack) * sizeof(float);
-        if (hipMalloc((void**)&h, bytes) != hipSuccess || hipMemsetAsync(h, 0, bytes, s) != hipSuccess) {
+    if (!Xh.p || rows != idx->n) return nullptr;
+    if (Hn.p && hn_rows == idx->n) return Hn.p;
+    if (stream_capturing(s)) return nullptr;
+    if (!Hn.p) {
+        const size_t bytes = (size_t)(cap + kRowSlack) * sizeof(float);
+        if (Hn.alloc(bytes) != hipSuccess || hipMemsetAsync(Hn.p, 0, bytes, s) != hipSuccess) {
             (void)hipGetLastError();
-            if (h) (void)hipFree(h);
+            Hn.release();
             return nullptr;
         }
-        idx->Hn = h;
-        idx->hn_rows = 0;
+        hn_rows = 0;
     }
-    if (launch_half_norms(idx->X + idx->hn_rows * idx->ld, idx->ld, idx->d, idx->n - idx->hn_rows, idx->Hn + idx->hn_rows, idx->device,
-                          s) != 0 ||
+    if (launch_half_norms(idx->X.p + hn_rows * idx->ld, idx->ld, idx->d, idx->n - hn_rows, Hn.p + hn_rows, idx->device, s) != 0 ||
         hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipFree(idx->Hn);
-        idx->Hn = nullptr;
-        idx->hn_rows = 0;
+        Hn.release();
+        hn_rows = 0;
         return nullptr;
     }
-    idx->hn_rows = idx->n;
-    return idx->Hn;
+    hn_rows = idx->n;
+    return Hn.p;
+}
+
+// add: the shadow follows when it is there, still fits and the scale the new norm bound asks for is the one it was built with
+int ShadowStore::extend(mvdb_index* idx, int64_t n_new) {
+    if (!Xh.p) {
+        failed = false;
+        return 0;
+    }
+    const float xscale = half_xscale(idx->row_norm_bound);
+    if (cap < idx->n + n_new) {
+        drop();
+        return 0;
+    }
+    if (rows != idx->n || xscale != scale) {   // (the next batch search converts every row again, in place)
+        invalidate();
+        return 0;
+    }
+    MVDB_TRY(launch_half_shadow(idx->X.p + idx->n * idx->ld, idx->ld, idx->d, n_new, xscale, Xh.p + idx->n * idx->d, idx->device, idx->mut));
+    MVDB_HIP(hipStreamSynchronize(idx->mut));
+    rows = idx->n + n_new;
+    return 0;
 }
 
 // ---- the int8 code of the rows and the single-query prefilter route (code8_scan.hpp) -------------------
@@ -1867,126 +1934,102 @@ constexpr int64_t kCode8MaxCapacity = 65536;
 // pay for it, so a workload that alternates one delete and one query never builds.
 constexpr int kCode8RebuildAfter = 2;
 
-bool stream_capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    return s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
-}
-
 // (count_rebuild: the rows changed under a code that was held or wanted — the wait starts again, whether or not a code is
 //  held right now: every delete of a delete / query alternation restarts it, so such a workload never builds)
-void drop_code8(const mvdb_index* idx, bool count_rebuild = true) {
-    if (idx->C8) (void)hipFree(idx->C8);
-    if (idx->c8_ar) (void)hipFree(idx->c8_ar);
-    if (idx->c8_samp) (void)hipFree(idx->c8_samp);
-    idx->C8 = nullptr;
-    idx->c8_ar = nullptr;
-    idx->c8_samp = nullptr;
-    idx->c8_cap = idx->c8_rows = idx->c8_samp_n = 0;
-    if (count_rebuild && idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
+void Code8Store::drop(bool count_rebuild) {
+    C8.release();
+    ar.release();
+    samp.release();
+    cap = rows = samp_n = 0;
+    if (count_rebuild && wanted.load()) wait.store(kCode8RebuildAfter);
 }
-// rows were renumbered: emptied, the allocation kept (invalidate_shadow)
-void invalidate_code8(const mvdb_index* idx) {
-    if (idx->c8_wanted.load()) idx->c8_wait.store(kCode8RebuildAfter);
-    idx->c8_rows = idx->c8_samp_n = 0;
+// rows were renumbered: emptied, the allocation kept (ShadowStore::invalidate)
+void Code8Store::invalidate() {
+    if (wanted.load()) wait.store(kCode8RebuildAfter);
+    rows = samp_n = 0;
 }
 
-// the low plane lies behind the high plane of the whole CAPACITY: add into reserved space moves nothing
-uint8_t* c8_low(const mvdb_index* idx) { return idx->C8 + code8_low_offset(idx->c8_cap, idx->d); }
-
-int code8_convert(const mvdb_index* idx, int64_t row0, int64_t rows, hipStream_t s) {
-    if (rows > 0) {
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
-        hipLaunchKernelGGL(code8_build_kernel, dim3(grid), dim3(256), 0, s, (const float*)(idx->X + row0 * idx->ld), idx->ld, idx->d, rows,
-                           idx->C8 + row0 * code8_high_stride(idx->d), c8_low(idx) + row0 * code8_low_stride(idx->d), idx->c8_ar + row0,
-                           (const int64_t*)nullptr, (int64_t)0);
-    }
+// The one launch of code8_build_kernel: stored rows [row0, row0 + n) coded from the matrix, or — list_dev — the n stored rows
+// it names, those below `rows` (set_rows: what the code does not cover yet is coded by the next build anyway).
+int Code8Store::build(const mvdb_index* idx, int64_t row0, int64_t n, hipStream_t s, const int64_t* list_dev) {
+    if (n > 0)
+        hipLaunchKernelGGL(code8_build_kernel, dim3(row_grid(idx->device, n)), dim3(256), 0, s, (const float*)(idx->X.p + row0 * idx->ld), idx->ld,
+                           idx->d, n, C8.p + row0 * code8_high_stride(idx->d), low(idx->d) + row0 * code8_low_stride(idx->d), ar.p + row0,
+                           list_dev, list_dev ? rows : (int64_t)0);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
 
-// The stored copy of the floor's sample.  It is VALID iff the code is complete (c8_rows == n) and the copy was gathered for
-// this n after the last write to the code (c8_samp_n == n): code8_sample_valid is the only test, this function the only
-// writer.  Every writer of the code calls it behind its code8_build_kernel launch, on the same stream, with the row count the
-// index will have (ensure_code8: a build; extend_code8: add, where n moves and with it every slot; set_rows_core: rows
+// The stored copy of the floor's sample.  It is VALID iff the code is complete (rows == n) and the copy was gathered for
+// this n after the last write to the code (samp_n == n): sample_valid is the only test, this function the only
+// writer.  Every writer of the code calls it behind its build, on the same stream, with the row count the
+// index will have (ensure: a build; extend: add, where n moves and with it every slot; set_rows_core: rows
 // rewritten in place — a captured graph of the route stays valid across that, so the copy follows eagerly); the paths that
-// empty or free the code (invalidate_code8, drop_code8) mark it stale or free it with the code.  Nothing here runs inside a
-// stream capture: ensure_code8 refuses before it gets here, the mutators run on idx->mut.
-int code8_sample_gather(const mvdb_index* idx, int64_t n, hipStream_t s) {
-    idx->c8_samp_n = 0;
+// empty or free the code (invalidate, drop) mark it stale or free it with the code.  Nothing here runs inside a
+// stream capture: ensure refuses before it gets here, the mutators run on idx->mut.
+int Code8Store::gather_sample(const mvdb_index* idx, int64_t n, hipStream_t s) {
+    samp_n = 0;
     const int64_t chunks = kCode8Seed * (idx->d / 16);
     const int grid = (int)std::min<int64_t>((chunks + 255) / 256, (int64_t)device_cus(idx->device) * 16);
-    hipLaunchKernelGGL(code8_sample_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)idx->C8, (const uint8_t*)c8_low(idx), (const float2*)idx->c8_ar, n, idx->d,
-                       idx->c8_samp, reinterpret_cast<float2*>(idx->c8_samp + kCode8Seed * idx->d));
+    hipLaunchKernelGGL(code8_sample_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)C8.p, (const uint8_t*)low(idx->d), (const float2*)ar.p, n, idx->d,
+                       samp.p, reinterpret_cast<float2*>(samp.p + kCode8Seed * idx->d));
     MVDB_HIP(hipGetLastError());
-    idx->c8_samp_n = n;
+    samp_n = n;
     return 0;
 }
-bool code8_sample_valid(const mvdb_index* idx) { return idx->c8_samp && idx->c8_rows == idx->n && idx->c8_samp_n == idx->n; }
 
 // The code for a single query on stream s (caller holds the index shared).  false: the exact scan serves this call.
-bool ensure_code8(const mvdb_index* idx, hipStream_t s) {
+bool Code8Store::ensure(const mvdb_index* idx, hipStream_t s) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    if (idx->C8 && code8_sample_valid(idx)) return true;   // (complete code AND a current copy of the floor's sample)
-    if (idx->c8_failed || stream_capturing(s)) return false;
-    idx->c8_wanted.store(true);
-    if (idx->c8_wait.load(std::memory_order_relaxed) > 0) {
-        idx->c8_wait.fetch_sub(1, std::memory_order_relaxed);
+    if (C8.p && sample_valid(idx->n)) return true;   // (complete code AND a current copy of the floor's sample)
+    if (failed || stream_capturing(s)) return false;
+    wanted.store(true);
+    if (wait.load(std::memory_order_relaxed) > 0) {
+        wait.fetch_sub(1, std::memory_order_relaxed);
         return false;
     }
-    if (idx->C8 && idx->c8_cap < idx->n) drop_code8(idx, false);
-    if (!idx->C8) {
-        const int64_t cap = std::max<int64_t>(idx->cap, idx->n);
-        bool ok = hipMalloc((void**)&idx->C8, (size_t)cap * idx->d) == hipSuccess &&
-                  hipMalloc((void**)&idx->c8_ar, (size_t)cap * sizeof(float2)) == hipSuccess &&
-                  hipMalloc((void**)&idx->c8_samp, code8_sample_bytes(idx->d)) == hipSuccess;
-        if (ok && !idx->c8_ctr_dev) {
-            ok = hipMalloc((void**)&idx->c8_ctr_dev, 4 * sizeof(unsigned int)) == hipSuccess &&
-                 hipMemset(idx->c8_ctr_dev, 0, 4 * sizeof(unsigned int)) == hipSuccess && idx->c8_stats.reserve(64) == 0;
-            if (ok) memset(idx->c8_stats.p, 0, 64);
-        }
-        if (!ok) {
+    if (C8.p && cap < idx->n) drop(false);
+    if (!C8.p) {
+        const int64_t want = std::max<int64_t>(idx->cap, idx->n);
+        if (C8.alloc((size_t)want * idx->d) != hipSuccess || ar.alloc((size_t)want * sizeof(float2)) != hipSuccess ||
+            samp.alloc(code8_sample_bytes(idx->d)) != hipSuccess || !idx->c8_ctr.ensure(4)) {
             (void)hipGetLastError();
-            drop_code8(idx, false);
-            idx->c8_failed = true;
+            drop(false);
+            failed = true;
             return false;
         }
-        idx->c8_cap = cap;
-        idx->c8_rows = 0;
+        cap = want;
+        rows = 0;
     }
-    if (code8_convert(idx, idx->c8_rows, idx->n - idx->c8_rows, s) != 0 || code8_sample_gather(idx, idx->n, s) != 0 ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        drop_code8(idx, false);
-        idx->c8_failed = true;
+    if (build(idx, rows, idx->n - rows, s) != 0 || gather_sample(idx, idx->n, s) != 0 || hipStreamSynchronize(s) != hipSuccess) {
+        drop(false);
+        failed = true;
         return false;
     }
-    idx->c8_rows = idx->n;
+    rows = idx->n;
     return true;
 }
 
-// One decision per call the route would serve: true = suspended, the exact scan answers (single_route_suspended's windows).
-bool code8_suspended(const mvdb_index* idx) {
-    if (idx->c8_suspend_left.load(std::memory_order_relaxed) > 0) {
-        idx->c8_suspend_left.fetch_sub(1, std::memory_order_relaxed);
-        return true;
+// add: the code follows when it is there, complete and still fits (the rows are coded from the matrix, on the mutators' stream)
+int Code8Store::extend(mvdb_index* idx, int64_t n_new) {
+    if (!C8.p) return 0;
+    if (cap < idx->n + n_new) {
+        drop();
+        return 0;
     }
-    const unsigned int calls = idx->c8_calls.fetch_add(1, std::memory_order_relaxed) + 1;
-    if (calls - idx->c8_window_calls.load(std::memory_order_relaxed) >= (unsigned int)kSingleWindow && idx->c8_stats.p) {
-        const unsigned int fails = *reinterpret_cast<volatile unsigned int*>(idx->c8_stats.p);
-        if ((fails - idx->c8_window_fail.load(std::memory_order_relaxed)) * 2 >= (unsigned int)kSingleWindow) {
-            idx->c8_suspend_left.store(kSingleSuspend, std::memory_order_relaxed);
-            idx->c8_suspensions.fetch_add(1, std::memory_order_relaxed);
-        }
-        idx->c8_window_calls.store(calls, std::memory_order_relaxed);
-        idx->c8_window_fail.store(fails, std::memory_order_relaxed);
-    }
-    return false;
+    if (rows != idx->n) return 0;  // emptied by a delete: the next eligible query codes every row again
+    MVDB_TRY(build(idx, idx->n, n_new, idx->mut));
+    MVDB_TRY(gather_sample(idx, idx->n + n_new, idx->mut));   // n moves: every slot of the floor's sample does
+    MVDB_HIP(hipStreamSynchronize(idx->mut));
+    rows = idx->n + n_new;
+    return 0;
 }
 
 bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, const uint64_t* mask_dev, int64_t n) {
     if (nq != 1 || !idx->kn.code8_single_query || idx->kn.shadow_single_query) return false;
     if (idx->metric != MVDB_METRIC_IP || rows_dev || mask_dev || k > kMaxFusedK) return false;
     if (n != idx->n || n < kCode8MinRows || !code8_dim(idx->d) || idx->ld != idx->d) return false;
-    if (!(idx->row_norm_bound > 0.f) || !(idx->row_norm_bound < 1.0e30f) || idx->c8_failed) return false;
+    if (!(idx->row_norm_bound > 0.f) || !(idx->row_norm_bound < 1.0e30f) || idx->code.failed) return false;
     return true;
 }
 
@@ -2078,8 +2121,8 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     const size_t cand_keys = (size_t)scan_grid_upper_bound(idx->device) * k;
     const bool capturing = stream_capturing(s);
     if (capturing && (ws->c8.cap < off || ws->cand.cap < cand_keys)) return 0;  // nothing is allocated inside a capture
-    if (code8_suspended(idx)) return 0;
-    if (!ensure_code8(idx, s)) return 0;
+    if (idx->c8_route.suspended(idx->c8_ctr.mirror())) return 0;
+    if (!idx->code.ensure(idx, s)) return 0;
     MVDB_TRY(ws->c8.reserve(off));
     MVDB_TRY(ws->cand.reserve(cand_keys));
     char* base = ws->c8.p;
@@ -2095,8 +2138,8 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     // 1. the query's planes and margin terms (every block; block 0 leaves them here and zeroes the candidate counter), and
     //    per block the k best LOWER bounds of its share of the seed sample, from its stored copy
     Code8SeedArgs sd;
-    sd.scodes = idx->c8_samp;
-    sd.sar = reinterpret_cast<const float2*>(idx->c8_samp + kCode8Seed * d);
+    sd.scodes = idx->code.samp.p;
+    sd.sar = reinterpret_cast<const float2*>(idx->code.samp.p + kCode8Seed * d);
     sd.d = d;
     sd.q = a0.q;
     sd.normalize_q = a0.normalize_q;
@@ -2114,9 +2157,9 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     }));
     // 2. the floor — the k-th best of those lower bounds, merged by every block at its head — and the prefilter over the codes
     Code8ScanArgs c;
-    c.high = idx->C8;
-    c.low = c8_low(idx);
-    c.ar = idx->c8_ar;
+    c.high = idx->code.C8.p;
+    c.low = idx->code.low(d);
+    c.ar = idx->code.ar.p;
     c.n = idx->n;
     c.d = d;
     c.hstride = code8_high_stride(d);
@@ -2130,7 +2173,7 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.cand = cand;
     c.cap = cap;
     c.counter = counter;
-    c.survivors = reinterpret_cast<unsigned long long*>(idx->c8_ctr_dev + 2);
+    c.survivors = reinterpret_cast<unsigned long long*>(idx->c8_ctr.dev() + 2);
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
         return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
@@ -2151,8 +2194,8 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     r.lists = ws->cand.p;
     r.active = active;
     r.gate = gate;
-    r.ctr_dev = idx->c8_ctr_dev;
-    r.stats = (volatile unsigned int*)idx->c8_stats.p;
+    r.ctr_dev = idx->c8_ctr.dev();
+    r.stats = idx->c8_ctr.mirror();
     // (the exact scan's shape: the arithmetic is restated for exactly that; the route serves unpadded rows that fill it)
     MVDB_TRY(with_code8_exact_shape(a0.d4, [&](auto shape) {
         using S = decltype(shape);
@@ -2187,28 +2230,24 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     return 0;
 }
 
-int grow(mvdb_index* idx, int64_t need) {
+// The only place the matrix is reallocated (caller: index held exclusively, searches quiesced): room for `need` rows, with
+// half as much again unless `exact` (reserve: the caller knows the final size).
+int grow(mvdb_index* idx, int64_t need, bool exact) {
     if (need <= idx->cap) return 0;
-    int64_t cap = std::max<int64_t>(need, idx->cap + idx->cap / 2);
-    cap = std::max<int64_t>(cap, 1024);
+    const int64_t cap = exact ? need : std::max<int64_t>(std::max<int64_t>(need, idx->cap + idx->cap / 2), 1024);
     // the fp16 shadow (50 % of the matrix's bytes) goes first: it is sized for the old capacity anyway (rebuilt by the next
     // batch search), and an add on a nearly full device must not fail for a copy that is about to be dropped
-    drop_shadow(idx);
-    drop_code8(idx);
-    float* nx = nullptr;
-    MVDB_HIP(hipMalloc((void**)&nx, (size_t)(cap + kRowSlack) * idx->ld * sizeof(float)));
+    idx->shadow.drop();
+    idx->code.drop();
+    DevMem<float> nx;
+    MVDB_HIP(nx.alloc((size_t)(cap + kRowSlack) * idx->ld * sizeof(float)));
     if (idx->n > 0) {
-        hipError_t e = hipMemcpyAsync(nx, idx->X, (size_t)idx->n * idx->ld * sizeof(float),
-                                      hipMemcpyDeviceToDevice, idx->mut);
+        hipError_t e = hipMemcpyAsync(nx.p, idx->X.p, (size_t)idx->n * idx->ld * sizeof(float), hipMemcpyDeviceToDevice, idx->mut);
         if (e == hipSuccess) e = hipStreamSynchronize(idx->mut);
-        if (e != hipSuccess) {
-            (void)hipFree(nx);
-            return fail(MVDB_ERR_HIP, "device copy while growing index failed: %s",
-                        hipGetErrorString(e));
-        }
+        if (e != hipSuccess)
+            return fail(MVDB_ERR_HIP, "device copy while %s failed: %s", exact ? "reserving" : "growing index", hipGetErrorString(e));
     }
-    if (idx->X) (void)hipFree(idx->X);
-    idx->X = nx;
+    std::swap(idx->X.p, nx.p);  // (the old matrix goes with nx)
     idx->cap = cap;
     return 0;
 }
@@ -2217,10 +2256,7 @@ int normalize_range(const mvdb_index* idx, float* base, int64_t n, hipStream_t s
     if (n <= 0) return 0;
     const Shape sh = choose_shape(idx->d4);
     const int rpi = 64 / sh.G;
-    const int64_t waves = (n + rpi - 1) / rpi;
-    const int cus = device_cus(idx->device);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)cus * 8));
-    hipLaunchKernelGGL(normalize_rows_kernel, dim3(grid), dim3(256), 0, s, base, n, idx->ld, idx->d4,
+    hipLaunchKernelGGL(normalize_rows_kernel, dim3(row_grid(idx->device, (n + rpi - 1) / rpi, 8)), dim3(256), 0, s, base, n, idx->ld, idx->d4,
                        sh.G);
     MVDB_HIP(hipGetLastError());
     return 0;
@@ -2290,14 +2326,10 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     const std::string n(name);
     if (n == "shadow_single_query") {
         idx->kn.shadow_single_query = value != 0;
-        idx->sq_suspend_left.store(0);   // a fresh start: the route probes again from its next call
-        idx->sq_window_calls.store(idx->sq_calls.load());
-        if (idx->sq_fail_host.p) idx->sq_window_fail.store(*reinterpret_cast<volatile unsigned int*>(idx->sq_fail_host.p));
+        idx->sq_route.restart(idx->sq_fail.mirror());
     } else if (n == "code8_single_query") {
         idx->kn.code8_single_query = value != 0;
-        idx->c8_suspend_left.store(0);
-        idx->c8_window_calls.store(idx->c8_calls.load());
-        if (idx->c8_stats.p) idx->c8_window_fail.store(*reinterpret_cast<volatile unsigned int*>(idx->c8_stats.p));
+        idx->c8_route.restart(idx->c8_ctr.mirror());
     } else if (n == "code8_capacity") {  // diagnostic: a small candidate capacity makes calls take the fallback
         if (value <= 0 || value > kCode8MaxCapacity) return fail(MVDB_ERR_ARG, "code8_capacity must lie in [1, %lld]", (long long)kCode8MaxCapacity);
         idx->kn.code8_capacity = value;
@@ -2318,7 +2350,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
 }
 
 long long mvdb_index_single_route_suspensions(const mvdb_index* idx) {
-    return idx ? (long long)idx->sq_suspensions.load() : -1;
+    return idx ? (long long)idx->sq_route.suspensions.load() : -1;
 }
 
 int mvdb_index_free(mvdb_index* idx) {
@@ -2328,17 +2360,11 @@ int mvdb_index_free(mvdb_index* idx) {
         std::unique_lock<std::shared_mutex> lk(idx->mu);
         (void)quiesce(idx);
         if (idx->mut) (void)hipStreamDestroy(idx->mut);
-        void* words[] = {idx->normmax, idx->ctmp, idx->sq_fail_dev, idx->rf_dev, idx->c8_ctr_dev, idx->rg_ctr_dev};
-        for (void* p : words)
-            if (p) (void)hipFree(p);
-        drop_shadow(idx);
-        drop_code8(idx);
         for (Workspace* w : idx->free_ws) delete w;
         for (auto& kv : idx->stream_ws) delete kv.second;
         delete idx->default_stream_ws;
-        if (idx->X) (void)hipFree(idx->X);
     }
-    delete idx;  // (the host-mapped mirrors it owns go here)
+    delete idx;  // (the matrix, the stores, the counters and their mirrors: every member frees what it holds)
     return 0;
 }
 
@@ -2348,8 +2374,8 @@ int mvdb_index_reset(mvdb_index* idx) {
     DeviceGuard dg(idx->device);
     MVDB_TRY(quiesce(idx));
     idx->n = 0;
-    drop_shadow(idx);
-    drop_code8(idx);
+    idx->shadow.drop();
+    idx->code.drop();
     idx->row_norm_bound = 0.f;
     idx->norm2_lo = INFINITY;
     idx->norm2_hi = 0.f;
@@ -2361,27 +2387,25 @@ int64_t mvdb_index_ntotal(const mvdb_index* idx) { return idx ? idx->n : -1; }
 int64_t mvdb_index_shadow_rows(const mvdb_index* idx) {
     if (!idx) return -1;
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    return idx->Xh ? idx->xh_rows : 0;
+    return idx->shadow.Xh.p ? idx->shadow.rows : 0;
 }
 int64_t mvdb_index_code8_rows(const mvdb_index* idx) {
     if (!idx) return -1;
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    return idx->C8 ? idx->c8_rows : 0;
+    return idx->code.C8.p ? idx->code.rows : 0;
 }
 int mvdb_index_code8_counters(const mvdb_index* idx, long long* fallbacks, long long* last_candidates, long long* calls) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
-    const volatile unsigned int* st = reinterpret_cast<const volatile unsigned int*>(idx->c8_stats.p);
-    if (fallbacks) *fallbacks = st ? (long long)st[0] : 0;
-    if (last_candidates) *last_candidates = st ? (long long)st[1] : 0;
-    if (calls) *calls = st ? (long long)st[2] : 0;
+    if (fallbacks) *fallbacks = (long long)idx->c8_ctr.read(0);
+    if (last_candidates) *last_candidates = (long long)idx->c8_ctr.read(1);
+    if (calls) *calls = (long long)idx->c8_ctr.read(2);
     return 0;
 }
 int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries, long long* last_candidates) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
-    const volatile unsigned long long* st = reinterpret_cast<const volatile unsigned long long*>(idx->rg_stats.p);
     if (shared_calls) *shared_calls = (long long)idx->rg_shared_calls.load();
-    if (fallback_queries) *fallback_queries = st ? (long long)st[0] : 0;
-    if (last_candidates) *last_candidates = st ? (long long)st[1] : 0;
+    if (fallback_queries) *fallback_queries = (long long)idx->rg_ctr.read<unsigned long long>(0);
+    if (last_candidates) *last_candidates = (long long)idx->rg_ctr.read<unsigned long long>(1);
     return 0;
 }
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
@@ -2391,10 +2415,10 @@ double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
 int mvdb_index_code8_refined(const mvdb_index* idx, long long* rows) {
     if (!idx || !rows) return fail(MVDB_ERR_ARG, "mvdb_index_code8_refined: bad arguments");
     *rows = 0;
-    if (!idx->c8_ctr_dev) return 0;
+    if (!idx->c8_ctr.dev()) return 0;
     DeviceGuard dg(idx->device);
     unsigned long long v = 0;
-    MVDB_HIP(hipMemcpy(&v, idx->c8_ctr_dev + 2, sizeof(v), hipMemcpyDeviceToHost));
+    MVDB_HIP(hipMemcpy(&v, idx->c8_ctr.dev() + 2, sizeof(v), hipMemcpyDeviceToHost));
     *rows = (long long)v;
     return 0;
 }
@@ -2435,24 +2459,7 @@ int mvdb_index_reserve(mvdb_index* idx, int64_t n) {
     DeviceGuard dg(idx->device);
     if (n <= idx->cap) return 0;
     MVDB_TRY(quiesce(idx));
-    // exact-size growth (no 1.5x slack): the caller knows the final size
-    drop_shadow(idx);  // before the new matrix is allocated (see grow)
-    drop_code8(idx);
-    float* nx = nullptr;
-    MVDB_HIP(hipMalloc((void**)&nx, (size_t)(n + kRowSlack) * idx->ld * sizeof(float)));
-    if (idx->n > 0) {
-        hipError_t e = hipMemcpyAsync(nx, idx->X, (size_t)idx->n * idx->ld * sizeof(float), hipMemcpyDeviceToDevice, idx->mut);
-        if (e == hipSuccess) e = hipStreamSynchronize(idx->mut);
-        if (e != hipSuccess) {
-            (void)hipFree(nx);
-            return fail(MVDB_ERR_HIP, "device copy while reserving failed: %s", hipGetErrorString(e));
-        }
-    }
-    if (idx->X) (void)hipFree(idx->X);
-    idx->X = nx;
-    idx->cap = n;
-    drop_shadow(idx);
-    return 0;
+    return grow(idx, n, /*exact=*/true);
 }
 
 // Keeps idx->row_norm_bound >= |row| for every stored row: 1 for rows normalised on the device, one
@@ -2468,13 +2475,13 @@ static int note_row_norms(mvdb_index* idx, const float* dst, int64_t n, int norm
     }
     // raw rows — and every row of an L2 index, whose certified batch passes need BOTH ends of the norm range (a zero row
     // that normalisation left alone has norm 0): one extra read of the new rows
-    if (!idx->normmax) MVDB_HIP(hipMalloc((void**)&idx->normmax, 2 * sizeof(unsigned int)));
-    unsigned int* dmax = idx->normmax;
+    if (!idx->normmax.p) MVDB_HIP(idx->normmax.alloc(2 * sizeof(unsigned int)));
+    unsigned int* dmax = idx->normmax.p;
     unsigned int bits[2] = {0u, 0x7F800000u};  // max = 0, min = +inf
     hipError_t e = hipMemcpyAsync(dmax, bits, sizeof(bits), hipMemcpyHostToDevice, idx->mut);
     if (e == hipSuccess) e = hipStreamSynchronize(idx->mut);  // (bits is a stack buffer)
     if (e == hipSuccess) {
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)device_cus(idx->device) * 16));
+        const int grid = row_grid(idx->device, n);
         if (l2)
             hipLaunchKernelGGL(row_norm2_range_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d4, dmax, list_dev);
         else
@@ -2502,40 +2509,24 @@ static int note_row_norms(mvdb_index* idx, const float* dst, int64_t n, int norm
     return 0;
 }
 
-// add: the shadow follows when it is there, still fits and the scale the new norm bound asks for is the one it was built with
-static int extend_shadow(mvdb_index* idx, int64_t n_new) {
-    if (!idx->Xh) {
-        idx->xh_failed = false;
-        return 0;
-    }
-    const float xscale = half_xscale(idx->row_norm_bound);
-    if (idx->xh_cap < idx->n + n_new) {
-        drop_shadow(idx);
-        return 0;
-    }
-    if (idx->xh_rows != idx->n || xscale != idx->xh_scale) {   // (the next batch search converts every row again, in place)
-        invalidate_shadow(idx);
-        return 0;
-    }
-    MVDB_TRY(launch_half_shadow(idx->X + idx->n * idx->ld, idx->ld, idx->d, n_new, xscale, idx->Xh + idx->n * idx->d, idx->device,
-                                idx->mut));
-    MVDB_HIP(hipStreamSynchronize(idx->mut));
-    idx->xh_rows = idx->n + n_new;
-    return 0;
-}
-
-// add: the code follows when it is there, complete and still fits (the rows are coded from the matrix, on the mutators' stream)
-static int extend_code8(mvdb_index* idx, int64_t n_new) {
-    if (!idx->C8) return 0;
-    if (idx->c8_cap < idx->n + n_new) {
-        drop_code8(idx);
-        return 0;
-    }
-    if (idx->c8_rows != idx->n) return 0;  // emptied by a delete: the next eligible query codes every row again
-    MVDB_TRY(code8_convert(idx, idx->n, n_new, idx->mut));
-    MVDB_TRY(code8_sample_gather(idx, idx->n + n_new, idx->mut));   // n moves: every slot of the floor's sample does
-    MVDB_HIP(hipStreamSynchronize(idx->mut));
-    idx->c8_rows = idx->n + n_new;
+// What the three add entry points share (they keep their argument checks): room for n more rows, then fill(dst) enqueues the
+// rows behind dst on idx->mut.  The rows are not visible to searches until idx->n moves, at the end; everything runs on the
+// index's own stream.
+static int append_rows(mvdb_index* idx, int64_t n, int normalize, const std::function<int(float*)>& fill) {
+    std::unique_lock<std::shared_mutex> lk(idx->mu);
+    DeviceGuard dg(idx->device);
+    if (idx->n + n > 0xFFFFFFFFll)
+        return fail(MVDB_ERR_ARG, "more than 2^32-1 rows per device index are not supported");
+    MVDB_TRY(quiesce(idx));
+    MVDB_TRY(grow(idx, idx->n + n, /*exact=*/false));
+    float* dst = idx->X.p + idx->n * idx->ld;
+    MVDB_TRY(fill(dst));
+    if (normalize) MVDB_TRY(normalize_range(idx, dst, n, idx->mut));
+    MVDB_HIP(hipStreamSynchronize(idx->mut));  // the caller's buffer is free again, the rows are in place
+    MVDB_TRY(note_row_norms(idx, dst, n, normalize));
+    MVDB_TRY(idx->shadow.extend(idx, n));
+    MVDB_TRY(idx->code.extend(idx, n));
+    idx->n += n;
     return 0;
 }
 
@@ -2544,28 +2535,16 @@ int mvdb_index_add(mvdb_index* idx, const float* x_host, int64_t n, int normaliz
     if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
     if (n == 0) return 0;
     if (!x_host) return fail(MVDB_ERR_ARG, "x is NULL");
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    DeviceGuard dg(idx->device);
-    if (idx->n + n > 0xFFFFFFFFll)
-        return fail(MVDB_ERR_ARG, "more than 2^32-1 rows per device index are not supported");
-    MVDB_TRY(quiesce(idx));
-    MVDB_TRY(grow(idx, idx->n + n));
-    float* dst = idx->X + idx->n * idx->ld;
-    // (the rows are not visible to searches until idx->n moves, below; everything runs on the index's own stream)
-    if (idx->ld == idx->d) {
-        MVDB_HIP(hipMemcpyAsync(dst, x_host, (size_t)n * idx->d * sizeof(float), hipMemcpyHostToDevice, idx->mut));
-    } else {
-        MVDB_HIP(hipMemsetAsync(dst, 0, (size_t)n * idx->ld * sizeof(float), idx->mut));
-        MVDB_HIP(hipMemcpy2DAsync(dst, idx->ld * sizeof(float), x_host, idx->d * sizeof(float),
-                                  idx->d * sizeof(float), (size_t)n, hipMemcpyHostToDevice, idx->mut));
-    }
-    if (normalize) MVDB_TRY(normalize_range(idx, dst, n, idx->mut));
-    MVDB_HIP(hipStreamSynchronize(idx->mut));  // the caller's buffer is free again, the rows are in place
-    MVDB_TRY(note_row_norms(idx, dst, n, normalize));
-    MVDB_TRY(extend_shadow(idx, n));
-    MVDB_TRY(extend_code8(idx, n));
-    idx->n += n;
-    return 0;
+    return append_rows(idx, n, normalize, [&](float* dst) {
+        if (idx->ld == idx->d) {
+            MVDB_HIP(hipMemcpyAsync(dst, x_host, (size_t)n * idx->d * sizeof(float), hipMemcpyHostToDevice, idx->mut));
+        } else {
+            MVDB_HIP(hipMemsetAsync(dst, 0, (size_t)n * idx->ld * sizeof(float), idx->mut));
+            MVDB_HIP(hipMemcpy2DAsync(dst, idx->ld * sizeof(float), x_host, idx->d * sizeof(float),
+                                      idx->d * sizeof(float), (size_t)n, hipMemcpyHostToDevice, idx->mut));
+        }
+        return 0;
+    });
 }
 
 int mvdb_index_add_device(mvdb_index* idx, const float* x_dev, int64_t n, int normalize) {
@@ -2573,34 +2552,20 @@ int mvdb_index_add_device(mvdb_index* idx, const float* x_dev, int64_t n, int no
     if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
     if (n == 0) return 0;
     if (!x_dev) return fail(MVDB_ERR_ARG, "x is NULL");
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    DeviceGuard dg(idx->device);
-    if (idx->n + n > 0xFFFFFFFFll)
-        return fail(MVDB_ERR_ARG, "more than 2^32-1 rows per device index are not supported");
-    MVDB_TRY(quiesce(idx));
-    MVDB_TRY(grow(idx, idx->n + n));
-    float* dst = idx->X + idx->n * idx->ld;
-    // x_dev is the caller's: whatever produced it must be complete (or ordered before the legacy stream) — as before, the
-    // copy below waits for the legacy stream only when it is issued there, so it is issued on the mutators' stream after a
-    // legacy-stream join
-    MVDB_HIP(hipStreamSynchronize(nullptr));
-    if (idx->ld == idx->d) {
-        MVDB_HIP(hipMemcpyAsync(dst, x_dev, (size_t)n * idx->d * sizeof(float), hipMemcpyDeviceToDevice, idx->mut));
-    } else {
-        const int cus = device_cus(idx->device);
-        const int64_t total = n * idx->ld;
-        const int grid = (int)std::min<int64_t>((total + 255) / 256, (int64_t)cus * 16);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, x_dev, n, idx->d,
-                           idx->ld);
-        MVDB_HIP(hipGetLastError());
-    }
-    if (normalize) MVDB_TRY(normalize_range(idx, dst, n, idx->mut));
-    MVDB_HIP(hipStreamSynchronize(idx->mut));
-    MVDB_TRY(note_row_norms(idx, dst, n, normalize));
-    MVDB_TRY(extend_shadow(idx, n));
-    MVDB_TRY(extend_code8(idx, n));
-    idx->n += n;
-    return 0;
+    return append_rows(idx, n, normalize, [&](float* dst) {
+        // x_dev is the caller's: whatever produced it must be complete (or ordered before the legacy stream) — as before, the
+        // copy below waits for the legacy stream only when it is issued there, so it is issued on the mutators' stream after a
+        // legacy-stream join
+        MVDB_HIP(hipStreamSynchronize(nullptr));
+        if (idx->ld == idx->d) {
+            MVDB_HIP(hipMemcpyAsync(dst, x_dev, (size_t)n * idx->d * sizeof(float), hipMemcpyDeviceToDevice, idx->mut));
+        } else {
+            const int grid = (int)std::min<int64_t>((n * idx->ld + 255) / 256, (int64_t)device_cus(idx->device) * 16);
+            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, x_dev, n, idx->d, idx->ld);
+            MVDB_HIP(hipGetLastError());
+        }
+        return 0;
+    });
 }
 
 int mvdb_index_add_synthetic(mvdb_index* idx, int64_t n, uint64_t seed, int64_t first_row,
@@ -2608,39 +2573,26 @@ int mvdb_index_add_synthetic(mvdb_index* idx, int64_t n, uint64_t seed, int64_t 
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (n < 0 || first_row < 0) return fail(MVDB_ERR_ARG, "negative row count / offset");
     if (n == 0) return 0;
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    DeviceGuard dg(idx->device);
-    if (idx->n + n > 0xFFFFFFFFll)
-        return fail(MVDB_ERR_ARG, "more than 2^32-1 rows per device index are not supported");
-    MVDB_TRY(quiesce(idx));
-    MVDB_TRY(grow(idx, idx->n + n));
-    float* dst = idx->X + idx->n * idx->ld;
-    const int cus = device_cus(idx->device);
-    const int64_t total = n * idx->d4;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)cus * 16));
-    hipLaunchKernelGGL(synth_fill_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d,
-                       seed, first_row);
-    MVDB_HIP(hipGetLastError());
-    if (normalize) MVDB_TRY(normalize_range(idx, dst, n, idx->mut));
-    MVDB_HIP(hipStreamSynchronize(idx->mut));
-    MVDB_TRY(note_row_norms(idx, dst, n, normalize));
-    MVDB_TRY(extend_shadow(idx, n));
-    MVDB_TRY(extend_code8(idx, n));
-    idx->n += n;
-    return 0;
+    return append_rows(idx, n, normalize, [&](float* dst) {
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n * idx->d4 + 255) / 256, (int64_t)device_cus(idx->device) * 16));
+        hipLaunchKernelGGL(synth_fill_kernel, dim3(grid), dim3(256), 0, idx->mut, dst, n, idx->ld, idx->d, seed, first_row);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 // ---- set_rows: stored rows overwritten in place (contract: mvdb.h) -----------------------------------------------------------
 constexpr size_t kSetStageBytes = 32u << 20;   // one chunk of staged rows: at most this many bytes (and at least one row)
 
-// every row in [0, n), none twice; nothing is enqueued before this has passed
-static int check_row_list(const int64_t* rows_host, int64_t m, int64_t n) {
+// every row in [0, n), none twice; nothing is enqueued before this has passed.  sorted: takes the ascending copy.
+static int check_row_list(const int64_t* rows_host, int64_t m, int64_t n, std::vector<int64_t>* sorted = nullptr) {
     std::vector<int64_t> v(rows_host, rows_host + m);
     std::sort(v.begin(), v.end());
     for (int64_t i = 0; i < m; ++i) {
         if (v[i] < 0 || v[i] >= n) return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)v[i], (long long)n);
         if (i && v[i] == v[i - 1]) return fail(MVDB_ERR_ARG, "row %lld listed twice", (long long)v[i]);
     }
+    if (sorted) sorted->swap(v);
     return 0;
 }
 
@@ -2657,13 +2609,13 @@ static int set_rows_core(mvdb_index* idx, const int64_t* rows_host, const float*
     int64_t* L = idx->set_list.p;
     const Shape sh = choose_shape(idx->d4);
     const int rpi = 64 / sh.G;
-    const int64_t cus = device_cus(idx->device);
     const bool padded = idx->ld != idx->d;
+    ShadowStore& sh16 = idx->shadow;
     if (x_on_device) MVDB_HIP(hipStreamSynchronize(nullptr));  // (mvdb_index_add_device's join with the legacy stream)
     // the shadow at the scale it was built with: should the widened bound ask for another one, it is invalidated below
-    const bool shadow = idx->Xh && idx->xh_rows > 0;
-    const bool offsets = idx->Hn && idx->hn_rows > 0;
-    const bool code = idx->C8 && idx->c8_rows > 0;
+    const bool shadow = sh16.Xh.p && sh16.rows > 0;
+    const bool offsets = sh16.Hn.p && sh16.hn_rows > 0;
+    const bool code = idx->code.C8.p && idx->code.rows > 0;
     for (int64_t i0 = 0; i0 < m; i0 += chunk) {
         const int64_t rows = std::min(chunk, m - i0);
         const float* src = x + i0 * idx->d;
@@ -2671,34 +2623,29 @@ static int set_rows_core(mvdb_index* idx, const int64_t* rows_host, const float*
         if (!padded) {
             MVDB_HIP(hipMemcpyAsync(S, src, (size_t)rows * row_bytes, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, idx->mut));
         } else if (x_on_device) {
-            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows * idx->ld + 255) / 256, cus * 16));
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows * idx->ld + 255) / 256, (int64_t)device_cus(idx->device) * 16));
             hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, S, src, rows, idx->d, idx->ld);
         } else {
             MVDB_HIP(hipMemsetAsync(S, 0, (size_t)rows * row_bytes, idx->mut));
             MVDB_HIP(hipMemcpy2DAsync(S, row_bytes, src, idx->d * sizeof(float), idx->d * sizeof(float), (size_t)rows, hipMemcpyHostToDevice,
                                       idx->mut));
         }
-        const int64_t waves = (rows + rpi - 1) / rpi;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, cus * 8));
-        hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, idx->X, (const float*)S, (const int64_t*)L, rows, idx->ld,
-                           idx->d4, (int)(idx->ld / 4), sh.G, normalize);
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3(row_grid(idx->device, (rows + rpi - 1) / rpi, 8)), dim3(256), 0, idx->mut, idx->X.p,
+                           (const float*)S, (const int64_t*)L, rows, idx->ld, idx->d4, (int)(idx->ld / 4), sh.G, normalize);
         MVDB_HIP(hipGetLastError());
         if (shadow)
-            MVDB_TRY(launch_half_shadow(idx->X, idx->ld, idx->d, rows, idx->xh_scale, idx->Xh, idx->device, idx->mut, L, idx->xh_rows));
-        if (offsets) MVDB_TRY(launch_half_norms(idx->X, idx->ld, idx->d, rows, idx->Hn, idx->device, idx->mut, L, idx->hn_rows));
+            MVDB_TRY(launch_half_shadow(idx->X.p, idx->ld, idx->d, rows, sh16.scale, sh16.Xh.p, idx->device, idx->mut, L, sh16.rows));
+        if (offsets) MVDB_TRY(launch_half_norms(idx->X.p, idx->ld, idx->d, rows, sh16.Hn.p, idx->device, idx->mut, L, sh16.hn_rows));
         if (code) {
-            const int g8 = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, cus * 16));
-            hipLaunchKernelGGL(code8_build_kernel, dim3(g8), dim3(256), 0, idx->mut, (const float*)idx->X, idx->ld, idx->d, rows, idx->C8,
-                               c8_low(idx), idx->c8_ar, (const int64_t*)L, idx->c8_rows);
-            MVDB_HIP(hipGetLastError());
+            MVDB_TRY(idx->code.build(idx, 0, rows, idx->mut, L));
             // a listed row may be one of the floor's sample: the whole copy is gathered again (a fixed 131,072 rows)
-            if (code8_sample_valid(idx)) MVDB_TRY(code8_sample_gather(idx, idx->n, idx->mut));
+            if (idx->code.sample_valid(idx->n)) MVDB_TRY(idx->code.gather_sample(idx, idx->n, idx->mut));
         }
         // (waits for the chunk: the staging buffers are free again, and so is the caller's part of x)
-        MVDB_TRY(note_row_norms(idx, idx->X, rows, normalize, L));
+        MVDB_TRY(note_row_norms(idx, idx->X.p, rows, normalize, L));
         MVDB_HIP(hipStreamSynchronize(idx->mut));
     }
-    if (idx->Xh && idx->xh_rows > 0 && half_xscale(idx->row_norm_bound) != idx->xh_scale) invalidate_shadow(idx);  // (extend_shadow's rule)
+    if (shadow && half_xscale(idx->row_norm_bound) != sh16.scale) sh16.invalidate();  // (ShadowStore::extend's rule)
     return 0;
 }
 
@@ -2732,7 +2679,7 @@ int mvdb_index_get_rows(const mvdb_index* idx, int64_t row0, int64_t n, float* o
         return fail(MVDB_ERR_ARG, "rows [%lld,%lld) out of range [0,%lld)", (long long)row0,
                     (long long)(row0 + n), (long long)idx->n);
     DeviceGuard dg(idx->device);
-    const float* src = idx->X + row0 * idx->ld;
+    const float* src = idx->X.p + row0 * idx->ld;
     if (idx->ld == idx->d)
         MVDB_HIP(hipMemcpy(out_host, src, (size_t)n * idx->d * sizeof(float), hipMemcpyDeviceToHost));
     else
@@ -2741,128 +2688,124 @@ int mvdb_index_get_rows(const mvdb_index* idx, int64_t row0, int64_t n, float* o
     return 0;
 }
 
+// ---- remove_rows: the tail behind the first deleted row is compacted in place, by one of two routes ----------------------------
+// the staging buffer of both routes, kept between calls
+static int reserve_ctmp(mvdb_index* idx, size_t bytes) {
+    if (idx->ctmp_bytes >= bytes) return 0;
+    idx->ctmp_bytes = 0;
+    if (idx->ctmp.alloc(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MVDB_ERR_OOM, "device allocation for row compaction failed (%zu bytes)", bytes);
+    }
+    idx->ctmp_bytes = bytes;
+    return 0;
+}
+
+// The sorted delete list, made relative to the tail's first row, goes to the device on idx->mut (stream-ordered allocation:
+// hipFree would synchronise the device).  *e: the copy's status, which finish_compaction reports with the launches'.
+static int upload_deletes(mvdb_index* idx, std::vector<int64_t>& del, int64_t** del_dev, hipError_t* e) {
+    MVDB_HIP(hipMallocAsync((void**)del_dev, del.size() * sizeof(int64_t), idx->mut));
+    const int64_t first = del[0];
+    for (auto& v : del) v -= first;
+    *e = hipMemcpyAsync(*del_dev, del.data(), del.size() * sizeof(int64_t), hipMemcpyHostToDevice, idx->mut);
+    return 0;
+}
+
+static int finish_compaction(mvdb_index* idx, int64_t* del_dev, hipError_t e) {
+    if (del_dev) (void)hipFreeAsync(del_dev, idx->mut);
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(idx->mut);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(MVDB_ERR_HIP, "row compaction failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// A handful of rows (the reference deletes ONE per call, vector_database.py:119) or one run: the tail is shifted in place in one
+// pass — every byte read once and written once — with a side copy of m rows per workgroup boundary (util_kernels.hpp:
+// shift_rows_kernel); delete of an early row of 10M x 512: 14.5 -> 8.2 ms (profiles/r06_delete_probe.jsonl).  *done stays
+// false where the side copies would outgrow their bound: the staged route serves.
+static int compact_shift(mvdb_index* idx, std::vector<int64_t>& del, int64_t tail_new, bool* done) {
+    const int64_t m = (int64_t)del.size(), first = del[0];
+    const bool run = del[m - 1] - del[0] == m - 1;
+    const int64_t rowunits = idx->ld / 4;  // 16-byte units per row (ld is a multiple of 4 floats)
+    const int64_t new_units = tail_new * rowunits, old_units = (idx->n - first) * rowunits;
+    const int64_t slice = 256 * kShiftUnits;
+    const int64_t side_units = m * rowunits;
+    const int64_t cus = device_cus(idx->device);
+    // eight workgroups per CU; fewer (down to two) where the side copies of that many boundaries would outgrow their bound
+    int64_t groups = std::min<int64_t>(cus * 8, (new_units + slice - 1) / slice);
+    const int64_t fit = (int64_t)(kShiftSideBytes / ((size_t)side_units * 16)) + 1;
+    const bool fits = fit >= std::min<int64_t>(groups, cus * 2);
+    groups = std::min(groups, fit);
+    const int64_t range = ((new_units + groups - 1) / groups + slice - 1) / slice * slice;
+    groups = (new_units + range - 1) / range;
+    const size_t side_bytes = (size_t)std::max<int64_t>(groups - 1, 1) * side_units * 16;
+    if (!fits || side_bytes > kShiftSideBytes) return 0;
+    MVDB_TRY(reserve_ctmp(idx, side_bytes));
+    int64_t* del_dev = nullptr;
+    hipError_t e = hipSuccess;
+    if (!run) MVDB_TRY(upload_deletes(idx, del, &del_dev, &e));
+    f32x4u* tail = reinterpret_cast<f32x4u*>(idx->X.p + first * idx->ld);
+    f32x4u* side = reinterpret_cast<f32x4u*>(idx->ctmp.p);
+    if (groups > 1) {
+        const unsigned gx = (unsigned)std::min<int64_t>((side_units + 255) / 256, 64);
+        hipLaunchKernelGGL(shift_save_kernel, dim3(gx, (unsigned)(groups - 1)), dim3(256), 0, idx->mut, side, tail, range, side_units,
+                           old_units);
+    }
+    if (run)
+        hipLaunchKernelGGL(shift_rows_kernel<true>, dim3((unsigned)groups), dim3(256), 0, idx->mut, tail, side, del_dev, m, new_units,
+                           range, rowunits, side_units);
+    else
+        hipLaunchKernelGGL(shift_rows_kernel<false>, dim3((unsigned)groups), dim3(256), 0, idx->mut, tail, side, del_dev, m, new_units,
+                           range, rowunits, side_units);
+    *done = true;
+    return finish_compaction(idx, del_dev, e);
+}
+
+// Every kept row moves UP, so the tail is compacted in place, in ascending chunks through a bounded staging buffer (512 MiB,
+// MVDB_COMPACT_BYTES; kept by the index): chunk c gathers the sources of the new rows [r0, r0 + rows) — all at or above
+// r0 + 1 — into the buffer, then copies the buffer over [r0, r0 + rows); stream order makes the next chunk's sources (all
+// >= r0 + rows) untouched by that copy.  (Until round 4 the whole tail went through a temporary of its own size: one early
+// delete in a 164 GB index needed another 164 GB.)  The source row of a new row is found by binary search in the sorted list
+// of deleted rows.
+static int compact_staged(mvdb_index* idx, std::vector<int64_t>& del, int64_t tail_new) {
+    const int64_t m = (int64_t)del.size(), first = del[0];
+    const size_t row_bytes = (size_t)idx->ld * sizeof(float);
+    MVDB_TRY(reserve_ctmp(idx, std::min<size_t>((size_t)tail_new * row_bytes, std::max<size_t>((size_t)idx->kn.compact_bytes, row_bytes))));
+    const int64_t chunk_rows = (int64_t)(idx->ctmp_bytes / row_bytes);
+    int64_t* del_dev = nullptr;
+    hipError_t e = hipSuccess;
+    MVDB_TRY(upload_deletes(idx, del, &del_dev, &e));
+    float* tail = idx->X.p + first * idx->ld;
+    for (int64_t r0 = 0; r0 < tail_new && e == hipSuccess; r0 += chunk_rows) {
+        const int64_t rows = std::min(chunk_rows, tail_new - r0);
+        hipLaunchKernelGGL(gather_kept_rows_kernel, dim3(row_grid(idx->device, rows)), dim3(256), 0, idx->mut, idx->ctmp.p, tail, del_dev, m, r0,
+                           rows, idx->ld);
+        e = hipMemcpyAsync(tail + r0 * idx->ld, idx->ctmp.p, (size_t)rows * row_bytes, hipMemcpyDeviceToDevice, idx->mut);
+    }
+    return finish_compaction(idx, del_dev, e);
+}
+
 int mvdb_index_remove_rows(mvdb_index* idx, const int64_t* rows_host, int64_t m) {
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (m < 0) return fail(MVDB_ERR_ARG, "negative row count");
     if (m == 0) return 0;
     if (!rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
     std::unique_lock<std::shared_mutex> lk(idx->mu);
-    std::vector<int64_t> del(rows_host, rows_host + m);
-    std::sort(del.begin(), del.end());
-    for (int64_t i = 0; i < m; ++i) {
-        if (del[i] < 0 || del[i] >= idx->n)
-            return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)del[i],
-                        (long long)idx->n);
-        if (i && del[i] == del[i - 1])
-            return fail(MVDB_ERR_ARG, "row %lld listed twice", (long long)del[i]);
-    }
+    std::vector<int64_t> del;
+    MVDB_TRY(check_row_list(rows_host, m, idx->n, &del));
     DeviceGuard dg(idx->device);
     MVDB_TRY(quiesce(idx));
     ++idx->renumbered;
-    invalidate_shadow(idx);  // rows are renumbered: the next batch search rebuilds the shadow in the allocation it already has
-    invalidate_code8(idx);
+    idx->shadow.invalidate();  // rows are renumbered: the next batch search rebuilds the shadow in the allocation it already has
+    idx->code.invalidate();
     const int64_t n_new = idx->n - m;
-    if (n_new == 0) {
-        idx->n = 0;
-        return 0;
-    }
-    // rows before the first deleted one do not move: compact only the tail [first, n).  Every kept row moves UP, so the
-    // tail is compacted in place, in ascending chunks through a bounded staging buffer (512 MiB, MVDB_COMPACT_BYTES; kept by the index):
-    // chunk c gathers the sources of the new rows [r0, r0 + rows) — all at or above r0 + 1 — into the buffer, then copies
-    // the buffer over [r0, r0 + rows); stream order makes the next chunk's sources (all >= r0 + rows) untouched by that
-    // copy.  (Until round 4 the whole tail went through a temporary of its own size: one early delete in a 164 GB index
-    // needed another 164 GB.)  The source row of a new row is found by binary search in the sorted list of deleted rows.
-    const int64_t first = del[0];
-    const int64_t tail_new = n_new - first;
-    // A handful of rows (the reference deletes ONE per call, vector_database.py:119): the tail is shifted in place in one pass —
-    // every byte read once and written once — with a side copy of m rows per workgroup boundary (util_kernels.hpp:
-    // shift_rows_kernel); delete of an early row of 10M x 512: 14.5 -> 8.2 ms (profiles/r06_delete_probe.jsonl).  MVDB_COMPACT_INPLACE=0: always the staging path.
-    if (tail_new > 0 && idx->kn.compact_inplace && (m <= kShiftMaxRows || del[m - 1] - del[0] == m - 1)) {
-        const bool run = del[m - 1] - del[0] == m - 1;
-        const int64_t rowunits = idx->ld / 4;  // 16-byte units per row (ld is a multiple of 4 floats)
-        const int64_t new_units = tail_new * rowunits, old_units = (idx->n - first) * rowunits;
-        const int64_t slice = 256 * kShiftUnits;
-        const int64_t side_units = m * rowunits;
-        const int64_t cus = device_cus(idx->device);
-        // eight workgroups per CU; fewer (down to two) where the side copies of that many boundaries would outgrow their bound
-        int64_t groups = std::min<int64_t>(cus * 8, (new_units + slice - 1) / slice);
-        const int64_t fit = (int64_t)(kShiftSideBytes / ((size_t)side_units * 16)) + 1;
-        const bool fits = fit >= std::min<int64_t>(groups, cus * 2);
-        groups = std::min(groups, fit);
-        const int64_t range = ((new_units + groups - 1) / groups + slice - 1) / slice * slice;
-        groups = (new_units + range - 1) / range;
-        const size_t side_bytes = (size_t)std::max<int64_t>(groups - 1, 1) * side_units * 16;
-        if (fits && side_bytes <= kShiftSideBytes) {
-            if (idx->ctmp_bytes < side_bytes) {
-                if (idx->ctmp) (void)hipFree(idx->ctmp);
-                idx->ctmp = nullptr;
-                idx->ctmp_bytes = 0;
-                if (hipMalloc((void**)&idx->ctmp, side_bytes) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(MVDB_ERR_OOM, "device allocation for row compaction failed (%zu bytes)", side_bytes);
-                }
-                idx->ctmp_bytes = side_bytes;
-            }
-            int64_t* del_dev = nullptr;
-            hipError_t e = hipSuccess;
-            if (!run) {
-                MVDB_HIP(hipMallocAsync((void**)&del_dev, (size_t)m * sizeof(int64_t), idx->mut));
-                for (auto& v : del) v -= first;  // positions relative to the tail
-                e = hipMemcpyAsync(del_dev, del.data(), (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, idx->mut);
-            }
-            f32x4u* tail = reinterpret_cast<f32x4u*>(idx->X + first * idx->ld);
-            f32x4u* side = reinterpret_cast<f32x4u*>(idx->ctmp);
-            if (groups > 1) {
-                const unsigned gx = (unsigned)std::min<int64_t>((side_units + 255) / 256, 64);
-                hipLaunchKernelGGL(shift_save_kernel, dim3(gx, (unsigned)(groups - 1)), dim3(256), 0, idx->mut, side, tail, range, side_units,
-                                   old_units);
-            }
-            if (run)
-                hipLaunchKernelGGL(shift_rows_kernel<true>, dim3((unsigned)groups), dim3(256), 0, idx->mut, tail, side, del_dev, m, new_units,
-                                   range, rowunits, side_units);
-            else
-                hipLaunchKernelGGL(shift_rows_kernel<false>, dim3((unsigned)groups), dim3(256), 0, idx->mut, tail, side, del_dev, m, new_units,
-                                   range, rowunits, side_units);
-            if (del_dev) (void)hipFreeAsync(del_dev, idx->mut);
-            if (e == hipSuccess) e = hipGetLastError();
-            const hipError_t es = hipStreamSynchronize(idx->mut);
-            if (e == hipSuccess) e = es;
-            if (e != hipSuccess) return fail(MVDB_ERR_HIP, "row compaction failed: %s", hipGetErrorString(e));
-            idx->n = n_new;
-            return 0;
-        }
-    }
-    if (tail_new > 0) {
-        const size_t row_bytes = (size_t)idx->ld * sizeof(float);
-        const size_t want = std::min<size_t>((size_t)tail_new * row_bytes, std::max<size_t>((size_t)idx->kn.compact_bytes, row_bytes));
-        if (idx->ctmp_bytes < want) {
-            if (idx->ctmp) (void)hipFree(idx->ctmp);
-            idx->ctmp = nullptr;
-            idx->ctmp_bytes = 0;
-            if (hipMalloc((void**)&idx->ctmp, want) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MVDB_ERR_OOM, "device allocation for row compaction failed (%zu bytes)", want);
-            }
-            idx->ctmp_bytes = want;
-        }
-        const int64_t chunk_rows = (int64_t)(idx->ctmp_bytes / row_bytes);
-        int64_t* del_dev = nullptr;
-        MVDB_HIP(hipMallocAsync((void**)&del_dev, (size_t)m * sizeof(int64_t), idx->mut));  // stream-ordered: hipFree would synchronise the device
-        for (auto& v : del) v -= first;  // positions relative to the tail
-        hipError_t e = hipMemcpyAsync(del_dev, del.data(), (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, idx->mut);
-        float* tail = idx->X + first * idx->ld;
-        for (int64_t r0 = 0; r0 < tail_new && e == hipSuccess; r0 += chunk_rows) {
-            const int64_t rows = std::min(chunk_rows, tail_new - r0);
-            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, (int64_t)device_cus(idx->device) * 16));
-            hipLaunchKernelGGL(gather_kept_rows_kernel, dim3(grid), dim3(256), 0, idx->mut, idx->ctmp, tail, del_dev, m, r0, rows,
-                               idx->ld);
-            e = hipMemcpyAsync(tail + r0 * idx->ld, idx->ctmp, (size_t)rows * row_bytes, hipMemcpyDeviceToDevice, idx->mut);
-        }
-        (void)hipFreeAsync(del_dev, idx->mut);
-        if (e == hipSuccess) e = hipGetLastError();
-        const hipError_t es = hipStreamSynchronize(idx->mut);
-        if (e == hipSuccess) e = es;
-        if (e != hipSuccess) return fail(MVDB_ERR_HIP, "row compaction failed: %s", hipGetErrorString(e));
+    // rows before the first deleted one do not move: compact only the tail [first, n)
+    const int64_t tail_new = n_new - del[0];
+    if (n_new > 0 && tail_new > 0) {
+        bool done = false;  // MVDB_COMPACT_INPLACE=0: always the staged route
+        if (idx->kn.compact_inplace && (m <= kShiftMaxRows || del[m - 1] - del[0] == m - 1)) MVDB_TRY(compact_shift(idx, del, tail_new, &done));
+        if (!done) MVDB_TRY(compact_staged(idx, del, tail_new));
     }
     idx->n = n_new;
     return 0;
@@ -3152,7 +3095,7 @@ static int rowset_search_core(const mvdb_index* idx, Workspace* ws, const float*
         const int64_t n = rs->n_at_create;
         const bool half = half_path_ok(idx) && nq >= half_min_nq(idx, n);
         const int per = half ? std::max(1, half_max_queries(idx->d)) : std::max(1, mfma_gated_queries(idx));
-        const bool have_shadow = __atomic_load_n(&idx->Xh, __ATOMIC_RELAXED) != nullptr;  // a heuristic read: ensure_shadow writes it under shadow_mu
+        const bool have_shadow = __atomic_load_n(&idx->shadow.Xh.p, __ATOMIC_RELAXED) != nullptr;  // a heuristic read: ShadowStore::ensure writes it under shadow_mu
         const double shared = (double)((nq + per - 1) / per) * (half && have_shadow ? 0.6 : 1.0);
         const double gathered = (double)nq * (double)rs->count / (double)n * 1.1;
         if (shared < gathered)
@@ -3322,18 +3265,7 @@ int range_shared_min_nq(int64_t n) {
 // the counters of the route: allocated with the first call that takes it, never inside a capture
 bool ensure_range_stats(const mvdb_index* idx, hipStream_t s) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    if (idx->rg_ctr_dev) return true;
-    if (stream_capturing(s)) return false;
-    unsigned int* p = nullptr;
-    if (hipMalloc((void**)&p, sizeof(unsigned int)) != hipSuccess || hipMemset(p, 0, sizeof(unsigned int)) != hipSuccess ||
-        idx->rg_stats.reserve(64) != 0) {
-        (void)hipGetLastError();
-        if (p) (void)hipFree(p);
-        return false;
-    }
-    memset(idx->rg_stats.p, 0, 64);
-    idx->rg_ctr_dev = p;
-    return true;
+    return idx->rg_ctr.dev() || (!stream_capturing(s) && idx->rg_ctr.ensure(1));
 }
 
 // Does this launch group go through the shared pass?  Inner product, a batch, every row or a bitmap-form set, an index that
@@ -3349,7 +3281,7 @@ const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq,
         while ((1 << lg) < sh.G) ++lg;
         if (4 * sh.C + lg > (idx->d + 127) / 128 * 4 + 6) return nullptr;
     }
-    const _Float16* Xh = ensure_shadow(idx, ws->stream, half_xscale(idx->row_norm_bound));
+    const _Float16* Xh = idx->shadow.ensure(idx, ws->stream, half_xscale(idx->row_norm_bound));
     if (!Xh || !ensure_range_stats(idx, ws->stream)) return nullptr;
     return Xh;
 }
@@ -3429,8 +3361,8 @@ int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh,
     r.cap = a.cap;
     r.counts = a.counts;
     MVDB_TRY(launch_rescore(r, nq, idx->device, s));
-    hipLaunchKernelGGL(range_stats_kernel, dim3(1), dim3(256), 0, s, ws->rccount.p, (unsigned long long)ccap, nq, idx->rg_ctr_dev,
-                       (volatile unsigned long long*)idx->rg_stats.p);
+    hipLaunchKernelGGL(range_stats_kernel, dim3(1), dim3(256), 0, s, ws->rccount.p, (unsigned long long)ccap, nq, idx->rg_ctr.dev(),
+                       idx->rg_ctr.mirror<unsigned long long>());
     MVDB_HIP(hipGetLastError());
     a.gate_count = ws->rccount.p;
     a.gate_cap = (unsigned long long)ccap;
@@ -3458,7 +3390,7 @@ int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int n
     hipStream_t s = ws->stream;
     MVDB_TRY(ws->rkeys.reserve((size_t)nq * (size_t)seg));
     RangeScanArgs a;
-    a.X = idx->X;
+    a.X = idx->X.p;
     a.ld = idx->ld;
     a.d4 = idx->d4;
     a.q = q;
@@ -3733,8 +3665,7 @@ int stage_grouped_table(Workspace* ws, const std::vector<GroupedQuery>& queries,
     const size_t ibytes = items.size() * sizeof(GroupedItem);
     const size_t bytes = qbytes + ibytes;
     MVDB_TRY(ws->gtab.reserve(bytes));
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    const bool capturing = ws->stream && hipStreamIsCapturing(ws->stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
+    const bool capturing = stream_capturing(ws->stream);
     void* pin = nullptr;
     Workspace::GroupedStage* slot = nullptr;
     if (capturing) {
@@ -3808,7 +3739,7 @@ int grouped_search_core(const mvdb_index* idx, Workspace* ws, const float* q, in
         MVDB_TRY(ws->cand.reserve((size_t)std::max(nitems, 1) * k));
         if (nitems > 0) {
             GroupedScanArgs a;
-            a.X = idx->X;
+            a.X = idx->X.p;
             a.ld = idx->ld;
             a.d4 = idx->d4;
             a.q = q;

@@ -237,7 +237,7 @@ __global__ __launch_bounds__(64) void split_plan_kernel(const int* __restrict__ 
         *nb_out = run;
         if (bad) atomicAdd(rerun_ctr, (unsigned long long)bad);
         // the opt-in single-query route: a running count of refused certificates, mirrored into a host-mapped word that the
-        // routing reads WITHOUT synchronising (mvdb.hip: single_route_suspended)
+        // routing reads WITHOUT synchronising (index_state.hpp: RouteWindow)
         if (fail_dev && run) *fail_host = atomicAdd(fail_dev, (unsigned int)run) + (unsigned int)run;
         // every certified call: the same for the adaptive tile flags (mvdb.hip: tile_flags_wanted)
         if (any_dev && run) *any_host = atomicAdd(any_dev, (unsigned int)run) + (unsigned int)run;
