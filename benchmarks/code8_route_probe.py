@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--blocks", default="0", help="comma list of MVDB_SCAN_BLOCKS_PER_CU values (0 = the library's choice)")
     ap.add_argument("--family", default="zero_mean", choices=["zero_mean", "positive", "clustered"], help="the synthetic corpus and its queries")
     ap.add_argument("--timers", type=int, default=1, help="0: no per-launch event timers (for runs under a tracer)")
+    ap.add_argument("--front", type=int, default=1, help="index option code8_front_plane: 1 the library decides, 2 always the front form, "
+                    "3 the plane kept and never streamed, 0 no plane")
     args = ap.parse_args()
 
     import numpy as np
@@ -68,11 +70,15 @@ def main():
         return out
 
     planes = hasattr(idx, "code8_refined")
+    fronted = hasattr(idx, "code8_front_counters")
+    if fronted:
+        idx.set_option("code8_front_plane", args.front)
 
     def measure(steps, bytes_per_launch, label):
         run(0, W)
         native.prof_read("ip_scan")
         refined = idx.code8_refined() if planes else 0
+        front0 = idx.code8_front_counters() if fronted else None
         native.prof_enable(bool(args.timers))
         t0 = time.perf_counter()
         run(W, steps)
@@ -81,6 +87,16 @@ def main():
         if label["route"] == "code8" and planes:
             label = dict(label, refined_per_query=round((idx.code8_refined() - refined) / steps, 1))
             bytes_per_launch = n * (d // 4 * 3 + 8) + int(label["refined_per_query"] * (d // 4))
+            if fronted:
+                # the front form streams 5 d / 8 + 8 bytes per row and gathers 3 d / 4 + 8 for every row its stage 0 keeps; the
+                # launches of this measurement that ran it (the library's window may have suspended it for some)
+                front1 = idx.code8_front_counters()
+                fcalls = front1[1] - front0[1]
+                per_front = (front1[0] - front0[0]) / max(fcalls, 1)
+                label = dict(label, front_option=args.front, front_launches=fcalls, front_suspensions=front1[2],
+                             front_survivors_per_launch=round(per_front, 1))
+                front_bytes = n * (d // 8 * 5 + 8) + int(per_front * (d // 4 * 3 + 8)) + int(label["refined_per_query"] * (d // 4))
+                bytes_per_launch = (fcalls * front_bytes + (steps - fcalls) * bytes_per_launch) // steps
         launches, ms = native.prof_read("ip_scan")
         avg = ms / max(launches, 1)
         rec = dict(label, rows=n, dim=d, k=k, steps=steps, kernel=native.prof_symbol("ip_scan"), launches=launches,

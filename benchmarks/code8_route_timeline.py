@@ -10,8 +10,11 @@ mean duration of the exact scan's launches (steps with `code8_single_query = 0`)
 With the corpus' shape the prefilter launch (`code8_scan_kernel`) is also rated on its own streamed bytes: N (3 d / 4 + 8) — the
 high plane of the code and (a, r) — for a build with the two planes (`planes` = 1, the default), N (d + 8) for a build from
 before them (`planes` = 0).  The low plane of the refined rows (d / 4 bytes each, a few thousand rows) is not in the figure.
+`planes` = 2: the front form (the traced kernel then names five template arguments) — N (5 d / 8 + 8) for the front plane and
+(a, r), plus 3 d / 4 + 8 for each of the `survivors` rows per launch its stage 0 kept (code8_route_probe.py reports them).
+`prefilter_form` says which form the trace holds, by the kernel's name.
 
-usage: code8_route_timeline.py <trace dir or csv> [git-head [rows dim [planes]]]"""
+usage: code8_route_timeline.py <trace dir or csv> [git-head [rows dim [planes [survivors]]]]"""
 import collections
 import csv
 import glob
@@ -60,8 +63,11 @@ def main():
         n, d = int(sys.argv[3]), int(sys.argv[4])
         planes = int(sys.argv[5]) if len(sys.argv) > 5 else 1
         nbytes = n * (d // 4 * 3 + 8) if planes else n * (d + 8)
+        if planes == 2:
+            nbytes = n * (d // 8 * 5 + 8) + int(float(sys.argv[6]) if len(sys.argv) > 6 else 0) * (d // 4 * 3 + 8)
         pre = [l for l in launches if "code8_scan_kernel" in l["kernel"]]
         if pre:
+            out.update(prefilter_form="front" if pre[0]["kernel"].count(",") == 4 else "6-bit plane streamed")
             out.update(prefilter_streamed_bytes=nbytes, prefilter_mean_us=pre[0]["mean_us"],
                        prefilter_tb_per_s=round(nbytes / (pre[0]["mean_us"] * 1e-6) / 1e12, 4))
     print(json.dumps(out, indent=1))

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """How many GPU kernels does libmvdb.so hold, per translation unit, and does any of them spill?  Parses the clang offload
 bundles inside the library (one per .hip file), extracts the gfx950 code objects and reads their symbol tables and
-.AMDGPU metadata notes with llvm-readelf.  usage: kernel_census.py [path/to/libmvdb.so]  -> one JSON line."""
+.AMDGPU metadata notes with llvm-readelf.  usage: kernel_census.py [path/to/libmvdb.so]  -> one JSON line.
+MVDB_CENSUS_KERNEL=substring also lists, under "registers", the VGPRs, scratch bytes and VGPR spills of every kernel whose
+mangled name holds the substring (e.g. code8_scan_kernel)."""
 import json
 import os
 import re
@@ -43,6 +45,14 @@ with tempfile.TemporaryDirectory() as tmp:
             for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", notes, re.S):
                 if int(m.group(2)) or int(m.group(3)):
                     spills.append({"kernel": m.group(1)[:80], "scratch_bytes": int(m.group(2)), "vgpr_spills": int(m.group(3))})
+            want = os.environ.get("MVDB_CENSUS_KERNEL", "")
+            if want:
+                for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)",
+                                     notes, re.S):
+                    if want in m.group(1):
+                        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+                        out.setdefault("registers", []).append({"kernel": name.replace("void mvdb::", ""), "vgprs": int(m.group(3)),
+                                                                "scratch_bytes": int(m.group(2)), "vgpr_spills": int(m.group(4))})
             fam = {}
             for k in kds:
                 d = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()

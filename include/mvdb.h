@@ -78,6 +78,12 @@ int mvdb_index_reload_env(mvdb_index* idx);
  *       "shadow_single_query" = 1 takes precedence.
  *   "code8_capacity" (1 .. 65536, default 32768): most candidate rows a call of that route may keep; a call that keeps more (or fewer
  *       than k) is answered by the full exact scan, enabled on the device.  Diagnostic: a small value forces that fallback.
+ *   "code8_front_plane" (0 .. 3, default 1): 1 = the int8 code keeps a third plane, the top 5 bits of every code (+5 d / 8
+ *       bytes per row: 3.2 GB at 10M x 512), and the prefilter streams that plane, fetching the 6-bit plane only for the rows
+ *       it cannot reject; an index whose queries leave too many such rows goes back to streaming the 6-bit plane by itself
+ *       (mvdb_index_code8_front_counters).  0 frees the plane.  Diagnostic: 2 = 1, never going back; 3 = 1, the plane kept
+ *       and never streamed.  D, I and the candidate
+ *       rows of a call do not depend on this option.  An allocation that fails leaves the index without the plane, no more.
  *   "half_shadow" (0 | 1, default 1): 0 = batches nominate from the fp32 rows (no second copy of the corpus).
  *   "compact_bytes" (> 0, default 512 MiB): staging buffer of mvdb_index_remove_rows. */
 int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value);
@@ -137,6 +143,26 @@ int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, flo
  * the device code packs and unpacks 16-code chunks with.  Pure host arithmetic (no device needed). */
 int mvdb_code8_pack(int d, const int8_t* codes, uint8_t* high, uint8_t* low);
 int mvdb_code8_unpack(int d, const uint8_t* high, const uint8_t* low, int8_t* codes);
+
+/* The FRONT plane of the code: the top 5 bits of every code, c & ~7, at 5 d / 8 bytes per row — what
+ * the prefilter streams first where the index holds it (option "code8_front_plane").  The d int8 codes of one row (d a
+ * multiple of 32, at most 2048; other widths are refused) <-> the row's image in the plane: the 16-byte parts of its d / 32
+ * chunks, then their 4-byte parts.  unpack returns c & ~7.  The very functions the device code uses.  Pure host arithmetic. */
+int mvdb_code8_front_pack(int d, const int8_t* codes, uint8_t* image);
+int mvdb_code8_front_unpack(int d, const uint8_t* image, int8_t* codes);
+
+/* Diagnostic: mvdb_code8_scan_geometry for the form of the prefilter's launch that streams the front plane. */
+int mvdb_code8_front_geometry(int d, int64_t n, int device, int* rows_per_batch, int* waves);
+
+/* Diagnostics of the front form: the rows its first look (the front plane) could not reject, summed over its calls; those
+ * calls; how often its window has suspended it (the mean share of such rows over 32 calls was above the share at which
+ * the other form is faster: the next 512 calls stream the 6-bit plane); whether the code holds the plane.  Any pointer may
+ * be NULL.  Reads device words: synchronises with the device. */
+int mvdb_index_code8_front_counters(const mvdb_index* idx, long long* survivors, long long* calls, long long* suspensions, int* held);
+
+/* Diagnostic: one stored row of the code as the device holds it — its 3 d / 4 bytes of the high plane, d / 4 of the low
+ * plane and its 5 d / 8-byte image in the front plane (mvdb_code8_front_unpack).  Any pointer may be NULL. */
+int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high, uint8_t* low, uint8_t* front);
 
 /* Diagnostic: how the prefilter's launch shares n rows of width d (384 / 512 / 1024) out on `device`: wave w of `waves`
  * takes the batches w, w + waves, ... of rows_per_batch consecutive rows.  Tests plant rows by it. */

@@ -70,6 +70,11 @@ PROTOTYPES = {
     "mvdb_code8_pack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_code8_unpack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_index_code8_refined": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_code8_front_pack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp]),
+    "mvdb_code8_front_unpack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp]),
+    "mvdb_code8_front_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_index_code8_front_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_code8_read_row": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_code8_scan_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_dim": (ctypes.c_int, [c_vp]),
     "mvdb_index_device": (ctypes.c_int, [c_vp]),
@@ -288,6 +293,22 @@ class FlatIndex:
         v = [ctypes.c_longlong(0) for _ in range(3)]
         check(lib().mvdb_index_code8_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def code8_front_counters(self):
+        """(rows the front plane could not reject over all calls of the front form, those calls, suspensions of the front
+        form, whether the code holds the front plane) — diagnostic; synchronises with the device."""
+        v = [ctypes.c_longlong(0) for _ in range(3)]
+        held = ctypes.c_int(0)
+        check(lib().mvdb_index_code8_front_counters(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(held)))
+        return tuple(int(x.value) for x in v) + (bool(held.value),)
+
+    def code8_read_row(self, row, front=True):
+        """(high plane, low plane, front-plane image or None) of one stored row of the int8 code, as uint8 arrays (diagnostic)."""
+        d = self.d
+        high, low = np.empty(d // 4 * 3, np.uint8), np.empty(d // 4, np.uint8)
+        image = np.empty(d // 8 * 5, np.uint8) if front else None
+        check(lib().mvdb_index_code8_read_row(self._h, int(row), high.ctypes.data, low.ctypes.data, image.ctypes.data if front else None))
+        return high, low, image
 
     def code8_refined(self):
         """Rows whose low plane the prefilter has fetched, over all calls so far (diagnostic; synchronises with the device)."""
@@ -879,6 +900,31 @@ def code8_unpack(high, low):
     codes = np.empty(d, np.int8)
     check(lib().mvdb_code8_unpack(int(d), high.ctypes.data, low.ctypes.data, codes.ctypes.data))
     return codes
+
+
+def code8_front_pack(codes):
+    """The image of one row of int8 codes in the front plane, 5 d / 8 bytes (include/mvdb.h: mvdb_code8_front_pack)."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    d = codes.shape[0]
+    image = np.empty(max(d // 8 * 5, 1), np.uint8)
+    check(lib().mvdb_code8_front_pack(int(d), codes.ctypes.data, image.ctypes.data))
+    return image
+
+
+def code8_front_unpack(image):
+    """c & ~7 of the codes of one row, from its image in the front plane (include/mvdb.h: mvdb_code8_front_unpack)."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    d = image.shape[0] // 5 * 8
+    codes = np.empty(max(d, 1), np.int8)
+    check(lib().mvdb_code8_front_unpack(int(d), image.ctypes.data, codes.ctypes.data))
+    return codes
+
+
+def code8_front_geometry(d, n, device=0):
+    """code8_scan_geometry for the form of the prefilter's launch that streams the front plane."""
+    rb, waves = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().mvdb_code8_front_geometry(int(d), int(n), int(device), ctypes.byref(rb), ctypes.byref(waves)))
+    return int(rb.value), int(waves.value)
 
 
 def code8_scan_geometry(d, n, device=0):

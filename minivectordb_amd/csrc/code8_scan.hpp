@@ -16,6 +16,10 @@
 // Roofline: HBM.  Algorithmic bytes per launch = n * (3 d / 4 + 8) + (rows refined) * d / 4: the high plane once, 8 bytes of
 // (a, r) per row, the low plane of the rows the first stage cannot reject.
 //
+// Where the index also keeps the FRONT plane — the top 5 bits of every code, 5 d / 8 bytes per row — the kernel's front form
+// streams that one instead and gathers the high plane for the rows 5 bits cannot reject: n * (5 d / 8 + 8) + (stage-0
+// survivors) * (3 d / 4 + 8) + (rows refined) * d / 4.  The same rows are kept.
+//
 // Shape of the work (flat_scan_kernel's): G lanes share a row, one 16-code chunk (12 bytes) each (d = 512: G = 32, two rows
 // per wave-instruction), U row groups in flight per wave, non-temporal loads, a persistent grid, no branch between the loads
 // of a batch.  Per chunk: nine and / shift / or, eight v_dot4_i32_i8; per batch one halving reduction of the U sums and one
@@ -120,15 +124,92 @@ inline void code8_unpack_row(int d, const uint8_t* high, const uint8_t* low, int
     }
 }
 
+// ---- the front plane: the top 5 bits of every code, a third store beside the two planes --------------------------------------------
+// H5 = c & ~7 of every code at 5 d / 8 bytes per row: what the prefilter streams first (stage 0 of code8_scan_kernel's front
+// form); the two planes above stay what they are and serve the rows this plane cannot reject.  Nothing else reads it.
+// A 32-code chunk t — the dwords c[0 .. 8) of the codes 32 t .. 32 t + 31 — becomes five dwords f[0 .. 5): f[i] = c[i] with
+// the low 3 bits of every byte replaced by top bits of the matching byte of c[5], c[6], c[7]:
+//   f[0] bits 2:0 = c[5] bits 7:5,   f[1] bits 1:0 = c[5] bits 4:3,   f[1] bit 2 = c[7] bit 4,
+//   f[2] bits 2:0 = c[6] bits 7:5,   f[3] bits 1:0 = c[6] bits 4:3,   f[3] bit 2 = c[7] bit 3,
+//   f[4] bits 2:0 = c[7] bits 7:5.
+// `f[i] & 0xF8F8F8F8` is (c & ~7) of c[0 .. 5) as int8 dwords; ten and / shift / or give the other three.
+// Layout: f[0 .. 4) is the chunk's WIDE part (16 bytes), f[4] its NARROW part.  The plane is stored in tiles of R rows, R the
+// rows one wave-instruction of the scan covers (code8_front_tile_rows): the wide parts of the tile's rows — row g at
+// g * 16 * (d / 32), chunk t at 16 t — and behind them the narrow parts, row g at g * 4 * (d / 32), chunk t at 4 t.  A
+// 16-byte load per lane then reads one contiguous span of the tile per wave-instruction, and so does the 4-byte load.  The
+// plane is sized in whole tiles (code8_front_bytes): the rows of the last tile past the row count are never written.
+constexpr uint32_t kCode8FrontMask = 0xF8F8F8F8u;
+__host__ __device__ inline bool code8_front_dim(int d) { return d > 0 && d % 32 == 0 && d <= 2048; }
+__host__ __device__ inline int code8_front_stride(int d) { return d / 8 * 5; }
+// lanes per row of the scan's front form: the chunks of a row, rounded up to a power of two (the others are masked off)
+__host__ __device__ inline int code8_front_lanes(int d) {
+    int g = 1;
+    while (g * 32 < d) g *= 2;
+    return g;
+}
+__host__ __device__ inline int code8_front_tile_rows(int d) { return 64 / code8_front_lanes(d); }
+__host__ __device__ inline size_t code8_front_bytes(int64_t cap, int d) {
+    const int64_t R = code8_front_tile_rows(d);
+    return (size_t)((cap + R - 1) / R * R) * (size_t)code8_front_stride(d);
+}
+// byte offsets of a row's wide parts (16 * d / 32 bytes) and narrow parts (4 * d / 32 bytes) in the plane
+__host__ __device__ inline size_t code8_front_wide_offset(int64_t row, int d) {
+    const int64_t R = code8_front_tile_rows(d);
+    return (size_t)(row / R * R) * (size_t)code8_front_stride(d) + (size_t)(row % R) * (size_t)(d / 2);
+}
+__host__ __device__ inline size_t code8_front_narrow_offset(int64_t row, int d) {
+    const int64_t R = code8_front_tile_rows(d);
+    return (size_t)(row / R * R) * (size_t)code8_front_stride(d) + (size_t)R * (size_t)(d / 2) + (size_t)(row % R) * (size_t)(d / 8);
+}
+
+__host__ __device__ inline void code8_front_pack_chunk(const uint32_t (&c)[8], uint32_t (&f)[5]) {
+    f[0] = (c[0] & kCode8FrontMask) | ((c[5] >> 5) & 0x07070707u);
+    f[1] = (c[1] & kCode8FrontMask) | ((c[5] >> 3) & 0x03030303u) | ((c[7] >> 2) & 0x04040404u);
+    f[2] = (c[2] & kCode8FrontMask) | ((c[6] >> 5) & 0x07070707u);
+    f[3] = (c[3] & kCode8FrontMask) | ((c[6] >> 3) & 0x03030303u) | ((c[7] >> 1) & 0x04040404u);
+    f[4] = (c[4] & kCode8FrontMask) | ((c[7] >> 5) & 0x07070707u);
+}
+// (c & ~7) of the 32 codes
+__host__ __device__ inline void code8_front_unpack_chunk(const uint32_t (&f)[5], uint32_t (&c)[8]) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) c[i] = f[i] & kCode8FrontMask;
+    c[5] = ((f[0] & 0x07070707u) << 5) | ((f[1] & 0x03030303u) << 3);
+    c[6] = ((f[2] & 0x07070707u) << 5) | ((f[3] & 0x03030303u) << 3);
+    c[7] = ((f[4] & 0x07070707u) << 5) | ((f[1] & 0x04040404u) << 2) | ((f[3] & 0x04040404u) << 1);
+}
+// d codes of one row <-> its image in the front plane, 5 d / 8 bytes: the wide parts of its chunks, then the narrow parts
+// (host: mvdb_code8_front_pack / mvdb_code8_front_unpack; unpack yields c & ~7)
+inline void code8_front_pack_row(int d, const int8_t* codes, uint8_t* image) {
+    for (int t = 0; t < d / 32; ++t) {
+        uint32_t c[8], f[5];
+        memcpy(c, codes + 32 * t, 32);
+        code8_front_pack_chunk(c, f);
+        memcpy(image + 16 * t, f, 16);
+        memcpy(image + d / 2 + 4 * t, &f[4], 4);
+    }
+}
+inline void code8_front_unpack_row(int d, const uint8_t* image, int8_t* codes) {
+    for (int t = 0; t < d / 32; ++t) {
+        uint32_t c[8], f[5];
+        memcpy(f, image + 16 * t, 16);
+        memcpy(&f[4], image + d / 2 + 4 * t, 4);
+        code8_front_unpack_chunk(f, c);
+        memcpy(codes + 32 * t, c, 32);
+    }
+}
+
 // ---- build: rows [0, n) of X -> codes, (a, r) ------------------------------------------------------------------------------------
 // One wave per row.  a = max|x| / 127, c = rint(x / a); r = sqrt(sum (x - a c)^2) rounded up.  A row with a non-finite element
 // gets zero codes and r = +inf: it is always a candidate and the exact kernel treats it as it always has.
 // list == NULL: rows [0, n) behind the four pointers.  list != NULL (set_rows): the n stored rows list[0 .. n), the pointers
 // at row 0; a listed row at or above `limit` (not coded yet) is skipped.
 // The codes go out as the two planes: a lane holds one dword of codes, the four lanes of a quad hold a 16-code chunk.
+// front != NULL: the front plane of the whole index (tiled: addressed by the stored row's number, front_row0 + row); eight
+// lanes hold a 32-code chunk (d is a multiple of 32 then: code8_front_dim).
 __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restrict__ X, int64_t ld, int d, int64_t n,
                                                           uint8_t* __restrict__ high, uint8_t* __restrict__ low, float2* __restrict__ ar,
-                                                          const int64_t* __restrict__ list, int64_t limit) {
+                                                          const int64_t* __restrict__ list, int64_t limit, uint8_t* __restrict__ front,
+                                                          int64_t front_row0) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
@@ -179,6 +260,18 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
                 hdst[3 * (c >> 2) + part] = part == 0 ? h[0] : part == 1 ? h[1] : h[2];
             else
                 ldst[c >> 2] = l;
+            if (front) {
+                uint32_t oct[8], f[5];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) oct[j] = (uint32_t)__shfl((int)word, (lane & ~7) + j);
+                code8_front_pack_chunk(oct, f);
+                const int fpart = lane & 7;
+                if (fpart < 4)
+                    reinterpret_cast<uint32_t*>(front + code8_front_wide_offset(front_row0 + row, d))[4 * (c >> 3) + fpart] =
+                        fpart == 0 ? f[0] : fpart == 1 ? f[1] : fpart == 2 ? f[2] : f[3];
+                else if (fpart == 4)
+                    reinterpret_cast<uint32_t*>(front + code8_front_narrow_offset(front_row0 + row, d))[c >> 3] = f[4];
+            }
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) r2 += __shfl_xor(r2, m);
@@ -426,6 +519,12 @@ struct Code8ScanArgs {
     int64_t cap;
     unsigned long long* counter;  // zeroed by code8_seed_kernel's block 0; keeps counting past cap
     unsigned long long* survivors;  // diagnostic, never zeroed: the rows the first stage could not reject, over all calls
+    // the front form only (GF > 0):
+    const uint8_t* front;  // the front plane (tiled: code8_front_wide_offset): streamed; `high` is then gathered for its survivors
+    unsigned long long* front_survivors;   // never zeroed: the rows stage 0 could not reject, over all calls of the front form
+    unsigned int* front_calls;             // never zeroed: the calls of the front form
+    volatile unsigned long long* front_msum;   // host-mapped: block 0 leaves both counts here at its head, as it finds them
+    volatile unsigned int* front_mcalls;       //   (the calls before this one and their survivors: the host's window takes the mean)
 };
 
 // lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
@@ -483,11 +582,21 @@ __device__ __forceinline__ int code8_reduce(int (&T)[U], int t) {
 // T, and runs the predicate itself on T: what is appended is what the one-plane prefilter appended, row for row.
 typedef int i32x3 __attribute__((ext_vector_type(3), aligned(4)));
 
-template <int G, int U, bool MASKED>
+//
+// The front form (GF > 0: GF lanes per row, UF tiles per batch).  Stage 0 in front of the two: the loop streams the FRONT plane
+// (H5 = c & ~7, 5 d / 8 bytes per row; a lane holds a 32-code chunk: one 16-byte and one 4-byte load), has T5 = Q . H5 and
+// T5 - 7 N <= T <= T5 + 7 P, and evaluates the predicate at the upper end exactly as stage 1 does with 3 (the same proof, the
+// same int32 argument: every factor H5_j + 7 [Q_j > 0] lies in [-128, 127]).  The rows it cannot reject are staged, 64 per
+// wave; gather0() fetches their chunks of the high plane and their (a, r) in this kernel's (G, U) geometry, forms T6 with
+// `scores` and hands it to stage 1: from there on the row goes the way it goes in the other form.  What is appended is the
+// same set of rows; only the order of the appends differs.
+template <int G, int U, bool MASKED, int GF = 0, int UF = 0>
 __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
     constexpr int RB = RPI * U;
+    constexpr bool FRONT = GF > 0;
     static_assert(U >= 2 && U <= 8 && (U & (U - 1)) == 0 && U <= G, "code8_reduce halves U down to one value inside a row group");
+    static_assert(!FRONT || (UF >= 2 && UF <= 8 && (UF & (UF - 1)) == 0 && UF <= GF && kWave % GF == 0), "the same, for the front form");
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = lane % G;
@@ -518,6 +627,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         p3 += __shfl_xor(p3, m);
         n3 += __shfl_xor(n3, m);
     }
+    const int p7 = __builtin_amdgcn_readfirstlane(p3) * 7, n7 = __builtin_amdgcn_readfirstlane(n3) * 7;   // (stage 0; at most 7 d qmax < 2^27)
     p3 = __builtin_amdgcn_readfirstlane(p3) * 3;
     n3 = __builtin_amdgcn_readfirstlane(n3) * 3;
 
@@ -525,14 +635,14 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     uint32_t stage = 0;
     int nst = 0;
     const unsigned long long cap = (unsigned long long)a.cap;
-    auto flush = [&]() {
+    auto flush = [&]() __attribute__((always_inline)) {
         unsigned long long base = 0;
         if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)nst);
         base = readlane_u64(base, 0);
         if (lane < nst && base + (unsigned long long)lane < cap) a.cand[base + lane] = stage;
         nst = 0;
     };
-    auto append = [&](uint64_t m, uint32_t row) {
+    auto append = [&](uint64_t m, uint32_t row) __attribute__((always_inline)) {
         while (m) {
             const int src = __ffsll((long long)m) - 1;
             m &= m - 1;
@@ -567,7 +677,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     };
     // THE predicate, on the row's integer sum.  Every lane evaluates it (its (a, r) load is issued with the batch's loads, not
     // behind a lane test); `mine` keeps the bits of the lanes that report a row
-    auto epilogue = [&](int tot, float2 sr, uint64_t mine, int64_t r) {
+    auto epilogue = [&](int tot, float2 sr, uint64_t mine, int64_t r) __attribute__((always_inline)) {
         const float s = ((float)tot * qstep) * sr.x;
         float m = fmaf(alpha, sr.y, beta);
         m = fmaf(fabsf(s) + m, 2.4e-7f, m);   // the rounding of s + m itself
@@ -582,7 +692,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     int st6 = 0, ns1 = 0;
     unsigned long long nrefined = 0;   // (the diagnostic count: one atomic per wave, at its end)
     const int lstride4 = a.d / 16;   // dwords per row of the low plane
-    auto refine = [&]() {
+    auto refine = [&]() __attribute__((always_inline)) {
         nrefined += (unsigned long long)ns1;
         for (int base = 0; base < ns1; base += RB) {
             // staged entries past the last re-read the last one, their result is discarded
@@ -625,7 +735,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     // |s(T)| <= max(|sl|, |su|), the margin formed from that is >= the predicate's, and su + it is >= the predicate's bound, bit
     // for bit (fp32 + and fma are monotone in every operand) — or NaN, which passes.  The lower end saturates at INT_MIN: still
     // <= T, which fits (code8_qmax).
-    auto stage1 = [&](int t6, float2 sr, uint64_t mine, int64_t r) {
+    auto stage1 = [&](int t6, float2 sr, uint64_t mine, int64_t r) __attribute__((always_inline)) {
         const int tl = (t6 > INT_MIN + n3 ? t6 : INT_MIN + n3) - n3;
         const float su = ((float)(t6 + p3) * qstep) * sr.x;
         const float sl = ((float)tl * qstep) * sr.x;
@@ -648,6 +758,186 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
 
     const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
     const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
+    __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
+    __shared__ float sfloor;
+
+    if constexpr (FRONT) {
+        constexpr int RPF = kWave / GF;
+        constexpr int RBF = RPF * UF;
+        const int tf = lane % GF;
+        const int gf = lane / GF;
+        const bool validf = !MASKED || tf * 32 < a.d;
+        i32x4 fh[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, fl[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        if (validf) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fh[i] = *reinterpret_cast<const i32x4*>(a.qhi + tf * 32 + 16 * i);
+                fl[i] = *reinterpret_cast<const i32x4*>(a.qlo + tf * 32 + 16 * i);
+            }
+        }
+        int uef = 0;
+#pragma unroll
+        for (int m = 1, h = UF / 2; m < UF; m <<= 1, h >>= 1) uef += (tf & m) ? h : 0;
+        const int erowf = uef * RPF + gf;
+        const uint64_t elanesf = __ballot(tf < UF);
+
+        // the counts as block 0 finds them, for the host's window (index_state.hpp): no synchronisation, they lag
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const unsigned int calls = atomicAdd(a.front_calls, 1u);
+            const unsigned long long sum = atomicAdd(a.front_survivors, 0ull);
+            if (a.front_msum) {
+                *a.front_msum = sum;
+                *a.front_mcalls = calls;
+            }
+        }
+
+        // (c & ~7) of the lane's chunks against the query's planes: T5
+        auto scores0 = [&](const i32x4 (&xw)[UF], const int (&xn)[UF], int (&T)[UF]) {
+#pragma unroll
+            for (int u = 0; u < UF; ++u) {
+                const uint32_t f[5] = {(uint32_t)xw[u].x, (uint32_t)xw[u].y, (uint32_t)xw[u].z, (uint32_t)xw[u].w, (uint32_t)xn[u]};
+                uint32_t c[8];
+                code8_front_unpack_chunk(f, c);
+                int hi = 0, lo = 0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    hi = __builtin_amdgcn_sdot4((int)c[j], fh[j >> 2][j & 3], hi, false);
+                    lo = __builtin_amdgcn_sdot4((int)c[j], fl[j >> 2][j & 3], lo, false);
+                }
+                T[u] = hi * 256 + lo;
+            }
+        };
+        // ---- the rows stage 0 staged -> their chunks of the high plane -> T6 -> stage 1 ----
+        uint32_t s0row = 0;
+        int ns0 = 0;
+        unsigned long long nfront = 0;   // (one atomic per wave, at its end)
+        auto gather0 = [&]() __attribute__((always_inline)) {
+            nfront += (unsigned long long)ns0;
+            for (int base = 0; base < ns0; base += RB) {
+                // staged entries past the last re-read the last one, their result is discarded
+                i32x3 x[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    int e = base + u * RPI + g;
+                    e = e < ns0 - 1 ? e : ns0 - 1;
+                    const uint32_t row = (uint32_t)__shfl((int)s0row, e);
+                    const i32x3* src = reinterpret_cast<const i32x3*>(a.high + (int64_t)row * a.hstride + t * 12);
+                    if (MASKED)
+                        x[u] = valid ? *src : i32x3{0, 0, 0};
+                    else
+                        x[u] = *src;
+                }
+                const int e = base + erow;
+                const int ec = e < ns0 - 1 ? e : ns0 - 1;
+                const uint32_t row = (uint32_t)__shfl((int)s0row, ec);
+                const float2 sr = a.ar[row];
+                int T[U];
+                scores(x, T);
+                stage1(code8_reduce<G, U>(T, t), sr, __ballot(t < U && e < ns0), row);
+            }
+            ns0 = 0;
+        };
+        // ---- stage 0: the predicate at the upper end of what the missing 3 bits can make of T5 (stage1's form, 7 for 3) ----
+        auto stage0 = [&](int t5, float2 sr, uint64_t mine, int64_t r) __attribute__((always_inline)) {
+            const int tl = (t5 > INT_MIN + n7 ? t5 : INT_MIN + n7) - n7;
+            const float su = ((float)(t5 + p7) * qstep) * sr.x;
+            const float sl = ((float)tl * qstep) * sr.x;
+            float m = fmaf(alpha, sr.y, beta);
+            m = fmaf(fmaxf(fabsf(su), fabsf(sl)) + m, 2.4e-7f, m);
+            const float ub = su + m;
+            uint64_t pass = __ballot(!(ub < floor)) & mine;
+            while (pass) {
+                const int src = __ffsll((long long)pass) - 1;
+                pass &= pass - 1;
+                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)r, src);
+                if (lane == ns0) s0row = v;
+                if (++ns0 == kWave) gather0();
+            }
+        };
+
+        const int nch = a.d / 32;
+        const int64_t tile_bytes = (int64_t)RPF * code8_front_stride(a.d);
+        const int64_t batch_bytes = (int64_t)UF * tile_bytes;
+        const int wide_off = gf * 16 * nch + tf * 16;
+        const int narrow_off = RPF * 16 * nch + gf * 4 * nch + tf * 4;
+        const int64_t nfull = a.n / RBF;
+        auto load0 = [&](i32x4 (&xw)[UF], int (&xn)[UF], float2& sr, int64_t b) {
+            const uint8_t* base = a.front + b * batch_bytes;
+#pragma unroll
+            for (int u = 0; u < UF; ++u) {
+                const i32x4* ws = reinterpret_cast<const i32x4*>(base + u * tile_bytes + wide_off);
+                const int* ns = reinterpret_cast<const int*>(base + u * tile_bytes + narrow_off);
+                if (MASKED) {
+                    xw[u] = validf ? __builtin_nontemporal_load(ws) : i32x4{0, 0, 0, 0};
+                    xn[u] = validf ? __builtin_nontemporal_load(ns) : 0;
+                } else {
+                    xw[u] = __builtin_nontemporal_load(ws);
+                    xn[u] = __builtin_nontemporal_load(ns);
+                }
+            }
+            sr = a.ar[b * RBF + erowf];
+        };
+        // the head, as in the other form: the first batch's loads, then the floor
+        int64_t b = gw;
+        const bool head = b < nfull;
+        i32x4 xw0[UF];
+        int xn0[UF];
+        float2 sr0 = make_float2(0.f, 0.f);
+        if (head) load0(xw0, xn0, sr0, b);
+        floor = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)__float_as_uint(code8_lists_floor(a.lists, a.nlists, a.k, sh, &sfloor, kScanWaves))));
+        if (blockIdx.x == 0 && threadIdx.x == 0) *a.floor = floor;
+        if (head) {
+            int T[UF];
+            scores0(xw0, xn0, T);
+            stage0(code8_reduce<GF, UF>(T, tf), sr0, elanesf, b * RBF + erowf);
+            b += nwaves_total;
+        }
+        for (; b < nfull; b += nwaves_total) {
+            i32x4 xw[UF];
+            int xn[UF];
+            float2 sr;
+            load0(xw, xn, sr, b);
+            int T[UF];
+            scores0(xw, xn, T);
+            stage0(code8_reduce<GF, UF>(T, tf), sr, elanesf, b * RBF + erowf);
+        }
+        // the partial batch behind the full ones: tiles past the last re-read the last tile (the plane is whole tiles), rows
+        // past the end are discarded
+        if (nfull * RBF < a.n && nfull % nwaves_total == gw) {
+            const int64_t last = a.n - 1;
+            const int64_t last_tile = last / RPF;
+            i32x4 xw[UF];
+            int xn[UF];
+#pragma unroll
+            for (int u = 0; u < UF; ++u) {
+                int64_t tile = nfull * UF + u;
+                tile = tile < last_tile ? tile : last_tile;
+                const uint8_t* base = a.front + tile * tile_bytes;
+                const i32x4* ws = reinterpret_cast<const i32x4*>(base + wide_off);
+                const int* ns = reinterpret_cast<const int*>(base + narrow_off);
+                if (MASKED) {
+                    xw[u] = validf ? __builtin_nontemporal_load(ws) : i32x4{0, 0, 0, 0};
+                    xn[u] = validf ? __builtin_nontemporal_load(ns) : 0;
+                } else {
+                    xw[u] = __builtin_nontemporal_load(ws);
+                    xn[u] = __builtin_nontemporal_load(ns);
+                }
+            }
+            const int64_t r = nfull * RBF + erowf;
+            const float2 sr = a.ar[r < last ? r : last];
+            int T[UF];
+            scores0(xw, xn, T);
+            stage0(code8_reduce<GF, UF>(T, tf), sr, __ballot(tf < UF && r < a.n), r);
+        }
+        if (ns0) gather0();
+        if (ns1) refine();
+        if (nfront && lane == 0) atomicAdd(a.front_survivors, nfront);
+        if (nrefined && lane == 0) atomicAdd(a.survivors, nrefined);
+        if (nst) flush();
+        return;
+    }
+
     const int64_t nfull = a.n / RB;
     const int64_t batch_bytes = (int64_t)RB * a.hstride;
     const int64_t group_bytes = (int64_t)RPI * a.hstride;
@@ -667,8 +957,6 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     };
     // The head: the floor, merged by every block from the lists the seed launch's blocks left (the same bits in every block:
     // code8_lists_floor).  The wave's first batch depends on neither the floor nor the merge: its loads are issued first.
-    __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
-    __shared__ float sfloor;
     int64_t b = gw;
     const bool head = b < nfull;
     i32x3 x0[U];

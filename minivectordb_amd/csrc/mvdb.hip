@@ -72,6 +72,7 @@ Knobs read_knobs() {
     k.code8_seed_blocks = env_int("MVDB_CODE8_SEED_BLOCKS", 0);
     k.code8_seed_threads = env_int("MVDB_CODE8_SEED_THREADS", 0);
     k.code8_rescore_rows = env_int("MVDB_CODE8_RESCORE_ROWS", 0);
+    k.code8_front_u = env_int("MVDB_CODE8_FRONT_U", 0);
     return k;
 }
 
@@ -356,6 +357,10 @@ static std::atomic<uint64_t> g_index_serial{0};
 //   capture                      | ensure builds nothing: a complete shadow is    | ensure builds nothing: a complete code with a
 //                                | used, else the fp32 passes serve               | valid sample is used, else the exact scan serves
 //
+// The code's FRONT plane (Code8Store::F5, the top 5 bits of every code: code8_scan.hpp) is part of the code in every row of
+// this table: allocated (index option code8_front_plane; an allocation that fails leaves the code without it, nothing else),
+// written by the same launch of code8_build_kernel, emptied, dropped and freed with the two planes.  Setting the option to 0
+// frees it alone; setting it again drops a code that lacks it, and the next eligible query builds both.
 // (`failed` of both is read by routing code that holds only the shared lock and written under shadow_mu: atomic.)
 namespace {
 
@@ -376,6 +381,7 @@ struct ShadowStore {   // half_scan.hip: flat_scan_h16_kernel
 
 struct Code8Store {   // code8_scan.hpp; DESIGN.md section 4.1b: d codes + (scale, residual bound) per row, the operand of the single-query prefilter
     DevMem<uint8_t> C8;  // two planes: [cap, 3 d / 4] high, then [cap, d / 4] low (low())
+    DevMem<uint8_t> F5;  // the front plane: [cap rounded up to whole tiles, 5 d / 8], tiled (code8_front_wide_offset); may be absent
     DevMem<float2> ar;
     DevMem<int8_t> samp;  // the stored copy of the floor's sample (code8_sample_kernel; the rule: gather_sample): codes, then (a, r) entries
     int64_t cap = 0, rows = 0;
@@ -428,9 +434,13 @@ struct mvdb_index {
     mutable std::atomic<unsigned int> rf_seen{0};
     mutable std::atomic<int> rf_calls_left{0};
     // the int8 route, created with the code.  Device words: [0] fallbacks, [1] calls, [2..3] one 64-bit word: rows refined
-    // (code8_scan_kernel); mirror: fallbacks, candidates of the latest call, calls
+    // (code8_scan_kernel), [4..5] one 64-bit word: rows stage 0 of its front form could not reject, [6] calls of the front form;
+    // mirror: fallbacks, candidates of the latest call, calls, then (64-bit, at byte 16) the survivors of stage 0 and, word 6,
+    // the front form's calls, as block 0 of the latest front launch found them.  c8_front: the front form's own window over
+    // the mean share of survivors (index_state.hpp: RouteWindow::suspended_mean) — suspended, the other form of the kernel runs
     mutable MirroredCounter c8_ctr;
     mutable RouteWindow c8_route;
+    mutable RouteWindow c8_front;
     // range search, shared pass (range_shared_phase), created by the first call that takes it: a running count of queries its
     // fallback answered, mirrored with the candidates of the latest launch group as 64-bit words; calls that took the route
     // are counted on the host
@@ -1009,6 +1019,7 @@ bool half_path_ok(const mvdb_index* idx) {
 }
 
 bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, const uint64_t* mask_dev, int64_t n);
+bool code8_front_wanted(int option, int d);   // whether an index of width d keeps the front plane under this value of code8_front_plane
 int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, int k, int64_t label_offset, float* D_dev, int64_t* I_dev,
                  bool* served);
 
@@ -1938,6 +1949,7 @@ constexpr int kCode8RebuildAfter = 2;
 //  held right now: every delete of a delete / query alternation restarts it, so such a workload never builds)
 void Code8Store::drop(bool count_rebuild) {
     C8.release();
+    F5.release();
     ar.release();
     samp.release();
     cap = rows = samp_n = 0;
@@ -1955,7 +1967,7 @@ int Code8Store::build(const mvdb_index* idx, int64_t row0, int64_t n, hipStream_
     if (n > 0)
         hipLaunchKernelGGL(code8_build_kernel, dim3(row_grid(idx->device, n)), dim3(256), 0, s, (const float*)(idx->X.p + row0 * idx->ld), idx->ld,
                            idx->d, n, C8.p + row0 * code8_high_stride(idx->d), low(idx->d) + row0 * code8_low_stride(idx->d), ar.p + row0,
-                           list_dev, list_dev ? rows : (int64_t)0);
+                           list_dev, list_dev ? rows : (int64_t)0, F5.p, row0);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
@@ -1992,11 +2004,16 @@ bool Code8Store::ensure(const mvdb_index* idx, hipStream_t s) {
     if (!C8.p) {
         const int64_t want = std::max<int64_t>(idx->cap, idx->n);
         if (C8.alloc((size_t)want * idx->d) != hipSuccess || ar.alloc((size_t)want * sizeof(float2)) != hipSuccess ||
-            samp.alloc(code8_sample_bytes(idx->d)) != hipSuccess || !idx->c8_ctr.ensure(4)) {
+            samp.alloc(code8_sample_bytes(idx->d)) != hipSuccess || !idx->c8_ctr.ensure(8)) {
             (void)hipGetLastError();
             drop(false);
             failed = true;
             return false;
+        }
+        // (the front plane never fails a search: without it the prefilter streams the high plane)
+        if (code8_front_wanted(idx->kn.code8_front_plane, idx->d) && F5.alloc(code8_front_bytes(want, idx->d)) != hipSuccess) {
+            (void)hipGetLastError();
+            F5.release();
         }
         cap = want;
         rows = 0;
@@ -2036,17 +2053,24 @@ bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_de
 // What is specific to the codes: (G, U, MASKED) of code8_seed_kernel per width, and for code8_scan_kernel — whose loads are
 // 12 bytes per lane, not 16 — its own U and blocks per CU (SCAN_U, SCAN_BLOCKS).  All measured per shape: DESIGN.md section
 // 4.1b.  launch(Code8Shape<...>{}) for d; the exact-scan shapes of the route come from with_scan_shape.
-template <int G_, int U_, bool MASKED_, int SCAN_U_, int SCAN_BLOCKS_>
+// The front form of code8_scan_kernel (it streams the front plane, a 32-code chunk per lane): FRONT_G lanes per row
+// (code8_front_lanes: the plane's tiles are 64 / FRONT_G rows), FRONT_U tiles per batch, FRONT_BLOCKS per CU.
+// FRONT_DEFAULT: whether option code8_front_plane = 1 keeps and streams the plane at this width (measured: DESIGN.md section
+// 4.1b — at d = 1024 the front form loses on the zero-mean corpus, whose stage 0 leaves 11 % of the rows; the diagnostic
+// values 2 and 3 of the option still build the plane there).
+template <int G_, int U_, bool MASKED_, int SCAN_U_, int SCAN_BLOCKS_, int FRONT_G_, int FRONT_U_, int FRONT_BLOCKS_, bool FRONT_DEFAULT_>
 struct Code8Shape {
+    static constexpr bool FRONT_DEFAULT = FRONT_DEFAULT_;
     static constexpr int G = G_, U = U_, SCAN_U = SCAN_U_, SCAN_BLOCKS = SCAN_BLOCKS_;
+    static constexpr int FRONT_G = FRONT_G_, FRONT_U = FRONT_U_, FRONT_BLOCKS = FRONT_BLOCKS_;
     static constexpr bool MASKED = MASKED_;
 };
 template <typename Launch>
 int with_code8_shape(int d, Launch launch) {
     switch (d) {
-        case 384: return launch(Code8Shape<32, 8, true, 8, 4>{});
-        case 512: return launch(Code8Shape<32, 4, false, 8, 2>{});
-        case 1024: return launch(Code8Shape<64, 4, false, 8, 2>{});
+        case 384: return launch(Code8Shape<32, 8, true, 8, 4, 16, 8, 2, true>{});
+        case 512: return launch(Code8Shape<32, 4, false, 8, 2, 16, 4, 2, true>{});
+        case 1024: return launch(Code8Shape<64, 4, false, 8, 2, 32, 4, 2, false>{});
         default: return fail(MVDB_ERR_ARG, "internal: no int8 prefilter kernel for d = %d", d);
     }
 }
@@ -2059,21 +2083,47 @@ int with_code8_exact_shape(int d4, Launch launch) {
     });
 }
 
+bool code8_front_wanted(int option, int d) {
+    if (option == 0 || !code8_dim(d) || !code8_front_dim(d)) return false;
+    bool dflt = false;
+    (void)with_code8_shape(d, [&](auto cs) {
+        dflt = decltype(cs)::FRONT_DEFAULT;
+        return 0;
+    });
+    return option >= 2 || dflt;
+}
+
 // the prefilter's grid: CUs x BLOCKS blocks, BLOCKS per shape from the sweep of this kernel (Code8Shape::SCAN_BLOCKS;
 // profiles/code8_planes_sweep.jsonl: U = 8 with 2 blocks per CU at d = 512 and 1024, with 4 at d = 384)
-template <int G, int U, bool MASKED, int BLOCKS>
+// (GF, UF > 0: the front form — its batches are (64 / GF) UF rows)
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0>
 int code8_scan_blocks(int64_t n, int device) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF>;
     int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), BLOCKS);
     if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
-    return scan_grid(n, (kWave / G) * U, per_cu, device);
+    return scan_grid(n, GF > 0 ? (kWave / GF) * UF : (kWave / G) * U, per_cu, device);
 }
-template <int G, int U, bool MASKED, int BLOCKS>
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0>
 int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED>;
-    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS>(a.n, device);
-    return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
-                           "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF>;
+    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF>(a.n, device);
+    if constexpr (GF > 0)
+        return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
+                               "code8_scan_kernel<%d, %d, %s, %d, %d>", G, U, MASKED ? "true" : "false", GF, UF);
+    else
+        return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
+                               "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
+}
+// Which form of the prefilter serves this call: the front form where the code holds the plane, unless its window has
+// suspended it (the survivors of stage 0 pay three gathered lines each: past kCode8FrontShare of the rows the other form is
+// faster) — option value 2 keeps it on.  One decision per call; no synchronisation (the mirrored words lag).
+constexpr double kCode8FrontShare = 0.12;
+bool code8_front_serves(const mvdb_index* idx) {
+    if (!idx->code.F5.p || !code8_front_wanted(idx->kn.code8_front_plane, idx->d)) return false;
+    if (idx->kn.code8_front_plane >= 2) return idx->kn.code8_front_plane == 2;   // (diagnostic values: always / never)
+    const volatile unsigned long long* sum = idx->c8_ctr.mirror<unsigned long long>();
+    return !idx->c8_front.suspended_mean(sum ? sum + 2 : nullptr, idx->c8_ctr.mirror() ? idx->c8_ctr.mirror() + 6 : nullptr,
+                                         kCode8FrontShare * (double)idx->n);
 }
 
 // The floor's launch.  The stored sample streams; every block leaves one list, which every block of the prefilter merges.
@@ -2174,9 +2224,18 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.cap = cap;
     c.counter = counter;
     c.survivors = reinterpret_cast<unsigned long long*>(idx->c8_ctr.dev() + 2);
+    c.front = idx->code.F5.p;
+    c.front_survivors = reinterpret_cast<unsigned long long*>(idx->c8_ctr.dev() + 4);
+    c.front_calls = idx->c8_ctr.dev() + 6;
+    c.front_msum = idx->c8_ctr.mirror<unsigned long long>() + 2;
+    c.front_mcalls = idx->c8_ctr.mirror() + 6;
+    const bool front = code8_front_serves(idx);
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
-        return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
+        if (!front) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
+        const int fu = kn().code8_front_u == 4 || kn().code8_front_u == 8 ? kn().code8_front_u : K::FRONT_U;   // (tuning hook)
+        if (fu == 4) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 4>(c, idx->device, s);
+        return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 8>(c, idx->device, s);
     }));
     // 3. the fallback decision and the exact scores of the candidates, ties by row: one sorted k-list per active block
     Code8RescoreArgs r;
@@ -2309,11 +2368,13 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     const bool code8 = idx->kn.code8_single_query;   // (options without an environment switch: kept)
     const long long code8_cap = idx->kn.code8_capacity;
+    const int code8_front = idx->kn.code8_front_plane;
     const int range_shared = idx->kn.range_shared;
     const long long range_cand = idx->kn.range_candidates;
     idx->kn = read_knobs();
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
+    idx->kn.code8_front_plane = code8_front;
     idx->kn.range_shared = range_shared;
     idx->kn.range_candidates = range_cand;
     return 0;
@@ -2333,6 +2394,17 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "code8_capacity") {  // diagnostic: a small candidate capacity makes calls take the fallback
         if (value <= 0 || value > kCode8MaxCapacity) return fail(MVDB_ERR_ARG, "code8_capacity must lie in [1, %lld]", (long long)kCode8MaxCapacity);
         idx->kn.code8_capacity = value;
+    } else if (n == "code8_front_plane") {
+        if (value < 0 || value > 3) return fail(MVDB_ERR_ARG, "code8_front_plane must be 0, 1, 2 or 3");
+        DeviceGuard dg(idx->device);
+        MVDB_TRY(quiesce(idx));
+        idx->kn.code8_front_plane = (int)value;
+        if (!code8_front_wanted((int)value, idx->d))
+            idx->code.F5.release();
+        else if (idx->code.C8.p && !idx->code.F5.p && code8_front_wanted((int)value, idx->d))
+            idx->code.drop(false);   // (a code without the plane: the next eligible query builds both)
+        const volatile unsigned long long* sum = idx->c8_ctr.mirror<unsigned long long>();
+        idx->c8_front.restart_mean(sum ? sum + 2 : nullptr, idx->c8_ctr.mirror() ? idx->c8_ctr.mirror() + 6 : nullptr);
     } else if (n == "range_shared") {  // batches of a range search on the shared fp16 pass: 0 never, 1 by size, 2 wherever eligible
         if (value < 0 || value > 2) return fail(MVDB_ERR_ARG, "range_shared must be 0, 1 or 2");
         idx->kn.range_shared = (int)value;
@@ -2345,7 +2417,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, range_shared, range_candidates, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, range_candidates, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2440,6 +2512,60 @@ int mvdb_code8_pack(int d, const int8_t* codes, uint8_t* high, uint8_t* low) {
 int mvdb_code8_unpack(int d, const uint8_t* high, const uint8_t* low, int8_t* codes) {
     if (d <= 0 || d % 16 || !codes || !high || !low) return fail(MVDB_ERR_ARG, "mvdb_code8_unpack: bad arguments");
     code8_unpack_row(d, high, low, codes);
+    return 0;
+}
+int mvdb_code8_front_pack(int d, const int8_t* codes, uint8_t* image) {
+    if (!code8_front_dim(d) || !codes || !image) return fail(MVDB_ERR_ARG, "mvdb_code8_front_pack: bad arguments (d must be a multiple of 32, at most 2048)");
+    code8_front_pack_row(d, codes, image);
+    return 0;
+}
+int mvdb_code8_front_unpack(int d, const uint8_t* image, int8_t* codes) {
+    if (!code8_front_dim(d) || !codes || !image) return fail(MVDB_ERR_ARG, "mvdb_code8_front_unpack: bad arguments (d must be a multiple of 32, at most 2048)");
+    code8_front_unpack_row(d, image, codes);
+    return 0;
+}
+int mvdb_code8_front_geometry(int d, int64_t n, int device, int* rows_per_batch, int* waves) {
+    if (!code8_dim(d) || n <= 0 || !rows_per_batch || !waves) return fail(MVDB_ERR_ARG, "mvdb_code8_front_geometry: bad arguments");
+    DeviceGuard dg(device);
+    return with_code8_shape(d, [&](auto cs) {
+        using K = decltype(cs);
+        *rows_per_batch = (kWave / K::FRONT_G) * K::FRONT_U;
+        *waves = code8_scan_blocks<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, K::FRONT_U>(n, device) * kScanWaves;
+        return 0;
+    });
+}
+int mvdb_index_code8_front_counters(const mvdb_index* idx, long long* survivors, long long* calls, long long* suspensions, int* held) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (survivors) *survivors = 0;
+    if (calls) *calls = 0;
+    if (suspensions) *suspensions = (long long)idx->c8_front.suspensions.load();
+    if (held) {
+        std::lock_guard<std::mutex> lk(idx->shadow_mu);
+        *held = idx->code.F5.p ? 1 : 0;
+    }
+    if (!idx->c8_ctr.dev()) return 0;
+    DeviceGuard dg(idx->device);
+    unsigned int w[3] = {0, 0, 0};
+    MVDB_HIP(hipMemcpy(w, idx->c8_ctr.dev() + 4, sizeof(w), hipMemcpyDeviceToHost));
+    if (survivors) *survivors = (long long)((unsigned long long)w[0] | ((unsigned long long)w[1] << 32));
+    if (calls) *calls = (long long)w[2];
+    return 0;
+}
+int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high, uint8_t* low, uint8_t* front) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    std::lock_guard<std::mutex> sk(idx->shadow_mu);
+    const Code8Store& c = idx->code;
+    if (!c.C8.p || row < 0 || row >= c.rows) return fail(MVDB_ERR_ARG, "mvdb_index_code8_read_row: row %lld is not in the code", (long long)row);
+    if (front && !c.F5.p) return fail(MVDB_ERR_ARG, "mvdb_index_code8_read_row: the code holds no front plane");
+    DeviceGuard dg(idx->device);
+    const int d = idx->d;
+    if (high) MVDB_HIP(hipMemcpy(high, c.C8.p + row * code8_high_stride(d), code8_high_stride(d), hipMemcpyDeviceToHost));
+    if (low) MVDB_HIP(hipMemcpy(low, c.low(d) + row * code8_low_stride(d), code8_low_stride(d), hipMemcpyDeviceToHost));
+    if (front) {
+        MVDB_HIP(hipMemcpy(front, c.F5.p + code8_front_wide_offset(row, d), d / 2, hipMemcpyDeviceToHost));
+        MVDB_HIP(hipMemcpy(front + d / 2, c.F5.p + code8_front_narrow_offset(row, d), d / 8, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta) {
