@@ -451,6 +451,39 @@ double mvdb_range_band(int d, float qnorm, float row_norm_bound);
 int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries,
                               long long* last_candidates);
 
+/* MMR SEARCH (maximal marginal relevance): k rows that are relevant AND unlike each other, picked greedily on the device from
+ * the fetch_k best — the answer to a top-k that is k near-copies of one passage.  Inner-product indexes only.
+ * Candidates.  The candidates of query i are, bit for bit, row i of what mvdb_index_search (rs == NULL) or
+ * mvdb_index_search_rowset returns for the same (q, nq, fetch_k, normalize_q): the same routing, tie order and -1 padding.
+ * rel[j] is the fp32 score of candidate position j.
+ * Selection, per query.  Step 0 picks position 0.  Step t >= 1 picks the not yet picked valid position j that maximises
+ *     obj[j] = lambda * rel[j] - (1 - lambda) * max over the picked p of s(p, j)
+ * in fp32 (1 - lambda rounded once, each product rounded, then the difference), where s(p, j) is the fp32 inner product of
+ * the two STORED rows as they sit in the matrix — the quantity the relevance is.  Ties go to the lower candidate position
+ * (the lower row number, or the lower list position for an unsorted list: the search's own tie order).  A NaN objective
+ * compares as -inf.  The summation order of s depends on d alone, not on the position, the step, the query's place in the
+ * batch or the form below: exact duplicate rows score bit-identically and a call is reproducible run to run.
+ * lambda = 1 returns the first k candidates (while every s is finite); lambda = 0 ignores relevance after the first pick.
+ * Output.  Row i of I [nq,k]: the picked rows in selection order (row numbers; + label_offset in the device variant); row i
+ * of D [nq,k]: their rel values, the very bits the search returned.  A query with fewer than k valid candidates is padded
+ * with -1 / -FLT_MAX.
+ * Arguments.  1 <= k <= fetch_k <= 1024; lambda in [0, 1] (NaN or outside: MVDB_ERR_ARG); an L2 index: MVDB_ERR_ARG; a stale
+ * or foreign row set: MVDB_ERR_ARG before anything is enqueued, nothing written; an empty index or set: all missing markers.
+ * Cost.  The candidate search, then ONE launch, a workgroup per query, k - 1 passes over the candidates' rows:
+ * mvdb_mmr_form says from where — 0: the fetch_k rows are gathered into LDS once (fetch_k * ld * 4 bytes; the everyday shapes,
+ * fetch_k 20 - 64 at d <= 512), 1: every pass reads them from the matrix through L2 ((k - 1) * fetch_k * ld * 4 bytes per
+ * query, at most fetch_k * ld * 4 distinct).  The rule looks at d, fetch_k and the device's LDS only; < 0: error.
+ * Workspace: nq (at most 1024 at a time) x fetch_k candidates, never anything sized by the index.
+ * The device variant follows the contract of mvdb_index_search_device: no synchronisation, no host read, one call at a time
+ * per (index, stream), capturable into a hipGraph after one eager call of the same shape has sized the workspace.
+ * No reference counterpart (its autocut and hybrid_rerank_results work on a fixed top-k after the fact). */
+int mvdb_index_search_mmr(const mvdb_index* idx, const float* q_host, int nq, int k, int fetch_k, float lambda,
+                          int normalize_q, const mvdb_rowset* rs, float* D_host, int64_t* I_host);
+int mvdb_index_search_mmr_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int fetch_k, float lambda,
+                                 int normalize_q, const mvdb_rowset* rs, int64_t label_offset,
+                                 float* D_dev, int64_t* I_dev, void* stream);
+int mvdb_mmr_form(int d, int fetch_k, int device);   /* 0 = candidates held in LDS, 1 = streamed; < 0 = error */
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be

@@ -465,6 +465,10 @@ class _ValueIndex:
                 entry[1][handle] = field
 
 
+class _MmrShape(Exception):
+    """k > fetch_k after clamping: not a ValueError on its way out of the search, which would read as a stale row set."""
+
+
 class FilterAndRerankMixin:
     """Needs: self.inverted_index, self._ids (_IdIndex), self.metadata, self.hash_vectorizer, self._mat (_RowStore),
     self.index, self.embedding_size, self._device, self.lock."""
@@ -603,9 +607,13 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, autocut))
         return out
 
-    def _nearest_rows_many(self, query, metadata_filter, exclude_filter, or_filters, k):
-        """_nearest_rows for a [nq, d] float32 matrix of queries: one list of (row, score) per query."""
-        nq = query.shape[0]
+    def _search_selected(self, metadata_filter, exclude_filter, or_filters, nothing, search):
+        """What every search under one filter shares: lazy device sync, filter evaluation (or the filter's resident row set,
+        found in the cache), and the retry after a concurrent delete.  Returns `nothing` when the filter selects no row (or
+        there is no index yet), else ``search(index, count, rowset)`` — `count` rows selected, `rowset()` their resident
+        row set, None when they are all the rows.  A ValueError out of `search` (another thread deleted rows between the
+        filter and the search; the reference would still be searching its old index object) evaluates the filter again on
+        the current rows, twice at the most."""
         filtered = bool(metadata_filter or exclude_filter or or_filters)
         key = None
         if filtered:
@@ -621,26 +629,40 @@ class FilterAndRerankMixin:
                 gen = self.__dict__.get("_write_gen", 0)
                 hit = self.__dict__.get("_rowsets", {}).get(key) if key is not None else None
                 if hit is not None and hit[0] == gen and hit[1] is index:
-                    count, rowset, wanted = hit[2], hit[3], None
+                    count, held, wanted = hit[2], hit[3], None
                 else:
                     wanted = self._get_filtered_indices(metadata_filter, exclude_filter, or_filters)
-                    count, rowset = len(wanted), None
+                    count, held = len(wanted), None
             if not count or index is None:
-                return [[] for _ in range(nq)]
-            take = min(k, count)
-            try:
+                return nothing
+
+            def rowset():
                 if count == n_rows:
-                    scores, rows = index.search(query, take, normalize_q=True)
-                else:
-                    if rowset is None:
-                        rowset = self._resident_rowset(index, wanted, key, gen)
-                    scores, rows = index.search_rowset(query, take, rowset, normalize_q=True)
-                break
+                    return None
+                return held if held is not None else self._resident_rowset(index, wanted, key, gen)
+
+            try:
+                return search(index, count, rowset)
             except ValueError:
-                # another thread deleted rows between the filter and the search (the reference would still be searching
-                # its old index object): evaluate the filter again on the current rows
+                # rows were deleted between the filter and the search: evaluate the filter again on the current rows
                 if attempt == 2:
                     raise
+
+    def _nearest_rows_many(self, query, metadata_filter, exclude_filter, or_filters, k):
+        """_nearest_rows for a [nq, d] float32 matrix of queries: one list of (row, score) per query."""
+        nq = query.shape[0]
+
+        def search(index, count, rowset):
+            take = min(k, count)
+            rs = rowset()
+            if rs is None:
+                return index.search(query, take, normalize_q=True)
+            return index.search_rowset(query, take, rs, normalize_q=True)
+
+        found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        if found is None:
+            return [[] for _ in range(nq)]
+        scores, rows = found
         return [[(int(r), s) for r, s in zip(rows[i], scores[i]) if r != -1] for i in range(nq)]
 
     def _resident_rowset(self, index, wanted, key, gen):
@@ -744,41 +766,83 @@ class FilterAndRerankMixin:
         `_nearest_rows_many`'s."""
         nq = query.shape[0]
         min_score = self._range_min_scores(min_score, nq)
-        filtered = bool(metadata_filter or exclude_filter or or_filters)
-        key = None
-        if filtered:
-            try:
-                key = repr((metadata_filter, exclude_filter, or_filters))
-            except Exception:
-                key = None
-        for attempt in range(3):
-            with self.lock:
-                if self._embeddings_changed:
-                    self._build_index()
-                index, n_rows = self.index, self._mat.n
-                gen = self.__dict__.get("_write_gen", 0)
-                hit = self.__dict__.get("_rowsets", {}).get(key) if key is not None else None
-                if hit is not None and hit[0] == gen and hit[1] is index:
-                    count, rowset, wanted = hit[2], hit[3], None
-                else:
-                    wanted = self._get_filtered_indices(metadata_filter, exclude_filter, or_filters)
-                    count, rowset = len(wanted), None
-            if not count or index is None:
-                return [0] * nq if count_only else [[] for _ in range(nq)]
+
+        def search(index, count, rowset):
             if not hasattr(index, "range_search"):
                 raise NotImplementedError(f"{type(index).__name__} has no range search")
-            try:
-                if count != n_rows and rowset is None:
-                    rowset = self._resident_rowset(index, wanted, key, gen)
-                if count_only:
-                    return [int(c) for c in index.range_count(query, min_score, rowset=rowset, normalize_q=True)]
-                lims, scores, rows = index.range_search(query, min_score, rowset=rowset, normalize_q=True)
-                break
-            except ValueError:
-                # another thread deleted rows between the filter and the search: evaluate the filter again on the current rows
-                if attempt == 2:
-                    raise
+            rs = rowset()
+            if count_only:
+                return [int(c) for c in index.range_count(query, min_score, rowset=rs, normalize_q=True)]
+            return index.range_search(query, min_score, rowset=rs, normalize_q=True)
+
+        found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        if found is None:
+            return [0] * nq if count_only else [[] for _ in range(nq)]
+        if count_only:
+            return found
+        lims, scores, rows = found
         return [[(int(r), s) for r, s in zip(rows[lims[i]:lims[i + 1]], scores[lims[i]:lims[i + 1]])] for i in range(nq)]
+
+    # ---- MMR search: k results that are relevant and unlike each other ------------------------------------------
+    MMR_MAX_FETCH = 1024   # most candidates the device selection takes (include/mvdb.h "MMR SEARCH")
+
+    def find_most_similar_mmr(self, embedding, k=5, fetch_k=None, lambda_mult=0.5, metadata_filter=None, exclude_filter=None,
+                              or_filters=None):
+        """`k` results picked for relevance AND diversity (maximal marginal relevance) instead of the k best, which on a
+        corpus with near-duplicates are k copies of one passage: of the `fetch_k` best rows under the filters of
+        ``find_most_similar`` (default ``max(4 * k, 20)``), the best one, then repeatedly the row that maximises
+        ``lambda_mult * score - (1 - lambda_mult) * (largest cosine to a row already picked)``.  ``lambda_mult=1`` is
+        ``find_most_similar(k=k)``, 0 looks at diversity alone.  No reference counterpart (its ``autocut`` and
+        ``hybrid_rerank_results`` work on a fixed top-k after the fact).  The rows never leave the device: the selection
+        is one launch behind the search.  Returns ``(ids, distances, metadatas)`` in SELECTION order, packaged as
+        ``find_most_similar`` does without autocut; the distances are the rows' search scores.  `k` and `fetch_k` are
+        clamped to the number of rows the filters select, `fetch_k` also to 1024; ``k > fetch_k`` after that is a ValueError."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        return self.find_most_similar_mmr_batch(query, k, fetch_k, lambda_mult, metadata_filter, exclude_filter, or_filters)[0]
+
+    def find_most_similar_mmr_batch(self, embeddings, k=5, fetch_k=None, lambda_mult=0.5, metadata_filter=None,
+                                    exclude_filter=None, or_filters=None):
+        """Several queries under ONE filter: element i is what ``find_most_similar_mmr(embeddings[i], ...)`` returns."""
+        queries = self._range_queries(embeddings)
+        nq = queries.shape[0]
+        k = int(k)
+        fetch_k = max(4 * k, 20) if fetch_k is None else int(fetch_k)
+        lambda_mult = float(lambda_mult)
+        if k < 1 or fetch_k < 1:
+            raise ValueError("k and fetch_k must be positive")
+        if not 0.0 <= lambda_mult <= 1.0:
+            raise ValueError(f"lambda_mult must lie in [0, 1] (got {lambda_mult})")
+        if nq == 0 or self._mat is None:
+            return [([], [], []) for _ in range(nq)]
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_mmr"):
+                raise NotImplementedError(f"{type(index).__name__} has no MMR search")
+            take, fetch = min(k, count), min(fetch_k, count, self.MMR_MAX_FETCH)
+            if take > fetch:
+                raise _MmrShape(f"k = {take} exceeds fetch_k = {fetch} (fetch_k is clamped to {self.MMR_MAX_FETCH})")
+            return index.search_mmr(queries, take, fetch, lambda_mult, rowset=rowset(), normalize_q=True)
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _MmrShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            return [([], [], []) for _ in range(nq)]
+        scores, rows = found
+        uids = self._ids.uids
+        out = []
+        for i in range(nq):
+            hits = []
+            for row, score in zip(rows[i], scores[i]):
+                if row == -1:
+                    continue
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, False))
+        return out
 
     # ---- a batch in which every query brings its own filter -------------------------------------------------
     _EACH_FILTER_KEYS = ("metadata_filter", "exclude_filter", "or_filters")

@@ -117,6 +117,11 @@ PROTOTYPES = {
                                                            ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_range_band": (ctypes.c_double, [ctypes.c_int, ctypes.c_float, ctypes.c_float]),
     "mvdb_index_range_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_mmr": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                             c_vp, c_vp, c_vp]),
+    "mvdb_index_search_mmr_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                    ctypes.c_int, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_mmr_form": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -603,6 +608,46 @@ class FlatIndex:
             self._h, ctypes.c_void_p(q_ptr), int(nq), float(threshold), int(bool(normalize_q)),
             rowset._h if rowset is not None else None, int(cap), int(label_offset), ctypes.c_void_p(counts_ptr),
             ctypes.c_void_p(D_ptr) if D_ptr else None, ctypes.c_void_p(I_ptr) if I_ptr else None, ctypes.c_void_p(stream)))
+
+    # ---- MMR search: k diverse rows picked on the device from the top fetch_k (include/mvdb.h "MMR SEARCH") ----------
+    MMR_MAX_FETCH = 1024
+
+    def search_mmr(self, q, k, fetch_k, lambda_mult, rowset=None, normalize_q=False, out=None):
+        """(D float32[nq, k], I int64[nq, k]): per query k of the `fetch_k` best rows (of the row set, if one is given), picked
+        greedily by lambda_mult * relevance - (1 - lambda_mult) * (largest inner product with a row already picked), in
+        selection order; D holds the rows' search scores, labels are ROW NUMBERS, a short row ends in -1 / -FLT_MAX.
+        out=(D, I): caller-owned result arrays (float32 / int64, [nq, k], C-contiguous)."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        nq, k = q.shape[0], int(k)
+        if out is None:
+            D = np.empty((nq, max(k, 0)), dtype=np.float32)
+            I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        else:
+            D, I = out
+            if (D.dtype != np.float32 or I.dtype != np.int64 or D.shape != (nq, k) or I.shape != (nq, k)
+                    or not D.flags.c_contiguous or not I.flags.c_contiguous):
+                raise ValueError("out must be C-contiguous (float32[nq, k], int64[nq, k])")
+        check(lib().mvdb_index_search_mmr(self._h, _ptr(q), nq, k, int(fetch_k), float(lambda_mult), int(bool(normalize_q)),
+                                          rowset._h if rowset is not None else None, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_mmr_device(self, q_ptr, nq, k, fetch_k, lambda_mult, D_ptr, I_ptr, rowset=None, stream=0, normalize_q=False,
+                          label_offset=0):
+        """Device-pointer variant of search_mmr (labels: row numbers + label_offset); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_search_mmr_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(fetch_k), float(lambda_mult), int(bool(normalize_q)),
+            rowset._h if rowset is not None else None, int(label_offset), ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            ctypes.c_void_p(stream)))
+
+    @staticmethod
+    def mmr_form(d, fetch_k, device=0):
+        """0: the selection holds the fetch_k candidate rows in LDS; 1: it streams them from the matrix at every step."""
+        form = int(lib().mvdb_mmr_form(int(d), int(fetch_k), int(device)))
+        if form < 0:
+            check(-form)
+        return form
 
 
 class RowSet:

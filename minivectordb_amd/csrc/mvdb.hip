@@ -19,6 +19,7 @@
 #include "scan_kernels.hpp"
 #include "grouped_scan.hpp"
 #include "range_scan.hpp"
+#include "mmr_select.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
@@ -292,6 +293,8 @@ struct Workspace {
     DevBuf<uint32_t> rcand;              // range search, shared pass: [nq, capacity] candidate rows ...
     DevBuf<unsigned long long> rccount;  // ... and their per-query counters
     DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
+    DevBuf<float> mmrD;                  // MMR search: stage 1's candidates of one tile of queries, [min(nq, kCoreTile), fetch_k] ...
+    DevBuf<int64_t> mmrI;                // ... scores and row numbers (mmr_select.hpp)
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -3717,6 +3720,122 @@ int mvdb_index_range_search_each_device(const mvdb_index* idx, const float* q_de
                                         int64_t* I_dev, void* stream) {
     if (!thresholds_dev) return fail(MVDB_ERR_ARG, "NULL buffer passed to range search");
     return range_search_dev(idx, q_dev, nq, 0.f, thresholds_dev, normalize_q, rs, cap, label_offset, counts_dev, D_dev, I_dev, stream);
+}
+
+}  // extern "C"
+
+// ---- MMR search: k diverse rows picked on the device from the top fetch_k (mmr_select.hpp) --------------------------------
+namespace {
+
+// LDS one workgroup may ask for on `device` (remembered)
+size_t device_lds_per_block(int device) {
+    static std::mutex mu;
+    static std::map<int, size_t> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(device);
+    if (it != cache.end()) return it->second;
+    int bytes = 0;
+    if (hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || bytes <= 0) bytes = 64 << 10;
+    return cache[device] = (size_t)bytes;
+}
+
+// THE rule of the two forms, from the row stride, fetch_k and the device's LDS alone: 0 where the candidates' rows and the
+// per-candidate arrays fit the budget — seven eighths of the LDS a workgroup may have (140 of 160 KiB: 64 rows of 512 floats
+// fit, 1024 rows of 32 do not; the selection then has the CU to itself) —, else 1; -1 where not even one row fits beside
+// the arrays.
+int mmr_form_rule(int64_t ld, int fetch_k, size_t lds_per_block) {
+    const size_t budget = lds_per_block - lds_per_block / 8;
+    if (mmr_lds_bytes(0, fetch_k, ld) + kMmrStaticLds <= budget) return 0;
+    if (mmr_lds_bytes(1, fetch_k, ld) + kMmrStaticLds <= lds_per_block) return 1;
+    return -1;
+}
+
+int check_mmr_args(const mvdb_index* idx, const void* q, int nq, int k, int fetch_k, float lambda, const void* D, const void* I) {
+    MVDB_TRY(check_search_args(idx, q, nq, k, D, I));
+    if (fetch_k < k || fetch_k > kMmrMaxFetch)
+        return fail(MVDB_ERR_ARG, "MMR search needs k <= fetch_k <= %d (got k = %d, fetch_k = %d)", kMmrMaxFetch, k, fetch_k);
+    if (!(lambda >= 0.f && lambda <= 1.f)) return fail(MVDB_ERR_ARG, "lambda must lie in [0, 1] (got %g)", (double)lambda);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "MMR search needs an inner-product index");
+    return 0;
+}
+
+// Queries on the device at stride ld, results to device buffers: per tile of kCoreTile queries the candidate search
+// (search_core / rowset_search_core with label_offset 0, into the workspace) and one launch of the selection behind it.
+int mmr_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int fetch_k, float lambda, int normalize_q,
+             const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    const int form = mmr_form_rule(idx->ld, fetch_k, device_lds_per_block(idx->device));
+    if (form < 0) return fail(MVDB_ERR_ARG, "MMR search: a row of %d floats does not fit the device's LDS", idx->d);
+    const size_t lds = mmr_lds_bytes(form, fetch_k, idx->ld);
+    void (*kern)(MmrArgs) = form == 0 ? mmr_select_kernel<0> : mmr_select_kernel<1>;
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, idx->device));
+    const size_t tile = (size_t)std::min(nq, kCoreTile);
+    MVDB_TRY(ws->mmrD.reserve(tile * fetch_k));
+    MVDB_TRY(ws->mmrI.reserve(tile * fetch_k));
+    MmrArgs a;
+    a.X = idx->X.p;
+    a.ld = idx->ld;
+    a.candD = ws->mmrD.p;
+    a.candI = ws->mmrI.p;
+    a.fetch_k = fetch_k;
+    a.k = k;
+    a.lambda = lambda;
+    a.mu = 1.f - lambda;
+    a.label_offset = label_offset;
+    for (int t0 = 0; t0 < nq; t0 += kCoreTile) {
+        const int take = std::min(kCoreTile, nq - t0);
+        const float* qt = q + (int64_t)t0 * idx->ld;
+        if (rs) MVDB_TRY(rowset_search_core(idx, ws, qt, take, fetch_k, normalize_q, rs, 0, ws->mmrD.p, ws->mmrI.p));
+        else MVDB_TRY(search_core(idx, ws, qt, take, fetch_k, normalize_q, nullptr, 0, 0, ws->mmrD.p, ws->mmrI.p));
+        a.D = D_dev + (int64_t)t0 * k;
+        a.I = I_dev + (int64_t)t0 * k;
+        MVDB_TRY(profiled_launch("mmr_select", ws->stream,
+                                 [&] { hipLaunchKernelGGL(kern, dim3((unsigned)take), dim3(kMmrThreads), lds, ws->stream, a); },
+                                 "mmr_select_kernel<%d>", form));
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_search_mmr(const mvdb_index* idx, const float* q_host, int nq, int k, int fetch_k, float lambda, int normalize_q,
+                          const mvdb_rowset* rs, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_mmr_args(idx, q_host, nq, k, fetch_k, lambda, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(mmr_core(idx, call.ws, call.ws->q.p, nq, k, fetch_k, lambda, normalize_q, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_mmr_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int fetch_k, float lambda,
+                                 int normalize_q, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                                 void* stream) {
+    MVDB_TRY(check_mmr_args(idx, q_dev, nq, k, fetch_k, lambda, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
+    return mmr_core(idx, call.ws, call.q, nq, k, fetch_k, lambda, normalize_q, rs, label_offset, D_dev, I_dev);
+}
+
+int mvdb_mmr_form(int d, int fetch_k, int device) {
+    if (d <= 0) return -fail(MVDB_ERR_ARG, "d must be positive (got %d)", d);
+    if (fetch_k < 1 || fetch_k > kMmrMaxFetch) return -fail(MVDB_ERR_ARG, "fetch_k must lie in [1, %d] (got %d)", kMmrMaxFetch, fetch_k);
+    if (const int rc = ensure_device(device)) return -rc;
+    const int form = mmr_form_rule(((int64_t)d + 3) / 4 * 4, fetch_k, device_lds_per_block(device));
+    if (form < 0) return -fail(MVDB_ERR_ARG, "MMR search: a row of %d floats does not fit the device's LDS", d);
+    return form;
 }
 
 }  // extern "C"

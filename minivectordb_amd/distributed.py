@@ -556,3 +556,13 @@ class DistributedShardedVectorDatabase:
 
     def count_similar_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RANGE)
+
+    # ---- MMR search: not across ranks ---------------------------------------------------------------------------
+    _NO_MMR = ("DistributedShardedVectorDatabase has no MMR search: the selection compares stored rows with each other, and "
+               "the candidates of one query live on several ranks (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_mmr(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MMR)
+
+    def find_most_similar_mmr_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MMR)

@@ -155,3 +155,13 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
 
     def count_similar_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RANGE)
+
+    # ---- MMR search: not on the int8 cosine index -----------------------------------------------------------------
+    _NO_MMR = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: MMR search, whose selection takes "
+               "inner products of stored fp32 rows, is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_mmr(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MMR)
+
+    def find_most_similar_mmr_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MMR)
