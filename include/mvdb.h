@@ -484,6 +484,56 @@ int mvdb_index_search_mmr_device(const mvdb_index* idx, const float* q_dev, int 
                                  float* D_dev, int64_t* I_dev, void* stream);
 int mvdb_mmr_form(int d, int fetch_k, int device);   /* 0 = candidates held in LDS, 1 = streamed; < 0 = error */
 
+/* DISTINCT SEARCH: the best row of each GROUP of stored rows, the k best groups — "the k best documents" of a store whose
+ * documents are chunked into several rows.  Inner-product indexes only.
+ * Grouping.  One int32 group code per stored row, resident on the index's device (4 bytes per row).  n must equal
+ * mvdb_index_ntotal, every code must lie in [0, n_groups), 1 <= n_groups <= n: anything else is MVDB_ERR_ARG before any
+ * allocation (the host array is checked on the host).  n == 0 gives an empty grouping without device memory, for an empty
+ * index.  A grouping belongs to the index state it was built against: a search refuses it with MVDB_ERR_ARG, before anything
+ * is enqueued and with nothing written, when it belongs to another index, when rows were added since (the row count
+ * differs) or when rows were removed since.  mvdb_index_set_rows renumbers nothing: the grouping stays valid.  There is no
+ * extend call: re-creating a grouping after a write is one upload (4 MB per million rows).
+ * Contract, per query i.  m: the rows selected (ntotal, or mvdb_rowset_size(rs)).  R_i: row i of what mvdb_index_search
+ * (rs == NULL) or mvdb_index_search_rowset returns for the same (q, nq, fetch_k, normalize_q) — its routing, bits, tie order
+ * and -1 padding; v: its valid entries, g: the distinct codes among them.  The COLLAPSE of a ranking keeps, in order, the
+ * first entry of every group.
+ *   Tier 1 (g >= k, or v < fetch_k, or fetch_k >= m): the first k entries of the collapse of R_i, bit for bit.  Exact: a
+ *   group absent from R_i has no row above R_i's last score, so the k best groups are the first k it holds, each by its best
+ *   row; and an R_i that is not full, or covers the selection, is the whole ranking.
+ *   Tier 2 (otherwise: R_i is full, does not cover the selection and holds fewer than k groups — one document fills the
+ *   fetch): the first k entries of the collapse of the FULL ranking of the selected rows, i.e. of what mvdb_index_search /
+ *   mvdb_index_search_rowset returns for query i alone with nq = 1 and k = m on the default routing: the scores are bit for
+ *   bit the single-query scan's, ties go to the lower row number (an unsorted row list: the lower list position), rows whose
+ *   score is NaN are never results.
+ *   In a batch, a tier-2 query therefore carries the single-query scan's bits while its tier-1 neighbours carry the bits of
+ *   the route the batch took.
+ * Output.  I [nq,k]: row numbers (+ label_offset in the device variant), best group first; D [nq,k]: their scores; G [nq,k]
+ * (may be NULL): their group codes.  Fewer than k groups: padded with -1 / -FLT_MAX / -1.  Reproducible run to run.
+ * Arguments.  1 <= k <= 64 (tier 2 keeps one result per lane of a wave), k <= fetch_k <= 1024; an L2 index: MVDB_ERR_ARG;
+ * rs == NULL: every row, else a resident row set of any form, checked as every row-set search checks it; an empty index or
+ * set: all missing markers.
+ * Cost.  The candidate search, then ONE launch, a workgroup per query, that reads no row of the matrix.  Behind it, unless
+ * fetch_k >= m, three launches per T queries that cost a query answered by tier 1 nothing: they clear, fill and read a
+ * table of T x n_groups x 8 bytes, T = max(1, min(queries, budget / (8 n_groups))), budget = index option
+ * "distinct_table_bytes" (default 256 MiB).  A tier-2 query costs one exact scan of the selected rows + 4 bytes per row.
+ * The device variant follows the contract of mvdb_index_search_device: no synchronisation, no host read, one call at a time
+ * per (index, stream), capturable into a hipGraph after one eager call of the same shape (same grouping, same set).
+ * mvdb_index_distinct_counters: calls served (counted on the host) and queries tier 2 answered (a running total, read
+ * without synchronising: the device-side word lags by the calls in flight).  Either pointer may be NULL.
+ * No reference counterpart. */
+typedef struct mvdb_grouping mvdb_grouping;
+int mvdb_grouping_create(const mvdb_index* idx, const int32_t* codes_host /*[n]*/, int64_t n, int64_t n_groups, mvdb_grouping** out);
+int64_t mvdb_grouping_rows(const mvdb_grouping* g);
+int64_t mvdb_grouping_groups(const mvdb_grouping* g);
+int mvdb_grouping_free(mvdb_grouping* g);
+int mvdb_index_search_distinct(const mvdb_index* idx, const float* q_host, int nq, int k, int fetch_k, int normalize_q,
+                               const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_host, int64_t* I_host,
+                               int32_t* G_host /* [nq,k] or NULL */);
+int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int fetch_k, int normalize_q,
+                                      const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_dev, int64_t* I_dev,
+                                      int32_t* G_dev /* [nq,k] or NULL */, int64_t label_offset, void* stream);
+int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long long* fallback_queries);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be
@@ -528,7 +578,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * When enabled, every launch of the dominant kernels is bracketed by hipEvents on the launch
  * stream.  mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "encoder") and returns the number of launches and their summed duration.
+ * "distinct_collapse", "distinct_scan", "distinct_select", "encoder") and returns the number of launches and their summed duration.
  * Turning profiling on while it was off forgets the symbols recorded so far (mvdb_prof_symbol): after it, a label under which
  * nothing has been launched since reads "", not the symbol of an earlier bracket. */
 int mvdb_prof_enable(int on);

@@ -469,6 +469,10 @@ class _MmrShape(Exception):
     """k > fetch_k after clamping: not a ValueError on its way out of the search, which would read as a stale row set."""
 
 
+class _DistinctShape(Exception):
+    """k > 64 after clamping: not a ValueError on its way out of the search, which would read as a stale object."""
+
+
 class FilterAndRerankMixin:
     """Needs: self.inverted_index, self._ids (_IdIndex), self.metadata, self.hash_vectorizer, self._mat (_RowStore),
     self.index, self.embedding_size, self._device, self.lock."""
@@ -843,6 +847,121 @@ class FilterAndRerankMixin:
                     pass
             out.append(self._package(hits, False))
         return out
+
+    # ---- distinct search: the best row of each metadata group, the k best groups ----------------------------
+    DISTINCT_MAX_K = 64        # most groups one call returns (include/mvdb.h "DISTINCT SEARCH")
+    DISTINCT_MAX_FETCH = 1024  # most candidates its first tier collapses
+    _GROUPINGS_KEPT = 4        # metadata keys whose codes stay resident
+
+    def find_most_similar_distinct(self, embedding, group_by, k=5, fetch_k=None, metadata_filter=None, exclude_filter=None,
+                                   or_filters=None):
+        """The `k` best GROUPS under the filters of ``find_most_similar``, each represented by its best row — "the k best
+        documents" of a store whose documents are chunked into several rows, where ``find_most_similar(k=5)`` often returns
+        five chunks of one document.  `group_by` is a metadata key: rows whose value under it compares equal as a dict key
+        form one group; a row without the key is a group of its own (no row is silently dropped); an unhashable value is a
+        TypeError naming the id.  The answer is EXACT whatever `fetch_k` is (default ``max(4 * k, 32)``): it only sizes the
+        cheap first tier — a query whose `fetch_k` best rows hold fewer than `k` groups (one document fills the fetch) is
+        answered by one pass over the selected rows on the device.  No reference counterpart.  Returns ``(ids, distances,
+        metadatas)``, best group first, packaged as ``find_most_similar`` does without autocut.  `fetch_k` is clamped to 1024
+        and to the number of rows the filters select, `k` to that number; ``k > 64`` after that is a ValueError."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        return self.find_most_similar_distinct_batch(query, group_by, k, fetch_k, metadata_filter, exclude_filter, or_filters)[0]
+
+    def find_most_similar_distinct_batch(self, embeddings, group_by, k=5, fetch_k=None, metadata_filter=None,
+                                         exclude_filter=None, or_filters=None):
+        """Several queries under ONE filter: element i is what ``find_most_similar_distinct(embeddings[i], ...)`` returns."""
+        queries = self._range_queries(embeddings)
+        nq = queries.shape[0]
+        k = int(k)
+        fetch_k = max(4 * k, 32) if fetch_k is None else int(fetch_k)
+        if k < 1 or fetch_k < 1:
+            raise ValueError("k and fetch_k must be positive")
+        if fetch_k < k:
+            raise ValueError(f"k = {k} exceeds fetch_k = {fetch_k}")
+        hash(group_by)  # (a metadata key: an unhashable one is the caller's TypeError, before anything is searched)
+        if nq == 0 or self._mat is None:
+            return [([], [], []) for _ in range(nq)]
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_distinct"):
+                raise NotImplementedError(f"{type(index).__name__} has no distinct search")
+            take = min(k, count)
+            if take > self.DISTINCT_MAX_K:
+                raise _DistinctShape(f"k = {take} exceeds {self.DISTINCT_MAX_K}, the most groups a distinct search returns")
+            fetch = max(take, min(fetch_k, count, self.DISTINCT_MAX_FETCH))
+            grouping = self._resident_grouping(index, group_by)   # (an unhashable value: its TypeError is not retried)
+            return index.search_distinct(queries, take, fetch, grouping, rowset=rowset(), normalize_q=True)
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            return [([], [], []) for _ in range(nq)]
+        scores, rows = found[0], found[1]
+        uids = self._ids.uids
+        out = []
+        for i in range(nq):
+            hits = []
+            for row, score in zip(rows[i], scores[i]):
+                if row == -1:
+                    continue
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, False))
+        return out
+
+    def _group_codes(self, group_by):
+        """One pass over the metadata (under the lock): an int32 code per row and the value -> code dict.  Rows that share a
+        value share a code; a row without the key gets a code of its own."""
+        n = len(self.metadata)
+        codes = np.empty(n, dtype=np.int32)
+        table = {}
+        nxt = 0
+        for row, meta in enumerate(self.metadata):
+            if group_by in meta:
+                value = meta[group_by]
+                try:
+                    code = table.get(value)
+                except TypeError:
+                    raise TypeError(f"the value of {group_by!r} of id {self._ids.uids[row]!r} is unhashable "
+                                    f"({type(value).__name__}): it cannot name a group") from None
+                if code is None:
+                    code = table[value] = nxt
+                    nxt += 1
+            else:
+                code = nxt
+                nxt += 1
+            codes[row] = code
+        return codes, table, nxt
+
+    def _resident_grouping(self, index, group_by):
+        """The device-resident group codes of `group_by` (`mvdb_grouping`), cached per key — at most four keys — and stamped
+        with the write generation and the index object: any store, delete or metadata update since makes the next use build
+        the codes again with one pass over the metadata and upload them once (4 bytes per row).  A ValueError where the
+        device index is no longer the state the metadata describes: `_search_selected` starts over."""
+        with self.lock:
+            if self._embeddings_changed or self.index is not index:
+                raise ValueError("the index changed between the filter and the search")
+            gen = self.__dict__.get("_write_gen", 0)
+            cache = self.__dict__.get("_groupings")
+            if cache is None:
+                cache = self.__dict__["_groupings"] = OrderedDict()
+            hit = cache.get(group_by)
+            if hit is not None and hit[0] == gen and hit[1] is index:
+                cache.move_to_end(group_by)
+                return hit[2]
+            codes, table, n_groups = self._group_codes(group_by)
+            grouping = index.grouping(codes, n_groups)
+            # an outdated entry is dropped, not freed: a search running outside the lock may still hold it (its device
+            # memory goes when the last reference does)
+            cache[group_by] = (gen, index, grouping, codes, table)
+            cache.move_to_end(group_by)
+            while len(cache) > self._GROUPINGS_KEPT:
+                cache.popitem(last=False)
+            return grouping
 
     # ---- a batch in which every query brings its own filter -------------------------------------------------
     _EACH_FILTER_KEYS = ("metadata_filter", "exclude_filter", "or_filters")

@@ -122,6 +122,15 @@ PROTOTYPES = {
     "mvdb_index_search_mmr_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                                     ctypes.c_int, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_mmr_form": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mvdb_grouping_create": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(c_vp)]),
+    "mvdb_grouping_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_grouping_groups": (ctypes.c_int64, [c_vp]),
+    "mvdb_grouping_free": (ctypes.c_int, [c_vp]),
+    "mvdb_index_search_distinct": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                  c_vp, c_vp, c_vp]),
+    "mvdb_index_search_distinct_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                                         c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "mvdb_index_distinct_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -648,6 +657,72 @@ class FlatIndex:
         if form < 0:
             check(-form)
         return form
+
+    # ---- distinct search: the best row of each group, the k best groups (include/mvdb.h "DISTINCT SEARCH") ----------
+    def grouping(self, codes, n_groups):
+        """A resident Grouping: one int32 group code in [0, n_groups) per stored row."""
+        return Grouping(self, codes, n_groups)
+
+    def search_distinct(self, q, k, fetch_k, grouping, rowset=None, normalize_q=False):
+        """(D float32[nq, k], I int64[nq, k], G int32[nq, k]): per query the best row of each of the k best groups (of the row
+        set, if one is given), best group first; exact whatever fetch_k is (a query whose fetch_k candidates hold fewer than k
+        groups is answered by one pass over the selected rows).  Labels are ROW NUMBERS, G their group codes; a short row ends
+        in -1 / -FLT_MAX / -1."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        nq, k = q.shape[0], int(k)
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        G = np.empty((nq, max(k, 0)), dtype=np.int32)
+        check(lib().mvdb_index_search_distinct(self._h, _ptr(q), nq, k, int(fetch_k), int(bool(normalize_q)), grouping._h,
+                                               rowset._h if rowset is not None else None, _ptr(D), _ptr(I), _ptr(G)))
+        return D, I, G
+
+    def search_distinct_device(self, q_ptr, nq, k, fetch_k, grouping, D_ptr, I_ptr, G_ptr=0, rowset=None, stream=0,
+                               normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_distinct (labels: row numbers + label_offset; G_ptr 0: no group codes); enqueues on
+        `stream` and returns."""
+        check(lib().mvdb_index_search_distinct_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(fetch_k), int(bool(normalize_q)), grouping._h,
+            rowset._h if rowset is not None else None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            ctypes.c_void_p(G_ptr) if G_ptr else None, int(label_offset), ctypes.c_void_p(stream)))
+
+    def distinct_counters(self):
+        """(distinct searches served, queries their one-pass tier answered): running totals, read without synchronising."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_distinct_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+
+class Grouping:
+    """mvdb_grouping*: one int32 group code per stored row, resident on the index's device.  Valid until the index it was
+    built on gains or loses a row (updating rows in place keeps it valid)."""
+
+    def __init__(self, index, codes, n_groups):
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if codes.ndim != 1:
+            raise ValueError("codes must be one-dimensional")
+        self._h = ctypes.c_void_p()
+        check(lib().mvdb_grouping_create(index._h, _ptr(codes), codes.shape[0], int(n_groups), ctypes.byref(self._h)))
+
+    def __len__(self):
+        return int(lib().mvdb_grouping_rows(self._h))
+
+    @property
+    def n_groups(self):
+        return int(lib().mvdb_grouping_groups(self._h))
+
+    def free(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_grouping_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class RowSet:

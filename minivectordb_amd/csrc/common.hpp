@@ -112,6 +112,7 @@ struct Knobs {
     int range_shared = 0;              // index option range_shared: batches of a range search on the shared fp16 pass (0 never — the default until the
                                        // route has been timed, DESIGN.md section 6e —, 1 by size, 2 wherever eligible)
     long long range_candidates = 0;    // index option range_candidates: candidates per query that pass holds (0: max(2 cap rounded up to a power of two, 4096))
+    long long distinct_table_bytes = 256ll << 20;  // index option distinct_table_bytes: budget of the distinct search's tier-2 table (mvdb.hip: distinct_core)
     int grouped_items_per_cu = 0;      // MVDB_GROUPED_ITEMS_PER_CU: work items per CU the grouped launch aims at (0: the default of mvdb.hip plan_grouped; sweep in DESIGN.md section 6c)
     int grouped_min_batches = 4;       // MVDB_GROUPED_MIN_BATCHES: fewest row batches per wave of a work item
     long long compact_bytes = 512ll << 20;  // MVDB_COMPACT_BYTES: staging buffer of a row compaction (mvdb_index_remove_rows)

@@ -20,6 +20,7 @@
 #include "grouped_scan.hpp"
 #include "range_scan.hpp"
 #include "mmr_select.hpp"
+#include "distinct_select.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
@@ -295,6 +296,9 @@ struct Workspace {
     DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
     DevBuf<float> mmrD;                  // MMR search: stage 1's candidates of one tile of queries, [min(nq, kCoreTile), fetch_k] ...
     DevBuf<int64_t> mmrI;                // ... scores and row numbers (mmr_select.hpp)
+    DevBuf<int> dneed;                   // distinct search: kCoreTile need words of one tile of queries, then the collapse launch's ticket
+    DevBuf<uint64_t> dtab;               // ... the table of tier 2, [T slots, n_groups] (distinct_select.hpp)
+    DevBuf<int32_t> dG;                  // ... the host entry point's group codes, [nq, k]
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -449,6 +453,10 @@ struct mvdb_index {
     // are counted on the host
     mutable MirroredCounter rg_ctr;
     mutable std::atomic<unsigned long long> rg_shared_calls{0};
+    // distinct search, created by the first call: a running count of the queries tier 2 answered (one device word and its
+    // mirror, written by distinct_collapse_kernel); the calls are counted on the host
+    mutable MirroredCounter ds_ctr;
+    mutable std::atomic<unsigned long long> ds_calls{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -2374,7 +2382,9 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const int code8_front = idx->kn.code8_front_plane;
     const int range_shared = idx->kn.range_shared;
     const long long range_cand = idx->kn.range_candidates;
+    const long long distinct_table = idx->kn.distinct_table_bytes;
     idx->kn = read_knobs();
+    idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
     idx->kn.code8_front_plane = code8_front;
@@ -2414,13 +2424,16 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "range_candidates") {  // candidates per query the shared pass holds (0: by cap); a small value forces the fallback
         if (value != 0 && (value < 64 || value > (1ll << 20))) return fail(MVDB_ERR_ARG, "range_candidates must be 0 or lie in [64, 2^20]");
         idx->kn.range_candidates = value;
+    } else if (n == "distinct_table_bytes") {  // budget of the distinct search's tier-2 table (T slots of 8 n_groups bytes; T >= 1 whatever it is)
+        if (value <= 0) return fail(MVDB_ERR_ARG, "distinct_table_bytes must be positive");
+        idx->kn.distinct_table_bytes = value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, range_candidates, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, range_candidates, distinct_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2481,6 +2494,12 @@ int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, lo
     if (shared_calls) *shared_calls = (long long)idx->rg_shared_calls.load();
     if (fallback_queries) *fallback_queries = (long long)idx->rg_ctr.read<unsigned long long>(0);
     if (last_candidates) *last_candidates = (long long)idx->rg_ctr.read<unsigned long long>(1);
+    return 0;
+}
+int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long long* fallback_queries) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->ds_calls.load();
+    if (fallback_queries) *fallback_queries = (long long)idx->ds_ctr.read(0);
     return 0;
 }
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
@@ -3836,6 +3855,262 @@ int mvdb_mmr_form(int d, int fetch_k, int device) {
     const int form = mmr_form_rule(((int64_t)d + 3) / 4 * 4, fetch_k, device_lds_per_block(device));
     if (form < 0) return -fail(MVDB_ERR_ARG, "MMR search: a row of %d floats does not fit the device's LDS", d);
     return form;
+}
+
+}  // extern "C"
+
+// ---- distinct search: the best row of each group, the k best groups (distinct_select.hpp) ---------------------------------
+struct mvdb_grouping {
+    uint64_t owner = 0;       // serial number of the index the grouping was built on
+    int device = 0;
+    int64_t n = 0;            // the index's row count it was built against: one code per row
+    uint64_t renumbered = 0;  // ... and its renumbering generation
+    int64_t n_groups = 0;
+    int32_t* codes = nullptr; // [n] on the device (none for an empty index)
+};
+
+namespace {
+
+int grouping_check(const mvdb_index* idx, const mvdb_grouping* g) {
+    if (!g) return fail(MVDB_ERR_ARG, "grouping is NULL");
+    if (g->owner != idx->serial) return fail(MVDB_ERR_ARG, "the grouping belongs to another index");
+    // one code per stored row: rows added since have none, rows removed since have renumbered the rest
+    if (g->device != idx->device || g->n != idx->n || g->renumbered != idx->renumbered)
+        return fail(MVDB_ERR_ARG, "the grouping was built for another state of the index (%lld rows then, %lld now)", (long long)g->n,
+                    (long long)idx->n);
+    return 0;
+}
+
+int check_distinct_args(const mvdb_index* idx, const void* q, int nq, int k, int fetch_k, const void* D, const void* I) {
+    MVDB_TRY(check_search_args(idx, q, nq, k, D, I));
+    if (k > kMaxFusedK) return fail(MVDB_ERR_ARG, "distinct search needs k <= %d (got %d)", kMaxFusedK, k);
+    if (fetch_k < k || fetch_k > kDistinctMaxFetch)
+        return fail(MVDB_ERR_ARG, "distinct search needs k <= fetch_k <= %d (got k = %d, fetch_k = %d)", kDistinctMaxFetch, k, fetch_k);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "distinct search needs an inner-product index");
+    return 0;
+}
+
+__global__ void distinct_fill_missing_kernel(float* D, int64_t* I, int32_t* G, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) {
+        D[i] = -3.402823466e+38f;
+        I[i] = -1;
+        if (G) G[i] = -1;
+    }
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_group_best_kern(const GroupBestArgs& a, int slots, int device, hipStream_t stream) {
+    void (*kern)(GroupBestArgs) = group_best_scan_kernel<G, C, U, SEL, MASKED>;
+    // the grid of the single-query scan (launch_scan_kern)
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
+    return profiled_launch("distinct_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks, slots), dim3(kScanThreads), 0, stream, a); },
+                           "group_best_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// the shapes and rows in flight of launch_scan: a score depends on (G, C, MASKED) only
+int launch_group_best(const GroupBestArgs& a, int slots, int device, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);
+            return launch_group_best_kern<S::G, S::C, U, F::SEL, F::MASKED>(a, slots, device, s);
+        });
+    });
+}
+
+// the counter of tier 2: allocated with the first call, never inside a capture
+bool ensure_distinct_stats(const mvdb_index* idx, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(idx->shadow_mu);
+    return idx->ds_ctr.dev() || (!stream_capturing(s) && idx->ds_ctr.ensure(1));
+}
+
+// Queries on the device at stride ld, results to device buffers.  Per tile of kCoreTile queries: the candidate search
+// (search_core / rowset_search_core with label_offset 0, into the workspace), the collapse launch behind it, and — unless
+// the candidates cover the selection, which the host knows — per sub-tile of T slots the three gated launches of tier 2.
+int distinct_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int fetch_k, int normalize_q,
+                  const mvdb_grouping* grp, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev, int32_t* G_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->ds_calls;
+    const int64_t m = rs ? rs->count : idx->n;  // rows selected
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {
+        const int64_t total = (int64_t)nq * k;
+        hipLaunchKernelGGL(distinct_fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, G_dev, total);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    }
+    const bool covers = fetch_k >= m;
+    const size_t tile = (size_t)std::min(nq, kCoreTile);
+    MVDB_TRY(ws->mmrD.reserve(tile * fetch_k));
+    MVDB_TRY(ws->mmrI.reserve(tile * fetch_k));
+    if (!ws->dneed.p) {  // (a fixed size: the ticket behind the need words is zeroed once and left zero by every launch)
+        MVDB_TRY(ws->dneed.reserve((size_t)kCoreTile + 1));
+        MVDB_HIP(hipMemsetAsync(ws->dneed.p, 0, ((size_t)kCoreTile + 1) * sizeof(int), s));
+    }
+    const bool counted = ensure_distinct_stats(idx, s);
+    const int64_t ng = grp->n_groups;
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)tile, idx->kn.distinct_table_bytes / (8 * ng)));
+    if (!covers) MVDB_TRY(ws->dtab.reserve((size_t)T * (size_t)ng));
+
+    DistinctCollapseArgs c;
+    c.candD = ws->mmrD.p;
+    c.candI = ws->mmrI.p;
+    c.codes = grp->codes;
+    c.fetch_k = fetch_k;
+    c.k = k;
+    c.covers = covers ? 1 : 0;
+    c.label_offset = label_offset;
+    c.need = ws->dneed.p;
+    c.ticket = reinterpret_cast<unsigned int*>(ws->dneed.p + kCoreTile);
+    c.ctr = counted ? idx->ds_ctr.dev() : nullptr;
+    c.host = counted ? idx->ds_ctr.mirror() : nullptr;
+    const int cthreads = (fetch_k + kWave - 1) / kWave * kWave;
+
+    GroupBestArgs g;
+    g.X = idx->X.p;
+    g.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : idx->n;
+    g.ld = idx->ld;
+    g.d4 = idx->d4;
+    g.normalize_q = normalize_q;
+    g.rows = rs ? rs->rows : nullptr;
+    g.mask = rs ? rs->mask : nullptr;
+    g.codes = grp->codes;
+    g.table = ws->dtab.p;
+    g.n_groups = ng;
+    DistinctTopkArgs t;
+    t.table = ws->dtab.p;
+    t.n_groups = ng;
+    t.rows = g.rows;
+    t.codes = grp->codes;
+    t.k = k;
+    t.label_offset = label_offset;
+    const int clear_gx = (int)std::max<int64_t>(1, std::min<int64_t>((ng + 2047) / 2048, 1024));
+
+    for (int t0 = 0; t0 < nq; t0 += kCoreTile) {
+        const int take = std::min(kCoreTile, nq - t0);
+        const float* qt = q + (int64_t)t0 * idx->ld;
+        if (rs) MVDB_TRY(rowset_search_core(idx, ws, qt, take, fetch_k, normalize_q, rs, 0, ws->mmrD.p, ws->mmrI.p));
+        else MVDB_TRY(search_core(idx, ws, qt, take, fetch_k, normalize_q, nullptr, 0, 0, ws->mmrD.p, ws->mmrI.p));
+        c.D = D_dev + (int64_t)t0 * k;
+        c.I = I_dev + (int64_t)t0 * k;
+        c.G = G_dev ? G_dev + (int64_t)t0 * k : nullptr;
+        MVDB_TRY(profiled_launch("distinct_collapse", s,
+                                 [&] { hipLaunchKernelGGL(distinct_collapse_kernel, dim3((unsigned)take), dim3(cthreads), 0, s, c); },
+                                 "distinct_collapse_kernel"));
+        if (covers) continue;
+        for (int s0 = 0; s0 < take; s0 += T) {
+            const int slots = std::min(T, take - s0);
+            const int* need = ws->dneed.p + s0;
+            // (the clear runs under the scan's label, as a record of its own: it names no symbol)
+            MVDB_TRY(profiled_launch("distinct_scan", s, [&] {
+                hipLaunchKernelGGL(distinct_clear_kernel, dim3(clear_gx, slots), dim3(256), 0, s, ws->dtab.p, ng, need);
+            }));
+            g.q = qt + (int64_t)s0 * idx->ld;
+            g.need = need;
+            MVDB_TRY(launch_group_best(g, slots, idx->device, s));
+            t.need = need;
+            t.D = c.D + (int64_t)s0 * k;
+            t.I = c.I + (int64_t)s0 * k;
+            t.G = c.G ? c.G + (int64_t)s0 * k : nullptr;
+            MVDB_TRY(profiled_launch("distinct_select", s,
+                                     [&] { hipLaunchKernelGGL(distinct_topk_kernel, dim3((unsigned)slots), dim3(kDistinctThreads), 0, s, t); },
+                                     "distinct_topk_kernel"));
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_grouping_create(const mvdb_index* idx, const int32_t* codes_host, int64_t n, int64_t n_groups, mvdb_grouping** out) {
+    if (!out) return fail(MVDB_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (n > 0 && !codes_host) return fail(MVDB_ERR_ARG, "codes is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (n != idx->n) return fail(MVDB_ERR_ARG, "a grouping needs one code per stored row (%lld codes, %lld rows)", (long long)n, (long long)idx->n);
+    if (n > 0 && (n_groups < 1 || n_groups > n))
+        return fail(MVDB_ERR_ARG, "n_groups must lie in [1, %lld] (got %lld)", (long long)n, (long long)n_groups);
+    int32_t lo = 0, hi = -1;
+    if (n > 0) lo = hi = codes_host[0];
+    for (int64_t i = 1; i < n; ++i) {  // (branch-free: vectorises)
+        lo = codes_host[i] < lo ? codes_host[i] : lo;
+        hi = codes_host[i] > hi ? codes_host[i] : hi;
+    }
+    if (n > 0 && (lo < 0 || hi >= n_groups))
+        return fail(MVDB_ERR_ARG, "group code %d out of range [0,%lld)", (int)(lo < 0 ? lo : hi), (long long)n_groups);
+    DeviceGuard dg(idx->device);
+    mvdb_grouping* g = new mvdb_grouping();
+    g->owner = idx->serial;
+    g->device = idx->device;
+    g->n = n;
+    g->renumbered = idx->renumbered;
+    g->n_groups = n > 0 ? n_groups : 0;
+    if (n > 0) {
+        hipError_t e = hipMalloc((void**)&g->codes, (size_t)n * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpy(g->codes, codes_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (g->codes) (void)hipFree(g->codes);
+            delete g;
+            return fail(MVDB_ERR_HIP, "grouping upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    *out = g;
+    return 0;
+}
+
+int64_t mvdb_grouping_rows(const mvdb_grouping* g) { return g ? g->n : -1; }
+int64_t mvdb_grouping_groups(const mvdb_grouping* g) { return g ? g->n_groups : -1; }
+
+int mvdb_grouping_free(mvdb_grouping* g) {
+    if (!g) return 0;
+    if (g->codes) {
+        DeviceGuard dg(g->device);
+        (void)hipFree(g->codes);
+    }
+    delete g;
+    return 0;
+}
+
+int mvdb_index_search_distinct(const mvdb_index* idx, const float* q_host, int nq, int k, int fetch_k, int normalize_q,
+                               const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_host, int64_t* I_host, int32_t* G_host) {
+    MVDB_TRY(check_distinct_args(idx, q_host, nq, k, fetch_k, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(grouping_check(idx, grp));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    if (G_host) MVDB_TRY(call.ws->dG.reserve(total));
+    MVDB_TRY(distinct_core(idx, call.ws, call.ws->q.p, nq, k, fetch_k, normalize_q, grp, rs, 0, D_dev, I_dev, G_host ? call.ws->dG.p : nullptr));
+    if (G_host) {
+        MVDB_TRY(copy_back(call.ws, call.ws->dG.p, total * sizeof(int32_t), "distinct search"));
+        memcpy(G_host, call.ws->pin_out.p, total * sizeof(int32_t));
+    }
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int fetch_k, int normalize_q,
+                                      const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_dev, int64_t* I_dev, int32_t* G_dev,
+                                      int64_t label_offset, void* stream) {
+    MVDB_TRY(check_distinct_args(idx, q_dev, nq, k, fetch_k, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(grouping_check(idx, grp));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
+    return distinct_core(idx, call.ws, call.q, nq, k, fetch_k, normalize_q, grp, rs, label_offset, D_dev, I_dev, G_dev);
 }
 
 }  // extern "C"

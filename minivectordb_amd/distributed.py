@@ -566,3 +566,13 @@ class DistributedShardedVectorDatabase:
 
     def find_most_similar_mmr_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_MMR)
+
+    # ---- distinct search: not here ---------------------------------------------------------------------------------
+    _NO_DISTINCT = ("DistributedShardedVectorDatabase has no distinct search: the rows of one group live on several ranks, "
+                   "and the per-group maximum is taken on one device (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_distinct(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_DISTINCT)
+
+    def find_most_similar_distinct_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_DISTINCT)

@@ -165,3 +165,13 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
 
     def find_most_similar_mmr_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_MMR)
+
+    # ---- distinct search: not here ---------------------------------------------------------------------------------
+    _NO_DISTINCT = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: distinct search, whose second tier is an exact fp32 pass with a per-group maximum, "
+                   "is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_distinct(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_DISTINCT)
+
+    def find_most_similar_distinct_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_DISTINCT)
