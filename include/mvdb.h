@@ -451,6 +451,37 @@ double mvdb_range_band(int d, float qnorm, float row_norm_bound);
 int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries,
                               long long* last_candidates);
 
+/* RANGE JOIN: which stored rows are near each other — a range search whose queries are stored rows, each matched against
+ * the rows stored BEFORE it, so that every pair is found once, from its later member (duplicate checks over a corpus, or
+ * over the rows a bulk add appended).  The contract is mvdb_index_range_search's, word for word (counts, cap, overflow
+ * markers, cap == 0, ties, labels, NaN rows, stale or foreign sets), with two differences:
+ *   - query i is stored row qrows[i], with its fp32 bits as they sit in the matrix and normalize_q = 0.  It is never
+ *     uploaded; only the row numbers travel.
+ *   - only rows whose row number is below qrows[i] can match.
+ * So counts[i] is the true number of rows j < qrows[i] that are in rs (if given) and whose score reaches the threshold
+ * (inner product: score >= threshold; L2: squared distance <= threshold), and row i of (D, I) lists them best first.  Every
+ * returned score is bit for bit what mvdb_index_range_search returns for the query get_rows(qrows[i]) with normalize_q = 0;
+ * order and labels match too.  qrows may be in any order and may repeat; a query row need not be in rs; rows appended after
+ * rs was created are not in the set, as for every row-set call.
+ * Argument errors are MVDB_ERR_ARG before anything is enqueued, nothing written: NULL buffers (D / I may be NULL with
+ * cap == 0), nq <= 0, a NaN threshold, cap < 0, a row number outside [0, ntotal), a row set of another index.
+ * Corpus passes.  Option "join_shared": 0 never shares — one fp32 pass per query row, ended at the row's own bound (the
+ * correctness baseline); 1 (default) shares where mvdb_index_range_search's batches may (inner product, every row or a
+ * bitmap-form set, an index that keeps an fp16 shadow) from 33 query rows on; 2 wherever the call is eligible.  The default
+ * is 1, not 0 as "range_shared": a join has as many queries as rows, and the per-query route costs rows x rows x d x 4 / 2
+ * bytes.  On the shared route one pass over the shadow per 128 / 256 query rows covers rows [0, largest bound of those
+ * query rows) and admits a row for a query only below the query's bound; the band is mvdb_range_band unchanged (the queries
+ * are not re-normalised), the exact re-score and the per-query fallback (option "range_candidates" sizes the candidate
+ * segments) are the range search's.  Both metrics, every width, padded rows and indexes that hold non-finite rows work,
+ * through the per-query route.  The results are the same bits on every route.
+ * A device-resident, capturable _device variant is out of scope: this entry point reads the counts back before it sorts. */
+int mvdb_index_range_join(const mvdb_index* idx, const int64_t* qrows_host /*[nq] row numbers, each in [0, ntotal)*/, int nq,
+                          float threshold, const mvdb_rowset* rs /*NULL: every row*/, int64_t cap,
+                          int64_t* counts_host /*[nq]*/, float* D_host /*[nq, cap]*/, int64_t* I_host /*[nq, cap]*/);
+/* Diagnostics of the join's shared pass, counters of its own (mvdb_index_range_counters keeps reporting range calls only):
+ * calls that took it, query rows its fallback answered (running total, read without synchronising).  Any pointer may be NULL. */
+int mvdb_index_join_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries);
+
 /* MMR SEARCH (maximal marginal relevance): k rows that are relevant AND unlike each other, picked greedily on the device from
  * the fetch_k best — the answer to a top-k that is k near-copies of one passage.  Inner-product indexes only.
  * Candidates.  The candidates of query i are, bit for bit, row i of what mvdb_index_search (rs == NULL) or

@@ -18,7 +18,7 @@ reference's ``list(set_of_rows)`` (vector_database.py:510) follows CPython's has
 """
 import bisect
 from array import array
-from collections import OrderedDict
+from collections import OrderedDict, defaultdict
 from operator import ge, gt, le, lt, ne
 
 import numpy as np
@@ -611,13 +611,14 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, autocut))
         return out
 
-    def _search_selected(self, metadata_filter, exclude_filter, or_filters, nothing, search):
+    def _search_selected(self, metadata_filter, exclude_filter, or_filters, nothing, search, with_selection=False):
         """What every search under one filter shares: lazy device sync, filter evaluation (or the filter's resident row set,
         found in the cache), and the retry after a concurrent delete.  Returns `nothing` when the filter selects no row (or
         there is no index yet), else ``search(index, count, rowset)`` — `count` rows selected, `rowset()` their resident
         row set, None when they are all the rows.  A ValueError out of `search` (another thread deleted rows between the
         filter and the search; the reference would still be searching its old index object) evaluates the filter again on
-        the current rows, twice at the most."""
+        the current rows, twice at the most.  with_selection: ``search(index, count, rowset, selection)`` — the `_Selection`
+        itself too (the duplicate-pair search takes its query rows from it)."""
         filtered = bool(metadata_filter or exclude_filter or or_filters)
         key = None
         if filtered:
@@ -634,9 +635,11 @@ class FilterAndRerankMixin:
                 hit = self.__dict__.get("_rowsets", {}).get(key) if key is not None else None
                 if hit is not None and hit[0] == gen and hit[1] is index:
                     count, held, wanted = hit[2], hit[3], None
+                    selection = hit[4]
                 else:
                     wanted = self._get_filtered_indices(metadata_filter, exclude_filter, or_filters)
                     count, held = len(wanted), None
+                    selection = wanted
             if not count or index is None:
                 return nothing
 
@@ -646,7 +649,7 @@ class FilterAndRerankMixin:
                 return held if held is not None else self._resident_rowset(index, wanted, key, gen)
 
             try:
-                return search(index, count, rowset)
+                return search(index, count, rowset, selection) if with_selection else search(index, count, rowset)
             except ValueError:
                 # rows were deleted between the filter and the search: evaluate the filter again on the current rows
                 if attempt == 2:
@@ -686,7 +689,7 @@ class FilterAndRerankMixin:
                     cache = self.__dict__.setdefault("_rowsets", {})
                     if len(cache) >= 16:  # a handful of filters in rotation; each holds device memory until its last user drops it
                         cache.clear()
-                    cache[key] = (gen, index, len(wanted), rowset)
+                    cache[key] = (gen, index, len(wanted), rowset, wanted)
         return rowset
 
     # ---- range search: everything at or above a score, instead of the k best --------------------------------
@@ -786,6 +789,102 @@ class FilterAndRerankMixin:
             return found
         lims, scores, rows = found
         return [[(int(r), s) for r, s in zip(rows[lims[i]:lims[i + 1]], scores[lims[i]:lims[i + 1]])] for i in range(nq)]
+
+    # ---- duplicate-pair search: which stored embeddings are near each other -------------------------------------------
+    def find_duplicate_pairs(self, min_score, metadata_filter=None, exclude_filter=None, or_filters=None, first_row=0, limit=None):
+        """Every PAIR of stored embeddings, both inside the filter, whose score is at least `min_score` (cosine: the rows are
+        normalised): ``(ids_earlier, ids_later, scores)``, three parallel lists, best pair first, ties by (storage position of
+        the later member, of the earlier).  Each pair is listed once.  `first_row`: only pairs whose later-stored member sits
+        at storage position >= first_row — pass the store's size from before a bulk add to check only what was added.
+        `limit`: only the best `limit` pairs.  The rows never leave the device: only row numbers go up and pairs come back
+        (a range join, include/mvdb.h "RANGE JOIN").  No reference counterpart."""
+        later, earlier, scores = self._join_pairs(min_score, metadata_filter, exclude_filter, or_filters, first_row, limit)
+        uids = self._ids.uids if len(later) else None
+        a, b, s = [], [], []
+        for r_late, r_early, score in zip(later.tolist(), earlier.tolist(), scores.tolist()):
+            try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                pair = (uids[r_early], uids[r_late])
+            except (KeyError, IndexError):
+                continue
+            a.append(pair[0])
+            b.append(pair[1])
+            s.append(score)
+        return a, b, s
+
+    def count_duplicate_pairs(self, min_score, metadata_filter=None, exclude_filter=None, or_filters=None, first_row=0, limit=None):
+        """``len(find_duplicate_pairs(...)[0])`` without fetching a single pair: counts only come back from the device."""
+        total = self._join_pairs(min_score, metadata_filter, exclude_filter, or_filters, first_row, limit, count_only=True)
+        return total if limit is None else min(total, limit)
+
+    def find_duplicate_groups(self, min_score, metadata_filter=None, exclude_filter=None, or_filters=None, first_row=0, limit=None):
+        """The connected components of the graph ``find_duplicate_pairs`` lists, as lists of ids: each list in storage order,
+        the groups ordered by their first member, singletons left out — keep the first id of each list and drop the rest to
+        deduplicate a store.  A host union-find over the pairs."""
+        later, earlier, _ = self._join_pairs(min_score, metadata_filter, exclude_filter, or_filters, first_row, limit)
+        parent = {}
+
+        def find(r):
+            root = r
+            while parent.setdefault(root, root) != root:
+                root = parent[root]
+            while parent[r] != root:
+                parent[r], r = root, parent[r]
+            return root
+
+        for r_late, r_early in zip(later.tolist(), earlier.tolist()):
+            a, b = find(r_early), find(r_late)
+            if a != b:
+                parent[max(a, b)] = min(a, b)   # the root of a group is its first member
+        members = defaultdict(list)
+        for r in sorted(parent):
+            members[find(r)].append(r)
+        uids = self._ids.uids if members else None
+        groups = []
+        for root in sorted(members):
+            try:
+                groups.append([uids[r] for r in members[root]])
+            except (KeyError, IndexError):
+                pass
+        return groups
+
+    def _join_pairs(self, min_score, metadata_filter, exclude_filter, or_filters, first_row, limit, count_only=False):
+        """Device half of the duplicate-pair search: (later rows, earlier rows, scores) as arrays in the order
+        find_duplicate_pairs documents, cut to `limit` — or, count_only, the number of pairs.  The filter becomes the row set
+        through `_search_selected`; the query rows are the selected rows at or above first_row."""
+        min_score = float(min_score)
+        if min_score != min_score:
+            raise ValueError("min_score is NaN")
+        first_row = int(first_row)
+        if first_row < 0:
+            raise ValueError("first_row must not be negative")
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        empty = (np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32))
+        nothing = 0 if count_only else empty
+        if self._mat is None:
+            return nothing
+
+        def search(index, count, rowset, selection):
+            if not hasattr(index, "range_join"):
+                raise NotImplementedError(f"{type(index).__name__} has no range join")
+            if selection.everything:
+                rows = np.arange(min(first_row, selection.n), selection.n, dtype=np.int64)
+            else:
+                rows = selection.materialize()
+                rows = rows[np.searchsorted(rows, first_row):]
+            if rows.shape[0] == 0:
+                return nothing
+            rs = rowset()
+            if count_only:
+                return index.range_join_count(min_score, rows=rows, rowset=rs)
+            qrows, lims, scores, earlier = index.range_join(min_score, rows=rows, rowset=rs)
+            later = np.repeat(qrows, np.diff(lims))
+            order = np.lexsort((earlier, later, -scores.astype(np.float64)))   # best first, then (later, earlier) position
+            if limit is not None:
+                order = order[:limit]
+            return later[order], earlier[order], scores[order]
+
+        return self._search_selected(metadata_filter, exclude_filter, or_filters, nothing, search, with_selection=True)
 
     # ---- MMR search: k results that are relevant and unlike each other ------------------------------------------
     MMR_MAX_FETCH = 1024   # most candidates the device selection takes (include/mvdb.h "MMR SEARCH")

@@ -117,6 +117,8 @@ PROTOTYPES = {
                                                            ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_range_band": (ctypes.c_double, [ctypes.c_int, ctypes.c_float, ctypes.c_float]),
     "mvdb_index_range_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_range_join": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_float, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_join_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_index_search_mmr": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                              c_vp, c_vp, c_vp]),
     "mvdb_index_search_mmr_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
@@ -617,6 +619,87 @@ class FlatIndex:
             self._h, ctypes.c_void_p(q_ptr), int(nq), float(threshold), int(bool(normalize_q)),
             rowset._h if rowset is not None else None, int(cap), int(label_offset), ctypes.c_void_p(counts_ptr),
             ctypes.c_void_p(D_ptr) if D_ptr else None, ctypes.c_void_p(I_ptr) if I_ptr else None, ctypes.c_void_p(stream)))
+
+    # ---- range join: which stored rows are near each other (include/mvdb.h "RANGE JOIN") ----------------------------
+    JOIN_DEFAULT_CAP = 64
+
+    def join_counters(self):
+        """(join calls that took the shared pass, query rows its fallback answered): running totals."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_join_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def range_join_raw(self, qrows, threshold, cap, rowset=None):
+        """One call of mvdb_index_range_join: query i is STORED row qrows[i], matched against the rows below it (of the row
+        set, if one is given).  (counts int64[nq], D float32[nq, cap], I int64[nq, cap]); a row whose count exceeds `cap` has
+        missing markers (-1) and its true count; cap == 0: counts only, D and I are None."""
+        qrows = np.ascontiguousarray(qrows, dtype=np.int64).reshape(-1)
+        nq, cap = qrows.shape[0], int(cap)
+        counts = np.empty(nq, dtype=np.int64)
+        D = np.empty((nq, cap), dtype=np.float32) if cap > 0 else None
+        I = np.empty((nq, cap), dtype=np.int64) if cap > 0 else None
+        check(lib().mvdb_index_range_join(self._h, _ptr(qrows), nq, float(threshold), rowset._h if rowset is not None else None, cap,
+                                          _ptr(counts), _ptr(D) if D is not None else None, _ptr(I) if I is not None else None))
+        return counts, D, I
+
+    def _join_rows(self, first_row, rows):
+        if rows is None:
+            return np.arange(int(first_row), self.ntotal, dtype=np.int64)
+        return np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+
+    def range_join(self, threshold, first_row=0, rows=None, rowset=None, cap=None, block=4096):
+        """Every pair (earlier row, later row) of stored rows that reaches the threshold, found from its later member:
+        (qrows int64[nq], lims int64[nq + 1], D, I) in faiss's range layout — the rows below qrows[i] (of the row set, if one is
+        given) that match it are I[lims[i]:lims[i + 1]], best first, ties to the lower row.  The query rows are `rows`, or every
+        row from `first_row` on; no row is uploaded.  Works through them `block` at a time with a small per-row `cap`
+        (default 64); the rows of a block that overflowed are asked once more with the largest count seen."""
+        qrows = self._join_rows(first_row, rows)
+        cap = self.JOIN_DEFAULT_CAP if cap is None else int(cap)
+        block = int(block)
+        if cap < 0 or block <= 0:
+            raise ValueError("cap must not be negative and block must be positive")
+        lims = np.zeros(qrows.shape[0] + 1, dtype=np.int64)
+        Ds, Is = [], []
+        for b0 in range(0, qrows.shape[0], block):
+            part = qrows[b0:b0 + block]
+            for _ in range(3):
+                counts, D, I = self.range_join_raw(part, threshold, cap, rowset)
+                fits = counts <= cap
+                over = np.flatnonzero(~fits)
+                if over.size:
+                    c2, D2, I2 = self.range_join_raw(part[over], threshold, int(counts[over].max()), rowset)
+                    if not np.array_equal(c2, counts[over]):
+                        continue   # rows were written between the two calls: both again, on the index as it is now
+                keep = np.arange(cap)[None, :] < counts[:, None] if cap > 0 else np.zeros((part.shape[0], 0), dtype=bool)
+                if not over.size:
+                    Ds.append(D[keep] if cap > 0 else np.empty(0, np.float32))
+                    Is.append(I[keep] if cap > 0 else np.empty(0, np.int64))
+                else:
+                    which = {int(i): j for j, i in enumerate(over)}
+                    for i in range(part.shape[0]):
+                        if i in which:
+                            j = which[i]
+                            Ds.append(D2[j, :c2[j]])
+                            Is.append(I2[j, :c2[j]])
+                        else:
+                            Ds.append(D[i, :counts[i]])
+                            Is.append(I[i, :counts[i]])
+                np.cumsum(counts, out=lims[b0 + 1:b0 + 1 + part.shape[0]])
+                lims[b0 + 1:b0 + 1 + part.shape[0]] += lims[b0]
+                break
+            else:
+                raise ValueError("the index kept changing between the two calls of a range join")
+        Dout = np.concatenate(Ds) if Ds else np.empty(0, dtype=np.float32)
+        Iout = np.concatenate(Is) if Is else np.empty(0, dtype=np.int64)
+        return qrows, lims, Dout.astype(np.float32, copy=False), Iout.astype(np.int64, copy=False)
+
+    def range_join_count(self, threshold, first_row=0, rows=None, rowset=None, block=4096):
+        """int: how many pairs range_join would list (no pair is fetched)."""
+        qrows = self._join_rows(first_row, rows)
+        total = 0
+        for b0 in range(0, qrows.shape[0], int(block)):
+            total += int(self.range_join_raw(qrows[b0:b0 + int(block)], threshold, 0, rowset)[0].sum())
+        return total
 
     # ---- MMR search: k diverse rows picked on the device from the top fetch_k (include/mvdb.h "MMR SEARCH") ----------
     MMR_MAX_FETCH = 1024

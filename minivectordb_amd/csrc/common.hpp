@@ -111,6 +111,8 @@ struct Knobs {
     int code8_front_u = 0;             // MVDB_CODE8_FRONT_U: tuning hook, tiles per batch of the front form (4 | 8; 0: the measured default)
     int range_shared = 0;              // index option range_shared: batches of a range search on the shared fp16 pass (0 never — the default until the
                                        // route has been timed, DESIGN.md section 6e —, 1 by size, 2 wherever eligible)
+    int join_shared = 1;               // index option join_shared: the range join on the shared fp16 pass (0 never, 1 by size — the default: a join has
+                                       // as many queries as rows, DESIGN.md section 6j —, 2 wherever eligible)
     long long range_candidates = 0;    // index option range_candidates: candidates per query that pass holds (0: max(2 cap rounded up to a power of two, 4096))
     long long distinct_table_bytes = 256ll << 20;  // index option distinct_table_bytes: budget of the distinct search's tier-2 table (mvdb.hip: distinct_core)
     int grouped_items_per_cu = 0;      // MVDB_GROUPED_ITEMS_PER_CU: work items per CU the grouped launch aims at (0: the default of mvdb.hip plan_grouped; sweep in DESIGN.md section 6c)

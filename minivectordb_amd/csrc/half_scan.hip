@@ -707,8 +707,11 @@ static int launch_h16(int d, int nqpad, const HalfScanArgs& a, int device, hipSt
 // band's accumulation term from growing with d (half_range_eps).  Two chain accumulators in turns and the running total: 48
 // registers whatever NACC is (one accumulator per chain spilled at d = 896 / 1024); the fold of chain c - 2 sits behind the
 // first MFMA of chain c, off the matrix cores' critical path.  NACC = 1 up to d = 512: one chain of d products, as before.
-template <int KT, int KS, int WV, int NST, int NACC>
-__global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeArgs a) {
+// JOIN (join_nominate_h16_kernel, the range join): query q admits rows below a.before[q] only.  The bound is one more register
+// per lane, loaded and pinned in the prologue with the floor; it is looked at in the slow path alone, where the bitmap word and
+// the corpus end are — the fast path stays at 16 multiply-compares and one ballot.
+template <int KT, int KS, int WV, int NST, int NACC, bool JOIN>
+__device__ __forceinline__ void range_nominate_body(const HalfRangeArgs& a) {
     static_assert(KT % NACC == 0, "whole MFMAs per accumulator");
     constexpr int K = KT * 16;
     constexpr int NSTG = KT / KS;
@@ -735,6 +738,13 @@ __global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeAr
 #pragma unroll
     for (int kb = 0; kb < KT; ++kb) asm volatile("" : "+v"(Q[kb]));
     asm volatile("" : "+v"(fl), "+v"(inv));
+    // (row numbers are 32-bit here — the candidate segments hold uint32 —, so the bound is clamped to that)
+    uint32_t bd = 0u;
+    if constexpr (JOIN) {
+        const int64_t b64 = live ? a.before[myq] : 0;
+        bd = b64 <= 0 ? 0u : b64 >= 0xffffffffll ? 0xffffffffu : (uint32_t)b64;
+        asm volatile("" : "+v"(bd));
+    }
     bool open = live;  // this lane still admits
     unsigned long long* const ctr = a.ccount + (live ? myq : 0);
     uint32_t* const seg = a.cand + (int64_t)(live ? myq : 0) * a.ccap;
@@ -782,6 +792,10 @@ __global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeAr
         const int64_t left = last - m0;                              // >= 0: rows m0 .. m0 + left exist
         const uint32_t inside = left >= 31 ? 0xffffffffu : (2u << (int)left) - 1u;
         hit = open ? ((hit << (4 * fk)) & mw & inside) : 0u;
+        if constexpr (JOIN) {   // rows m0 .. m0 + below - 1 lie under this lane's bound
+            const int64_t below = (int64_t)bd - m0;
+            hit &= below >= 32 ? 0xffffffffu : below <= 0 ? 0u : (1u << (int)below) - 1u;
+        }
         const int c = __popc(hit);
         if (c) {
             unsigned long long at = atomicAdd(ctr, (unsigned long long)c);
@@ -849,12 +863,25 @@ __global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeAr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped look-ahead DMAs must land before the LDS is released
 }
 
+template <int KT, int KS, int WV, int NST, int NACC>
+__global__ __launch_bounds__(WV * 64) void range_nominate_h16_kernel(HalfRangeArgs a) {
+    range_nominate_body<KT, KS, WV, NST, NACC, false>(a);
+}
+template <int KT, int KS, int WV, int NST, int NACC>
+__global__ __launch_bounds__(WV * 64) void join_nominate_h16_kernel(HalfRangeArgs a) {
+    range_nominate_body<KT, KS, WV, NST, NACC, true>(a);
+}
+
 int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream) {
     if (a.n <= 0) return fail(MVDB_ERR_ARG, "no fp16-shadow range kernel for %d queries per pass", nqpad);
     return with_h16_shape(d, nqpad, "range ", [&](auto shape) {
         using S = decltype(shape);
         constexpr int NACC = S::KT <= 32 ? 1 : S::KT / 8;   // d <= 512: one chain of d products; wider: chains of 128 (half_range_eps)
         static_assert(S::BPC * S::kLds <= 160 * 1024, "LDS budget of a CU");
+        if (a.before)   // the range join: rows [0, a.n) with a.n the largest bound of the chunk, each query gated on its own
+            return launch_ring(join_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC,
+                               device, stream, nullptr, "ip_scan_join_half", "join_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV,
+                               S::NST, NACC);
         return launch_ring(range_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC, device,
                            stream, nullptr, "ip_scan_range_half", "range_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV, S::NST, NACC);
     });

@@ -137,6 +137,7 @@ struct HalfRangeArgs {
     uint32_t* cand;       // [nq][ccap] candidate rows, in no defined order
     int64_t ccap;
     unsigned long long* ccount;  // [nq] zeroed by the caller
+    const int64_t* before = nullptr;  // NULL, or [nq] (the range join, join_nominate_h16_kernel): query q admits rows below before[q] only
 };
 int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream);
 

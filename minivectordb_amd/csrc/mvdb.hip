@@ -19,6 +19,7 @@
 #include "scan_kernels.hpp"
 #include "grouped_scan.hpp"
 #include "range_scan.hpp"
+#include "join_scan.hpp"
 #include "mmr_select.hpp"
 #include "distinct_select.hpp"
 #include "code8_scan.hpp"
@@ -294,6 +295,7 @@ struct Workspace {
     DevBuf<uint32_t> rcand;              // range search, shared pass: [nq, capacity] candidate rows ...
     DevBuf<unsigned long long> rccount;  // ... and their per-query counters
     DevBuf<float> rthr;                  // per-query thresholds on the device (host entry point; L2: negated)
+    DevBuf<int64_t> jrows;               // range join: the query rows' numbers = their bounds, one launch group
     DevBuf<float> mmrD;                  // MMR search: stage 1's candidates of one tile of queries, [min(nq, kCoreTile), fetch_k] ...
     DevBuf<int64_t> mmrI;                // ... scores and row numbers (mmr_select.hpp)
     DevBuf<int> dneed;                   // distinct search: kCoreTile need words of one tile of queries, then the collapse launch's ticket
@@ -453,6 +455,9 @@ struct mvdb_index {
     // are counted on the host
     mutable MirroredCounter rg_ctr;
     mutable std::atomic<unsigned long long> rg_shared_calls{0};
+    // the range join (range_shared_phase with bounds): the same pair of counters, of its own
+    mutable MirroredCounter jn_ctr;
+    mutable std::atomic<unsigned long long> jn_shared_calls{0};
     // distinct search, created by the first call: a running count of the queries tier 2 answered (one device word and its
     // mirror, written by distinct_collapse_kernel); the calls are counted on the host
     mutable MirroredCounter ds_ctr;
@@ -2382,6 +2387,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const int code8_front = idx->kn.code8_front_plane;
     const int range_shared = idx->kn.range_shared;
     const long long range_cand = idx->kn.range_candidates;
+    const int join_shared = idx->kn.join_shared;
     const long long distinct_table = idx->kn.distinct_table_bytes;
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
@@ -2390,6 +2396,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     idx->kn.code8_front_plane = code8_front;
     idx->kn.range_shared = range_shared;
     idx->kn.range_candidates = range_cand;
+    idx->kn.join_shared = join_shared;
     return 0;
 }
 
@@ -2421,6 +2428,9 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "range_shared") {  // batches of a range search on the shared fp16 pass: 0 never, 1 by size, 2 wherever eligible
         if (value < 0 || value > 2) return fail(MVDB_ERR_ARG, "range_shared must be 0, 1 or 2");
         idx->kn.range_shared = (int)value;
+    } else if (n == "join_shared") {  // the range join on the shared fp16 pass: 0 never, 1 by size, 2 wherever eligible
+        if (value < 0 || value > 2) return fail(MVDB_ERR_ARG, "join_shared must be 0, 1 or 2");
+        idx->kn.join_shared = (int)value;
     } else if (n == "range_candidates") {  // candidates per query the shared pass holds (0: by cap); a small value forces the fallback
         if (value != 0 && (value < 64 || value > (1ll << 20))) return fail(MVDB_ERR_ARG, "range_candidates must be 0 or lie in [64, 2^20]");
         idx->kn.range_candidates = value;
@@ -2433,7 +2443,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, range_candidates, distinct_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2494,6 +2504,12 @@ int mvdb_index_range_counters(const mvdb_index* idx, long long* shared_calls, lo
     if (shared_calls) *shared_calls = (long long)idx->rg_shared_calls.load();
     if (fallback_queries) *fallback_queries = (long long)idx->rg_ctr.read<unsigned long long>(0);
     if (last_candidates) *last_candidates = (long long)idx->rg_ctr.read<unsigned long long>(1);
+    return 0;
+}
+int mvdb_index_join_counters(const mvdb_index* idx, long long* shared_calls, long long* fallback_queries) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (shared_calls) *shared_calls = (long long)idx->jn_shared_calls.load();
+    if (fallback_queries) *fallback_queries = (long long)idx->jn_ctr.read<unsigned long long>(0);
     return 0;
 }
 int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long long* fallback_queries) {
@@ -3315,6 +3331,28 @@ int launch_range(int metric, const RangeScanArgs& a, int nq, int device, hipStre
     });
 }
 
+// the range join's bounded scan (join_scan.hpp): the same shapes, forms and grid, labels of its own
+template <int G, int C, int U, int METRIC, int SEL, bool MASKED>
+int launch_join_kern(const JoinScanArgs& a, int nq, int device, hipStream_t stream) {
+    void (*kern)(JoinScanArgs) = join_scan_kernel<G, C, U, METRIC, SEL, MASKED>;
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
+    return profiled_launch(a.gate_count ? "ip_scan_join_fallback" : "ip_scan_join", stream,
+                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           "join_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
+}
+
+int launch_join(int metric, const JoinScanArgs& a, int nq, int device, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);
+            return metric == MVDB_METRIC_IP ? launch_join_kern<S::G, S::C, U, 0, F::SEL, F::MASKED>(a, nq, device, s)
+                                            : launch_join_kern<S::G, S::C, U, 1, F::SEL, F::MASKED>(a, nq, device, s);
+        });
+    });
+}
+
 constexpr int kRangeTile = 1024;  // queries of one range launch (a call of more is answered that many at a time)
 
 // ---- the shared pass of a range batch (inner product): nomination over the fp16 shadow, exact re-score, gated fallback ----------
@@ -3411,16 +3449,17 @@ int range_shared_min_nq(int64_t n) {
 }
 
 // the counters of the route: allocated with the first call that takes it, never inside a capture
-bool ensure_range_stats(const mvdb_index* idx, hipStream_t s) {
+bool ensure_range_stats(const mvdb_index* idx, MirroredCounter& ctr, hipStream_t s) {
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
-    return idx->rg_ctr.dev() || (!stream_capturing(s) && idx->rg_ctr.ensure(1));
+    return ctr.dev() || (!stream_capturing(s) && ctr.ensure(1));
 }
 
 // Does this launch group go through the shared pass?  Inner product, a batch, every row or a bitmap-form set, an index that
 // meets the certified pass's shadow conditions (half_path_ok: a width with a shadow kernel, unpadded rows, rows of known finite
 // norm), and a shadow that exists or may be built now (never while the stream is capturing).
-const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq, const mvdb_rowset* rs, int64_t n) {
-    const int mode = idx->kn.range_shared;
+// (mode, ctr: option range_shared and the range calls' counter, or the range join's pair)
+const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq, const mvdb_rowset* rs, int64_t n, int mode,
+                                   MirroredCounter& ctr) {
     if (mode == 0 || nq < 2 || n <= 0 || idx->metric != MVDB_METRIC_IP || (rs && !rs->mask) || !half_path_ok(idx)) return nullptr;
     if (mode == 1 && nq < range_shared_min_nq(n)) return nullptr;
     {   // the band (half_range_eps) bounds the scan's sum by its depth, 4 C + log2 G <= 4 ceil(d / 128) + 6: hold the shape to it
@@ -3430,7 +3469,7 @@ const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq,
         if (4 * sh.C + lg > (idx->d + 127) / 128 * 4 + 6) return nullptr;
     }
     const _Float16* Xh = idx->shadow.ensure(idx, ws->stream, half_xscale(idx->row_norm_bound));
-    if (!Xh || !ensure_range_stats(idx, ws->stream)) return nullptr;
+    if (!Xh || !ensure_range_stats(idx, ctr, ws->stream)) return nullptr;
     return Xh;
 }
 
@@ -3438,7 +3477,11 @@ const _Float16* range_shared_route(const mvdb_index* idx, Workspace* ws, int nq,
 // shadow against the floors threshold_i - band_i; (b) the exact re-score of the candidates appends the passing keys; (c) the
 // thresholded scan, enabled per query on the device, answers the queries whose candidates overflowed.  `a`: the arguments the
 // per-query route would launch with.
-int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh, RangeScanArgs a, int nq) {
+// bounds_host (the range join; bounds_dev: the same on the device): query i admits rows below bounds_host[i] only — the nomination launch
+// of a chunk covers the tiles below the chunk's largest bound (none: no launch), the gated fallback is the bounded scan, and
+// the diagnostics go to the join's own counter.
+int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh, RangeScanArgs a, int nq,
+                       const int64_t* bounds_host = nullptr, const int64_t* bounds_dev = nullptr) {
     hipStream_t s = ws->stream;
     const int chunk = half_max_queries(idx->d);
     int64_t ccap = idx->kn.range_candidates > 0 ? idx->kn.range_candidates : std::max<int64_t>(pow2ceil(std::max<int64_t>(2 * a.cap, 2)), 4096);
@@ -3472,6 +3515,9 @@ int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh,
     _Float16* qf = reinterpret_cast<_Float16*>(ws->qsplit.p);
     for (int c0 = 0; c0 < nq; c0 += chunk) {
         const int take = std::min(chunk, nq - c0);
+        int64_t rows_below = a.n;
+        if (bounds_host) rows_below = std::min(a.n, *std::max_element(bounds_host + c0, bounds_host + c0 + take));
+        if (rows_below <= 0) continue;
         const int nqpad = half_chunk_queries(idx->d, take);
         float* qnorm = ws->qnorm.p;
         float* floors = qnorm + nqpad;
@@ -3486,7 +3532,8 @@ int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh,
         h.qinv = qinv;
         h.floors = floors;
         h.nq = take;
-        h.n = a.n;
+        h.n = rows_below;
+        h.before = bounds_host ? bounds_dev + c0 : nullptr;
         h.mask = reinterpret_cast<const uint32_t*>(a.mask);
         h.cand = ws->rcand.p + (size_t)c0 * (size_t)ccap;
         h.ccap = ccap;
@@ -3509,12 +3556,17 @@ int range_shared_phase(const mvdb_index* idx, Workspace* ws, const _Float16* Xh,
     r.cap = a.cap;
     r.counts = a.counts;
     MVDB_TRY(launch_rescore(r, nq, idx->device, s));
-    hipLaunchKernelGGL(range_stats_kernel, dim3(1), dim3(256), 0, s, ws->rccount.p, (unsigned long long)ccap, nq, idx->rg_ctr.dev(),
-                       idx->rg_ctr.mirror<unsigned long long>());
+    MirroredCounter& ctr = bounds_host ? idx->jn_ctr : idx->rg_ctr;
+    hipLaunchKernelGGL(range_stats_kernel, dim3(1), dim3(256), 0, s, ws->rccount.p, (unsigned long long)ccap, nq, ctr.dev(),
+                       ctr.mirror<unsigned long long>());
     MVDB_HIP(hipGetLastError());
     a.gate_count = ws->rccount.p;
     a.gate_cap = (unsigned long long)ccap;
-    return launch_range(idx->metric, a, nq, idx->device, s);
+    if (!bounds_host) return launch_range(idx->metric, a, nq, idx->device, s);
+    JoinScanArgs j;
+    static_cast<RangeScanArgs&>(j) = a;
+    j.before = bounds_dev;
+    return launch_join(idx->metric, j, nq, idx->device, s);
 }
 
 int check_range_args(const mvdb_index* idx, const void* q, int nq, float threshold, int64_t cap, const void* counts, const void* D,
@@ -3563,7 +3615,7 @@ int range_scan_phase(const mvdb_index* idx, Workspace* ws, const float* q, int n
     a.counts = counts;
     *rows_out = a.rows;
     if (a.n > 0) {
-        if (const _Float16* Xh = range_shared_route(idx, ws, nq, rs, a.n)) {
+        if (const _Float16* Xh = range_shared_route(idx, ws, nq, rs, a.n, idx->kn.range_shared, idx->rg_ctr)) {
             *shared = true;
             return range_shared_phase(idx, ws, Xh, a, nq);   // (zeroes the counters itself)
         }
@@ -3597,14 +3649,10 @@ int range_emit_phase(const mvdb_index* idx, Workspace* ws, int nq, int64_t seg, 
     return 0;
 }
 
-// host entry point, one tile of queries already staged in ws->q
-int range_host_tile(const mvdb_index* idx, HostCall& call, int nq, float threshold, const float* thrs, int normalize_q, const mvdb_rowset* rs,
-                    int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host, bool* shared) {
+// host entry points, behind the scan phase of one tile (counters in ws->rcounts, keys in ws->rkeys): counts, sort, emit, fill
+int range_host_finish(const mvdb_index* idx, HostCall& call, int nq, int64_t cap, int64_t seg, const int64_t* rows, int64_t* counts_host,
+                      float* D_host, int64_t* I_host) {
     Workspace* ws = call.ws;
-    const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
-    MVDB_TRY(ws->rcounts.reserve((size_t)nq));
-    const int64_t* rows = nullptr;
-    MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, thrs, normalize_q, rs, cap, seg, ws->rcounts.p, &rows, shared));
     // the counts come back first: the sort and the copy are sized by what is there, not by the capacity
     MVDB_TRY(copy_back(ws, ws->rcounts.p, (size_t)nq * sizeof(unsigned long long), "range search"));
     int64_t width = 0;
@@ -3637,6 +3685,82 @@ int range_host_tile(const mvdb_index* idx, HostCall& call, int nq, float thresho
         std::fill(Ir + have, Ir + cap, (int64_t)-1);
     }
     return 0;
+}
+
+// host entry point, one tile of queries already staged in ws->q
+int range_host_tile(const mvdb_index* idx, HostCall& call, int nq, float threshold, const float* thrs, int normalize_q, const mvdb_rowset* rs,
+                    int64_t cap, int64_t* counts_host, float* D_host, int64_t* I_host, bool* shared) {
+    Workspace* ws = call.ws;
+    const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
+    MVDB_TRY(ws->rcounts.reserve((size_t)nq));
+    const int64_t* rows = nullptr;
+    MVDB_TRY(range_scan_phase(idx, ws, ws->q.p, nq, threshold, thrs, normalize_q, rs, cap, seg, ws->rcounts.p, &rows, shared));
+    return range_host_finish(idx, call, nq, cap, seg, rows, counts_host, D_host, I_host);
+}
+
+// ---- range join (join_scan.hpp): the queries are stored rows, each matched against the rows before it -----------------------
+// The scan phase of one launch group of query rows: their numbers = their bounds go to the device (8 bytes per query — the rows
+// themselves never leave it), the queries are read from the matrix in place where the group is a run of consecutive rows and
+// gathered into the workspace otherwise.
+int join_scan_phase(const mvdb_index* idx, Workspace* ws, const int64_t* qrows_host, int nq, float threshold, const mvdb_rowset* rs,
+                    int64_t cap, int64_t seg, unsigned long long* counts, const int64_t** rows_out, bool* shared) {
+    KnobScope knobs(&idx->kn);
+    hipStream_t s = ws->stream;
+    MVDB_TRY(ws->rkeys.reserve((size_t)nq * (size_t)seg));
+    MVDB_TRY(ws->jrows.reserve((size_t)nq));
+    // (pageable memory: the copy has left the host buffer when the call returns)
+    if (hipMemcpyAsync(ws->jrows.p, qrows_host, (size_t)nq * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(MVDB_ERR_HIP, "range join: the row numbers' upload failed");
+    bool consecutive = true;
+    int64_t max_bound = qrows_host[0];
+    for (int i = 1; i < nq; ++i) {
+        consecutive = consecutive && qrows_host[i] == qrows_host[0] + i;
+        max_bound = std::max(max_bound, qrows_host[i]);
+    }
+    const float* q = idx->X.p + qrows_host[0] * idx->ld;
+    if (!consecutive) {
+        MVDB_TRY(ws->q.reserve((size_t)nq * idx->ld));
+        const int64_t units = (int64_t)nq * (idx->ld / 4);
+        hipLaunchKernelGGL(join_gather_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, ws->q.p, idx->X.p, ws->jrows.p,
+                           (int64_t)nq, idx->ld);
+        MVDB_HIP(hipGetLastError());
+        q = ws->q.p;
+    }
+    JoinScanArgs a;
+    a.X = idx->X.p;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.q = q;
+    a.normalize_q = 0;
+    a.thr = idx->metric == MVDB_METRIC_IP ? threshold : -threshold;  // the key's score of an L2 row is -distance
+    a.rows = nullptr;
+    a.mask = nullptr;
+    a.n = idx->n;
+    if (rs) {
+        if (rs->mask) {
+            a.mask = rs->mask;
+            a.n = rs->count == 0 ? 0 : std::min<int64_t>(rs->n_at_create, idx->n);  // rows appended since are not part of the set
+        } else {
+            a.rows = rs->rows;
+            a.n = rs->count;
+        }
+    }
+    if (!a.rows) a.n = std::min(a.n, max_bound);  // streamed forms: no query of the group looks at or beyond its largest bound
+    a.keys = ws->rkeys.p;
+    a.seg = seg;
+    a.cap = cap;
+    a.counts = counts;
+    a.before = ws->jrows.p;
+    *rows_out = a.rows;
+    if (a.n > 0 && max_bound > 0) {
+        if (const _Float16* Xh = range_shared_route(idx, ws, nq, rs, a.n, idx->kn.join_shared, idx->jn_ctr)) {
+            *shared = true;
+            return range_shared_phase(idx, ws, Xh, a, nq, qrows_host, a.before);   // (zeroes the counters itself)
+        }
+    }
+    MVDB_HIP(hipMemsetAsync(counts, 0, (size_t)nq * sizeof(unsigned long long), s));
+    if (a.n <= 0 || max_bound <= 0) return 0;
+    return launch_join(idx->metric, a, nq, idx->device, s);
 }
 
 }  // namespace
@@ -3715,6 +3839,34 @@ static int range_search_dev(const mvdb_index* idx, const float* q_dev, int nq, f
     }
     if (shared) idx->rg_shared_calls.fetch_add(1);
     return 0;
+}
+
+int mvdb_index_range_join(const mvdb_index* idx, const int64_t* qrows_host, int nq, float threshold, const mvdb_rowset* rs, int64_t cap,
+                          int64_t* counts_host, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_range_args(idx, qrows_host, nq, threshold, cap, counts_host, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    const RowRange rr = row_range(qrows_host, nq);
+    if (rr.lo < 0 || rr.hi >= idx->n)
+        return fail(MVDB_ERR_ARG, "query row %lld out of range [0,%lld)", (long long)(rr.lo < 0 ? rr.lo : rr.hi), (long long)idx->n);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* ws = call.ws;
+    const int64_t seg = cap > 0 ? pow2ceil(std::max<int64_t>(cap, 2)) : 0;
+    bool shared = false;
+    int rc = 0;
+    for (int t0 = 0; t0 < nq && !rc; t0 += kRangeTile) {
+        const int take = std::min(kRangeTile, nq - t0);
+        const int64_t* rows = nullptr;
+        rc = ws->rcounts.reserve((size_t)take);
+        if (!rc) rc = join_scan_phase(idx, ws, qrows_host + t0, take, threshold, rs, cap, seg, ws->rcounts.p, &rows, &shared);
+        if (!rc)
+            rc = range_host_finish(idx, call, take, cap, seg, rows, counts_host + t0, cap ? D_host + (size_t)t0 * cap : nullptr,
+                                   cap ? I_host + (size_t)t0 * cap : nullptr);
+    }
+    if (shared) idx->jn_shared_calls.fetch_add(1);  // (a call that failed behind the shared pass counts too)
+    return rc;
 }
 
 int mvdb_index_range_search(const mvdb_index* idx, const float* q_host, int nq, float threshold, int normalize_q,

@@ -576,3 +576,16 @@ class DistributedShardedVectorDatabase:
 
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
+
+    # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
+    _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
+                "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")
+
+    def find_duplicate_pairs(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)
+
+    def count_duplicate_pairs(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)
+
+    def find_duplicate_groups(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)

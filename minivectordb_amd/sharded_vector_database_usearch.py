@@ -175,3 +175,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
 
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
+
+    # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
+    _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
+                "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
+
+    def find_duplicate_pairs(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)
+
+    def count_duplicate_pairs(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)
+
+    def find_duplicate_groups(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_JOIN)
