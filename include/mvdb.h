@@ -606,14 +606,33 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
                            int normalize, int device, void* stream);
 
 /* ---- profiling hooks (bench.py's roofline leg) ---------------------------------------------
- * When enabled, every launch of the dominant kernels is bracketed by hipEvents on the launch
- * stream.  mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
+ * When enabled, every launch of the dominant kernels is timed by a pair of hipEvents.  A bracket of one kernel hands its
+ * stop event to the launch itself (hipExtLaunchKernel): the runtime fills it from the kernel's own dispatch — its time is the
+ * kernel's end — and the stream carries nothing behind the kernel.  Its start event is recorded on the launch stream in front
+ * of the kernel, one marker, so the duration is the kernel's plus that marker's hand-over.  The four launches of the
+ * single-query int8 route ("ip_scan_code8_seed", "ip_scan", "ip_scan_code8_rescore", "ip_scan_code8_fallback") follow one
+ * another with nothing in between and share their boundaries: only the first records a start, each of the others begins at
+ * the stop event of the one before it, and its duration is the time from the end of that kernel to the end of its own — the
+ * launch gap and the kernel (measured against a kernel trace: profiles/prof_bracket_overhead.jsonl).  A call of that route puts
+ * one marker on the stream.  A bracket of several launches or of a graph launch ("encoder", "ip_scan_mfma_masked") records
+ * both events on the launch stream around them, and its duration includes those two markers.
+ * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "encoder") and returns the number of launches and their summed duration.
- * Turning profiling on while it was off forgets the symbols recorded so far (mvdb_prof_symbol): after it, a label under which
- * nothing has been launched since reads "", not the symbol of an earlier bracket. */
+ * "distinct_collapse", "distinct_scan", "distinct_select", "encoder") and returns the number of launches and their summed duration;
+ * pairs recorded while profiling was on stay readable after it is turned off.
+ * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
+ * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.
+ * The events come from a pool that is created on first use and only recycled afterwards: mvdb_prof_read returns the pairs it
+ * drains to it.  Pairs that nobody reads are bounded by two rules.  Turning profiling on while it was off returns every unread
+ * pair to the pool (and forgets the symbols recorded so far, mvdb_prof_symbol: after it, a label under which nothing has been
+ * launched since reads "", not the symbol of an earlier bracket).  And a label holds at most MVDB_PROF_LABEL_CAP unread pairs:
+ * past that its launches run untimed and uncounted until a read or an off -> on makes room.  So the pool never holds more than
+ * 2 * (the most pairs left unread at one time since the library was loaded) events, and no label contributes more than
+ * 2 * MVDB_PROF_LABEL_CAP of them.  mvdb_prof_live_events: the events the pool holds, in use or free.  Diagnostic only. */
+#define MVDB_PROF_LABEL_CAP 8192
 int mvdb_prof_enable(int on);
 int mvdb_prof_read(const char* name, int64_t* launches, double* total_ms);
+int64_t mvdb_prof_live_events(void);
 /* The kernel instantiation last launched under label `name` while profiling was on, as rocprofv3 prints it
  * ("flat_scan_kernel<64, 2, 2, 0, 0, true, 0, false>"; "" if none): bench.py refuses a committed PMC profile whose kernel
  * differs from what the timed run launched.  The ops of an encoder forward record theirs with the grid, the block and the LDS

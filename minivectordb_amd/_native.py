@@ -153,6 +153,7 @@ PROTOTYPES = {
     "mvdb_prof_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_double)]),
     "mvdb_prof_symbol": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
+    "mvdb_prof_live_events": (ctypes.c_int64, []),
     # int8 cosine index (cos8.hip)
     "mvdb_cos8_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "mvdb_cos8_free": (ctypes.c_int, [c_vp]),
@@ -1070,6 +1071,14 @@ def prof_read(name):
     ms = ctypes.c_double(0.0)
     check(lib().mvdb_prof_read(name.encode(), ctypes.byref(n), ctypes.byref(ms)))
     return n.value, ms.value
+
+
+PROF_LABEL_CAP = 8192   # include/mvdb.h: MVDB_PROF_LABEL_CAP, the unread pairs one label may hold
+
+
+def prof_live_events():
+    """Events the profiler's pool holds, in use or free (include/mvdb.h: the two rules that bound them)."""
+    return int(lib().mvdb_prof_live_events())
 
 
 def range_band(d, qnorm, row_norm_bound):

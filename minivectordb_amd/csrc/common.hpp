@@ -1,6 +1,7 @@
 // common.hpp — host-side plumbing shared by the translation units of libmvdb.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include <cstdarg>
@@ -52,22 +53,60 @@ int device_cus(int device);
 
 // ---- profiling hooks ---------------------------------------------------------------------------
 bool prof_enabled();
-// returns an opaque slot (or -1 when disabled) after recording the start event on `stream`
+// The events of one bracket of `name` on `stream`, from the library's pool: its slot, *stop for the launch to carry
+// (launch_kernel), and *start where the caller has to record one on `stream` before the launch — null where the bracket
+// begins at the end of the bracket before it (ProfChain).  -1 and null events: profiling off, `stream` capturing (a timed
+// event inside a graph measures nothing), or the label holds its cap of unread pairs (include/mvdb.h).
+int prof_open(const char* name, hipStream_t stream, hipEvent_t* start, hipEvent_t* stop);
+void prof_close(int slot, hipStream_t stream);  // the launch is enqueued: the pair is readable
+// the recorded form, for brackets that hold several launches: prof_open + both events recorded on `stream` + prof_close
 int prof_begin(const char* name, hipStream_t stream);
 void prof_end(int slot, hipStream_t stream);
+// While one is alive, the single-kernel brackets this thread launches on `stream` share their boundaries: a bracket begins
+// where the one before it ended, at that kernel's stop event, and puts no marker of its own on the stream.  Its duration is
+// then the time from the end of the kernel before it to the end of its own: the launch gap and the kernel.  For a run of
+// brackets with NOTHING enqueued between them — a launch without a bracket would be counted into the next label.  The first
+// bracket of the run records a start event.
+struct ProfChain {
+    hipStream_t stream;
+    int last = -1;  // pool index of the stop event of the bracket before (the chain holds a reference), -1: none
+    ProfChain* prev;
+    explicit ProfChain(hipStream_t s);
+    ProfChain(const ProfChain&) = delete;
+    ProfChain& operator=(const ProfChain&) = delete;
+    ~ProfChain();
+};
+// One kernel launch that carries a bracket's stop event: the runtime fills it from the kernel's own dispatch — its time is the
+// kernel's end — and the stream gets no packet beside the kernel.  (A start event handed to the launch the same way is a marker
+// on the stream again, and reads 5 us late: profiles/prof_bracket_overhead.jsonl.)  A null event: the plain launch.
+template <typename... Params, typename... Args>
+void launch_kernel(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, hipEvent_t stop, Args... args) {
+    if (stop) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, stream, nullptr, stop, 0, args...);
+    else hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+}
 // while profiling is on: remember which kernel instantiation a label's launches run (mvdb_prof_symbol; bench.py checks
 // the committed PMC profile against it)
 void prof_symbol(const char* label, const char* fmt, ...);
 // One launch inside its profiling bracket: the symbol of `label` (symbol...: the format and the arguments of prof_symbol; none:
-// the label records no symbol), the event pair around launch() on `stream`, and the launch's error.  launch() enqueues the
-// kernel; one that brackets launches of its own returns their status, and a failure ends the call there.
+// the label records no symbol), the event pair of the launch, and the launch's error.  A bracket of exactly one kernel takes
+// launch(stop) and hands the event to launch_kernel (null: profiling is off, or the launch is not timed).  launch() is the
+// recorded form, the pair around it on `stream`: it enqueues what it likes; one that brackets launches of its own returns their
+// status, and a failure ends the call there.
 template <typename Launch, typename... Sym>
 int profiled_launch(const char* label, hipStream_t stream, Launch launch, Sym... symbol) {
     if constexpr (sizeof...(Sym) > 0) prof_symbol(label, symbol...);
-    const int slot = prof_begin(label, stream);
-    if constexpr (std::is_void_v<decltype(launch())>) launch();
-    else MVDB_TRY(launch());
-    prof_end(slot, stream);
+    if constexpr (std::is_invocable_v<Launch, hipEvent_t>) {
+        hipEvent_t start = nullptr, stop = nullptr;
+        const int slot = prof_open(label, stream, &start, &stop);
+        if (start) (void)hipEventRecord(start, stream);
+        launch(stop);
+        prof_close(slot, stream);
+    } else {
+        const int slot = prof_begin(label, stream);
+        if constexpr (std::is_void_v<decltype(launch())>) launch();
+        else MVDB_TRY(launch());
+        prof_end(slot, stream);
+    }
     MVDB_HIP(hipGetLastError());
     return 0;
 }

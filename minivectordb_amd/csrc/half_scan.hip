@@ -646,7 +646,7 @@ static int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int thread
     MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * per_cu));
     if (nblocks_out) *nblocks_out = nblocks;
-    return profiled_launch(label, stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, a); }, symbol...);
+    return profiled_launch(label, stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(threads), lds, stream, done, a); }, symbol...);
 }
 
 // The shapes of the launches that stream the whole shadow: the certified pass's main launches and the shared pass of a batch range

@@ -149,15 +149,32 @@ int device_cus(int device) {
     return cus;
 }
 
-struct ProfPair {
-    std::string name;
-    hipEvent_t a, b;
-    bool closed;
+// The profiler's events and pairs live in pools that only grow: a launch takes a free pair and free events (created on first
+// use only), and mvdb_prof_read or an off -> on of mvdb_prof_enable gives them back — no event, map node or string is made per
+// launch.  A pair's index is the bracket's ticket.  An event is counted: a bracket of a ProfChain begins at the stop event of
+// the bracket before it, which must outlive that bracket's own pair.
+struct ProfEvent {
+    hipEvent_t ev = nullptr;
+    int device = 0;  // the device that was current when it was created: the launching object's
+    int refs = 0;
 };
+struct ProfPair {
+    int a = -1, b = -1;                      // indices into g_prof_ev
+    int label = -1;                          // index into g_prof_labels
+    enum { kFree, kOpen, kClosed } state = kFree;
+};
+struct ProfLabel {
+    std::string name;
+    int held = 0;  // pairs of this label that are open or unread
+};
+constexpr int kProfLabelCap = MVDB_PROF_LABEL_CAP;
 static std::mutex g_prof_mu;
 static bool g_prof_on = false;
-static int g_prof_next = 0;
-static std::map<int, ProfPair> g_prof;  // keyed by a ticket that stays valid across mvdb_prof_read
+static std::vector<ProfEvent> g_prof_ev;
+static std::vector<ProfPair> g_prof;
+static std::vector<int> g_prof_ev_free, g_prof_free;
+static std::vector<ProfLabel> g_prof_labels;  // every label seen so far: a few dozen, searched linearly
+static thread_local ProfChain* tls_prof_chain = nullptr;
 
 static std::map<std::string, std::string> g_prof_sym;  // label -> the kernel instantiation last launched under it
 void prof_symbol(const char* label, const char* fmt, ...) {
@@ -171,30 +188,124 @@ void prof_symbol(const char* label, const char* fmt, ...) {
     g_prof_sym[label] = buf;
 }
 bool prof_enabled() { return g_prof_on; }
-int prof_begin(const char* name, hipStream_t stream) {
-    if (!g_prof_on) return -1;
-    ProfPair p;
-    p.name = name;
-    p.closed = false;
-    if (hipEventCreate(&p.a) != hipSuccess) return -1;
-    if (hipEventCreate(&p.b) != hipSuccess) {
-        (void)hipEventDestroy(p.a);
+// (g_prof_mu held, all four)
+static int prof_event_take() {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return -1;
+    for (size_t i = g_prof_ev_free.size(); i-- > 0;) {  // an event serves the device it was created on: the newest free one of it
+        const int e = g_prof_ev_free[i];
+        if (g_prof_ev[e].device != device) continue;
+        g_prof_ev_free.erase(g_prof_ev_free.begin() + (long)i);
+        g_prof_ev[e].refs = 1;
+        return e;
+    }
+    ProfEvent pe;
+    if (hipEventCreate(&pe.ev) != hipSuccess) {
+        (void)hipGetLastError();
         return -1;
     }
-    (void)hipEventRecord(p.a, stream);
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    const int ticket = g_prof_next++;
-    g_prof[ticket] = p;
-    return ticket;
+    pe.device = device;
+    pe.refs = 1;
+    g_prof_ev.push_back(pe);
+    g_prof_ev_free.reserve(g_prof_ev.capacity());  // prof_event_drop never allocates
+    return (int)g_prof_ev.size() - 1;
 }
-void prof_end(int ticket, hipStream_t stream) {
-    if (ticket < 0) return;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    auto it = g_prof.find(ticket);
-    if (it != g_prof.end()) {
-        (void)hipEventRecord(it->second.b, stream);
-        it->second.closed = true;
+static void prof_event_drop(int e) {
+    if (e >= 0 && --g_prof_ev[e].refs == 0) g_prof_ev_free.push_back(e);
+}
+static ProfChain* prof_chain_on(hipStream_t stream) {
+    return tls_prof_chain && tls_prof_chain->stream == stream ? tls_prof_chain : nullptr;
+}
+static void prof_release(int slot) {
+    ProfPair& p = g_prof[slot];
+    prof_event_drop(p.a);
+    prof_event_drop(p.b);
+    g_prof_labels[p.label].held--;
+    p.state = ProfPair::kFree;
+    g_prof_free.push_back(slot);
+}
+// chained: the bracket may begin at the stop event of the one before it (the single-kernel form; the recorded form records
+// both of its events)
+static int prof_open_pair(const char* name, hipStream_t stream, bool chained, hipEvent_t* start, hipEvent_t* stop) {
+    *start = *stop = nullptr;
+    if (!g_prof_on) return -1;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
     }
+    if (cs != hipStreamCaptureStatusNone) return -1;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    ProfChain* chain = prof_chain_on(stream);
+    int label = 0;
+    while (label < (int)g_prof_labels.size() && g_prof_labels[label].name != name) ++label;
+    if (label == (int)g_prof_labels.size()) g_prof_labels.push_back({name, 0});
+    const bool shared = chained && chain && chain->last >= 0;
+    const int a = g_prof_labels[label].held >= kProfLabelCap ? -1 : shared ? chain->last : prof_event_take();
+    const int b = a >= 0 ? prof_event_take() : -1;
+    if (b < 0) {  // not timed: the bracket after it has no boundary to share
+        if (a >= 0 && !shared) prof_event_drop(a);
+        if (chain) {
+            prof_event_drop(chain->last);
+            chain->last = -1;
+        }
+        return -1;
+    }
+    if (shared) g_prof_ev[a].refs++;
+    int slot;
+    if (!g_prof_free.empty()) {
+        slot = g_prof_free.back();
+        g_prof_free.pop_back();
+    } else {
+        slot = (int)g_prof.size();
+        g_prof.push_back(ProfPair());
+        g_prof_free.reserve(g_prof.capacity());  // prof_release never allocates
+    }
+    ProfPair& p = g_prof[slot];
+    p.a = a;
+    p.b = b;
+    p.label = label;
+    p.state = ProfPair::kOpen;
+    g_prof_labels[label].held++;
+    if (!shared) *start = g_prof_ev[a].ev;
+    *stop = g_prof_ev[b].ev;
+    return slot;
+}
+int prof_open(const char* name, hipStream_t stream, hipEvent_t* start, hipEvent_t* stop) {
+    return prof_open_pair(name, stream, true, start, stop);
+}
+void prof_close(int slot, hipStream_t stream) {
+    if (slot < 0) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof[slot].state = ProfPair::kClosed;
+    if (ProfChain* chain = prof_chain_on(stream)) {  // the next bracket of the chain begins here
+        prof_event_drop(chain->last);
+        chain->last = g_prof[slot].b;
+        g_prof_ev[chain->last].refs++;
+    }
+}
+int prof_begin(const char* name, hipStream_t stream) {
+    hipEvent_t a, b;
+    const int slot = prof_open_pair(name, stream, false, &a, &b);
+    if (slot >= 0) (void)hipEventRecord(a, stream);
+    return slot;
+}
+void prof_end(int slot, hipStream_t stream) {
+    if (slot < 0) return;
+    hipEvent_t b;
+    {
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        b = g_prof_ev[g_prof[slot].b].ev;
+    }
+    (void)hipEventRecord(b, stream);
+    prof_close(slot, stream);
+}
+ProfChain::ProfChain(hipStream_t s) : stream(s), prev(tls_prof_chain) { tls_prof_chain = this; }
+ProfChain::~ProfChain() {
+    tls_prof_chain = prev;
+    if (last < 0) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    prof_event_drop(last);
 }
 
 }  // namespace mvdb
@@ -669,7 +780,7 @@ int launch_scan_kern(const ScanArgs& a, int nq, int device, hipStream_t stream, 
     const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C, knob), device);
     if (nblocks_out) *nblocks_out = nblocks;
     return profiled_launch(label ? label : MODE == kModeTopK ? "ip_scan" : "ip_scan_scores", stream,
-                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, done, a); },
                            "flat_scan_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", G, C, U, METRIC, MODE, "true", SEL, MASKED ? "true" : "false",
                            gated ? "true" : "false");
 }
@@ -749,7 +860,7 @@ int launch_mfma_inst(const MfmaScanArgs& a, int device, hipStream_t stream, int*
     int nb = cached_occupancy((const void*)kern, kScanThreads, lds, 1);
     nb = std::min(nb, kn().mfma_blocks_per_cu > 0 ? kn().mfma_blocks_per_cu : 4);
     const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
-    return profiled_launch("ip_scan_mfma", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a); });
+    return profiled_launch("ip_scan_mfma", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, done, a); });
 }
 
 template <int KB, int NG, int SKB>
@@ -763,7 +874,7 @@ int launch_mfma2_gated_inst(const MfmaScanArgs& a, int device, hipStream_t strea
     const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
     return profiled_launch(
         "ip_scan_rerun", stream,
-        [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a, gate, gate_lo, need, npasses, per_pass, rtot, cand_stride); },
+        [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, done, a, gate, gate_lo, need, npasses, per_pass, rtot, cand_stride); },
         "flat_scan_mfma2_gated_kernel<%d, %d, %d, %s>", KB, NG, SKB, a.mask ? "true" : "false");
 }
 
@@ -785,7 +896,7 @@ int launch_mfma2_inst(const MfmaScanArgs& a, int device, hipStream_t stream, int
     int nb = cached_occupancy((const void*)kern, kScanThreads, lds, 1);
     nb = std::min(nb, kn().mfma_blocks_per_cu > 0 ? kn().mfma_blocks_per_cu : 2);
     const int nblocks = *nblocks_out = mfma_tile_grid(a.n, nb, device);
-    return profiled_launch("ip_scan_mfma", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, a); },
+    return profiled_launch("ip_scan_mfma", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), lds, stream, done, a); },
                            "flat_scan_mfma2_kernel<%d, %d, %d, %d>", KB, NG, SKB, metric == MVDB_METRIC_L2 ? 1 : 0);
 }
 
@@ -902,7 +1013,7 @@ int launch_gemm_scan(const mvdb_index* idx, const float* q, int nq, int k, int64
         MVDB_HIP(hipGetLastError());
         return 0;
     }
-    return profiled_launch("ip_scan_gemm", stream, [&] { hipLaunchKernelGGL(flat_scan_gemm_kernel, dim3(gx, qtiles), dim3(256), lds, stream, a); });
+    return profiled_launch("ip_scan_gemm", stream, [&](hipEvent_t done) { launch_kernel(flat_scan_gemm_kernel, dim3(gx, qtiles), dim3(256), lds, stream, done, a); });
 }
 
 // Chunks that held an uncertified query, counted ON THE DEVICE (split_plan_kernel): the host never reads a certification
@@ -2124,10 +2235,10 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
     void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF>;
     const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF>(a.n, device);
     if constexpr (GF > 0)
-        return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
+        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, done, a); },
                                "code8_scan_kernel<%d, %d, %s, %d, %d>", G, U, MASKED ? "true" : "false", GF, UF);
     else
-        return profiled_launch("ip_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, a); },
+        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, done, a); },
                                "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 // Which form of the prefilter serves this call: the front form where the code holds the plane, unless its window has
@@ -2154,7 +2265,7 @@ int launch_code8_seed(const Code8SeedArgs& a, int device, hipStream_t stream, in
     int64_t blocks = kn().code8_seed_blocks > 0 ? kn().code8_seed_blocks : device_cus(device);
     blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, want), scan_grid_upper_bound(device)));
     *nlists = (int)blocks;
-    return profiled_launch("ip_scan_code8_seed", stream, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, a); },
+    return profiled_launch("ip_scan_code8_seed", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3((unsigned)blocks), dim3(threads), 0, stream, done, a); },
                            "code8_seed_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
 }
 
@@ -2164,7 +2275,7 @@ int launch_code8_rescore(const Code8RescoreArgs& a, int device, hipStream_t stre
     void (*kern)(Code8RescoreArgs) = code8_rescore_kernel<G, C, U, MASKED>;
     const int64_t want = (a.cap + a.rows_per_block - 1) / a.rows_per_block;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * 4));
-    return profiled_launch("ip_scan_code8_rescore", stream, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kScanThreads), 0, stream, a); },
+    return profiled_launch("ip_scan_code8_rescore", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3((unsigned)blocks), dim3(kScanThreads), 0, stream, done, a); },
                            "code8_rescore_kernel<%d, %d, %d, %s>", G, C, U, MASKED ? "true" : "false");
 }
 
@@ -2201,6 +2312,9 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     float* floor = reinterpret_cast<float*>(base + o_floor);
     uint32_t* cand = reinterpret_cast<uint32_t*>(base + o_cand);
 
+    // launches 1 to 4 follow one another with nothing in between: while they are timed, each bracket begins where the one
+    // before it ended, and the call puts one marker on the stream (in front of the first) where it used to put eight
+    ProfChain chain(s);
     // 1. the query's planes and margin terms (every block; block 0 leaves them here and zeroes the candidate counter), and
     //    per block the k best LOWER bounds of its share of the seed sample, from its stored copy
     Code8SeedArgs sd;
@@ -3314,7 +3428,7 @@ int launch_range_kern(const RangeScanArgs& a, int nq, int device, hipStream_t st
     // (the gated launch of the shared pass runs under a label of its own: a profile tells the scans that were asked for from
     //  the launches that return at once)
     return profiled_launch(a.gate_count ? "ip_scan_range_fallback" : "ip_scan_range", stream,
-                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, done, a); },
                            "range_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
 }
 
@@ -3337,7 +3451,7 @@ int launch_join_kern(const JoinScanArgs& a, int nq, int device, hipStream_t stre
     void (*kern)(JoinScanArgs) = join_scan_kernel<G, C, U, METRIC, SEL, MASKED>;
     const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
     return profiled_launch(a.gate_count ? "ip_scan_join_fallback" : "ip_scan_join", stream,
-                           [&] { hipLaunchKernelGGL(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, a); },
+                           [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, done, a); },
                            "join_scan_kernel<%d, %d, %d, %d, %d, %s>", G, C, U, METRIC, SEL, MASKED ? "true" : "false");
 }
 
@@ -3375,7 +3489,7 @@ int launch_rescore(const RangeRescoreArgs& a, int nq, int device, hipStream_t s)
                 const int64_t want = (a.ccap + (int64_t)RB * kScanWaves * 4 - 1) / ((int64_t)RB * kScanWaves * 4);
                 const int64_t room = std::max<int64_t>(1, (int64_t)device_cus(device) * 8 / nq);
                 const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, room));
-                return profiled_launch("ip_scan_range_rescore", s, [&] { hipLaunchKernelGGL(kern, dim3(gx, nq), dim3(kScanThreads), 0, s, a); },
+                return profiled_launch("ip_scan_range_rescore", s, [&](hipEvent_t done) { launch_kernel(kern, dim3(gx, nq), dim3(kScanThreads), 0, s, done, a); },
                                        "range_rescore_kernel<%d, %d, %d, %s>", S::G, S::C, U, MASKED ? "true" : "false");
             });
         }
@@ -3960,7 +4074,7 @@ int mmr_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k
         a.D = D_dev + (int64_t)t0 * k;
         a.I = I_dev + (int64_t)t0 * k;
         MVDB_TRY(profiled_launch("mmr_select", ws->stream,
-                                 [&] { hipLaunchKernelGGL(kern, dim3((unsigned)take), dim3(kMmrThreads), lds, ws->stream, a); },
+                                 [&](hipEvent_t done) { launch_kernel(kern, dim3((unsigned)take), dim3(kMmrThreads), lds, ws->stream, done, a); },
                                  "mmr_select_kernel<%d>", form));
     }
     return 0;
@@ -4056,7 +4170,7 @@ int launch_group_best_kern(const GroupBestArgs& a, int slots, int device, hipStr
     void (*kern)(GroupBestArgs) = group_best_scan_kernel<G, C, U, SEL, MASKED>;
     // the grid of the single-query scan (launch_scan_kern)
     const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
-    return profiled_launch("distinct_scan", stream, [&] { hipLaunchKernelGGL(kern, dim3(nblocks, slots), dim3(kScanThreads), 0, stream, a); },
+    return profiled_launch("distinct_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, slots), dim3(kScanThreads), 0, stream, done, a); },
                            "group_best_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
 }
 
@@ -4148,15 +4262,15 @@ int distinct_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, 
         c.I = I_dev + (int64_t)t0 * k;
         c.G = G_dev ? G_dev + (int64_t)t0 * k : nullptr;
         MVDB_TRY(profiled_launch("distinct_collapse", s,
-                                 [&] { hipLaunchKernelGGL(distinct_collapse_kernel, dim3((unsigned)take), dim3(cthreads), 0, s, c); },
+                                 [&](hipEvent_t done) { launch_kernel(distinct_collapse_kernel, dim3((unsigned)take), dim3(cthreads), 0, s, done, c); },
                                  "distinct_collapse_kernel"));
         if (covers) continue;
         for (int s0 = 0; s0 < take; s0 += T) {
             const int slots = std::min(T, take - s0);
             const int* need = ws->dneed.p + s0;
             // (the clear runs under the scan's label, as a record of its own: it names no symbol)
-            MVDB_TRY(profiled_launch("distinct_scan", s, [&] {
-                hipLaunchKernelGGL(distinct_clear_kernel, dim3(clear_gx, slots), dim3(256), 0, s, ws->dtab.p, ng, need);
+            MVDB_TRY(profiled_launch("distinct_scan", s, [&](hipEvent_t done) {
+                launch_kernel(distinct_clear_kernel, dim3(clear_gx, slots), dim3(256), 0, s, done, ws->dtab.p, ng, need);
             }));
             g.q = qt + (int64_t)s0 * idx->ld;
             g.need = need;
@@ -4166,7 +4280,7 @@ int distinct_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, 
             t.I = c.I + (int64_t)s0 * k;
             t.G = c.G ? c.G + (int64_t)s0 * k : nullptr;
             MVDB_TRY(profiled_launch("distinct_select", s,
-                                     [&] { hipLaunchKernelGGL(distinct_topk_kernel, dim3((unsigned)slots), dim3(kDistinctThreads), 0, s, t); },
+                                     [&](hipEvent_t done) { launch_kernel(distinct_topk_kernel, dim3((unsigned)slots), dim3(kDistinctThreads), 0, s, done, t); },
                                      "distinct_topk_kernel"));
         }
     }
@@ -4278,7 +4392,7 @@ int launch_grouped(int metric, const GroupedScanArgs& a, int nitems, hipStream_t
         return with_scan_form<S::G, S::C>(a.d4, false, false, [&](auto form) {
             constexpr bool MASKED = decltype(form)::MASKED;
             void (*kern)(GroupedScanArgs) = metric == MVDB_METRIC_IP ? grouped_scan_kernel<S::G, S::C, U, 0, MASKED> : grouped_scan_kernel<S::G, S::C, U, 1, MASKED>;
-            return profiled_launch("grouped_scan", s, [&] { hipLaunchKernelGGL(kern, dim3(nitems), dim3(kScanThreads), 0, s, a); },
+            return profiled_launch("grouped_scan", s, [&](hipEvent_t done) { launch_kernel(kern, dim3(nitems), dim3(kScanThreads), 0, s, done, a); },
                                    "grouped_scan_kernel<%d, %d, %d, %d, %s>", S::G, S::C, U, metric == MVDB_METRIC_IP ? 0 : 1, MASKED ? "true" : "false");
         });
     });
@@ -4430,7 +4544,7 @@ int grouped_search_core(const mvdb_index* idx, Workspace* ws, const float* q, in
         mg.label_offset = label_offset;
         mg.D = D_dev;
         mg.I = I_dev;
-        MVDB_TRY(profiled_launch("grouped_merge", s, [&] { hipLaunchKernelGGL(merge_keys_seg_kernel, dim3(nq), dim3(kMergeThreads), 0, s, mg); }));
+        MVDB_TRY(profiled_launch("grouped_merge", s, [&](hipEvent_t done) { launch_kernel(merge_keys_seg_kernel, dim3(nq), dim3(kMergeThreads), 0, s, done, mg); }));
     }
     // bitmap and NULL sets (and every query when k is beyond the fused select): the exact single-query routes, row by row
     for (int i = 0; i < nq; ++i) {
@@ -4566,9 +4680,18 @@ int mvdb_rescue_tile_stats(int64_t* listed, int64_t* total) {
 
 int mvdb_prof_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (on && !g_prof_on) g_prof_sym.clear();  // off -> on: a label that launches nothing from here on reads ""
+    if (on && !g_prof_on) {
+        g_prof_sym.clear();  // off -> on: a label that launches nothing from here on reads ""
+        for (int slot = 0; slot < (int)g_prof.size(); ++slot)  // ... and the pairs nobody read go back to the pool
+            if (g_prof[slot].state == ProfPair::kClosed) prof_release(slot);
+    }
     g_prof_on = on != 0;
     return 0;
+}
+
+int64_t mvdb_prof_live_events(void) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    return (int64_t)g_prof_ev.size();
 }
 
 int mvdb_prof_symbol(const char* name, char* out, int len) {
@@ -4584,20 +4707,20 @@ int mvdb_prof_read(const char* name, int64_t* launches, double* total_ms) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     int64_t cnt = 0;
     double ms = 0.0;
-    for (auto it = g_prof.begin(); it != g_prof.end();) {
-        ProfPair& p = it->second;
-        if (p.name != name || !p.closed) {
-            ++it;
-            continue;
-        }
+    int label = 0;
+    while (label < (int)g_prof_labels.size() && g_prof_labels[label].name != name) ++label;
+    for (int slot = 0; slot < (int)g_prof.size() && label < (int)g_prof_labels.size(); ++slot) {
+        ProfPair& p = g_prof[slot];
+        if (p.label != label || p.state != ProfPair::kClosed) continue;
         float t = 0.f;
-        if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&t, p.a, p.b) == hipSuccess) {
+        if (hipEventSynchronize(g_prof_ev[p.b].ev) == hipSuccess &&
+            hipEventElapsedTime(&t, g_prof_ev[p.a].ev, g_prof_ev[p.b].ev) == hipSuccess) {
             ++cnt;
             ms += t;
+        } else {
+            (void)hipGetLastError();
         }
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-        it = g_prof.erase(it);
+        prof_release(slot);
     }
     *launches = cnt;
     *total_ms = ms;
