@@ -565,6 +565,46 @@ int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev,
                                       int32_t* G_dev /* [nq,k] or NULL */, int64_t label_offset, void* stream);
 int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long long* fallback_queries);
 
+/* MAXSIM SEARCH: ONE question that is T query vectors (sub-questions, paraphrases, the token states of a late-interaction
+ * encoder); a GROUP of stored rows — a document — scores the sum, over the vectors, of its best row for each vector.
+ * Inner-product indexes only.  One call is one question; a batch is a loop of calls (a call is a corpus pass of milliseconds).
+ * Contract.  Groups come from an mvdb_grouping (above), the selected rows are all rows (rs == NULL) or those of a resident
+ * row set of any form.
+ *   Per-vector maximum m[t][g], for every group g with at least one selected row and every vector t: the maximum over the
+ *   selected rows of g of the inner product of the row and q_t, each score BIT FOR BIT the single-query scan's — what
+ *   mvdb_index_search / mvdb_index_search_rowset returns for q_t alone with nq = 1 and k = the rows selected (tier 2 of
+ *   distinct search defines its scores the same way).  normalize_q normalises every vector on its own, with the scan's own
+ *   prologue.  A row whose score is NaN is never offered.  Equal scores inside a group go to the lower position (row number;
+ *   of a row list: the list position).  Scores are ordered as the scan's keys order them: -0.0 below +0.0.
+ *   Group score S[g] = m[0][g], then S = S + m[t][g] for t = 1 .. T-1: plain fp32 adds in this order.  A group that has no
+ *   offer for some t (every selected row of it scored NaN there) is never a result; nor is a group whose S is NaN (+inf and
+ *   -inf met).  +inf ranks first, -inf last.
+ * Output.  The k groups with the largest S, best first, equal S to the LOWER group code: D [k] = S, G [k] = the code;
+ * I_tok [k,T] (may be NULL): the row that gave m[t][G[j]], a physical row number (+ label_offset in the device variant);
+ * D_tok [k,T] (may be NULL): m[t][G[j]].  Fewer than k groups: padded with -FLT_MAX / -1 / -1 / -FLT_MAX.  Reproducible run
+ * to run: integer maxima and a fixed order of the adds.
+ * Arguments.  1 <= T <= 256, 1 <= k <= 64; an L2 index: MVDB_ERR_ARG.  The grouping and the row set are checked as
+ * mvdb_index_search_distinct checks them: refused before anything is enqueued, with nothing written.  An empty index or an
+ * empty set: all padding.
+ * Cost.  A table of T x n_groups x 8 bytes, group-major, held whole for the call: above the index option
+ * "maxsim_table_bytes" (default 2 GiB) the call is MVDB_ERR_ARG and the message states the bytes needed.  One launch clears
+ * it; ceil(T / Tp) passes over the selected rows fill it, each scoring every row against Tp of the vectors held in LDS,
+ * Tp = min(T, 32, 128 KiB / (4 ld)) with ld the row stride in floats (d rounded up to 4); the index option
+ * "maxsim_tokens_per_pass" (1 .. 32; 0, the default: that rule) lowers it — for tests and for measuring what a pass per
+ * vector costs.  Results do not depend on Tp.  Two launches pick the k groups and write the outputs.
+ * The device variant follows the contract of mvdb_index_search_distinct_device: no synchronisation, no host read, one call at
+ * a time per (index, stream), capturable into a hipGraph after one eager call of the same shape (same grouping, same set).
+ * mvdb_index_maxsim_counters: calls served and corpus passes enqueued, both counted on the host.  Either pointer may be NULL.
+ * No reference counterpart. */
+int mvdb_index_search_maxsim(const mvdb_index* idx, const float* q_host /*[T,d]*/, int T, int k, int normalize_q,
+                             const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_host /*[k]*/, int32_t* G_host /*[k]*/,
+                             int64_t* I_tok_host /*[k,T] or NULL*/, float* D_tok_host /*[k,T] or NULL*/);
+int mvdb_index_search_maxsim_device(const mvdb_index* idx, const float* q_dev /*[T,d]*/, int T, int k, int normalize_q,
+                                    const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_dev, int32_t* G_dev,
+                                    int64_t* I_tok_dev /*[k,T] or NULL*/, float* D_tok_dev /*[k,T] or NULL*/,
+                                    int64_t label_offset, void* stream);
+int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long long* passes);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be
@@ -618,7 +658,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * both events on the launch stream around them, and its duration includes those two markers.
  * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "encoder") and returns the number of launches and their summed duration;
+ * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "encoder") and returns the number of launches and their summed duration;
  * pairs recorded while profiling was on stay readable after it is turned off.
  * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
  * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.

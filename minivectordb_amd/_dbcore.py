@@ -1012,6 +1012,74 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, False))
         return out
 
+    # ---- MaxSim search: a question of several vectors, scored per metadata group ----------------------------
+    MAXSIM_MAX_K = 64          # most groups one call returns (include/mvdb.h "MAXSIM SEARCH")
+    MAXSIM_MAX_VECTORS = 256   # most query vectors of one question
+
+    def find_most_similar_maxsim(self, embeddings, group_by, k=5, metadata_filter=None, exclude_filter=None, or_filters=None):
+        """The `k` best GROUPS for ONE question that is several vectors — sub-questions, paraphrases, the token states of a
+        late-interaction encoder: `embeddings` is a 2-D ``[T, d]`` array-like, ``1 <= T <= 256``.  A group (the rows that
+        share a value under the metadata key `group_by`, as in ``find_most_similar_distinct``: a row without the key is a
+        group of its own, an unhashable value is a TypeError naming the id) scores the SUM over the T vectors of its best
+        row for each vector (MaxSim), under the filters of ``find_most_similar``; every vector is normalised on the device.
+        One pass over the selected rows scores each row against up to 32 of the vectors.  No reference counterpart.  Returns
+        ``(ids, scores, metadatas)``, best group first: ``ids[j]`` is a tuple of T unique ids — the row of group j that
+        answered vector t —, ``scores[j]`` the group's sum (np.float32), ``metadatas[j]`` the list of those T metadata
+        dicts.  `k` is clamped to the number of rows the filters select; ``k > 64`` after that is a ValueError."""
+        return self.find_most_similar_maxsim_batch([embeddings], group_by, k, metadata_filter, exclude_filter, or_filters)[0]
+
+    def find_most_similar_maxsim_batch(self, list_of_embeddings, group_by, k=5, metadata_filter=None, exclude_filter=None,
+                                       or_filters=None):
+        """Several questions — a list of ``[T_i, d]`` arrays — under ONE filter: element i is what
+        ``find_most_similar_maxsim(list_of_embeddings[i], ...)`` returns.  One device call per question."""
+        questions = []
+        for e in list_of_embeddings:
+            q = np.ascontiguousarray(np.asarray(e, dtype=np.float32))
+            if q.ndim != 2:
+                raise ValueError("a MaxSim question must be a 2-D array-like [T, d], one query vector per row")
+            if not 1 <= q.shape[0] <= self.MAXSIM_MAX_VECTORS:
+                raise ValueError(f"a MaxSim question holds 1 to {self.MAXSIM_MAX_VECTORS} query vectors (got {q.shape[0]})")
+            if self._mat is not None and q.shape[1] != self._mat.d:
+                raise ValueError(f"query dimension {q.shape[1]} != index dimension {self._mat.d}")
+            questions.append(q)
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be positive")
+        hash(group_by)  # (a metadata key: an unhashable one is the caller's TypeError, before anything is searched)
+        if not questions or self._mat is None:
+            return [([], [], []) for _ in questions]
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_maxsim"):
+                raise NotImplementedError(f"{type(index).__name__} has no MaxSim search")
+            take = min(k, count)
+            if take > self.MAXSIM_MAX_K:
+                raise _DistinctShape(f"k = {take} exceeds {self.MAXSIM_MAX_K}, the most groups a MaxSim search returns")
+            grouping = self._resident_grouping(index, group_by)   # (an unhashable value: its TypeError is not retried)
+            rs = rowset()
+            return [index.search_maxsim(q, take, grouping, rowset=rs, normalize_q=True) for q in questions]
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            return [([], [], []) for _ in questions]
+        uids = self._ids.uids
+        out = []
+        for scores, codes, rows, _ in found:
+            hits = []
+            for j in range(len(codes)):
+                if codes[j] < 0:
+                    continue
+                try:  # a row a concurrent delete has just renumbered away drops its document, as the other searches skip such rows
+                    picked = [int(r) for r in rows[j]]
+                    hits.append((tuple(uids[r] for r in picked), scores[j], [self.metadata[r] for r in picked]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, False))
+        return out
+
     def _group_codes(self, group_by):
         """One pass over the metadata (under the lock): an int32 code per row and the value -> code dict.  Rows that share a
         value share a code; a row without the key gets a code of its own."""

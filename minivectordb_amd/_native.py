@@ -133,6 +133,11 @@ PROTOTYPES = {
     "mvdb_index_search_distinct_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                          c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
     "mvdb_index_distinct_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_search_maxsim": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                c_vp]),
+    "mvdb_index_search_maxsim_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+                                                       c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "mvdb_index_maxsim_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -776,6 +781,41 @@ class FlatIndex:
         """(distinct searches served, queries their one-pass tier answered): running totals, read without synchronising."""
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_distinct_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    # ---- MaxSim search: one question of T vectors, a group scores the sum of its per-vector maxima (include/mvdb.h "MAXSIM SEARCH") ----
+    def search_maxsim(self, q, k, grouping, rowset=None, normalize_q=False, with_tokens=True):
+        """(D float32[k], G int32[k], I_tok int64[k, T], D_tok float32[k, T]) for ONE question q[T, d]: the k groups with the
+        largest sum over the T vectors of the group's best row for each vector, best first (equal sums: the lower code);
+        I_tok[j, t] is the row of group G[j] that answered vector t and D_tok[j, t] its score (both None without
+        with_tokens).  Fewer than k groups end in -FLT_MAX / -1 / -1 / -FLT_MAX."""
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.float32))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"a MaxSim question is a [T, {self.d}] array (got shape {q.shape})")
+        T, k = q.shape[0], int(k)
+        D = np.empty(max(k, 0), dtype=np.float32)
+        G = np.empty(max(k, 0), dtype=np.int32)
+        I_tok = np.empty((max(k, 0), T), dtype=np.int64) if with_tokens else None
+        D_tok = np.empty((max(k, 0), T), dtype=np.float32) if with_tokens else None
+        check(lib().mvdb_index_search_maxsim(self._h, _ptr(q), T, k, int(bool(normalize_q)), grouping._h,
+                                             rowset._h if rowset is not None else None, _ptr(D), _ptr(G),
+                                             _ptr(I_tok) if with_tokens else None, _ptr(D_tok) if with_tokens else None))
+        return D, G, I_tok, D_tok
+
+    def search_maxsim_device(self, q_ptr, T, k, grouping, D_ptr, G_ptr, I_tok_ptr=0, D_tok_ptr=0, rowset=None, stream=0,
+                             normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_maxsim (I_tok: row numbers + label_offset; a 0 pointer: that output is not
+        written); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_search_maxsim_device(
+            self._h, ctypes.c_void_p(q_ptr), int(T), int(k), int(bool(normalize_q)), grouping._h,
+            rowset._h if rowset is not None else None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(G_ptr),
+            ctypes.c_void_p(I_tok_ptr) if I_tok_ptr else None, ctypes.c_void_p(D_tok_ptr) if D_tok_ptr else None,
+            int(label_offset), ctypes.c_void_p(stream)))
+
+    def maxsim_counters(self):
+        """(MaxSim searches served, corpus passes they enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_maxsim_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
 

@@ -22,6 +22,7 @@
 #include "join_scan.hpp"
 #include "mmr_select.hpp"
 #include "distinct_select.hpp"
+#include "maxsim_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
@@ -412,6 +413,9 @@ struct Workspace {
     DevBuf<int> dneed;                   // distinct search: kCoreTile need words of one tile of queries, then the collapse launch's ticket
     DevBuf<uint64_t> dtab;               // ... the table of tier 2, [T slots, n_groups] (distinct_select.hpp)
     DevBuf<int32_t> dG;                  // ... the host entry point's group codes, [nq, k]
+    DevBuf<uint64_t> mxtab;              // MaxSim search: the table of one call, [n_groups, T] (maxsim_scan.hpp) ...
+    DevBuf<uint64_t> mxpart;             // ... the block lists of its top-k launch, [lists, 64] ...
+    DevBuf<char> mxout;                  // ... the host entry point's results, packed: I_tok | D_tok | D | G
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -573,6 +577,8 @@ struct mvdb_index {
     // mirror, written by distinct_collapse_kernel); the calls are counted on the host
     mutable MirroredCounter ds_ctr;
     mutable std::atomic<unsigned long long> ds_calls{0};
+    // MaxSim search: calls served and corpus passes enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -2503,8 +2509,12 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const long long range_cand = idx->kn.range_candidates;
     const int join_shared = idx->kn.join_shared;
     const long long distinct_table = idx->kn.distinct_table_bytes;
+    const long long maxsim_table = idx->kn.maxsim_table_bytes;
+    const int maxsim_tokens = idx->kn.maxsim_tokens_per_pass;
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
+    idx->kn.maxsim_table_bytes = maxsim_table;
+    idx->kn.maxsim_tokens_per_pass = maxsim_tokens;
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
     idx->kn.code8_front_plane = code8_front;
@@ -2551,13 +2561,19 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "distinct_table_bytes") {  // budget of the distinct search's tier-2 table (T slots of 8 n_groups bytes; T >= 1 whatever it is)
         if (value <= 0) return fail(MVDB_ERR_ARG, "distinct_table_bytes must be positive");
         idx->kn.distinct_table_bytes = value;
+    } else if (n == "maxsim_table_bytes") {  // most bytes of the MaxSim search's table (T x n_groups x 8 of one call): a call above it is refused
+        if (value <= 0) return fail(MVDB_ERR_ARG, "maxsim_table_bytes must be positive");
+        idx->kn.maxsim_table_bytes = value;
+    } else if (n == "maxsim_tokens_per_pass") {  // query vectors one corpus pass of a MaxSim search scores (0: as many as the rule allows)
+        if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "maxsim_tokens_per_pass must lie in [0, %d]", kMaxsimPassTokens);
+        idx->kn.maxsim_tokens_per_pass = (int)value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2630,6 +2646,12 @@ int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long l
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->ds_calls.load();
     if (fallback_queries) *fallback_queries = (long long)idx->ds_ctr.read(0);
+    return 0;
+}
+int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long long* passes) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->mx_calls.load();
+    if (passes) *passes = (long long)idx->mx_passes.load();
     return 0;
 }
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
@@ -4377,6 +4399,170 @@ int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev,
     MVDB_TRY(call.rc);
     // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
     return distinct_core(idx, call.ws, call.q, nq, k, fetch_k, normalize_q, grp, rs, label_offset, D_dev, I_dev, G_dev);
+}
+
+}  // extern "C"
+
+// ---- MaxSim search: one question of T vectors, a group scores the sum of its per-vector maxima (maxsim_scan.hpp) ----------
+namespace {
+
+int check_maxsim_args(const mvdb_index* idx, const void* q, int T, int k, const void* D, const void* G) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (!q || !D || !G) return fail(MVDB_ERR_ARG, "NULL buffer passed to search");
+    if (T < 1 || T > kMaxsimMaxTokens) return fail(MVDB_ERR_ARG, "MaxSim search needs 1 <= T <= %d query vectors (got %d)", kMaxsimMaxTokens, T);
+    if (k < 1 || k > kMaxFusedK) return fail(MVDB_ERR_ARG, "MaxSim search needs 1 <= k <= %d (got %d)", kMaxFusedK, k);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "MaxSim search needs an inner-product index");
+    return 0;
+}
+
+// under the index's shared lock, before anything is enqueued: the grouping, the row set, the table against its bound
+int check_maxsim_state(const mvdb_index* idx, int T, const mvdb_grouping* grp, const mvdb_rowset* rs) {
+    MVDB_TRY(grouping_check(idx, grp));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    const long long bytes = (long long)T * (long long)grp->n_groups * 8;
+    if (bytes > idx->kn.maxsim_table_bytes)
+        return fail(MVDB_ERR_ARG, "MaxSim search: the table of %d vectors x %lld groups needs %lld bytes, above the index option maxsim_table_bytes (%lld)",
+                    T, (long long)grp->n_groups, bytes, idx->kn.maxsim_table_bytes);
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_maxsim_kern(const MaxsimScanArgs& a, int device, hipStream_t stream) {
+    void (*kern)(MaxsimScanArgs) = maxsim_scan_kernel<G, C, U, SEL, MASKED>;
+    constexpr int RB = (kWave / G) * U;
+    const size_t lds = maxsim_lds_bytes(a.Tp, a.ld, RB);
+    if (lds > device_lds_per_block(device))
+        return fail(MVDB_ERR_ARG, "MaxSim search: a pass needs %zu bytes of LDS, the device gives a workgroup %zu", lds, device_lds_per_block(device));
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
+    // two resident blocks of eight waves where the vectors leave room for them (the scan's eight waves per CU, twice)
+    const int per_cu = std::min(cached_occupancy((const void*)kern, kMaxsimThreads, lds, 1), 2);
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kMaxsimWaves - 1) / kMaxsimWaves;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+    return profiled_launch("maxsim_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kMaxsimThreads), lds, stream, done, a); },
+                           "maxsim_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// the shapes of launch_scan: a score depends on (G, C, MASKED) only; the rows in flight are maxsim_u's
+int launch_maxsim(const MaxsimScanArgs& a, int device, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            return launch_maxsim_kern<S::G, S::C, maxsim_u(S::G, S::C), F::SEL, F::MASKED>(a, device, s);
+        });
+    });
+}
+
+// The T vectors on the device at stride ld, results to device buffers: the clear, ceil(T / Tp) passes over consecutive ranges
+// of the vectors into their own columns of the table, the block lists, the merge that writes the outputs.
+int maxsim_core(const mvdb_index* idx, Workspace* ws, const float* q, int T, int k, int normalize_q, const mvdb_grouping* grp,
+                const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int32_t* G_dev, int64_t* I_tok_dev, float* D_tok_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->mx_calls;
+    const int64_t m = rs ? rs->count : idx->n;  // rows selected
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {
+        hipLaunchKernelGGL(maxsim_fill_missing_kernel, dim3((unsigned)((k * T + 255) / 256)), dim3(256), 0, s, D_dev, G_dev, I_tok_dev, D_tok_dev, k, T);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    }
+    const int64_t ng = grp->n_groups;
+    const int64_t words = (int64_t)T * ng;
+    const int nlists = (int)std::max<int64_t>(1, std::min<int64_t>((ng + kDistinctThreads - 1) / kDistinctThreads, kMaxsimLists));
+    MVDB_TRY(ws->mxtab.reserve((size_t)words));
+    MVDB_TRY(ws->mxpart.reserve((size_t)nlists * kWave));
+    const int Tp = maxsim_tokens_per_pass(T, idx->ld, idx->kn.maxsim_tokens_per_pass);
+
+    const int clear_gx = (int)std::max<int64_t>(1, std::min<int64_t>((words + 2047) / 2048, 2048));
+    // (the clear runs under the scan's label, as a record of its own: it names no symbol)
+    MVDB_TRY(profiled_launch("maxsim_scan", s, [&](hipEvent_t done) { launch_kernel(maxsim_clear_kernel, dim3(clear_gx), dim3(256), 0, s, done, ws->mxtab.p, words); }));
+
+    MaxsimScanArgs a;
+    a.X = idx->X.p;
+    a.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : idx->n;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.normalize_q = normalize_q;
+    a.rows = rs ? rs->rows : nullptr;
+    a.mask = rs ? rs->mask : nullptr;
+    a.codes = grp->codes;
+    a.T = T;
+    for (int v0 = 0; v0 < T; v0 += Tp) {
+        a.q = q + (int64_t)v0 * idx->ld;
+        a.Tp = std::min(Tp, T - v0);
+        a.table = ws->mxtab.p + v0;
+        MVDB_TRY(launch_maxsim(a, idx->device, s));
+        ++idx->mx_passes;
+    }
+
+    MaxsimTopkArgs t;
+    t.table = ws->mxtab.p;
+    t.n_groups = ng;
+    t.T = T;
+    t.k = k;
+    t.part = ws->mxpart.p;
+    MVDB_TRY(profiled_launch("maxsim_select", s,
+                             [&](hipEvent_t done) { launch_kernel(maxsim_topk_kernel, dim3((unsigned)nlists), dim3(kDistinctThreads), 0, s, done, t); },
+                             "maxsim_topk_kernel"));
+    MaxsimEmitArgs e;
+    e.part = ws->mxpart.p;
+    e.nlists = nlists;
+    e.table = ws->mxtab.p;
+    e.T = T;
+    e.k = k;
+    e.rows = a.rows;
+    e.label_offset = label_offset;
+    e.D = D_dev;
+    e.G = G_dev;
+    e.I_tok = I_tok_dev;
+    e.D_tok = D_tok_dev;
+    MVDB_TRY(profiled_launch("maxsim_select", s, [&](hipEvent_t done) { launch_kernel(maxsim_emit_kernel, dim3(1), dim3(kDistinctThreads), 0, s, done, e); }));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_search_maxsim(const mvdb_index* idx, const float* q_host, int T, int k, int normalize_q, const mvdb_grouping* grp,
+                             const mvdb_rowset* rs, float* D_host, int32_t* G_host, int64_t* I_tok_host, float* D_tok_host) {
+    MVDB_TRY(check_maxsim_args(idx, q_host, T, k, D_host, G_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_maxsim_state(idx, T, grp, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, T));
+    // packed: I_tok [k, T] int64 | D_tok [k, T] fp32 | D [k] fp32 | G [k] int32 -> ONE copy back
+    const size_t kt = (size_t)k * T;
+    const size_t bytes = kt * 12 + (size_t)k * 8;
+    MVDB_TRY(call.ws->mxout.reserve(bytes));
+    char* const out = call.ws->mxout.p;
+    int64_t* I_tok = reinterpret_cast<int64_t*>(out);
+    float* D_tok = reinterpret_cast<float*>(out + kt * 8);
+    float* D = reinterpret_cast<float*>(out + kt * 12);
+    int32_t* G = reinterpret_cast<int32_t*>(out + kt * 12 + (size_t)k * 4);
+    MVDB_TRY(maxsim_core(idx, call.ws, call.ws->q.p, T, k, normalize_q, grp, rs, 0, D, G, I_tok, D_tok));
+    MVDB_TRY(copy_back(call.ws, out, bytes, "MaxSim search"));
+    const char* const pin = (const char*)call.ws->pin_out.p;
+    if (I_tok_host) memcpy(I_tok_host, pin, kt * 8);
+    if (D_tok_host) memcpy(D_tok_host, pin + kt * 8, kt * 4);
+    memcpy(D_host, pin + kt * 12, (size_t)k * 4);
+    memcpy(G_host, pin + kt * 12 + (size_t)k * 4, (size_t)k * 4);
+    return 0;
+}
+
+int mvdb_index_search_maxsim_device(const mvdb_index* idx, const float* q_dev, int T, int k, int normalize_q, const mvdb_grouping* grp,
+                                    const mvdb_rowset* rs, float* D_dev, int32_t* G_dev, int64_t* I_tok_dev, float* D_tok_dev,
+                                    int64_t label_offset, void* stream) {
+    MVDB_TRY(check_maxsim_args(idx, q_dev, T, k, D_dev, G_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_maxsim_state(idx, T, grp, rs));
+    DeviceGuard dg(idx->device);
+    StreamCall call(idx, stream, q_dev, T);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
+    return maxsim_core(idx, call.ws, call.q, T, k, normalize_q, grp, rs, label_offset, D_dev, G_dev, I_tok_dev, D_tok_dev);
 }
 
 }  // extern "C"

@@ -577,6 +577,16 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
 
+    # ---- MaxSim search: not across ranks ----------------------------------------------------------------------------
+    _NO_MAXSIM = ("DistributedShardedVectorDatabase has no MaxSim search: the rows of one group live on several ranks, and the "
+                  "per-group maxima of every query vector are taken on one device (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_maxsim(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MAXSIM)
+
+    def find_most_similar_maxsim_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MAXSIM)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

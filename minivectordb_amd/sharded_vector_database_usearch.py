@@ -176,6 +176,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
 
+    # ---- MaxSim search: not on the int8 cosine index ----------------------------------------------------------------
+    _NO_MAXSIM = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: MaxSim search, an exact fp32 pass "
+                  "with a per-group maximum for every query vector, is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_maxsim(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MAXSIM)
+
+    def find_most_similar_maxsim_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_MAXSIM)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
