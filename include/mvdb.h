@@ -605,6 +605,61 @@ int mvdb_index_search_maxsim_device(const mvdb_index* idx, const float* q_dev /*
                                     int64_t label_offset, void* stream);
 int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long long* passes);
 
+/* ASSIGN AND K-MEANS: questions about the WHOLE corpus in terms of C vectors.  mvdb_index_assign labels every stored row with
+ * the nearest (largest inner product) of C vectors; mvdb_index_kmeans clusters the rows into C clusters with spherical k-means
+ * (Lloyd's algorithm under the inner product, centres of unit length).  Inner-product indexes only: nearest by L2 is out of
+ * scope, an L2 index is MVDB_ERR_ARG.
+ * ASSIGN.  The selected rows are all rows (rs == NULL) or those of a resident row set of any form.
+ *   Outputs are indexed by PHYSICAL row number, [ntotal], whatever form the set has — list, bitmap or excluded.  A row that
+ *   is not selected gets label -1 and score -FLT_MAX; an empty index or an empty set gives all padding.
+ *   Scores.  For a selected row r and vector j the score is BIT FOR BIT what mvdb_index_search / mvdb_index_search_rowset
+ *   returns for c_j alone with nq = 1: the scan's chunk order and butterfly, as MaxSim search defines its scores.  normalize_c
+ *   normalises every vector on its own, with the scan's own prologue.
+ *   Labels.  labels[r] is the j with the largest score, scores ordered as the scan's keys order them (-0.0 below +0.0); equal
+ *   scores go to the LOWER j; a NaN score is never a candidate; a row whose every score is NaN gets -1 / -FLT_MAX.  scores[r]
+ *   (may be NULL) is the winning score.  Reproducible run to run.
+ *   Arguments.  1 <= C <= 4096 — a guard, not a measured limit: every Vp vectors are one corpus pass.  A stale or foreign row
+ *   set is refused before anything is enqueued, with nothing written, as mvdb_index_search_maxsim refuses one.
+ *   Cost.  ceil(C / Vp) passes over the selected rows, each scoring every row against Vp of the vectors held in LDS,
+ *   Vp = min(C, 32, 128 KiB / (4 ld)) — MaxSim's rule; the index option "assign_vectors_per_pass" (1 .. 32; 0, the default:
+ *   that rule) lowers it.  Results do not depend on Vp: a row's running best is carried across the passes as one 64-bit
+ *   (score, inverted j) word, merged by the lanes that own the row with a plain read-compare-write — no floating-point
+ *   atomics, no dependence on the order of arrival, no workgroup waits for another.  Workspace: 8 bytes per stored row plus
+ *   the staged vectors (the host variant packs label and score into the row's word for its one copy back).
+ *   The device variant does no synchronisation and no host read; one call at a time per (index, stream).  Capture into a
+ *   hipGraph is not supported.
+ *   mvdb_index_assign_counters: assignments served (those k-means runs included) and corpus passes enqueued, both counted on
+ *   the host.  Either pointer may be NULL.
+ * K-MEANS.  The loop, exactly (a numpy restatement reproduces every bit: tests/kmeans_oracle.py):
+ *     centres = the initial centres, each normalised by the scan's prologue
+ *     for it = 1 .. max_iter:
+ *         labels = assign(centres)
+ *         if it > 1 and no label changed: stop          (one 8-byte read per iteration: a bulk call)
+ *         centres = update(labels, centres)
+ *     if the loop ran out: labels = assign(centres)
+ *   so the returned labels / scores ALWAYS equal assign(returned centres).  update, for cluster c: its member rows in ascending
+ *   physical row number, cut into chunks of 256 members; each chunk summed element-wise, sequentially in member order, in
+ *   fp64; the chunk partials summed sequentially in chunk order, in fp64 (both sums START at their first term); divided by the
+ *   count in fp64; norm = the square root of the sequential fp64 sum of the squares (product rounded, then added), in element
+ *   order; centre = (float)(mean / norm).  IEEE fp64 throughout.  A cluster with no members keeps its centre; so does one whose
+ *   norm is not a positive finite number (a zero or non-finite mean).  Rows labelled -1 belong to no cluster.
+ *   Outputs.  centres [C,d]: in, the initial centres; out, the final ones.  labels / scores [ntotal] (either may be NULL) as
+ *   assign writes them; counts [C]: members under the returned labels; *iterations (may be NULL): updates performed.
+ *   Bit-identical run to run: the member lists are a stable counting sort (per-slice histograms, a column scan, an ordered
+ *   scatter inside each slice) and no sum depends on scheduling.  No floating-point atomics.
+ *   Arguments.  Those of assign, and max_iter >= 1.
+ *   Workspace.  assign's 8 bytes per stored row; the centres; two label arrays and the member lists, 4 bytes per stored row
+ *   each; the list build's counts, 4 C x min(ceil(n / 2048), 2048) bytes; and (n / 256 + C) x d fp64 chunk partials.
+ * No reference counterpart (the reference delegates its arithmetic to faiss, whose Kmeans is the sibling of IndexFlatIP). */
+int mvdb_index_assign(const mvdb_index* idx, const float* c_host /*[C,d]*/, int C, int normalize_c, const mvdb_rowset* rs /*NULL: every row*/,
+                      int32_t* labels_host /*[ntotal]*/, float* scores_host /*[ntotal] or NULL*/);
+int mvdb_index_assign_device(const mvdb_index* idx, const float* c_dev /*[C,d]*/, int C, int normalize_c, const mvdb_rowset* rs,
+                             int32_t* labels_dev /*[ntotal]*/, float* scores_dev /*[ntotal] or NULL*/, void* stream);
+int mvdb_index_assign_counters(const mvdb_index* idx, long long* calls, long long* passes);
+int mvdb_index_kmeans(const mvdb_index* idx, float* centres_host /*[C,d] in: initial centres, out: final*/, int C, int max_iter,
+                      const mvdb_rowset* rs, int32_t* labels_host /*[ntotal] or NULL*/, float* scores_host /*[ntotal] or NULL*/,
+                      int64_t* counts_host /*[C]*/, int* iterations /*or NULL*/);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be
@@ -658,7 +713,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * both events on the launch stream around them, and its duration includes those two markers.
  * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "encoder") and returns the number of launches and their summed duration;
+ * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "encoder") and returns the number of launches and their summed duration;
  * pairs recorded while profiling was on stay readable after it is turned off.
  * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
  * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.

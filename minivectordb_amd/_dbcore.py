@@ -1080,6 +1080,91 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, False))
         return out
 
+    # ---- clustering: every selected row labelled by the nearest of a few vectors; spherical k-means -----------------
+    ASSIGN_MAX_VECTORS = 4096   # most vectors / clusters of one call (include/mvdb.h "ASSIGN AND K-MEANS")
+
+    def _centre_matrix(self, vectors, what):
+        c = np.ascontiguousarray(np.asarray(vectors, dtype=np.float32))
+        if c.ndim != 2:
+            raise ValueError(f"{what} must be a 2-D array-like [C, d], one vector per row")
+        if not 1 <= c.shape[0] <= self.ASSIGN_MAX_VECTORS:
+            raise ValueError(f"{what} hold 1 to {self.ASSIGN_MAX_VECTORS} vectors (got {c.shape[0]})")
+        if self._mat is not None and c.shape[1] != self._mat.d:
+            raise ValueError(f"vector dimension {c.shape[1]} != index dimension {self._mat.d}")
+        return c
+
+    def _labelled(self, rows, labels, scores):
+        """(ids, labels, scores) of the selected rows, in storage order."""
+        uids = self._ids.uids
+        return [uids[int(r)] for r in rows], np.ascontiguousarray(labels[rows], dtype=np.int32), np.ascontiguousarray(scores[rows], dtype=np.float32)
+
+    def assign_to_nearest(self, vectors, metadata_filter=None, exclude_filter=None, or_filters=None):
+        """Label EVERY stored embedding the filters select with the nearest of `vectors` (a 2-D ``[C, d]`` array-like,
+        ``1 <= C <= 4096``; cosine: rows and vectors are normalised) — tag passages with the closest of a set of label
+        embeddings, route rows to topics, bucket a corpus.  One pass over the selected rows per 32 vectors, on the device;
+        nothing but the labels comes back.  No reference counterpart.  Returns ``(ids, labels, scores)``: `ids` the
+        selected unique ids in storage order, ``labels[i]`` (int32) the index into `vectors` of the nearest one — equal
+        scores go to the lower index, -1 for a row that scores NaN against all of them —, ``scores[i]`` (float32) that
+        score."""
+        c = self._centre_matrix(vectors, "the vectors to assign to")
+        empty = ([], np.empty(0, np.int32), np.empty(0, np.float32))
+        if self._mat is None:
+            return empty
+
+        def search(index, count, rowset, selection):
+            if not hasattr(index, "assign"):
+                raise NotImplementedError(f"{type(index).__name__} has no clustering")
+            labels, scores = index.assign(c, rowset=rowset(), normalize_c=True)
+            return selection.materialize(), labels, scores
+
+        found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search, with_selection=True)
+        return empty if found is None else self._labelled(*found)
+
+    def cluster_embeddings(self, n_clusters, max_iter=25, seed=0, init=None, metadata_filter=None, exclude_filter=None,
+                           or_filters=None):
+        """Cluster the stored embeddings the filters select into `n_clusters` clusters: spherical k-means (Lloyd's algorithm
+        under the cosine), every iteration on the device, bit-identical run to run.  Initial centres: `init`, an
+        ``[n_clusters, d]`` array-like, or — ``init=None`` — the stored rows
+        ``numpy.random.default_rng(seed).choice(selected_rows, n_clusters, replace=False)``.  At most `max_iter` updates of
+        the centres; the run ends earlier once no label changes.  No reference counterpart.  Returns ``(ids, labels, scores,
+        centroids)``: `ids`, `labels` (int32) and `scores` (float32) as ``assign_to_nearest(centroids, ...)`` returns them,
+        `centroids` the float32 ``[n_clusters, d]`` unit-length centres (a cluster that lost every member keeps its centre).
+        Fewer selected rows than `n_clusters` is a ValueError."""
+        n_clusters, max_iter = int(n_clusters), int(max_iter)
+        if not 1 <= n_clusters <= self.ASSIGN_MAX_VECTORS:
+            raise ValueError(f"n_clusters must lie in [1, {self.ASSIGN_MAX_VECTORS}] (got {n_clusters})")
+        if max_iter < 1:
+            raise ValueError("max_iter must be positive")
+        start = None
+        if init is not None:
+            start = self._centre_matrix(init, "the initial centres")
+            if start.shape[0] != n_clusters:
+                raise ValueError(f"init holds {start.shape[0]} centres, n_clusters is {n_clusters}")
+        too_few = "fewer rows selected ({}) than n_clusters ({})"
+        if self._mat is None:
+            raise ValueError(too_few.format(0, n_clusters))
+
+        def search(index, count, rowset, selection):
+            if not hasattr(index, "kmeans"):
+                raise NotImplementedError(f"{type(index).__name__} has no clustering")
+            if count < n_clusters:
+                raise _DistinctShape(too_few.format(count, n_clusters))
+            rows = selection.materialize()
+            centres = start
+            if centres is None:
+                picked = np.random.default_rng(seed).choice(rows, n_clusters, replace=False)
+                centres = np.concatenate([index.get_rows(int(r), 1) for r in picked])
+            centres, labels, scores, _, _ = index.kmeans(centres, max_iter, rowset=rowset())
+            return rows, labels, scores, centres
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search, with_selection=True)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            raise ValueError(too_few.format(0, n_clusters))
+        return self._labelled(*found[:3]) + (found[3],)
+
     def _group_codes(self, group_by):
         """One pass over the metadata (under the lock): an int32 code per row and the value -> code dict.  Rows that share a
         value share a code; a row without the key gets a code of its own."""

@@ -138,6 +138,10 @@ PROTOTYPES = {
     "mvdb_index_search_maxsim_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
                                                        c_vp, c_vp, ctypes.c_int64, c_vp]),
     "mvdb_index_maxsim_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_index_assign_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_assign_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -816,6 +820,51 @@ class FlatIndex:
         """(MaxSim searches served, corpus passes they enqueued): running totals counted on the host."""
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_maxsim_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    # ---- assignment and k-means: every stored row labelled by the nearest of C vectors (include/mvdb.h "ASSIGN AND K-MEANS") ----
+    def _centres(self, c):
+        c = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
+        if c.ndim != 2 or c.shape[1] != self.d:
+            raise ValueError(f"the vectors to assign to are a [C, {self.d}] array (got shape {c.shape})")
+        return c
+
+    def assign(self, c, rowset=None, normalize_c=False, with_scores=True):
+        """(labels int32[ntotal], scores float32[ntotal]) for the vectors c[C, d]: per PHYSICAL row the vector with the largest
+        inner product (equal scores: the lower vector) and that score; a row outside `rowset`, or whose every score is NaN,
+        gets -1 / -FLT_MAX.  scores is None without with_scores."""
+        c = self._centres(c)
+        n = self.ntotal
+        labels = np.empty(n, dtype=np.int32)
+        scores = np.empty(n, dtype=np.float32) if with_scores else None
+        check(lib().mvdb_index_assign(self._h, _ptr(c), c.shape[0], int(bool(normalize_c)), rowset._h if rowset is not None else None,
+                                      _ptr(labels), _ptr(scores) if with_scores else None))
+        return labels, scores
+
+    def assign_device(self, c_ptr, C, labels_ptr, scores_ptr=0, rowset=None, stream=0, normalize_c=False):
+        """Device-pointer variant of assign (a 0 scores pointer: not written); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_assign_device(
+            self._h, ctypes.c_void_p(c_ptr), int(C), int(bool(normalize_c)), rowset._h if rowset is not None else None,
+            ctypes.c_void_p(labels_ptr), ctypes.c_void_p(scores_ptr) if scores_ptr else None, ctypes.c_void_p(stream)))
+
+    def kmeans(self, centres, max_iter=25, rowset=None):
+        """Spherical k-means from the initial `centres` [C, d]: (centres float32[C, d], labels int32[ntotal], scores
+        float32[ntotal], counts int64[C], iterations).  labels / scores are assign(returned centres); counts the members
+        under them; iterations the updates performed.  Bit-identical run to run."""
+        centres = self._centres(centres).copy()
+        n = self.ntotal
+        labels = np.empty(n, dtype=np.int32)
+        scores = np.empty(n, dtype=np.float32)
+        counts = np.zeros(centres.shape[0], dtype=np.int64)
+        iterations = ctypes.c_int(0)
+        check(lib().mvdb_index_kmeans(self._h, _ptr(centres), centres.shape[0], int(max_iter), rowset._h if rowset is not None else None,
+                                      _ptr(labels), _ptr(scores), _ptr(counts), ctypes.byref(iterations)))
+        return centres, labels, scores, counts, int(iterations.value)
+
+    def assign_counters(self):
+        """(assignments served — those of k-means included —, corpus passes they enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_assign_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
 

@@ -102,6 +102,30 @@ __device__ __forceinline__ void maxsim_butterfly(float (&s)[U]) {
     }
 }
 
+// One query vector into the registers of the G lanes that own it (lane t of the group: chunks c * G + t), normalised or not:
+// flat_scan_kernel's prologue, the same operation order.  Every lane of the wave runs it (the reduction needs them all on).
+// Shared by the MaxSim pass and the assignment pass (assign_scan.hpp), which also writes k-means' centres with it.
+template <int G, int C>
+__device__ __forceinline__ void maxsim_load_vector(const float* qptr, int t, const bool (&cvalid)[C], int normalize, f32x4 (&qv)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int chunk = c * G + t;
+        qv[c] = cvalid[c] ? *reinterpret_cast<const f32x4*>(qptr + chunk * 4) : f32x4{0, 0, 0, 0};
+    }
+    if (normalize) {
+        float nr = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            nr += qv[c].x * qv[c].x + qv[c].y * qv[c].y + qv[c].z * qv[c].z + qv[c].w * qv[c].w;
+        nr = group_reduce_add<G>(nr);
+        if (nr > 0.f) {
+            const float inorm = 1.0f / sqrtf(nr);
+#pragma unroll
+            for (int c = 0; c < C; ++c) qv[c] *= inorm;
+        }
+    }
+}
+
 struct MaxsimScanArgs {
     const float* X;        // [n_phys, ld] corpus
     int64_t n;             // rows to score (m for a row list)
@@ -144,24 +168,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_scan_kernel(MaxsimScanA
             const int v = v0 + gi;
             const bool live = v < Tp;
             f32x4 qv[C];
-            const float* qptr = a.q + (int64_t)(live ? v : 0) * a.ld;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int chunk = c * G + t;
-                qv[c] = cvalid[c] ? *reinterpret_cast<const f32x4*>(qptr + chunk * 4) : f32x4{0, 0, 0, 0};
-            }
-            if (a.normalize_q) {
-                float nr = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    nr += qv[c].x * qv[c].x + qv[c].y * qv[c].y + qv[c].z * qv[c].z + qv[c].w * qv[c].w;
-                nr = group_reduce_add<G>(nr);
-                if (nr > 0.f) {
-                    const float inorm = 1.0f / sqrtf(nr);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) qv[c] *= inorm;
-                }
-            }
+            maxsim_load_vector<G, C>(a.q + (int64_t)(live ? v : 0) * a.ld, t, cvalid, a.normalize_q, qv);
             if (live) {
 #pragma unroll
                 for (int c = 0; c < C; ++c)

@@ -23,6 +23,7 @@
 #include "mmr_select.hpp"
 #include "distinct_select.hpp"
 #include "maxsim_scan.hpp"
+#include "assign_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
@@ -416,6 +417,14 @@ struct Workspace {
     DevBuf<uint64_t> mxtab;              // MaxSim search: the table of one call, [n_groups, T] (maxsim_scan.hpp) ...
     DevBuf<uint64_t> mxpart;             // ... the block lists of its top-k launch, [lists, 64] ...
     DevBuf<char> mxout;                  // ... the host entry point's results, packed: I_tok | D_tok | D | G
+    DevBuf<uint64_t> asbest;             // assignment: the running best of every stored row, one word each (assign_scan.hpp)
+    DevBuf<float> kmc;                   // k-means: the centres, [C, ld] ...
+    DevBuf<int32_t> kmlab[2];            // ... the labels of this iteration and of the one before, [n] each ...
+    DevBuf<uint32_t> kmmem;              // ... the member lists, label after label, [n] ...
+    DevBuf<uint32_t> kmhist;             // ... the list build's counts, [C, slices] ...
+    DevBuf<int64_t> kmcount;             // ... members per label, [C], then the changed-label count ...
+    DevBuf<uint32_t> kmoff;              // ... the lists' bases [C + 1], then the work items' bases [C + 1] ...
+    DevBuf<double> kmpart;               // ... the chunk partials, [n / 256 + C, d]
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -579,6 +588,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> ds_calls{0};
     // MaxSim search: calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
+    // assignment (and the assignments of k-means): calls served and corpus passes enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> as_calls{0}, as_passes{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -2511,10 +2522,12 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const long long distinct_table = idx->kn.distinct_table_bytes;
     const long long maxsim_table = idx->kn.maxsim_table_bytes;
     const int maxsim_tokens = idx->kn.maxsim_tokens_per_pass;
+    const int assign_vectors = idx->kn.assign_vectors_per_pass;
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
     idx->kn.maxsim_tokens_per_pass = maxsim_tokens;
+    idx->kn.assign_vectors_per_pass = assign_vectors;
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
     idx->kn.code8_front_plane = code8_front;
@@ -2567,13 +2580,16 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "maxsim_tokens_per_pass") {  // query vectors one corpus pass of a MaxSim search scores (0: as many as the rule allows)
         if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "maxsim_tokens_per_pass must lie in [0, %d]", kMaxsimPassTokens);
         idx->kn.maxsim_tokens_per_pass = (int)value;
+    } else if (n == "assign_vectors_per_pass") {  // vectors one corpus pass of an assignment scores (0: as many as the rule allows)
+        if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "assign_vectors_per_pass must lie in [0, %d]", kMaxsimPassTokens);
+        idx->kn.assign_vectors_per_pass = (int)value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2652,6 +2668,12 @@ int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long lon
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->mx_calls.load();
     if (passes) *passes = (long long)idx->mx_passes.load();
+    return 0;
+}
+int mvdb_index_assign_counters(const mvdb_index* idx, long long* calls, long long* passes) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->as_calls.load();
+    if (passes) *passes = (long long)idx->as_passes.load();
     return 0;
 }
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
@@ -4563,6 +4585,275 @@ int mvdb_index_search_maxsim_device(const mvdb_index* idx, const float* q_dev, i
     MVDB_TRY(call.rc);
     // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
     return maxsim_core(idx, call.ws, call.q, T, k, normalize_q, grp, rs, label_offset, D_dev, G_dev, I_tok_dev, D_tok_dev);
+}
+
+}  // extern "C"
+
+// ---- assignment and k-means: every stored row labelled by the nearest of C vectors (assign_scan.hpp) -----------------------
+namespace {
+
+int check_assign_args(const mvdb_index* idx, const void* c, int C) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (!c) return fail(MVDB_ERR_ARG, "NULL buffer passed to assign");
+    if (C < 1 || C > kAssignMaxVectors) return fail(MVDB_ERR_ARG, "assignment needs 1 <= C <= %d vectors (got %d)", kAssignMaxVectors, C);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "assignment needs an inner-product index");
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_assign_kern(const AssignScanArgs& a, int device, hipStream_t stream) {
+    void (*kern)(AssignScanArgs) = assign_scan_kernel<G, C, U, SEL, MASKED>;
+    constexpr int RB = (kWave / G) * U;
+    const size_t lds = 4 * (size_t)a.Vp * (size_t)a.ld;
+    if (lds > device_lds_per_block(device))
+        return fail(MVDB_ERR_ARG, "assignment: a pass needs %zu bytes of LDS, the device gives a workgroup %zu", lds, device_lds_per_block(device));
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
+    // MaxSim's grid: two resident blocks of eight waves where the vectors leave room for them
+    const int per_cu = std::min(cached_occupancy((const void*)kern, kMaxsimThreads, lds, 1), 2);
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kMaxsimWaves - 1) / kMaxsimWaves;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+    return profiled_launch("assign_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kMaxsimThreads), lds, stream, done, a); },
+                           "assign_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// MaxSim's forms, from the one shape table
+int launch_assign(const AssignScanArgs& a, int device, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            return launch_assign_kern<S::G, S::C, maxsim_u(S::G, S::C), F::SEL, F::MASKED>(a, device, s);
+        });
+    });
+}
+
+int utility_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048, 2048)); }
+
+// The C vectors on the device at stride ld -> ws->asbest, a word per stored row: the clear, then ceil(C / Vp) passes over
+// consecutive ranges of the vectors.
+int assign_core(const mvdb_index* idx, Workspace* ws, const float* c, int C, int normalize_c, const mvdb_rowset* rs) {
+    hipStream_t s = ws->stream;
+    ++idx->as_calls;
+    const int64_t n = idx->n;
+    MVDB_TRY(ws->asbest.reserve((size_t)std::max<int64_t>(n, 1)));
+    MVDB_TRY(profiled_launch("assign_scan", s, [&](hipEvent_t done) { launch_kernel(assign_clear_kernel, dim3(utility_grid(n)), dim3(256), 0, s, done, ws->asbest.p, n); }));
+    const int64_t m = rs ? rs->count : n;  // rows selected
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) return 0;
+    const int Vp = assign_vectors_per_pass(C, idx->ld, idx->kn.assign_vectors_per_pass);
+    AssignScanArgs a;
+    a.X = idx->X.p;
+    a.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : n;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.normalize_q = normalize_c;
+    a.rows = rs ? rs->rows : nullptr;
+    a.mask = rs ? rs->mask : nullptr;
+    a.best = ws->asbest.p;
+    for (int v0 = 0; v0 < C; v0 += Vp) {
+        a.q = c + (int64_t)v0 * idx->ld;
+        a.Vp = std::min(Vp, C - v0);
+        a.v0 = v0;
+        MVDB_TRY(launch_assign(a, idx->device, s));
+        ++idx->as_passes;
+    }
+    return 0;
+}
+
+// the words -> labels / scores (either may be NULL), or packed in place for the host entry points' one copy back
+int assign_emit(const mvdb_index* idx, Workspace* ws, int32_t* labels, float* scores, bool pack) {
+    AssignEmitArgs e;
+    e.best = ws->asbest.p;
+    e.n = idx->n;
+    e.labels = labels;
+    e.scores = scores;
+    e.pack = pack ? 1 : 0;
+    hipLaunchKernelGGL(assign_emit_kernel, dim3(utility_grid(idx->n)), dim3(256), 0, ws->stream, e);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// the packed words of every row to the host, unpacked
+int assign_fetch(const mvdb_index* idx, Workspace* ws, int32_t* labels_host, float* scores_host, const char* what) {
+    const int64_t n = idx->n;
+    if (n == 0 || (!labels_host && !scores_host)) return 0;
+    MVDB_TRY(copy_back(ws, ws->asbest.p, (size_t)n * 8, what));
+    const uint64_t* const w = (const uint64_t*)ws->pin_out.p;
+    for (int64_t i = 0; i < n; ++i) {
+        if (labels_host) labels_host[i] = (int32_t)(uint32_t)w[i];
+        if (scores_host) {
+            const uint32_t bits = (uint32_t)(w[i] >> 32);
+            memcpy(&scores_host[i], &bits, 4);
+        }
+    }
+    return 0;
+}
+
+int launch_normalize(const mvdb_index* idx, const float* src, float* dst, int nv, hipStream_t s) {
+    return with_scan_shape(idx->d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(idx->d4, false, false, [&](auto form) {
+            using F = decltype(form);
+            const int64_t threads = (int64_t)nv * S::G;
+            hipLaunchKernelGGL((assign_normalize_kernel<S::G, S::C, F::MASKED>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, src, dst, nv,
+                               idx->ld, idx->d4);
+            MVDB_HIP(hipGetLastError());
+            return 0;
+        });
+    });
+}
+
+// slices of the list build: about 2048 rows each, at most kKmeansSlices
+struct KmeansSlices {
+    int nb;
+    int64_t per;
+};
+KmeansSlices kmeans_slices(int64_t n) {
+    KmeansSlices k;
+    k.nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048, kKmeansSlices));
+    k.per = std::max<int64_t>(1, (n + k.nb - 1) / k.nb);
+    return k;
+}
+
+// labels -> counts per label (ws->kmcount) and, with `lists`, the member lists and the work items' bases
+int kmeans_lists(const mvdb_index* idx, Workspace* ws, const int32_t* labels, int C, bool lists) {
+    hipStream_t s = ws->stream;
+    const int64_t n = idx->n;
+    const KmeansSlices sl = kmeans_slices(n);
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(sl.nb), dim3(256), (size_t)C * 4, s, labels, n, sl.per, C, sl.nb, ws->kmhist.p);
+    hipLaunchKernelGGL(kmeans_colscan_kernel, dim3(C), dim3(kWave), 0, s, ws->kmhist.p, sl.nb, ws->kmcount.p);
+    if (lists) {
+        uint32_t* const base = ws->kmoff.p;
+        hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(1), dim3(kWave), 0, s, ws->kmcount.p, C, base, base + C + 1);
+        hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(sl.nb), dim3(kWave), (size_t)C * 4, s, labels, n, sl.per, C, sl.nb, ws->kmhist.p, base, ws->kmmem.p);
+    }
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// one update of the centres from the labels: the lists, the chunk sums, the finalise
+int kmeans_update(const mvdb_index* idx, Workspace* ws, const int32_t* labels, int C) {
+    hipStream_t s = ws->stream;
+    MVDB_TRY(kmeans_lists(idx, ws, labels, C, true));
+    const int64_t items = idx->n / kKmeansChunk + C;  // at most: a label's last chunk may be short
+    KmeansSumArgs a;
+    a.X = idx->X.p;
+    a.ld = idx->ld;
+    a.d = idx->d;
+    a.C = C;
+    a.members = ws->kmmem.p;
+    a.base = ws->kmoff.p;
+    a.ioff = ws->kmoff.p + C + 1;
+    a.part = ws->kmpart.p;
+    hipLaunchKernelGGL(kmeans_chunksum_kernel, dim3((unsigned)items), dim3(kKmeansChunk), 0, s, a);
+    KmeansFinalArgs f;
+    f.part = ws->kmpart.p;
+    f.ioff = a.ioff;
+    f.count = ws->kmcount.p;
+    f.centres = ws->kmc.p;
+    f.ld = idx->ld;
+    f.d = idx->d;
+    hipLaunchKernelGGL(kmeans_finalise_kernel, dim3(C), dim3(256), 0, s, f);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_assign(const mvdb_index* idx, const float* c_host, int C, int normalize_c, const mvdb_rowset* rs, int32_t* labels_host,
+                      float* scores_host) {
+    MVDB_TRY(check_assign_args(idx, c_host, C));
+    if (!labels_host) return fail(MVDB_ERR_ARG, "NULL buffer passed to assign");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(c_host, C));
+    MVDB_TRY(assign_core(idx, call.ws, call.ws->q.p, C, normalize_c, rs));
+    MVDB_TRY(assign_emit(idx, call.ws, nullptr, nullptr, true));
+    return assign_fetch(idx, call.ws, labels_host, scores_host, "assign");
+}
+
+int mvdb_index_assign_device(const mvdb_index* idx, const float* c_dev, int C, int normalize_c, const mvdb_rowset* rs, int32_t* labels_dev,
+                             float* scores_dev, void* stream) {
+    MVDB_TRY(check_assign_args(idx, c_dev, C));
+    if (!labels_dev) return fail(MVDB_ERR_ARG, "NULL buffer passed to assign");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    StreamCall call(idx, stream, c_dev, C);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises
+    MVDB_TRY(assign_core(idx, call.ws, call.q, C, normalize_c, rs));
+    return assign_emit(idx, call.ws, labels_dev, scores_dev, false);
+}
+
+int mvdb_index_kmeans(const mvdb_index* idx, float* centres_host, int C, int max_iter, const mvdb_rowset* rs, int32_t* labels_host,
+                      float* scores_host, int64_t* counts_host, int* iterations) {
+    MVDB_TRY(check_assign_args(idx, centres_host, C));
+    if (!counts_host) return fail(MVDB_ERR_ARG, "NULL buffer passed to kmeans");
+    if (max_iter < 1) return fail(MVDB_ERR_ARG, "k-means needs max_iter >= 1 (got %d)", max_iter);
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    hipStream_t s = ws->stream;
+    const int64_t n = idx->n;
+    const KmeansSlices sl = kmeans_slices(n);
+    const size_t nrows = (size_t)std::max<int64_t>(n, 1);
+    MVDB_TRY(ws->kmc.reserve((size_t)C * idx->ld));
+    MVDB_TRY(ws->kmlab[0].reserve(nrows));
+    MVDB_TRY(ws->kmlab[1].reserve(nrows));
+    MVDB_TRY(ws->kmmem.reserve(nrows));
+    MVDB_TRY(ws->kmhist.reserve((size_t)C * sl.nb));
+    MVDB_TRY(ws->kmcount.reserve((size_t)C + 1));
+    MVDB_TRY(ws->kmoff.reserve(2 * ((size_t)C + 1)));
+    MVDB_TRY(ws->kmpart.reserve((size_t)(n / kKmeansChunk + C) * idx->d));
+    unsigned long long* const changed_dev = reinterpret_cast<unsigned long long*>(ws->kmcount.p + C);
+
+    // centres = initial, each normalised by the scan's prologue (the padding of a row stays zero: staged so)
+    MVDB_TRY(call.stage(centres_host, C));
+    MVDB_HIP(hipMemsetAsync(ws->kmc.p, 0, (size_t)C * idx->ld * sizeof(float), s));
+    MVDB_TRY(launch_normalize(idx, ws->q.p, ws->kmc.p, C, s));
+
+    int cur = 0, updates = 0;
+    bool converged = false;
+    for (int it = 1; it <= max_iter; ++it) {
+        MVDB_TRY(assign_core(idx, ws, ws->kmc.p, C, 0, rs));
+        MVDB_TRY(assign_emit(idx, ws, ws->kmlab[cur].p, nullptr, false));
+        if (it > 1) {
+            MVDB_HIP(hipMemsetAsync(changed_dev, 0, 8, s));
+            hipLaunchKernelGGL(kmeans_changed_kernel, dim3(utility_grid(n)), dim3(256), 0, s, ws->kmlab[cur].p, ws->kmlab[cur ^ 1].p, n, changed_dev);
+            MVDB_HIP(hipGetLastError());
+            MVDB_TRY(copy_back(ws, changed_dev, 8, "k-means"));  // the one read of an iteration
+            if (*(const unsigned long long*)ws->pin_out.p == 0ull) {
+                converged = true;
+                break;
+            }
+        }
+        MVDB_TRY(kmeans_update(idx, ws, ws->kmlab[cur].p, C));
+        ++updates;
+        cur ^= 1;
+    }
+    if (!converged) {  // the loop ran out: the labels of the centres as they are now
+        MVDB_TRY(assign_core(idx, ws, ws->kmc.p, C, 0, rs));
+        MVDB_TRY(assign_emit(idx, ws, ws->kmlab[cur].p, nullptr, false));
+    }
+    // ws->asbest is the assignment of the returned centres in both cases, ws->kmlab[cur] its labels
+    MVDB_TRY(kmeans_lists(idx, ws, ws->kmlab[cur].p, C, false));
+    MVDB_TRY(copy_back(ws, ws->kmcount.p, (size_t)C * 8, "k-means"));
+    memcpy(counts_host, ws->pin_out.p, (size_t)C * 8);
+    MVDB_TRY(copy_back(ws, ws->kmc.p, (size_t)C * idx->ld * sizeof(float), "k-means"));
+    for (int c = 0; c < C; ++c) memcpy(centres_host + (size_t)c * idx->d, (const float*)ws->pin_out.p + (size_t)c * idx->ld, (size_t)idx->d * sizeof(float));
+    MVDB_TRY(assign_emit(idx, ws, nullptr, nullptr, true));
+    MVDB_TRY(assign_fetch(idx, ws, labels_host, scores_host, "k-means"));
+    if (iterations) *iterations = updates;
+    return 0;
 }
 
 }  // extern "C"

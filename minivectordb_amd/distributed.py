@@ -587,6 +587,16 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_maxsim_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_MAXSIM)
 
+    # ---- clustering (assign_to_nearest, cluster_embeddings): not here ------------------------------------------------------------
+    _NO_CLUSTERING = ("DistributedShardedVectorDatabase has no clustering: every rank holds a part of the rows, and neither the labels nor the "
+                      "centres' partial sums are exchanged between ranks (use ShardedVectorDatabase on one device)")
+
+    def assign_to_nearest(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_CLUSTERING)
+
+    def cluster_embeddings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_CLUSTERING)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

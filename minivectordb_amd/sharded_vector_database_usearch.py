@@ -186,6 +186,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_maxsim_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_MAXSIM)
 
+    # ---- clustering (assign_to_nearest, cluster_embeddings): not here ------------------------------------------------------------
+    _NO_CLUSTERING = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: clustering, exact fp32 passes that label "
+                      "every row by its nearest centre, is not implemented (use ShardedVectorDatabase)")
+
+    def assign_to_nearest(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_CLUSTERING)
+
+    def cluster_embeddings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_CLUSTERING)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
