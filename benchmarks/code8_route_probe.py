@@ -10,6 +10,7 @@ this file copied into its benchmarks/ — the index has no count of refined rows
 
   python3 benchmarks/code8_route_probe.py                              # 10M x 512, the grid the library picks
   python3 benchmarks/code8_route_probe.py --blocks 2,3,4               # MVDB_SCAN_BLOCKS_PER_CU swept in-process
+  python3 benchmarks/code8_route_probe.py --front 2 --front-u 1,2,4 --blocks 1,2,3,4   # the front form's tiles per batch x its grid
   python3 benchmarks/code8_route_probe.py --family positive            # the all-positive corpus (or: clustered)
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 benchmarks/code8_route_probe.py --timers 0
       (one trace session with both kernels: 200 route steps, then 40 exact scans; --timers 0 keeps the library's event
@@ -35,6 +36,8 @@ def main():
     ap.add_argument("--blocks", default="0", help="comma list of MVDB_SCAN_BLOCKS_PER_CU values (0 = the library's choice)")
     ap.add_argument("--family", default="zero_mean", choices=["zero_mean", "positive", "clustered"], help="the synthetic corpus and its queries")
     ap.add_argument("--timers", type=int, default=1, help="0: no per-launch event timers (for runs under a tracer)")
+    ap.add_argument("--front-u", default="0", help="comma list of MVDB_CODE8_FRONT_U values, tiles per batch of the front form (0 = the library's "
+                    "choice; d = 512, the quad layout: 1, 2, 4; the other widths: 4, 8), swept in-process with --blocks")
     ap.add_argument("--front", type=int, default=1, help="index option code8_front_plane: 1 the library decides, 2 always the front form, "
                     "3 the plane kept and never streamed, 0 no plane")
     args = ap.parse_args()
@@ -109,12 +112,13 @@ def main():
     want = results(8)
     idx.set_option("code8_single_query", 1)
     run(0, 3)   # the third eligible query builds the code
-    for blocks in args.blocks.split(","):
+    for front_u, blocks in [(u, b) for u in args.front_u.split(",") for b in args.blocks.split(",")]:
         os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = blocks if int(blocks) > 0 else ""
+        os.environ["MVDB_CODE8_FRONT_U"] = front_u if int(front_u) > 0 else ""
         idx.reload_env()
         got = results(8)
         same = all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(got, want))
-        rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks)})
+        rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks), "front_u": int(front_u)})
         fb, cand, calls = idx.code8_counters()
         cands = []
         for i in range(W, W + min(K, 32)):
@@ -124,6 +128,7 @@ def main():
                    candidates_min_median_max=[int(min(cands)), float(np.median(cands)), int(max(cands))], candidates=cands)
         print(json.dumps(rec), flush=True)
     os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = ""
+    os.environ["MVDB_CODE8_FRONT_U"] = ""
     idx.reload_env()
     idx.set_option("code8_single_query", 0)
     if args.exact_steps > 0:

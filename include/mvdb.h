@@ -164,6 +164,13 @@ int mvdb_index_code8_front_counters(const mvdb_index* idx, long long* survivors,
  * plane and its 5 d / 8-byte image in the front plane (mvdb_code8_front_unpack).  Any pointer may be NULL. */
 int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high, uint8_t* low, uint8_t* front);
 
+/* Diagnostic: where the device keeps the two parts of a row's 32-code chunk in the front plane of an index of width d — the
+ * byte offsets of its 16-byte part and of its 4-byte part from the start of the plane.  The plane is stored in tiles of the
+ * rows one wave-instruction of the prefilter covers; at d = 512 a tile is 16 rows in five 1-KiB slabs (a lane quad per row,
+ * four chunks per lane), at the other widths the 16-byte parts of the tile's rows and behind them the 4-byte parts.  Pure host
+ * arithmetic: the very functions every reader and writer of the plane uses. */
+int mvdb_code8_front_offset(int d, int64_t row, int chunk, int64_t* wide, int64_t* narrow);
+
 /* Diagnostic: how the prefilter's launch shares n rows of width d (384 / 512 / 1024) out on `device`: wave w of `waves`
  * takes the batches w, w + waves, ... of rows_per_batch consecutive rows.  Tests plant rows by it. */
 int mvdb_code8_scan_geometry(int d, int64_t n, int device, int* rows_per_batch, int* waves);

@@ -75,6 +75,7 @@ PROTOTYPES = {
     "mvdb_code8_front_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_code8_front_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_index_code8_read_row": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_code8_front_offset": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_code8_scan_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_dim": (ctypes.c_int, [c_vp]),
     "mvdb_index_device": (ctypes.c_int, [c_vp]),
@@ -1226,6 +1227,14 @@ def code8_front_geometry(d, n, device=0):
     rb, waves = ctypes.c_int(0), ctypes.c_int(0)
     check(lib().mvdb_code8_front_geometry(int(d), int(n), int(device), ctypes.byref(rb), ctypes.byref(waves)))
     return int(rb.value), int(waves.value)
+
+
+def code8_front_offset(d, row, chunk):
+    """(wide, narrow): the byte offsets of the 16-byte and the 4-byte part of chunk `chunk` of stored row `row` in the front
+    plane of an index of width d (include/mvdb.h: mvdb_code8_front_offset)."""
+    wide, narrow = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().mvdb_code8_front_offset(int(d), int(row), int(chunk), ctypes.byref(wide), ctypes.byref(narrow)))
+    return int(wide.value), int(narrow.value)
 
 
 def code8_scan_geometry(d, n, device=0):

@@ -138,28 +138,56 @@ inline void code8_unpack_row(int d, const uint8_t* high, const uint8_t* low, int
 // g * 16 * (d / 32), chunk t at 16 t — and behind them the narrow parts, row g at g * 4 * (d / 32), chunk t at 4 t.  A
 // 16-byte load per lane then reads one contiguous span of the tile per wave-instruction, and so does the 4-byte load.  The
 // plane is sized in whole tiles (code8_front_bytes): the rows of the last tile past the row count are never written.
+//
+// The QUAD layout (d = kCode8QuadDim): a lane QUAD per row, lane t of the quad owns the four chunks 4 t .. 4 t + 3 (128 codes),
+// so a tile is the 16 rows of one wave-instruction and every load of the stream is 16 bytes per lane.  The tile's
+// 16 x 5 d / 8 = 5 KiB are five contiguous 1-KiB slabs, lane (g, t) — row g of the tile — at (4 g + t) * 16 of each: slab
+// s = 0 .. 3 holds the wide part of chunk 4 t + s, slab 4 the narrow parts of the chunks 4 t .. 4 t + 3 as one 16-byte unit.
+// The row image (code8_front_pack_row) is the same in both layouts; only where its parts lie on the device differs, and every
+// reader and writer of the plane goes through code8_front_wide_offset / code8_front_narrow_offset.
 constexpr uint32_t kCode8FrontMask = 0xF8F8F8F8u;
+#ifdef MVDB_CODE8_ABLATE
+constexpr int kCode8QuadDim = 0;     // the timing-ablation library (Makefile: ABLATE) runs the one-chunk-per-lane form at every width
+#else
+constexpr int kCode8QuadDim = 512;   // the width that keeps the quad layout (0: none)
+#endif
+constexpr int kCode8QuadChunks = 4;  // chunks per lane of the quad layout
 __host__ __device__ inline bool code8_front_dim(int d) { return d > 0 && d % 32 == 0 && d <= 2048; }
 __host__ __device__ inline int code8_front_stride(int d) { return d / 8 * 5; }
-// lanes per row of the scan's front form: the chunks of a row, rounded up to a power of two (the others are masked off)
-__host__ __device__ inline int code8_front_lanes(int d) {
+// lanes per row of the scan's front form: the chunks of a row, rounded up to a power of two (the others are masked off) —
+// a quarter of them in the quad layout
+__host__ __device__ constexpr int code8_front_lanes(int d) {
+    if (d == kCode8QuadDim) return d / (32 * kCode8QuadChunks);
     int g = 1;
     while (g * 32 < d) g *= 2;
     return g;
 }
+// whether the plane of this width is laid out in quads: a lane owns kCode8QuadChunks chunks
+__host__ __device__ constexpr bool code8_front_quad(int d) { return code8_front_lanes(d) * 32 * kCode8QuadChunks == d; }
 __host__ __device__ inline int code8_front_tile_rows(int d) { return 64 / code8_front_lanes(d); }
 __host__ __device__ inline size_t code8_front_bytes(int64_t cap, int d) {
     const int64_t R = code8_front_tile_rows(d);
     return (size_t)((cap + R - 1) / R * R) * (size_t)code8_front_stride(d);
 }
-// byte offsets of a row's wide parts (16 * d / 32 bytes) and narrow parts (4 * d / 32 bytes) in the plane
-__host__ __device__ inline size_t code8_front_wide_offset(int64_t row, int d) {
+// byte offsets of the wide part (16 bytes) and the narrow part (4 bytes) of chunk `chunk` of a row in the plane
+__host__ __device__ inline size_t code8_front_wide_offset(int64_t row, int chunk, int d) {
     const int64_t R = code8_front_tile_rows(d);
-    return (size_t)(row / R * R) * (size_t)code8_front_stride(d) + (size_t)(row % R) * (size_t)(d / 2);
+    const size_t tile = (size_t)(row / R * R) * (size_t)code8_front_stride(d);
+    if (code8_front_quad(d)) {
+        const int L = code8_front_lanes(d);
+        return tile + (size_t)(chunk % kCode8QuadChunks) * (size_t)(R * L * 16) + (size_t)((row % R) * L + chunk / kCode8QuadChunks) * 16;
+    }
+    return tile + (size_t)(row % R) * (size_t)(d / 2) + (size_t)chunk * 16;
 }
-__host__ __device__ inline size_t code8_front_narrow_offset(int64_t row, int d) {
+__host__ __device__ inline size_t code8_front_narrow_offset(int64_t row, int chunk, int d) {
     const int64_t R = code8_front_tile_rows(d);
-    return (size_t)(row / R * R) * (size_t)code8_front_stride(d) + (size_t)R * (size_t)(d / 2) + (size_t)(row % R) * (size_t)(d / 8);
+    const size_t tile = (size_t)(row / R * R) * (size_t)code8_front_stride(d);
+    if (code8_front_quad(d)) {
+        const int L = code8_front_lanes(d);
+        return tile + (size_t)kCode8QuadChunks * (size_t)(R * L * 16) + (size_t)((row % R) * L + chunk / kCode8QuadChunks) * 16 +
+               (size_t)(chunk % kCode8QuadChunks) * 4;
+    }
+    return tile + (size_t)R * (size_t)(d / 2) + (size_t)(row % R) * (size_t)(d / 8) + (size_t)chunk * 4;
 }
 
 __host__ __device__ inline void code8_front_pack_chunk(const uint32_t (&c)[8], uint32_t (&f)[5]) {
@@ -267,10 +295,10 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
                 code8_front_pack_chunk(oct, f);
                 const int fpart = lane & 7;
                 if (fpart < 4)
-                    reinterpret_cast<uint32_t*>(front + code8_front_wide_offset(front_row0 + row, d))[4 * (c >> 3) + fpart] =
+                    reinterpret_cast<uint32_t*>(front + code8_front_wide_offset(front_row0 + row, c >> 3, d))[fpart] =
                         fpart == 0 ? f[0] : fpart == 1 ? f[1] : fpart == 2 ? f[2] : f[3];
                 else if (fpart == 4)
-                    reinterpret_cast<uint32_t*>(front + code8_front_narrow_offset(front_row0 + row, d))[c >> 3] = f[4];
+                    *reinterpret_cast<uint32_t*>(front + code8_front_narrow_offset(front_row0 + row, c >> 3, d)) = f[4];
             }
         }
 #pragma unroll
@@ -582,6 +610,19 @@ __device__ __forceinline__ int code8_reduce(int (&T)[U], int t) {
 // T, and runs the predicate itself on T: what is appended is what the one-plane prefilter appended, row for row.
 typedef int i32x3 __attribute__((ext_vector_type(3), aligned(4)));
 
+// the narrow parts a lane of the front form holds per tile: the dword of its one chunk, or (the quad form) the 16-byte unit
+// of its four chunks
+template <bool QUAD>
+struct Code8Narrow {
+    typedef int type;
+    static __device__ __forceinline__ int part(int v, int) { return v; }
+};
+template <>
+struct Code8Narrow<true> {
+    typedef i32x4 type;
+    static __device__ __forceinline__ int part(const i32x4& v, int s) { return v[s]; }
+};
+
 //
 // The front form (GF > 0: GF lanes per row, UF tiles per batch).  Stage 0 in front of the two: the loop streams the FRONT plane
 // (H5 = c & ~7, 5 d / 8 bytes per row; a lane holds a 32-code chunk: one 16-byte and one 4-byte load), has T5 = Q . H5 and
@@ -590,13 +631,19 @@ typedef int i32x3 __attribute__((ext_vector_type(3), aligned(4)));
 // wave; gather0() fetches their chunks of the high plane and their (a, r) in this kernel's (G, U) geometry, forms T6 with
 // `scores` and hands it to stage 1: from there on the row goes the way it goes in the other form.  What is appended is the
 // same set of rows; only the order of the appends differs.
+// The quad form of stage 0 (GF = 4 at d = 512, the quad layout of the plane): a lane quad per row, a lane holds four chunks —
+// five 16-byte loads per lane and tile, each one contiguous KiB per wave-instruction, 64 v_dot4 into one (hi, lo) pair, two
+// quad-local DPP adds (code8_reduce<4, UF>) — and UF counts tiles of 16 rows.  T5 is the same integer: everything behind
+// it is the other form's, statement for statement.
 template <int G, int U, bool MASKED, int GF = 0, int UF = 0>
 __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
     constexpr int RB = RPI * U;
     constexpr bool FRONT = GF > 0;
     static_assert(U >= 2 && U <= 8 && (U & (U - 1)) == 0 && U <= G, "code8_reduce halves U down to one value inside a row group");
-    static_assert(!FRONT || (UF >= 2 && UF <= 8 && (UF & (UF - 1)) == 0 && UF <= GF && kWave % GF == 0), "the same, for the front form");
+    // (the quad form: a lane holds kCode8QuadChunks chunks of an unmasked row of 16 G codes; one tile per batch is allowed)
+    constexpr bool QUAD = FRONT && !MASKED && GF * 32 * kCode8QuadChunks == G * 16;
+    static_assert(!FRONT || (UF >= (QUAD ? 1 : 2) && UF <= 8 && (UF & (UF - 1)) == 0 && UF <= GF && kWave % GF == 0), "the same, for the front form");
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = lane % G;
@@ -767,12 +814,21 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         const int tf = lane % GF;
         const int gf = lane / GF;
         const bool validf = !MASKED || tf * 32 < a.d;
-        i32x4 fh[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, fl[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        if (validf) {
+        // the chunks a lane holds: one, or (the quad form) the chunks NC tf .. NC tf + NC - 1 — 32 NC dimensions of the query's
+        // planes, 4 NC i32x4; their narrow parts arrive as ONE word of the lane's (one dword, or the quad layout's 16-byte unit)
+        constexpr int NC = QUAD ? kCode8QuadChunks : 1;
+        typedef typename Code8Narrow<QUAD>::type narrow_t;
+        i32x4 fh[NC][2], fl[NC][2];
+#pragma unroll
+        for (int s = 0; s < NC; ++s) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                fh[i] = *reinterpret_cast<const i32x4*>(a.qhi + tf * 32 + 16 * i);
-                fl[i] = *reinterpret_cast<const i32x4*>(a.qlo + tf * 32 + 16 * i);
+                fh[s][i] = i32x4{0, 0, 0, 0};
+                fl[s][i] = i32x4{0, 0, 0, 0};
+                if (validf) {
+                    fh[s][i] = *reinterpret_cast<const i32x4*>(a.qhi + (tf * NC + s) * 32 + 16 * i);
+                    fl[s][i] = *reinterpret_cast<const i32x4*>(a.qlo + (tf * NC + s) * 32 + 16 * i);
+                }
             }
         }
         int uef = 0;
@@ -792,17 +848,23 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         }
 
         // (c & ~7) of the lane's chunks against the query's planes: T5
-        auto scores0 = [&](const i32x4 (&xw)[UF], const int (&xn)[UF], int (&T)[UF]) {
+        // (ONE running (hi, lo) pair over the lane's chunks, T5 = hi * 256 + lo formed once: the partial sums are smaller in
+        // magnitude than the bound of the row's total, so the int32 argument holds for them)
+        auto scores0 = [&](const i32x4 (&xw)[UF][NC], const narrow_t (&xn)[UF], int (&T)[UF]) {
 #pragma unroll
             for (int u = 0; u < UF; ++u) {
-                const uint32_t f[5] = {(uint32_t)xw[u].x, (uint32_t)xw[u].y, (uint32_t)xw[u].z, (uint32_t)xw[u].w, (uint32_t)xn[u]};
-                uint32_t c[8];
-                code8_front_unpack_chunk(f, c);
                 int hi = 0, lo = 0;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    hi = __builtin_amdgcn_sdot4((int)c[j], fh[j >> 2][j & 3], hi, false);
-                    lo = __builtin_amdgcn_sdot4((int)c[j], fl[j >> 2][j & 3], lo, false);
+                for (int s = 0; s < NC; ++s) {
+                    const uint32_t f[5] = {(uint32_t)xw[u][s].x, (uint32_t)xw[u][s].y, (uint32_t)xw[u][s].z, (uint32_t)xw[u][s].w,
+                                           (uint32_t)Code8Narrow<QUAD>::part(xn[u], s)};
+                    uint32_t c[8];
+                    code8_front_unpack_chunk(f, c);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        hi = __builtin_amdgcn_sdot4((int)c[j], fh[s][j >> 2][j & 3], hi, false);
+                        lo = __builtin_amdgcn_sdot4((int)c[j], fl[s][j >> 2][j & 3], lo, false);
+                    }
                 }
                 T[u] = hi * 256 + lo;
             }
@@ -855,33 +917,46 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             }
         };
 
+        // one tile's loads of a lane: NC 16-byte loads and the narrow word, each a contiguous span of the tile per
+        // wave-instruction.  The quad layout: five 1-KiB slabs, the lane's unit at lane * 16 of each.
         const int nch = a.d / 32;
         const int64_t tile_bytes = (int64_t)RPF * code8_front_stride(a.d);
         const int64_t batch_bytes = (int64_t)UF * tile_bytes;
-        const int wide_off = gf * 16 * nch + tf * 16;
-        const int narrow_off = RPF * 16 * nch + gf * 4 * nch + tf * 4;
+        constexpr int slab = QUAD ? kWave * 16 : 0;
+        const int wide_off = QUAD ? lane * 16 : gf * 16 * nch + tf * 16;
+        const int narrow_off = QUAD ? NC * slab + lane * 16 : RPF * 16 * nch + gf * 4 * nch + tf * 4;
         const int64_t nfull = a.n / RBF;
-        auto load0 = [&](i32x4 (&xw)[UF], int (&xn)[UF], float2& sr, int64_t b) {
+        auto load_tile = [&](const uint8_t* tile, i32x4 (&w)[NC], narrow_t& nr) __attribute__((always_inline)) {
+            const narrow_t* ns = reinterpret_cast<const narrow_t*>(tile + narrow_off);
+#pragma unroll
+            for (int s = 0; s < NC; ++s) {
+                const i32x4* ws = reinterpret_cast<const i32x4*>(tile + s * slab + wide_off);
+                if (MASKED)
+                    w[s] = validf ? __builtin_nontemporal_load(ws) : i32x4{0, 0, 0, 0};
+                else
+                    w[s] = __builtin_nontemporal_load(ws);
+            }
+#ifdef MVDB_CODE8_ABLATE
+            nr = narrow_t{};   // (the timing ablation: the narrow loads left out — the results are wrong, only the time counts)
+            (void)ns;
+#else
+            if (MASKED)
+                nr = validf ? __builtin_nontemporal_load(ns) : narrow_t{};
+            else
+                nr = __builtin_nontemporal_load(ns);
+#endif
+        };
+        auto load0 = [&](i32x4 (&xw)[UF][NC], narrow_t (&xn)[UF], float2& sr, int64_t b) {
             const uint8_t* base = a.front + b * batch_bytes;
 #pragma unroll
-            for (int u = 0; u < UF; ++u) {
-                const i32x4* ws = reinterpret_cast<const i32x4*>(base + u * tile_bytes + wide_off);
-                const int* ns = reinterpret_cast<const int*>(base + u * tile_bytes + narrow_off);
-                if (MASKED) {
-                    xw[u] = validf ? __builtin_nontemporal_load(ws) : i32x4{0, 0, 0, 0};
-                    xn[u] = validf ? __builtin_nontemporal_load(ns) : 0;
-                } else {
-                    xw[u] = __builtin_nontemporal_load(ws);
-                    xn[u] = __builtin_nontemporal_load(ns);
-                }
-            }
+            for (int u = 0; u < UF; ++u) load_tile(base + u * tile_bytes, xw[u], xn[u]);
             sr = a.ar[b * RBF + erowf];
         };
         // the head, as in the other form: the first batch's loads, then the floor
         int64_t b = gw;
         const bool head = b < nfull;
-        i32x4 xw0[UF];
-        int xn0[UF];
+        i32x4 xw0[UF][NC];
+        narrow_t xn0[UF];
         float2 sr0 = make_float2(0.f, 0.f);
         if (head) load0(xw0, xn0, sr0, b);
         floor = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane(
@@ -894,8 +969,8 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             b += nwaves_total;
         }
         for (; b < nfull; b += nwaves_total) {
-            i32x4 xw[UF];
-            int xn[UF];
+            i32x4 xw[UF][NC];
+            narrow_t xn[UF];
             float2 sr;
             load0(xw, xn, sr, b);
             int T[UF];
@@ -907,22 +982,13 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         if (nfull * RBF < a.n && nfull % nwaves_total == gw) {
             const int64_t last = a.n - 1;
             const int64_t last_tile = last / RPF;
-            i32x4 xw[UF];
-            int xn[UF];
+            i32x4 xw[UF][NC];
+            narrow_t xn[UF];
 #pragma unroll
             for (int u = 0; u < UF; ++u) {
                 int64_t tile = nfull * UF + u;
                 tile = tile < last_tile ? tile : last_tile;
-                const uint8_t* base = a.front + tile * tile_bytes;
-                const i32x4* ws = reinterpret_cast<const i32x4*>(base + wide_off);
-                const int* ns = reinterpret_cast<const int*>(base + narrow_off);
-                if (MASKED) {
-                    xw[u] = validf ? __builtin_nontemporal_load(ws) : i32x4{0, 0, 0, 0};
-                    xn[u] = validf ? __builtin_nontemporal_load(ns) : 0;
-                } else {
-                    xw[u] = __builtin_nontemporal_load(ws);
-                    xn[u] = __builtin_nontemporal_load(ns);
-                }
+                load_tile(a.front + tile * tile_bytes, xw[u], xn[u]);
             }
             const int64_t r = nfull * RBF + erowf;
             const float2 sr = a.ar[r < last ? r : last];

@@ -2198,7 +2198,8 @@ bool code8_route_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_de
 // 12 bytes per lane, not 16 — its own U and blocks per CU (SCAN_U, SCAN_BLOCKS).  All measured per shape: DESIGN.md section
 // 4.1b.  launch(Code8Shape<...>{}) for d; the exact-scan shapes of the route come from with_scan_shape.
 // The front form of code8_scan_kernel (it streams the front plane, a 32-code chunk per lane): FRONT_G lanes per row
-// (code8_front_lanes: the plane's tiles are 64 / FRONT_G rows), FRONT_U tiles per batch, FRONT_BLOCKS per CU.
+// (code8_front_lanes: the plane's tiles are 64 / FRONT_G rows), FRONT_U tiles per batch, FRONT_BLOCKS per CU.  At d = 512 the
+// plane has the quad layout (code8_front_quad): FRONT_G = 4, a lane holds four chunks of its row.
 // FRONT_DEFAULT: whether option code8_front_plane = 1 keeps and streams the plane at this width (measured: DESIGN.md section
 // 4.1b — at d = 1024 the front form loses on the zero-mean corpus, whose stage 0 leaves 11 % of the rows; the diagnostic
 // values 2 and 3 of the option still build the plane there).
@@ -2213,7 +2214,9 @@ template <typename Launch>
 int with_code8_shape(int d, Launch launch) {
     switch (d) {
         case 384: return launch(Code8Shape<32, 8, true, 8, 4, 16, 8, 2, true>{});
-        case 512: return launch(Code8Shape<32, 4, false, 8, 2, 16, 4, 2, true>{});
+        // (the quad layout of the front plane, code8_front_quad: a lane quad per row, FRONT_U tiles of 16 rows per batch.
+        // Two tiles — 10 KiB of loads per wave — on ONE block per CU: the sweep's best cell, profiles/code8_front_sweep.jsonl)
+        case 512: return launch(Code8Shape<32, 4, false, 8, 2, code8_front_lanes(512), code8_front_quad(512) ? 2 : 4, code8_front_quad(512) ? 1 : 2, true>{});
         case 1024: return launch(Code8Shape<64, 4, false, 8, 2, 32, 4, 2, false>{});
         default: return fail(MVDB_ERR_ARG, "internal: no int8 prefilter kernel for d = %d", d);
     }
@@ -2261,13 +2264,15 @@ int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
 // Which form of the prefilter serves this call: the front form where the code holds the plane, unless its window has
 // suspended it (the survivors of stage 0 pay three gathered lines each: past kCode8FrontShare of the rows the other form is
 // faster) — option value 2 keeps it on.  One decision per call; no synchronisation (the mirrored words lag).
-constexpr double kCode8FrontShare = 0.12;
+// The quad form runs one block per CU: fewer gathers are in flight, a survivor costs more and the lines cross earlier
+// (measured again on the three 10M x 512 corpora: DESIGN.md section 4.1b).
+constexpr double kCode8FrontShare = 0.12, kCode8FrontShareQuad = 0.08;
 bool code8_front_serves(const mvdb_index* idx) {
     if (!idx->code.F5.p || !code8_front_wanted(idx->kn.code8_front_plane, idx->d)) return false;
     if (idx->kn.code8_front_plane >= 2) return idx->kn.code8_front_plane == 2;   // (diagnostic values: always / never)
     const volatile unsigned long long* sum = idx->c8_ctr.mirror<unsigned long long>();
     return !idx->c8_front.suspended_mean(sum ? sum + 2 : nullptr, idx->c8_ctr.mirror() ? idx->c8_ctr.mirror() + 6 : nullptr,
-                                         kCode8FrontShare * (double)idx->n);
+                                         (code8_front_quad(idx->d) ? kCode8FrontShareQuad : kCode8FrontShare) * (double)idx->n);
 }
 
 // The floor's launch.  The stored sample streams; every block leaves one list, which every block of the prefilter merges.
@@ -2380,9 +2385,18 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
         if (!front) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
-        const int fu = kn().code8_front_u == 4 || kn().code8_front_u == 8 ? kn().code8_front_u : K::FRONT_U;   // (tuning hook)
-        if (fu == 4) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 4>(c, idx->device, s);
-        return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 8>(c, idx->device, s);
+        const int hook = kn().code8_front_u;   // (tuning hook)
+        if constexpr (code8_front_quad(K::G * 16) && !K::MASKED) {
+            // the quad layout: a batch is 16 UF rows and must divide the stage of 64
+            const int fu = hook == 1 || hook == 2 || hook == 4 ? hook : K::FRONT_U;
+            if (fu == 1) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 1>(c, idx->device, s);
+            if (fu == 2) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 2>(c, idx->device, s);
+            return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 4>(c, idx->device, s);
+        } else {
+            const int fu = hook == 4 || hook == 8 ? hook : K::FRONT_U;
+            if (fu == 4) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 4>(c, idx->device, s);
+            return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, 8>(c, idx->device, s);
+        }
     }));
     // 3. the fallback decision and the exact scores of the candidates, ties by row: one sorted k-list per active block
     Code8RescoreArgs r;
@@ -2759,9 +2773,24 @@ int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high,
     if (high) MVDB_HIP(hipMemcpy(high, c.C8.p + row * code8_high_stride(d), code8_high_stride(d), hipMemcpyDeviceToHost));
     if (low) MVDB_HIP(hipMemcpy(low, c.low(d) + row * code8_low_stride(d), code8_low_stride(d), hipMemcpyDeviceToHost));
     if (front) {
-        MVDB_HIP(hipMemcpy(front, c.F5.p + code8_front_wide_offset(row, d), d / 2, hipMemcpyDeviceToHost));
-        MVDB_HIP(hipMemcpy(front + d / 2, c.F5.p + code8_front_narrow_offset(row, d), d / 8, hipMemcpyDeviceToHost));
+        // the row's tile in one copy; the image is put together chunk by chunk, by the offsets the writers use
+        const int64_t R = code8_front_tile_rows(d);
+        const size_t tile_bytes = (size_t)R * (size_t)code8_front_stride(d);
+        const size_t tile_at = (size_t)(row / R * R) * (size_t)code8_front_stride(d);
+        std::vector<uint8_t> tile(tile_bytes);
+        MVDB_HIP(hipMemcpy(tile.data(), c.F5.p + tile_at, tile_bytes, hipMemcpyDeviceToHost));
+        for (int t = 0; t < d / 32; ++t) {
+            memcpy(front + 16 * t, tile.data() + (code8_front_wide_offset(row, t, d) - tile_at), 16);
+            memcpy(front + d / 2 + 4 * t, tile.data() + (code8_front_narrow_offset(row, t, d) - tile_at), 4);
+        }
     }
+    return 0;
+}
+int mvdb_code8_front_offset(int d, int64_t row, int chunk, int64_t* wide, int64_t* narrow) {
+    if (!code8_front_dim(d) || row < 0 || chunk < 0 || chunk >= d / 32 || !wide || !narrow)
+        return fail(MVDB_ERR_ARG, "mvdb_code8_front_offset: bad arguments (d a multiple of 32, at most 2048; chunk in [0, d / 32))");
+    *wide = (int64_t)code8_front_wide_offset(row, chunk, d);
+    *narrow = (int64_t)code8_front_narrow_offset(row, chunk, d);
     return 0;
 }
 int mvdb_code8_margin(int d, float qnorm, float qstep, float row_norm_bound, float* alpha, float* beta) {
