@@ -901,7 +901,7 @@ class Grouping:
 
 class RowSet:
     """mvdb_rowset*: a filter's rows resident on the device (a bitmap for dense / excluded sets, a row list otherwise).
-    Valid until the index it was built on gains or loses a row."""
+    Valid until the index it was built on loses a row or is reset; rows appended later are not part of it (include/mvdb.h)."""
 
     def __init__(self, index, rows, excluded=False):
         rows = np.ascontiguousarray(rows, dtype=np.int64)
