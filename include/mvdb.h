@@ -667,6 +667,72 @@ int mvdb_index_kmeans(const mvdb_index* idx, float* centres_host /*[C,d] in: ini
                       const mvdb_rowset* rs, int32_t* labels_host /*[ntotal] or NULL*/, float* scores_host /*[ntotal] or NULL*/,
                       int64_t* counts_host /*[C]*/, int* iterations /*or NULL*/);
 
+/* PROBED SEARCH: the stored rows partitioned into C member lists by their nearest centre; a query is scored against the C
+ * centres and only the lists of its nprobe best centres are scanned.  The library's one APPROXIMATE route: it is taken only
+ * by these entry points, never by another call.  Only the choice of lists is approximate — given the lists, the answer is
+ * exact and bit for bit the single-query scan's.  Inner-product indexes only: an L2 index is MVDB_ERR_ARG, as for assign.
+ * Partition.  A resident object, a sibling of mvdb_grouping, on the index's device: the centres [C, ld] in fp32 after their
+ * own normalisation, one int32 label per stored row, the member lists as uint32 row numbers — ascending inside each list —
+ * and C + 1 offsets: 8 bytes per stored row plus the centres.  1 <= C <= 4096 (assign's guard).
+ *   create.  normalize_c normalises each centre with the scan's prologue, exactly as assign does.  labels_host == NULL: the
+ *   library labels every row itself with assign's pass; the labels are integer for integer what mvdb_index_assign(centres,
+ *   normalize_c) returns.  labels_host given: used as is, each checked on the host to lie in [-1, C); they need not be the
+ *   nearest centres.  A row labelled -1 is in no list and is never a result (so a row that scores NaN against every centre).
+ *   The lists come from the stable counting sort of k-means: they do not depend on scheduling.
+ *   Validity.  The partition belongs to its index, identified by the index's serial number, not its address.  A search refuses
+ *   with MVDB_ERR_ARG, before anything is enqueued and with nothing written, when the partition belongs to another index,
+ *   when the row count differs (rows were added since) or when rows were removed since.  mvdb_index_set_rows renumbers
+ *   nothing: the partition stays valid, a changed row stays in its old list and is scored with its new vector until update
+ *   names it.
+ *   update.  Brings the partition to the index's current state after adds and set_rows: the rows [mvdb_partition_rows(p),
+ *   ntotal) and the m listed rows are assigned to their nearest centres — one assign under a list-form selection of just
+ *   those rows, their new labels again what mvdb_index_assign gives for them —, written into the label array, and the lists
+ *   are rebuilt.  Cost: the rows touched plus one counting sort over the labels.  After a removal it is refused: read the
+ *   labels back (mvdb_partition_labels), drop the removed rows' and re-create from them.  update excludes the searches and
+ *   readers of the same partition (host calls; searches enqueued by the device variant must have finished).
+ *   labels / centres / sizes read the label array, the stored centres [C,d] and the list sizes [C] back; rows is the row
+ *   count the partition covers, lists is C.
+ * Search contract, per query i.
+ *   Probes.  P_i is the set of valid entries of what mvdb_index_search returns for (q_i, nq = 1, k = nprobe, normalize_q) on an
+ *   inner-product index whose rows are exactly the partition's stored centres, as mvdb_partition_centres returns them, added
+ *   without normalisation: that call's scores, its order, ties to the lower centre, NaN never a candidate.  An empty list
+ *   still takes a probe slot.
+ *   Result.  Row i of (D, I) is bit for bit what mvdb_index_search_rowset returns with nq = 1 and the same k for the ascending
+ *   list of the rows whose label lies in P_i, restricted to the rows of rs when rs is given: scores are the single-query
+ *   scan's bits for the index's (G, C, MASKED) shape, ties go to the lower row number, padding is -1 / -FLT_MAX, labels are
+ *   row numbers (+ label_offset in the device variant); a query whose every score is NaN gets all missing markers.
+ *   nprobe = C: the exact search over every row whose label is >= 0.
+ * Arguments.  nq >= 1, 1 <= k <= 64, 1 <= nprobe <= C.  rs: NULL or a BITMAP-form set (mvdb_rowset_is_bitmap), excluded form
+ *   included, checked like every row-set search checks it (a stale or foreign set is refused); a LIST-form set is
+ *   MVDB_ERR_ARG — a filter that small is already cheap on the exact gathered scan (mvdb_index_search_rowset).
+ * Cost.  Per chunk of queries four launches: the coarse scores (the single-query scan over the centre matrix, a grid row per
+ *   query), the plan (a workgroup per query orders its C keys in LDS, keeps nprobe and cuts their lists into work items of
+ *   128 list positions), the gathered scan of the items (the grid is sized on the host from the nprobe LARGEST lists;
+ *   blocks beyond a query's real item count return at once) and a segmented merge.  Bytes: the centres, then (4 ld + 4) per
+ *   row of the probed lists.  The item and candidate tables of a chunk stay within the index option "probe_table_bytes"
+ *   (default 256 MiB; at least one query per chunk); results do not depend on the chunking.
+ * The device variant does no synchronisation and no host read; one call at a time per (index, stream).  Capture into a
+ * hipGraph is not supported: a capturing stream is MVDB_ERR_ARG.
+ * mvdb_index_probe_counters: probed searches served and launches they enqueued, both counted on the host.  Either pointer may
+ * be NULL.
+ * No reference counterpart. */
+typedef struct mvdb_partition mvdb_partition;
+int mvdb_partition_create(const mvdb_index* idx, const float* centres_host /*[C,d]*/, int C, int normalize_c,
+                          const int32_t* labels_host /*[ntotal], each in [-1, C); or NULL*/, mvdb_partition** out);
+int mvdb_partition_update(mvdb_partition* p, const mvdb_index* idx, const int64_t* changed_rows_host /*[m] or NULL*/, int64_t m);
+int mvdb_partition_labels(const mvdb_partition* p, int64_t row0, int64_t n, int32_t* labels_host /*[n]*/);
+int mvdb_partition_centres(const mvdb_partition* p, float* centres_host /*[C,d]*/);
+int mvdb_partition_sizes(const mvdb_partition* p, int64_t* counts_host /*[C]*/);
+int64_t mvdb_partition_rows(const mvdb_partition* p);
+int mvdb_partition_lists(const mvdb_partition* p);
+int mvdb_partition_free(mvdb_partition* p);
+int mvdb_index_search_probe(const mvdb_index* idx, const mvdb_partition* p, const float* q_host, int nq, int k, int nprobe,
+                            int normalize_q, const mvdb_rowset* rs /*NULL or a bitmap-form set*/, float* D_host, int64_t* I_host);
+int mvdb_index_search_probe_device(const mvdb_index* idx, const mvdb_partition* p, const float* q_dev, int nq, int k, int nprobe,
+                                   int normalize_q, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                                   void* stream);
+int mvdb_index_probe_counters(const mvdb_index* idx, long long* calls, long long* probe_launches);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be

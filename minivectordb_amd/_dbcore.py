@@ -551,6 +551,7 @@ class FilterAndRerankMixin:
         else:
             doomed = set(rows)
             self.metadata[:] = [m for r, m in enumerate(self.metadata) if r not in doomed]
+        self._partition_rows_removed(rows)
         self._mat.delete(rows, self.index)
         self._note_write()
         self._embeddings_changed = True
@@ -1165,6 +1166,169 @@ class FilterAndRerankMixin:
             raise ValueError(too_few.format(0, n_clusters))
         return self._labelled(*found[:3]) + (found[3],)
 
+    # ---- probed search: a k-means partition of the rows, a query scans the lists of its nprobe nearest centres ----------------
+    PROBE_MAX_K = 64
+
+    def build_partition(self, n_clusters=None, max_iter=10, seed=0, train_rows=None, centroids=None):
+        """Partition the stored embeddings into `n_clusters` lists by their nearest centre, for ``find_most_similar_approx``.
+        `n_clusters` defaults to ``min(4096, max(1, round(sqrt(n))))``.  The centres come from spherical k-means (at most
+        `max_iter` updates) over ``min(n, train_rows or 256 * n_clusters)`` stored rows drawn by
+        ``numpy.random.default_rng(seed)``, which also draws the initial centres among them; then EVERY row is labelled by its
+        nearest centre on the device.  ``centroids=`` (an ``[n_clusters, d]`` array-like, e.g. a saved
+        ``partition_centroids()``) skips the training.  The partition lives on the device (8 bytes per row plus the
+        centres), follows later stores, updates and deletes by itself and is not persisted.  Returns the list sizes
+        (int64 ``[n_clusters]``).  No reference counterpart."""
+        with self.lock:
+            if self._mat is None or self._mat.n == 0:
+                raise ValueError("a partition needs stored embeddings")
+            if self._embeddings_changed:
+                self._build_index()
+            index, n = self.index, self._mat.n
+            if not hasattr(index, "partition"):
+                raise NotImplementedError(f"{type(index).__name__} has no probed search")
+            if centroids is not None:
+                centres = self._centre_matrix(centroids, "the centroids")
+                if n_clusters is not None and int(n_clusters) != centres.shape[0]:
+                    raise ValueError(f"centroids hold {centres.shape[0]} centres, n_clusters is {n_clusters}")
+                part = index.partition(centres, labels=None, normalize_c=True)
+            else:
+                C = min(self.ASSIGN_MAX_VECTORS, max(1, int(round(np.sqrt(n))))) if n_clusters is None else int(n_clusters)
+                if not 1 <= C <= min(n, self.ASSIGN_MAX_VECTORS):
+                    raise ValueError(f"n_clusters must lie in [1, {min(n, self.ASSIGN_MAX_VECTORS)}] (got {C})")
+                if int(max_iter) < 1:
+                    raise ValueError("max_iter must be positive")
+                rng = np.random.default_rng(seed)
+                m = min(n, int(train_rows) if train_rows else 256 * C)
+                if m < C:
+                    raise ValueError(f"train_rows ({m}) is below n_clusters ({C})")
+                sample = np.sort(rng.choice(n, m, replace=False)) if m < n else None
+                picked = rng.choice(sample if sample is not None else n, C, replace=False)
+                start = np.concatenate([index.get_rows(int(r), 1) for r in picked])
+                centres = index.kmeans(start, int(max_iter), rowset=index.rowset(sample) if sample is not None else None)[0]
+                part = index.partition(centres, labels=None, normalize_c=False)
+            self.__dict__["_partition"] = {"index": index, "part": part, "labels": None, "centres": part.centres(), "changed": set()}
+            return part.sizes()
+
+    def drop_partition(self):
+        """Forget the partition (its device memory goes with the last search that holds it)."""
+        with self.lock:
+            self.__dict__["_partition"] = None
+
+    def partition_centroids(self):
+        """float32 ``[n_clusters, d]``: the partition's centres as stored (unit length); ``build_partition(centroids=...)``
+        rebuilds the same partition from them without k-means."""
+        with self.lock:
+            state = self.__dict__.get("_partition")
+            if state is None:
+                raise ValueError("there is no partition: call build_partition first")
+            return state["centres"].copy()
+
+    def _partition_rows_changed(self, rows):
+        """update_embeddings_batch wrote new vectors into these rows (caller holds the lock): the next approximate search
+        assigns them again."""
+        state = self.__dict__.get("_partition")
+        if state is not None:
+            state["changed"].update(int(r) for r in rows)
+
+    def _partition_rows_removed(self, rows):
+        """A delete removed these stacked rows, ascending (caller holds the lock): the labels come back to the host once, the
+        removed rows' labels are dropped, and the next approximate search re-creates the partition from what is left — no
+        k-means, no re-assign."""
+        state = self.__dict__.get("_partition")
+        if state is None or not len(rows):
+            return
+        if state["part"] is not None:
+            state["labels"] = state["part"].labels()
+            state["part"] = None   # dropped, not freed: a search running outside the lock may still hold it
+        rows = np.asarray(rows, dtype=np.int64)
+        labels = state["labels"]
+        state["labels"] = np.delete(labels, rows[rows < labels.shape[0]])
+        doomed = set(int(r) for r in rows)
+        state["changed"] = {r - int(np.searchsorted(rows, r)) for r in state["changed"] if r not in doomed}
+
+    def _resident_partition(self, index):
+        """The partition, brought to the index's current rows (takes the lock).  After stores: ``update``, which labels the new
+        rows; after ``update_embedding``: the same call with the changed rows; after a delete: re-created from the labels
+        that are left.  A ValueError where the device index is no longer the state the rows describe: `_search_selected`
+        starts over."""
+        with self.lock:
+            if self._embeddings_changed or self.index is not index:
+                raise ValueError("the index changed between the filter and the search")
+            state = self.__dict__.get("_partition")
+            if state is None or state["index"] is not index:
+                raise _DistinctShape("there is no partition: call build_partition first")
+            n = index.ntotal
+            part, changed = state["part"], state["changed"]
+            if part is None:
+                kept = state["labels"]
+                labels = np.full(n, -1, dtype=np.int32)
+                labels[:kept.shape[0]] = kept
+                changed.update(range(kept.shape[0], n))
+                part = state["part"] = index.partition(state["centres"], labels=labels, normalize_c=False)
+                state["labels"] = None
+            if len(part) < n or changed:
+                part.update(sorted(changed))
+                changed.clear()
+            return part
+
+    def find_most_similar_approx(self, embedding, k=5, nprobe=8, metadata_filter=None, exclude_filter=None, or_filters=None,
+                                 autocut=False):
+        """``find_most_similar`` over the lists of the `nprobe` centres nearest to the query only (``build_partition``
+        first): the ONE search here whose answer can differ from ``find_most_similar`` — a true neighbour that lives in a
+        list the query does not probe is missed.  Given the lists the answer is exact (the same scores, ties to the earlier
+        row); ``nprobe`` is clipped to the number of lists, where the two calls agree.  A filter that selects few rows
+        (its resident row set is a list, not a bitmap) is answered by the exact search under that filter: a superset in
+        quality.  ``k > 64`` and a database without a partition are a ValueError.  No reference counterpart."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        return self.find_most_similar_approx_batch(query, k, nprobe, metadata_filter, exclude_filter, or_filters, autocut)[0]
+
+    def find_most_similar_approx_batch(self, embeddings, k=5, nprobe=8, metadata_filter=None, exclude_filter=None, or_filters=None,
+                                       autocut=False):
+        """Several queries under ONE filter: element i is what ``find_most_similar_approx(embeddings[i], ...)`` returns."""
+        queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
+        if queries.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like, one query per row")
+        k, nprobe = int(k), int(nprobe)
+        if k > self.PROBE_MAX_K:
+            raise ValueError(f"find_most_similar_approx returns at most {self.PROBE_MAX_K} results per query (k = {k})")
+        if nprobe < 1:
+            raise ValueError("nprobe must be positive")
+        if self.__dict__.get("_partition") is None:
+            raise ValueError("there is no partition: call build_partition first")
+        nq = queries.shape[0]
+        if nq == 0:
+            return []
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_probe"):
+                raise NotImplementedError(f"{type(index).__name__} has no probed search")
+            take = min(k, count)
+            rs = rowset()
+            if rs is not None and not rs.is_bitmap:   # few rows: the exact gathered scan under the filter, query by query
+                each = [index.search_rowset(queries[i:i + 1], take, rs, normalize_q=True) for i in range(nq)]
+                return np.concatenate([e[0] for e in each]), np.concatenate([e[1] for e in each])
+            part = self._resident_partition(index)
+            return index.search_probe(queries, take, min(nprobe, part.n_lists), part, rowset=rs, normalize_q=True)
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        uids = self._ids.uids
+        out = []
+        for i in range(nq):
+            hits = []
+            if found is not None:
+                for row, score in zip(found[1][i], found[0][i]):
+                    if row == -1:
+                        continue
+                    try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                        hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                    except (KeyError, IndexError):
+                        pass
+            out.append(self._package(hits, autocut))
+        return out
+
     def _group_codes(self, group_by):
         """One pass over the metadata (under the lock): an int32 code per row and the value -> code dict.  Rows that share a
         value share a code; a row without the key gets a code of its own."""
@@ -1568,6 +1732,7 @@ class UpdateMixin:
                 # either the old rows or the new ones — the index takes set_rows exclusively — and the two-call range search
                 # notices counts that moved between its calls and runs both again.
                 self._mat.replace(rows, vectors, self.index)
+                self._partition_rows_changed(rows)
             if metadata_dicts is not None:
                 values = self._live_value_index()
                 inverted = self.inverted_index

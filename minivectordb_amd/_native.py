@@ -143,6 +143,19 @@ PROTOTYPES = {
     "mvdb_index_assign_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_index_assign_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_index_kmeans": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_partition_create": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    "mvdb_partition_update": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_partition_labels": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "mvdb_partition_centres": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_partition_sizes": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_partition_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_partition_lists": (ctypes.c_int, [c_vp]),
+    "mvdb_partition_free": (ctypes.c_int, [c_vp]),
+    "mvdb_index_search_probe": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                               c_vp]),
+    "mvdb_index_search_probe_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                                      ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_probe_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -867,6 +880,102 @@ class FlatIndex:
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_assign_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    # ---- probed search: a k-means partition, a query scans the lists of its nprobe best centres (include/mvdb.h "PROBED SEARCH") ----
+    def partition(self, centres, labels=None, normalize_c=False):
+        """A resident Partition of the stored rows into len(centres) member lists.  labels None: every row is labelled on the
+        device by its nearest centre (what assign(centres, normalize_c=...) returns); else one int32 label in [-1, C) per
+        stored row, used as given (-1: the row is in no list)."""
+        return Partition(self, centres, labels, normalize_c)
+
+    def search_probe(self, q, k, nprobe, partition, rowset=None, normalize_q=False):
+        """(D float32[nq, k], I int64[nq, k]): per query the k best rows of the member lists of its nprobe best centres (of the
+        bitmap-form row set, if one is given).  APPROXIMATE in the choice of lists only: given the lists the answer is exact,
+        in the single-query scan's bits, ties to the lower row; nprobe = number of lists is the exact search over every
+        labelled row.  A short row ends in -1 / -FLT_MAX."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        nq, k = q.shape[0], int(k)
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        check(lib().mvdb_index_search_probe(self._h, partition._h, _ptr(q), nq, k, int(nprobe), int(bool(normalize_q)),
+                                            rowset._h if rowset is not None else None, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_probe_device(self, q_ptr, nq, k, nprobe, partition, D_ptr, I_ptr, rowset=None, stream=0, normalize_q=False,
+                            label_offset=0):
+        """Device-pointer variant of search_probe (labels: row numbers + label_offset); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_search_probe_device(
+            self._h, partition._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(nprobe), int(bool(normalize_q)),
+            rowset._h if rowset is not None else None, int(label_offset), ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            ctypes.c_void_p(stream)))
+
+    def probe_counters(self):
+        """(probed searches served, launches they enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_probe_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+
+class Partition:
+    """mvdb_partition*: centres, one int32 label per stored row and the member lists, resident on the index's device.  A search
+    refuses it once the index has gained or lost a row; update() follows adds and in-place updates, a removal needs a new
+    partition (from labels() with the removed rows dropped: no k-means, no re-assign)."""
+
+    def __init__(self, index, centres, labels=None, normalize_c=False):
+        centres = index._centres(centres)
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            if labels.ndim != 1 or labels.shape[0] != index.ntotal:
+                raise ValueError(f"a partition needs one label per stored row ({labels.shape} labels, {index.ntotal} rows)")
+        self._index = index
+        self.d = index.d
+        self._h = ctypes.c_void_p()
+        check(lib().mvdb_partition_create(index._h, _ptr(centres), centres.shape[0], int(bool(normalize_c)),
+                                          _ptr(labels) if labels is not None else None, ctypes.byref(self._h)))
+
+    def update(self, changed_rows=None):
+        """Label the rows added since, and the listed rows, by their nearest centre and rebuild the lists."""
+        rows = np.ascontiguousarray(changed_rows if changed_rows is not None else [], dtype=np.int64).reshape(-1)
+        check(lib().mvdb_partition_update(self._h, self._index._h, _ptr(rows) if rows.size else None, rows.shape[0]))
+
+    def __len__(self):
+        return int(lib().mvdb_partition_rows(self._h))
+
+    @property
+    def n_lists(self):
+        return int(lib().mvdb_partition_lists(self._h))
+
+    def labels(self, row0=0, n=None):
+        """int32[n]: the labels of rows [row0, row0 + n) (n None: to the last row the partition covers)."""
+        n = len(self) - int(row0) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.int32)
+        check(lib().mvdb_partition_labels(self._h, int(row0), n, _ptr(out)))
+        return out
+
+    def centres(self):
+        """float32[C, d]: the centres as stored (after their normalisation)."""
+        out = np.empty((self.n_lists, self.d), dtype=np.float32)
+        check(lib().mvdb_partition_centres(self._h, _ptr(out)))
+        return out
+
+    def sizes(self):
+        """int64[C]: rows per list."""
+        out = np.zeros(self.n_lists, dtype=np.int64)
+        check(lib().mvdb_partition_sizes(self._h, _ptr(out)))
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_partition_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Grouping:

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <functional>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 #include <shared_mutex>
@@ -24,6 +25,7 @@
 #include "distinct_select.hpp"
 #include "maxsim_scan.hpp"
 #include "assign_scan.hpp"
+#include "probe_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
 #include "select_kernels.hpp"
@@ -425,6 +427,8 @@ struct Workspace {
     DevBuf<int64_t> kmcount;             // ... members per label, [C], then the changed-label count ...
     DevBuf<uint32_t> kmoff;              // ... the lists' bases [C + 1], then the work items' bases [C + 1] ...
     DevBuf<double> kmpart;               // ... the chunk partials, [n / 256 + C, d]
+    DevBuf<ProbeItem> pitems;            // probed search: the work items of one chunk of queries, [queries, max_items] (probe_scan.hpp) ...
+    DevBuf<int> pcount;                  // ... and their item counts, [queries]
     DevBuf<char> gtab;
     DevBuf<char> c8;        // int8 prefilter of a single query (code8_search): planes, terms, counter and active lists, gate, floor, candidates
     struct GroupedStage {   // one pinned copy of a table + the event recorded behind its upload
@@ -590,6 +594,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
     // assignment (and the assignments of k-means): calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> as_calls{0}, as_passes{0};
+    // probed search: calls served and launches enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> pb_calls{0}, pb_launches{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
     mutable std::mutex ws_mu;
     mutable std::vector<Workspace*> free_ws;           // synchronous searches
@@ -2537,11 +2543,13 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const long long maxsim_table = idx->kn.maxsim_table_bytes;
     const int maxsim_tokens = idx->kn.maxsim_tokens_per_pass;
     const int assign_vectors = idx->kn.assign_vectors_per_pass;
+    const long long probe_table = idx->kn.probe_table_bytes;
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
     idx->kn.maxsim_tokens_per_pass = maxsim_tokens;
     idx->kn.assign_vectors_per_pass = assign_vectors;
+    idx->kn.probe_table_bytes = probe_table;
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
     idx->kn.code8_front_plane = code8_front;
@@ -2597,13 +2605,16 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "assign_vectors_per_pass") {  // vectors one corpus pass of an assignment scores (0: as many as the rule allows)
         if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "assign_vectors_per_pass must lie in [0, %d]", kMaxsimPassTokens);
         idx->kn.assign_vectors_per_pass = (int)value;
+    } else if (n == "probe_table_bytes") {  // budget of a probed search's item and candidate tables: a call above it runs its queries in chunks
+        if (value <= 0) return fail(MVDB_ERR_ARG, "probe_table_bytes must be positive");
+        idx->kn.probe_table_bytes = value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -4882,6 +4893,377 @@ int mvdb_index_kmeans(const mvdb_index* idx, float* centres_host, int C, int max
     MVDB_TRY(assign_emit(idx, ws, nullptr, nullptr, true));
     MVDB_TRY(assign_fetch(idx, ws, labels_host, scores_host, "k-means"));
     if (iterations) *iterations = updates;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- probed search: a partition of the rows into C member lists, a query scans the lists of its nprobe best centres (probe_scan.hpp) ----
+struct mvdb_partition {
+    uint64_t owner = 0;       // serial number of the index the partition was built on
+    int device = 0;
+    int64_t n = 0;            // the index's row count it covers: one label per row
+    uint64_t renumbered = 0;  // ... and the index's renumbering generation
+    int C = 0, d = 0;
+    int64_t ld = 0;
+    int64_t cap = 0;            // rows the label and member arrays hold
+    DevMem<float> centres;      // [C, ld] after their own normalisation, zero padded
+    DevMem<int32_t> labels;     // [cap] -1: in no list
+    DevMem<uint32_t> members;   // [cap] the lists, list after list, ascending rows inside each
+    DevMem<uint32_t> offsets;   // [C + 1]
+    std::vector<int64_t> sizes;  // [C] members per list (host copy)
+    std::vector<int64_t> items;  // [C + 1] items[j]: work items of the j LARGEST lists — what a query of j probes needs at most
+    mutable std::shared_mutex mu;  // search and the readers: shared; update: exclusive
+};
+
+namespace {
+
+int partition_check(const mvdb_index* idx, const mvdb_partition* p, bool for_update) {
+    if (p->owner != idx->serial) return fail(MVDB_ERR_ARG, "the partition belongs to another index");
+    if (p->device != idx->device || p->renumbered != idx->renumbered)
+        return fail(MVDB_ERR_ARG, "rows were removed since the partition was built: re-create it from its labels");
+    if (for_update ? p->n > idx->n : p->n != idx->n)
+        return fail(MVDB_ERR_ARG, "the partition covers %lld rows, the index holds %lld: mvdb_partition_update first", (long long)p->n, (long long)idx->n);
+    return 0;
+}
+
+// labels -> member lists, offsets and the host's copy of the sizes (the stable counting sort of kmeans_lists); waits for the stream
+int partition_lists(const mvdb_index* idx, Workspace* ws, mvdb_partition* p) {
+    hipStream_t s = ws->stream;
+    const int C = p->C;
+    const int64_t n = p->n;
+    const KmeansSlices sl = kmeans_slices(n);
+    MVDB_TRY(ws->kmhist.reserve((size_t)C * sl.nb));
+    MVDB_TRY(ws->kmcount.reserve((size_t)C + 1));
+    MVDB_TRY(ws->kmoff.reserve(2 * ((size_t)C + 1)));
+    uint32_t* const base = ws->kmoff.p;
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(sl.nb), dim3(256), (size_t)C * 4, s, p->labels.p, n, sl.per, C, sl.nb, ws->kmhist.p);
+    hipLaunchKernelGGL(kmeans_colscan_kernel, dim3(C), dim3(kWave), 0, s, ws->kmhist.p, sl.nb, ws->kmcount.p);
+    hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(1), dim3(kWave), 0, s, ws->kmcount.p, C, base, base + C + 1);
+    hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(sl.nb), dim3(kWave), (size_t)C * 4, s, p->labels.p, n, sl.per, C, sl.nb, ws->kmhist.p, base, p->members.p);
+    MVDB_HIP(hipGetLastError());
+    MVDB_HIP(hipMemcpyAsync(p->offsets.p, base, ((size_t)C + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    MVDB_TRY(copy_back(ws, ws->kmcount.p, (size_t)C * 8, "partition"));
+    p->sizes.assign((const int64_t*)ws->pin_out.p, (const int64_t*)ws->pin_out.p + C);
+    std::vector<int64_t> pieces(C);
+    for (int c = 0; c < C; ++c) pieces[c] = (p->sizes[c] + kProbeSlice - 1) / kProbeSlice;
+    std::sort(pieces.begin(), pieces.end(), std::greater<int64_t>());
+    p->items.assign((size_t)C + 1, 0);
+    for (int c = 0; c < C; ++c) p->items[c + 1] = p->items[c] + pieces[c];
+    return 0;
+}
+
+// room for `rows` labels and members; the labels held so far are kept
+int partition_reserve(mvdb_partition* p, int64_t rows) {
+    if (rows <= p->cap && p->labels.p) return 0;
+    const size_t want = (size_t)std::max<int64_t>(rows, 1);
+    DevMem<int32_t> grown;
+    if (grown.alloc(want * sizeof(int32_t)) != hipSuccess) return fail(MVDB_ERR_OOM, "partition: %zu bytes of labels could not be allocated", want * sizeof(int32_t));
+    if (p->labels.p && p->n > 0) MVDB_HIP(hipMemcpy(grown.p, p->labels.p, (size_t)p->n * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    if (p->members.alloc(want * sizeof(uint32_t)) != hipSuccess) return fail(MVDB_ERR_OOM, "partition: %zu bytes of member lists could not be allocated", want * sizeof(uint32_t));
+    std::swap(p->labels.p, grown.p);
+    p->cap = (int64_t)want;
+    return 0;
+}
+
+int check_probe_args(const mvdb_index* idx, const mvdb_partition* p, const void* q, int nq, int k, int nprobe, const void* D, const void* I) {
+    MVDB_TRY(check_search_args(idx, q, nq, k, D, I));
+    if (!p) return fail(MVDB_ERR_ARG, "partition is NULL");
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "probed search needs an inner-product index");
+    if (k > kMaxFusedK) return fail(MVDB_ERR_ARG, "probed search needs k <= %d (got %d)", kMaxFusedK, k);
+    if (nprobe < 1 || nprobe > p->C) return fail(MVDB_ERR_ARG, "probed search needs 1 <= nprobe <= %d lists (got %d)", p->C, nprobe);
+    return 0;
+}
+
+// the partition and the row set against the index's state: refused before anything is enqueued (the caller holds both locks)
+int check_probe_state(const mvdb_index* idx, const mvdb_partition* p, const mvdb_rowset* rs) {
+    MVDB_TRY(partition_check(idx, p, false));
+    if (rs) {
+        MVDB_TRY(rowset_check(idx, rs));
+        if (!rs->mask) return fail(MVDB_ERR_ARG, "probed search takes a bitmap-form row set; a list-form set is served by mvdb_index_search_rowset");
+    }
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_probe_scan_kern(const ProbeScanArgs& a, int nq, hipStream_t stream) {
+    void (*kern)(ProbeScanArgs) = probe_scan_kernel<G, C, U, SEL, MASKED>;
+    return profiled_launch("probe_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3((unsigned)a.max_items, (unsigned)nq), dim3(kScanThreads), 0, stream, done, a); },
+                           "probe_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// the shape of the single-query scan, the rows in flight of the gathered scans (U does not enter the arithmetic)
+int launch_probe_scan(const ProbeScanArgs& a, int nq, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        constexpr int U = gather_u(S::G, S::C);
+        static_assert(kProbeSlice % (kScanWaves * (kWave / S::G) * U) == 0, "an item is a whole number of block steps");
+        return with_scan_form<S::G, S::C>(a.d4, false, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            if constexpr (F::SEL == 1) return fail(MVDB_ERR_ARG, "internal: the probe scan has no row-list form");
+            else return launch_probe_scan_kern<S::G, S::C, U, F::SEL, F::MASKED>(a, nq, s);
+        });
+    });
+}
+
+// Queries on the device at stride ld, results to device buffers; everything has been checked.  Per chunk of queries four
+// launches: the coarse scores (the single-query scan over the centre matrix, a grid row per query), the plan, the scan of
+// the items, the merge.  Nothing is read back: the grid of the scan is sized from the nprobe LARGEST lists.
+int probe_core(const mvdb_index* idx, Workspace* ws, const mvdb_partition* p, const float* q, int nq, int k, int nprobe, int normalize_q,
+               const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    KnobScope knobs(&idx->kn);
+    hipStream_t s = ws->stream;
+    ++idx->pb_calls;
+    const int64_t max_items = p->items[nprobe];
+    if (max_items == 0 || (rs && (rs->count == 0 || rs->n_at_create == 0))) {  // no row in any list, or none selected
+        const int64_t total = (int64_t)nq * k;
+        hipLaunchKernelGGL(fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, total, idx->metric);
+        MVDB_HIP(hipGetLastError());
+        ++idx->pb_launches;
+        return 0;
+    }
+    if (max_items > 0x7FFFFFFFll) return fail(MVDB_ERR_ARG, "probed search: %lld work items per query", (long long)max_items);
+    const int C = p->C;
+    // the tables of ONE query: its items, their candidate lists, its coarse scores
+    const int64_t per_query = max_items * ((int64_t)sizeof(ProbeItem) + 8 * (int64_t)k) + 4 * (int64_t)C;
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nq, kCoreTile), idx->kn.probe_table_bytes / per_query));
+    MVDB_TRY(ws->scores.reserve((size_t)chunk * C));
+    MVDB_TRY(ws->pitems.reserve((size_t)chunk * max_items));
+    MVDB_TRY(ws->pcount.reserve((size_t)chunk));
+    MVDB_TRY(ws->cand.reserve((size_t)chunk * max_items * k));
+
+    ScanArgs c;
+    c.X = p->centres.p;
+    c.n = C;
+    c.ld = idx->ld;
+    c.d4 = idx->d4;
+    c.normalize_q = normalize_q;
+    c.k = 0;
+    c.rows = nullptr;
+    c.mask = nullptr;
+    c.cand = nullptr;
+    c.scores = ws->scores.p;
+    ProbePlanArgs pl;
+    pl.scores = reinterpret_cast<const uint32_t*>(ws->scores.p);
+    pl.C = C;
+    pl.P = (int)pow2ceil(std::max(C, 2));
+    pl.nprobe = nprobe;
+    pl.off = p->offsets.p;
+    pl.max_items = (int)max_items;
+    pl.items = ws->pitems.p;
+    pl.count = ws->pcount.p;
+    ProbeScanArgs a;
+    a.X = idx->X.p;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.normalize_q = normalize_q;
+    a.k = k;
+    a.members = p->members.p;
+    a.items = ws->pitems.p;
+    a.count = ws->pcount.p;
+    a.max_items = (int)max_items;
+    a.mask = rs ? rs->mask : nullptr;
+    a.mask_n = rs ? rs->n_at_create : 0;
+    a.cand = ws->cand.p;
+    ProbeMergeArgs mg;
+    mg.keys = ws->cand.p;
+    mg.count = ws->pcount.p;
+    mg.max_items = (int)max_items;
+    mg.k = k;
+    mg.label_offset = label_offset;
+
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int take = std::min(chunk, nq - q0);
+        c.q = a.q = q + (int64_t)q0 * idx->ld;
+        MVDB_TRY(launch_scan(MVDB_METRIC_IP, kModeScores, c, take, idx->device, s, nullptr));
+        MVDB_TRY(profiled_launch("probe_plan", s, [&](hipEvent_t done) { launch_kernel(probe_plan_kernel, dim3((unsigned)take), dim3(kProbePlanThreads), 0, s, done, pl); },
+                                 "probe_plan_kernel"));
+        MVDB_TRY(launch_probe_scan(a, take, s));
+        mg.D = D_dev + (int64_t)q0 * k;
+        mg.I = I_dev + (int64_t)q0 * k;
+        MVDB_TRY(profiled_launch("probe_merge", s, [&](hipEvent_t done) { launch_kernel(probe_merge_kernel, dim3((unsigned)take), dim3(kMergeThreads), 0, s, done, mg); },
+                                 "probe_merge_kernel"));
+        idx->pb_launches += 4;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_partition_create(const mvdb_index* idx, const float* centres_host, int C, int normalize_c, const int32_t* labels_host,
+                          mvdb_partition** out) {
+    if (!out) return fail(MVDB_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    MVDB_TRY(check_assign_args(idx, centres_host, C));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    const int64_t n = idx->n;
+    if (labels_host) {
+        int32_t lo = 0, hi = -1;
+        for (int64_t i = 0; i < n; ++i) {  // (branch-free: vectorises)
+            lo = labels_host[i] < lo ? labels_host[i] : lo;
+            hi = labels_host[i] > hi ? labels_host[i] : hi;
+        }
+        if (lo < -1 || hi >= C) return fail(MVDB_ERR_ARG, "label %d out of range [-1,%d)", (int)(lo < -1 ? lo : hi), C);
+    }
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    hipStream_t s = ws->stream;
+    std::unique_ptr<mvdb_partition> p(new mvdb_partition());
+    p->owner = idx->serial;
+    p->device = idx->device;
+    p->renumbered = idx->renumbered;
+    p->C = C;
+    p->d = idx->d;
+    p->ld = idx->ld;
+    const size_t cbytes = (size_t)C * idx->ld * sizeof(float);
+    if (p->centres.alloc(cbytes) != hipSuccess || p->offsets.alloc(((size_t)C + 1) * sizeof(uint32_t)) != hipSuccess)
+        return fail(MVDB_ERR_OOM, "partition: the centres could not be allocated");
+    MVDB_TRY(partition_reserve(p.get(), n));
+    p->n = n;
+    // the centres as they are searched from now on: normalised by the scan's prologue where asked (the padding stays zero: staged so)
+    MVDB_TRY(call.stage(centres_host, C));
+    if (normalize_c) {
+        MVDB_HIP(hipMemsetAsync(p->centres.p, 0, cbytes, s));
+        MVDB_TRY(launch_normalize(idx, ws->q.p, p->centres.p, C, s));
+    } else {
+        MVDB_HIP(hipMemcpyAsync(p->centres.p, ws->q.p, cbytes, hipMemcpyDeviceToDevice, s));
+    }
+    if (labels_host) {
+        if (n > 0) MVDB_HIP(hipMemcpyAsync(p->labels.p, labels_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    } else {  // assign's pass over every row: the labels of mvdb_index_assign(centres, normalize_c)
+        MVDB_TRY(assign_core(idx, ws, p->centres.p, C, 0, nullptr));
+        MVDB_TRY(assign_emit(idx, ws, p->labels.p, nullptr, false));
+    }
+    MVDB_TRY(partition_lists(idx, ws, p.get()));
+    *out = p.release();
+    return 0;
+}
+
+int mvdb_partition_update(mvdb_partition* p, const mvdb_index* idx, const int64_t* changed_rows_host, int64_t m) {
+    if (!p) return fail(MVDB_ERR_ARG, "partition is NULL");
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (m < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (m > 0 && !changed_rows_host) return fail(MVDB_ERR_ARG, "rows is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    std::unique_lock<std::shared_mutex> pk(p->mu);
+    MVDB_TRY(partition_check(idx, p, true));
+    const int64_t n = idx->n;
+    const RowRange rr = row_range(changed_rows_host, m);
+    if (m > 0 && (rr.lo < 0 || rr.hi >= n))
+        return fail(MVDB_ERR_ARG, "row %lld out of range [0,%lld)", (long long)(rr.lo < 0 ? rr.lo : rr.hi), (long long)n);
+    // the rows to label again: the listed ones and those added since, ascending, each once
+    std::vector<int64_t> rows(changed_rows_host, changed_rows_host + m);
+    for (int64_t r = p->n; r < n; ++r) rows.push_back(r);
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    if (rows.empty()) return 0;
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    hipStream_t s = ws->stream;
+    MVDB_TRY(partition_reserve(p, n));
+    const int64_t cnt = (int64_t)rows.size();
+    MVDB_TRY(ws->rows.reserve((size_t)cnt));
+    MVDB_HIP(hipMemcpyAsync(ws->rows.p, rows.data(), (size_t)cnt * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    // one assign under a list-form selection of just those rows
+    mvdb_rowset sel;
+    sel.owner = idx->serial;
+    sel.device = idx->device;
+    sel.n_at_create = n;
+    sel.renumbered = idx->renumbered;
+    sel.count = cnt;
+    sel.rows = ws->rows.p;
+    MVDB_TRY(assign_core(idx, ws, p->centres.p, p->C, 0, &sel));
+    hipLaunchKernelGGL(probe_relabel_kernel, dim3(utility_grid(cnt)), dim3(256), 0, s, (const int64_t*)ws->rows.p, cnt, (const uint64_t*)ws->asbest.p, p->labels.p);
+    MVDB_HIP(hipGetLastError());
+    p->n = n;
+    return partition_lists(idx, ws, p);
+}
+
+int mvdb_partition_labels(const mvdb_partition* p, int64_t row0, int64_t n, int32_t* labels_host) {
+    if (!p) return fail(MVDB_ERR_ARG, "partition is NULL");
+    std::shared_lock<std::shared_mutex> pk(p->mu);
+    if (row0 < 0 || n < 0 || row0 + n > p->n) return fail(MVDB_ERR_ARG, "rows [%lld, %lld) out of range [0,%lld)", (long long)row0, (long long)(row0 + n), (long long)p->n);
+    if (n == 0) return 0;
+    if (!labels_host) return fail(MVDB_ERR_ARG, "labels is NULL");
+    DeviceGuard dg(p->device);
+    MVDB_HIP(hipMemcpy(labels_host, p->labels.p + row0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mvdb_partition_centres(const mvdb_partition* p, float* centres_host) {
+    if (!p) return fail(MVDB_ERR_ARG, "partition is NULL");
+    if (!centres_host) return fail(MVDB_ERR_ARG, "centres is NULL");
+    DeviceGuard dg(p->device);
+    std::vector<float> padded((size_t)p->C * p->ld);
+    MVDB_HIP(hipMemcpy(padded.data(), p->centres.p, padded.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int c = 0; c < p->C; ++c) memcpy(centres_host + (size_t)c * p->d, padded.data() + (size_t)c * p->ld, (size_t)p->d * sizeof(float));
+    return 0;
+}
+
+int mvdb_partition_sizes(const mvdb_partition* p, int64_t* counts_host) {
+    if (!p) return fail(MVDB_ERR_ARG, "partition is NULL");
+    if (!counts_host) return fail(MVDB_ERR_ARG, "counts is NULL");
+    std::shared_lock<std::shared_mutex> pk(p->mu);
+    memcpy(counts_host, p->sizes.data(), (size_t)p->C * sizeof(int64_t));
+    return 0;
+}
+
+int64_t mvdb_partition_rows(const mvdb_partition* p) {
+    if (!p) return -1;
+    std::shared_lock<std::shared_mutex> pk(p->mu);
+    return p->n;
+}
+int mvdb_partition_lists(const mvdb_partition* p) { return p ? p->C : -1; }
+
+int mvdb_partition_free(mvdb_partition* p) {
+    if (!p) return 0;
+    DeviceGuard dg(p->device);  // the arrays free themselves, on the partition's device
+    delete p;
+    return 0;
+}
+
+int mvdb_index_search_probe(const mvdb_index* idx, const mvdb_partition* p, const float* q_host, int nq, int k, int nprobe, int normalize_q,
+                            const mvdb_rowset* rs, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_probe_args(idx, p, q_host, nq, k, nprobe, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    std::shared_lock<std::shared_mutex> pk(p->mu);
+    MVDB_TRY(check_probe_state(idx, p, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(probe_core(idx, call.ws, p, call.ws->q.p, nq, k, nprobe, normalize_q, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_probe_device(const mvdb_index* idx, const mvdb_partition* p, const float* q_dev, int nq, int k, int nprobe, int normalize_q,
+                                   const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev, void* stream) {
+    MVDB_TRY(check_probe_args(idx, p, q_dev, nq, k, nprobe, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    std::shared_lock<std::shared_mutex> pk(p->mu);
+    MVDB_TRY(check_probe_state(idx, p, rs));
+    DeviceGuard dg(idx->device);
+    if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "probed search cannot be captured into a hipGraph");
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises
+    return probe_core(idx, call.ws, p, call.q, nq, k, nprobe, normalize_q, rs, label_offset, D_dev, I_dev);
+}
+
+int mvdb_index_probe_counters(const mvdb_index* idx, long long* calls, long long* probe_launches) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->pb_calls.load();
+    if (probe_launches) *probe_launches = (long long)idx->pb_launches.load();
     return 0;
 }
 

@@ -196,6 +196,25 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def cluster_embeddings(self, *args, **kwargs):
         raise NotImplementedError(self._NO_CLUSTERING)
 
+    # ---- probed search (build_partition, find_most_similar_approx): not here ---------------------------------------------------
+    _NO_PROBE = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: probed search, whose partition is built by "
+                 "the exact fp32 passes of clustering, is not implemented (use ShardedVectorDatabase)")
+
+    def build_partition(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_PROBE)
+
+    def drop_partition(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_PROBE)
+
+    def partition_centroids(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_PROBE)
+
+    def find_most_similar_approx(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_PROBE)
+
+    def find_most_similar_approx_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_PROBE)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
