@@ -733,6 +733,48 @@ int mvdb_index_search_probe_device(const mvdb_index* idx, const mvdb_partition* 
                                    void* stream);
 int mvdb_index_probe_counters(const mvdb_index* idx, long long* calls, long long* probe_launches);
 
+/* SEARCH BY EXAMPLES: the question is stored-style vectors, not a query — "more like these P, unlike those N" (what other
+ * stores call recommend).  v is [P + N, d]: the P positives, then the N negatives.  Inner-product indexes only: an L2 index
+ * is MVDB_ERR_ARG, as for assign.  The selected rows are all rows (rs == NULL) or those of a resident row set of any form —
+ * list, bitmap or excluded.
+ * Score ("best score" rule), for a selected row r:
+ *   s(v, r) is BIT FOR BIT what mvdb_index_search / mvdb_index_search_rowset returns for v alone with nq = 1: the scan's chunk
+ *   order and butterfly, as MaxSim search and assign define their scores.  normalize normalises every vector on its own, with
+ *   the scan's own prologue.
+ *   bp(r) is the largest s(p_j, r) over the positives whose score is not NaN, scores ordered as the scan's keys order them
+ *   (-0.0 below +0.0).  A row with no such positive is never a result.
+ *   bn(r) is the same maximum over the negatives; -inf when N = 0 or when every negative scores NaN.
+ *   S(r) = bp if bp > bn (the IEEE fp32 comparison), else -(bn * bn) (one fp32 multiply, then a negation): a row that is no
+ *   closer to a positive than to a negative is ranked by how far it is from the negatives.
+ * Result.  The k rows with the largest S, best first: S ordered as the scan's keys order scores, +inf first, and -inf is still
+ *   a result; equal S goes to the LOWER physical row number, for list-form sets too.  Fewer than k rows end in -FLT_MAX / -1.
+ *   I holds physical row numbers (+ label_offset in the device variant).  An empty index or an empty set gives all padding.
+ *   N = 0: the per-row maximum over the positives.  P = 1, N = 0: mvdb_index_search, bit for bit, minus the skipped rows.
+ * Skip rows.  The n_skip listed rows are never results, whatever they score (the examples themselves, when they are stored
+ *   rows).  Duplicates are allowed.  They do not touch the row set.  The host variant refuses a row outside [0, ntotal) with
+ *   MVDB_ERR_ARG; the device variant, which reads nothing back, ignores such a row.
+ * Arguments.  1 <= P, 0 <= N, P + N <= 256, 1 <= k <= 64, 0 <= n_skip <= 1024.  A stale or foreign row set is refused before
+ *   anything is enqueued, with nothing written, as mvdb_index_assign refuses one.
+ * Cost.  ceil((P + N) / Vp) passes over the selected rows, each scoring every row against Vp consecutive vectors of v held in
+ *   LDS (a pass may hold positives and negatives), Vp = min(P + N, 32, 128 KiB / (4 ld)) — MaxSim's rule; the index option
+ *   "examples_vectors_per_pass" (1 .. 32; 0, the default: that rule) lowers it.  Results do not depend on Vp: a row's two
+ *   running maxima are carried across the passes in one 64-bit word (image of bp | image of bn), merged by the lanes that own
+ *   the row with a plain read / max / write — no atomics, no dependence on the order of arrival, no workgroup waits for
+ *   another.  Then the skip rows' words are zeroed, and a selection over the ntotal words keeps the k best keys (S, row).
+ *   Bytes: passes x (n ld 4 + 8 n) + 16 n.  Workspace: 8 bytes per stored row plus the staged vectors.
+ * The device variant does no synchronisation and no host read; one call at a time per (index, stream).  Capture into a
+ * hipGraph is not supported: a capturing stream is MVDB_ERR_ARG.
+ * mvdb_index_examples_counters: searches by examples served and corpus passes they enqueued, both counted on the host.  Either
+ * pointer may be NULL.
+ * No reference counterpart. */
+int mvdb_index_search_examples(const mvdb_index* idx, const float* v_host /*[P+N,d]: the positives, then the negatives*/, int P, int N,
+                               int k, int normalize, const mvdb_rowset* rs /*NULL: every row*/,
+                               const int64_t* skip_rows_host /*[n_skip] or NULL*/, int n_skip, float* D_host /*[k]*/, int64_t* I_host /*[k]*/);
+int mvdb_index_search_examples_device(const mvdb_index* idx, const float* v_dev /*[P+N,d]*/, int P, int N, int k, int normalize,
+                                      const mvdb_rowset* rs, const int64_t* skip_rows_dev /*[n_skip] or NULL*/, int n_skip,
+                                      int64_t label_offset, float* D_dev /*[k]*/, int64_t* I_dev /*[k]*/, void* stream);
+int mvdb_index_examples_counters(const mvdb_index* idx, long long* calls, long long* passes);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be
@@ -786,7 +828,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * both events on the launch stream around them, and its duration includes those two markers.
  * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "encoder") and returns the number of launches and their summed duration;
+ * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "examples_scan", "examples_select", "encoder") and returns the number of launches and their summed duration;
  * pairs recorded while profiling was on stay readable after it is turned off.
  * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
  * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.

@@ -1081,6 +1081,99 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, False))
         return out
 
+    # ---- search by examples: rows like the positives, unlike the negatives ------------------------------------------
+    EXAMPLES_MAX_VECTORS = 256   # most examples of one call, positives and negatives together (include/mvdb.h "SEARCH BY EXAMPLES")
+    EXAMPLES_MAX_K = 64
+
+    def _example_matrix(self, ids, embeddings, what):
+        """The examples of one side as a [m, d] float32 matrix: the stored vectors of `ids` (what ``get_vector`` returns, an
+        unknown id raises what it raises), then `embeddings`."""
+        rows = [np.asarray(self.get_vector(u), dtype=np.float32).reshape(-1) for u in ids]
+        if embeddings is not None and len(embeddings):
+            e = np.asarray(embeddings, dtype=np.float32)
+            if e.ndim != 2:
+                raise ValueError(f"{what} embeddings must be a 2-D array-like [m, d], one example per row")
+            rows.extend(e)
+        if not rows:
+            return None
+        if len({r.shape[0] for r in rows}) != 1:
+            raise ValueError(f"{what} examples differ in dimension")
+        m = np.ascontiguousarray(np.stack(rows), dtype=np.float32)
+        if self._mat is not None and m.shape[1] != self._mat.d:
+            raise ValueError(f"example dimension {m.shape[1]} != index dimension {self._mat.d}")
+        return m
+
+    def find_most_similar_by_examples(self, positive_ids=(), negative_ids=(), positive_embeddings=None, negative_embeddings=None,
+                                      k=5, strategy="best_score", metadata_filter=None, exclude_filter=None, or_filters=None,
+                                      autocut=False):
+        """The `k` stored embeddings most like the positive examples and unlike the negative ones — "more like these three",
+        "like this one, but not like those two" — under the filters of ``find_most_similar``.  An example is a stored id
+        (looked up as ``get_vector`` does; the id itself never comes back, even when the filters would not select it) or an
+        embedding (which excludes nothing); at least one positive, at most 256 examples in all.  No reference counterpart.
+
+        ``strategy="best_score"``: a row scores ``bp``, its cosine to the NEAREST positive, when that beats ``bn``, its
+        cosine to the nearest negative; otherwise ``-(bn * bn)`` — so three positives from three topics return rows of all
+        three, and rows near a negative sink by how near they are.  One pass over the selected rows per 32 examples, on the
+        device; nothing but the k results comes back.  ``strategy="average_vector"``: the classic single query ``mean(pos)``,
+        or ``2 * mean(pos) - mean(neg)`` with negatives (float32 means of the vectors as given), through the same device call
+        — ``find_most_similar`` of that vector minus the examples.  Returns ``(ids, scores, metadatas)`` packaged as
+        ``find_most_similar`` does.  `k` is clamped to the number of rows the filters select, ``k > 64`` after that is a
+        ValueError; fewer than `k` results come back when the examples eat into a small selection."""
+        if strategy not in ("best_score", "average_vector"):
+            raise ValueError(f"strategy must be 'best_score' or 'average_vector' (got {strategy!r})")
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be positive")
+        positive_ids, negative_ids = list(positive_ids or ()), list(negative_ids or ())
+        pos = self._example_matrix(positive_ids, positive_embeddings, "positive")
+        neg = self._example_matrix(negative_ids, negative_embeddings, "negative")
+        if pos is None:
+            raise ValueError("search by examples needs at least one positive example")
+        total = pos.shape[0] + (0 if neg is None else neg.shape[0])
+        if total > self.EXAMPLES_MAX_VECTORS:
+            raise ValueError(f"search by examples takes at most {self.EXAMPLES_MAX_VECTORS} examples (got {total})")
+        if neg is not None and neg.shape[1] != pos.shape[1]:
+            raise ValueError("positive and negative examples differ in dimension")
+        if self._mat is None:
+            return [], [], []
+        if strategy == "average_vector":
+            q = pos.mean(axis=0, dtype=np.float32)
+            if neg is not None:
+                q = np.float32(2) * q - neg.mean(axis=0, dtype=np.float32)
+            pos, neg = np.ascontiguousarray(q[None, :], dtype=np.float32), None
+        skip_ids = list(dict.fromkeys(positive_ids + negative_ids))
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_examples"):
+                raise NotImplementedError(f"{type(index).__name__} has no search by examples")
+            take = min(k, count)
+            if take > self.EXAMPLES_MAX_K:
+                raise _DistinctShape(f"k = {take} exceeds {self.EXAMPLES_MAX_K}, the most rows a search by examples returns")
+            with self.lock:   # the examples' rows as they are NOW: a concurrent delete renumbers them (and outdates the row set)
+                try:
+                    skip = [self._ids.row(u) for u in skip_ids]
+                except KeyError:
+                    raise ValueError("Unique ID does not exist.") from None
+            return index.search_examples(pos, neg, take, rowset=rowset(), skip_rows=skip, normalize=True)
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            return [], [], []
+        scores, rows = found
+        uids = self._ids.uids
+        hits = []
+        for r, s in zip(rows, scores):
+            if r == -1:
+                continue
+            try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                hits.append((uids[int(r)], s, self.metadata[int(r)]))
+            except (KeyError, IndexError):
+                pass
+        return self._package(hits, autocut)
+
     # ---- clustering: every selected row labelled by the nearest of a few vectors; spherical k-means -----------------
     ASSIGN_MAX_VECTORS = 4096   # most vectors / clusters of one call (include/mvdb.h "ASSIGN AND K-MEANS")
 

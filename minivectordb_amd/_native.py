@@ -156,6 +156,11 @@ PROTOTYPES = {
     "mvdb_index_search_probe_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                       ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_index_probe_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_search_examples": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                  ctypes.c_int, c_vp, c_vp]),
+    "mvdb_index_search_examples_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                         ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_examples_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -879,6 +884,44 @@ class FlatIndex:
         """(assignments served — those of k-means included —, corpus passes they enqueued): running totals counted on the host."""
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_assign_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    # ---- search by examples: rows like the positives, unlike the negatives (include/mvdb.h "SEARCH BY EXAMPLES") ----
+    def search_examples(self, positives, negatives, k, rowset=None, skip_rows=None, normalize=False):
+        """(D float32[k], I int64[k]) for the positives [P, d] and the negatives [N, d] (None or empty: none): the k rows with
+        the largest S = bp if bp > bn else -(bn * bn), bp / bn the row's best score against a positive / a negative, best first
+        (equal S: the lower row).  `skip_rows` are never results.  Fewer than k rows end in -FLT_MAX / -1."""
+        p = np.ascontiguousarray(np.asarray(positives, dtype=np.float32))
+        if p.ndim != 2 or p.shape[1] != self.d:
+            raise ValueError(f"the positives are a [P, {self.d}] array (got shape {p.shape})")
+        v, N = p, 0
+        if negatives is not None and len(negatives):
+            m = np.ascontiguousarray(np.asarray(negatives, dtype=np.float32))
+            if m.ndim != 2 or m.shape[1] != self.d:
+                raise ValueError(f"the negatives are a [N, {self.d}] array (got shape {m.shape})")
+            v, N = np.ascontiguousarray(np.concatenate([p, m])), m.shape[0]
+        skip = np.ascontiguousarray(np.asarray(skip_rows if skip_rows is not None else [], dtype=np.int64)).reshape(-1)
+        k = int(k)
+        D = np.empty(max(k, 0), dtype=np.float32)
+        I = np.empty(max(k, 0), dtype=np.int64)
+        check(lib().mvdb_index_search_examples(self._h, _ptr(v), p.shape[0], N, k, int(bool(normalize)),
+                                               rowset._h if rowset is not None else None, _ptr(skip) if len(skip) else None, len(skip),
+                                               _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_examples_device(self, v_ptr, P, N, k, D_ptr, I_ptr, rowset=None, skip_rows_ptr=0, n_skip=0, stream=0, normalize=False,
+                               label_offset=0):
+        """Device-pointer variant of search_examples (v: the positives, then the negatives; I: row numbers + label_offset; skip
+        rows outside [0, ntotal) are ignored); enqueues on `stream` and returns."""
+        check(lib().mvdb_index_search_examples_device(
+            self._h, ctypes.c_void_p(v_ptr), int(P), int(N), int(k), int(bool(normalize)), rowset._h if rowset is not None else None,
+            ctypes.c_void_p(skip_rows_ptr) if skip_rows_ptr else None, int(n_skip), int(label_offset), ctypes.c_void_p(D_ptr),
+            ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def examples_counters(self):
+        """(searches by examples served, corpus passes they enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_examples_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
     # ---- probed search: a k-means partition, a query scans the lists of its nprobe best centres (include/mvdb.h "PROBED SEARCH") ----

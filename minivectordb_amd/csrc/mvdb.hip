@@ -25,6 +25,7 @@
 #include "distinct_select.hpp"
 #include "maxsim_scan.hpp"
 #include "assign_scan.hpp"
+#include "examples_scan.hpp"
 #include "probe_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
@@ -420,6 +421,9 @@ struct Workspace {
     DevBuf<uint64_t> mxpart;             // ... the block lists of its top-k launch, [lists, 64] ...
     DevBuf<char> mxout;                  // ... the host entry point's results, packed: I_tok | D_tok | D | G
     DevBuf<uint64_t> asbest;             // assignment: the running best of every stored row, one word each (assign_scan.hpp)
+    DevBuf<uint64_t> exbest;             // search by examples: the running (best positive, best negative) of every stored row (examples_scan.hpp) ...
+    DevBuf<uint64_t> expart;             // ... the block lists of its top-k launch, [lists, 64] ...
+    DevBuf<int64_t> exskip;              // ... the host entry point's skip rows
     DevBuf<float> kmc;                   // k-means: the centres, [C, ld] ...
     DevBuf<int32_t> kmlab[2];            // ... the labels of this iteration and of the one before, [n] each ...
     DevBuf<uint32_t> kmmem;              // ... the member lists, label after label, [n] ...
@@ -594,6 +598,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
     // assignment (and the assignments of k-means): calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> as_calls{0}, as_passes{0};
+    // search by examples: calls served and corpus passes enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> ex_calls{0}, ex_passes{0};
     // probed search: calls served and launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> pb_calls{0}, pb_launches{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
@@ -2543,12 +2549,14 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const long long maxsim_table = idx->kn.maxsim_table_bytes;
     const int maxsim_tokens = idx->kn.maxsim_tokens_per_pass;
     const int assign_vectors = idx->kn.assign_vectors_per_pass;
+    const int examples_vectors = idx->kn.examples_vectors_per_pass;
     const long long probe_table = idx->kn.probe_table_bytes;
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
     idx->kn.maxsim_tokens_per_pass = maxsim_tokens;
     idx->kn.assign_vectors_per_pass = assign_vectors;
+    idx->kn.examples_vectors_per_pass = examples_vectors;
     idx->kn.probe_table_bytes = probe_table;
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
@@ -2605,6 +2613,9 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "assign_vectors_per_pass") {  // vectors one corpus pass of an assignment scores (0: as many as the rule allows)
         if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "assign_vectors_per_pass must lie in [0, %d]", kMaxsimPassTokens);
         idx->kn.assign_vectors_per_pass = (int)value;
+    } else if (n == "examples_vectors_per_pass") {  // vectors one corpus pass of a search by examples scores (0: as many as the rule allows)
+        if (value < 0 || value > kMaxsimPassTokens) return fail(MVDB_ERR_ARG, "examples_vectors_per_pass must lie in [0, %d]", kMaxsimPassTokens);
+        idx->kn.examples_vectors_per_pass = (int)value;
     } else if (n == "probe_table_bytes") {  // budget of a probed search's item and candidate tables: a call above it runs its queries in chunks
         if (value <= 0) return fail(MVDB_ERR_ARG, "probe_table_bytes must be positive");
         idx->kn.probe_table_bytes = value;
@@ -2614,7 +2625,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2699,6 +2710,12 @@ int mvdb_index_assign_counters(const mvdb_index* idx, long long* calls, long lon
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->as_calls.load();
     if (passes) *passes = (long long)idx->as_passes.load();
+    return 0;
+}
+int mvdb_index_examples_counters(const mvdb_index* idx, long long* calls, long long* passes) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->ex_calls.load();
+    if (passes) *passes = (long long)idx->ex_passes.load();
     return 0;
 }
 double mvdb_range_band(int d, float qnorm, float row_norm_bound) {
@@ -5265,6 +5282,160 @@ int mvdb_index_probe_counters(const mvdb_index* idx, long long* calls, long long
     if (calls) *calls = (long long)idx->pb_calls.load();
     if (probe_launches) *probe_launches = (long long)idx->pb_launches.load();
     return 0;
+}
+
+}  // extern "C"
+
+// ---- search by examples: P positives and N negatives, a row scores by its nearest positive (examples_scan.hpp) -------------
+namespace {
+
+int check_examples_args(const mvdb_index* idx, const void* v, int P, int N, int k, const void* skip, int n_skip, const void* D, const void* I) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (!v || !D || !I) return fail(MVDB_ERR_ARG, "NULL buffer passed to search");
+    if (P < 1) return fail(MVDB_ERR_ARG, "search by examples needs at least one positive (got P = %d)", P);
+    if (N < 0) return fail(MVDB_ERR_ARG, "search by examples needs N >= 0 (got %d)", N);
+    if ((long long)P + N > kExamplesMaxVectors)
+        return fail(MVDB_ERR_ARG, "search by examples needs P + N <= %d vectors (got %d + %d)", kExamplesMaxVectors, P, N);
+    if (k < 1 || k > kMaxFusedK) return fail(MVDB_ERR_ARG, "search by examples needs 1 <= k <= %d (got %d)", kMaxFusedK, k);
+    if (n_skip < 0 || n_skip > kExamplesMaxSkip) return fail(MVDB_ERR_ARG, "search by examples needs 0 <= n_skip <= %d (got %d)", kExamplesMaxSkip, n_skip);
+    if (n_skip > 0 && !skip) return fail(MVDB_ERR_ARG, "NULL skip rows passed to search by examples");
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "search by examples needs an inner-product index");
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_examples_kern(const ExamplesScanArgs& a, int device, hipStream_t stream) {
+    void (*kern)(ExamplesScanArgs) = examples_scan_kernel<G, C, U, SEL, MASKED>;
+    constexpr int RB = (kWave / G) * U;
+    const size_t lds = 4 * (size_t)a.Vp * (size_t)a.ld;
+    if (lds > device_lds_per_block(device))
+        return fail(MVDB_ERR_ARG, "search by examples: a pass needs %zu bytes of LDS, the device gives a workgroup %zu", lds, device_lds_per_block(device));
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
+    // assign's grid: two resident blocks of eight waves where the vectors leave room for them
+    const int per_cu = std::min(cached_occupancy((const void*)kern, kMaxsimThreads, lds, 1), 2);
+    const int64_t nbatches = (a.n + RB - 1) / RB;
+    const int64_t want = (nbatches + kMaxsimWaves - 1) / kMaxsimWaves;
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus(device) * per_cu));
+    return profiled_launch("examples_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kMaxsimThreads), lds, stream, done, a); },
+                           "examples_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// assign's forms, from the one shape table
+int launch_examples(const ExamplesScanArgs& a, int device, hipStream_t s) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            return launch_examples_kern<S::G, S::C, maxsim_u(S::G, S::C), F::SEL, F::MASKED>(a, device, s);
+        });
+    });
+}
+
+// The P + N vectors on the device at stride ld, the skip rows on the device, results to device buffers: the clear, ceil((P + N)
+// / Vp) passes over consecutive ranges of the vectors, the skip rows' words zeroed, the block lists, the merge that writes.
+int examples_core(const mvdb_index* idx, Workspace* ws, const float* v, int P, int N, int k, int normalize, const mvdb_rowset* rs,
+                  const int64_t* skip_dev, int n_skip, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->ex_calls;
+    const int64_t n = idx->n;
+    ExamplesEmitArgs e;
+    e.part = nullptr;
+    e.nlists = 0;
+    e.k = k;
+    e.label_offset = label_offset;
+    e.D = D_dev;
+    e.I = I_dev;
+    const int64_t m = rs ? rs->count : n;  // rows selected
+    if (m > 0 && !(rs && rs->mask && rs->n_at_create == 0)) {
+        const int nlists = (int)std::max<int64_t>(1, std::min<int64_t>((n + kDistinctThreads - 1) / kDistinctThreads, kExamplesLists));
+        MVDB_TRY(ws->exbest.reserve((size_t)n));
+        MVDB_TRY(ws->expart.reserve((size_t)nlists * kWave));
+        // (the clear runs under the scan's label, as a record of its own: it names no symbol)
+        MVDB_TRY(profiled_launch("examples_scan", s, [&](hipEvent_t done) { launch_kernel(examples_clear_kernel, dim3(utility_grid(n)), dim3(256), 0, s, done, ws->exbest.p, n); }));
+        const int V = P + N;
+        const int Vp = examples_vectors_per_pass(V, idx->ld, idx->kn.examples_vectors_per_pass);
+        ExamplesScanArgs a;
+        a.X = idx->X.p;
+        a.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : n;
+        a.ld = idx->ld;
+        a.d4 = idx->d4;
+        a.P = P;
+        a.normalize_q = normalize;
+        a.rows = rs ? rs->rows : nullptr;
+        a.mask = rs ? rs->mask : nullptr;
+        a.best = ws->exbest.p;
+        for (int v0 = 0; v0 < V; v0 += Vp) {
+            a.q = v + (int64_t)v0 * idx->ld;
+            a.Vp = std::min(Vp, V - v0);
+            a.v0 = v0;
+            MVDB_TRY(launch_examples(a, idx->device, s));
+            ++idx->ex_passes;
+        }
+        if (n_skip > 0) {
+            hipLaunchKernelGGL(examples_skip_kernel, dim3((unsigned)((n_skip + 255) / 256)), dim3(256), 0, s, ws->exbest.p, n, skip_dev, n_skip);
+            MVDB_HIP(hipGetLastError());
+        }
+        ExamplesTopkArgs t;
+        t.best = ws->exbest.p;
+        t.n = n;
+        t.k = k;
+        t.part = ws->expart.p;
+        MVDB_TRY(profiled_launch("examples_select", s,
+                                 [&](hipEvent_t done) { launch_kernel(examples_topk_kernel, dim3((unsigned)nlists), dim3(kDistinctThreads), 0, s, done, t); },
+                                 "examples_topk_kernel"));
+        e.part = ws->expart.p;
+        e.nlists = nlists;
+    }
+    // (an empty index or an empty set: no lists, every output is padding)
+    MVDB_TRY(profiled_launch("examples_select", s, [&](hipEvent_t done) { launch_kernel(examples_emit_kernel, dim3(1), dim3(kDistinctThreads), 0, s, done, e); }));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_search_examples(const mvdb_index* idx, const float* v_host, int P, int N, int k, int normalize, const mvdb_rowset* rs,
+                               const int64_t* skip_rows_host, int n_skip, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_examples_args(idx, v_host, P, N, k, skip_rows_host, n_skip, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    for (int i = 0; i < n_skip; ++i)
+        if (skip_rows_host[i] < 0 || skip_rows_host[i] >= idx->n)
+            return fail(MVDB_ERR_ARG, "search by examples: skip row %lld is outside [0, %lld)", (long long)skip_rows_host[i], (long long)idx->n);
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    // the vectors and, behind them in the same pinned staging buffer, the skip rows
+    const size_t vbytes = (size_t)(P + N) * idx->ld * sizeof(float);
+    MVDB_TRY(ws->pin.reserve(vbytes + (size_t)n_skip * sizeof(int64_t)));
+    MVDB_TRY(call.stage(v_host, P + N));
+    if (n_skip > 0) {
+        MVDB_TRY(ws->exskip.reserve((size_t)n_skip));
+        char* const st = (char*)ws->pin.p + vbytes;
+        memcpy(st, skip_rows_host, (size_t)n_skip * sizeof(int64_t));
+        MVDB_HIP(hipMemcpyAsync(ws->exskip.p, st, (size_t)n_skip * sizeof(int64_t), hipMemcpyHostToDevice, ws->stream));
+    }
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results((size_t)k, &D_dev, &I_dev));
+    MVDB_TRY(examples_core(idx, ws, ws->q.p, P, N, k, normalize, rs, ws->exskip.p, n_skip, 0, D_dev, I_dev));
+    return call.fetch((size_t)k, D_host, I_host);
+}
+
+int mvdb_index_search_examples_device(const mvdb_index* idx, const float* v_dev, int P, int N, int k, int normalize, const mvdb_rowset* rs,
+                                      const int64_t* skip_rows_dev, int n_skip, int64_t label_offset, float* D_dev, int64_t* I_dev,
+                                      void* stream) {
+    MVDB_TRY(check_examples_args(idx, v_dev, P, N, k, skip_rows_dev, n_skip, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "search by examples cannot be captured into a hipGraph");
+    StreamCall call(idx, stream, v_dev, P + N);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises (skip rows outside [0, ntotal) are ignored by the kernel)
+    return examples_core(idx, call.ws, call.q, P, N, k, normalize, rs, skip_rows_dev, n_skip, label_offset, D_dev, I_dev);
 }
 
 }  // extern "C"

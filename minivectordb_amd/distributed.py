@@ -597,6 +597,13 @@ class DistributedShardedVectorDatabase:
     def cluster_embeddings(self, *args, **kwargs):
         raise NotImplementedError(self._NO_CLUSTERING)
 
+    # ---- search by examples: not across ranks ------------------------------------------------------------------------
+    _NO_EXAMPLES = ("DistributedShardedVectorDatabase has no search by examples: an example given by id lives on one rank, and neither "
+                    "its vector nor its row to skip is exchanged between ranks (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_by_examples(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_EXAMPLES)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

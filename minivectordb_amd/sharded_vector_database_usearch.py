@@ -215,6 +215,13 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_approx_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_PROBE)
 
+    # ---- search by examples: not on the int8 cosine index -------------------------------------------------------------
+    _NO_EXAMPLES = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: search by examples, an exact fp32 pass "
+                    "that keeps every row's best positive and best negative score, is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_by_examples(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_EXAMPLES)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
