@@ -32,6 +32,8 @@ ids, distances, _ = db.find_most_similar(query, k=5, autocut=True)
 print("autocut:", ids, [round(float(d), 4) for d in distances])
 ids, scores, _ = db.find_most_similar_by_examples(positive_ids=[1, 4], negative_ids=[5], k=2)   # like 1 or 4, unlike 5; never 1, 4 or 5
 print("by examples:", ids, [round(float(s), 4) for s in scores])
+ids, scores, _ = db.find_most_similar_boosted(query, boosts={"n": 0.05}, id_boosts={3: 0.5}, k=3)   # cosine + 0.05 * n, + 0.5 for id 3
+print("boosted:", ids, [round(float(s), 4) for s in scores])
 
 db.delete_embedding(2)
 db.persist_to_disk()

@@ -775,6 +775,63 @@ int mvdb_index_search_examples_device(const mvdb_index* idx, const float* v_dev 
                                       int64_t label_offset, float* D_dev /*[k]*/, int64_t* I_dev /*[k]*/, void* stream);
 int mvdb_index_examples_counters(const mvdb_index* idx, long long* calls, long long* passes);
 
+/* BOOSTED SEARCH: something besides the embedding takes part in the SCORE — recency, popularity, authority ("cosine +
+ * w * metadata[key]", what other stores call score boosting or a function score), or the per-query scores of a lexical engine
+ * (the convex combination of hybrid search: a value on the engine's hits, 0 elsewhere).  A selected row r scores
+ *   S(r) = w_s * s(r) + T[r]
+ * and the k rows with the largest S are the result: ONE pass over the selected rows, exact over every one of them — a row
+ * that wins on S from rank k + 1 of the plain search is found, which no re-ranking of a fetched top-k can promise.
+ * mvdb_rowterm: one fp32 value per stored row, resident on the index's device.  mvdb_rowterm_create needs n == ntotal
+ *   (MVDB_ERR_ARG otherwise).  A search refuses a term whose row count differs from ntotal — rows were added since — with an
+ *   MVDB_ERR_ARG that names both counts, and a term created before a remove_rows / reset (the rule of mvdb_rowset: the rows
+ *   were renumbered); mvdb_index_set_rows, which keeps the row numbers, does not outdate it.  mvdb_rowterm_rows: its row
+ *   count (-1 for NULL); mvdb_rowterm_free(NULL) is a no-op.
+ * Arithmetic — all fp32, every operation rounded on its own (no contraction: numpy float32 arithmetic reproduces every bit):
+ *   T[r] = w_1 * t_1[r]; then for j = 2 .. nterms, in call order, T[r] = T[r] + (w_j * t_j[r]).
+ *   For each sparse entry (r, v): T[r] = T[r] + v.  With nterms = 0 (sparse entries only) T starts as +0.0.
+ *   S = (w_s * s) + T[r]: one multiply, then one add.
+ *   s is BIT FOR BIT what mvdb_index_search / mvdb_index_search_rowset returns for the query alone with nq = 1: the scan's
+ *   chunk order of fmaf, its xor butterfly, and (normalize_q) its query normalisation prologue.
+ * Result.  A row is a candidate iff it is selected and S == S (not NaN: a NaN score, a NaN term, +inf and -inf meeting);
+ *   -inf and +inf are ordinary scores.  Best first, S ordered as the scan's keys order scores; equal S goes to the LOWER
+ *   physical row number in every row-set form, under an unsorted row list too (the convention of search by examples, not of
+ *   mvdb_index_search_rowset).  I holds physical row numbers (+ label_offset in the device variant); fewer than k candidates
+ *   end in -FLT_MAX / -1.  One term of -0.0 at weight 1 with w_s = 1 is mvdb_index_search, bit for bit.
+ * Arguments.  Inner-product indexes only: an L2 index is MVDB_ERR_ARG.  1 <= k <= 64, 1 <= nq, 0 <= nterms <= 4; nterms = 0
+ *   with nsparse = 0 is MVDB_ERR_ARG (nothing to boost by).  Sparse entries need nq = 1; their rows are distinct and inside
+ *   [0, ntotal) — both checked on the host, MVDB_ERR_ARG otherwise.  A stale or foreign term or row set is refused before
+ *   anything is enqueued.  terms / weights may be NULL when nterms = 0, the sparse arrays when nsparse = 0.
+ * Launches.  boost_combine_kernel writes T (4 n (nterms + 1) bytes), boost_scatter_kernel adds the sparse entries, ONE
+ *   boost_scan_kernel per 1,024 queries scans the selected rows with the queries as the grid's y dimension — n (4 ld + 4) bytes
+ *   per query: the queries of a batch share T, not the corpus pass — and the merge of the block lists writes the results.
+ *   Nothing is selected (an empty index, an empty set): no combine, no scan, every output is padding.
+ *   Workspace: 4 bytes per stored row.
+ * The device variant takes the sparse rows and values as HOST arrays, as mvdb_index_set_rows_device takes its rows.  With
+ *   nsparse == 0 it enqueues and returns without a host synchronisation or a read from the device, like its siblings; with
+ *   nsparse > 0 it waits once, for the upload of the entries, before it enqueues the rest.  One call at a time per (index,
+ *   stream).  Capture into a hipGraph is not supported: a capturing stream is MVDB_ERR_ARG.
+ * mvdb_index_boost_combine runs the combine and scatter launches alone and copies T [ntotal] back: the column can be held to
+ *   the arithmetic above by itself.  It takes the term, weight and sparse arguments of a search with nq = 1.
+ * mvdb_index_boost_counters: boosted searches served (mvdb_index_boost_combine is not one) and boost_scan_kernel launches
+ *   enqueued — one per search and 1,024 queries, none where nothing is selected —, both counted on the host.  Either pointer
+ *   may be NULL.
+ * No reference counterpart. */
+typedef struct mvdb_rowterm mvdb_rowterm;
+int mvdb_rowterm_create(const mvdb_index* idx, const float* values_host /*[n]*/, int64_t n, mvdb_rowterm** out);
+int64_t mvdb_rowterm_rows(const mvdb_rowterm* t);
+int mvdb_rowterm_free(mvdb_rowterm* t);
+int mvdb_index_search_boosted(const mvdb_index* idx, const float* q_host /*[nq,d]*/, int nq, int k, int normalize_q, float score_weight,
+                              const mvdb_rowterm* const* terms /*[nterms]*/, const float* weights /*[nterms]*/, int nterms,
+                              const int64_t* sparse_rows_host /*[nsparse] or NULL*/, const float* sparse_values_host /*[nsparse] or NULL*/,
+                              int64_t nsparse, const mvdb_rowset* rs /*NULL: every row*/, float* D_host /*[nq,k]*/, int64_t* I_host /*[nq,k]*/);
+int mvdb_index_search_boosted_device(const mvdb_index* idx, const float* q_dev /*[nq,d]*/, int nq, int k, int normalize_q, float score_weight,
+                                     const mvdb_rowterm* const* terms, const float* weights, int nterms, const int64_t* sparse_rows_host,
+                                     const float* sparse_values_host, int64_t nsparse, const mvdb_rowset* rs, int64_t label_offset,
+                                     float* D_dev /*[nq,k]*/, int64_t* I_dev /*[nq,k]*/, void* stream);
+int mvdb_index_boost_combine(const mvdb_index* idx, const mvdb_rowterm* const* terms, const float* weights, int nterms,
+                             const int64_t* sparse_rows_host, const float* sparse_values_host, int64_t nsparse, float* T_host /*[ntotal]*/);
+int mvdb_index_boost_counters(const mvdb_index* idx, long long* calls, long long* scan_launches);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be
@@ -828,7 +885,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * both events on the launch stream around them, and its duration includes those two markers.
  * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "examples_scan", "examples_select", "encoder") and returns the number of launches and their summed duration;
+ * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "examples_scan", "examples_select", "boost_combine", "boost_scan", "encoder") and returns the number of launches and their summed duration;
  * pairs recorded while profiling was on stay readable after it is turned off.
  * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
  * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.

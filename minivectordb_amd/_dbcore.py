@@ -17,6 +17,7 @@ rows in ASCENDING row order (exact score ties resolve to the lower row, as in th
 reference's ``list(set_of_rows)`` (vector_database.py:510) follows CPython's hash-table order.
 """
 import bisect
+import numbers
 from array import array
 from collections import OrderedDict, defaultdict
 from operator import ge, gt, le, lt, ne
@@ -1173,6 +1174,148 @@ class FilterAndRerankMixin:
             except (KeyError, IndexError):
                 pass
         return self._package(hits, autocut)
+
+    # ---- boosted search: the cosine plus weighted per-row terms, ranked in one exact pass -------------------------------
+    BOOST_MAX_K = 64       # most rows a boosted search returns (include/mvdb.h "BOOSTED SEARCH")
+    BOOST_MAX_TERMS = 4    # most metadata keys of one call
+    _BOOST_COLUMNS_KEPT = 8   # (key, missing) columns that stay resident
+
+    def _boost_values(self, key, missing):
+        """The float32 column of metadata key `key` over the stored rows (caller holds the lock): ``np.float32(v)`` where
+        the row's value is a real number — bool is not one —, `missing` where it is anything else or the key is absent."""
+        out = np.full(len(self.metadata), missing, dtype=np.float32)
+        for row, meta in enumerate(self.metadata):
+            v = meta.get(key) if meta else None
+            if isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_)):
+                out[row] = np.float32(v)
+        return out
+
+    def _resident_boost_column(self, index, key, missing):
+        """The device-resident column of `key` (`mvdb_rowterm`), cached per (key, missing) — at most eight — and stamped with
+        the write generation and the index object, as `_resident_grouping` stamps groupings: any store, delete or metadata
+        update since makes the next use build the column again with one pass over the metadata and upload it once (4 bytes
+        per row); an embedding-only update keeps it.  A ValueError where the device index is no longer the state the
+        metadata describes: `_search_selected` starts over."""
+        with self.lock:
+            if self._embeddings_changed or self.index is not index:
+                raise ValueError("the index changed between the filter and the search")
+            gen = self.__dict__.get("_write_gen", 0)
+            cache = self.__dict__.get("_boost_columns")
+            if cache is None:
+                cache = self.__dict__["_boost_columns"] = OrderedDict()
+            slot = (key, float(missing))
+            hit = cache.get(slot)
+            if hit is not None and hit[0] == gen and hit[1] is index:
+                cache.move_to_end(slot)
+                return hit[2]
+            term = index.rowterm(self._boost_values(key, missing))
+            # an outdated entry is dropped, not freed: a search running outside the lock may still hold it (its device
+            # memory goes when the last reference does)
+            cache[slot] = (gen, index, term)
+            cache.move_to_end(slot)
+            while len(cache) > self._BOOST_COLUMNS_KEPT:
+                cache.popitem(last=False)
+            return term
+
+    def _boosted(self, queries, boosts, id_boosts, k, score_weight, missing, metadata_filter, exclude_filter, or_filters, autocut):
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be positive")
+        if k > self.BOOST_MAX_K:
+            raise ValueError(f"k = {k} exceeds {self.BOOST_MAX_K}, the most rows a boosted search returns")
+        boosts = dict(boosts) if boosts else {}
+        id_boosts = dict(id_boosts) if id_boosts else {}
+        if not boosts and not id_boosts:
+            raise ValueError("a boosted search needs something to boost by: boosts or id_boosts")
+        if len(boosts) > self.BOOST_MAX_TERMS:
+            raise ValueError(f"a boosted search takes at most {self.BOOST_MAX_TERMS} metadata keys (got {len(boosts)})")
+        keys = list(boosts)
+        for key in keys:
+            hash(key)
+        weights = np.array([boosts[key] for key in keys], dtype=np.float32)
+        missing = np.float32(missing)
+        if missing != missing:
+            raise ValueError("missing must not be NaN")
+        score_weight = float(np.float32(score_weight))
+        nq = queries.shape[0]
+        if nq == 0 or self._mat is None:
+            return [([], [], []) for _ in range(nq)]
+        if queries.shape[1] != self._mat.d:
+            raise ValueError(f"query dimension {queries.shape[1]} != index dimension {self._mat.d}")
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_boosted"):
+                raise NotImplementedError(f"{type(index).__name__} has no boosted search")
+            take = min(k, count)
+            terms = [self._resident_boost_column(index, key, missing) for key in keys]
+            rows, values = [], []
+            if id_boosts:
+                with self.lock:   # the ids' rows as they are NOW: a concurrent delete renumbers them (and outdates the terms)
+                    if self._embeddings_changed or self.index is not index:
+                        raise ValueError("the index changed between the filter and the search")
+                    for uid, value in id_boosts.items():
+                        try:
+                            rows.append(self._ids.row(uid))
+                        except (KeyError, TypeError):
+                            continue   # an id that is not stored boosts nothing
+                        values.append(value)
+            if not terms and not rows:   # every boosted id is unknown: the plain ranking, through the same call
+                rows, values = [0], [0.0]
+            return index.search_boosted(queries, take, terms, weights, score_weight=score_weight, sparse_rows=rows or None,
+                                        sparse_values=np.asarray(values, dtype=np.float32) if rows else None, rowset=rowset(),
+                                        normalize_q=True)
+
+        found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        if found is None:
+            return [([], [], []) for _ in range(nq)]
+        scores, rows = found
+        uids = self._ids.uids
+        out = []
+        for i in range(nq):
+            hits = []
+            for row, score in zip(rows[i], scores[i]):
+                if row == -1:
+                    continue
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                except (KeyError, IndexError):
+                    pass
+            out.append(self._package(hits, autocut))
+        return out
+
+    def find_most_similar_boosted(self, embedding, boosts=None, id_boosts=None, k=5, score_weight=1.0, missing=0.0,
+                                  metadata_filter=None, exclude_filter=None, or_filters=None, autocut=False):
+        """The `k` stored embeddings with the largest ``S = score_weight * cosine + sum(weight * metadata[key]) + id_boost``
+        under the filters of ``find_most_similar`` — "rank by relevance, but prefer newer or better-rated passages", or the
+        convex combination of hybrid search with the scores of a lexical engine.  The ranking is exact over every selected
+        row, in one pass on the device: a row that wins on S from far down the plain ranking is found, which fetching a
+        larger top-k and re-ranking on the host cannot promise.  No reference counterpart (its ``hybrid_rerank_results``
+        re-weights only the k rows the dense search returned).
+
+        `boosts`: ``{metadata_key: weight}``, one to four keys; the terms are added in the dict's order (float32: ``w1 * v1``,
+        then ``+ w2 * v2`` ...).  A row's value under a key is ``np.float32(v)`` when ``v`` is a real number
+        (``numbers.Real``; a bool is not one), else — or when the key is absent — `missing`.  The per-key columns stay on the
+        device until the next store, delete or metadata update.  `id_boosts`: ``{unique_id: value}``, added as is; ids that
+        are not stored are ignored, and an id the filters exclude is still never a result.  At least one of the two.
+        Returns ``(ids, scores, metadatas)`` packaged as ``find_most_similar`` does; ``scores`` holds S (np.float32), best
+        first, equal S in storage order.  A row whose S is NaN is never a result.  `k` is clamped to the number of rows the
+        filters select; ``k > 64`` is a ValueError."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        if query.ndim != 2:
+            raise ValueError("embedding must be one vector")
+        return self._boosted(query, boosts, id_boosts, k, score_weight, missing, metadata_filter, exclude_filter, or_filters, autocut)[0]
+
+    def find_most_similar_boosted_batch(self, embeddings, boosts, k=5, score_weight=1.0, missing=0.0, metadata_filter=None,
+                                        exclude_filter=None, or_filters=None, autocut=False):
+        """Several queries under ONE filter and ONE set of `boosts`: element i is what
+        ``find_most_similar_boosted(embeddings[i], boosts, ...)`` returns.  The queries share the combined column and one
+        launch; each still reads the selected rows once.  No reference counterpart."""
+        queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
+        if queries.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like, one query per row")
+        if not boosts:
+            raise ValueError("a boosted search needs something to boost by: boosts")
+        return self._boosted(queries, boosts, None, k, score_weight, missing, metadata_filter, exclude_filter, or_filters, autocut)
 
     # ---- clustering: every selected row labelled by the nearest of a few vectors; spherical k-means -----------------
     ASSIGN_MAX_VECTORS = 4096   # most vectors / clusters of one call (include/mvdb.h "ASSIGN AND K-MEANS")

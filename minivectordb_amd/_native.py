@@ -161,6 +161,15 @@ PROTOTYPES = {
     "mvdb_index_search_examples_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                                          ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_index_examples_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_rowterm_create": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.POINTER(c_vp)]),
+    "mvdb_rowterm_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_rowterm_free": (ctypes.c_int, [c_vp]),
+    "mvdb_index_search_boosted": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_vp, c_vp, ctypes.c_int,
+                                                 c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_boosted_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_vp, c_vp,
+                                                        ctypes.c_int, c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_boost_combine": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "mvdb_index_boost_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -924,6 +933,66 @@ class FlatIndex:
         check(lib().mvdb_index_examples_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    # ---- boosted search: S = w_s * s + T[row], T from resident term columns and sparse entries (include/mvdb.h "BOOSTED SEARCH") ----
+    def rowterm(self, values):
+        """A resident RowTerm: one float32 value per stored row."""
+        return RowTerm(self, values)
+
+    @staticmethod
+    def _boost_args(terms, weights, sparse_rows, sparse_values):
+        """The term, weight and sparse arguments as ctypes values; the first element keeps the arrays alive."""
+        terms = list(terms or ())
+        w = np.ascontiguousarray(np.asarray(weights if weights is not None else [], dtype=np.float32)).reshape(-1)
+        if len(w) != len(terms):
+            raise ValueError(f"{len(terms)} terms, {len(w)} weights")
+        handles = (ctypes.c_void_p * max(len(terms), 1))(*[t._h for t in terms])
+        rows = np.ascontiguousarray(np.asarray(sparse_rows if sparse_rows is not None else [], dtype=np.int64)).reshape(-1)
+        vals = np.ascontiguousarray(np.asarray(sparse_values if sparse_values is not None else [], dtype=np.float32)).reshape(-1)
+        if len(rows) != len(vals):
+            raise ValueError(f"{len(rows)} sparse rows, {len(vals)} sparse values")
+        keep = (terms, w, handles, rows, vals)
+        return keep, (handles if terms else None, _ptr(w) if terms else None, len(terms), _ptr(rows) if len(rows) else None,
+                      _ptr(vals) if len(rows) else None, len(rows))
+
+    def search_boosted(self, q, k, terms, weights, score_weight=1.0, sparse_rows=None, sparse_values=None, rowset=None, normalize_q=False):
+        """(D float32[nq, k], I int64[nq, k]): the k rows with the largest S = score_weight * s + T[row], best first (equal S:
+        the lower physical row), T the weighted sum of the `terms` (RowTerm objects, at most four, chained in the order given)
+        plus — single query only — `sparse_values` on the distinct `sparse_rows`.  Fewer than k rows end in -FLT_MAX / -1."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        nq, k = q.shape[0], int(k)
+        keep, args = self._boost_args(terms, weights, sparse_rows, sparse_values)
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        check(lib().mvdb_index_search_boosted(self._h, _ptr(q), nq, k, int(bool(normalize_q)), ctypes.c_float(score_weight), *args,
+                                              rowset._h if rowset is not None else None, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_boosted_device(self, q_ptr, nq, k, terms, weights, D_ptr, I_ptr, score_weight=1.0, sparse_rows=None, sparse_values=None,
+                              rowset=None, stream=0, normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_boosted (I: row numbers + label_offset; the sparse entries stay host arrays);
+        enqueues on `stream` and returns — without waiting for anything when there are no sparse entries."""
+        keep, args = self._boost_args(terms, weights, sparse_rows, sparse_values)
+        check(lib().mvdb_index_search_boosted_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(bool(normalize_q)), ctypes.c_float(score_weight), *args,
+            rowset._h if rowset is not None else None, int(label_offset), ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            ctypes.c_void_p(stream)))
+
+    def boost_combine(self, terms, weights, sparse_rows=None, sparse_values=None):
+        """float32[ntotal]: the combined column T of a boosted search with these arguments, computed on the device by the
+        combine launches alone."""
+        keep, args = self._boost_args(terms, weights, sparse_rows, sparse_values)
+        T = np.empty(self.ntotal, dtype=np.float32)
+        check(lib().mvdb_index_boost_combine(self._h, *args, _ptr(T)))
+        return T
+
+    def boost_counters(self):
+        """(boosted searches served, boost_scan_kernel launches enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_boost_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     # ---- probed search: a k-means partition, a query scans the lists of its nprobe best centres (include/mvdb.h "PROBED SEARCH") ----
     def partition(self, centres, labels=None, normalize_c=False):
         """A resident Partition of the stored rows into len(centres) member lists.  labels None: every row is labelled on the
@@ -1042,6 +1111,33 @@ class Grouping:
     def free(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib().mvdb_grouping_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class RowTerm:
+    """mvdb_rowterm*: one float32 value per stored row, resident on the index's device — a term of a boosted search.  Valid
+    until the index it was built on gains or loses a row (updating rows in place keeps it valid); its device memory goes with
+    the last reference."""
+
+    def __init__(self, index, values):
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        if values.ndim != 1:
+            raise ValueError("values must be one-dimensional")
+        self._h = ctypes.c_void_p()
+        check(lib().mvdb_rowterm_create(index._h, _ptr(values), values.shape[0], ctypes.byref(self._h)))
+
+    def __len__(self):
+        return int(lib().mvdb_rowterm_rows(self._h))
+
+    def free(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_rowterm_free(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -26,6 +26,7 @@
 #include "maxsim_scan.hpp"
 #include "assign_scan.hpp"
 #include "examples_scan.hpp"
+#include "boost_scan.hpp"
 #include "probe_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
@@ -424,6 +425,9 @@ struct Workspace {
     DevBuf<uint64_t> exbest;             // search by examples: the running (best positive, best negative) of every stored row (examples_scan.hpp) ...
     DevBuf<uint64_t> expart;             // ... the block lists of its top-k launch, [lists, 64] ...
     DevBuf<int64_t> exskip;              // ... the host entry point's skip rows
+    DevBuf<float> bsT;                   // boosted search: the combined term column of one call, [n] (boost_scan.hpp) ...
+    DevBuf<int64_t> bsrows;              // ... the sparse entries' rows ...
+    DevBuf<float> bsvals;                // ... and their values
     DevBuf<float> kmc;                   // k-means: the centres, [C, ld] ...
     DevBuf<int32_t> kmlab[2];            // ... the labels of this iteration and of the one before, [n] each ...
     DevBuf<uint32_t> kmmem;              // ... the member lists, label after label, [n] ...
@@ -600,6 +604,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> as_calls{0}, as_passes{0};
     // search by examples: calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> ex_calls{0}, ex_passes{0};
+    // boosted search: searches served and boost_scan_kernel launches enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> bs_calls{0}, bs_launches{0};
     // probed search: calls served and launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> pb_calls{0}, pb_launches{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
@@ -5436,6 +5442,276 @@ int mvdb_index_search_examples_device(const mvdb_index* idx, const float* v_dev,
     MVDB_TRY(call.rc);
     // nothing below reads from the device or synchronises (skip rows outside [0, ntotal) are ignored by the kernel)
     return examples_core(idx, call.ws, call.q, P, N, k, normalize, rs, skip_rows_dev, n_skip, label_offset, D_dev, I_dev);
+}
+
+}  // extern "C"
+
+// ---- boosted search: S = w_s * s + T[row], T from resident term columns and sparse entries (boost_scan.hpp) -----------------
+struct mvdb_rowterm {
+    uint64_t owner = 0;       // serial number of the index the column was built on
+    int device = 0;
+    int64_t n = 0;            // the index's row count it was built against: one value per row
+    uint64_t renumbered = 0;  // ... and its renumbering generation
+    float* values = nullptr;  // [n] on the device (none for an empty index)
+};
+
+namespace {
+
+int rowterm_check(const mvdb_index* idx, const mvdb_rowterm* t, int j) {
+    if (!t) return fail(MVDB_ERR_ARG, "boosted search: term %d is NULL", j);
+    if (t->owner != idx->serial || t->device != idx->device) return fail(MVDB_ERR_ARG, "boosted search: term %d belongs to another index", j);
+    // one value per stored row: rows added since have none, rows removed since have renumbered the rest (set_rows keeps the numbers)
+    if (t->n != idx->n)
+        return fail(MVDB_ERR_ARG, "boosted search: term %d holds %lld rows, the index %lld", j, (long long)t->n, (long long)idx->n);
+    if (t->renumbered != idx->renumbered)
+        return fail(MVDB_ERR_ARG, "boosted search: term %d was built before rows were removed (%lld rows then, %lld now)", j, (long long)t->n,
+                    (long long)idx->n);
+    return 0;
+}
+
+// the term, weight and sparse arguments every boosted entry point takes (the caller holds idx->mu shared)
+int check_boost_terms(const mvdb_index* idx, const mvdb_rowterm* const* terms, const float* weights, int nterms, const int64_t* sparse_rows,
+                      const float* sparse_values, int64_t nsparse, int nq) {
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "boosted search needs an inner-product index");
+    if (nterms < 0 || nterms > kBoostMaxTerms) return fail(MVDB_ERR_ARG, "boosted search takes 0 to %d terms (got %d)", kBoostMaxTerms, nterms);
+    if (nsparse < 0) return fail(MVDB_ERR_ARG, "boosted search: negative sparse count");
+    if (nterms == 0 && nsparse == 0) return fail(MVDB_ERR_ARG, "boosted search has nothing to boost by: no term and no sparse entry");
+    if (nterms > 0 && (!terms || !weights)) return fail(MVDB_ERR_ARG, "NULL terms or weights passed to boosted search");
+    if (nsparse > 0 && (!sparse_rows || !sparse_values)) return fail(MVDB_ERR_ARG, "NULL sparse rows or values passed to boosted search");
+    if (nsparse > 0 && nq != 1) return fail(MVDB_ERR_ARG, "boosted search: sparse entries belong to a single query (got nq = %d)", nq);
+    for (int j = 0; j < nterms; ++j) MVDB_TRY(rowterm_check(idx, terms[j], j));
+    if (nsparse > 0) {
+        std::vector<int64_t> sorted(sparse_rows, sparse_rows + nsparse);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.front() < 0 || sorted.back() >= idx->n)
+            return fail(MVDB_ERR_ARG, "boosted search: sparse row %lld is outside [0, %lld)", (long long)(sorted.front() < 0 ? sorted.front() : sorted.back()),
+                        (long long)idx->n);
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return fail(MVDB_ERR_ARG, "boosted search: sparse row %lld is listed twice", (long long)*dup);
+    }
+    return 0;
+}
+
+// The sparse entries to the device through the workspace's pinned staging, `pin_off` bytes in (behind what the caller staged
+// there).  The staging bytes are read when the copies run: the host entry points wait for their results anyway; the device
+// entry point waits for the copies before it returns (boost_search_device).
+int stage_boost_sparse(Workspace* ws, size_t pin_off, const int64_t* rows, const float* values, int64_t m) {
+    MVDB_TRY(ws->bsrows.reserve((size_t)m));
+    MVDB_TRY(ws->bsvals.reserve((size_t)m));
+    MVDB_TRY(ws->pin.reserve(pin_off + (size_t)m * (sizeof(int64_t) + sizeof(float))));
+    char* const st = (char*)ws->pin.p + pin_off;
+    memcpy(st, rows, (size_t)m * sizeof(int64_t));
+    memcpy(st + (size_t)m * sizeof(int64_t), values, (size_t)m * sizeof(float));
+    MVDB_HIP(hipMemcpyAsync(ws->bsrows.p, st, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ws->stream));
+    MVDB_HIP(hipMemcpyAsync(ws->bsvals.p, st + (size_t)m * sizeof(int64_t), (size_t)m * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+    return 0;
+}
+
+// T into ws->bsT: the combine launch, then the scatter of the sparse entries (already on the device)
+int boost_combine_core(const mvdb_index* idx, Workspace* ws, const mvdb_rowterm* const* terms, const float* weights, int nterms, int64_t nsparse) {
+    const int64_t n = idx->n;
+    if (n == 0) return 0;
+    hipStream_t s = ws->stream;
+    MVDB_TRY(ws->bsT.reserve((size_t)n));
+    BoostCombineArgs c;
+    for (int j = 0; j < kBoostMaxTerms; ++j) {
+        c.t[j] = j < nterms ? terms[j]->values : nullptr;
+        c.w[j] = j < nterms ? weights[j] : 0.f;
+    }
+    c.nterms = nterms;
+    c.n = n;
+    c.T = ws->bsT.p;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n / 4 + 255) / 256, (int64_t)device_cus(idx->device) * 8));
+    MVDB_TRY(profiled_launch("boost_combine", s, [&](hipEvent_t done) { launch_kernel(boost_combine_kernel, dim3(grid), dim3(256), 0, s, done, c); },
+                             "boost_combine_kernel"));
+    if (nsparse > 0)
+        MVDB_TRY(profiled_launch("boost_combine", s, [&](hipEvent_t done) {
+            launch_kernel(boost_scatter_kernel, dim3((unsigned)((nsparse + 255) / 256)), dim3(256), 0, s, done, ws->bsT.p, n, (const int64_t*)ws->bsrows.p,
+                          (const float*)ws->bsvals.p, nsparse);
+        }, "boost_scatter_kernel"));
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_boost_kern(const BoostScanArgs& a, int nq, int device, hipStream_t stream, int* nblocks_out) {
+    void (*kern)(BoostScanArgs) = boost_scan_kernel<G, C, U, SEL, MASKED>;
+    // the grid of the single-query scan (launch_scan_kern)
+    const int nblocks = scan_grid(a.n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);
+    *nblocks_out = nblocks;
+    return profiled_launch("boost_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, nq), dim3(kScanThreads), 0, stream, done, a); },
+                           "boost_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// the shapes, forms and rows in flight of launch_scan
+int launch_boost(const BoostScanArgs& a, int nq, int device, hipStream_t s, int* nblocks) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);
+            return launch_boost_kern<S::G, S::C, U, F::SEL, F::MASKED>(a, nq, device, s, nblocks);
+        });
+    });
+}
+
+// Queries on the device at stride ld, the sparse entries on the device, results to device buffers: the combine (shared by the
+// queries of the call), then per tile of kCoreTile queries ONE scan launch — the queries are the grid's y dimension — and the merge.
+int boost_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int normalize_q, float score_weight,
+               const mvdb_rowterm* const* terms, const float* weights, int nterms, int64_t nsparse, const mvdb_rowset* rs, int64_t label_offset,
+               float* D_dev, int64_t* I_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->bs_calls;
+    const int64_t n = idx->n;
+    const int64_t m = rs ? rs->count : n;  // rows selected
+    const int64_t total = (int64_t)nq * k;
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {  // an empty index or an empty set: every output is padding
+        hipLaunchKernelGGL(fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, total, idx->metric);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    }
+    MVDB_TRY(boost_combine_core(idx, ws, terms, weights, nterms, nsparse));
+    const int tile = std::min(nq, kCoreTile);
+    MVDB_TRY(ws->cand.reserve((size_t)tile * scan_grid_upper_bound(idx->device) * k));
+    BoostScanArgs a;
+    a.X = idx->X.p;
+    a.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : n;
+    a.ld = idx->ld;
+    a.d4 = idx->d4;
+    a.normalize_q = normalize_q;
+    a.k = k;
+    a.rows = rs ? rs->rows : nullptr;
+    a.mask = rs ? rs->mask : nullptr;
+    a.T = ws->bsT.p;
+    a.score_weight = score_weight;
+    a.cand = ws->cand.p;
+    for (int q0 = 0; q0 < nq; q0 += tile) {
+        const int take = std::min(tile, nq - q0);
+        a.q = q + (int64_t)q0 * idx->ld;
+        int nblocks = 0;
+        MVDB_TRY(launch_boost(a, take, idx->device, s, &nblocks));
+        ++idx->bs_launches;
+        MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
+    }
+    return 0;
+}
+
+int check_boost_args(const mvdb_index* idx, const void* q, int nq, int k, const void* D, const void* I) {
+    MVDB_TRY(check_search_args(idx, q, nq, k, D, I));
+    if (k > kMaxFusedK) return fail(MVDB_ERR_ARG, "boosted search needs 1 <= k <= %d (got %d)", kMaxFusedK, k);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_rowterm_create(const mvdb_index* idx, const float* values_host, int64_t n, mvdb_rowterm** out) {
+    if (!out) return fail(MVDB_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (n > 0 && !values_host) return fail(MVDB_ERR_ARG, "values is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (n != idx->n) return fail(MVDB_ERR_ARG, "a row term needs one value per stored row (%lld values, %lld rows)", (long long)n, (long long)idx->n);
+    DeviceGuard dg(idx->device);
+    mvdb_rowterm* t = new mvdb_rowterm();
+    t->owner = idx->serial;
+    t->device = idx->device;
+    t->n = n;
+    t->renumbered = idx->renumbered;
+    if (n > 0) {
+        hipError_t e = hipMalloc((void**)&t->values, (size_t)n * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(t->values, values_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (t->values) (void)hipFree(t->values);
+            delete t;
+            return fail(MVDB_ERR_HIP, "row term upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    *out = t;
+    return 0;
+}
+
+int64_t mvdb_rowterm_rows(const mvdb_rowterm* t) { return t ? t->n : -1; }
+
+int mvdb_rowterm_free(mvdb_rowterm* t) {
+    if (!t) return 0;
+    if (t->values) {
+        DeviceGuard dg(t->device);
+        (void)hipFree(t->values);
+    }
+    delete t;
+    return 0;
+}
+
+int mvdb_index_search_boosted(const mvdb_index* idx, const float* q_host, int nq, int k, int normalize_q, float score_weight,
+                              const mvdb_rowterm* const* terms, const float* weights, int nterms, const int64_t* sparse_rows_host,
+                              const float* sparse_values_host, int64_t nsparse, const mvdb_rowset* rs, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_boost_args(idx, q_host, nq, k, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_boost_terms(idx, terms, weights, nterms, sparse_rows_host, sparse_values_host, nsparse, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    // the queries and, behind them in the same pinned staging buffer, the sparse entries
+    const size_t qbytes = (size_t)nq * idx->ld * sizeof(float);
+    MVDB_TRY(ws->pin.reserve(qbytes + (size_t)nsparse * (sizeof(int64_t) + sizeof(float))));
+    MVDB_TRY(call.stage(q_host, nq));
+    if (nsparse > 0) MVDB_TRY(stage_boost_sparse(ws, qbytes, sparse_rows_host, sparse_values_host, nsparse));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(boost_core(idx, ws, ws->q.p, nq, k, normalize_q, score_weight, terms, weights, nterms, nsparse, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_boosted_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int normalize_q, float score_weight,
+                                     const mvdb_rowterm* const* terms, const float* weights, int nterms, const int64_t* sparse_rows_host,
+                                     const float* sparse_values_host, int64_t nsparse, const mvdb_rowset* rs, int64_t label_offset,
+                                     float* D_dev, int64_t* I_dev, void* stream) {
+    MVDB_TRY(check_boost_args(idx, q_dev, nq, k, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_boost_terms(idx, terms, weights, nterms, sparse_rows_host, sparse_values_host, nsparse, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "boosted search cannot be captured into a hipGraph");
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    if (nsparse > 0) {
+        // the one host wait of this entry point: the staging copy of the sparse entries belongs to the workspace, and the next
+        // call on this stream may rewrite it — so the uploads have run before this call returns.  nsparse == 0: no wait at all.
+        MVDB_TRY(stage_boost_sparse(call.ws, 0, sparse_rows_host, sparse_values_host, nsparse));
+        MVDB_HIP(hipStreamSynchronize(call.ws->stream));
+    }
+    return boost_core(idx, call.ws, call.q, nq, k, normalize_q, score_weight, terms, weights, nterms, nsparse, rs, label_offset, D_dev, I_dev);
+}
+
+int mvdb_index_boost_combine(const mvdb_index* idx, const mvdb_rowterm* const* terms, const float* weights, int nterms,
+                             const int64_t* sparse_rows_host, const float* sparse_values_host, int64_t nsparse, float* T_host) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(check_boost_terms(idx, terms, weights, nterms, sparse_rows_host, sparse_values_host, nsparse, 1));
+    if (idx->n == 0) return 0;
+    if (!T_host) return fail(MVDB_ERR_ARG, "T is NULL");
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    if (nsparse > 0) MVDB_TRY(stage_boost_sparse(ws, 0, sparse_rows_host, sparse_values_host, nsparse));
+    MVDB_TRY(boost_combine_core(idx, ws, terms, weights, nterms, nsparse));
+    MVDB_TRY(copy_back(ws, ws->bsT.p, (size_t)idx->n * sizeof(float), "boost combine"));
+    memcpy(T_host, ws->pin_out.p, (size_t)idx->n * sizeof(float));
+    return 0;
+}
+
+int mvdb_index_boost_counters(const mvdb_index* idx, long long* calls, long long* scan_launches) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->bs_calls.load();
+    if (scan_launches) *scan_launches = (long long)idx->bs_launches.load();
+    return 0;
 }
 
 }  // extern "C"

@@ -604,6 +604,16 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_by_examples(self, *args, **kwargs):
         raise NotImplementedError(self._NO_EXAMPLES)
 
+    # ---- boosted search: not across ranks ------------------------------------------------------------------------------
+    _NO_BOOST = ("DistributedShardedVectorDatabase has no boosted search: the per-row term columns are built from one rank's "
+                 "metadata and are not exchanged between ranks (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_boosted(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_BOOST)
+
+    def find_most_similar_boosted_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_BOOST)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

@@ -222,6 +222,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_by_examples(self, *args, **kwargs):
         raise NotImplementedError(self._NO_EXAMPLES)
 
+    # ---- boosted search: not on the int8 cosine index ------------------------------------------------------------------
+    _NO_BOOST = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: boosted search, an exact fp32 pass that "
+                 "adds a per-row term to every score, is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_boosted(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_BOOST)
+
+    def find_most_similar_boosted_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_BOOST)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
