@@ -12,6 +12,8 @@ this file copied into its benchmarks/ — the index has no count of refined rows
   python3 benchmarks/code8_route_probe.py --blocks 2,3,4               # MVDB_SCAN_BLOCKS_PER_CU swept in-process
   python3 benchmarks/code8_route_probe.py --front 2 --front-u 1,2,4 --blocks 1,2,3,4   # the front form's tiles per batch x its grid
   python3 benchmarks/code8_route_probe.py --family positive            # the all-positive corpus (or: clustered)
+  python3 benchmarks/code8_route_probe.py --front 2 --lift 0,-1,0,-1   # the front form's survivors: lifted from the bit plane, gathered from
+                                                                       # the 6-bit plane (no bit plane), in ONE process
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 benchmarks/code8_route_probe.py --timers 0
       (one trace session with both kernels: 200 route steps, then 40 exact scans; --timers 0 keeps the library's event
        pairs out of the stream, so the gaps in the trace are the route's own)
@@ -40,6 +42,9 @@ def main():
                     "choice; d = 512, the quad layout: 1, 2, 4; the other widths: 4, 8), swept in-process with --blocks")
     ap.add_argument("--front", type=int, default=1, help="index option code8_front_plane: 1 the library decides, 2 always the front form, "
                     "3 the plane kept and never streamed, 0 no plane")
+    ap.add_argument("--lift", default="0", help="comma list, swept in-process outside --front-u and --blocks: 0 the library's choice (the survivors of "
+                    "the front form are lifted from the bit plane), -1 index option code8_bit_plane = 0 (gathered from the 6-bit plane); "
+                    "a list that begins with -1 is written --lift=-1,0")
     args = ap.parse_args()
 
     import numpy as np
@@ -74,6 +79,7 @@ def main():
 
     planes = hasattr(idx, "code8_refined")
     fronted = hasattr(idx, "code8_front_counters")
+    lifted = hasattr(idx, "code8_bit_plane_held")
     if fronted:
         idx.set_option("code8_front_plane", args.front)
 
@@ -98,7 +104,9 @@ def main():
                 per_front = (front1[0] - front0[0]) / max(fcalls, 1)
                 label = dict(label, front_option=args.front, front_launches=fcalls, front_suspensions=front1[2],
                              front_survivors_per_launch=round(per_front, 1))
-                front_bytes = n * (d // 8 * 5 + 8) + int(per_front * (d // 4 * 3 + 8)) + int(label["refined_per_query"] * (d // 4))
+                per_survivor = d // 8 if lifted and idx.code8_bit_plane_held() else d // 4 * 3 + 8   # (the bit plane's row, or the gather)
+                label = dict(label, bit_plane=bool(lifted and idx.code8_bit_plane_held()))
+                front_bytes = n * (d // 8 * 5 + 8) + int(per_front * per_survivor) + int(label["refined_per_query"] * (d // 4))
                 bytes_per_launch = (fcalls * front_bytes + (steps - fcalls) * bytes_per_launch) // steps
         launches, ms = native.prof_read("ip_scan")
         avg = ms / max(launches, 1)
@@ -112,13 +120,16 @@ def main():
     want = results(8)
     idx.set_option("code8_single_query", 1)
     run(0, 3)   # the third eligible query builds the code
-    for front_u, blocks in [(u, b) for u in args.front_u.split(",") for b in args.blocks.split(",")]:
+    for lift, front_u, blocks in [(l, u, b) for l in args.lift.split(",") for u in args.front_u.split(",") for b in args.blocks.split(",")]:
         os.environ["MVDB_SCAN_BLOCKS_PER_CU"] = blocks if int(blocks) > 0 else ""
         os.environ["MVDB_CODE8_FRONT_U"] = front_u if int(front_u) > 0 else ""
         idx.reload_env()
+        if lifted:
+            idx.set_option("code8_bit_plane", 0 if int(lift) < 0 else 1)
+            run(0, 3)   # (a code that lacks the plane is rebuilt)
         got = results(8)
         same = all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(got, want))
-        rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks), "front_u": int(front_u)})
+        rec = measure(K, n * (d + 8), {"route": "code8", "blocks_per_cu": int(blocks), "front_u": int(front_u), "lift": int(lift)})
         fb, cand, calls = idx.code8_counters()
         cands = []
         for i in range(W, W + min(K, 32)):

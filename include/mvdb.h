@@ -84,6 +84,11 @@ int mvdb_index_reload_env(mvdb_index* idx);
  *       (mvdb_index_code8_front_counters).  0 frees the plane.  Diagnostic: 2 = 1, never going back; 3 = 1, the plane kept
  *       and never streamed.  D, I and the candidate
  *       rows of a call do not depend on this option.  An allocation that fails leaves the index without the plane, no more.
+ *   "code8_bit_plane" (0 | 1, default 1): 1 = an index that keeps the front plane also keeps the plane of bit 2 of every code
+ *       (+d / 8 bytes per row: 640 MB at 10M x 512), and the rows the front plane cannot reject fetch their d / 8 bytes of it
+ *       where they would fetch 3 d / 4 + 8 of the 6-bit plane.  0 frees this plane alone ("code8_front_plane" = 0 does not
+ *       free it); 1 again rebuilds the code with it at the next eligible query.  D, I, the candidate rows and the counters
+ *       of a call do not depend on this option.  An allocation that fails leaves the index without the plane, no more.
  *   "half_shadow" (0 | 1, default 1): 0 = batches nominate from the fp32 rows (no second copy of the corpus).
  *   "compact_bytes" (> 0, default 512 MiB): staging buffer of mvdb_index_remove_rows. */
 int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value);
@@ -170,6 +175,17 @@ int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high,
  * four chunks per lane), at the other widths the 16-byte parts of the tile's rows and behind them the 4-byte parts.  Pure host
  * arithmetic: the very functions every reader and writer of the plane uses. */
 int mvdb_code8_front_offset(int d, int64_t row, int chunk, int64_t* wide, int64_t* narrow);
+
+/* The bit plane of the code (option "code8_bit_plane"): bit 2 of every code, d / 8 bytes per row — bit i of dword s of a row
+ * is bit 2 of code 32 s + i.  With H5 = c & ~7 (the front plane) and b2 = (c >> 2) & 1: c & ~3 = H5 + 4 b2, so the sum over
+ * the 6-bit plane is Q . H5 + 4 Q . b2.  pack: d codes (d a multiple of 32, at most 2048) -> d / 8 bytes; unpack: -> b2 of every
+ * code, 0 or 1.  Host only. */
+int mvdb_code8_bit2_pack(int d, const int8_t* codes, uint8_t* bits);
+int mvdb_code8_bit2_unpack(int d, const uint8_t* bits, int8_t* codes);
+
+/* Diagnostic: the d / 8 bytes of one stored row in the bit plane as the device holds them (bits may be NULL), and whether
+ * the code holds the plane (held may be NULL). */
+int mvdb_index_code8_read_bit2(const mvdb_index* idx, int64_t row, uint8_t* bits, int* held);
 
 /* Diagnostic: how the prefilter's launch shares n rows of width d (384 / 512 / 1024) out on `device`: wave w of `waves`
  * takes the batches w, w + waves, ... of rows_per_batch consecutive rows.  Tests plant rows by it. */

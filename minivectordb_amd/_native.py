@@ -75,6 +75,9 @@ PROTOTYPES = {
     "mvdb_code8_front_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_code8_front_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_index_code8_read_row": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_code8_bit2_pack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp]),
+    "mvdb_code8_bit2_unpack": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp]),
+    "mvdb_index_code8_read_bit2": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp]),
     "mvdb_code8_front_offset": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_code8_scan_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
     "mvdb_index_dim": (ctypes.c_int, [c_vp]),
@@ -363,6 +366,18 @@ class FlatIndex:
         image = np.empty(d // 8 * 5, np.uint8) if front else None
         check(lib().mvdb_index_code8_read_row(self._h, int(row), high.ctypes.data, low.ctypes.data, image.ctypes.data if front else None))
         return high, low, image
+
+    def code8_bit_plane_held(self):
+        """Whether the int8 code holds the plane of bit 2 (index option code8_bit_plane) — diagnostic."""
+        held = ctypes.c_int(0)
+        check(lib().mvdb_index_code8_read_bit2(self._h, 0, None, ctypes.byref(held)))
+        return bool(held.value)
+
+    def code8_read_bit2(self, row):
+        """The d / 8 bytes of one stored row in the bit plane of the int8 code, as a uint8 array (diagnostic)."""
+        bits = np.empty(self.d // 8, np.uint8)
+        check(lib().mvdb_index_code8_read_bit2(self._h, int(row), bits.ctypes.data, None))
+        return bits
 
     def code8_refined(self):
         """Rows whose low plane the prefilter has fetched, over all calls so far (diagnostic; synchronises with the device)."""
@@ -1467,6 +1482,24 @@ def code8_front_unpack(image):
     d = image.shape[0] // 5 * 8
     codes = np.empty(max(d, 1), np.int8)
     check(lib().mvdb_code8_front_unpack(int(d), image.ctypes.data, codes.ctypes.data))
+    return codes
+
+
+def code8_bit2_pack(codes):
+    """The d / 8 bytes of one row of int8 codes in the bit plane: bit 2 of every code (include/mvdb.h: mvdb_code8_bit2_pack)."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    d = codes.shape[0]
+    bits = np.empty(max(d // 8, 1), np.uint8)
+    check(lib().mvdb_code8_bit2_pack(int(d), codes.ctypes.data, bits.ctypes.data))
+    return bits
+
+
+def code8_bit2_unpack(bits):
+    """(c >> 2) & 1 of the codes of one row, from its bytes of the bit plane (include/mvdb.h: mvdb_code8_bit2_unpack)."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    d = bits.shape[0] * 8
+    codes = np.empty(max(d, 1), np.int8)
+    check(lib().mvdb_code8_bit2_unpack(int(d), bits.ctypes.data, codes.ctypes.data))
     return codes
 
 

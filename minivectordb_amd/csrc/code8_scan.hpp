@@ -226,6 +226,44 @@ inline void code8_front_unpack_row(int d, const uint8_t* image, int8_t* codes) {
     }
 }
 
+// ---- the bit plane: bit 2 of every code, a fourth store ----------------------------------------------------------------------------
+// The front plane holds c & ~7 and stage 1 wants T6 = Q . (c & ~3): c & ~3 = (c & ~7) + 4 ((c >> 2) & 1) in two's complement,
+// so T6 = T5 + 4 Q . b2 with b2 the plane of bit 2 — d / 8 bytes per row where the high plane is 3 d / 4.  The front form's
+// lift (code8_scan_kernel, LIFT) reads it for the rows stage 0 cannot reject, in place of their chunks of the high plane.
+// Layout: plain row-major over the capacity, d / 8 bytes per row; bit i of dword s of a row is bit 2 of code 32 s + i, so
+// dword s belongs to the 32-code chunk s of the front plane and nibble j of it to dword j of that chunk.
+__host__ __device__ inline int code8_bit2_stride(int d) { return d / 8; }
+__host__ __device__ inline size_t code8_bit2_bytes(int64_t cap, int d) { return (size_t)cap * (size_t)code8_bit2_stride(d); }
+__host__ __device__ inline uint32_t code8_bit2_pack_chunk(const uint32_t (&c)[8]) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        w |= (((c[j] >> 2) & 1u) | ((c[j] >> 9) & 2u) | ((c[j] >> 16) & 4u) | ((c[j] >> 23) & 8u)) << (4 * j);
+    return w;
+}
+// nibble j of a dword of the plane -> four bytes of 0 / 1, bit 2 of the four codes of dword j of the chunk.  The product
+// lays the nibble down at bits 0, 7, 14 and 21 — the four copies do not overlap, nothing carries — and the mask keeps bit b
+// of the nibble at bit 8 b.
+__host__ __device__ inline uint32_t code8_bit2_spread(uint32_t w, int j) { return (((w >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u; }
+// d codes of one row <-> its d / 8 bytes of the plane (host: mvdb_code8_bit2_pack / mvdb_code8_bit2_unpack; unpack yields
+// (c >> 2) & 1 of every code)
+inline void code8_bit2_pack_row(int d, const int8_t* codes, uint8_t* bits) {
+    for (int s = 0; s < d / 32; ++s) {
+        uint32_t c[8];
+        memcpy(c, codes + 32 * s, 32);
+        const uint32_t w = code8_bit2_pack_chunk(c);
+        memcpy(bits + 4 * s, &w, 4);
+    }
+}
+inline void code8_bit2_unpack_row(int d, const uint8_t* bits, int8_t* codes) {
+    for (int s = 0; s < d / 32; ++s) {
+        uint32_t w, c[8];
+        memcpy(&w, bits + 4 * s, 4);
+        for (int j = 0; j < 8; ++j) c[j] = code8_bit2_spread(w, j);
+        memcpy(codes + 32 * s, c, 32);
+    }
+}
+
 // ---- build: rows [0, n) of X -> codes, (a, r) ------------------------------------------------------------------------------------
 // One wave per row.  a = max|x| / 127, c = rint(x / a); r = sqrt(sum (x - a c)^2) rounded up.  A row with a non-finite element
 // gets zero codes and r = +inf: it is always a candidate and the exact kernel treats it as it always has.
@@ -234,10 +272,11 @@ inline void code8_front_unpack_row(int d, const uint8_t* image, int8_t* codes) {
 // The codes go out as the two planes: a lane holds one dword of codes, the four lanes of a quad hold a 16-code chunk.
 // front != NULL: the front plane of the whole index (tiled: addressed by the stored row's number, front_row0 + row); eight
 // lanes hold a 32-code chunk (d is a multiple of 32 then: code8_front_dim).
+// bit2 != NULL: the bit plane, at row 0 as the two planes are; the sixth lane of the eight stores the chunk's dword of it.
 __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restrict__ X, int64_t ld, int d, int64_t n,
                                                           uint8_t* __restrict__ high, uint8_t* __restrict__ low, float2* __restrict__ ar,
                                                           const int64_t* __restrict__ list, int64_t limit, uint8_t* __restrict__ front,
-                                                          int64_t front_row0) {
+                                                          int64_t front_row0, uint8_t* __restrict__ bit2) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
@@ -288,12 +327,15 @@ __global__ __launch_bounds__(256) void code8_build_kernel(const float* __restric
                 hdst[3 * (c >> 2) + part] = part == 0 ? h[0] : part == 1 ? h[1] : h[2];
             else
                 ldst[c >> 2] = l;
-            if (front) {
+            if (front || bit2) {
                 uint32_t oct[8], f[5];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) oct[j] = (uint32_t)__shfl((int)word, (lane & ~7) + j);
                 code8_front_pack_chunk(oct, f);
                 const int fpart = lane & 7;
+                if (bit2 && fpart == 5)
+                    reinterpret_cast<uint32_t*>(bit2 + row * (int64_t)code8_bit2_stride(d))[c >> 3] = code8_bit2_pack_chunk(oct);
+                if (!front) continue;
                 if (fpart < 4)
                     reinterpret_cast<uint32_t*>(front + code8_front_wide_offset(front_row0 + row, c >> 3, d))[fpart] =
                         fpart == 0 ? f[0] : fpart == 1 ? f[1] : fpart == 2 ? f[2] : f[3];
@@ -553,6 +595,7 @@ struct Code8ScanArgs {
     unsigned int* front_calls;             // never zeroed: the calls of the front form
     volatile unsigned long long* front_msum;   // host-mapped: block 0 leaves both counts here at its head, as it finds them
     volatile unsigned int* front_mcalls;       //   (the calls before this one and their survivors: the host's window takes the mean)
+    const uint8_t* bit2;   // the bit plane [n, d / 8] (LIFT only): read for the survivors of stage 0 in place of `high`
 };
 
 // lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
@@ -635,7 +678,19 @@ struct Code8Narrow<true> {
 // five 16-byte loads per lane and tile, each one contiguous KiB per wave-instruction, 64 v_dot4 into one (hi, lo) pair, two
 // quad-local DPP adds (code8_reduce<4, UF>) — and UF counts tiles of 16 rows.  T5 is the same integer: everything behind
 // it is the other form's, statement for statement.
-template <int G, int U, bool MASKED, int GF = 0, int UF = 0>
+//
+// LIFT (the index holds the bit plane): lift0 in place of gather0.  Stage 0 stages (row, T5, a, r) — all four were in the
+// reporting lane's registers — and the survivors' T6 is LIFTED from T5: T6 = T5 + 4 Q . b2 (the bit plane above), in stage 0's
+// own geometry and on its query registers.  Lane tf of a row's GF lanes loads the NC dwords of the row's bit plane that belong
+// to its chunks (16 bytes in the quad form), spreads every nibble to four bytes of 0 / 1, runs 16 v_dot4 per 32 codes into one
+// (hi, lo) pair, and the GF lanes add up (code8_reduce<GF, 1>: every lane ends with the total).  The int32 argument: every
+// factor H5_j + 4 lies in [-128, 127].  stage1 gets the same rows with the same T6 and the same (a, r) as from gather0.
+// A survivor fetches d / 8 bytes where gather0 fetches 3 d / 4 + 8.  The staged rows are drained inline when 64 are staged
+// and at the wave's end (drain0), the loads of up to four wave-instructions — 4 x 64 / GF rows, all 64 in the quad form — in
+// flight per lane: one round trip where gather0 takes four.  (Built and measured, not kept: the loads of 64 / GF staged rows
+// issued behind each batch's stream loads and consumed behind its scoring — 1.7 us slower than the inline drains at 10M x 512,
+// DESIGN.md section 4.1b, "The bit plane".)
+template <int G, int U, bool MASKED, int GF = 0, int UF = 0, bool LIFT = false>
 __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
     constexpr int RB = RPI * U;
@@ -875,6 +930,9 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         unsigned long long nfront = 0;   // (one atomic per wave, at its end)
         auto gather0 = [&]() __attribute__((always_inline)) {
             nfront += (unsigned long long)ns0;
+#if defined(MVDB_CODE8_ABLATE_GATHER) && MVDB_CODE8_ABLATE_GATHER == 2
+            ns0 = 0;   // (the timing ablation: the survivors are counted and discarded)
+#endif
             for (int base = 0; base < ns0; base += RB) {
                 // staged entries past the last re-read the last one, their result is discarded
                 i32x3 x[U];
@@ -893,9 +951,69 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
                 const int ec = e < ns0 - 1 ? e : ns0 - 1;
                 const uint32_t row = (uint32_t)__shfl((int)s0row, ec);
                 const float2 sr = a.ar[row];
+#if defined(MVDB_CODE8_ABLATE_GATHER) && MVDB_CODE8_ABLATE_GATHER == 3
+                // (the timing ablation: the gathers are waited for — an empty statement takes their registers — and dropped)
+#pragma unroll
+                for (int u = 0; u < U; ++u) asm volatile("" ::"v"(x[u].x), "v"(x[u].y), "v"(x[u].z));
+                asm volatile("" ::"v"(sr.x), "v"(sr.y));
+                continue;
+#endif
                 int T[U];
                 scores(x, T);
                 stage1(code8_reduce<G, U>(T, t), sr, __ballot(t < U && e < ns0), row);
+            }
+            ns0 = 0;
+        };
+        // ---- LIFT: the rows stage 0 staged -> their dwords of the bit plane -> T6 = T5 + 4 Q . b2 -> stage 1 ----
+        // (staged per lane beside the row: T5 and (a, r) as the reporting lane held them)
+        int st5 = 0;
+        float sta = 0.f, str = 0.f;
+        // the loads of the staged rows base + gf (lane (gf, tf): the dwords of its own chunks); entries past the last
+        // re-read the last one
+        auto lift_load = [&](int base) __attribute__((always_inline)) {
+            int e = base + gf;
+            e = e < ns0 - 1 ? e : ns0 - 1;
+            const uint32_t row = (uint32_t)__shfl((int)s0row, e);
+            const narrow_t* src = reinterpret_cast<const narrow_t*>(a.bit2 + (int64_t)row * code8_bit2_stride(a.d) + tf * (NC * 4));
+            if (MASKED) return validf ? *src : narrow_t{};
+            return *src;
+        };
+        auto lift_use = [&](const narrow_t& w, int base) __attribute__((always_inline)) {
+            int hi = 0, lo = 0;
+#pragma unroll
+            for (int s = 0; s < NC; ++s) {
+                const uint32_t word = (uint32_t)Code8Narrow<QUAD>::part(w, s);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int b2 = (int)code8_bit2_spread(word, j);
+                    hi = __builtin_amdgcn_sdot4(b2, fh[s][j >> 2][j & 3], hi, false);
+                    lo = __builtin_amdgcn_sdot4(b2, fl[s][j >> 2][j & 3], lo, false);
+                }
+            }
+            int T[1] = {hi * 256 + lo};
+            const int tot = code8_reduce<GF, 1>(T, tf);
+            const int e = base + gf;
+            const int ec = e < ns0 - 1 ? e : ns0 - 1;
+            const uint32_t row = (uint32_t)__shfl((int)s0row, ec);
+            const int t5 = __shfl(st5, ec);
+            const float2 sr = make_float2(__shfl(sta, ec), __shfl(str, ec));
+            stage1(t5 + 4 * tot, sr, __ballot(tf == 0 && e < ns0), row);
+        };
+        // all staged rows, inline: the loads of up to four wave-instructions in flight
+        auto drain0 = [&]() __attribute__((always_inline)) {
+            constexpr int UL = 4;
+            nfront += (unsigned long long)ns0;
+            for (int base = 0; base < ns0; base += UL * RPF) {
+                narrow_t w[UL];
+#pragma unroll
+                for (int u = 0; u < UL; ++u) w[u] = lift_load(base + u * RPF);
+                // (ONE copy of lift_use and of what stage1 inlines: the words move down instead)
+#pragma unroll 1
+                for (int at = base; at < ns0 && at < base + UL * RPF; at += RPF) {
+                    lift_use(w[0], at);
+#pragma unroll
+                    for (int u = 0; u + 1 < UL; ++u) w[u] = w[u + 1];
+                }
             }
             ns0 = 0;
         };
@@ -912,8 +1030,21 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
                 const int src = __ffsll((long long)pass) - 1;
                 pass &= pass - 1;
                 const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)r, src);
-                if (lane == ns0) s0row = v;
-                if (++ns0 == kWave) gather0();
+                if constexpr (LIFT) {
+                    const int w = __builtin_amdgcn_readlane(t5, src);
+                    const float fa = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sr.x), src));
+                    const float fr = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sr.y), src));
+                    if (lane == ns0) {
+                        s0row = v;
+                        st5 = w;
+                        sta = fa;
+                        str = fr;
+                    }
+                    if (++ns0 == kWave) drain0();
+                } else {
+                    if (lane == ns0) s0row = v;
+                    if (++ns0 == kWave) gather0();
+                }
             }
         };
 
@@ -996,7 +1127,11 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             scores0(xw, xn, T);
             stage0(code8_reduce<GF, UF>(T, tf), sr, __ballot(tf < UF && r < a.n), r);
         }
-        if (ns0) gather0();
+        if constexpr (LIFT) {
+            if (ns0) drain0();
+        } else {
+            if (ns0) gather0();
+        }
         if (ns1) refine();
         if (nfront && lane == 0) atomicAdd(a.front_survivors, nfront);
         if (nrefined && lane == 0) atomicAdd(a.survivors, nrefined);

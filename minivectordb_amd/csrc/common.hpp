@@ -147,6 +147,8 @@ struct Knobs {
     long long code8_capacity = 32768;  // index option code8_capacity: candidates the prefilter may hand to the exact re-score
     int code8_front_plane = 1;         // index option code8_front_plane: 1 the code keeps a plane of the top 5 bits and the prefilter streams it
                                        // (+5 d / 8 bytes per row), 0 no such plane; diagnostic: 2 as 1 and the front form is never suspended, 3 as 1 and it always is
+    int code8_bit_plane = 1;           // index option code8_bit_plane: 1 an index that keeps the front plane also keeps the plane of bit 2 (+d / 8 bytes per
+                                       // row) and the front form lifts its survivors from it (code8_scan.hpp: LIFT), 0 no such plane: they are gathered
     int code8_front_u = 0;             // MVDB_CODE8_FRONT_U: tuning hook, tiles per batch of the front form (4 | 8; the quad layout: 1 | 2 | 4; 0: the measured default)
     int range_shared = 0;              // index option range_shared: batches of a range search on the shared fp16 pass (0 never — the default until the
                                        // route has been timed, DESIGN.md section 6e —, 1 by size, 2 wherever eligible)

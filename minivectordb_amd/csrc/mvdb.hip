@@ -506,6 +506,18 @@ static std::atomic<uint64_t> g_index_serial{0};
 // this table: allocated (index option code8_front_plane; an allocation that fails leaves the code without it, nothing else),
 // written by the same launch of code8_build_kernel, emptied, dropped and freed with the two planes.  Setting the option to 0
 // frees it alone; setting it again drops a code that lacks it, and the next eligible query builds both.
+//
+// The code's BIT plane (Code8Store::B2, bit 2 of every code: code8_scan.hpp) — one more row of the table, the same in every
+// column:
+//   event                        | B2
+//   ensure (first build)         | allocated where the front plane was (index option code8_bit_plane = 1); an allocation that
+//                                | fails leaves the front form on its gathers, nothing else
+//   build / add / set_rows       | written by the same launch of code8_build_kernel, range and list form
+//   add beyond capacity, reserve | dropped with the code
+//   remove_rows                  | emptied with the code, allocation kept
+//   reset, build failure, free   | dropped / freed with the code
+//   code8_bit_plane = 0          | freed alone; = 1 again drops a code that holds the front plane without it
+//   code8_front_plane = 0        | KEPT (and kept current by the builds): only the front plane is freed
 // (`failed` of both is read by routing code that holds only the shared lock and written under shadow_mu: atomic.)
 namespace {
 
@@ -527,6 +539,7 @@ struct ShadowStore {   // half_scan.hip: flat_scan_h16_kernel
 struct Code8Store {   // code8_scan.hpp; DESIGN.md section 4.1b: d codes + (scale, residual bound) per row, the operand of the single-query prefilter
     DevMem<uint8_t> C8;  // two planes: [cap, 3 d / 4] high, then [cap, d / 4] low (low())
     DevMem<uint8_t> F5;  // the front plane: [cap rounded up to whole tiles, 5 d / 8], tiled (code8_front_wide_offset); may be absent
+    DevMem<uint8_t> B2;  // the bit plane: [cap, d / 8], bit 2 of every code (code8_bit2_pack_chunk); held only beside F5, may be absent
     DevMem<float2> ar;
     DevMem<int8_t> samp;  // the stored copy of the floor's sample (code8_sample_kernel; the rule: gather_sample): codes, then (a, r) entries
     int64_t cap = 0, rows = 0;
@@ -2112,6 +2125,7 @@ constexpr int kCode8RebuildAfter = 2;
 void Code8Store::drop(bool count_rebuild) {
     C8.release();
     F5.release();
+    B2.release();
     ar.release();
     samp.release();
     cap = rows = samp_n = 0;
@@ -2129,7 +2143,8 @@ int Code8Store::build(const mvdb_index* idx, int64_t row0, int64_t n, hipStream_
     if (n > 0)
         hipLaunchKernelGGL(code8_build_kernel, dim3(row_grid(idx->device, n)), dim3(256), 0, s, (const float*)(idx->X.p + row0 * idx->ld), idx->ld,
                            idx->d, n, C8.p + row0 * code8_high_stride(idx->d), low(idx->d) + row0 * code8_low_stride(idx->d), ar.p + row0,
-                           list_dev, list_dev ? rows : (int64_t)0, F5.p, row0);
+                           list_dev, list_dev ? rows : (int64_t)0, F5.p, row0,
+                           B2.p ? B2.p + row0 * code8_bit2_stride(idx->d) : (uint8_t*)nullptr);
     MVDB_HIP(hipGetLastError());
     return 0;
 }
@@ -2176,6 +2191,11 @@ bool Code8Store::ensure(const mvdb_index* idx, hipStream_t s) {
         if (code8_front_wanted(idx->kn.code8_front_plane, idx->d) && F5.alloc(code8_front_bytes(want, idx->d)) != hipSuccess) {
             (void)hipGetLastError();
             F5.release();
+        }
+        // (nor does the bit plane: without it the front form gathers the high plane for its survivors)
+        if (F5.p && idx->kn.code8_bit_plane && B2.alloc(code8_bit2_bytes(want, idx->d)) != hipSuccess) {
+            (void)hipGetLastError();
+            B2.release();
         }
         cap = want;
         rows = 0;
@@ -2261,17 +2281,18 @@ bool code8_front_wanted(int option, int d) {
 // the prefilter's grid: CUs x BLOCKS blocks, BLOCKS per shape from the sweep of this kernel (Code8Shape::SCAN_BLOCKS;
 // profiles/code8_planes_sweep.jsonl: U = 8 with 2 blocks per CU at d = 512 and 1024, with 4 at d = 384)
 // (GF, UF > 0: the front form — its batches are (64 / GF) UF rows)
-template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0>
+// (LIFT: the front form's survivors are lifted from the bit plane — code8_scan.hpp; the label keeps its five arguments)
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false>
 int code8_scan_blocks(int64_t n, int device) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF>;
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT>;
     int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), BLOCKS);
     if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
     return scan_grid(n, GF > 0 ? (kWave / GF) * UF : (kWave / G) * U, per_cu, device);
 }
-template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0>
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false>
 int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF>;
-    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF>(a.n, device);
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT>;
+    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF, LIFT>(a.n, device);
     if constexpr (GF > 0)
         return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, done, a); },
                                "code8_scan_kernel<%d, %d, %s, %d, %d>", G, U, MASKED ? "true" : "false", GF, UF);
@@ -2399,10 +2420,14 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.front_calls = idx->c8_ctr.dev() + 6;
     c.front_msum = idx->c8_ctr.mirror<unsigned long long>() + 2;
     c.front_mcalls = idx->c8_ctr.mirror() + 6;
+    c.bit2 = idx->code.B2.p;
     const bool front = code8_front_serves(idx);
+    // the lift serves where the plane is held and wanted, at the measured tiles per batch (the tuning hook keeps the gathers)
+    const bool lift = front && idx->code.B2.p && idx->kn.code8_bit_plane && kn().code8_front_u == 0;
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
         if (!front) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
+        if (lift) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, K::FRONT_U, true>(c, idx->device, s);
         const int hook = kn().code8_front_u;   // (tuning hook)
         if constexpr (code8_front_quad(K::G * 16) && !K::MASKED) {
             // the quad layout: a batch is 16 UF rows and must divide the stage of 64
@@ -2548,6 +2573,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const bool code8 = idx->kn.code8_single_query;   // (options without an environment switch: kept)
     const long long code8_cap = idx->kn.code8_capacity;
     const int code8_front = idx->kn.code8_front_plane;
+    const int code8_bit = idx->kn.code8_bit_plane;
     const int range_shared = idx->kn.range_shared;
     const long long range_cand = idx->kn.range_candidates;
     const int join_shared = idx->kn.join_shared;
@@ -2567,6 +2593,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     idx->kn.code8_single_query = code8;
     idx->kn.code8_capacity = code8_cap;
     idx->kn.code8_front_plane = code8_front;
+    idx->kn.code8_bit_plane = code8_bit;
     idx->kn.range_shared = range_shared;
     idx->kn.range_candidates = range_cand;
     idx->kn.join_shared = join_shared;
@@ -2598,6 +2625,15 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
             idx->code.drop(false);   // (a code without the plane: the next eligible query builds both)
         const volatile unsigned long long* sum = idx->c8_ctr.mirror<unsigned long long>();
         idx->c8_front.restart_mean(sum ? sum + 2 : nullptr, idx->c8_ctr.mirror() ? idx->c8_ctr.mirror() + 6 : nullptr);
+    } else if (n == "code8_bit_plane") {  // the plane of bit 2 beside the front plane: 0 frees it alone, 1 drops a code that holds the front plane without it
+        if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "code8_bit_plane must be 0 or 1");
+        DeviceGuard dg(idx->device);
+        MVDB_TRY(quiesce(idx));
+        idx->kn.code8_bit_plane = (int)value;
+        if (value == 0)
+            idx->code.B2.release();
+        else if (idx->code.C8.p && idx->code.F5.p && !idx->code.B2.p)
+            idx->code.drop(false);   // (the next eligible query builds the code with the plane)
     } else if (n == "range_shared") {  // batches of a range search on the shared fp16 pass: 0 never, 1 by size, 2 wherever eligible
         if (value < 0 || value > 2) return fail(MVDB_ERR_ARG, "range_shared must be 0, 1 or 2");
         idx->kn.range_shared = (int)value;
@@ -2631,7 +2667,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2818,6 +2854,30 @@ int mvdb_index_code8_read_row(const mvdb_index* idx, int64_t row, uint8_t* high,
             memcpy(front + d / 2 + 4 * t, tile.data() + (code8_front_narrow_offset(row, t, d) - tile_at), 4);
         }
     }
+    return 0;
+}
+int mvdb_code8_bit2_pack(int d, const int8_t* codes, uint8_t* bits) {
+    if (!code8_front_dim(d) || !codes || !bits) return fail(MVDB_ERR_ARG, "mvdb_code8_bit2_pack: bad arguments (d must be a multiple of 32, at most 2048)");
+    code8_bit2_pack_row(d, codes, bits);
+    return 0;
+}
+int mvdb_code8_bit2_unpack(int d, const uint8_t* bits, int8_t* codes) {
+    if (!code8_front_dim(d) || !codes || !bits) return fail(MVDB_ERR_ARG, "mvdb_code8_bit2_unpack: bad arguments (d must be a multiple of 32, at most 2048)");
+    code8_bit2_unpack_row(d, bits, codes);
+    return 0;
+}
+int mvdb_index_code8_read_bit2(const mvdb_index* idx, int64_t row, uint8_t* bits, int* held) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    std::lock_guard<std::mutex> sk(idx->shadow_mu);
+    const Code8Store& c = idx->code;
+    if (held) *held = c.B2.p ? 1 : 0;
+    if (!bits) return 0;
+    if (!c.C8.p || row < 0 || row >= c.rows) return fail(MVDB_ERR_ARG, "mvdb_index_code8_read_bit2: row %lld is not in the code", (long long)row);
+    if (!c.B2.p) return fail(MVDB_ERR_ARG, "mvdb_index_code8_read_bit2: the code holds no bit plane");
+    DeviceGuard dg(idx->device);
+    const int stride = code8_bit2_stride(idx->d);
+    MVDB_HIP(hipMemcpy(bits, c.B2.p + row * stride, stride, hipMemcpyDeviceToHost));
     return 0;
 }
 int mvdb_code8_front_offset(int d, int64_t row, int chunk, int64_t* wide, int64_t* narrow) {
