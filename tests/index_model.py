@@ -16,25 +16,38 @@ model's own seeded generator), applies them to the mirror and returns them for t
 
 The store states: the shadow is "absent" (no allocation), "emptied" (allocation kept, no row converted) or "complete";
 idx.shadow_rows reads n for the last and 0 for the other two.  The L2 offsets beside it are "absent", "emptied", "behind"
-(fewer rows than the shadow: an add into a complete shadow extends the shadow alone) or "present"."""
+(fewer rows than the shadow: an add into a complete shadow extends the shadow alone) or "present".
+
+Two resident handles have validity rules of their own (include/mvdb.h "PROBED SEARCH", "BOOSTED SEARCH").  A partition is
+searchable while no row was added or removed; update() revives it after adds, nothing does after a removal or a reset (read
+the labels back, drop the removed rows', re-create); set_rows leaves it valid with the changed rows in their OLD lists until
+update(rows) names them.  The model keeps the labels such a partition must hold and the rows still waiting to be named
+(partition_plan / partition_done); part_cells logs "action/operations since the partition was last in step".  A term column
+dies with every add and every removal and survives set_rows."""
 import math
 
 import numpy as np
 
+import boost_oracle
 import distinct_oracle
+import examples_oracle
 import kmeans_oracle
 import maxsim_oracle
 import mmr_oracle
+import probe_oracle
 from oracle import flat
 
 SHADOW_DIMS = (128, 256, 384, 512, 640, 768, 896, 1024)      # half_scan.hip: half_shadow_dim
 TIE_EPS = 2e-6                                               # flat.adjudicate's tie_eps
 ROWSET_BITMAP_MIN_ROWS = 4096                                # mvdb_rowset_create: bitmap / twin only from here
+N_CENTRES = 33                                               # the partition's lists (assign takes two passes from 33 centres)
+PROBE_ITEM = 128                                             # probe plan: a list is cut into work items of 128 positions
+BOOST_WEIGHTS = (0.05, 0.02)                                 # the weights of the two term columns
 
 
 class Handle:
-    """What the model remembers of a row set or a grouping: the selection (row sets), the row count and the renumbering
-    generation it was built at."""
+    """What the model remembers of a resident handle — kind "rowset", "grouping", "partition" or "rowterm": the selection (row
+    sets), the row count and the renumbering generation it was built (a partition: last brought up to date) at."""
 
     def __init__(self, kind, n, gen, selected=None, form=None):
         self.kind, self.n, self.gen, self.selected, self.form = kind, n, gen, selected, form
@@ -42,7 +55,7 @@ class Handle:
 
 class IndexModel:
     def __init__(self, d, metric=flat.METRIC_IP, norms="unit", seed=0):
-        self.d, self.metric, self.norms = int(d), metric, norms
+        self.d, self.metric, self.norms, self.seed = int(d), metric, norms, seed
         self.rng = np.random.default_rng(seed)
         self.centre = self.rng.standard_normal(self.d)
         self.x = np.empty((0, self.d), np.float32)
@@ -58,6 +71,15 @@ class IndexModel:
         self.big = None                   # the row ("big",) wrote
         self.touched = 0                  # a row just written, or the first row a delete shifted
         self.prev_kind = None
+        # the partition (the section "the partition's labels" below)
+        self.part = None                  # Handle of the partition as it was last created or updated
+        self.labels = np.empty(0, np.int32)   # the labels it must hold: those of the rows [0, len) that have one
+        self.part_cap = 0                 # rows its label storage has room for
+        self.set_since = set()            # rows written by set_rows that no update has named yet
+        self.last_set = set()             # ... those of them the last event wrote
+        self.part_gone = []               # removals since it was last in step: sorted row arrays, None for a reset
+        self.part_since = []              # the operations since it was last in step, by name
+        self.part_cells = []              # the (action / operations since) cells the partition went through
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     @property
@@ -100,9 +122,14 @@ class IndexModel:
                 self.hn_alloc, self.hn_rows = True, self.n
 
     def valid(self, h):
-        """Row sets survive adds and set_rows; groupings need the very row count too."""
-        if h.kind == "grouping":
+        """Row sets survive adds and set_rows; groupings, row terms and (to be searched) partitions need the very row count too."""
+        if h.kind in ("grouping", "rowterm", "partition"):
             return h.gen == self.gen and h.n == self.n
+        return h.gen == self.gen and h.n <= self.n
+
+    def updatable(self, h):
+        """A partition follows adds and set_rows through update; after a removal or a reset update is refused as well."""
+        assert h.kind == "partition"
         return h.gen == self.gen and h.n <= self.n
 
     def rowset(self, form):
@@ -125,6 +152,129 @@ class IndexModel:
 
     def grouping(self):
         return (np.arange(self.n) // 8).astype(np.int32), (self.n + 7) // 8, Handle("grouping", self.n, self.gen)
+
+    # ---- the partition's labels ---------------------------------------------------------------------------------------------
+    # The model does not look for nearest centres: it records WHICH rows take a fresh label and which keep theirs; the fresh
+    # ones come from the caller (`assigned`: what assign gives for every row now — include/mvdb.h: "integer for integer").
+    def centres(self):
+        """The scenario's N_CENTRES centres [C, d] float32, from a generator of their own: two thirds near the cluster of
+        make_rows, the rest isotropic, none normalised — uneven lists on both sides of the 128-position work item."""
+        rng = np.random.default_rng(7000 + self.seed)
+        c = rng.standard_normal((N_CENTRES, self.d))
+        near = 2 * N_CENTRES // 3
+        c[:near] = 0.45 * c[:near] + self.centre * rng.uniform(0.4, 1.3, (near, 1))
+        return np.ascontiguousarray(c, dtype=np.float32)
+
+    def nearest64(self, centres):
+        """int32[n]: the float64 nearest centre of every row (the CPU tests' stand-in for the device's assign)."""
+        return np.argmax(self.x.astype(np.float64) @ np.asarray(centres, np.float32).astype(np.float64).T, axis=1).astype(np.int32)
+
+    def partition_plan(self):
+        """What the holder of the partition does before the next search, as (action, rows):
+        "none" / "create" (there is none; create: labels=None), "keep" (rows: those set_rows wrote that no update has named —
+        they stay in their old lists), "update" (refused by a search when rows were added; update(rows)), "recreate" (refused
+        by search and update; read the labels back, drop the removed rows', create from them), "drop" (the same on an empty
+        index: nothing to create from).  Rows written by the LAST event wait one check in their old lists."""
+        h = self.part
+        if h is None:
+            return ("create" if self.n else "none"), None
+        if not self.updatable(h):
+            return ("recreate" if self.n else "drop"), None
+        rows = np.array(sorted(r for r in self.set_since if r < len(self.labels)), np.int64)
+        if self.valid(h) and (len(rows) == 0 or self.last_set):
+            return "keep", rows
+        return "update", rows
+
+    def drop_removed(self, labels):
+        """The labels read back from a dead partition without those of the rows removed since."""
+        for gone in self.part_gone:
+            labels = labels[:0] if gone is None else np.delete(labels, gone[gone < len(labels)])
+        return labels
+
+    def partition_done(self, action, rows, assigned=None):
+        """The action of partition_plan was carried out; returns the labels the partition holds now."""
+        since = "+".join(self.part_since)
+        if action in ("none", "keep"):
+            if action == "keep" and len(rows):
+                self.part_cells.append("search/set_pending")
+            return self.labels
+        if action == "drop":
+            self.part_cells.append("refused/" + since)
+            self.part, self.labels, self.set_since, self.part_gone, self.part_since = None, np.empty(0, np.int32), set(), [], []
+            return self.labels
+        assigned = np.asarray(assigned, np.int32)
+        assert assigned.shape == (self.n,)
+        kept = len(self.labels)
+        labels = np.concatenate([self.labels, assigned[kept:]])                  # rows without a label take a fresh one
+        if action == "update":
+            self.part_cells.append(("update_rows/" if len(rows) else "update/") + since)
+            if self.n > self.part_cap:
+                self.part_cells.append("labels_grow")
+            labels[rows] = assigned[rows]                                        # ... and so do the rows named
+            self.set_since = {r for r in self.set_since if r < kept} - set(np.asarray(rows).tolist())
+            self.part_cap = max(self.part_cap, self.n)
+        elif action == "recreate":
+            self.part_cells.append(("recreate_same_count/" if self.n == self.part.n else "recreate/") + since)
+            self.set_since = {r for r in self.set_since if r < kept}
+            self.part_cap = self.n
+        else:
+            assert action == "create" and kept == 0
+            self.part_cells.append("create/" + since)
+            self.set_since = set()
+            self.part_cap = self.n
+        self.labels = labels
+        self.part = Handle("partition", self.n, self.gen)
+        self.part_gone, self.part_since = [], []
+        return self.labels
+
+    def _part_note(self, name, written=None, gone=None, reset=False):
+        self.part_since.append(name)
+        if written is not None:
+            self.set_since |= set(np.asarray(written).tolist())
+            self.last_set |= set(np.asarray(written).tolist())
+        if gone is not None:
+            self.labels = np.delete(self.labels, gone[gone < len(self.labels)])
+            self.part_gone.append(gone)
+            left = np.array(sorted(self.set_since), np.int64)
+            left = left[~np.isin(left, gone)]
+            self.set_since = set((left - np.searchsorted(gone, left)).tolist())
+            self.last_set = set()
+        if reset:
+            self.labels = self.labels[:0]
+            self.part_gone.append(None)
+            self.set_since, self.last_set = set(), set()
+
+    # ---- the term columns of boosted search ------------------------------------------------------------------------------------
+    def term_special(self):
+        """The rows whose second term is NaN, +inf and -inf."""
+        n, g = self.n, self.gen
+        return {"nan": (n // 3 + g) % n, "pinf": (n // 2 + g) % n, "ninf": (n // 5 + g) % n}
+
+    def term_columns(self):
+        """([recency, category] float32[n] each, Handle): a ramp over the rows and a column of five values (-0.0 among them) with
+        one NaN, one +inf and one -inf row; functions of (n, gen) alone."""
+        n, g = self.n, self.gen
+        r = np.arange(n)
+        ramp = (4.0 * ((r + 3 * g) % n) / n).astype(np.float32)
+        few = np.array([-0.0, 0.5, -1.5, 2.0, 3.0], np.float32)[(r * 7 + g + n) % 5]
+        sp = self.term_special()
+        few[sp["nan"]], few[sp["pinf"]], few[sp["ninf"]] = np.nan, np.inf, -np.inf
+        return [ramp, few], Handle("rowterm", n, self.gen)
+
+    def tie_column(self):
+        """The five-valued column without its non-finite rows, equal on the two copies: their boosted scores tie."""
+        r = np.arange(self.n)
+        col = np.array([-0.0, 0.5, -1.5, 2.0, 3.0], np.float32)[(r * 7 + self.gen + self.n) % 5]
+        if self.copies is not None:
+            col[self.copies[1]] = col[self.copies[0]]
+        return col
+
+    def sparse_entries(self):
+        """Five (row, value) entries of a single boosted query; the lower copy is one of the rows."""
+        n = self.n
+        first = self.copies[0] if self.copies is not None else 11
+        rows = list(dict.fromkeys([first, n - 1, 0, n // 2 + 1, n // 7, n // 9, 17]))[:5]
+        return np.array(rows, np.int64), np.array([0.25, -0.125, 0.3, 0.001, -2.0], np.float32)
 
     # ---- events -----------------------------------------------------------------------------------------------------------
     def make_rows(self, m):
@@ -173,6 +323,7 @@ class IndexModel:
         """Apply one event to the mirror; returns the operations for the index: ("add", X), ("set_rows", rows, X),
         ("remove_rows", rows), ("reserve", n), ("reset",)."""
         kind = event[0]
+        self.last_set = set()
         if kind == "pair":
             self.kinds.append("pair")
             ops = []
@@ -190,11 +341,13 @@ class IndexModel:
             X = self.make_rows(event[1])
             if n + len(X) > self.cap:                                            # grow: both stores dropped first
                 self._cell("add_grows")
+                self._part_note("add_grows")
                 self.cap = max(n + len(X), self.cap + self.cap // 2, 1024)
                 self._drop()
                 self._note_norms(X)
             else:
                 self._store_cells("add_fits")
+                self._part_note("add_fits")
                 if prev == "reset":
                     self._cell("reset_then_add")
                 self._note_norms(X)
@@ -232,6 +385,7 @@ class IndexModel:
             if moves:
                 self._invalidate()
             self.x[rows] = X
+            self._part_note("set", written=rows)
             self.touched = int(rows[0])
             return [("set_rows", rows, X)]
         if kind in ("del_big", "del_one", "del_scatter", "del_suffix"):
@@ -244,20 +398,25 @@ class IndexModel:
                 rows = self.rng.choice(n, event[1], replace=False).astype(np.int64)
             else:
                 rows = np.arange(n - event[1], n, dtype=np.int64)
-            self._store_cells("remove_" + {"del_big": "one", "del_one": "one_early", "del_scatter": "scattered", "del_suffix": "suffix"}[kind])
+            name = "remove_" + {"del_big": "one", "del_one": "one_early", "del_scatter": "scattered", "del_suffix": "suffix"}[kind]
+            self._store_cells(name)
+            self._part_note(name, gone=np.sort(rows))
             self._renumber(rows)
             return [("remove_rows", rows)]
         if kind == "reserve":
             want = self.cap + event[1]
             if want > self.cap:
                 self._cell("reserve_grows")
+                self._part_note("reserve_grows")
                 self.cap = want
                 self._drop()
             else:
                 self._cell("reserve_noop")
+                self._part_note("reserve_noop")
             return [("reserve", want)]
         if kind == "reset":
             self._store_cells("reset")
+            self._part_note("reset", reset=True)
             self.gen += 1
             self._drop()
             self.x = np.empty((0, self.d), np.float32)
@@ -383,6 +542,32 @@ class IndexModel:
 
     def kmeans(self, scores_of, centres, max_iter):
         return kmeans_oracle.kmeans(scores_of, self.x, centres, max_iter)
+
+    @staticmethod
+    def _masked(s, selected):
+        """The scores of the selected rows, NaN (no offer) elsewhere."""
+        s = np.asarray(s, np.float32)
+        if selected is None:
+            return s
+        out = np.full_like(s, np.nan)
+        out[..., selected] = s[..., selected]
+        return out
+
+    def probe(self, coarse, fine, labels, k, nprobe, selected=None):
+        """(D, I, probes) of one probed query: coarse [C] its scores against the centres, fine [n] against the rows."""
+        return probe_oracle.probe_search(coarse, fine, labels, k, nprobe, selected)
+
+    def examples(self, S, P, k, skip=(), selected=None):
+        """(D, I) of a search by examples: S [P + N, n], the positives' rows of the score matrix first."""
+        return examples_oracle.examples(self._masked(S, selected), P, k, skip)
+
+    @staticmethod
+    def boost_column(terms, weights, n, sparse=None):
+        return boost_oracle.combine(terms, weights, n, sparse)
+
+    def boosted(self, s_row, T, w_s, k, selected=None):
+        """(D, I) of one boosted query: S = w_s * s + T over the selected rows, ties to the lower ROW in every form."""
+        return boost_oracle.boosted(self._masked(s_row, selected), T, w_s, k)
 
     def mmr_adjudicate(self, rel, cand_rows, picks, k, lam):
         return mmr_oracle.adjudicate(rel, self.x[np.asarray(cand_rows)], picks, k, lam)

@@ -5,7 +5,7 @@ checked after every kind of event."""
 import numpy as np
 import pytest
 
-from index_model import TIE_EPS, IndexModel
+from index_model import BOOST_WEIGHTS, N_CENTRES, PROBE_ITEM, TIE_EPS, IndexModel
 from oracle import flat
 from test_lifecycle_gpu import FORMS, IP_ONLY, N0, NQ, ROUTES, SCENARIOS, random_events, routes_checked
 
@@ -157,25 +157,239 @@ def test_mmr_and_kmeans_references_are_the_existing_oracles():
     assert got[4] == 1
 
 
+def no_near_tie(values, what, top=None):
+    """The float32 oracles may differ from float64 only where float64 values are within TIE_EPS: these inputs have none
+    (among the `top` + 1 largest, when only the first `top` of the ranking are compared)."""
+    ranked = np.sort(np.asarray(values, np.float64))[::-1]
+    gaps = np.abs(np.diff(ranked if top is None else ranked[:top + 1]))
+    assert len(gaps) == 0 or gaps.min() > TIE_EPS, (what, gaps.min())
+
+
+def test_probe_reference():
+    m = small_model()
+    q = queries(m, 6)
+    c = m.centres()
+    labels = m.nearest64(c)
+    labels[::17] = -1                                                     # rows in no list are never results
+    s = brute(m, q)
+    coarse = q.astype(np.float64) @ c.astype(np.float64).T
+    S = m.score_matrix(q)
+    sel = np.sort(np.random.default_rng(4).permutation(N)[:200])
+    seen_short = False
+    for selected in (None, sel):
+        for nprobe in (1, 5, len(c)):
+            for i in range(len(q)):
+                no_near_tie(coarse[i], ("centres", i))
+                P = np.argsort(-coarse[i])[:nprobe]
+                rows = [r for r in range(N) if labels[r] in P and labels[r] >= 0 and (selected is None or r in selected)]
+                no_near_tie(s[i, rows], ("rows", i, nprobe), top=10)
+                want = sorted(rows, key=lambda r: -s[i, r])[:10]
+                D_, I, probes = m.probe(coarse[i].astype(np.float32), S[i], labels, 10, nprobe, selected)
+                assert probes.tolist() == P.tolist()
+                assert I[:len(want)].tolist() == want and (I[len(want):] == -1).all(), (i, nprobe, I, want)
+                assert np.abs(D_[:len(want)] - s[i, want]).max() < 1e-5
+                seen_short |= len(want) < 10
+                if nprobe == len(c):                                      # every list: the exact search over the labelled rows
+                    lab = np.flatnonzero(labels >= 0) if selected is None else np.intersect1d(np.flatnonzero(labels >= 0), selected)
+                    assert I.tolist() == m.search(q[i:i + 1], 10, lab)[1][0].tolist()
+    assert seen_short                                                     # a probed list shorter than k: padding
+
+
+def test_examples_reference():
+    m = small_model()
+    v = np.random.default_rng(6).standard_normal((5, D)).astype(np.float32)
+    P, Nn = 3, 2
+    s = brute(m, v[:P + Nn])
+    S = m.score_matrix(v[:P + Nn])
+    sel = np.sort(np.random.default_rng(5).permutation(N)[:70])
+    for selected, k in ((None, 10), (None, 64), (sel, 64)):
+        lab = np.arange(N) if selected is None else selected
+        skip = [int(lab[np.argmax(s[j, lab])]) for j in range(P)]
+        bp, bn = s[:P].max(axis=0), s[P:].max(axis=0)
+        assert np.abs(bp - bn)[lab].min() > TIE_EPS                       # no row near the rule's comparison
+        score = np.where(bp > bn, bp, -(bn * bn))
+        rows = [r for r in lab.tolist() if r not in skip]
+        no_near_tie(score[rows], "examples", top=k)
+        want = sorted(rows, key=lambda r: -score[r])[:k]
+        D_, I = m.examples(S, P, k, skip, selected)
+        assert I.tolist() == want and np.abs(D_ - score[want]).max() < 1e-5, (k, I, want)
+        if selected is not None:                                          # both branches of the rule in one result
+            closer = bp[I] > bn[I]
+            assert closer.any() and (~closer).any() and (D_[~closer] <= 0).all()
+    # no negative: the per-row maximum over the positives; one positive: the plain search
+    D_, I = m.examples(S[:P], P, 10)
+    assert I.tolist() == np.argsort(-s[:P].max(axis=0))[:10].tolist()
+    D_, I = m.examples(S[:1], 1, 10)
+    assert I.tolist() == m.search(v[:1], 10)[1][0].tolist()
+
+
+def test_boost_reference():
+    m = small_model()
+    q = queries(m, 4)
+    s = brute(m, q)
+    S = m.score_matrix(q)
+    cols, h = m.term_columns()
+    sp = m.term_special()
+    assert h.kind == "rowterm" and len({*sp.values()}) == 3 and (np.signbit(cols[1]) & (cols[1] == 0)).any()
+    assert np.isnan(cols[1][sp["nan"]]) and cols[1][sp["pinf"]] == np.inf and cols[1][sp["ninf"]] == -np.inf
+    assert np.isfinite(cols[0]).all() and np.isfinite(cols[1]).sum() == N - 3 and len(set(cols[1][np.isfinite(cols[1])].tolist())) == 5
+    sparse = m.sparse_entries()
+    assert len(set(sparse[0].tolist())) == 5 and len(sparse[1]) == 5
+    sel = np.sort(np.random.default_rng(6).permutation(N)[:150])
+    for entries in (None, sparse):
+        T = m.boost_column(cols, BOOST_WEIGHTS, N, entries)
+        with np.errstate(invalid="ignore"):
+            T64 = sum(np.float64(np.float32(w)) * t.astype(np.float64) for w, t in zip(BOOST_WEIGHTS, cols))
+        if entries is not None:
+            T64[entries[0]] += entries[1].astype(np.float64)
+        fin = np.isfinite(T64)
+        assert T.dtype == np.float32 and np.array_equal(np.isnan(T), np.isnan(T64)) and np.array_equal(T[~fin & ~np.isnan(T64)], T64[~fin & ~np.isnan(T64)])
+        assert np.abs(T[fin] - T64[fin]).max() < 1e-6
+        for selected in (None, sel):
+            lab = np.arange(N) if selected is None else selected
+            for i in range(len(q)):
+                total = 0.7 * s[i] + T64
+                rows = [r for r in lab.tolist() if not np.isnan(total[r])]
+                no_near_tie(total[[r for r in rows if np.isfinite(total[r])]], ("boost", i), top=10)
+                want = sorted(rows, key=lambda r: -total[r])[:10]
+                D_, I = m.boosted(S[i], T, 0.7, 10, selected)
+                assert I.tolist() == want, (i, I, want)
+                assert sp["nan"] not in I and (I[0] == sp["pinf"] and D_[0] == np.inf) == (sp["pinf"] in lab)
+                assert np.abs(D_[1:] - total[want[1:]]).max() < 1e-5
+    # ties go to the lower ROW, whatever the order of the selection
+    m.apply(("copy",))
+    a, b = m.copies
+    tie = m.tie_column()
+    assert tie[a] == tie[b] and np.isfinite(tie).all()
+    s_row = m.score_matrix(m.x[a:a + 1])[0]
+    for selected in (None, np.array([b, 5, a, 9])):
+        D_, I = m.boosted(s_row, m.boost_column([tie], [0.02], N), 0.7, 4, selected)
+        at = I.tolist().index(a)
+        assert I[at + 1] == b and D_[at] == D_[at + 1]
+    assert m.sparse_entries()[0][0] == a
+
+
+def test_terms_reorder_and_lists_straddle_the_work_item():
+    """On every scenario's initial corpus: the boost changes the top 10 of most queries (float64, the non-finite rows left
+    out), and the float64 nearest-centre lists fall on both sides of the 128-position work item, one of them needing three."""
+    for name, sc in SCENARIOS.items():
+        m = IndexModel(sc["d"], sc["metric"], sc["norms"], sc["seed"])
+        m.apply(("add", N0))
+        c = m.centres()
+        assert c.shape == (N_CENTRES, sc["d"]) and c.dtype == np.float32 and np.array_equal(c, m.centres())
+        sizes = np.bincount(m.nearest64(c), minlength=N_CENTRES)
+        assert (sizes < PROBE_ITEM).any() and ((sizes > PROBE_ITEM) & (sizes <= 2 * PROBE_ITEM)).any() and (sizes > 2 * PROBE_ITEM).any(), (name, sizes)
+        if sc["metric"] != flat.METRIC_IP:
+            continue
+        q = np.random.default_rng(900 + sc["seed"]).standard_normal((NQ, m.d)).astype(np.float32)
+        q[8:20] = m.x[np.arange(8, 20) * 50 + 299] * 3.0 + 0.2 * q[8:20]
+        q[0], q[1], q[3] = m.x[5], 3.0 * m.x[17], m.x[N0 - 1]
+        s = m.scores64(q)
+        cols, _ = m.term_columns()
+        T = sum(np.float64(w) * t.astype(np.float64) for w, t in zip(BOOST_WEIGHTS, cols))
+        s = s[:, np.isfinite(T)]
+        T = T[np.isfinite(T)]
+        plain, boosted = np.argsort(-s, axis=1)[:, :10], np.argsort(-(0.7 * s + T), axis=1)[:, :10]
+        differs = sum(set(a.tolist()) != set(b.tolist()) for a, b in zip(plain, boosted))
+        assert differs > NQ // 2, (name, differs)
+
+
 # ---- the mirror: events, handles, store states ---------------------------------------------------------------------------------
+def test_handles_across_every_kind_of_event():
+    """(partition searchable, partition updatable, term valid, row set valid, grouping valid) after each kind of event."""
+    alive, added, dead = (True, True, True, True, True), (False, True, False, True, False), (False, False, False, False, False)
+    table = {("add", 20): added, ("set", 10): alive, ("copy",): alive, ("big",): alive, ("reserve", 0): alive, ("reserve", 50): alive,
+             ("del_big",): dead, ("del_one",): dead, ("del_scatter", 7): dead, ("del_suffix", 7): dead, ("reset",): dead,
+             ("pair", ("add", 20), ("set", 10)): added, ("pair", ("del_one",), ("add", 1)): dead, ("pair", ("add", 1), ("del_one",)): dead}
+    for event, want in table.items():
+        m = IndexModel(16, seed=3)
+        m.apply(("add", 1000))
+        m.apply(("big",))
+        c = m.centres()
+        m.partition_done(*m.partition_plan(), m.nearest64(c))
+        part, term, rs, grp = m.part, m.term_columns()[1], m.rowset("sparse")[2], m.grouping()[2]
+        assert part.kind == "partition" and m.valid(part) and m.updatable(part) and m.valid(term) and m.partition_plan()[0] == "keep"
+        m.apply(event)
+        got = (m.valid(part), m.updatable(part), m.valid(term), m.valid(rs), m.valid(grp))
+        assert got == want, (event, got)
+        action = m.partition_plan()[0]
+        assert action == ("drop" if event == ("reset",) else "recreate" if want == dead else "update" if want == added else "keep"), (event, action)
+        if event[0] == "pair" and want == dead:
+            assert m.n == 1000                                            # the row count is back: dead by the renumbering alone
+
+
+def test_the_label_mirror():
+    """Which rows take a fresh label: `assigned` is a constant per step, so a label names the step that wrote it."""
+    m = IndexModel(16, seed=4)
+    m.apply(("add", 1000))
+
+    def sync(step, expect):
+        action, rows = m.partition_plan()
+        assert action == expect, (step, action)
+        return rows, m.partition_done(action, rows, np.full(m.n, step, np.int32) if m.n else None)
+
+    assert (sync(0, "create")[1] == 0).all() and m.part_cap == 1000
+    op, = m.apply(("set", 10))
+    rows, labels = sync(1, "keep")                                        # the rows just set wait in their old lists ...
+    assert sorted(rows.tolist()) == sorted(op[1].tolist()) and (labels == 0).all() and m.part_cells[-1] == "search/set_pending"
+    m.apply(("reserve", 0))
+    rows, labels = sync(2, "update")                                      # ... until the update that names them
+    assert sorted(rows.tolist()) == sorted(op[1].tolist()) and (labels[rows] == 2).all() and (labels == 2).sum() == 10
+    assert m.part_cells[-1] == "update_rows/set+reserve_noop" and not m.set_since
+    m.apply(("add", 5))
+    rows, labels = sync(3, "update")
+    assert len(rows) == 0 and (labels[1000:] == 3).all() and len(labels) == 1005 and m.part_cells[-2:] == ["update/add_fits", "labels_grow"]
+    # a removal: the labels move with the rows, the rows set before it stay unnamed, rows added before it have no label yet
+    labels[:] = np.arange(1005)
+    op, _ = m.apply(("pair", ("set", 4), ("add", 3)))
+    before = m.labels.copy()
+    gone, = m.apply(("del_scatter", 6))
+    keep = np.setdiff1d(np.arange(1008), gone[1])
+    assert np.array_equal(m.labels, keep[keep < 1005]) and np.array_equal(m.drop_removed(before), m.labels)
+    pending = sorted(int(np.searchsorted(keep, r)) for r in op[1] if r in keep)
+    assert sorted(m.set_since) == pending
+    rows, labels = sync(-1, "recreate")
+    assert len(labels) == 1002 and (labels[keep >= 1005] == -1).all() and np.array_equal(labels[keep < 1005], keep[keep < 1005])
+    assert m.part_cells[-1] == "recreate/set+add_fits+remove_scattered" and sorted(m.set_since) == pending
+    m.apply(("reserve", 0))
+    rows, labels = sync(-2, "update")
+    assert sorted(rows.tolist()) == pending and (labels == -2).sum() == len(pending) and m.part_cells[-1] == "update_rows/reserve_noop"
+    # a delete and an add that restore the row count: dead all the same
+    m.apply(("pair", ("del_one",), ("add", 1)))
+    assert m.n == m.part.n and sync(-3, "recreate")[1][-1] == -3 and m.part_cells[-1].startswith("recreate_same_count/")
+    m.apply(("reset",))
+    assert np.array_equal(m.drop_removed(np.arange(5)), []) and sync(0, "drop")[1].size == 0 and m.part is None
+    assert m.partition_plan()[0] == "none"
+    m.apply(("add", 30))
+    assert (sync(7, "create")[1] == 7).all()
+
+
 def test_events_on_the_mirror():
     m = IndexModel(128, seed=9)
     assert m.apply(("add", 1000))[0][0] == "add" and m.cap == 1024 and m.cells == ["add_grows"]
     keep = m.x.copy()
     m.after_batch_search()
     assert m.shadow == "complete" and m.shadow_rows() == 1000
-    rs, grp = m.rowset("sparse")[2], m.grouping()[2]
+    rs, grp, term = m.rowset("sparse")[2], m.grouping()[2], m.term_columns()[1]
+    m.partition_done(*m.partition_plan(), m.nearest64(m.centres()))
+    part = m.part
     op, = m.apply(("add", 20))
     assert m.shadow == "complete" and m.shadow_rows() == 1020 and np.array_equal(m.x[:1000], keep) and np.array_equal(m.x[1000:], op[1])
     assert m.valid(rs) and not m.valid(grp)                             # a row set outlives an add, a grouping does not
+    assert not m.valid(term) and not m.valid(part) and m.updatable(part)   # ... nor a term; a partition waits for its update
+    term = m.term_columns()[1]
+    m.partition_done(*m.partition_plan(), m.nearest64(m.centres()))
+    part = m.part
     op, = m.apply(("set", 10))
     assert np.array_equal(m.x[op[1]], op[2]) and op[1][0] == 1019 and m.valid(rs) and m.shadow == "complete"
+    assert m.valid(term) and m.valid(part) and part.n == 1020           # set_rows keeps the row numbers: both stay valid
     m.apply(("copy",))
     a, b = m.copies
     assert a < b and m.x[a].tobytes() == m.x[b].tobytes()
     grp = m.grouping()[2]
     op, = m.apply(("del_scatter", 30))
     assert m.n == 990 and not m.valid(rs) and not m.valid(grp) and m.shadow == "emptied" and m.shadow_rows() == 0
+    assert not m.valid(term) and not m.valid(part) and not m.updatable(part) and len(m.labels) == 990
     if m.copies is not None:                                            # the copies moved with the renumbering
         a2, b2 = m.copies
         assert (a2, b2) != (a, b) or not (op[1] < b).any()
@@ -215,9 +429,13 @@ def replay(name):
     m = IndexModel(sc["d"], sc["metric"], sc["norms"], sc["seed"])
     m.cap = sc["reserve"]
     ns = []
+    centres = m.centres()
     for event in [("add", N0)] + list(sc["events"]):
         m.apply(event)
         ns.append(m.n)
+        if sc["metric"] == flat.METRIC_IP:                                  # the partition, as sync_handles keeps it in step
+            action, rows = m.partition_plan()
+            m.partition_done(action, rows, m.nearest64(centres) if m.n else None)
         if m.n:
             m.after_batch_search()
     return m, ns
@@ -230,6 +448,12 @@ UNREACHABLE = {
     "every cell of the int8 code": "the code needs 500,000 rows (kCode8MinRows); test_code8_gpu has its lifecycle",
     "free": "freed with the index: nothing can be searched afterwards",
     "every route after reset": "the index is empty: only the state and the refusal of stale handles are checked",
+    "partition: update racing a device-variant search": "excluded by the contract: update excludes the searches of its partition, "
+                                                        "searches enqueued by the device variant must have finished",
+    "partition / term: every cell on an L2 index": "refused at creation or at the search (check_l2_refusals)",
+    "partition / term: the routes inside a capture": "a capturing stream is MVDB_ERR_ARG (test_probe_gpu, test_examples_gpu, test_boost_gpu)",
+    "partition: update(rows) on an empty index": "after a reset there is no row to name: the partition is dropped, then created anew",
+    "term: valid after a removal": "a term dies with every removal; one is built for each (n, generation) the scenarios visit",
     "l2:reserve / reset with offsets behind": "reserve and reset drop the offsets with the shadow whatever they hold: the "
                                               "cells with offsets present are the same code",
 }
@@ -253,6 +477,37 @@ def test_scenarios_reach_every_cell_of_the_table():
     # d = 30: no shadow, ever
     assert all(c.endswith("/absent") or "/" not in c for c in cells["padded_d30"]), cells["padded_d30"]
     assert all(isinstance(reason, str) and reason for reason in UNREACHABLE.values())
+
+
+def test_the_partition_meets_every_required_cell():
+    """What the partition goes through across the inner-product scenarios, read off the model's part_cells
+    ("action/operations since it was last in step"); the scenario "probe_growing" exists for the cells the others miss."""
+    cells = {name: replay(name)[0].part_cells for name, sc in SCENARIOS.items() if sc["metric"] == flat.METRIC_IP}
+    every = [c for name in cells for c in cells[name]]
+    ops = [(c.split("/")[0], c.split("/")[1].split("+")) for c in every if "/" in c]
+    required = {
+        "update() after add_fits": ("update", ["add_fits"]) in ops,
+        "update() after add_grows": ("update", ["add_grows"]) in ops,
+        "update() after reserve_grows, then an add": ("update", ["reserve_grows", "add_fits"]) in ops,
+        "update(rows) after set": any(a == "update_rows" and o[0] == "set" for a, o in ops),
+        "update after (pair, add, set)": any(a == "update_rows" and o[:2] in (["add_fits", "set"], ["add_grows", "set"]) for a, o in ops),
+        "a search between a set and its update": "search/set_pending" in every,
+        "refusal after reset": ("refused", ["reset"]) in ops,
+        "a delete and an add that restore the row count": any(a == "recreate_same_count" and o[0].startswith("remove_") and o[-1] == "add_fits" for a, o in ops),
+        "label storage past its first capacity": "labels_grow" in every,
+        "created by the library again after a reset": any(a == "refused/reset" and b.startswith("create/") for cs in cells.values() for a, b in zip(cs, cs[1:])),
+    }
+    for kind in ("remove_one", "remove_one_early", "remove_scattered", "remove_suffix"):
+        required["re-creation after " + kind] = any(a.startswith("recreate") and kind in o for a, o in ops)
+    assert all(required.values()), [what for what, met in required.items() if not met]
+    # a row set by set_rows is searched in its old list first and named to update later, in one scenario
+    for name in ("unit_growing", "probe_growing"):
+        first = cells[name].index("search/set_pending")
+        assert any(c.startswith("update_rows/set") for c in cells[name][first:]), (name, cells[name])
+    # no partition on the L2 scenario (refused: check_l2_refusals)
+    assert replay("l2_offsets")[0].part_cells == []
+    # the growing scenario's storage crosses its capacity under the partition: the rows move, the labels are copied
+    assert {"update/add_grows", "labels_grow", "update/reserve_grows+add_fits"} <= set(cells["probe_growing"])
 
 
 def test_every_route_is_checked_after_every_kind_of_event():

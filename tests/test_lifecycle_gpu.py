@@ -3,8 +3,14 @@
 A scenario is a list of events (index_model.py names them) run on ONE index with the model beside it.  After every event
 `check` compares the state (ntotal, the bytes of get_rows, shadow_rows as the table above ShadowStore in csrc/mvdb.hip
 predicts it) and every route — exact scan, certified batch, range batch, range join, the four forms of resident row set on
-every entry point that takes one, grouping, distinct, MaxSim, assign, one k-means step, MMR, grouped search — with the mirror,
-and at the end of the scenario the whole index with a rebuild from the mirror.
+every entry point that takes one, grouping, distinct, MaxSim, assign, one k-means step, MMR, grouped search, probed search,
+search by examples, boosted search — with the mirror, and at the end of the scenario the whole index with a rebuild from the
+mirror.
+
+Two more resident handles live beside the row sets and the grouping: ONE partition of 33 lists, kept in step as the model's
+partition_plan says (kept, update()d, or — after a removal — read back and re-created from its labels), and two term columns,
+rebuilt whenever the row count or the numbering changes.  Their labels and values are compared with the mirror's after every
+change; the three routes are compared as bits with their contract oracles fed the device's own single-query scores.
 
 Shapes: d = 128 (the narrowest width with a shadow kernel) and d = 30 (padded rows, no shadow); n between 3,900 and 4,450,
 crossing 4,096 (from where a sorted row list becomes a bitmap or gains a bitmap twin) in both directions, never a multiple of
@@ -21,7 +27,7 @@ import time
 import numpy as np
 import pytest
 
-from index_model import ROWSET_BITMAP_MIN_ROWS, IndexModel
+from index_model import BOOST_WEIGHTS, N_CENTRES, ROWSET_BITMAP_MIN_ROWS, IndexModel
 from oracle import flat
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +45,10 @@ _EVENTS_3 = [("add", 97), ("set", 37), ("big",), ("set", 11), ("del_big",), ("ad
 _EVENTS_4 = [("add", 97), ("set", 37), ("pair", ("add", 40), ("set", 30)), ("pair", ("add", 23), ("add", 19)),
              ("pair", ("del_scatter", 45), ("add", 60)), ("pair", ("add", 30), ("del_one",)), ("copy",), ("del_scatter", 21),
              ("del_suffix", 350), ("add", 140)]
+# the cells of the partition the scenarios above miss: rows reallocated under it by a reserve, then an add; an add and a set
+# with no search between; a delete and an add that bring the row count back
+_EVENTS_5 = [("add", 97), ("reserve", 300), ("add", 31), ("pair", ("add", 40), ("set", 30)), ("pair", ("del_scatter", 9), ("add", 9)),
+             ("set", 25), ("copy",), ("reserve", 0), ("del_suffix", 300), ("add", 120), ("big",), ("del_big",)]
 
 
 def random_events(seed, count=12):
@@ -84,9 +94,11 @@ SCENARIOS = {
     "padded_d30": dict(d=30, metric=flat.METRIC_IP, norms="unit", reserve=4500, seed=5, events=_EVENTS_1),
     "random_18": dict(d=128, metric=flat.METRIC_IP, norms="unit", reserve=0, seed=18, events=random_events(18)),
     "random_27": dict(d=128, metric=flat.METRIC_IP, norms="mixed", reserve=0, seed=27, events=random_events(27)),
+    "probe_growing": dict(d=128, metric=flat.METRIC_IP, norms="mixed", reserve=0, seed=8, events=_EVENTS_5),
 }
-ROUTES = ("state", "exact", "batch", "range", "join", "rowsets", "grouping", "distinct", "maxsim", "assign", "kmeans", "mmr", "grouped")
-IP_ONLY = ("distinct", "maxsim", "assign", "kmeans", "mmr")
+ROUTES = ("state", "exact", "batch", "range", "join", "rowsets", "grouping", "distinct", "maxsim", "assign", "kmeans", "mmr", "grouped",
+          "probe", "examples", "boost")
+IP_ONLY = ("distinct", "maxsim", "assign", "kmeans", "mmr", "probe", "examples", "boost")
 
 
 def routes_checked(scenario, n_after):
@@ -115,7 +127,8 @@ def apply_ops(idx, ops):
 
 
 class Run:
-    """One scenario in flight: the index, the model, the queries and the handles (row sets by form, one grouping)."""
+    """One scenario in flight: the index, the model, the queries and the handles (row sets by form, one grouping, one partition
+    with the index of its centres, two term columns)."""
 
     def __init__(self, native, sc, model=None, idx=None):
         self.native, self.sc = native, sc
@@ -126,6 +139,16 @@ class Run:
         self.grouping = None              # (Grouping, Handle, codes)
         self.refused_l2 = False
         self.q = None
+        self.partition = None             # the Partition; the model holds its Handle and the labels it must have
+        self.mirrors_partition = model is None   # (the rebuild's partition is the library's own: labels=None)
+        self.centres = None               # its stored centres, as partition.centres() returns them ...
+        self.cidx = None                  # ... and the index that holds exactly those: the contract's definition of the probes
+        self.terms = None                 # ([RowTerm, RowTerm], Handle)
+        self.coarse = None                # [6, C] the centre index's single-query bits for q[:6], per check
+        self.extra_terms = None           # per check: (a term of -0.0, the tie column's term, the tie column)
+        self.refused_list_probe = False
+        self.pending = np.empty(0, np.int64)   # rows set_rows wrote that wait in their old lists (partition_plan: "keep")
+        self.pending_checks = 0           # the checks that ran in that state
 
     def make_queries(self):
         m = self.model
@@ -150,6 +173,12 @@ class Run:
             rs.close()
         if self.grouping:
             self.grouping[0].free()
+        if self.partition:
+            self.partition.free()
+        for t in (self.terms[0] if self.terms else []) + list((self.extra_terms or ())[:2]):
+            t.free()
+        if self.cidx is not None and self.mirrors_partition:
+            self.cidx.close()
         self.idx.close()
 
 
@@ -189,9 +218,42 @@ def _p(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-def refused_untouched(run, rs, grp, what):
-    """Every entry point that takes a row set (or the grouping `grp`, when rs is None) refuses the stale handle and leaves the
-    caller's buffers as they were."""
+class DeviceBuffers:
+    """Queries, examples and poisoned result buffers on the device, for the device variants of the three routes."""
+
+    def __init__(self, q, v):
+        import torch
+        self.torch = torch
+        self.q, self.v = torch.from_numpy(q[:6].copy()).cuda(), torch.from_numpy(v).cuda()
+        self.D = torch.full((6, K), 7.5, dtype=torch.float32, device="cuda")
+        self.I = torch.full((6, K), 777, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+
+    def results(self, rows=6):
+        self.torch.cuda.synchronize()
+        D, I = self.D.cpu().numpy(), self.I.cpu().numpy()
+        assert (D[rows:] == 7.5).all() and (I[rows:] == 777).all()       # nothing behind the results is written
+        self.D.fill_(7.5)
+        self.I.fill_(777)
+        return D[:rows], I[:rows]
+
+    def untouched(self):
+        self.torch.cuda.synchronize()
+        return bool((self.D == 7.5).all()) and bool((self.I == 777).all())
+
+
+def example_vectors(q):
+    """The vectors of the search by examples: three positives, then two negatives."""
+    return np.ascontiguousarray(np.concatenate([q[5:8], q[20:22]]))
+
+
+def refused_untouched(run, rs, grp, what, part=None, terms=None, match="another state"):
+    """Every entry point that takes a row set (or the grouping `grp`, the partition `part`, the term columns `terms`, when rs is
+    None) refuses the stale handle and leaves the caller's buffers as they were."""
+    if part is not None or terms is not None or (rs is not None and run.ip and run.partition is not None and run.terms is not None):
+        refused_new_routes(run, rs, part, terms, what, match)
+    if part is not None or terms is not None:
+        return
     native, idx, q = run.native, run.idx, run.q
     L, h = native.lib(), idx.handle
     n = idx.ntotal
@@ -233,9 +295,144 @@ def refused_untouched(run, rs, grp, what):
         fresh_grp.free()
 
 
+def refused_new_routes(run, rs, part, terms, what, match):
+    """Probed search, search by examples, boosted search and boost_combine, host and device entry points, with ONE stale
+    handle — the row set rs, the partition `part` or the term columns `terms` — beside valid ones: refused with the library's
+    message for it, nothing written to host or device buffers."""
+    native, idx, q = run.native, run.idx, run.q
+    L, h = native.lib(), idx.handle
+    Df, If = np.full((NQ, K), 7.0, np.float32), np.full((NQ, K), 7, np.int64)
+    T = np.full(max(idx.ntotal, 1), 7.0, np.float32)
+    v = example_vectors(q)
+    dev = DeviceBuffers(q, v)
+    qp, vp, Dp, Ip = dev.q.data_ptr(), dev.v.data_ptr(), dev.D.data_ptr(), dev.I.data_ptr()
+    rsh = rs._h if rs is not None else None
+    if rs is not None:                                                   # beside the stale row set: the run's valid handles
+        part, terms = run.partition, run.terms[0]
+    calls = []
+    if part is not None:
+        ph = part._h
+        calls += [("search_probe", lambda: L.mvdb_index_search_probe(h, ph, _p(q), 1, K, 5, 0, rsh, _p(Df), _p(If))),
+                  ("search_probe batch", lambda: L.mvdb_index_search_probe(h, ph, _p(q), NQ, K, N_CENTRES, 0, rsh, _p(Df), _p(If))),
+                  ("search_probe_device", lambda: idx.search_probe_device(qp, 6, K, 5, part, Dp, Ip, rowset=rs, label_offset=1000))]
+    if rs is not None:
+        calls += [("search_examples", lambda: L.mvdb_index_search_examples(h, _p(v), 3, 2, K, 0, rsh, None, 0, _p(Df), _p(If))),
+                  ("search_examples_device", lambda: idx.search_examples_device(vp, 3, 2, K, Dp, Ip, rowset=rs, label_offset=1000))]
+    if terms is not None:
+        keep, args = idx._boost_args(terms, BOOST_WEIGHTS, None, None)
+        w = ctypes.c_float(0.7)
+        calls += [("search_boosted", lambda: L.mvdb_index_search_boosted(h, _p(q), 1, K, 0, w, *args, rsh, _p(Df), _p(If))),
+                  ("search_boosted batch", lambda: L.mvdb_index_search_boosted(h, _p(q), NQ, K, 0, w, *args, rsh, _p(Df), _p(If))),
+                  ("search_boosted_device", lambda: idx.search_boosted_device(qp, 6, K, terms, BOOST_WEIGHTS, Dp, Ip, score_weight=0.7, rowset=rs,
+                                                                              label_offset=1000))]
+        if rs is None:
+            calls.append(("boost_combine", lambda: L.mvdb_index_boost_combine(h, *args, _p(T))))
+    assert calls, what
+    for name, call in calls:
+        with pytest.raises(ValueError, match=match):
+            native.check(call() or 0)
+        assert (Df == 7.0).all() and (If == 7).all() and (T == 7.0).all(), (what, name)
+    assert dev.untouched(), (what, "a refused device variant wrote to its buffers")
+
+
+def sync_terms(run, what):
+    """The two term columns: shown refused once stale (rows added or removed since), built from the model's columns."""
+    m, idx = run.model, run.idx
+    if run.terms and not m.valid(run.terms[1]):
+        terms, _ = run.terms
+        run.terms = None
+        refused_untouched(run, None, None, (what, "stale terms"), terms=terms, match=r"holds \d+ rows, the index \d+|before rows were removed")
+        for t in terms:
+            t.free()
+    if m.n and run.terms is None:
+        cols, h = m.term_columns()
+        run.terms = ([idx.rowterm(c) for c in cols], h)
+        assert all(len(t) == m.n for t in run.terms[0]), what
+
+
+def sync_partition(run, what):
+    """The partition, as the model's partition_plan says; after every change its labels are the mirror's, integer for integer."""
+    m, idx = run.model, run.idx
+    if not run.mirrors_partition:                                        # the rebuild: labelled by the library, never touched
+        if run.partition is None:
+            run.partition = idx.partition(run.centres)
+        return
+    action, rows = m.partition_plan()
+    run.pending = rows if action == "keep" else np.empty(0, np.int64)
+    if action in ("none", "keep"):
+        m.partition_done(action, rows)
+        return
+    part = run.partition
+    if action == "create":
+        run.partition = part = idx.partition(m.centres())                # labels=None: the library's own assign
+        if run.cidx is None:
+            run.centres = part.centres()
+            assert np.array_equal(bits(run.centres), bits(m.centres())), (what, "centres as given: none is normalised")
+            run.cidx = run.native.FlatIndex(m.d)
+            run.cidx.add(run.centres, normalize=False)
+        assert np.array_equal(bits(part.centres()), bits(run.centres)), what
+        sizes = part.sizes()                                             # lists on both sides of the 128-position work item, one of three items
+        assert (sizes < 128).any() and ((sizes > 128) & (sizes <= 256)).any() and (sizes > 256).any(), (what, sizes)
+    elif action == "update":
+        if not m.valid(m.part):                                          # rows were added: stale for a search, not for update
+            refused_untouched(run, None, None, (what, "stale partition"), part=part, match="mvdb_partition_update first")
+        part.update(rows if len(rows) else None)
+    else:                                                                # rows were removed, or the index was reset: dead
+        refused_untouched(run, None, None, (what, "dead partition"), part=part, match="rows were removed since the partition was built")
+        for named in (None, np.zeros(1, np.int64)):
+            with pytest.raises(ValueError, match="rows were removed since the partition was built"):
+                part.update(named)
+        kept = m.drop_removed(part.labels())
+        assert np.array_equal(kept, m.labels), (what, "the labels read back, the removed rows' dropped", np.flatnonzero(kept != m.labels)[:8])
+        part.free()
+        run.partition = part = None
+    assigned = idx.assign(run.centres)[0] if m.n else None
+    want = m.partition_done(action, rows, assigned)
+    if action == "recreate":
+        run.partition = part = idx.partition(run.centres, labels=want)
+    if part is None:
+        return
+    got = part.labels()
+    assert got.dtype == np.int32 and np.array_equal(got, want), (what, action, "labels", np.flatnonzero(got != want)[:8])
+    assert np.array_equal(part.sizes(), np.bincount(want, minlength=N_CENTRES)) and len(part) == m.n and part.n_lists == N_CENTRES, (what, action)
+
+
+def check_partition_invariant(run, what):
+    """Every row no set_rows wrote since it was labelled holds the label assign gives it NOW (a row's label depends on its own
+    vector and the centres alone); a row that waits in its old list is found through that list, with its new score."""
+    from probe_oracle import probes
+    m, idx = run.model, run.idx
+    assigned = idx.assign(run.centres)[0]
+    settled = np.ones(m.n, bool)
+    settled[sorted(m.set_since)] = False
+    assert np.array_equal(m.labels[settled], assigned[settled]), (what, "labels of rows nobody wrote", np.flatnonzero(settled & (m.labels != assigned))[:8])
+    if not len(run.pending):
+        return
+    run.pending_checks += 1
+    moved = run.pending[m.labels[run.pending] != assigned[run.pending]]
+    if not len(moved):
+        return
+    r = int(moved[0])
+    query = m.x[r:r + 1] / np.float32(max(1.0, np.linalg.norm(m.x[r]) / 2))   # (a row of norm ~40: the scores stay small)
+    coarse = score_matrix(run.cidx, query, N_CENTRES)[0][0]
+    at = int(np.flatnonzero(probes(coarse, N_CENTRES) == m.labels[r])[0])  # its OLD list is the query's probe number at + 1
+    alone = idx.rowset(np.delete(np.arange(m.n, dtype=np.int64), r), excluded=True)   # a bitmap that selects this row alone
+    assert alone.is_bitmap and len(alone) == 1
+    Dw, Iw = idx.search_rowset(query, K, alone)
+    assert Iw[0, 0] == r and (Iw[0, 1:] == -1).all()
+    same_bits(idx.search_probe(query, K, at + 1, run.partition, rowset=alone), (Dw, Iw), (what, "old list, new vector", r, at))
+    if at:                                                               # one probe fewer: the row is in none of the probed lists
+        D, I = idx.search_probe(query, K, at, run.partition, rowset=alone)
+        assert (I == -1).all(), (what, "the old list is not probed", r, at, I[0])
+    alone.close()
+
+
 def sync_handles(run, what):
     """Stale handles are shown to be refused and dropped; missing ones are built on the index as it is now."""
     m, idx = run.model, run.idx
+    if run.ip:                                                           # first: the row sets' refusals pass them as the VALID handles
+        sync_terms(run, what)
+        sync_partition(run, what)
     for form in FORMS:
         if form in run.rowsets and not m.valid(run.rowsets[form][1]):
             rs, _ = run.rowsets.pop(form)
@@ -391,6 +588,143 @@ def check_scored_routes(run, S, what, rowset=None, selected=None):
     for i, picks in enumerate(check_against_candidates(D, I, Dc, Ic, 5, what)):
         ok, msg, _ = m.mmr_adjudicate(Dc[i], Ic[i], picks, 5, 0.5)
         assert ok, (what, "mmr", i, msg)
+    check_probe(run, S, what, rowset, selected)
+    check_examples(run, S, what, rowset, selected)
+    check_boost(run, S, what, rowset, selected)
+    if rowset is None:
+        check_device_variants(run, what)
+
+
+def same_bits(got, want, what):
+    assert np.array_equal(got[1], want[1]), (what, "rows", got[1], want[1])
+    assert np.array_equal(bits(got[0]), bits(want[0])), (what, "scores", got[0], want[0])
+
+
+def copies_selected(m, selected):
+    return m.copies is not None and (selected is None or np.isin(m.copies, selected).all())
+
+
+def check_probe(run, S, what, rowset, selected):
+    """Probed search against probe_oracle fed the device's bits: the coarse row from the index of the stored centres, the fine
+    row from the score matrix, the labels from the mirror — between a set_rows and its update a changed row's OLD label."""
+    idx, m, q = run.idx, run.model, run.q
+    part, C = run.partition, N_CENTRES
+    if rowset is not None and not rowset.is_bitmap:                      # a list-form set is refused by contract: shown once
+        if not run.refused_list_probe:
+            Df, If = np.full((NQ, K), 7.0, np.float32), np.full((NQ, K), 7, np.int64)
+            with pytest.raises(ValueError, match="takes a bitmap-form row set"):
+                run.native.check(run.native.lib().mvdb_index_search_probe(idx.handle, part._h, _p(q), NQ, K, 5, 0, rowset._h, _p(Df), _p(If)))
+            assert (Df == 7.0).all() and (If == 7).all(), (what, "list-form set")
+            run.refused_list_probe = True
+        return
+    for nprobe in (1, 5, C):
+        for t in (0, 2, 4):
+            got = idx.search_probe(q[t:t + 1], K, nprobe, part, rowset=rowset)
+            Dw, Iw, P = m.probe(run.coarse[t], S[t], m.labels, K, nprobe, selected)
+            same_bits((got[0][0], got[1][0]), (Dw, Iw), (what, "probe", nprobe, t))
+            if nprobe == C:                                              # every list: the exact search over the labelled rows
+                assert (m.labels >= 0).all()
+                same_bits(got, idx.search(q[t:t + 1], K) if rowset is None else idx.search_rowset(q[t:t + 1], K, rowset), (what, "probe, every list", t))
+            if t == 4 and copies_selected(m, selected) and np.isin(m.labels[list(m.copies)], P).all():
+                ties_lowest_first(m, got[0][0], got[1][0], (what, "probe", nprobe))
+    D, I = idx.search_probe(q[:6], K, 5, part, rowset=rowset)            # a batch in one call: each row its own probes
+    for t in range(6):
+        Dw, Iw, _ = m.probe(run.coarse[t], S[t], m.labels, K, 5, selected)
+        same_bits((D[t], I[t]), (Dw, Iw), (what, "probe batch", t))
+
+
+def check_examples(run, S, what, rowset, selected):
+    idx, m, q = run.idx, run.model, run.q
+    sel = np.arange(m.n, dtype=np.int64) if selected is None else selected
+    Sx = np.concatenate([S[5:8], S[20:22]])
+    skip = np.array([m.ranking(S[j], sel)[1][0] for j in (5, 6, 7)], np.int64)   # the top hit of each positive
+    want = m.examples(Sx, 3, K, skip, selected)
+    assert (want[1] >= 0).all() and not np.isin(skip, want[1]).any()
+    try:
+        idx.set_option("examples_vectors_per_pass", 2)                   # three passes that carry the packed maxima
+        calls0, passes0 = idx.examples_counters()
+        carried = idx.search_examples(q[5:8], q[20:22], K, rowset=rowset, skip_rows=skip)
+        assert idx.examples_counters() == (calls0 + 1, passes0 + 3), (what, "examples passes")
+    finally:
+        idx.set_option("examples_vectors_per_pass", 0)
+    same_bits(carried, want, (what, "examples, 2 vectors per pass"))
+    same_bits(idx.search_examples(q[5:8], q[20:22], K, rowset=rowset, skip_rows=skip), want, (what, "examples"))
+    got = idx.search_examples(q[4:5], None, K, rowset=rowset)            # one positive, no negative: the plain search
+    same_bits(got, m.examples(S[4:5], 1, K, (), selected), (what, "examples, one positive"))
+    if rowset is None or rowset.is_bitmap or (np.diff(sel) > 0).all():   # (an unsorted list: search_rowset's ties go by list position)
+        Dw, Iw = idx.search(q[4:5], K) if rowset is None else idx.search_rowset(q[4:5], K, rowset)
+        same_bits(got, (Dw[0], Iw[0]), (what, "examples vs search"))
+    if copies_selected(m, selected):
+        ties_lowest_first(m, got[0], got[1], (what, "examples"))
+
+
+def check_boost(run, S, what, rowset, selected):
+    """Boosted search against boost_oracle: the columns are the model's, recomputed — the resident terms must still hold them."""
+    idx, m, q = run.idx, run.model, run.q
+    terms, n = run.terms[0], m.n
+    cols, special = m.term_columns()[0], m.term_special()
+    zero, tie, tie_col = run.extra_terms
+    inside = (lambda r: True) if selected is None else (lambda r: r in selected)
+    sparse = m.sparse_entries()
+    for sp in (None, sparse):
+        T = m.boost_column(cols, BOOST_WEIGHTS, n, sp)
+        if rowset is None:                                               # the column by itself: the NaN row compares as bits
+            got_T = idx.boost_combine(terms, BOOST_WEIGHTS, *(sp or (None, None)))
+            assert np.array_equal(bits(got_T), bits(T)), (what, "boost_combine", sp is not None, np.flatnonzero(bits(got_T) != bits(T))[:8])
+            assert np.isnan(got_T[special["nan"]]) and got_T[special["pinf"]] == np.inf and got_T[special["ninf"]] == -np.inf
+        singles = {}
+        for t in (0, 2, 4):
+            D, I = idx.search_boosted(q[t], K, terms, BOOST_WEIGHTS, score_weight=0.7, sparse_rows=sp and sp[0], sparse_values=sp and sp[1], rowset=rowset)
+            same_bits((D[0], I[0]), m.boosted(S[t], T, 0.7, K, selected), (what, "boost", t, sp is not None))
+            assert special["nan"] not in I[0] and special["ninf"] not in I[0] and (I[0] >= 0).all(), (what, "boost", t)
+            if inside(special["pinf"]):
+                assert I[0, 0] == special["pinf"] and D[0, 0] == np.inf, (what, "the +inf row leads", t)
+            singles[t] = (D[0], I[0])
+        if sp is None:                                                   # a batch shares T: each row equals its single call
+            D, I = idx.search_boosted(q[:6], K, terms, BOOST_WEIGHTS, score_weight=0.7, rowset=rowset)
+            for t in range(6):
+                same_bits((D[t], I[t]), singles[t] if t in singles else m.boosted(S[t], T, 0.7, K, selected), (what, "boost batch", t))
+    # a term of -0.0 at weight 1 with w_s = 1: the plain search
+    if rowset is None or rowset.is_bitmap or (np.diff(selected) > 0).all():
+        for t in (0, 2, 4):
+            want = idx.search(q[t:t + 1], K) if rowset is None else idx.search_rowset(q[t:t + 1], K, rowset)
+            same_bits(idx.search_boosted(q[t], K, [zero], [1.0], score_weight=1.0, rowset=rowset), want, (what, "boost, -0.0", t))
+    # equal terms on the two copies: their scores tie, the lower ROW first in every form (an unsorted list too)
+    D, I = idx.search_boosted(q[4], K, [tie], [BOOST_WEIGHTS[1]], score_weight=0.7, rowset=rowset)
+    same_bits((D[0], I[0]), m.boosted(S[4], m.boost_column([tie_col], BOOST_WEIGHTS[1:], n), 0.7, K, selected), (what, "boost, tied copies"))
+    if copies_selected(m, selected):
+        ties_lowest_first(m, D[0], I[0], (what, "boost"))
+
+
+def check_device_variants(run, what):
+    """The device variants of the three routes on a stream of their own with label_offset = 1000: the host results, the labels
+    shifted, the padding still -1."""
+    import torch
+    idx, m, q = run.idx, run.model, run.q
+    terms = run.terms[0]
+    dev = DeviceBuffers(q, example_vectors(q))
+    stream = torch.cuda.Stream()
+    qp, vp, Dp, Ip, s = dev.q.data_ptr(), dev.v.data_ptr(), dev.D.data_ptr(), dev.I.data_ptr(), stream.cuda_stream
+    sparse = m.sparse_entries()
+    skip = np.array([m.touched, 0], np.int64)
+    skip_dev = torch.from_numpy(skip).cuda()
+    torch.cuda.synchronize()
+    for name, rows, call, host in (
+            ("probe", 6, lambda: idx.search_probe_device(qp, 6, K, 1, run.partition, Dp, Ip, stream=s, label_offset=1000),
+             lambda: idx.search_probe(q[:6], K, 1, run.partition)),
+            ("examples", 1, lambda: idx.search_examples_device(vp, 3, 2, K, Dp, Ip, skip_rows_ptr=skip_dev.data_ptr(), n_skip=2, stream=s, label_offset=1000),
+             lambda: tuple(a[None] for a in idx.search_examples(q[5:8], q[20:22], K, skip_rows=skip))),
+            ("boost batch", 6, lambda: idx.search_boosted_device(qp, 6, K, terms, BOOST_WEIGHTS, Dp, Ip, score_weight=0.7, stream=s, label_offset=1000),
+             lambda: idx.search_boosted(q[:6], K, terms, BOOST_WEIGHTS, score_weight=0.7)),
+            ("boost sparse", 1, lambda: idx.search_boosted_device(qp, 1, K, terms, BOOST_WEIGHTS, Dp, Ip, score_weight=0.7, sparse_rows=sparse[0],
+                                                                  sparse_values=sparse[1], stream=s, label_offset=1000),
+             lambda: idx.search_boosted(q[0], K, terms, BOOST_WEIGHTS, score_weight=0.7, sparse_rows=sparse[0], sparse_values=sparse[1]))):
+        call()
+        stream.synchronize()
+        D, I = dev.results(rows)
+        Dh, Ih = host()
+        assert ((I >= 1000) | (I == -1)).all(), (what, name, "padding stays -1 under a label offset")
+        same_bits((D, np.where(I >= 0, I - 1000, -1)), (Dh, Ih), (what, name, "device variant"))
 
 
 def check_rowset(run, form, S, what):
@@ -424,12 +758,22 @@ def check_grouped(run, what):
 
 
 def check_l2_refusals(run, what):
-    idx, q = run.idx, run.q
+    idx, q, m = run.idx, run.q, run.model
     grp = run.grouping[0]
+    term = idx.rowterm(np.zeros(m.n, np.float32))                        # (a column can be stored; no search takes it)
+    ip = run.native.FlatIndex(m.d)                                       # a partition can only come from an inner-product index
+    ip.add(m.x[:64], normalize=False)
+    foreign = ip.partition(m.centres())
     for call in (lambda: idx.search_mmr(q[:2], 5, 32, 0.5), lambda: idx.search_distinct(q[:2], K, 32, grp),
-                 lambda: idx.search_maxsim(q[4:8], 5, grp), lambda: idx.assign(q[:N_VECTORS]), lambda: idx.kmeans(q[:5], 1)):
+                 lambda: idx.search_maxsim(q[4:8], 5, grp), lambda: idx.assign(q[:N_VECTORS]), lambda: idx.kmeans(q[:5], 1),
+                 lambda: idx.partition(m.centres()), lambda: idx.partition(m.centres(), labels=np.zeros(m.n, np.int32)),
+                 lambda: idx.search_probe(q[:2], K, 5, foreign), lambda: idx.search_examples(q[5:8], q[20:22], K),
+                 lambda: idx.search_boosted(q[:2], K, [term], [1.0]), lambda: idx.boost_combine([term], [1.0])):
         with pytest.raises(ValueError, match="inner-product"):
             call()
+    foreign.free()
+    ip.close()
+    term.free()
     run.refused_l2 = True
 
 
@@ -452,12 +796,20 @@ def check(run, what):
         assert np.abs(S.astype(np.float64) - m.scores64(run.q[:N_VECTORS])).max() <= 1e-4, (what, "score matrix vs float64")
         for t in (0, 4):
             assert np.array_equal(order[t], m.ranking(S[t], np.arange(m.n))[1]), (what, "order of the full ranking", t)
+        run.coarse = score_matrix(run.cidx, run.q[:6], N_CENTRES)[0]
+        tie_col = m.tie_column()
+        run.extra_terms = (idx.rowterm(np.full(m.n, -0.0, np.float32)), idx.rowterm(tie_col), tie_col)
+        check_partition_invariant(run, what)
         check_scored_routes(run, S, what)
     elif not run.refused_l2:
         check_l2_refusals(run, what)
     for form in FORMS:
         check_rowset(run, form, S, what)
     check_grouped(run, what)
+    if run.extra_terms:
+        for t in run.extra_terms[:2]:
+            t.free()
+        run.extra_terms = None
     assert idx.shadow_rows == m.shadow_rows(), (what, "shadow_rows at the end of the check")
 
 
@@ -481,6 +833,20 @@ def snapshot(run):
         out.append(("maxsim", idx.search_maxsim(q[4:8], 5, grp)))
         out.append(("assign", idx.assign(q[:N_VECTORS])))
         out.append(("assign dense", idx.assign(q[:N_VECTORS], rowset=run.rowsets["dense"][0])))
+        part, terms = run.partition, run.terms[0]
+        out.append(("partition", (part.labels(), part.sizes(), part.centres())))
+        for nprobe in (1, 5, N_CENTRES):
+            out.append((f"probe {nprobe}", idx.search_probe(q, K, nprobe, part)))
+        out.append(("probe excluded", idx.search_probe(q, K, 5, part, rowset=run.rowsets["excluded"][0])))
+        if run.rowsets["dense"][0].is_bitmap:
+            out.append(("probe dense", idx.search_probe(q, K, 5, part, rowset=run.rowsets["dense"][0])))
+        for form in (None, "unsorted", "dense"):
+            rs = run.rowsets[form][0] if form else None
+            out.append((f"examples {form}", idx.search_examples(q[5:8], q[20:22], K, rowset=rs)))
+            out.append((f"boost {form}", idx.search_boosted(q[:6], K, terms, BOOST_WEIGHTS, score_weight=0.7, rowset=rs)))
+        sparse = m.sparse_entries()
+        out.append(("boost sparse", idx.search_boosted(q[2], K, terms, BOOST_WEIGHTS, score_weight=0.7, sparse_rows=sparse[0], sparse_values=sparse[1])))
+        out.append(("boost column", (idx.boost_combine(terms, BOOST_WEIGHTS, *sparse),)))
     return out, idx.search(q, K)
 
 
@@ -488,6 +854,8 @@ def check_equals_rebuild(run, what):
     m = run.model
     other = Run(run.native, run.sc, model=m)
     other.q = run.q
+    other.centres, other.cidx = run.centres, run.cidx
+    m.last_set = set()                # the run's partition hears of every row set_rows wrote: update(rows) in sync_handles
     try:
         other.idx.add(m.x, normalize=False)
         for r in (run, other):                                           # handles of the same selections on both
@@ -501,6 +869,8 @@ def check_equals_rebuild(run, what):
             r.idx.set_option("join_shared", 2)
             sync_handles(r, what)
         assert other.idx.get_rows(0, m.n).tobytes() == run.idx.get_rows(0, m.n).tobytes()
+        if run.ip:                    # kept labels may differ from a fresh assign only on rows set and never named: none is left
+            assert not m.set_since and np.array_equal(other.partition.labels(), m.labels), (what, "labels of a rebuild")
         (mine, batch_a), (theirs, batch_b) = snapshot(run), snapshot(other)
         for (name, a), (_, b) in zip(mine, theirs):
             for x, y in zip(a, b):
@@ -537,6 +907,10 @@ def run_scenario(native, name, tamper=None):
             check(run, (name, number, event))
             print(f"  event {number} {event}: n = {run.model.n}, cells {run.model.cells[-3:]}, {time.perf_counter() - t0:.2f} s")
         check_equals_rebuild(run, (name, "rebuild"))
+        # a row searched in its old list with its new vector, between a set_rows and the update that names it
+        assert not run.ip or tamper or run.pending_checks > 0, (name, run.model.part_cells)
+        served = (run.idx.probe_counters()[0], run.idx.examples_counters()[0], run.idx.boost_counters()[0])
+        assert not run.ip or min(served) > len(sc["events"]), (name, "the three routes were served", served)
     finally:
         run.close()
 
