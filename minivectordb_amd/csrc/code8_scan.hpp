@@ -596,6 +596,17 @@ struct Code8ScanArgs {
     volatile unsigned long long* front_msum;   // host-mapped: block 0 leaves both counts here at its head, as it finds them
     volatile unsigned int* front_mcalls;       //   (the calls before this one and their survivors: the host's window takes the mean)
     const uint8_t* bit2;   // the bit plane [n, d / 8] (LIFT only): read for the survivors of stage 0 in place of `high`
+    int ring;              // entries of the survivor ring (HANDOFF only): a power of two, kCode8RingMin .. kCode8RingMax
+};
+
+// the survivor rings of the hand-off form (code8_scan_kernel, HANDOFF): 16-byte entries (row, T5, a, r) in LDS, `ring` entries
+// in all, a quarter of them per producer wave — every ring has ONE writer and one reader.
+constexpr int kCode8RingMin = 64, kCode8RingMax = 4096, kCode8RingDefault = 1024;
+struct Code8Ring {
+    i32x4 slot[kCode8RingMax];     // producer w: the slots [w * ring / 4, (w + 1) * ring / 4)
+    uint32_t tail[kScanWaves];     // entries producer w has written so far (stored by it alone, with release behind the entries)
+    uint32_t head[kScanWaves];     // entries of producer w's ring copied out so far (stored by the survivor wave, with release)
+    uint32_t done;                 // producer waves that have ended
 };
 
 // lane l's value of v from lane l ^ M.  M = 1, 2, 8 stay inside a row of 16 lanes and are DPP operand modifiers (no
@@ -690,8 +701,29 @@ struct Code8Narrow<true> {
 // flight per lane: one round trip where gather0 takes four.  (Built and measured, not kept: the loads of 64 / GF staged rows
 // issued behind each batch's stream loads and consumed behind its scoring — 1.7 us slower than the inline drains at 10M x 512,
 // DESIGN.md section 4.1b, "The bit plane".)
-template <int G, int U, bool MASKED, int GF = 0, int UF = 0, bool LIFT = false>
-__global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs a) {
+//
+// HANDOFF (the quad front form with the lift only): a FIFTH wave per block takes the survivors.  Waves 0 .. 3 are the
+// producers: the parent's streaming waves, batch for batch (gw, nwaves_total and the owner of the partial batch are computed
+// from four waves).  Every producer owns a ring in LDS (Code8Ring: a quarter of the entries each).  Where stage 0's ballot is
+// not empty the wave reserves popcount(pass) slots of its ring — granted iff they fit between its tail and the head the
+// survivor wave has released; the tail is the wave's own, so nothing is swapped —, every passing lane writes its 16-byte
+// entry to the slot of its rank among the set bits, and the new tail is stored with release: the entries below it are
+// complete.  A refused reservation (the ring is full) sends that batch's survivors down the parent's path: staged in the
+// wave's own registers, drained inline at 64 and at the wave's end.  Wave 4 streams nothing: it polls the four tails
+// (s_sleep between polls that find too little), copies up to 64 entries, ring after ring and each in its order, into the
+// lift's staging registers, releases the heads, and runs drain0 -> stage1 -> refine -> append -> flush unchanged: a survivor
+// meets the same arithmetic with the same (T5, a, r) on whichever wave takes it, and that wave counts it.
+// (Built and measured first: ONE ring, slots reserved by a compare-and-swap on a shared tail, a ready word per slot — its
+// two LDS round trips per batch with a survivor cost more than the parent's staging: DESIGN.md section 4.1b.)
+// WAITING.  The only wait in this kernel is wave 4 waiting for the four producer waves OF ITS OWN BLOCK.  A producer never
+// waits — not for its ring, not for wave 4, not for another producer — so it always ends and counts itself into `done`; wave 4
+// leaves when done == 4 and the rings are empty.  Nothing waits on another block, on a count of resident blocks or on global
+// memory: all five waves of a block are resident together by construction.  No block-wide barrier follows the head.
+// ORDER.  `tail`, `head` and `done` are workgroup-scope atomics: release by the writer behind what it covers (the entries
+// below the tail; the copies out of the slots below the head; the wave's last entries), acquire by the reader in front of
+// what depends on it.  Nothing relies on the order of LDS instructions across waves.
+template <int G, int U, bool MASKED, int GF = 0, int UF = 0, bool LIFT = false, bool HANDOFF = false>
+__global__ __launch_bounds__(kScanThreads + (HANDOFF ? kWave : 0)) void code8_scan_kernel(Code8ScanArgs a) {
     constexpr int RPI = kWave / G;
     constexpr int RB = RPI * U;
     constexpr bool FRONT = GF > 0;
@@ -699,6 +731,8 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
     // (the quad form: a lane holds kCode8QuadChunks chunks of an unmasked row of 16 G codes; one tile per batch is allowed)
     constexpr bool QUAD = FRONT && !MASKED && GF * 32 * kCode8QuadChunks == G * 16;
     static_assert(!FRONT || (UF >= (QUAD ? 1 : 2) && UF <= 8 && (UF & (UF - 1)) == 0 && UF <= GF && kWave % GF == 0), "the same, for the front form");
+    static_assert(!HANDOFF || (QUAD && LIFT), "the survivor wave serves the quad front form with the lift");
+    constexpr int NW = kScanWaves + (HANDOFF ? 1 : 0);   // waves of the block: the head's merge is shared out among all of them
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int t = lane % G;
@@ -860,7 +894,7 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
 
     const int64_t nwaves_total = (int64_t)gridDim.x * kScanWaves;
     const int64_t gw = (int64_t)blockIdx.x * kScanWaves + wave;
-    __shared__ uint64_t sh[(kScanWaves - 1) * kWave];
+    __shared__ uint64_t sh[(NW - 1) * kWave];
     __shared__ float sfloor;
 
     if constexpr (FRONT) {
@@ -1003,10 +1037,19 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         auto drain0 = [&]() __attribute__((always_inline)) {
             constexpr int UL = 4;
             nfront += (unsigned long long)ns0;
+#if defined(MVDB_CODE8_ABLATE_GATHER) && MVDB_CODE8_ABLATE_GATHER == 2
+            ns0 = 0;   // (the timing ablation: the survivors are counted and discarded)
+#endif
             for (int base = 0; base < ns0; base += UL * RPF) {
                 narrow_t w[UL];
 #pragma unroll
                 for (int u = 0; u < UL; ++u) w[u] = lift_load(base + u * RPF);
+#if defined(MVDB_CODE8_ABLATE_GATHER) && MVDB_CODE8_ABLATE_GATHER == 3
+                // (the timing ablation: the loads are waited for — an empty statement takes their registers — and dropped)
+#pragma unroll
+                for (int u = 0; u < UL; ++u) asm volatile("" ::"v"(w[u]));
+                continue;
+#endif
                 // (ONE copy of lift_use and of what stage1 inlines: the words move down instead)
 #pragma unroll 1
                 for (int at = base; at < ns0 && at < base + UL * RPF; at += RPF) {
@@ -1017,6 +1060,33 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             }
             ns0 = 0;
         };
+        // ---- HANDOFF: the ring, and a batch's survivors into it (false: refused, the caller stages them itself) ----
+        [[maybe_unused]] Code8Ring* rg = nullptr;
+        if constexpr (HANDOFF) {
+            __shared__ Code8Ring ring_store;
+            rg = &ring_store;
+        }
+        [[maybe_unused]] const uint32_t rsub = (uint32_t)a.ring / kScanWaves, rmask = rsub - 1u;   // entries of one producer's ring
+        [[maybe_unused]] uint32_t mytail = 0u;    // this producer's tail (wave-uniform)
+        [[maybe_unused]] uint32_t hd_seen = 0u;   // its ring's head as the wave last read it: read again only when that one refuses
+        [[maybe_unused]] auto ring_put = [&](uint64_t pass, int t5, float2 sr, uint32_t r) __attribute__((always_inline)) {
+            const uint32_t cnt = (uint32_t)__popcll(pass);
+            // (the head only grows: a stale value refuses too early, never too late — and was read with acquire, so the slots
+            // below it + rsub have been copied out)
+            if (mytail - hd_seen + cnt > rsub) {
+                hd_seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&rg->head[wave], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                if (mytail - hd_seen + cnt > rsub) return false;
+            }
+            if ((pass >> lane) & 1ull) {
+                const uint32_t slot = (uint32_t)wave * rsub + ((mytail + (uint32_t)__popcll(pass & ((1ull << lane) - 1ull))) & rmask);
+                rg->slot[slot] = i32x4{(int)r, t5, (int)__float_as_uint(sr.x), (int)__float_as_uint(sr.y)};
+            }
+            mytail += cnt;
+            // (the entries, by every lane that wrote one, in front of the tail that covers them)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_store(&rg->tail[wave], mytail, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return true;
+        };
         // ---- stage 0: the predicate at the upper end of what the missing 3 bits can make of T5 (stage1's form, 7 for 3) ----
         auto stage0 = [&](int t5, float2 sr, uint64_t mine, int64_t r) __attribute__((always_inline)) {
             const int tl = (t5 > INT_MIN + n7 ? t5 : INT_MIN + n7) - n7;
@@ -1026,6 +1096,9 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
             m = fmaf(fmaxf(fabsf(su), fabsf(sl)) + m, 2.4e-7f, m);
             const float ub = su + m;
             uint64_t pass = __ballot(!(ub < floor)) & mine;
+            if constexpr (HANDOFF) {
+                if (pass && ring_put(pass, t5, sr, (uint32_t)r)) pass = 0ull;
+            }
             while (pass) {
                 const int src = __ffsll((long long)pass) - 1;
                 pass &= pass - 1;
@@ -1085,14 +1158,78 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         };
         // the head, as in the other form: the first batch's loads, then the floor
         int64_t b = gw;
-        const bool head = b < nfull;
+        const bool head = (!HANDOFF || wave < kScanWaves) && b < nfull;
         i32x4 xw0[UF][NC];
         narrow_t xn0[UF];
         float2 sr0 = make_float2(0.f, 0.f);
         if (head) load0(xw0, xn0, sr0, b);
+        if constexpr (HANDOFF) {
+            // the empty rings: the barriers of the head stand between these stores and the first entry
+            if (threadIdx.x < kScanWaves) {
+                rg->tail[threadIdx.x] = 0u;
+                rg->head[threadIdx.x] = 0u;
+            }
+            if (threadIdx.x == 0) rg->done = 0u;
+        }
         floor = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane(
-            (int)__float_as_uint(code8_lists_floor(a.lists, a.nlists, a.k, sh, &sfloor, kScanWaves))));
+            (int)__float_as_uint(code8_lists_floor(a.lists, a.nlists, a.k, sh, &sfloor, NW))));
         if (blockIdx.x == 0 && threadIdx.x == 0) *a.floor = floor;
+        if constexpr (HANDOFF) {
+            if (wave == kScanWaves) {
+                // ---- the survivor wave ----
+                const uint32_t want = rsub < (uint32_t)kWave ? rsub : (uint32_t)kWave;   // (a full ring always holds as many)
+                uint32_t hd[kScanWaves] = {0u, 0u, 0u, 0u};
+                for (;;) {
+                    // `done` in front of the tails: with all producers ended, the tails are final
+                    const uint32_t dn = __hip_atomic_load(&rg->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // up to 64 entries: ring after ring, each from its head
+                    uint32_t take[kScanWaves], total = 0u;
+#pragma unroll
+                    for (int w = 0; w < kScanWaves; ++w) {
+                        const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&rg->tail[w], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                        const uint32_t av = tl - hd[w], room = (uint32_t)kWave - total;
+                        take[w] = av < room ? av : room;
+                        total += take[w];
+                    }
+                    const bool ended = dn == (uint32_t)kScanWaves;
+                    if (total >= want || (ended && total > 0u)) {
+                        uint32_t o = (uint32_t)lane, at = 0u;   // the lane's entry: the o-th taken of ring w, slot `at`
+                        bool found = false;
+#pragma unroll
+                        for (int w = 0; w < kScanWaves; ++w) {
+                            if (!found && o < take[w]) {
+                                at = (uint32_t)w * rsub + ((hd[w] + o) & rmask);
+                                found = true;
+                            }
+                            if (!found) o -= take[w];
+                            hd[w] += take[w];
+                        }
+                        if (found) {
+                            const i32x4 e = rg->slot[at];
+                            s0row = (uint32_t)e.x;
+                            st5 = e.y;
+                            sta = __uint_as_float((uint32_t)e.z);
+                            str = __uint_as_float((uint32_t)e.w);
+                        }
+                        ns0 = (int)total;
+                        // (copied out, by every lane, before the slots can be written again)
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                        const uint32_t hmine = lane == 0 ? hd[0] : lane == 1 ? hd[1] : lane == 2 ? hd[2] : hd[3];
+                        if (lane < kScanWaves) __hip_atomic_store(&rg->head[lane], hmine, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        drain0();
+                    } else if (ended) {
+                        break;   // all producers have ended and their rings are empty
+                    } else {
+                        __builtin_amdgcn_s_sleep(8);
+                    }
+                }
+                if (ns1) refine();
+                if (nfront && lane == 0) atomicAdd(a.front_survivors, nfront);
+                if (nrefined && lane == 0) atomicAdd(a.survivors, nrefined);
+                if (nst) flush();
+                return;
+            }
+        }
         if (head) {
             int T[UF];
             scores0(xw0, xn0, T);
@@ -1136,6 +1273,11 @@ __global__ __launch_bounds__(kScanThreads) void code8_scan_kernel(Code8ScanArgs 
         if (nfront && lane == 0) atomicAdd(a.front_survivors, nfront);
         if (nrefined && lane == 0) atomicAdd(a.survivors, nrefined);
         if (nst) flush();
+        if constexpr (HANDOFF) {
+            // the wave's entries are ready (release, by every lane that wrote one): it ends
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_fetch_add(&rg->done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
         return;
     }
 

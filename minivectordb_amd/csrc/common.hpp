@@ -150,6 +150,8 @@ struct Knobs {
     int code8_bit_plane = 1;           // index option code8_bit_plane: 1 an index that keeps the front plane also keeps the plane of bit 2 (+d / 8 bytes per
                                        // row) and the front form lifts its survivors from it (code8_scan.hpp: LIFT), 0 no such plane: they are gathered
     int code8_front_u = 0;             // MVDB_CODE8_FRONT_U: tuning hook, tiles per batch of the front form (4 | 8; the quad layout: 1 | 2 | 4; 0: the measured default)
+    int code8_handoff = 0;             // MVDB_CODE8_HANDOFF: A/B hook, the survivor wave of the front form's lift (code8_scan.hpp: HANDOFF): 0 the measured default (on), 1 never, 2 always
+    int code8_ring = 0;                // MVDB_CODE8_RING: tuning hook, entries of its rings in LDS, all four together (a power of two, 64 .. 4096; 0: 1024)
     int range_shared = 0;              // index option range_shared: batches of a range search on the shared fp16 pass (0 never — the default until the
                                        // route has been timed, DESIGN.md section 6e —, 1 by size, 2 wherever eligible)
     int join_shared = 1;               // index option join_shared: the range join on the shared fp16 pass (0 never, 1 by size — the default: a join has

@@ -82,6 +82,8 @@ Knobs read_knobs() {
     k.code8_seed_threads = env_int("MVDB_CODE8_SEED_THREADS", 0);
     k.code8_rescore_rows = env_int("MVDB_CODE8_RESCORE_ROWS", 0);
     k.code8_front_u = env_int("MVDB_CODE8_FRONT_U", 0);
+    k.code8_handoff = env_int("MVDB_CODE8_HANDOFF", 0);
+    k.code8_ring = env_int("MVDB_CODE8_RING", 0);
     return k;
 }
 
@@ -2282,23 +2284,34 @@ bool code8_front_wanted(int option, int d) {
 // profiles/code8_planes_sweep.jsonl: U = 8 with 2 blocks per CU at d = 512 and 1024, with 4 at d = 384)
 // (GF, UF > 0: the front form — its batches are (64 / GF) UF rows)
 // (LIFT: the front form's survivors are lifted from the bit plane — code8_scan.hpp; the label keeps its five arguments)
-template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false>
+// (HANDOFF: a fifth wave per block takes them; one block per CU as without it)
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false, bool HANDOFF = false>
 int code8_scan_blocks(int64_t n, int device) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT>;
-    int per_cu = std::min(cached_occupancy((const void*)kern, kScanThreads, 0, 4), BLOCKS);
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT, HANDOFF>;
+    constexpr int threads = kScanThreads + (HANDOFF ? kWave : 0);
+    int per_cu = std::min(cached_occupancy((const void*)kern, threads, 0, 4), BLOCKS);
     if (kn().scan_blocks_per_cu > 0) per_cu = kn().scan_blocks_per_cu;
     return scan_grid(n, GF > 0 ? (kWave / GF) * UF : (kWave / G) * U, per_cu, device);
 }
-template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false>
+template <int G, int U, bool MASKED, int BLOCKS, int GF = 0, int UF = 0, bool LIFT = false, bool HANDOFF = false>
 int launch_code8_scan(const Code8ScanArgs& a, int device, hipStream_t stream) {
-    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT>;
-    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF, LIFT>(a.n, device);
+    void (*kern)(Code8ScanArgs) = code8_scan_kernel<G, U, MASKED, GF, UF, LIFT, HANDOFF>;
+    constexpr int threads = kScanThreads + (HANDOFF ? kWave : 0);
+    const int nblocks = code8_scan_blocks<G, U, MASKED, BLOCKS, GF, UF, LIFT, HANDOFF>(a.n, device);
     if constexpr (GF > 0)
-        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, done, a); },
+        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(threads), 0, stream, done, a); },
                                "code8_scan_kernel<%d, %d, %s, %d, %d>", G, U, MASKED ? "true" : "false", GF, UF);
     else
-        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(kScanThreads), 0, stream, done, a); },
+        return profiled_launch("ip_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(threads), 0, stream, done, a); },
                                "code8_scan_kernel<%d, %d, %s>", G, U, MASKED ? "true" : "false");
+}
+// Whether the hand-off form serves where the lift serves (MVDB_CODE8_HANDOFF: 1 never, 2 always, 0 the measured default —
+// DESIGN.md section 4.1b, "The survivor wave"), and its ring (MVDB_CODE8_RING: a power of two, 0 or anything else the default)
+constexpr bool kCode8HandoffDefault = true;
+bool code8_handoff_serves() { return kn().code8_handoff == 2 || (kn().code8_handoff != 1 && kCode8HandoffDefault); }
+int code8_ring_entries() {
+    const int r = kn().code8_ring;
+    return r >= kCode8RingMin && r <= kCode8RingMax && (r & (r - 1)) == 0 ? r : kCode8RingDefault;
 }
 // Which form of the prefilter serves this call: the front form where the code holds the plane, unless its window has
 // suspended it (the survivors of stage 0 pay three gathered lines each: past kCode8FrontShare of the rows the other form is
@@ -2421,12 +2434,17 @@ int code8_search(const mvdb_index* idx, Workspace* ws, const ScanArgs& a0, int k
     c.front_msum = idx->c8_ctr.mirror<unsigned long long>() + 2;
     c.front_mcalls = idx->c8_ctr.mirror() + 6;
     c.bit2 = idx->code.B2.p;
+    c.ring = code8_ring_entries();
     const bool front = code8_front_serves(idx);
     // the lift serves where the plane is held and wanted, at the measured tiles per batch (the tuning hook keeps the gathers)
     const bool lift = front && idx->code.B2.p && idx->kn.code8_bit_plane && kn().code8_front_u == 0;
     MVDB_TRY(with_code8_shape(d, [&](auto cs) {
         using K = decltype(cs);
         if (!front) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::SCAN_BLOCKS>(c, idx->device, s);
+        if constexpr (code8_front_quad(K::G * 16) && !K::MASKED) {
+            if (lift && code8_handoff_serves())
+                return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, K::FRONT_U, true, true>(c, idx->device, s);
+        }
         if (lift) return launch_code8_scan<K::G, K::SCAN_U, K::MASKED, K::FRONT_BLOCKS, K::FRONT_G, K::FRONT_U, true>(c, idx->device, s);
         const int hook = kn().code8_front_u;   // (tuning hook)
         if constexpr (code8_front_quad(K::G * 16) && !K::MASKED) {
