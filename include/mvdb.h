@@ -588,6 +588,45 @@ int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev,
                                       int32_t* G_dev /* [nq,k] or NULL */, int64_t label_offset, void* stream);
 int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long long* fallback_queries);
 
+/* GROUP HITS SEARCH: the k best groups of stored rows, each with its group_size best rows — "the 5 best documents, and the 3
+ * best chunks of each" of a chunked store, in one call.  Inner-product indexes only.  The grouping is distinct search's.
+ * Contract, per query i.  m: the rows selected (ntotal, or mvdb_rowset_size(rs)).
+ *   Groups.  G[i] is exactly what mvdb_index_search_distinct returns for the same (q, nq, k, fetch_k, normalize_q, grp, rs):
+ *   the same k groups in the same order, -1 padded.  The call runs distinct search unchanged, both tiers.
+ *   Members.  F_i: the FULL ranking of the selected rows for query i alone, i.e. what mvdb_index_search /
+ *   mvdb_index_search_rowset returns with nq = 1 and k = m on the default routing.  For each j with G[i][j] >= 0, D[i][j][:]
+ *   and I[i][j][:] are the first group_size entries of F_i whose code is G[i][j], best first: the scores are bit for bit
+ *   the single-query scan's, equal scores go to the lower position (the row number; of a row list: the list position), rows
+ *   whose score is NaN are never offered, -0.0 sorts below +0.0.  A group with fewer members is padded with -FLT_MAX / -1;
+ *   a padding group (G[i][j] == -1) is all padding.  I holds physical rows (+ label_offset for valid entries in the device
+ *   variant).
+ *   Relation to distinct search.  With nq = 1, D[0][j][0] and I[0][j][0] equal distinct search's (D, I) bit for bit.  With
+ *   nq > 1 the heads come from the member pass like every other member, so they carry the single-query scan's bits, while
+ *   distinct search's candidate search may have ranked near-ties with the bits of the route the batch took: G is its
+ *   answer, and a head may then differ from distinct search's row where two rows of a group tie to within those bits.
+ * Arguments.  1 <= k <= 64, 1 <= group_size <= 16, fetch_k as for distinct search (k <= fetch_k <= 1024); an L2 index:
+ * MVDB_ERR_ARG.  A stale or foreign grouping or row set is refused as distinct search refuses it: before anything is enqueued,
+ * with nothing written.  An empty index or an empty set: all padding.
+ * Cost.  Distinct search, then per T queries two launches.  The first streams the selected rows' CODES — 4 bytes per row
+ * (+ 8 of a row list, + 1 bit of a bitmap) — and reads from the matrix only the rows whose code is one of the query's k
+ * groups; it writes one list of k x group_size keys per workgroup.  The second merges them, one workgroup per query.
+ * T = max(1, min(queries, budget / (grid x k x group_size x 8))), budget = index option "groups_partials_bytes" (default
+ * 64 MiB): the answer does not depend on T.  Every list is a maximum over integer keys: reproducible run to run, no
+ * floating-point atomics.
+ * The device variant follows the contract of mvdb_index_search_distinct_device: no synchronisation, no host read, one call at
+ * a time per (index, stream), capturable into a hipGraph after one eager call of the same shape (same grouping, same set).
+ * mvdb_index_groups_counters: calls served (counted on the host) and member_rows, the running total of selected rows whose
+ * code was one of their query's k groups — rows scoring NaN included —, read without synchronising: the device-side word
+ * lags by the calls in flight.  Either pointer may be NULL.
+ * No reference counterpart. */
+int mvdb_index_search_groups(const mvdb_index* idx, const float* q_host, int nq, int k, int group_size, int fetch_k, int normalize_q,
+                             const mvdb_grouping* grp, const mvdb_rowset* rs /* or NULL */, float* D_host /* [nq,k,group_size] */,
+                             int64_t* I_host /* [nq,k,group_size] */, int32_t* G_host /* [nq,k] or NULL */);
+int mvdb_index_search_groups_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int group_size, int fetch_k,
+                                    int normalize_q, const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_dev, int64_t* I_dev,
+                                    int32_t* G_dev /* [nq,k] or NULL */, int64_t label_offset, void* stream);
+int mvdb_index_groups_counters(const mvdb_index* idx, long long* calls, long long* member_rows);
+
 /* MAXSIM SEARCH: ONE question that is T query vectors (sub-questions, paraphrases, the token states of a late-interaction
  * encoder); a GROUP of stored rows — a document — scores the sum, over the vectors, of its best row for each vector.
  * Inner-product indexes only.  One call is one question; a batch is a loop of calls (a call is a corpus pass of milliseconds).
@@ -901,7 +940,7 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
  * both events on the launch stream around them, and its duration includes those two markers.
  * mvdb_prof_read drains the finished pairs of kernel `name` ("ip_scan", "ip_scan_mfma",
  * "ip_scan_gemm", "ip_scan_half", "ip_scan_half_seed", "ip_scan_rescue", "ip_scan_rerun", "ip_scan_scores",
- * "distinct_collapse", "distinct_scan", "distinct_select", "maxsim_scan", "maxsim_select", "assign_scan", "examples_scan", "examples_select", "boost_combine", "boost_scan", "encoder") and returns the number of launches and their summed duration;
+ * "distinct_collapse", "distinct_scan", "distinct_select", "groups_scan", "groups_select", "maxsim_scan", "maxsim_select", "assign_scan", "examples_scan", "examples_select", "boost_combine", "boost_scan", "encoder") and returns the number of launches and their summed duration;
  * pairs recorded while profiling was on stay readable after it is turned off.
  * Launches on a stream that is being captured are not counted: a timed event inside a graph measures nothing, so a captured
  * search holds its kernels and no event, whether profiling is on or not, and neither the capture nor a replay adds a launch.

@@ -1014,6 +1014,74 @@ class FilterAndRerankMixin:
             out.append(self._package(hits, False))
         return out
 
+    # ---- group hits search: the k best metadata groups, each with its best rows -----------------------------
+    GROUPS_MAX_SIZE = 16       # most rows of one group a call returns (include/mvdb.h "GROUP HITS SEARCH")
+
+    def find_most_similar_groups(self, embedding, group_by, k=5, group_size=3, fetch_k=None, metadata_filter=None,
+                                 exclude_filter=None, or_filters=None):
+        """The `k` best GROUPS under the filters of ``find_most_similar`` — exactly those of ``find_most_similar_distinct``,
+        in its order — each with its `group_size` best rows: "the 5 best documents, and the 3 best chunks of each" of a
+        chunked store, in one call and exact (over-fetching and bucketing on the host is wrong when one document fills the
+        fetch).  `group_by`, `k` and `fetch_k` are as in ``find_most_similar_distinct``.  No reference counterpart.  Returns
+        a list of groups, best group first; each is ``(ids, distances, metadatas)``, best row first, packaged as
+        ``find_most_similar`` does without autocut; a group with fewer rows is shorter.  ``group_size`` outside [1, 16] is a
+        ValueError."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        return self.find_most_similar_groups_batch(query, group_by, k, group_size, fetch_k, metadata_filter, exclude_filter,
+                                                   or_filters)[0]
+
+    def find_most_similar_groups_batch(self, embeddings, group_by, k=5, group_size=3, fetch_k=None, metadata_filter=None,
+                                       exclude_filter=None, or_filters=None):
+        """Several queries under ONE filter: element i is what ``find_most_similar_groups(embeddings[i], ...)`` returns."""
+        queries = self._range_queries(embeddings)
+        nq = queries.shape[0]
+        k, group_size = int(k), int(group_size)
+        fetch_k = max(4 * k, 32) if fetch_k is None else int(fetch_k)
+        if k < 1 or fetch_k < 1:
+            raise ValueError("k and fetch_k must be positive")
+        if fetch_k < k:
+            raise ValueError(f"k = {k} exceeds fetch_k = {fetch_k}")
+        if not 1 <= group_size <= self.GROUPS_MAX_SIZE:
+            raise ValueError(f"group_size must lie in [1, {self.GROUPS_MAX_SIZE}] (got {group_size})")
+        hash(group_by)  # (a metadata key: an unhashable one is the caller's TypeError, before anything is searched)
+        if nq == 0 or self._mat is None:
+            return [[] for _ in range(nq)]
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_groups"):
+                raise NotImplementedError(f"{type(index).__name__} has no group hits search")
+            take = min(k, count)
+            if take > self.DISTINCT_MAX_K:
+                raise _DistinctShape(f"k = {take} exceeds {self.DISTINCT_MAX_K}, the most groups a group hits search returns")
+            fetch = max(take, min(fetch_k, count, self.DISTINCT_MAX_FETCH))
+            grouping = self._resident_grouping(index, group_by)   # (an unhashable value: its TypeError is not retried)
+            return index.search_groups(queries, take, group_size, fetch, grouping, rowset=rowset(), normalize_q=True)
+
+        try:
+            found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        except _DistinctShape as e:
+            raise ValueError(str(e)) from None
+        if found is None:
+            return [[] for _ in range(nq)]
+        scores, rows = found[0], found[1]
+        uids = self._ids.uids
+        out = []
+        for i in range(nq):
+            groups = []
+            for grows, gscores in zip(rows[i], scores[i]):
+                hits = []
+                for row, score in zip(grows, gscores):
+                    if row == -1:
+                        continue
+                    try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                        hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                    except (KeyError, IndexError):
+                        pass
+                if hits:
+                    groups.append(self._package(hits, False))
+            out.append(groups)
+        return out
+
     # ---- MaxSim search: a question of several vectors, scored per metadata group ----------------------------
     MAXSIM_MAX_K = 64          # most groups one call returns (include/mvdb.h "MAXSIM SEARCH")
     MAXSIM_MAX_VECTORS = 256   # most query vectors of one question

@@ -137,6 +137,11 @@ PROTOTYPES = {
     "mvdb_index_search_distinct_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                          c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
     "mvdb_index_distinct_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_search_groups": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_groups_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "mvdb_index_groups_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_index_search_maxsim": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                 c_vp]),
     "mvdb_index_search_maxsim_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
@@ -828,6 +833,38 @@ class FlatIndex:
         """(distinct searches served, queries their one-pass tier answered): running totals, read without synchronising."""
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_distinct_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    # ---- group hits search: the k best groups, each with its group_size best rows (include/mvdb.h "GROUP HITS SEARCH") ----
+    def search_groups(self, q, k, group_size, fetch_k, grouping, rowset=None, normalize_q=False):
+        """(D float32[nq, k, group_size], I int64[nq, k, group_size], G int32[nq, k]): per query the k best groups (of the row
+        set, if one is given) — G, exactly search_distinct's — and of each its group_size best rows, best first.  Labels are
+        ROW NUMBERS; a group with fewer rows ends in -FLT_MAX / -1, a missing group (G == -1) is all of that."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        nq, k, group_size = q.shape[0], int(k), int(group_size)
+        D = np.empty((nq, max(k, 0), max(group_size, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0), max(group_size, 0)), dtype=np.int64)
+        G = np.empty((nq, max(k, 0)), dtype=np.int32)
+        check(lib().mvdb_index_search_groups(self._h, _ptr(q), nq, k, group_size, int(fetch_k), int(bool(normalize_q)), grouping._h,
+                                             rowset._h if rowset is not None else None, _ptr(D), _ptr(I), _ptr(G)))
+        return D, I, G
+
+    def search_groups_device(self, q_ptr, nq, k, group_size, fetch_k, grouping, D_ptr, I_ptr, G_ptr=0, rowset=None, stream=0,
+                             normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_groups (labels: row numbers + label_offset; G_ptr 0: no group codes); enqueues on
+        `stream` and returns."""
+        check(lib().mvdb_index_search_groups_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(group_size), int(fetch_k), int(bool(normalize_q)), grouping._h,
+            rowset._h if rowset is not None else None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr),
+            ctypes.c_void_p(G_ptr) if G_ptr else None, int(label_offset), ctypes.c_void_p(stream)))
+
+    def groups_counters(self):
+        """(group hits searches served, selected rows whose group was one of their query's k): running totals, read without
+        synchronising."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_groups_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
     # ---- MaxSim search: one question of T vectors, a group scores the sum of its per-vector maxima (include/mvdb.h "MAXSIM SEARCH") ----

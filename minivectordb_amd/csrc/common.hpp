@@ -158,6 +158,7 @@ struct Knobs {
                                        // as many queries as rows, DESIGN.md section 6j —, 2 wherever eligible)
     long long range_candidates = 0;    // index option range_candidates: candidates per query that pass holds (0: max(2 cap rounded up to a power of two, 4096))
     long long distinct_table_bytes = 256ll << 20;  // index option distinct_table_bytes: budget of the distinct search's tier-2 table (mvdb.hip: distinct_core)
+    long long groups_partials_bytes = 64ll << 20;  // index option groups_partials_bytes: budget of the group hits search's block lists (mvdb.hip: groups_core)
     long long maxsim_table_bytes = 2ll << 30;  // index option maxsim_table_bytes: most bytes of a MaxSim search's table, T x n_groups x 8 (mvdb.hip: check_maxsim_state)
     int maxsim_tokens_per_pass = 0;    // index option maxsim_tokens_per_pass: query vectors per corpus pass of a MaxSim search (0: maxsim_scan.hpp maxsim_tokens_per_pass)
     int assign_vectors_per_pass = 0;   // index option assign_vectors_per_pass: vectors per corpus pass of an assignment (0: assign_scan.hpp assign_vectors_per_pass)

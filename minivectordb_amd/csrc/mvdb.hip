@@ -23,6 +23,7 @@
 #include "join_scan.hpp"
 #include "mmr_select.hpp"
 #include "distinct_select.hpp"
+#include "group_hits.hpp"
 #include "maxsim_scan.hpp"
 #include "assign_scan.hpp"
 #include "examples_scan.hpp"
@@ -420,6 +421,10 @@ struct Workspace {
     DevBuf<int> dneed;                   // distinct search: kCoreTile need words of one tile of queries, then the collapse launch's ticket
     DevBuf<uint64_t> dtab;               // ... the table of tier 2, [T slots, n_groups] (distinct_select.hpp)
     DevBuf<int32_t> dG;                  // ... the host entry point's group codes, [nq, k]
+    DevBuf<float> ghD;                   // group hits search: distinct search's scores of the call, [nq, k] (group_hits.hpp) ...
+    DevBuf<int64_t> ghI;                 // ... its rows ...
+    DevBuf<int32_t> ghG;                 // ... its group codes, where the caller takes none ...
+    DevBuf<uint64_t> ghpart;             // ... and the block lists of the member pass, [T slots, grid.x, k * group_size + 1]
     DevBuf<uint64_t> mxtab;              // MaxSim search: the table of one call, [n_groups, T] (maxsim_scan.hpp) ...
     DevBuf<uint64_t> mxpart;             // ... the block lists of its top-k launch, [lists, 64] ...
     DevBuf<char> mxout;                  // ... the host entry point's results, packed: I_tok | D_tok | D | G
@@ -613,6 +618,10 @@ struct mvdb_index {
     // mirror, written by distinct_collapse_kernel); the calls are counted on the host
     mutable MirroredCounter ds_ctr;
     mutable std::atomic<unsigned long long> ds_calls{0};
+    // group hits search, created by the first call: a running count of the member rows met (one 64-bit device word and its
+    // mirror, written by group_members_select_kernel); the calls are counted on the host
+    mutable MirroredCounter gh_ctr;
+    mutable std::atomic<unsigned long long> gh_calls{0};
     // MaxSim search: calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
     // assignment (and the assignments of k-means): calls served and corpus passes enqueued, both counted on the host
@@ -2597,6 +2606,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const int join_shared = idx->kn.join_shared;
     const long long distinct_table = idx->kn.distinct_table_bytes;
     const long long maxsim_table = idx->kn.maxsim_table_bytes;
+    const long long groups_partials = idx->kn.groups_partials_bytes;
     const int maxsim_tokens = idx->kn.maxsim_tokens_per_pass;
     const int assign_vectors = idx->kn.assign_vectors_per_pass;
     const int examples_vectors = idx->kn.examples_vectors_per_pass;
@@ -2604,6 +2614,7 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     idx->kn = read_knobs();
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
+    idx->kn.groups_partials_bytes = groups_partials;
     idx->kn.maxsim_tokens_per_pass = maxsim_tokens;
     idx->kn.assign_vectors_per_pass = assign_vectors;
     idx->kn.examples_vectors_per_pass = examples_vectors;
@@ -2664,6 +2675,9 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "distinct_table_bytes") {  // budget of the distinct search's tier-2 table (T slots of 8 n_groups bytes; T >= 1 whatever it is)
         if (value <= 0) return fail(MVDB_ERR_ARG, "distinct_table_bytes must be positive");
         idx->kn.distinct_table_bytes = value;
+    } else if (n == "groups_partials_bytes") {  // budget of the group hits search's block lists (T slots of grid.x k group_size 8 bytes; T >= 1 whatever it is)
+        if (value <= 0) return fail(MVDB_ERR_ARG, "groups_partials_bytes must be positive");
+        idx->kn.groups_partials_bytes = value;
     } else if (n == "maxsim_table_bytes") {  // most bytes of the MaxSim search's table (T x n_groups x 8 of one call): a call above it is refused
         if (value <= 0) return fail(MVDB_ERR_ARG, "maxsim_table_bytes must be positive");
         idx->kn.maxsim_table_bytes = value;
@@ -2685,7 +2699,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2758,6 +2772,12 @@ int mvdb_index_distinct_counters(const mvdb_index* idx, long long* calls, long l
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->ds_calls.load();
     if (fallback_queries) *fallback_queries = (long long)idx->ds_ctr.read(0);
+    return 0;
+}
+int mvdb_index_groups_counters(const mvdb_index* idx, long long* calls, long long* member_rows) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->gh_calls.load();
+    if (member_rows) *member_rows = (long long)idx->gh_ctr.read<unsigned long long>(0);
     return 0;
 }
 int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long long* passes) {
@@ -4562,6 +4582,169 @@ int mvdb_index_search_distinct_device(const mvdb_index* idx, const float* q_dev,
     MVDB_TRY(call.rc);
     // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
     return distinct_core(idx, call.ws, call.q, nq, k, fetch_k, normalize_q, grp, rs, label_offset, D_dev, I_dev, G_dev);
+}
+
+}  // extern "C"
+
+// ---- group hits search: the k best groups, each with its group_size best rows (group_hits.hpp) ----------------------------
+namespace {
+
+int check_groups_args(const mvdb_index* idx, const void* q, int nq, int k, int group_size, int fetch_k, const void* D, const void* I) {
+    MVDB_TRY(check_distinct_args(idx, q, nq, k, fetch_k, D, I));
+    if (group_size < 1 || group_size > kGroupsMaxSize)
+        return fail(MVDB_ERR_ARG, "group hits search needs 1 <= group_size <= %d (got %d)", kGroupsMaxSize, group_size);
+    return 0;
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int groups_scan_blocks(int64_t n, int device) {
+    void (*kern)(GroupMembersArgs) = group_members_scan_kernel<G, C, U, SEL, MASKED>;
+    return scan_grid(n, (kWave / G) * U, scan_resident_blocks((const void*)kern, C), device);  // the grid of the single-query scan
+}
+
+template <int G, int C, int U, int SEL, bool MASKED>
+int launch_group_members_kern(const GroupMembersArgs& a, int slots, int nblocks, hipStream_t stream) {
+    void (*kern)(GroupMembersArgs) = group_members_scan_kernel<G, C, U, SEL, MASKED>;
+    return profiled_launch("groups_scan", stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, slots), dim3(kScanThreads), 0, stream, done, a); },
+                           "group_members_scan_kernel<%d, %d, %d, %d, %s>", G, C, U, SEL, MASKED ? "true" : "false");
+}
+
+// the shapes and rows in flight of launch_scan: a score depends on (G, C, MASKED) only.  slots == 0: the grid only.
+int launch_group_members(const GroupMembersArgs& a, int slots, int device, hipStream_t s, int* nblocks) {
+    return with_scan_shape(a.d4, [&](auto shape) {
+        using S = decltype(shape);
+        return with_scan_form<S::G, S::C>(a.d4, a.rows != nullptr, a.mask != nullptr, [&](auto form) {
+            using F = decltype(form);
+            constexpr int U = F::SEL == 1 ? gather_u(S::G, S::C) : stream_u(S::G, S::C);
+            if (slots == 0) {
+                *nblocks = groups_scan_blocks<S::G, S::C, U, F::SEL, F::MASKED>(a.n, device);
+                return 0;
+            }
+            return launch_group_members_kern<S::G, S::C, U, F::SEL, F::MASKED>(a, slots, *nblocks, s);
+        });
+    });
+}
+
+// the counter of member rows: allocated with the first call, never inside a capture
+bool ensure_groups_stats(const mvdb_index* idx, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(idx->shadow_mu);
+    return idx->gh_ctr.dev() || (!stream_capturing(s) && idx->gh_ctr.ensure(2));
+}
+
+// Queries on the device at stride ld, results to device buffers.  distinct_core — unchanged, both tiers — picks the groups
+// of every query into G_dev (its rows and scores go to the workspace); then, per tile of kCoreTile queries and per sub-tile
+// of T slots, the member pass and its select.  The workspace is sized by the call's shape alone.
+int groups_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int group_size, int fetch_k, int normalize_q,
+                const mvdb_grouping* grp, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev, int32_t* G_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->gh_calls;
+    const size_t heads = (size_t)nq * k;
+    MVDB_TRY(ws->ghD.reserve(heads));
+    MVDB_TRY(ws->ghI.reserve(heads));
+    if (!G_dev) {
+        MVDB_TRY(ws->ghG.reserve(heads));
+        G_dev = ws->ghG.p;
+    }
+    MVDB_TRY(distinct_core(idx, ws, q, nq, k, fetch_k, normalize_q, grp, rs, 0, ws->ghD.p, ws->ghI.p, G_dev));
+    const int64_t m = rs ? rs->count : idx->n;  // rows selected
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {
+        const int64_t total = (int64_t)heads * group_size;
+        hipLaunchKernelGGL(distinct_fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, (int32_t*)nullptr, total);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    }
+    const bool counted = ensure_groups_stats(idx, s);
+
+    GroupMembersArgs g;
+    g.X = idx->X.p;
+    g.n = rs ? (rs->mask ? rs->n_at_create : rs->count) : idx->n;
+    g.ld = idx->ld;
+    g.d4 = idx->d4;
+    g.normalize_q = normalize_q;
+    g.rows = rs ? rs->rows : nullptr;
+    g.mask = rs ? rs->mask : nullptr;
+    g.codes = grp->codes;
+    g.k = k;
+    g.group_size = group_size;
+    int gx = 0;
+    MVDB_TRY(launch_group_members(g, 0, idx->device, s, &gx));
+    const int64_t tile = std::min(nq, kCoreTile);
+    const int64_t list_words = (int64_t)k * group_size;
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(tile, idx->kn.groups_partials_bytes / ((int64_t)gx * list_words * 8)));
+    // (by the call's shape, not the index: the largest grid of a scan, the budget in block lists — at least one slot's, at
+    //  most the tile's)
+    const int64_t gx_ub = std::max<int64_t>(scan_grid_upper_bound(idx->device), gx);
+    const int64_t lists_ub = idx->kn.groups_partials_bytes / (list_words * 8);
+    MVDB_TRY(ws->ghpart.reserve((size_t)std::min<int64_t>(tile * gx_ub, std::max<int64_t>(gx_ub, lists_ub)) * (size_t)(list_words + 1)));
+    g.partials = ws->ghpart.p;
+
+    GroupMembersSelectArgs t;
+    t.partials = ws->ghpart.p;
+    t.nblocks = gx;
+    t.k = k;
+    t.group_size = group_size;
+    t.rows = g.rows;
+    t.label_offset = label_offset;
+    t.ticket = reinterpret_cast<unsigned int*>(ws->dneed.p + kCoreTile);  // (distinct_core's: zero between launches)
+    t.ctr = counted ? reinterpret_cast<unsigned long long*>(idx->gh_ctr.dev()) : nullptr;
+    t.host = counted ? idx->gh_ctr.mirror<unsigned long long>() : nullptr;
+
+    for (int t0 = 0; t0 < nq; t0 += kCoreTile) {
+        const int take = std::min(kCoreTile, nq - t0);
+        for (int s0 = t0; s0 < t0 + take; s0 += T) {
+            const int slots = std::min(T, t0 + take - s0);
+            g.q = q + (int64_t)s0 * idx->ld;
+            g.G = G_dev + (int64_t)s0 * k;
+            MVDB_TRY(launch_group_members(g, slots, idx->device, s, &gx));
+            t.D = D_dev + (int64_t)s0 * list_words;
+            t.I = I_dev + (int64_t)s0 * list_words;
+            MVDB_TRY(profiled_launch("groups_select", s,
+                                     [&](hipEvent_t done) { launch_kernel(group_members_select_kernel, dim3((unsigned)slots), dim3(kGroupsSelectThreads), 0, s, done, t); },
+                                     "group_members_select_kernel"));
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_index_search_groups(const mvdb_index* idx, const float* q_host, int nq, int k, int group_size, int fetch_k, int normalize_q,
+                             const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_host, int64_t* I_host, int32_t* G_host) {
+    MVDB_TRY(check_groups_args(idx, q_host, nq, k, group_size, fetch_k, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(grouping_check(idx, grp));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(call.stage(q_host, nq));
+    const size_t heads = (size_t)nq * k, total = heads * group_size;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(call.ws->dG.reserve(heads));
+    MVDB_TRY(groups_core(idx, call.ws, call.ws->q.p, nq, k, group_size, fetch_k, normalize_q, grp, rs, 0, D_dev, I_dev, call.ws->dG.p));
+    if (G_host) {
+        MVDB_TRY(copy_back(call.ws, call.ws->dG.p, heads * sizeof(int32_t), "group hits search"));
+        memcpy(G_host, call.ws->pin_out.p, heads * sizeof(int32_t));
+    }
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_groups_device(const mvdb_index* idx, const float* q_dev, int nq, int k, int group_size, int fetch_k, int normalize_q,
+                                    const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_dev, int64_t* I_dev, int32_t* G_dev,
+                                    int64_t label_offset, void* stream) {
+    MVDB_TRY(check_groups_args(idx, q_dev, nq, k, group_size, fetch_k, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(grouping_check(idx, grp));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    // nothing below reads from the device or synchronises: capturable once an eager call of the same shape has sized the workspace
+    return groups_core(idx, call.ws, call.q, nq, k, group_size, fetch_k, normalize_q, grp, rs, label_offset, D_dev, I_dev, G_dev);
 }
 
 }  // extern "C"

@@ -577,6 +577,16 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
 
+    # ---- group hits search: not here -------------------------------------------------------------------------------
+    _NO_GROUPS = ("DistributedShardedVectorDatabase has no group hits search: the rows of one group live on several ranks, "
+                 "and a group's best rows are picked on one device (use ShardedVectorDatabase on one device)")
+
+    def find_most_similar_groups(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_GROUPS)
+
+    def find_most_similar_groups_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_GROUPS)
+
     # ---- MaxSim search: not across ranks ----------------------------------------------------------------------------
     _NO_MAXSIM = ("DistributedShardedVectorDatabase has no MaxSim search: the rows of one group live on several ranks, and the "
                   "per-group maxima of every query vector are taken on one device (use ShardedVectorDatabase on one device)")

@@ -176,6 +176,16 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_distinct_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_DISTINCT)
 
+    # ---- group hits search: not here -------------------------------------------------------------------------------
+    _NO_GROUPS = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: group hits search, whose member pass scores "
+                 "the rows of the winning groups in exact fp32, is not implemented (use ShardedVectorDatabase)")
+
+    def find_most_similar_groups(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_GROUPS)
+
+    def find_most_similar_groups_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_GROUPS)
+
     # ---- MaxSim search: not on the int8 cosine index ----------------------------------------------------------------
     _NO_MAXSIM = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: MaxSim search, an exact fp32 pass "
                   "with a per-group maximum for every query vector, is not implemented (use ShardedVectorDatabase)")
