@@ -887,6 +887,76 @@ int mvdb_index_boost_combine(const mvdb_index* idx, const mvdb_rowterm* const* t
                              const int64_t* sparse_rows_host, const float* sparse_values_host, int64_t nsparse, float* T_host /*[ntotal]*/);
 int mvdb_index_boost_counters(const mvdb_index* idx, long long* calls, long long* scan_launches);
 
+/* SPARSE VECTORS AND HYBRID SEARCH: beside its embedding a stored row may hold a SPARSE vector — BM25 or SPLADE weights, the
+ * lexical weights a model emits as {token id: weight} — and a sparse query is scored against every one of them: exact sparse
+ * top-k, and hybrid search as dense_weight * s(r) + sparse_weight * sparse(r) ranked exactly over every selected row in one
+ * pass (not a re-ranking of the dense top-k: a row that wins on the combined score from further down is found).
+ * mvdb_sparse: one sparse vector per stored row in CSR form, resident on the index's device.  mvdb_sparse_create needs
+ *   n == ntotal, indptr[0] == 0, indptr non-decreasing (indptr[n] = nnz), every index inside [0, dim), the indices of a row
+ *   strictly ascending and 1 <= dim <= 2^31 - 1 — all checked on the host, MVDB_ERR_ARG otherwise.  Values may be anything,
+ *   non-finite included; empty rows are ordinary.  The store follows mvdb_rowterm's rules: a search refuses it with an
+ *   MVDB_ERR_ARG that names both counts when rows were added since, and when it was created before a remove_rows / reset;
+ *   mvdb_index_set_rows does not outdate it.  At creation the host also cuts the rows into TILES — consecutive rows with at
+ *   most span_entries non-zeros and tile_rows rows, a row longer than the span alone — and uploads the tile table (first
+ *   row, first entry): the launches balance by non-zeros and need no device-side scan.  Device memory: 8 bytes per
+ *   non-zero + 8 per row.  mvdb_sparse_rows / _nnz / _dim: -1 for NULL; mvdb_sparse_free(NULL) is a no-op.
+ *   mvdb_sparse_geometry: span_entries, tile_rows and table_slots of this build (any pointer may be NULL).
+ * Query: m distinct indices in any order, 1 <= m <= 1024, each inside [0, dim); a duplicate, m = 0, m > 1024 and an index
+ *   out of range are MVDB_ERR_ARG, checked on the host.  A batch is given in CSR form too (q_indptr[0] == 0).
+ * Arithmetic — all fp32, every operation rounded on its own (numpy float32 reproduces every bit):
+ *   sparse(r): acc = +0.0; for the row's entries IN STORED ORDER whose index is in the query: acc = acc + (q[index] * value).
+ *   matched(r) counts the entries used.  (acc is never -0.0, so a skipped entry may add +0.0: the same bits.)
+ * mvdb_index_sparse_scores runs the scoring launch alone over every row and copies sparse(r) back, and matched(r) where
+ *   matched_host is not NULL: the kernel can be held to the arithmetic above by itself.
+ * mvdb_index_search_sparse: a row is a candidate iff it is selected by rs, matched >= 1 and its score is not NaN (a matched
+ *   row whose products cancel to 0 is one; -inf and +inf are ordinary scores).  Best first, equal scores to the LOWER
+ *   physical row in every row-set form; fewer than k candidates end in -FLT_MAX / -1.  1 <= k <= 64, nq >= 1.  It works on
+ *   an index of either metric and never reads the dense matrix.
+ * mvdb_index_search_hybrid: S(r) = (dense_weight * s(r)) + (sparse_weight * sparse(r)) — one rounded multiply for the sparse
+ *   term, then exactly the boosted search's S = (w_s * s) + T[r].  Every selected row is a candidate (an unmatched row's
+ *   sparse term is sparse_weight * +0.0); candidacy, order, ties, padding and limits are the boosted search's, inner-product
+ *   indexes only.  The call returns, bit for bit, what mvdb_index_search_boosted returns for the same dense query with one
+ *   term — the column of mvdb_index_sparse_scores — at weight sparse_weight and score_weight = dense_weight.
+ * Launches.  sparse_scan_kernel: the query sits in LDS as an open-addressed table of table_slots slots; a block streams a
+ *   tile's entries with 16-byte loads into an LDS staging buffer of products, then one lane per row adds the row's products
+ *   in order.  mvdb_index_sparse_scores: one launch.  mvdb_index_search_sparse: one launch per 1,024 queries — the queries
+ *   are the grid's y dimension — and the merge of its block lists; a row LIST is first turned into a bitmap (n / 8 bytes of
+ *   workspace).  mvdb_index_search_hybrid: per query the scoring launch writes T into the boosted search's workspace column
+ *   (4 bytes per stored row), then boost_scan_kernel and its merge run; the queries of a call follow each other on one
+ *   stream over one column.  Nothing is selected (an empty index, an empty set): no launches, every output is padding.
+ * The device variants take the sparse queries as HOST arrays (as mvdb_index_search_boosted_device takes its sparse entries)
+ *   and wait once, for their upload, before they enqueue the rest; I holds row numbers + label_offset.  One call at a time
+ *   per (index, stream).  Capture into a hipGraph is not supported: a capturing stream is MVDB_ERR_ARG.
+ * mvdb_index_sparse_counters: sparse and hybrid searches served (mvdb_index_sparse_scores is not one) and sparse_scan_kernel
+ *   launches enqueued — one per mvdb_index_sparse_scores, one per sparse search and 1,024 queries, one per query of a hybrid
+ *   search, none where nothing is selected —, both counted on the host; a refused call counts nothing.  Either pointer may
+ *   be NULL.  (The boost_scan_kernel launches of a hybrid search are counted by mvdb_index_boost_counters' scan_launches.)
+ * No reference counterpart. */
+typedef struct mvdb_sparse mvdb_sparse;
+int mvdb_sparse_create(const mvdb_index* idx, const int64_t* indptr_host /*[n+1]*/, const int32_t* indices_host /*[nnz]*/,
+                       const float* values_host /*[nnz]*/, int64_t n, int64_t dim, mvdb_sparse** out);
+int64_t mvdb_sparse_rows(const mvdb_sparse* sp);
+int64_t mvdb_sparse_nnz(const mvdb_sparse* sp);
+int64_t mvdb_sparse_dim(const mvdb_sparse* sp);
+int mvdb_sparse_free(mvdb_sparse* sp);
+int mvdb_sparse_geometry(int* span_entries, int* tile_rows, int* table_slots);
+int mvdb_index_sparse_scores(const mvdb_index* idx, const mvdb_sparse* sp, const int32_t* q_indices_host /*[m]*/, const float* q_values_host /*[m]*/,
+                             int m, float* T_host /*[ntotal]*/, int32_t* matched_host /*[ntotal] or NULL*/);
+int mvdb_index_search_sparse(const mvdb_index* idx, const mvdb_sparse* sp, const int64_t* q_indptr_host /*[nq+1]*/, const int32_t* q_indices_host,
+                             const float* q_values_host, int nq, int k, const mvdb_rowset* rs /*NULL: every row*/, float* D_host /*[nq,k]*/,
+                             int64_t* I_host /*[nq,k]*/);
+int mvdb_index_search_sparse_device(const mvdb_index* idx, const mvdb_sparse* sp, const int64_t* q_indptr_host, const int32_t* q_indices_host,
+                                    const float* q_values_host, int nq, int k, const mvdb_rowset* rs, int64_t label_offset, float* D_dev /*[nq,k]*/,
+                                    int64_t* I_dev /*[nq,k]*/, void* stream);
+int mvdb_index_search_hybrid(const mvdb_index* idx, const mvdb_sparse* sp, const float* q_host /*[nq,d]*/, int normalize_q, const int64_t* q_indptr_host,
+                             const int32_t* q_indices_host, const float* q_values_host, int nq, int k, float dense_weight, float sparse_weight,
+                             const mvdb_rowset* rs /*NULL: every row*/, float* D_host /*[nq,k]*/, int64_t* I_host /*[nq,k]*/);
+int mvdb_index_search_hybrid_device(const mvdb_index* idx, const mvdb_sparse* sp, const float* q_dev /*[nq,d]*/, int normalize_q,
+                                    const int64_t* q_indptr_host, const int32_t* q_indices_host, const float* q_values_host, int nq, int k,
+                                    float dense_weight, float sparse_weight, const mvdb_rowset* rs, int64_t label_offset, float* D_dev /*[nq,k]*/,
+                                    int64_t* I_dev /*[nq,k]*/, void* stream);
+int mvdb_index_sparse_counters(const mvdb_index* idx, long long* calls, long long* score_launches);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be

@@ -18,6 +18,8 @@ reference's ``list(set_of_rows)`` (vector_database.py:510) follows CPython's has
 """
 import bisect
 import numbers
+import os
+import pickle
 from array import array
 from collections import OrderedDict, defaultdict
 from operator import ge, gt, le, lt, ne
@@ -535,7 +537,10 @@ class FilterAndRerankMixin:
         pending rows.  Returns the removed rows, ascending."""
         unique_ids = list(dict.fromkeys(unique_ids))
         values = self._live_value_index()
+        sparse = self.__dict__.get("_sparse")
         for uid in unique_ids:
+            if sparse:
+                sparse.pop(uid, None)   # a later store of the same id starts without a sparse vector
             meta = self.metadata[self._ids.row(uid)]
             if values is not None and meta:
                 values.note_delete(self._ids.handle[uid], meta)
@@ -1384,6 +1389,293 @@ class FilterAndRerankMixin:
         if not boosts:
             raise ValueError("a boosted search needs something to boost by: boosts")
         return self._boosted(queries, boosts, None, k, score_weight, missing, metadata_filter, exclude_filter, or_filters, autocut)
+
+    # ---- sparse vectors: exact sparse search, and hybrid search ranked in one exact pass -------------------------------
+    SPARSE_MAX_K = 64             # most rows a sparse or hybrid search returns (include/mvdb.h "SPARSE VECTORS AND HYBRID SEARCH")
+    SPARSE_MAX_DIM = 2**31 - 1    # indices live in [0, SPARSE_MAX_DIM)
+
+    @staticmethod
+    def _sparse_pair(sparse):
+        """``{index: weight}`` or ``(indices, values)`` as (int64 indices ascending, float32 values); None for None or an
+        empty one.  A ValueError for an index that is no integer, negative or too large, for a duplicate index and for
+        arrays of different lengths."""
+        if sparse is None:
+            return None
+        if isinstance(sparse, dict):
+            indices, values = list(sparse.keys()), list(sparse.values())
+        else:
+            try:
+                indices, values = sparse
+            except (TypeError, ValueError):
+                raise ValueError("a sparse vector is {index: weight} or (indices, values)") from None
+        raw = np.asarray(indices).reshape(-1)
+        values = np.asarray(values, dtype=np.float32).reshape(-1)
+        if len(raw) != len(values):
+            raise ValueError(f"a sparse vector needs one value per index ({len(raw)} indices, {len(values)} values)")
+        if len(raw) == 0:
+            return None
+        if raw.dtype.kind not in "iu":
+            as_int = raw.astype(np.int64) if raw.dtype.kind == "f" else None
+            if as_int is None or not np.array_equal(as_int, raw):
+                raise ValueError("the indices of a sparse vector must be integers")
+            raw = as_int
+        if raw.dtype.kind == "u":
+            if raw.max() >= FilterAndRerankMixin.SPARSE_MAX_DIM:
+                raise ValueError(f"sparse index {int(raw.max())} is outside [0, 2^31 - 1)")
+        idx = raw.astype(np.int64)
+        if idx.min() < 0 or idx.max() >= FilterAndRerankMixin.SPARSE_MAX_DIM:
+            bad = idx.min() if idx.min() < 0 else idx.max()
+            raise ValueError(f"sparse index {int(bad)} is outside [0, 2^31 - 1)")
+        order = np.argsort(idx, kind="stable")
+        idx, values = idx[order], values[order]
+        dup = np.flatnonzero(idx[1:] == idx[:-1])
+        if len(dup):
+            raise ValueError(f"sparse index {int(idx[dup[0]])} is listed twice")
+        return idx, np.ascontiguousarray(values)
+
+    @staticmethod
+    def _sparse_dim_for(largest):
+        """The smallest power of two above the index `largest` (at most 2^31 - 1)."""
+        dim = 1
+        while dim <= largest:
+            dim *= 2
+        return min(dim, FilterAndRerankMixin.SPARSE_MAX_DIM)
+
+    @staticmethod
+    def _sparse_csr(uids, vectors):
+        """The CSR arrays of the rows `uids` (row order): (indptr int64[n + 1], indices int32, values float32); an id without a
+        sparse vector is an empty row."""
+        indptr = np.zeros(len(uids) + 1, dtype=np.int64)
+        idx, val = [], []
+        for row, uid in enumerate(uids):
+            pair = vectors.get(uid)
+            if pair is not None:
+                idx.append(pair[0])
+                val.append(pair[1])
+                indptr[row + 1] = len(pair[0])
+        np.cumsum(indptr, out=indptr)
+        indices = np.concatenate(idx).astype(np.int32) if idx else np.empty(0, np.int32)
+        values = np.concatenate(val).astype(np.float32) if val else np.empty(0, np.float32)
+        return indptr, indices, values
+
+    def _sparse_vectors(self):
+        vectors = self.__dict__.get("_sparse")
+        if vectors is None:
+            vectors = self.__dict__["_sparse"] = {}
+        return vectors
+
+    @property
+    def sparse_dim(self):
+        """The dimension of the sparse vectors: what ``set_sparse_dim`` fixed, else the smallest power of two above the
+        largest index stored so far (None before the first one)."""
+        return self.__dict__.get("_sparse_dim")
+
+    def set_sparse_dim(self, dim):
+        """Fix the dimension of the sparse vectors: indices live in [0, dim), and a later vector with a larger index is a
+        ValueError instead of growing the dimension.  `dim` must cover what is stored."""
+        dim = int(dim)
+        if not 1 <= dim <= self.SPARSE_MAX_DIM:
+            raise ValueError("sparse_dim must be in [1, 2^31 - 1]")
+        with self.lock:
+            largest = max((int(pair[0][-1]) for pair in self._sparse_vectors().values()), default=-1)
+            if largest >= dim:
+                raise ValueError(f"sparse_dim = {dim} does not cover the stored index {largest}")
+            self.__dict__["_sparse_dim"] = dim
+            self.__dict__["_sparse_dim_fixed"] = True
+            self.__dict__["_sparse_gen"] = self.__dict__.get("_sparse_gen", 0) + 1
+
+    def set_sparse_vector(self, unique_id, sparse):
+        """Give the stored id `unique_id` the sparse vector `sparse` — ``{index: weight}`` or ``(indices, values)``, indices
+        distinct integers in [0, sparse_dim) — beside its embedding; it replaces an earlier one, None or an empty one removes
+        it.  An unknown id is a ValueError.  The vectors live on the host keyed by id (a deleted id loses its vector); the
+        next sparse or hybrid search uploads them once.  No reference counterpart."""
+        self.set_sparse_vectors_batch([unique_id], [sparse])
+
+    def set_sparse_vectors_batch(self, unique_ids, sparses):
+        """``set_sparse_vector`` for several ids; nothing is stored when one of them is refused."""
+        unique_ids = list(unique_ids)
+        sparses = list(sparses)
+        if len(unique_ids) != len(sparses):
+            raise ValueError("Sparse vectors must be provided for all unique IDs.")
+        pairs = [self._sparse_pair(s) for s in sparses]
+        with self.lock:
+            for uid in unique_ids:
+                if uid not in self._ids:
+                    raise ValueError("Unique ID does not exist.")
+            largest = max((int(p[0][-1]) for p in pairs if p is not None), default=-1)
+            dim = self.__dict__.get("_sparse_dim")
+            if largest >= 0 and (dim is None or largest >= dim):
+                if self.__dict__.get("_sparse_dim_fixed"):
+                    raise ValueError(f"sparse index {largest} is outside [0, {dim}), the dimension set_sparse_dim fixed")
+                self.__dict__["_sparse_dim"] = self._sparse_dim_for(largest)
+            vectors = self._sparse_vectors()
+            for uid, pair in zip(unique_ids, pairs):
+                if pair is None:
+                    vectors.pop(uid, None)
+                else:
+                    vectors[uid] = pair
+            self.__dict__["_sparse_gen"] = self.__dict__.get("_sparse_gen", 0) + 1
+
+    def get_sparse_vector(self, unique_id):
+        """``(indices, values)`` of the id's sparse vector, sorted by index (int64, float32), or None when it has none."""
+        with self.lock:
+            if unique_id not in self._ids:
+                raise ValueError("Unique ID does not exist.")
+            pair = self._sparse_vectors().get(unique_id)
+            return None if pair is None else (pair[0].copy(), pair[1].copy())
+
+    def _resident_sparse_store(self, index):
+        """The device-resident sparse store (`mvdb_sparse`), stamped with the write generation, the sparse generation and the
+        index object as `_resident_boost_column` stamps its columns: a store, a delete, a metadata update or a change of a
+        sparse vector since makes the next search assemble the CSR arrays in row order once and upload them once; an
+        embedding-only update keeps the store.  A ValueError where the device index is no longer the state the ids describe:
+        `_search_selected` starts over."""
+        with self.lock:
+            if self._embeddings_changed or self.index is not index:
+                raise ValueError("the index changed between the filter and the search")
+            stamp = (self.__dict__.get("_write_gen", 0), self.__dict__.get("_sparse_gen", 0))
+            hit = self.__dict__.get("_sparse_store")
+            if hit is not None and hit[0] == stamp and hit[1] is index:
+                return hit[2]
+            indptr, indices, values = self._sparse_csr(self._ids.uids, self._sparse_vectors())
+            store = index.sparse(indptr, indices, values, self.__dict__.get("_sparse_dim") or 1)
+            # an outdated store is dropped, not freed: a search running outside the lock may still hold it
+            self.__dict__["_sparse_store"] = (stamp, index, store)
+            self.__dict__["_sparse_builds"] = self.__dict__.get("_sparse_builds", 0) + 1
+            return store
+
+    def _sparse_save(self, path):
+        """The sparse vectors beside the main file (caller holds the lock): written when there are any, a leftover file
+        removed when there are none."""
+        vectors = self._sparse_vectors()
+        if vectors:
+            with open(path, 'wb') as f:
+                pickle.dump({'dim': self.__dict__.get("_sparse_dim"), 'dim_fixed': bool(self.__dict__.get("_sparse_dim_fixed")),
+                             'vectors': {uid: (pair[0], pair[1]) for uid, pair in vectors.items()}}, f)
+        elif os.path.exists(path):
+            os.remove(path)
+
+    def _sparse_load(self, path):
+        """Read what `_sparse_save` wrote (caller holds the lock); entries of ids that are not stored are dropped."""
+        self.__dict__["_sparse"] = {}
+        self.__dict__.pop("_sparse_store", None)
+        self.__dict__["_sparse_gen"] = self.__dict__.get("_sparse_gen", 0) + 1
+        if not os.path.exists(path):
+            return
+        with open(path, 'rb') as f:
+            data = pickle.load(f)
+        self.__dict__["_sparse_dim"] = data.get('dim')
+        self.__dict__["_sparse_dim_fixed"] = bool(data.get('dim_fixed'))
+        self.__dict__["_sparse"] = {uid: (np.asarray(pair[0], dtype=np.int64), np.asarray(pair[1], dtype=np.float32))
+                                    for uid, pair in data['vectors'].items() if uid in self._ids}
+
+    def _sparse_search(self, dense, sparse_queries, k, dense_weight, sparse_weight, metadata_filter, exclude_filter, or_filters, autocut):
+        """Sparse search (dense None) or hybrid search of the queries: one result triple per query."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be positive")
+        if k > self.SPARSE_MAX_K:
+            raise ValueError(f"k = {k} exceeds {self.SPARSE_MAX_K}, the most rows a sparse or hybrid search returns")
+        pairs = [self._sparse_pair(q) for q in sparse_queries]
+        nq = len(pairs)
+        if nq == 0 or self._mat is None:
+            return [([], [], []) for _ in range(nq)]
+        if dense is not None:
+            if dense.shape[0] != nq:
+                raise ValueError(f"{dense.shape[0]} embeddings, {nq} sparse queries")
+            if dense.shape[1] != self._mat.d:
+                raise ValueError(f"query dimension {dense.shape[1]} != index dimension {self._mat.d}")
+            dense_weight = float(np.float32(dense_weight))
+        sparse_weight = float(np.float32(sparse_weight))
+        answered = []   # the queries the device sees (sparse search: those that are not empty)
+
+        def search(index, count, rowset):
+            if not hasattr(index, "search_sparse"):
+                raise NotImplementedError(f"{type(index).__name__} has no sparse search")
+            take = min(k, count)
+            store = self._resident_sparse_store(index)
+            # indices the store's dimension does not cover are dropped: no row can hold them
+            queries = []
+            for pair in pairs:
+                if pair is None:
+                    queries.append((np.empty(0, np.int64), np.empty(0, np.float32)))
+                else:
+                    keep = pair[0] < store.dim
+                    queries.append((pair[0][keep], pair[1][keep]))
+            del answered[:]
+            if dense is None:
+                answered.extend(i for i, q in enumerate(queries) if len(q[0]))
+                if not answered:
+                    return None
+                return index.search_sparse(store, [queries[i] for i in answered], take, rowset=rowset())
+            answered.extend(range(nq))
+            if any(len(q[0]) == 0 for q in queries):
+                # a query left empty ranks by the dense score alone, through the same call: the smallest stored index at weight 0
+                with self.lock:
+                    first = min((int(p[0][0]) for p in self._sparse_vectors().values()), default=0)
+                filler = (np.array([min(first, store.dim - 1)], np.int64), np.zeros(1, np.float32))
+                queries = [q if len(q[0]) else filler for q in queries]
+            return index.search_hybrid(store, dense, queries, take, dense_weight=dense_weight, sparse_weight=sparse_weight, rowset=rowset(),
+                                       normalize_q=True)
+
+        found = self._search_selected(metadata_filter, exclude_filter, or_filters, None, search)
+        out = [([], [], []) for _ in range(nq)]
+        if found is None:
+            return out
+        scores, rows = found
+        uids = self._ids.uids
+        for slot, i in enumerate(answered):
+            hits = []
+            for row, score in zip(rows[slot], scores[slot]):
+                if row == -1:
+                    continue
+                try:  # a row a concurrent delete has just renumbered away is skipped, as in find_most_similar
+                    hits.append((uids[int(row)], score, self.metadata[int(row)]))
+                except (KeyError, IndexError):
+                    pass
+            out[i] = self._package(hits, autocut)
+        return out
+
+    def find_most_similar_sparse(self, sparse_query, k=5, metadata_filter=None, exclude_filter=None, or_filters=None, autocut=False):
+        """The `k` stored ids whose SPARSE vector scores highest against `sparse_query` (``{index: weight}`` or ``(indices,
+        values)``, at most 1,024 terms): the float32 dot product over the indices both hold, under the filters of
+        ``find_most_similar``.  Only ids that share an index with the query are results; the ranking is exact over every
+        selected row, in one pass over the stored non-zeros on the device.  Query indices beyond ``sparse_dim`` are dropped
+        (no row can hold them); a query left empty gives ``([], [], [])``.  Returns ``(ids, scores, metadatas)`` packaged as
+        ``find_most_similar`` does, best first, equal scores in storage order; ``k > 64`` is a ValueError.  No reference
+        counterpart."""
+        return self._sparse_search(None, [sparse_query], k, 1.0, 1.0, metadata_filter, exclude_filter, or_filters, autocut)[0]
+
+    def find_most_similar_sparse_batch(self, sparse_queries, k=5, metadata_filter=None, exclude_filter=None, or_filters=None, autocut=False):
+        """Several sparse queries under ONE filter in one launch: element i is what ``find_most_similar_sparse(sparse_queries[i],
+        ...)`` returns."""
+        return self._sparse_search(None, list(sparse_queries), k, 1.0, 1.0, metadata_filter, exclude_filter, or_filters, autocut)
+
+    def find_most_similar_hybrid(self, embedding, sparse_query, k=5, dense_weight=1.0, sparse_weight=1.0, metadata_filter=None,
+                                 exclude_filter=None, or_filters=None, autocut=False):
+        """The `k` stored ids with the largest ``S = dense_weight * cosine + sparse_weight * sparse`` — `sparse` the score of
+        ``find_most_similar_sparse``, 0 for an id that shares no index with the query — under the filters of
+        ``find_most_similar``.  Every selected row is ranked on S in one exact pass on the device: the sparse scores of all rows
+        are written as one column, then the boosted search's scan runs over it — a row that wins on S from far down the dense
+        ranking is found, which re-ranking a dense top-k (the reference's ``hybrid_rerank_results``) cannot promise.  A sparse
+        query left empty (None, or only indices beyond ``sparse_dim``) ranks by ``dense_weight * cosine``.  Returns ``(ids,
+        scores, metadatas)``; ``scores`` holds S (np.float32).  ``k > 64`` is a ValueError.  No reference counterpart."""
+        query = np.array([np.array(embedding, dtype=np.float32)])  # [1, d]; normalised on the device
+        if query.ndim != 2:
+            raise ValueError("embedding must be one vector")
+        return self._sparse_search(query, [sparse_query], k, dense_weight, sparse_weight, metadata_filter, exclude_filter, or_filters,
+                                   autocut)[0]
+
+    def find_most_similar_hybrid_batch(self, embeddings, sparse_queries, k=5, dense_weight=1.0, sparse_weight=1.0, metadata_filter=None,
+                                       exclude_filter=None, or_filters=None, autocut=False):
+        """Several (embedding, sparse query) pairs under ONE filter: element i is what ``find_most_similar_hybrid(embeddings[i],
+        sparse_queries[i], ...)`` returns.  The queries follow each other on the device; each writes its column and reads the
+        selected rows once."""
+        queries = np.ascontiguousarray(np.asarray(embeddings, dtype=np.float32))
+        if queries.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like, one query per row")
+        return self._sparse_search(queries, list(sparse_queries), k, dense_weight, sparse_weight, metadata_filter, exclude_filter,
+                                   or_filters, autocut)
 
     # ---- clustering: every selected row labelled by the nearest of a few vectors; spherical k-means -----------------
     ASSIGN_MAX_VECTORS = 4096   # most vectors / clusters of one call (include/mvdb.h "ASSIGN AND K-MEANS")

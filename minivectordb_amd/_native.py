@@ -178,6 +178,21 @@ PROTOTYPES = {
                                                         ctypes.c_int, c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_index_boost_combine": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int64, c_vp]),
     "mvdb_index_boost_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_sparse_create": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(c_vp)]),
+    "mvdb_sparse_rows": (ctypes.c_int64, [c_vp]),
+    "mvdb_sparse_nnz": (ctypes.c_int64, [c_vp]),
+    "mvdb_sparse_dim": (ctypes.c_int64, [c_vp]),
+    "mvdb_sparse_free": (ctypes.c_int, [c_vp]),
+    "mvdb_sparse_geometry": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_sparse_scores": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_index_search_sparse": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_sparse_device": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64, c_vp, c_vp,
+                                                       c_vp]),
+    "mvdb_index_search_hybrid": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                ctypes.c_float, c_vp, c_vp, c_vp]),
+    "mvdb_index_search_hybrid_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                       ctypes.c_float, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "mvdb_index_sparse_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -1045,6 +1060,87 @@ class FlatIndex:
         check(lib().mvdb_index_boost_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    # ---- sparse vectors and hybrid search (include/mvdb.h "SPARSE VECTORS AND HYBRID SEARCH") ----
+    def sparse(self, indptr, indices, values, dim):
+        """A resident SparseStore: one sparse vector per stored row, CSR."""
+        return SparseStore(self, indptr, indices, values, dim)
+
+    @staticmethod
+    def _sparse_queries(queries):
+        """[(indices, values), ...] as the CSR arrays of a call: (indptr int64[nq + 1], indices int32, values float32)."""
+        indptr, idx, val = [0], [], []
+        for qi, qv in queries:
+            qi = np.asarray(qi).reshape(-1)
+            if qi.size and (qi.min() < -2**31 or qi.max() >= 2**31):
+                raise ValueError(f"sparse query: index {int(qi.max() if qi.max() >= 2**31 else qi.min())} does not fit 32 bits")
+            qv = np.asarray(qv, dtype=np.float32).reshape(-1)
+            if len(qi) != len(qv):
+                raise ValueError(f"{len(qi)} sparse query indices, {len(qv)} values")
+            idx.append(qi.astype(np.int32))
+            val.append(qv)
+            indptr.append(indptr[-1] + len(qi))
+        return (np.asarray(indptr, dtype=np.int64), np.ascontiguousarray(np.concatenate(idx) if idx else np.empty(0, np.int32), dtype=np.int32),
+                np.ascontiguousarray(np.concatenate(val) if val else np.empty(0, np.float32), dtype=np.float32))
+
+    def sparse_scores(self, store, q_indices, q_values, with_matched=True):
+        """(T float32[ntotal], matched int32[ntotal]): the sparse score of every stored row against one query and the number
+        of its entries the query holds, computed by the scoring launch alone."""
+        indptr, qi, qv = self._sparse_queries([(q_indices, q_values)])
+        T = np.empty(self.ntotal, dtype=np.float32)
+        matched = np.empty(self.ntotal, dtype=np.int32) if with_matched else None
+        check(lib().mvdb_index_sparse_scores(self._h, store._h, _ptr(qi), _ptr(qv), len(qi), _ptr(T), _ptr(matched) if with_matched else None))
+        return (T, matched) if with_matched else T
+
+    def search_sparse(self, store, queries, k, rowset=None):
+        """(D float32[nq, k], I int64[nq, k]): per sparse query (indices, values) the k selected rows with the largest sparse
+        score among those that share an index with it, best first (equal scores: the lower row); fewer end in -FLT_MAX / -1."""
+        indptr, qi, qv = self._sparse_queries(queries)
+        nq, k = len(indptr) - 1, int(k)
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        check(lib().mvdb_index_search_sparse(self._h, store._h, _ptr(indptr), _ptr(qi), _ptr(qv), nq, k, rowset._h if rowset is not None else None,
+                                             _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_sparse_device(self, store, queries, k, D_ptr, I_ptr, rowset=None, stream=0, label_offset=0):
+        """Device-pointer variant of search_sparse (I: row numbers + label_offset; the queries stay host arrays)."""
+        indptr, qi, qv = self._sparse_queries(queries)
+        check(lib().mvdb_index_search_sparse_device(self._h, store._h, _ptr(indptr), _ptr(qi), _ptr(qv), len(indptr) - 1, int(k),
+                                                    rowset._h if rowset is not None else None, int(label_offset), ctypes.c_void_p(D_ptr),
+                                                    ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def search_hybrid(self, store, q, queries, k, dense_weight=1.0, sparse_weight=1.0, rowset=None, normalize_q=False):
+        """(D float32[nq, k], I int64[nq, k]): the k selected rows with the largest S = dense_weight * s + sparse_weight *
+        sparse, query i being the dense q[i] with the sparse queries[i]; exact over every selected row."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q, dtype=np.float32)))
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[-1]} != index dimension {self.d}")
+        indptr, qi, qv = self._sparse_queries(queries)
+        nq, k = q.shape[0], int(k)
+        if len(indptr) - 1 != nq:
+            raise ValueError(f"{nq} dense queries, {len(indptr) - 1} sparse queries")
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        check(lib().mvdb_index_search_hybrid(self._h, store._h, _ptr(q), int(bool(normalize_q)), _ptr(indptr), _ptr(qi), _ptr(qv), nq, k,
+                                             ctypes.c_float(dense_weight), ctypes.c_float(sparse_weight), rowset._h if rowset is not None else None,
+                                             _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_hybrid_device(self, store, q_ptr, queries, k, D_ptr, I_ptr, dense_weight=1.0, sparse_weight=1.0, rowset=None, stream=0,
+                             normalize_q=False, label_offset=0):
+        """Device-pointer variant of search_hybrid (the sparse queries stay host arrays)."""
+        indptr, qi, qv = self._sparse_queries(queries)
+        check(lib().mvdb_index_search_hybrid_device(
+            self._h, store._h, ctypes.c_void_p(q_ptr), int(bool(normalize_q)), _ptr(indptr), _ptr(qi), _ptr(qv), len(indptr) - 1, int(k),
+            ctypes.c_float(dense_weight), ctypes.c_float(sparse_weight), rowset._h if rowset is not None else None, int(label_offset),
+            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def sparse_counters(self):
+        """(sparse and hybrid searches served, sparse_scan_kernel launches enqueued): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(2)]
+        check(lib().mvdb_index_sparse_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     # ---- probed search: a k-means partition, a query scans the lists of its nprobe best centres (include/mvdb.h "PROBED SEARCH") ----
     def partition(self, centres, labels=None, normalize_c=False):
         """A resident Partition of the stored rows into len(centres) member lists.  labels None: every row is labelled on the
@@ -1190,6 +1286,54 @@ class RowTerm:
     def free(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib().mvdb_rowterm_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def sparse_geometry():
+    """(span_entries, tile_rows, table_slots) of the sparse scan of this build (mvdb_sparse_geometry)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    check(lib().mvdb_sparse_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+class SparseStore:
+    """mvdb_sparse*: one sparse vector per stored row in CSR form, resident on the index's device.  Valid until the index it
+    was built on gains or loses a row (updating rows in place keeps it valid); its device memory goes with the last
+    reference."""
+
+    def __init__(self, index, indptr, indices, values, dim):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64).reshape(-1)
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if len(indptr) < 1:
+            raise ValueError("indptr must hold n + 1 offsets")
+        if len(indices) != len(values):
+            raise ValueError(f"{len(indices)} indices, {len(values)} values")
+        if len(indptr) > 1 and int(indptr[-1]) > len(indices):
+            raise ValueError(f"indptr ends at {int(indptr[-1])}, beyond the {len(indices)} entries")
+        self._h = ctypes.c_void_p()
+        check(lib().mvdb_sparse_create(index._h, _ptr(indptr), _ptr(indices), _ptr(values), len(indptr) - 1, int(dim), ctypes.byref(self._h)))
+
+    def __len__(self):
+        return int(lib().mvdb_sparse_rows(self._h))
+
+    @property
+    def nnz(self):
+        return int(lib().mvdb_sparse_nnz(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_sparse_dim(self._h))
+
+    def free(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_sparse_free(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -28,6 +28,7 @@
 #include "assign_scan.hpp"
 #include "examples_scan.hpp"
 #include "boost_scan.hpp"
+#include "sparse_scan.hpp"
 #include "probe_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
@@ -435,6 +436,9 @@ struct Workspace {
     DevBuf<float> bsT;                   // boosted search: the combined term column of one call, [n] (boost_scan.hpp) ...
     DevBuf<int64_t> bsrows;              // ... the sparse entries' rows ...
     DevBuf<float> bsvals;                // ... and their values
+    DevBuf<uint64_t> spq;                // sparse search: the queries of one call, [nq + 1] term offsets then the (index, value) terms (sparse_scan.hpp) ...
+    DevBuf<uint64_t> spmask;             // ... a row list as a bitmap over the stored rows ...
+    DevBuf<int32_t> spmatched;           // ... and mvdb_index_sparse_scores' matched counts, [n]
     DevBuf<float> kmc;                   // k-means: the centres, [C, ld] ...
     DevBuf<int32_t> kmlab[2];            // ... the labels of this iteration and of the one before, [n] each ...
     DevBuf<uint32_t> kmmem;              // ... the member lists, label after label, [n] ...
@@ -630,6 +634,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> ex_calls{0}, ex_passes{0};
     // boosted search: searches served and boost_scan_kernel launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> bs_calls{0}, bs_launches{0};
+    // sparse and hybrid search: searches served and sparse_scan_kernel launches enqueued, both counted on the host
+    mutable std::atomic<unsigned long long> sp_calls{0}, sp_launches{0};
     // probed search: calls served and launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> pb_calls{0}, pb_launches{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
@@ -5815,22 +5821,12 @@ int launch_boost(const BoostScanArgs& a, int nq, int device, hipStream_t s, int*
     });
 }
 
-// Queries on the device at stride ld, the sparse entries on the device, results to device buffers: the combine (shared by the
-// queries of the call), then per tile of kCoreTile queries ONE scan launch — the queries are the grid's y dimension — and the merge.
-int boost_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int normalize_q, float score_weight,
-               const mvdb_rowterm* const* terms, const float* weights, int nterms, int64_t nsparse, const mvdb_rowset* rs, int64_t label_offset,
-               float* D_dev, int64_t* I_dev) {
+// The scan over ws->bsT, whoever wrote it (the combine above; the sparse scoring launch of hybrid search): per tile of kCoreTile
+// queries ONE scan launch — the queries are the grid's y dimension — and the merge.  Something is selected.
+int boost_scan_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int normalize_q, float score_weight, const mvdb_rowset* rs,
+                    int64_t label_offset, float* D_dev, int64_t* I_dev) {
     hipStream_t s = ws->stream;
-    ++idx->bs_calls;
     const int64_t n = idx->n;
-    const int64_t m = rs ? rs->count : n;  // rows selected
-    const int64_t total = (int64_t)nq * k;
-    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {  // an empty index or an empty set: every output is padding
-        hipLaunchKernelGGL(fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, total, idx->metric);
-        MVDB_HIP(hipGetLastError());
-        return 0;
-    }
-    MVDB_TRY(boost_combine_core(idx, ws, terms, weights, nterms, nsparse));
     const int tile = std::min(nq, kCoreTile);
     MVDB_TRY(ws->cand.reserve((size_t)tile * scan_grid_upper_bound(idx->device) * k));
     BoostScanArgs a;
@@ -5854,6 +5850,25 @@ int boost_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int
         MVDB_TRY(launch_merge(idx, ws, take, nblocks, k, label_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k));
     }
     return 0;
+}
+
+// Queries on the device at stride ld, the sparse entries on the device, results to device buffers: the combine (shared by the
+// queries of the call), then boost_scan_core.
+int boost_core(const mvdb_index* idx, Workspace* ws, const float* q, int nq, int k, int normalize_q, float score_weight,
+               const mvdb_rowterm* const* terms, const float* weights, int nterms, int64_t nsparse, const mvdb_rowset* rs, int64_t label_offset,
+               float* D_dev, int64_t* I_dev) {
+    hipStream_t s = ws->stream;
+    ++idx->bs_calls;
+    const int64_t n = idx->n;
+    const int64_t m = rs ? rs->count : n;  // rows selected
+    const int64_t total = (int64_t)nq * k;
+    if (m == 0 || (rs && rs->mask && rs->n_at_create == 0)) {  // an empty index or an empty set: every output is padding
+        hipLaunchKernelGGL(fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, D_dev, I_dev, total, idx->metric);
+        MVDB_HIP(hipGetLastError());
+        return 0;
+    }
+    MVDB_TRY(boost_combine_core(idx, ws, terms, weights, nterms, nsparse));
+    return boost_scan_core(idx, ws, q, nq, k, normalize_q, score_weight, rs, label_offset, D_dev, I_dev);
 }
 
 int check_boost_args(const mvdb_index* idx, const void* q, int nq, int k, const void* D, const void* I) {
@@ -5972,6 +5987,436 @@ int mvdb_index_boost_counters(const mvdb_index* idx, long long* calls, long long
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->bs_calls.load();
     if (scan_launches) *scan_launches = (long long)idx->bs_launches.load();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- sparse vectors: a CSR pass scores every stored sparse row against a sparse query; hybrid = that column, then the boosted scan (sparse_scan.hpp) ----
+struct mvdb_sparse {
+    uint64_t owner = 0;       // serial number of the index the store was built on
+    int device = 0;
+    int64_t n = 0;            // the index's row count it was built against: one sparse vector per row
+    uint64_t renumbered = 0;  // ... and its renumbering generation
+    int64_t dim = 0, nnz = 0, ntiles = 0;
+    SparseEntry* entries = nullptr;  // [nnz + 2] on the device
+    int64_t* indptr = nullptr;       // [n + 1]
+    int64_t* tiles = nullptr;        // [2 (ntiles + 1)]: the tiles' first rows, then their first entries
+};
+
+namespace {
+
+int sparse_check(const mvdb_index* idx, const mvdb_sparse* sp) {
+    if (!sp) return fail(MVDB_ERR_ARG, "sparse search: the sparse store is NULL");
+    if (sp->owner != idx->serial || sp->device != idx->device) return fail(MVDB_ERR_ARG, "sparse search: the sparse store belongs to another index");
+    if (sp->n != idx->n) return fail(MVDB_ERR_ARG, "sparse search: the sparse store holds %lld rows, the index %lld", (long long)sp->n, (long long)idx->n);
+    if (sp->renumbered != idx->renumbered)
+        return fail(MVDB_ERR_ARG, "sparse search: the sparse store was built before rows were removed (%lld rows then, %lld now)", (long long)sp->n,
+                    (long long)idx->n);
+    return 0;
+}
+
+// the queries of a call: offsets from 0, 1 .. kSparseMaxQuery distinct indices inside [0, dim) each
+int check_sparse_queries(const mvdb_sparse* sp, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq) {
+    if (nq <= 0) return fail(MVDB_ERR_ARG, "nq must be positive (got %d)", nq);
+    if (!q_indptr) return fail(MVDB_ERR_ARG, "NULL sparse query passed to sparse search");
+    if (q_indptr[0] != 0) return fail(MVDB_ERR_ARG, "sparse query: the offsets start at %lld, not 0", (long long)q_indptr[0]);
+    for (int i = 0; i < nq; ++i) {
+        const int64_t m = q_indptr[i + 1] - q_indptr[i];
+        if (m < 1 || m > kSparseMaxQuery)
+            return fail(MVDB_ERR_ARG, "sparse query %d holds %lld terms: a query needs 1 to %d", i, (long long)m, kSparseMaxQuery);
+    }
+    if (!q_indices || !q_values) return fail(MVDB_ERR_ARG, "NULL sparse query passed to sparse search");
+    std::vector<int32_t> sorted;
+    for (int i = 0; i < nq; ++i) {
+        sorted.assign(q_indices + q_indptr[i], q_indices + q_indptr[i + 1]);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.front() < 0 || sorted.back() >= sp->dim)
+            return fail(MVDB_ERR_ARG, "sparse query %d: index %lld is outside [0, %lld)", i, (long long)(sorted.front() < 0 ? sorted.front() : sorted.back()),
+                        (long long)sp->dim);
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return fail(MVDB_ERR_ARG, "sparse query %d: index %lld is listed twice", i, (long long)*dup);
+    }
+    return 0;
+}
+
+// The queries to ws->spq through the pinned staging, `pin_off` bytes in (a multiple of 8; the caller has reserved the staging
+// buffer): [nq + 1] offsets, then the packed terms.  The staging bytes are read when the copy runs (stage_boost_sparse).
+size_t sparse_query_bytes(const int64_t* q_indptr, int nq) { return (size_t)(nq + 1 + q_indptr[nq]) * sizeof(uint64_t); }
+int stage_sparse_queries(Workspace* ws, size_t pin_off, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq) {
+    const int64_t M = q_indptr[nq];
+    const size_t words = (size_t)(nq + 1 + M);
+    MVDB_TRY(ws->spq.reserve(words));
+    MVDB_TRY(ws->pin.reserve(pin_off + words * sizeof(uint64_t)));
+    char* const st = (char*)ws->pin.p + pin_off;
+    memcpy(st, q_indptr, (size_t)(nq + 1) * sizeof(int64_t));
+    SparseEntry* const e = reinterpret_cast<SparseEntry*>(st + (size_t)(nq + 1) * sizeof(int64_t));
+    for (int64_t i = 0; i < M; ++i) {
+        e[i].index = (uint32_t)q_indices[i];
+        memcpy(&e[i].value, q_values + i, sizeof(float));
+    }
+    MVDB_HIP(hipMemcpyAsync(ws->spq.p, st, words * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    return 0;
+}
+
+// the rows a sparse launch may offer: NULL (every row) or a bitmap over the rows [0, *mask_rows) — the set's own, its twin, or
+// the row list turned into one in the workspace
+int sparse_selector(const mvdb_index* idx, Workspace* ws, const mvdb_rowset* rs, const uint64_t** mask, int64_t* mask_rows) {
+    *mask = nullptr;
+    *mask_rows = 0;
+    if (!rs) return 0;
+    *mask_rows = rs->n_at_create;
+    if (rs->mask || rs->twin) {
+        *mask = rs->mask ? rs->mask : rs->twin;
+        return 0;
+    }
+    const size_t words = (size_t)((rs->n_at_create + 63) / 64);
+    MVDB_TRY(ws->spmask.reserve(words));
+    MVDB_HIP(hipMemsetAsync(ws->spmask.p, 0, words * sizeof(uint64_t), ws->stream));
+    hipLaunchKernelGGL(rows_to_mask_kernel, dim3((unsigned)((rs->count + 255) / 256)), dim3(256), 0, ws->stream, (const int64_t*)rs->rows, rs->count,
+                       rs->n_at_create, (unsigned long long*)ws->spmask.p);
+    MVDB_HIP(hipGetLastError());
+    *mask = ws->spmask.p;
+    return 0;
+}
+
+SparseScanArgs sparse_args(const mvdb_sparse* sp, Workspace* ws, int nq) {
+    SparseScanArgs a{};
+    a.entries = sp->entries;
+    a.indptr = sp->indptr;
+    a.tile_row = sp->tiles;
+    a.tile_ent = sp->tiles + sp->ntiles + 1;
+    a.ntiles = sp->ntiles;
+    a.q_indptr = reinterpret_cast<const int64_t*>(ws->spq.p);
+    a.q_terms = reinterpret_cast<const SparseEntry*>(ws->spq.p + nq + 1);
+    a.weight = 1.0f;
+    return a;
+}
+
+int sparse_grid(const mvdb_index* idx, const mvdb_sparse* sp) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(sp->ntiles, (int64_t)device_cus(idx->device) * kSparseBlocksPerCu));
+}
+
+// the scoring launch: T[r] = weight * sparse(r) of query `query` of the staged call, for every row (and matched[r], if asked)
+int sparse_column(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, int nq_staged, int query, float weight, float* T, int32_t* matched) {
+    SparseScanArgs a = sparse_args(sp, ws, nq_staged);
+    a.q_indptr += query;
+    a.weight = weight;
+    a.T = T;
+    a.matched = matched;
+    hipStream_t s = ws->stream;
+    ++idx->sp_launches;
+    return profiled_launch("sparse_scan", s, [&](hipEvent_t done) {
+        launch_kernel(sparse_scan_kernel<0, 0>, dim3(sparse_grid(idx, sp)), dim3(kSparseThreads), 0, s, done, a);
+    }, "sparse_scan_kernel<0, 0>");
+}
+
+bool nothing_selected(const mvdb_index* idx, const mvdb_rowset* rs) {
+    return (rs ? rs->count : idx->n) == 0 || (rs && rs->mask && rs->n_at_create == 0);
+}
+
+int fill_padding(Workspace* ws, float* D_dev, int64_t* I_dev, int64_t total) {
+    hipLaunchKernelGGL(fill_missing_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ws->stream, D_dev, I_dev, total, (int)MVDB_METRIC_IP);
+    MVDB_HIP(hipGetLastError());
+    return 0;
+}
+
+// the staged queries against the store: one top-k launch per kCoreTile queries (the grid's y) and the merge of its block lists
+int sparse_search_core(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, int nq, int k, const mvdb_rowset* rs, int64_t label_offset,
+                       float* D_dev, int64_t* I_dev) {
+    ++idx->sp_calls;
+    if (nothing_selected(idx, rs)) return fill_padding(ws, D_dev, I_dev, (int64_t)nq * k);
+    hipStream_t s = ws->stream;
+    SparseScanArgs a = sparse_args(sp, ws, nq);
+    MVDB_TRY(sparse_selector(idx, ws, rs, &a.mask, &a.mask_rows));
+    const int grid = sparse_grid(idx, sp);
+    const int tile = std::min(nq, kCoreTile);
+    MVDB_TRY(ws->cand.reserve((size_t)tile * grid * k));
+    a.k = k;
+    a.cand = ws->cand.p;
+    for (int q0 = 0; q0 < nq; q0 += tile) {
+        const int take = std::min(tile, nq - q0);
+        SparseScanArgs b = a;
+        b.q_indptr += q0;
+        ++idx->sp_launches;
+        if (a.mask)
+            MVDB_TRY(profiled_launch("sparse_scan", s, [&](hipEvent_t done) {
+                launch_kernel(sparse_scan_kernel<1, 2>, dim3(grid, take), dim3(kSparseThreads), 0, s, done, b);
+            }, "sparse_scan_kernel<1, 2>"));
+        else
+            MVDB_TRY(profiled_launch("sparse_scan", s, [&](hipEvent_t done) {
+                launch_kernel(sparse_scan_kernel<1, 0>, dim3(grid, take), dim3(kSparseThreads), 0, s, done, b);
+            }, "sparse_scan_kernel<1, 0>"));
+        MergeArgs mg;   // the scores are similarities whatever the index's metric
+        mg.keys = ws->cand.p;
+        mg.nlists = grid;
+        mg.k = k;
+        mg.metric = MVDB_METRIC_IP;
+        mg.label_offset = label_offset;
+        mg.D = D_dev + (int64_t)q0 * k;
+        mg.I = I_dev + (int64_t)q0 * k;
+        hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
+        MVDB_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// hybrid: per query the scoring launch writes T = sparse_weight * sparse into the boosted search's column, then its scan and merge
+int hybrid_core(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, const float* q, int nq, int k, int normalize_q, float dense_weight,
+                float sparse_weight, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev) {
+    ++idx->sp_calls;
+    if (nothing_selected(idx, rs)) return fill_padding(ws, D_dev, I_dev, (int64_t)nq * k);
+    MVDB_TRY(ws->bsT.reserve((size_t)idx->n));
+    for (int i = 0; i < nq; ++i) {
+        MVDB_TRY(sparse_column(idx, sp, ws, nq, i, sparse_weight, ws->bsT.p, nullptr));
+        MVDB_TRY(boost_scan_core(idx, ws, q + (int64_t)i * idx->ld, 1, k, normalize_q, dense_weight, rs, label_offset, D_dev + (int64_t)i * k,
+                                 I_dev + (int64_t)i * k));
+    }
+    return 0;
+}
+
+int check_sparse_k(int k) {
+    if (k < 1 || k > kMaxFusedK) return fail(MVDB_ERR_ARG, "sparse search needs 1 <= k <= %d (got %d)", kMaxFusedK, k);
+    return 0;
+}
+
+template <typename T>
+hipError_t upload_new(T** dst, const T* src, size_t count) {
+    hipError_t e = hipMalloc((void**)dst, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess && count) e = hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+// a device entry point's workspace without dense queries (StreamCall pads queries)
+struct SparseStreamCall {
+    Workspace* const ws;
+    std::unique_lock<std::mutex> use;
+    RetireScope keep;
+    SparseStreamCall(const mvdb_index* idx, void* stream)
+        : ws(idx->for_stream((hipStream_t)stream)),
+          use(ws ? std::unique_lock<std::mutex>(ws->use_mu) : std::unique_lock<std::mutex>()),
+          keep(ws && note_capture(ws) ? &ws->retired : nullptr) {}
+};
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_sparse_create(const mvdb_index* idx, const int64_t* indptr_host, const int32_t* indices_host, const float* values_host, int64_t n, int64_t dim,
+                       mvdb_sparse** out) {
+    if (!out) return fail(MVDB_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (n < 0) return fail(MVDB_ERR_ARG, "negative row count");
+    if (dim < 1 || dim > 2147483647ll) return fail(MVDB_ERR_ARG, "sparse store: dim must be in [1, 2^31 - 1] (got %lld)", (long long)dim);
+    if (!indptr_host) return fail(MVDB_ERR_ARG, "indptr is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (n != idx->n)
+        return fail(MVDB_ERR_ARG, "a sparse store needs one sparse vector per stored row (%lld vectors, %lld rows)", (long long)n, (long long)idx->n);
+    if (indptr_host[0] != 0) return fail(MVDB_ERR_ARG, "sparse store: indptr starts at %lld, not 0", (long long)indptr_host[0]);
+    for (int64_t r = 0; r < n; ++r)
+        if (indptr_host[r + 1] < indptr_host[r]) return fail(MVDB_ERR_ARG, "sparse store: indptr decreases at row %lld", (long long)r);
+    const int64_t nnz = indptr_host[n];
+    if (nnz > 0 && (!indices_host || !values_host)) return fail(MVDB_ERR_ARG, "indices or values is NULL");
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t i = indptr_host[r]; i < indptr_host[r + 1]; ++i) {
+            if (indices_host[i] < 0 || indices_host[i] >= dim)
+                return fail(MVDB_ERR_ARG, "sparse store: row %lld holds index %lld outside [0, %lld)", (long long)r, (long long)indices_host[i], (long long)dim);
+            if (i > indptr_host[r] && indices_host[i] <= indices_host[i - 1])
+                return fail(MVDB_ERR_ARG, "sparse store: the indices of row %lld are not strictly ascending", (long long)r);
+        }
+    // the tiles: consecutive rows, at most kSparseSpan entries and kSparseTileRows rows; a longer row alone
+    std::vector<int64_t> tile_row, tile_ent;
+    for (int64_t r = 0; r < n;) {
+        tile_row.push_back(r);
+        tile_ent.push_back(indptr_host[r]);
+        const int64_t e0 = indptr_host[r];
+        int64_t end = r + 1;
+        while (end < n && end - r < kSparseTileRows && indptr_host[end + 1] - e0 <= kSparseSpan) ++end;
+        r = end;
+    }
+    const int64_t ntiles = (int64_t)tile_row.size();
+    tile_row.push_back(n);
+    tile_ent.push_back(nnz);
+    tile_row.insert(tile_row.end(), tile_ent.begin(), tile_ent.end());
+    DeviceGuard dg(idx->device);
+    mvdb_sparse* sp = new mvdb_sparse();
+    sp->owner = idx->serial;
+    sp->device = idx->device;
+    sp->n = n;
+    sp->renumbered = idx->renumbered;
+    sp->dim = dim;
+    sp->nnz = nnz;
+    sp->ntiles = ntiles;
+    hipError_t e = upload_new(&sp->indptr, indptr_host, (size_t)n + 1);
+    if (e == hipSuccess) e = upload_new(&sp->tiles, tile_row.data(), tile_row.size());
+    if (e == hipSuccess) e = hipMalloc((void**)&sp->entries, (size_t)(nnz + 2) * sizeof(SparseEntry));
+    // the entries, interleaved, a chunk at a time; behind them the two padding entries
+    const int64_t chunk = 1 << 22;
+    std::vector<SparseEntry> buf((size_t)std::min<int64_t>(chunk, nnz + 2));
+    for (int64_t c = 0; e == hipSuccess && c < nnz + 2; c += chunk) {
+        const int64_t take = std::min(chunk, nnz + 2 - c);
+        for (int64_t i = 0; i < take; ++i) {
+            if (c + i < nnz) {
+                buf[i].index = (uint32_t)indices_host[c + i];
+                memcpy(&buf[i].value, values_host + c + i, sizeof(float));
+            } else {
+                buf[i] = SparseEntry{kSparsePadIndex, 0u};
+            }
+        }
+        e = hipMemcpy(sp->entries + c, buf.data(), (size_t)take * sizeof(SparseEntry), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        (void)mvdb_sparse_free(sp);
+        return fail(MVDB_ERR_HIP, "sparse store upload failed: %s", hipGetErrorString(e));
+    }
+    *out = sp;
+    return 0;
+}
+
+int64_t mvdb_sparse_rows(const mvdb_sparse* sp) { return sp ? sp->n : -1; }
+int64_t mvdb_sparse_nnz(const mvdb_sparse* sp) { return sp ? sp->nnz : -1; }
+int64_t mvdb_sparse_dim(const mvdb_sparse* sp) { return sp ? sp->dim : -1; }
+
+int mvdb_sparse_free(mvdb_sparse* sp) {
+    if (!sp) return 0;
+    {
+        DeviceGuard dg(sp->device);
+        if (sp->entries) (void)hipFree(sp->entries);
+        if (sp->indptr) (void)hipFree(sp->indptr);
+        if (sp->tiles) (void)hipFree(sp->tiles);
+    }
+    delete sp;
+    return 0;
+}
+
+int mvdb_sparse_geometry(int* span_entries, int* tile_rows, int* table_slots) {
+    if (span_entries) *span_entries = kSparseSpan;
+    if (tile_rows) *tile_rows = kSparseTileRows;
+    if (table_slots) *table_slots = kSparseSlots;
+    return 0;
+}
+
+int mvdb_index_sparse_scores(const mvdb_index* idx, const mvdb_sparse* sp, const int32_t* q_indices_host, const float* q_values_host, int m,
+                             float* T_host, int32_t* matched_host) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(sparse_check(idx, sp));
+    const int64_t q_indptr[2] = {0, m};
+    MVDB_TRY(check_sparse_queries(sp, q_indptr, q_indices_host, q_values_host, 1));
+    const int64_t n = idx->n;
+    if (n == 0) return 0;
+    if (!T_host) return fail(MVDB_ERR_ARG, "T is NULL");
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    MVDB_TRY(stage_sparse_queries(ws, 0, q_indptr, q_indices_host, q_values_host, 1));
+    MVDB_TRY(ws->bsT.reserve((size_t)n));
+    if (matched_host) MVDB_TRY(ws->spmatched.reserve((size_t)n));
+    MVDB_TRY(sparse_column(idx, sp, ws, 1, 0, 1.0f, ws->bsT.p, matched_host ? ws->spmatched.p : nullptr));
+    MVDB_TRY(copy_back(ws, ws->bsT.p, (size_t)n * sizeof(float), "sparse scores"));
+    memcpy(T_host, ws->pin_out.p, (size_t)n * sizeof(float));
+    if (matched_host) {
+        MVDB_TRY(copy_back(ws, ws->spmatched.p, (size_t)n * sizeof(int32_t), "sparse scores"));
+        memcpy(matched_host, ws->pin_out.p, (size_t)n * sizeof(int32_t));
+    }
+    return 0;
+}
+
+int mvdb_index_search_sparse(const mvdb_index* idx, const mvdb_sparse* sp, const int64_t* q_indptr_host, const int32_t* q_indices_host,
+                             const float* q_values_host, int nq, int k, const mvdb_rowset* rs, float* D_host, int64_t* I_host) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    MVDB_TRY(check_sparse_k(k));
+    if (nq <= 0) return fail(MVDB_ERR_ARG, "nq must be positive (got %d)", nq);
+    if (!D_host || !I_host) return fail(MVDB_ERR_ARG, "NULL buffer passed to search");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(sparse_check(idx, sp));
+    MVDB_TRY(check_sparse_queries(sp, q_indptr_host, q_indices_host, q_values_host, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(sparse_search_core(idx, sp, call.ws, nq, k, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_sparse_device(const mvdb_index* idx, const mvdb_sparse* sp, const int64_t* q_indptr_host, const int32_t* q_indices_host,
+                                    const float* q_values_host, int nq, int k, const mvdb_rowset* rs, int64_t label_offset, float* D_dev,
+                                    int64_t* I_dev, void* stream) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    MVDB_TRY(check_sparse_k(k));
+    if (nq <= 0) return fail(MVDB_ERR_ARG, "nq must be positive (got %d)", nq);
+    if (!D_dev || !I_dev) return fail(MVDB_ERR_ARG, "NULL buffer passed to search");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(sparse_check(idx, sp));
+    MVDB_TRY(check_sparse_queries(sp, q_indptr_host, q_indices_host, q_values_host, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "sparse search cannot be captured into a hipGraph");
+    SparseStreamCall call(idx, stream);
+    if (!call.ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
+    // the one host wait of this entry point: the staging copy of the queries belongs to the workspace (mvdb_index_search_boosted_device)
+    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_HIP(hipStreamSynchronize(call.ws->stream));
+    return sparse_search_core(idx, sp, call.ws, nq, k, rs, label_offset, D_dev, I_dev);
+}
+
+int mvdb_index_search_hybrid(const mvdb_index* idx, const mvdb_sparse* sp, const float* q_host, int normalize_q, const int64_t* q_indptr_host,
+                             const int32_t* q_indices_host, const float* q_values_host, int nq, int k, float dense_weight, float sparse_weight,
+                             const mvdb_rowset* rs, float* D_host, int64_t* I_host) {
+    MVDB_TRY(check_sparse_k(k));
+    MVDB_TRY(check_search_args(idx, q_host, nq, k, D_host, I_host));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "hybrid search needs an inner-product index");
+    MVDB_TRY(sparse_check(idx, sp));
+    MVDB_TRY(check_sparse_queries(sp, q_indptr_host, q_indices_host, q_values_host, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    Workspace* const ws = call.ws;
+    // the dense queries and, behind them in the same pinned staging buffer, the sparse ones
+    const size_t qbytes = (size_t)nq * idx->ld * sizeof(float);
+    MVDB_TRY(ws->pin.reserve(qbytes + sparse_query_bytes(q_indptr_host, nq)));
+    MVDB_TRY(call.stage(q_host, nq));
+    MVDB_TRY(stage_sparse_queries(ws, qbytes, q_indptr_host, q_indices_host, q_values_host, nq));
+    const size_t total = (size_t)nq * k;
+    float* D_dev = nullptr;
+    int64_t* I_dev = nullptr;
+    MVDB_TRY(call.results(total, &D_dev, &I_dev));
+    MVDB_TRY(hybrid_core(idx, sp, ws, ws->q.p, nq, k, normalize_q, dense_weight, sparse_weight, rs, 0, D_dev, I_dev));
+    return call.fetch(total, D_host, I_host);
+}
+
+int mvdb_index_search_hybrid_device(const mvdb_index* idx, const mvdb_sparse* sp, const float* q_dev, int normalize_q, const int64_t* q_indptr_host,
+                                    const int32_t* q_indices_host, const float* q_values_host, int nq, int k, float dense_weight,
+                                    float sparse_weight, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev, void* stream) {
+    MVDB_TRY(check_sparse_k(k));
+    MVDB_TRY(check_search_args(idx, q_dev, nq, k, D_dev, I_dev));
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (idx->metric != MVDB_METRIC_IP) return fail(MVDB_ERR_ARG, "hybrid search needs an inner-product index");
+    MVDB_TRY(sparse_check(idx, sp));
+    MVDB_TRY(check_sparse_queries(sp, q_indptr_host, q_indices_host, q_values_host, nq));
+    if (rs) MVDB_TRY(rowset_check(idx, rs));
+    DeviceGuard dg(idx->device);
+    if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "hybrid search cannot be captured into a hipGraph");
+    StreamCall call(idx, stream, q_dev, nq);
+    MVDB_TRY(call.rc);
+    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_HIP(hipStreamSynchronize(call.ws->stream));
+    return hybrid_core(idx, sp, call.ws, call.q, nq, k, normalize_q, dense_weight, sparse_weight, rs, label_offset, D_dev, I_dev);
+}
+
+int mvdb_index_sparse_counters(const mvdb_index* idx, long long* calls, long long* score_launches) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->sp_calls.load();
+    if (score_launches) *score_launches = (long long)idx->sp_launches.load();
     return 0;
 }
 

@@ -624,6 +624,34 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_boosted_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_BOOST)
 
+    # ---- sparse vectors and hybrid search: not across ranks ---------------------------------------------------------
+    _NO_SPARSE = ("DistributedShardedVectorDatabase has no sparse vectors: they are kept on one host keyed by id and their "
+                  "scores are not exchanged between ranks (use ShardedVectorDatabase on one device)")
+
+    def set_sparse_dim(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def set_sparse_vector(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def set_sparse_vectors_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def get_sparse_vector(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_sparse(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_sparse_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_hybrid(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_hybrid_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

@@ -15,6 +15,10 @@ reference rebuilds over ALL rows on every delete — ``metadata``, ``unique_ids`
 inverted-index key per deleted id (sharded_vector_database.py:225-241) — is not rebuilt; the shard FILE a delete touches
 is still rewritten whole, as there (:180-204): the files are the persistence contract.
 
+Sparse vectors (``set_sparse_vector``, ``find_most_similar_sparse``, ``find_most_similar_hybrid``) are kept IN MEMORY ONLY by
+this class: the shard files are the reference's layout and hold nothing else, so the vectors have to be set again after a
+load (``VectorDatabase`` writes them beside its file).
+
 Deliberate fix: ``get_vector`` indexes the shard's array with the row's
 position INSIDE that shard; the reference uses the global row number (:91-96), which is only right
 for shard 0.

@@ -242,6 +242,34 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_boosted_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_BOOST)
 
+    # ---- sparse vectors and hybrid search: not on the int8 cosine index ---------------------------------------------
+    _NO_SPARSE = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: sparse vectors, whose hybrid search "
+                  "adds a column of sparse scores to an exact fp32 pass, are not implemented (use ShardedVectorDatabase)")
+
+    def set_sparse_dim(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def set_sparse_vector(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def set_sparse_vectors_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def get_sparse_vector(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_sparse(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_sparse_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_hybrid(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def find_most_similar_hybrid_batch(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")

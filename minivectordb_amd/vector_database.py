@@ -91,6 +91,7 @@ class VectorDatabase(UpdateMixin, FilterAndRerankMixin):
                 self._ids = _IdIndex(id_map[i] for i in range(len(id_map)))
                 self.inverted_index = data.get('inverted_index', defaultdict(set))
                 self.__dict__.pop("_values", None)
+                self._sparse_load(self.storage_file + '.sparse')
                 self._note_write()
                 if self.embedding_size is not None:
                     self._build_index()
@@ -106,6 +107,8 @@ class VectorDatabase(UpdateMixin, FilterAndRerankMixin):
                     'inverted_index': self.inverted_index
                 }
                 pickle.dump(data, f)
+            # the sparse vectors travel beside the main file, whose bytes stay what they are without them
+            self._sparse_save(self.storage_file + '.sparse')
 
     # ---- ingest / delete (vector_database.py:49-155) -------------------------------------------------
     def get_vector(self, unique_id):
