@@ -1169,6 +1169,51 @@ int mvdb_encoder_forward_device(mvdb_encoder* enc, const int32_t* ids_dev, const
  * which is what mvdb_encoder_forward's Python wrapper does on the host path.  Valid until mvdb_encoder_free. */
 const unsigned int* mvdb_encoder_overflow_flag(const mvdb_encoder* enc);
 
+/* ---- BGE-M3's heads: lexical weights and ColBERT vectors from the same forward (csrc/m3_heads.hpp) ----
+ * With x[b,t,:] the last hidden state of token slot t of sentence b and len_b its valid tokens (masks are prefixes):
+ *   token weight   tw[b,t] = relu(sparse_w . x[b,t] + sparse_b) for t < len_b, 0 for masked slots (fp32; NaN stays NaN);
+ *   lexical weights of b: over t < len_b with ids[b,t] >= 0, not among unused_ids, and tw[b,t] > 0 — for every distinct token
+ *                  id its largest weight, emitted by ascending id (a NaN weight fails > 0 and is dropped, +inf is kept);
+ *   ColBERT vector v[b,t-1,:] = u / max(|u|_2, 1e-12), u = colbert_w x[b,t] + colbert_b, for 1 <= t < len_b (the CLS slot is
+ *                  dropped, the EOS slot kept): max(len_b - 1, 0) rows; the rows behind them read 0.
+ * colbert_dim C: a multiple of 32 with C <= hidden (the GEMM launchers' column granularity; BGE-M3: 1024).  Every reduction
+ * has a fixed order: the same bits run to run.  A token weight of a valid token, or a ColBERT row's squared norm, that is not
+ * finite ORs 1 into the overflow word above — the pooled row's protocol: re-run with compute = 0 when compute was 2.
+ *
+ * mvdb_encoder_set_heads keeps the pointers (device, fp32, 16-byte aligned; the caller owns the memory), like the weight table;
+ * NULL removes the heads.  unused_ids: at most 8 token ids that never get a lexical weight (BGE-M3: cls, pad, eos, unk =
+ * 0, 1, 2, 3). */
+typedef struct mvdb_m3_heads {
+    const float* sparse_w;   /* [H]   device, fp32 */
+    const float* sparse_b;   /* [1] */
+    const float* colbert_w;  /* [C,H] nn.Linear layout; NULL: no ColBERT head */
+    const float* colbert_b;  /* [C] */
+    int colbert_dim;         /* C */
+    int n_unused;
+    int unused_ids[8];
+} mvdb_m3_heads;
+int mvdb_encoder_set_heads(mvdb_encoder* enc, const mvdb_m3_heads* heads);
+
+/* The outputs wanted beside the pooled row; any pointer NULL = output not wanted; all device memory.  The padding is written
+ * by the forward's own kernels (no memset): token_weights of masked slots, ColBERT rows from colbert_count[b] on and
+ * lex_indices / lex_values from lex_count[b] on read 0.  lex_count, lex_indices and lex_values go together. */
+typedef struct mvdb_m3_out {
+    float* token_weights;    /* [B,S] */
+    int32_t* lex_count;      /* [B] */
+    int32_t* lex_indices;    /* [B,S] ascending token ids */
+    float* lex_values;       /* [B,S] */
+    float* colbert;          /* [B,S-1,C], 16-byte aligned */
+    int32_t* colbert_count;  /* [B] */
+} mvdb_m3_out;
+/* mvdb_encoder_forward_device's dense output plus the heads' outputs, from ONE forward; never synchronises, allocates nothing
+ * once the workspace has the batch's size.  It always runs the per-op kernels (never the layer-walking launch), on one lane,
+ * as plain launches on `stream` (not through the encoder's graph cache: the outputs are the caller's own buffers).  The heads
+ * run behind the last layer on the PACKED token states, in the call's compute mode.
+ * MVDB_ERR_ARG, before anything is enqueued: no heads set; a ColBERT output without a ColBERT head; the lexical outputs asked
+ * for in part; S > 1024 (the per-sentence sort of the lexical weights lives in 8 KiB of LDS); a misaligned `colbert`. */
+int mvdb_encoder_forward_multi_device(mvdb_encoder* enc, const int32_t* ids_dev, const int32_t* mask_dev, int B, int S,
+                                      int compute, float* dense_out_dev, const mvdb_m3_out* out, void* stream);
+
 /* 1 when a forward of B x S token slots is of the shape the ONE layer-walking launch serves (csrc/encoder_walk.hpp: at most 64
  * token slots — one sentence per call is the reference's only shape, embedding_model.py:62-71; beyond 64 slots the per-op kernels
  * are faster since round 6 —, exact fp32 matrix cores whatever `compute` says), 0 when it runs the per-op kernels.

@@ -52,6 +52,31 @@ class EncoderCfg(ctypes.Structure):
     ]
 
 
+class M3Heads(ctypes.Structure):
+    """mirror of mvdb_m3_heads"""
+    _fields_ = [
+        ("sparse_w", ctypes.c_void_p),
+        ("sparse_b", ctypes.c_void_p),
+        ("colbert_w", ctypes.c_void_p),
+        ("colbert_b", ctypes.c_void_p),
+        ("colbert_dim", ctypes.c_int),
+        ("n_unused", ctypes.c_int),
+        ("unused_ids", ctypes.c_int * 8),
+    ]
+
+
+class M3Out(ctypes.Structure):
+    """mirror of mvdb_m3_out"""
+    _fields_ = [
+        ("token_weights", ctypes.c_void_p),
+        ("lex_count", ctypes.c_void_p),
+        ("lex_indices", ctypes.c_void_p),
+        ("lex_values", ctypes.c_void_p),
+        ("colbert", ctypes.c_void_p),
+        ("colbert_count", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); the single source of truth for tests that check the export table
 PROTOTYPES = {
     "mvdb_last_error": (ctypes.c_char_p, []),
@@ -252,6 +277,9 @@ PROTOTYPES = {
     "mvdb_encoder_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
     "mvdb_encoder_forward_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    c_vp, c_vp, c_vp]),
+    "mvdb_encoder_set_heads": (ctypes.c_int, [c_vp, ctypes.POINTER(M3Heads)]),
+    "mvdb_encoder_forward_multi_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                                         ctypes.POINTER(M3Out), c_vp]),
 }
 
 

@@ -489,6 +489,8 @@ __global__ __launch_bounds__(256) void unpack_hidden_kernel(const float* __restr
     for (int c = threadIdx.x; c < H; c += blockDim.x) hidden[(int64_t)bt * H + c] = src ? src[c] : 0.f;
 }
 
+#include "m3_heads.hpp"  // BGE-M3's lexical-weight and ColBERT heads: m3_rows_kernel, m3_lex_kernel
+
 // =================================================================================================
 // GEMM  C[T,N] = A[T,K] · W[N,K]^T + bias (+ epilogue), exact fp32 on v_mfma_f32_32x32x2_f32
 // =================================================================================================
@@ -2540,6 +2542,11 @@ struct mvdb_encoder {
     unsigned int* walk_bar = nullptr;
     unsigned long long* walk_trace = nullptr;  // ablation build only
     unsigned int* overflow_flag = nullptr;     // device word: 1 after a forward whose pooled rows were not all finite
+    // BGE-M3's heads (mvdb_encoder_set_heads; m3_heads.hpp): the caller's pointers, like the weight table
+    bool have_heads = false;
+    mvdb_m3_heads heads{};
+    _Float16* colbert_p = nullptr;             // compute = 2: the (hi | lo) image of colbert_w (ensure_x3_weights) and 1 / its scale
+    float colbert_is = 1.f;
     PinnedBuf walk_pin;                        // host entry of the walking launch: [ids | mask | out] in ONE host-mapped buffer
     hipEvent_t walk_done = nullptr;            // recorded behind every forward of the device entry: the next one — on whatever
                                                // stream — waits for it (forwards share the staging buffers, the workspace and the
@@ -2958,12 +2965,18 @@ int make_interleaved(mvdb_encoder* e, const float* src, int64_t n, _Float16** ou
 }
 
 int ensure_x3_weights(mvdb_encoder* e, hipStream_t s) {
-    if (e->have_x3) return 0;
+    const bool head_due = e->have_heads && e->heads.colbert_w && !e->colbert_p;  // the ColBERT head's image: once per set_heads
+    if (e->have_x3 && !head_due) return 0;
     const int64_t H = e->cfg.hidden, F = e->cfg.intermediate;
     unsigned int* scratch = nullptr;
     MVDB_HIP(hipMalloc((void**)&scratch, sizeof(unsigned int)));
     int rc = 0;
+    if (head_due) {
+        rc = make_interleaved(e, e->heads.colbert_w, (int64_t)e->heads.colbert_dim * H, &e->colbert_p, &e->colbert_is, scratch, s);
+        if (!rc) e->owned_h.pop_back();  // (owned through colbert_p: set_heads replaces it)
+    }
     for (LayerW& L : e->layers) {
+        if (e->have_x3) break;
         if (!rc) rc = make_interleaved(e, L.wqkv, 3 * H * H, &L.wqkv_p, &L.wqkv_is, scratch, s);
         if (!rc) rc = make_interleaved(e, L.wo, H * H, &L.wo_p, &L.wo_is, scratch, s);
         if (!rc) rc = make_interleaved(e, L.w1, F * H, &L.w1_p, &L.w1_is, scratch, s);
@@ -3420,9 +3433,48 @@ int launch_proj_ln(const char* label, const char* ln_label, const LaneCall& c, c
 }
 
 
+// BGE-M3's heads behind the last layer, on the packed token states (m3_heads.hpp): the ColBERT projection as one more GEMM of
+// the forward's own launchers into w.y (free by now: pool_norm_kernel, its last user, ran before on the same stream; C <= H),
+// m3_rows_kernel (token weights, normalised ColBERT rows, the padding of both), m3_lex_kernel (per-sentence maximum per token id).
+// Lexical outputs without token_weights: the weights go through w.ctx, free behind the last layer as well.
+int enqueue_m3_heads(const LaneCall& c, const int32_t* ids, const mvdb_m3_out& o) {
+    mvdb_encoder* e = c.e;
+    const mvdb_m3_heads& hd = e->heads;
+    const int H = e->cfg.hidden, C = hd.colbert_dim;
+    const bool lex = o.lex_count != nullptr;
+    float* tw = o.token_weights ? o.token_weights : lex ? c.w.ctx : nullptr;
+    if (o.colbert) {
+        const Gemm g{c.compute == 2 ? c.xp : c.w.x, hd.colbert_w, e->colbert_p, e->colbert_is, hd.colbert_b, nullptr, c.w.y, C, H};
+        if (c.compute == 2) MVDB_TRY(launch_gemm_x3<EPI_BIAS>("enc_m3_colbert", c, g));
+        else launch_gemm<EPI_BIAS>("enc_m3_colbert", c, g);
+    }
+    if (tw || o.colbert || o.colbert_count) {
+        auto rows = [&](auto v4) {
+            constexpr int V4 = decltype(v4)::value;
+            enqueue("enc_m3_rows", kname("m3_rows_kernel<%d>", V4), m3_rows_kernel<V4>, dim3((unsigned)((c.Tmax + 3) / 4)), 256, 0, c.s, c.w.x, c.w.y,
+                    c.w.rank, c.w.seq_start, c.w.count, c.B, c.S, H, C, hd.sparse_w, hd.sparse_b, tw, o.colbert, o.colbert_count, e->overflow_flag);
+        };
+        switch ((H + 255) / 256) {  // 16-byte pieces per lane (H <= 1024)
+            case 1: rows(Int<1>{}); break;
+            case 2: rows(Int<2>{}); break;
+            case 3: rows(Int<3>{}); break;
+            default: rows(Int<4>{}); break;
+        }
+    }
+    if (lex) {
+        M3Unused unused{};
+        unused.n = hd.n_unused;
+        for (int i = 0; i < hd.n_unused; ++i) unused.id[i] = hd.unused_ids[i];
+        enqueue("enc_m3_lex", kname("m3_lex_kernel"), m3_lex_kernel, dim3(c.B), 256, 0, c.s, ids, c.w.rank, tw, c.S, unused, o.lex_count,
+                o.lex_indices, o.lex_values);
+    }
+    return 0;
+}
+
 // Enqueue every kernel of one forward on `s` (no allocation, no host sync: capturable in a hipGraph).
+// m3: the outputs of BGE-M3's heads wanted beside the pooled row (mvdb_encoder_forward_multi_device), or NULL.
 int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, const int32_t* mask, int B, int S,
-                 int compute, float* out, float* hidden, hipStream_t s, bool clear_flag = false) {
+                 int compute, float* out, float* hidden, hipStream_t s, bool clear_flag = false, const mvdb_m3_out* m3 = nullptr) {
     const mvdb_encoder_cfg& cfg = e->cfg;
     const EncoderKnobs& kn = e->kn;
     const int H = cfg.hidden, F = cfg.intermediate;
@@ -3480,6 +3532,7 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
     if (hidden)
         enqueue("enc_hidden", kname("unpack_hidden_kernel"), unpack_hidden_kernel, dim3((unsigned)Tmax), 256, 0, s, w.x, w.rank, w.seq_start, S, H,
                 hidden);
+    if (m3) MVDB_TRY(enqueue_m3_heads(c, ids, *m3));
     MVDB_HIP(hipGetLastError());
     return 0;
 }
@@ -3490,9 +3543,9 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
 // tails and attention run beside the other's GEMMs.  Measured (B = 256): S = 512 63.3 vs 65.4 ms, ragged 40.6 vs
 // 43.9 ms; at S = 32 (T = 8192) it gains nothing (4.09 vs 4.06 ms) and costs 6 % on a ragged batch: not used there.
 int enqueue_forward(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B, int S, int compute,
-                    float* out, float* hidden, hipStream_t s) {
-    const bool split = e->kn.split && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;
-    if (!split) return enqueue_lane(e, e->lane[0], ids, mask, B, S, compute, out, hidden, s, true);  // (clears the overflow word)
+                    float* out, float* hidden, hipStream_t s, const mvdb_m3_out* m3 = nullptr) {
+    const bool split = !m3 && e->kn.split && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;  // (the heads: one lane)
+    if (!split) return enqueue_lane(e, e->lane[0], ids, mask, B, S, compute, out, hidden, s, true, m3);  // (clears the overflow word)
     MVDB_HIP(hipMemsetAsync(e->overflow_flag, 0, sizeof(unsigned int), s));  // (a memset node of the captured graph)
     const int b0 = B / 2, b1 = B - b0;
     const int H = e->cfg.hidden;
@@ -3510,7 +3563,7 @@ int enqueue_forward(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, in
 // and then releases the device's gate (when *walked comes back true); 2 = the same, the gate released by a host callback
 // behind the launch (the device entry never waits).
 int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B, int S, int compute,
-                 float* out, float* hidden, hipStream_t s, int walk_mode = 0, bool* walked = nullptr) {
+                 float* out, float* hidden, hipStream_t s, int walk_mode = 0, bool* walked = nullptr, const mvdb_m3_out* m3 = nullptr) {
     if (walked) *walked = false;
     if (compute != 0 && compute != 2)
         return fail(MVDB_ERR_ARG, "unknown compute mode %d (0 = exact-fp32 MFMA, 2 = split-precision fp16 x 3; 1, the single-bf16-product "
@@ -3571,7 +3624,7 @@ int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B
     const bool outer_capture = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
     int pslot = outer_capture ? -1 : prof_begin("encoder", s);
     int rc = 0;
-    if (use_graph && !hidden && s && !outer_capture) {
+    if (use_graph && !hidden && !m3 && s && !outer_capture) {  // (the heads' outputs, like `hidden`: plain launches — DESIGN.md 6r)
         const GraphKey key{B, S, compute, ids, mask, out};
         auto it = e->graphs.find(key);
         if (it == e->graphs.end()) {
@@ -3597,7 +3650,7 @@ int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B
         }
         MVDB_HIP(hipGraphLaunch(it->second, s));
     } else {
-        rc = enqueue_forward(e, ids, mask, B, S, compute, out, hidden, s);
+        rc = enqueue_forward(e, ids, mask, B, S, compute, out, hidden, s, m3);
     }
     prof_end(pslot, s);
     return rc;
@@ -3768,6 +3821,7 @@ int mvdb_encoder_free(mvdb_encoder* e) {
         if (e->walk_done) (void)hipEventDestroy(e->walk_done);
         if (e->walk_aborts) (void)hipFree(e->walk_aborts);
         if (e->walk_aborts_host) (void)hipHostFree(e->walk_aborts_host);
+        if (e->colbert_p) (void)hipFree(e->colbert_p);
         e->walk_pin.release();
     }
     delete e;
@@ -3823,6 +3877,62 @@ int mvdb_encoder_forward_device(mvdb_encoder* e, const int32_t* ids_dev, const i
     MVDB_TRY(forward_core(e, e->ids_stage, e->mask_stage, B, S, compute, e->out_stage, nullptr, s, 2));
     MVDB_HIP(hipMemcpyAsync(out_dev, e->out_stage, outn * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (!capturing) MVDB_HIP(hipEventRecord(e->walk_done, s));
+    return 0;
+}
+
+int mvdb_encoder_set_heads(mvdb_encoder* e, const mvdb_m3_heads* heads) {
+    if (!e) return fail(MVDB_ERR_ARG, "encoder is NULL");
+    if (heads) {
+        if (!heads->sparse_w || !heads->sparse_b) return fail(MVDB_ERR_ARG, "sparse_w / sparse_b is NULL");
+        if ((uintptr_t)heads->sparse_w % 16) return fail(MVDB_ERR_ARG, "sparse_w must be 16-byte aligned");
+        if (heads->n_unused < 0 || heads->n_unused > kM3MaxUnused) return fail(MVDB_ERR_ARG, "n_unused %d outside [0, %d]", heads->n_unused, kM3MaxUnused);
+        if (heads->colbert_w) {
+            const int C = heads->colbert_dim;
+            if (!heads->colbert_b) return fail(MVDB_ERR_ARG, "colbert_b is NULL");
+            if (C <= 0 || C % 32 || C > e->cfg.hidden)
+                return fail(MVDB_ERR_ARG, "colbert_dim %d must be a multiple of 32 in (0, hidden = %d]", C, e->cfg.hidden);
+            if ((uintptr_t)heads->colbert_w % 16 || (uintptr_t)heads->colbert_b % 16) return fail(MVDB_ERR_ARG, "colbert_w / colbert_b must be 16-byte aligned");
+        }
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard dg(e->device);
+    if (e->colbert_p) {  // (a forward may still read the old image)
+        MVDB_HIP(hipDeviceSynchronize());
+        (void)hipFree(e->colbert_p);
+        e->colbert_p = nullptr;
+    }
+    e->have_heads = heads != nullptr;
+    e->heads = heads ? *heads : mvdb_m3_heads{};
+    if (heads && !heads->colbert_w) e->heads.colbert_dim = 0;
+    return 0;
+}
+
+int mvdb_encoder_forward_multi_device(mvdb_encoder* e, const int32_t* ids_dev, const int32_t* mask_dev, int B, int S, int compute,
+                                      float* dense_out_dev, const mvdb_m3_out* out, void* stream) {
+    if (!e) return fail(MVDB_ERR_ARG, "encoder is NULL");
+    if (!ids_dev || !mask_dev || !dense_out_dev) return fail(MVDB_ERR_ARG, "NULL buffer");
+    if (B <= 0 || S <= 0) return fail(MVDB_ERR_ARG, "B and S must be positive");
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard dg(e->device);
+    // every check before anything is enqueued
+    if (!e->have_heads) return fail(MVDB_ERR_ARG, "no heads: mvdb_encoder_set_heads first");
+    if (S > kM3MaxS) return fail(MVDB_ERR_ARG, "a multi-output forward takes S <= %d (S = %d)", kM3MaxS, S);
+    const mvdb_m3_out o = out ? *out : mvdb_m3_out{};
+    if ((o.colbert || o.colbert_count) && !e->heads.colbert_w) return fail(MVDB_ERR_ARG, "a ColBERT output was asked for, but no ColBERT head is set");
+    const int nlex = (o.lex_count != nullptr) + (o.lex_indices != nullptr) + (o.lex_values != nullptr);
+    if (nlex != 0 && nlex != 3) return fail(MVDB_ERR_ARG, "lex_count, lex_indices and lex_values go together");
+    if (o.colbert && (uintptr_t)o.colbert % 16) return fail(MVDB_ERR_ARG, "colbert must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // one forward at a time per encoder on the device (mvdb_encoder_forward_device): the workspace is shared
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool ordered = s && !(hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone);
+    if (ordered) {
+        if (!e->walk_done) MVDB_HIP(hipEventCreateWithFlags(&e->walk_done, hipEventDisableTiming));
+        else MVDB_HIP(hipStreamWaitEvent(s, e->walk_done, 0));
+    }
+    // always the per-op kernels (walk_mode 0), one lane, plain launches
+    MVDB_TRY(forward_core(e, ids_dev, mask_dev, B, S, compute, dense_out_dev, nullptr, s, 0, nullptr, &o));
+    if (ordered) MVDB_HIP(hipEventRecord(e->walk_done, s));
     return 0;
 }
 

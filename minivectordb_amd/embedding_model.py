@@ -12,8 +12,9 @@ PyTorch is used only as the container of the weights (state_dict -> device tenso
 tokenizer stays on the host, as in the reference.
 
 BGE-M3 (:73-79) is served by the same encoder with XLM-R position ids and CLS pooling
-(``dense_vecs`` = normalised first-token state); its sparse / ColBERT heads are not used by the
-reference and are not built.
+(``dense_vecs`` = normalised first-token state).  Its sparse and ColBERT heads, which the reference does not use, come from the
+same forward on request (``extract_embeddings_multi``, ``GpuEncoder.forward_multi``): they feed this package's sparse, hybrid
+and MaxSim searches.
 
 Not available in this build (SURVEY.md §8f "next"): the quantised ONNX USE model — its blob is
 absent from the reference tree (.MISSING_LARGE_BLOBS) and cannot be restated.  Selecting it raises
@@ -171,6 +172,130 @@ class GpuEncoder:
             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out, hidden
 
+    # ---- BGE-M3's heads: lexical weights and ColBERT vectors from the same forward --------------------------------------
+    def set_heads(self, sparse_linear, colbert_linear=None, unused_token_ids=(0, 1, 2, 3)):
+        """sparse_linear / colbert_linear: state dicts with ``weight`` / ``bias`` (what ``torch.load("sparse_linear.pt")`` and
+        ``torch.load("colbert_linear.pt")`` of a BGE-M3 directory give): Linear(H, 1) and Linear(H, C).  unused_token_ids:
+        at most 8 ids that never get a lexical weight (BGE-M3: cls, pad, eos, unk).  ``set_heads(None)`` removes the heads."""
+        import torch
+        lib = self._native.lib()
+        if sparse_linear is None:
+            self._native.check(lib.mvdb_encoder_set_heads(self._h, None))
+            self._heads = None
+            self.colbert_dim = 0
+            return
+
+        def dev(t, shape):
+            t = torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+            return t.clone() if t.data_ptr() % 16 else t
+
+        H = self.hidden
+        keep = [dev(sparse_linear["weight"], (H,)), dev(sparse_linear["bias"], (1,))]
+        heads = self._native.M3Heads(sparse_w=keep[0].data_ptr(), sparse_b=keep[1].data_ptr())
+        C = 0
+        if colbert_linear is not None:
+            C = int(torch.as_tensor(colbert_linear["weight"]).shape[0])
+            keep += [dev(colbert_linear["weight"], (C, H)), dev(colbert_linear["bias"], (C,))]
+            heads.colbert_w, heads.colbert_b, heads.colbert_dim = keep[2].data_ptr(), keep[3].data_ptr(), C
+        unused = [int(i) for i in unused_token_ids]
+        if len(unused) > 8:
+            raise ValueError("at most 8 unused token ids")
+        heads.n_unused = len(unused)
+        for i, v in enumerate(unused):
+            heads.unused_ids[i] = v
+        torch.cuda.synchronize(self.device)
+        self._native.check(lib.mvdb_encoder_set_heads(self._h, ctypes.byref(heads)))
+        self._heads = keep  # the encoder keeps the pointers: the tensors live as long as it does
+        self.colbert_dim = C
+
+    def forward_multi_device(self, ids, mask, compute=None, return_sparse=True, return_colbert=True):
+        """ids, mask: int32 torch tensors [B,S] on this device.  ONE forward, enqueued on torch's current stream, no wait.
+        Returns the untrimmed torch tensors: ``dense`` [B,H], ``token_weights`` [B,S]; with return_sparse ``lex_count`` [B],
+        ``lex_indices`` / ``lex_values`` [B,S] (ascending token ids, the first lex_count[b] of a row are set, the rest 0); with
+        return_colbert ``colbert`` [B,S-1,C] (rows from colbert_count[b] on are 0) and ``colbert_count`` [B]."""
+        import torch
+        compute = self.default_compute if compute is None else compute
+        B, S = ids.shape
+        H = self.hidden
+        # the small outputs are views into ONE buffer of 4-byte words, [word 0 | counts | dense | the three [B,S] arrays]: the
+        # host entry brings them over in one copy
+        names = ["dense", "token_weights"] + (["lex_count", "lex_indices", "lex_values"] if return_sparse else []) + (
+            ["colbert_count"] if return_colbert else [])
+        words = {"dense": B * H, "token_weights": B * S, "lex_count": B, "lex_indices": B * S, "lex_values": B * S, "colbert_count": B}
+        shapes = {"dense": (B, H), "token_weights": (B, S), "lex_count": (B,), "lex_indices": (B, S), "lex_values": (B, S), "colbert_count": (B,)}
+        flat = torch.empty(1 + sum(words[k] for k in names), dtype=torch.float32, device=self.device)
+        res, at = {}, 1
+        for k in names:
+            piece = flat[at:at + words[k]]
+            res[k] = (piece.view(torch.int32) if k in ("lex_count", "lex_indices", "colbert_count") else piece).view(shapes[k])
+            at += words[k]
+        if return_colbert:
+            res["colbert"] = torch.empty((B, max(S - 1, 0), max(getattr(self, "colbert_dim", 0), 1)), dtype=torch.float32, device=self.device)
+        out = self._native.M3Out(**{k: res[k].data_ptr() for k in res if k != "dense"})
+        self._native.check(self._native.lib().mvdb_encoder_forward_multi_device(
+            self._h, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(mask.data_ptr()), B, S, compute,
+            ctypes.c_void_p(res["dense"].data_ptr()), ctypes.byref(out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return res
+
+    def forward_multi(self, ids, mask, compute=None, return_sparse=True, return_colbert=True):
+        """ids, mask: int arrays [B,S] (host).  One forward, one stream wait.  Returns ``{"dense": [B,H] ndarray,
+        "lexical_weights": [{token_id (int): weight (float)} per sentence], "colbert_vecs": [[len_b - 1, C] ndarray per
+        sentence], "token_weights": [B,S] ndarray}`` (the keys a flag switches off are absent).  compute = 2 re-runs in the
+        exact mode when the forward raised the overflow word, as `forward` does.  Across the bus: ids and mask in one copy, the
+        small outputs and the overflow word in one copy, and the VALID ColBERT rows (gathered on the device) in one."""
+        import torch
+        compute = self.default_compute if compute is None else compute
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape != mask.shape:
+            raise ValueError("ids and mask must be [B,S] arrays of the same shape")
+        B, S = ids.shape
+        with torch.cuda.device(self.device):
+            both = torch.from_numpy(np.stack([ids, mask])).to(self.device)
+
+            def run(mode):
+                res = self.forward_multi_device(both[0], both[1], mode, return_sparse, return_colbert)
+                flat = res["dense"]._base  # the one buffer behind the small outputs
+                flat[0:1].view(torch.int32).copy_(self.overflow_flag())  # the overflow word rides along
+                return res, flat.cpu().numpy()  # (waits for the stream)
+
+            res, host = run(compute)
+            if compute == 2 and host[0:1].view(np.int32)[0]:
+                res, host = run(0)
+            base = res["dense"]._base.data_ptr()
+            off = {k: (res[k].data_ptr() - base) // 4 for k in res if k != "colbert"}
+            take = lambda k, dt=np.float32: host[off[k]:off[k] + res[k].numel()].view(dt).reshape(tuple(res[k].shape))  # noqa: E731
+            out = {"dense": take("dense").copy(), "token_weights": take("token_weights").copy()}
+            if return_sparse:
+                n, li, lv = take("lex_count", np.int32), take("lex_indices", np.int32), take("lex_values")
+                out["lexical_weights"] = [dict(zip(li[b, :n[b]].tolist(), lv[b, :n[b]].tolist())) for b in range(B)]
+            if return_colbert:
+                n = take("colbert_count", np.int32)
+                col = res["colbert"]
+                if B == 1:
+                    out["colbert_vecs"] = [col[0, :int(n[0])].cpu().numpy()]
+                else:  # only the valid rows cross the bus: gathered on the device, one copy
+                    keep = torch.arange(col.shape[1], device=self.device)[None, :] < res["colbert_count"][:, None]
+                    out["colbert_vecs"] = np.split(col[keep].cpu().numpy(), np.cumsum(n)[:-1])
+        return out
+
+
+def load_m3_heads(path):
+    """The two head files of a BGE-M3 directory, as state dicts of float32 CPU tensors: ``(sparse_linear, colbert_linear)``;
+    a file that is not there gives None.  Needs no GPU."""
+    import torch
+    out = []
+    for name in ("sparse_linear.pt", "colbert_linear.pt"):
+        f = os.path.join(path, name)
+        if not os.path.isfile(f):
+            out.append(None)
+            continue
+        sd = torch.load(f, map_location="cpu", weights_only=True)
+        if "weight" not in sd or "bias" not in sd:
+            raise KeyError(f"{f}: expected a state dict with 'weight' and 'bias'")
+        out.append({"weight": sd["weight"].float(), "bias": sd["bias"].float()})
+    return tuple(out)
+
 
 class EmbeddingModel:
 
@@ -191,6 +316,10 @@ class EmbeddingModel:
         self._state_dict = kwargs.get('state_dict')
         self._config = kwargs.get('config')
         self.tokenizer = kwargs.get('tokenizer')
+        # BGE-M3's heads (state dicts with weight / bias); a local model_path supplies them from its own two files
+        self._sparse_linear = kwargs.get('sparse_linear')
+        self._colbert_linear = kwargs.get('colbert_linear')
+        self.has_heads = False
         self.model = None
 
         if self.use_quantized_onnx_model:
@@ -227,6 +356,7 @@ class EmbeddingModel:
             # FlagEmbedding's BGEM3FlagModel.encode(...)['dense_vecs'] returns, embedding_model.py:74-78)
             if self._state_dict is not None:
                 self.model = GpuEncoder(self._config, self._state_dict, device=self._device, pooling="cls")
+                self._load_heads()
                 return
             from transformers import AutoModel, AutoTokenizer
             name = self._model_path or 'BAAI/bge-m3'
@@ -235,6 +365,17 @@ class EmbeddingModel:
             hf = AutoModel.from_pretrained(name)
             self.model = GpuEncoder(hf.config, hf.state_dict(), device=self._device, pooling="cls")
             del hf
+            self._load_heads()
+
+    def _load_heads(self):
+        """sparse_linear= / colbert_linear= kwargs, else sparse_linear.pt / colbert_linear.pt of a local model_path."""
+        sparse, colbert = self._sparse_linear, self._colbert_linear
+        if sparse is None and self._model_path and os.path.isdir(self._model_path):
+            sparse, from_dir = load_m3_heads(self._model_path)
+            colbert = colbert if colbert is not None else from_dir
+        if sparse is not None:
+            self.model.set_heads(sparse, colbert)
+            self.has_heads = True
 
     # ---- e5 path ---------------------------------------------------------------------------------------
     def _tokenize(self, texts):
@@ -265,6 +406,29 @@ class EmbeddingModel:
         ids = np.asarray(batch['input_ids'], dtype=np.int32)
         mask = np.asarray(batch['attention_mask'], dtype=np.int32)
         return self.encode_ids(ids, mask)[0].tolist()
+
+    # ---- BGE-M3: dense + lexical weights + ColBERT vectors from one forward ---------------------------------------------
+    def extract_embeddings_multi_batch(self, texts):
+        """One forward for the batch; a list of what `extract_embeddings_multi` returns, one per text."""
+        if not self.has_heads:
+            raise RuntimeError(
+                "no BGE-M3 heads loaded: pass model_path= a local directory that holds sparse_linear.pt (and colbert_linear.pt), "
+                "or the kwargs sparse_linear= (and colbert_linear=) with their state dicts, to EmbeddingModel")
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer loaded: pass tokenizer=... or model_path=... to EmbeddingModel")
+        batch = self.tokenizer(list(texts), max_length=512, padding=True, truncation=True, return_tensors='np')
+        ids = np.asarray(batch['input_ids'], dtype=np.int32)
+        mask = np.asarray(batch['attention_mask'], dtype=np.int32)
+        colbert = bool(self.model.colbert_dim)
+        out = self.model.forward_multi(ids, mask, return_colbert=colbert)
+        return [{"dense_vecs": out["dense"][b].tolist(), "lexical_weights": out["lexical_weights"][b],
+                 "colbert_vecs": out["colbert_vecs"][b] if colbert else None} for b in range(ids.shape[0])]
+
+    def extract_embeddings_multi(self, text):
+        """``{"dense_vecs": list, "lexical_weights": {token_id (int): weight (float)}, "colbert_vecs": [tokens - 1, C] ndarray}``
+        from ONE forward: BGE-M3's three outputs.  The lexical keys are INTEGER token ids, so the dict goes straight into
+        ``VectorDatabase.set_sparse_vector`` (FlagEmbedding's ``lexical_weights`` has the same ids as strings: ``str(k)``)."""
+        return self.extract_embeddings_multi_batch([text])[0]
 
     def extract_embeddings_quant_onnx(self, text):
         raise NotImplementedError("the quantised ONNX model is not available in minivectordb_amd")
