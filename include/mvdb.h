@@ -957,6 +957,54 @@ int mvdb_index_search_hybrid_device(const mvdb_index* idx, const mvdb_sparse* sp
                                     int64_t* I_dev /*[nq,k]*/, void* stream);
 int mvdb_index_sparse_counters(const mvdb_index* idx, long long* calls, long long* score_launches);
 
+/* SPARSE POSTINGS: the opt-in INVERTED form of a sparse store — posting lists by index, resident beside the CSR form — and a
+ * scoring launch that reads only the lists of the query's terms instead of every stored non-zero.  The results are the CSR
+ * pass's, bit for bit: the indices of a stored row are strictly ascending, so "the row's entries in stored order" is
+ * "ascending index", and the posting launch takes the query's terms in ascending index order — for every row the same chain
+ * acc = +0.0; acc = acc + (q[index] * value) in the same order.  Every line of SPARSE VECTORS AND HYBRID SEARCH above holds
+ * unchanged for a store that has postings.
+ * mvdb_sparse_build_postings(idx, sp) builds, on the device, from the resident CSR entries:
+ *   post_ptr [dim + 1] (int64): list t is [post_ptr[t], post_ptr[t + 1]);
+ *   post [nnz + 2]: 8-byte (row: uint32, value: fp32 bits) entries, every list in ascending row order, two padding entries
+ *     behind them;
+ *   and a host copy of post_ptr, taken at the end of the build — the call waits for its stream once, there.
+ *   The layout is the stable transposition of the CSR arrays (np.argsort(indices, kind="stable") applied to the entries): a
+ *   pure function of them, the same bytes from run to run.  The build is an LSD radix sort of (index; row, value), 8 bits a
+ *   pass, every pass stable (one wave ranks sort_lds_entries entries at a time in LDS; the digit table is scanned by a
+ *   multi-block exclusive scan), and post_ptr is a binary search per index over the sorted keys: integer LDS atomics count
+ *   digits, nothing else is atomic.  Limits, checked on the host, MVDB_ERR_ARG: ntotal < 2^32 (the row is 32 bits), dim <=
+ *   max_dim = 2^26 (the directory costs 8 (dim + 1) bytes, 512 MiB at the cap: beyond it create the store with a smaller dim
+ *   or stay on CSR), and the store must be current for idx (the rules of a search).  Device memory: + 8 bytes per non-zero
+ *   + 8 (dim + 1), and 16 bytes per non-zero more while the build runs.  nnz == 0 builds an empty directory and no lists.  A
+ *   second build replaces the first.  No search may run on the store while it is built or dropped.
+ * mvdb_sparse_drop_postings frees them; mvdb_sparse_has_postings: 1 or 0 (0 for NULL).  They go with the store, which is
+ *   outdated by a write under the rules above.
+ * mvdb_sparse_postings_geometry: block_rows (rows a workgroup of the scoring launch owns at a time), sort_lds_entries and
+ *   max_dim of this build (any pointer may be NULL).
+ * mvdb_sparse_postings_read copies the layout back: post_ptr [dim + 1], rows [nnz], values [nnz] (any may be NULL); a store
+ *   without postings is MVDB_ERR_ARG.
+ * Routing: index option "sparse_postings" (mvdb_index_set_option).  1, the default: a store that HAS postings answers
+ *   mvdb_index_sparse_scores, mvdb_index_search_sparse(_device) and the scoring step of mvdb_index_search_hybrid(_device)
+ *   through sparse_postings_kernel; 0: always the CSR pass.  A store without postings behaves as before.  There is no
+ *   fallback by query size.
+ * Launch, sparse_postings_kernel: the host sorts the query's terms by index, drops those whose list is empty (host
+ *   directory) and uploads (list begin, list end, index, value) per term.  A workgroup owns block_rows rows at a time and
+ *   holds their fp32 sums and 16-bit matched counts in LDS; one lane per term finds the part of the term's list inside the
+ *   block by binary search (bounded by the list length) and cuts it at the waves' row quarters; every wave then walks the
+ *   terms in order over its own rows.  No atomics on scores.  Launch counts are the CSR route's.
+ * mvdb_index_sparse_counters keeps its meaning: calls counts searches served by either route, score_launches counts
+ *   sparse_scan_kernel launches only.  mvdb_index_sparse_postings_counters: searches served through the postings,
+ *   sparse_postings_kernel launches enqueued (mvdb_index_sparse_scores' included), and entries — the sum of the list lengths
+ *   of the terms of the queries staged for the posting launch, from the host directory; all counted on the host, any pointer
+ *   may be NULL.
+ * No reference counterpart. */
+int mvdb_sparse_build_postings(const mvdb_index* idx, mvdb_sparse* sp);
+int mvdb_sparse_drop_postings(mvdb_sparse* sp);
+int mvdb_sparse_has_postings(const mvdb_sparse* sp);
+int mvdb_sparse_postings_geometry(int* block_rows, int* sort_lds_entries, long long* max_dim);
+int mvdb_sparse_postings_read(const mvdb_sparse* sp, int64_t* post_ptr_host /*[dim+1]*/, uint32_t* rows_host /*[nnz]*/, float* values_host /*[nnz]*/);
+int mvdb_index_sparse_postings_counters(const mvdb_index* idx, long long* calls, long long* launches, long long* entries);
+
 /* Merge `nlists` sorted top-k lists per query into one [nq,k] result on the device.  List l lives
  * at D_dev + l*list_stride_D (floats, [nq,k]) and I_dev + l*list_stride_I (int64, [nq,k]) — the
  * layout one RCCL all-gather of each rank's packed {I,D} block produces.  Labels must already be

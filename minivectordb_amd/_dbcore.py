@@ -1539,10 +1539,66 @@ class FilterAndRerankMixin:
                 return hit[2]
             indptr, indices, values = self._sparse_csr(self._ids.uids, self._sparse_vectors())
             store = index.sparse(indptr, indices, values, self.__dict__.get("_sparse_dim") or 1)
+            if self.__dict__.get("_sparse_postings"):
+                self._sparse_postings_dim_check(store.dim)
+                store.build_postings()
             # an outdated store is dropped, not freed: a search running outside the lock may still hold it
             self.__dict__["_sparse_store"] = (stamp, index, store)
             self.__dict__["_sparse_builds"] = self.__dict__.get("_sparse_builds", 0) + 1
             return store
+
+    # ---- the inverted form of the resident sparse store: same results, read from the query's posting lists only ----
+    @staticmethod
+    def _sparse_postings_dim_check(dim):
+        from . import _native
+        cap = _native.sparse_postings_geometry()[2]
+        if dim is not None and dim > cap:
+            raise ValueError(f"sparse postings need sparse_dim <= {cap} (it is {dim}): fix a smaller one with set_sparse_dim, "
+                             "or stay without postings (drop_sparse_postings)")
+
+    def build_sparse_postings(self):
+        """From now on every resident sparse store this database assembles also builds its posting lists (include/mvdb.h
+        "SPARSE POSTINGS"), and sparse and hybrid searches score through them: the same ids and scores, element for element,
+        at the cost of the query's lists instead of every stored non-zero.  The first store is assembled at once when
+        sparse vectors exist; after a store, a delete, an update or a ``set_sparse_vector`` the next sparse or hybrid search
+        rebuilds both, once.  Device memory: + 8 bytes per non-zero + 8 (sparse_dim + 1).  Derived state: not persisted.  A
+        ``sparse_dim`` above the cap is a ValueError that names ``set_sparse_dim``.  No reference counterpart."""
+        with self.lock:
+            self._sparse_postings_dim_check(self.__dict__.get("_sparse_dim"))
+            self.__dict__["_sparse_postings"] = True
+            # a store assembled without them is dropped, not rebuilt in place: a search outside the lock may still hold it
+            self.__dict__.pop("_sparse_store", None)
+            if not self._sparse_vectors() or self._mat is None:
+                return
+            if self._embeddings_changed:
+                self._build_index()
+            index = self.index
+        # outside the lock: it is not re-entrant, and _resident_sparse_store takes it itself
+        if index is not None and hasattr(index, "sparse"):
+            try:
+                self._resident_sparse_store(index)
+            except ValueError:
+                pass    # a write from another thread came between: the next sparse or hybrid search assembles the store
+
+    def drop_sparse_postings(self):
+        """Back to the CSR pass: stores assembled from now on build no posting lists, and the resident one is let go."""
+        with self.lock:
+            self.__dict__["_sparse_postings"] = False
+            self.__dict__.pop("_sparse_store", None)
+
+    def sparse_postings_info(self):
+        """``{'enabled', 'built', 'nnz', 'dim', 'bytes'}``: whether ``build_sparse_postings`` is in force, whether the resident
+        sparse store is current and holds its posting lists, and then its non-zeros, its dimension and the lists' device
+        bytes (0 while not built)."""
+        with self.lock:
+            stamp = (self.__dict__.get("_write_gen", 0), self.__dict__.get("_sparse_gen", 0))
+            hit = self.__dict__.get("_sparse_store")
+            built = bool(hit is not None and hit[0] == stamp and hit[1] is self.index and not self._embeddings_changed
+                         and hit[2].has_postings)
+            nnz = hit[2].nnz if built else 0
+            dim = hit[2].dim if built else (self.__dict__.get("_sparse_dim") or 0)
+            return {'enabled': bool(self.__dict__.get("_sparse_postings")), 'built': built, 'nnz': nnz, 'dim': dim,
+                    'bytes': 8 * nnz + 8 * (dim + 1) if built else 0}
 
     def _sparse_save(self, path):
         """The sparse vectors beside the main file (caller holds the lock): written when there are any, a leftover file
@@ -1559,6 +1615,7 @@ class FilterAndRerankMixin:
         """Read what `_sparse_save` wrote (caller holds the lock); entries of ids that are not stored are dropped."""
         self.__dict__["_sparse"] = {}
         self.__dict__.pop("_sparse_store", None)
+        self.__dict__["_sparse_postings"] = False   # derived state: a loaded database starts without posting lists
         self.__dict__["_sparse_gen"] = self.__dict__.get("_sparse_gen", 0) + 1
         if not os.path.exists(path):
             return

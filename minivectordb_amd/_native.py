@@ -218,6 +218,12 @@ PROTOTYPES = {
     "mvdb_index_search_hybrid_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                                        ctypes.c_float, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
     "mvdb_index_sparse_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_sparse_build_postings": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_sparse_drop_postings": (ctypes.c_int, [c_vp]),
+    "mvdb_sparse_has_postings": (ctypes.c_int, [c_vp]),
+    "mvdb_sparse_postings_geometry": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_sparse_postings_read": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_index_sparse_postings_counters": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mvdb_comm_available": (ctypes.c_int, []),
     "mvdb_comm_unique_id": (ctypes.c_int, [c_vp]),
     "mvdb_comm_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
@@ -1169,6 +1175,13 @@ class FlatIndex:
         check(lib().mvdb_index_sparse_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def sparse_postings_counters(self):
+        """(searches served through the postings, sparse_postings_kernel launches enqueued, list entries of the terms of the
+        queries staged for them): running totals counted on the host."""
+        v = [ctypes.c_longlong(0) for _ in range(3)]
+        check(lib().mvdb_index_sparse_postings_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     # ---- probed search: a k-means partition, a query scans the lists of its nprobe best centres (include/mvdb.h "PROBED SEARCH") ----
     def partition(self, centres, labels=None, normalize_c=False):
         """A resident Partition of the stored rows into len(centres) member lists.  labels None: every row is labelled on the
@@ -1330,6 +1343,13 @@ def sparse_geometry():
     return tuple(int(x.value) for x in v)
 
 
+def sparse_postings_geometry():
+    """(block_rows, sort_lds_entries, max_dim) of the sparse postings of this build (mvdb_sparse_postings_geometry)."""
+    b, l, m = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_longlong(0)
+    check(lib().mvdb_sparse_postings_geometry(ctypes.byref(b), ctypes.byref(l), ctypes.byref(m)))
+    return int(b.value), int(l.value), int(m.value)
+
+
 class SparseStore:
     """mvdb_sparse*: one sparse vector per stored row in CSR form, resident on the index's device.  Valid until the index it
     was built on gains or loses a row (updating rows in place keeps it valid); its device memory goes with the last
@@ -1346,6 +1366,7 @@ class SparseStore:
         if len(indptr) > 1 and int(indptr[-1]) > len(indices):
             raise ValueError(f"indptr ends at {int(indptr[-1])}, beyond the {len(indices)} entries")
         self._h = ctypes.c_void_p()
+        self._index = index
         check(lib().mvdb_sparse_create(index._h, _ptr(indptr), _ptr(indices), _ptr(values), len(indptr) - 1, int(dim), ctypes.byref(self._h)))
 
     def __len__(self):
@@ -1358,6 +1379,27 @@ class SparseStore:
     @property
     def dim(self):
         return int(lib().mvdb_sparse_dim(self._h))
+
+    # ---- the inverted form (include/mvdb.h "SPARSE POSTINGS") ----
+    def build_postings(self):
+        """Build the posting lists beside the CSR form, on the device: searches on an index whose option sparse_postings is 1
+        (the default) then score this store through them — the same bits, read from the lists of the query's terms only."""
+        check(lib().mvdb_sparse_build_postings(self._index._h, self._h))
+
+    def drop_postings(self):
+        check(lib().mvdb_sparse_drop_postings(self._h))
+
+    @property
+    def has_postings(self):
+        return bool(lib().mvdb_sparse_has_postings(self._h))
+
+    def postings(self):
+        """(post_ptr int64[dim + 1], rows uint32[nnz], values float32[nnz]): the layout, copied back."""
+        post_ptr = np.empty(self.dim + 1, dtype=np.int64)
+        rows = np.empty(self.nnz, dtype=np.uint32)
+        values = np.empty(self.nnz, dtype=np.float32)
+        check(lib().mvdb_sparse_postings_read(self._h, _ptr(post_ptr), _ptr(rows), _ptr(values)))
+        return post_ptr, rows, values
 
     def free(self):
         if getattr(self, "_h", None) is not None and self._h:

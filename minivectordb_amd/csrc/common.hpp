@@ -164,6 +164,7 @@ struct Knobs {
     int assign_vectors_per_pass = 0;   // index option assign_vectors_per_pass: vectors per corpus pass of an assignment (0: assign_scan.hpp assign_vectors_per_pass)
     int examples_vectors_per_pass = 0; // index option examples_vectors_per_pass: vectors per corpus pass of a search by examples (0: examples_scan.hpp examples_vectors_per_pass)
     long long probe_table_bytes = 256ll << 20;  // index option probe_table_bytes: most bytes of a probed search's item and candidate tables; beyond it the queries go in chunks (mvdb.hip: probe_core)
+    int sparse_postings = 1;           // index option sparse_postings: 1 a sparse store that has postings answers through them (sparse_postings.hpp), 0 always the CSR pass
     int grouped_items_per_cu = 0;      // MVDB_GROUPED_ITEMS_PER_CU: work items per CU the grouped launch aims at (0: the default of mvdb.hip plan_grouped; sweep in DESIGN.md section 6c)
     int grouped_min_batches = 4;       // MVDB_GROUPED_MIN_BATCHES: fewest row batches per wave of a work item
     long long compact_bytes = 512ll << 20;  // MVDB_COMPACT_BYTES: staging buffer of a row compaction (mvdb_index_remove_rows)

@@ -29,6 +29,7 @@
 #include "examples_scan.hpp"
 #include "boost_scan.hpp"
 #include "sparse_scan.hpp"
+#include "sparse_postings.hpp"
 #include "probe_scan.hpp"
 #include "code8_scan.hpp"
 #include "scan_mfma_kernels.hpp"
@@ -636,6 +637,8 @@ struct mvdb_index {
     mutable std::atomic<unsigned long long> bs_calls{0}, bs_launches{0};
     // sparse and hybrid search: searches served and sparse_scan_kernel launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> sp_calls{0}, sp_launches{0};
+    // ... served through the posting lists: searches, sparse_postings_kernel launches, and list entries of the queries' terms
+    mutable std::atomic<unsigned long long> pp_calls{0}, pp_launches{0}, pp_entries{0};
     // probed search: calls served and launches enqueued, both counted on the host
     mutable std::atomic<unsigned long long> pb_calls{0}, pb_launches{0};
     mutable std::shared_mutex mu;  // search: shared; add/reset/remove/free: exclusive
@@ -2617,7 +2620,9 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const int assign_vectors = idx->kn.assign_vectors_per_pass;
     const int examples_vectors = idx->kn.examples_vectors_per_pass;
     const long long probe_table = idx->kn.probe_table_bytes;
+    const int sparse_postings = idx->kn.sparse_postings;
     idx->kn = read_knobs();
+    idx->kn.sparse_postings = sparse_postings;
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
     idx->kn.groups_partials_bytes = groups_partials;
@@ -2699,13 +2704,16 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "probe_table_bytes") {  // budget of a probed search's item and candidate tables: a call above it runs its queries in chunks
         if (value <= 0) return fail(MVDB_ERR_ARG, "probe_table_bytes must be positive");
         idx->kn.probe_table_bytes = value;
+    } else if (n == "sparse_postings") {  // 1: a sparse store that has postings is scored through them, 0: always the CSR pass
+        if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "sparse_postings must be 0 or 1");
+        idx->kn.sparse_postings = (int)value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, sparse_postings, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -6002,6 +6010,11 @@ struct mvdb_sparse {
     SparseEntry* entries = nullptr;  // [nnz + 2] on the device
     int64_t* indptr = nullptr;       // [n + 1]
     int64_t* tiles = nullptr;        // [2 (ntiles + 1)]: the tiles' first rows, then their first entries
+    // the inverted form (sparse_postings.hpp), built on request: mvdb_sparse_build_postings
+    bool has_post = false;
+    PostEntry* post = nullptr;           // [nnz + 2] on the device
+    int64_t* post_ptr = nullptr;         // [dim + 1]
+    std::vector<int64_t> post_ptr_host;  // its host copy: absent terms are dropped and touched entries counted on the host
 };
 
 namespace {
@@ -6097,8 +6110,86 @@ int sparse_grid(const mvdb_index* idx, const mvdb_sparse* sp) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(sp->ntiles, (int64_t)device_cus(idx->device) * kSparseBlocksPerCu));
 }
 
+// ---- the posting route (sparse_postings.hpp): a store that has postings, unless the index option sparse_postings is 0 ----
+bool by_postings(const mvdb_index* idx, const mvdb_sparse* sp) { return sp->has_post && idx->kn.sparse_postings != 0; }
+
+// The queries in the posting route's form to ws->spq, through the pinned staging as stage_sparse_queries: [nq + 1] term offsets,
+// then per query its terms in ascending index order as (list begin, list end, index, value) — a term whose list is empty is
+// dropped here, from the host directory, so a query may keep no term at all.  Counts the list entries of the kept terms.
+size_t posting_query_bytes(const int64_t* q_indptr, int nq) { return (size_t)(nq + 1 + 3 * q_indptr[nq]) * sizeof(uint64_t); }
+int stage_posting_queries(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, size_t pin_off, const int64_t* q_indptr, const int32_t* q_indices,
+                          const float* q_values, int nq) {
+    const int64_t M = q_indptr[nq];
+    const size_t words = (size_t)(nq + 1 + 3 * M);
+    MVDB_TRY(ws->spq.reserve(words));
+    MVDB_TRY(ws->pin.reserve(pin_off + words * sizeof(uint64_t)));
+    char* const st = (char*)ws->pin.p + pin_off;
+    int64_t* const off = reinterpret_cast<int64_t*>(st);
+    PostTerm* const terms = reinterpret_cast<PostTerm*>(st + (size_t)(nq + 1) * sizeof(int64_t));
+    std::vector<std::pair<int32_t, int64_t>> order;  // (index, position in the caller's arrays)
+    int64_t kept = 0;
+    unsigned long long entries = 0;
+    off[0] = 0;
+    for (int i = 0; i < nq; ++i) {
+        order.clear();
+        for (int64_t j = q_indptr[i]; j < q_indptr[i + 1]; ++j) order.emplace_back(q_indices[j], j);
+        std::sort(order.begin(), order.end());
+        for (const auto& o : order) {
+            const int64_t b = sp->post_ptr_host[(size_t)o.first], e = sp->post_ptr_host[(size_t)o.first + 1];
+            if (b == e) continue;
+            PostTerm& t = terms[kept++];
+            t.begin = b;
+            t.end = e;
+            t.index = (uint32_t)o.first;
+            memcpy(&t.value, q_values + o.second, sizeof(float));
+            entries += (unsigned long long)(e - b);
+        }
+        off[i + 1] = kept;
+    }
+    idx->pp_entries += entries;
+    MVDB_HIP(hipMemcpyAsync(ws->spq.p, st, (size_t)(nq + 1 + 3 * kept) * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
+    return 0;
+}
+
+// the queries of a call in the form of the route that will score them
+size_t routed_query_bytes(const mvdb_index* idx, const mvdb_sparse* sp, const int64_t* q_indptr, int nq) {
+    return by_postings(idx, sp) ? posting_query_bytes(q_indptr, nq) : sparse_query_bytes(q_indptr, nq);
+}
+int stage_routed_queries(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, size_t pin_off, const int64_t* q_indptr, const int32_t* q_indices,
+                         const float* q_values, int nq) {
+    if (by_postings(idx, sp)) return stage_posting_queries(idx, sp, ws, pin_off, q_indptr, q_indices, q_values, nq);
+    return stage_sparse_queries(ws, pin_off, q_indptr, q_indices, q_values, nq);
+}
+
+PostingsArgs postings_args(const mvdb_sparse* sp, Workspace* ws, int nq) {
+    PostingsArgs a{};
+    a.post = sp->post;
+    a.n = sp->n;
+    a.nblocks = (sp->n + kPostBlockRows - 1) / kPostBlockRows;
+    a.q_off = reinterpret_cast<const int64_t*>(ws->spq.p);
+    a.q_terms = reinterpret_cast<const PostTerm*>(ws->spq.p + nq + 1);
+    a.weight = 1.0f;
+    return a;
+}
+
+int postings_grid(const mvdb_index* idx, const PostingsArgs& a) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(a.nblocks, (int64_t)device_cus(idx->device) * kPostBlocksPerCu));
+}
+
 // the scoring launch: T[r] = weight * sparse(r) of query `query` of the staged call, for every row (and matched[r], if asked)
 int sparse_column(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, int nq_staged, int query, float weight, float* T, int32_t* matched) {
+    if (by_postings(idx, sp)) {
+        PostingsArgs a = postings_args(sp, ws, nq_staged);
+        a.q_off += query;
+        a.weight = weight;
+        a.T = T;
+        a.matched = matched;
+        hipStream_t s = ws->stream;
+        ++idx->pp_launches;
+        return profiled_launch("sparse_postings", s, [&](hipEvent_t done) {
+            launch_kernel(sparse_postings_kernel<0, 0>, dim3(postings_grid(idx, a)), dim3(kPostThreads), 0, s, done, a);
+        }, "sparse_postings_kernel<0, 0>");
+    }
     SparseScanArgs a = sparse_args(sp, ws, nq_staged);
     a.q_indptr += query;
     a.weight = weight;
@@ -6127,6 +6218,41 @@ int sparse_search_core(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* 
     ++idx->sp_calls;
     if (nothing_selected(idx, rs)) return fill_padding(ws, D_dev, I_dev, (int64_t)nq * k);
     hipStream_t s = ws->stream;
+    if (by_postings(idx, sp)) {
+        ++idx->pp_calls;
+        PostingsArgs a = postings_args(sp, ws, nq);
+        MVDB_TRY(sparse_selector(idx, ws, rs, &a.mask, &a.mask_rows));
+        const int grid = postings_grid(idx, a);
+        const int tile = std::min(nq, kCoreTile);
+        MVDB_TRY(ws->cand.reserve((size_t)tile * grid * k));
+        a.k = k;
+        a.cand = ws->cand.p;
+        for (int q0 = 0; q0 < nq; q0 += tile) {
+            const int take = std::min(tile, nq - q0);
+            PostingsArgs b = a;
+            b.q_off += q0;
+            ++idx->pp_launches;
+            if (a.mask)
+                MVDB_TRY(profiled_launch("sparse_postings", s, [&](hipEvent_t done) {
+                    launch_kernel(sparse_postings_kernel<1, 2>, dim3(grid, take), dim3(kPostThreads), 0, s, done, b);
+                }, "sparse_postings_kernel<1, 2>"));
+            else
+                MVDB_TRY(profiled_launch("sparse_postings", s, [&](hipEvent_t done) {
+                    launch_kernel(sparse_postings_kernel<1, 0>, dim3(grid, take), dim3(kPostThreads), 0, s, done, b);
+                }, "sparse_postings_kernel<1, 0>"));
+            MergeArgs mg;   // the scores are similarities whatever the index's metric
+            mg.keys = ws->cand.p;
+            mg.nlists = grid;
+            mg.k = k;
+            mg.metric = MVDB_METRIC_IP;
+            mg.label_offset = label_offset;
+            mg.D = D_dev + (int64_t)q0 * k;
+            mg.I = I_dev + (int64_t)q0 * k;
+            hipLaunchKernelGGL(merge_keys_kernel, dim3(take), dim3(kMergeThreads), 0, s, mg);
+            MVDB_HIP(hipGetLastError());
+        }
+        return 0;
+    }
     SparseScanArgs a = sparse_args(sp, ws, nq);
     MVDB_TRY(sparse_selector(idx, ws, rs, &a.mask, &a.mask_rows));
     const int grid = sparse_grid(idx, sp);
@@ -6166,6 +6292,7 @@ int hybrid_core(const mvdb_index* idx, const mvdb_sparse* sp, Workspace* ws, con
                 float sparse_weight, const mvdb_rowset* rs, int64_t label_offset, float* D_dev, int64_t* I_dev) {
     ++idx->sp_calls;
     if (nothing_selected(idx, rs)) return fill_padding(ws, D_dev, I_dev, (int64_t)nq * k);
+    if (by_postings(idx, sp)) ++idx->pp_calls;
     MVDB_TRY(ws->bsT.reserve((size_t)idx->n));
     for (int i = 0; i < nq; ++i) {
         MVDB_TRY(sparse_column(idx, sp, ws, nq, i, sparse_weight, ws->bsT.p, nullptr));
@@ -6285,6 +6412,8 @@ int mvdb_sparse_free(mvdb_sparse* sp) {
         if (sp->entries) (void)hipFree(sp->entries);
         if (sp->indptr) (void)hipFree(sp->indptr);
         if (sp->tiles) (void)hipFree(sp->tiles);
+        if (sp->post) (void)hipFree(sp->post);
+        if (sp->post_ptr) (void)hipFree(sp->post_ptr);
     }
     delete sp;
     return 0;
@@ -6294,6 +6423,123 @@ int mvdb_sparse_geometry(int* span_entries, int* tile_rows, int* table_slots) {
     if (span_entries) *span_entries = kSparseSpan;
     if (tile_rows) *tile_rows = kSparseTileRows;
     if (table_slots) *table_slots = kSparseSlots;
+    return 0;
+}
+
+int mvdb_sparse_postings_geometry(int* block_rows, int* sort_lds_entries, long long* max_dim) {
+    if (block_rows) *block_rows = kPostBlockRows;
+    if (sort_lds_entries) *sort_lds_entries = kPostSortSeg;
+    if (max_dim) *max_dim = (long long)kPostMaxDim;
+    return 0;
+}
+
+int mvdb_sparse_drop_postings(mvdb_sparse* sp) {
+    if (!sp) return fail(MVDB_ERR_ARG, "the sparse store is NULL");
+    DeviceGuard dg(sp->device);
+    sp->has_post = false;
+    if (sp->post) (void)hipFree(sp->post);
+    if (sp->post_ptr) (void)hipFree(sp->post_ptr);
+    sp->post = nullptr;
+    sp->post_ptr = nullptr;
+    std::vector<int64_t>().swap(sp->post_ptr_host);
+    return 0;
+}
+
+int mvdb_sparse_has_postings(const mvdb_sparse* sp) { return sp && sp->has_post ? 1 : 0; }
+
+int mvdb_sparse_build_postings(const mvdb_index* idx, mvdb_sparse* sp) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    MVDB_TRY(sparse_check(idx, sp));
+    if (sp->n >= (1ll << 32)) return fail(MVDB_ERR_ARG, "sparse postings: %lld rows, a posting holds its row in 32 bits", (long long)sp->n);
+    if (sp->dim > kPostMaxDim)
+        return fail(MVDB_ERR_ARG, "sparse postings: dim %lld is above %lld (the directory takes 8 (dim + 1) bytes): create the store with a smaller dim",
+                    (long long)sp->dim, (long long)kPostMaxDim);
+    DeviceGuard dg(idx->device);
+    MVDB_TRY(mvdb_sparse_drop_postings(sp));
+    HostCall call(idx);
+    if (!call.ws) return MVDB_ERR_HIP;
+    hipStream_t s = call.ws->stream;
+    const int64_t nnz = sp->nnz, dim = sp->dim;
+    int bits = 0;
+    while (bits < 32 && ((dim - 1) >> bits) != 0) ++bits;
+    const int passes = std::max(1, (bits + kPostRadixBits - 1) / kPostRadixBits);
+    const int64_t nseg = (nnz + kPostSortSeg - 1) / kPostSortSeg;
+    const int64_t N = nseg * kPostRadixDigits;
+    const int64_t nb = (N + kPostScanChunk - 1) / kPostScanChunk;
+    // what the build needs and frees again: both key arrays, the second payload array, the digit table and its block sums
+    DevBuf<uint32_t> keys[2];
+    DevBuf<uint64_t> pay_tmp;
+    DevBuf<int64_t> table, sums;
+    const auto build = [&]() -> int {
+        MVDB_HIP(hipMalloc((void**)&sp->post, (size_t)(nnz + 2) * sizeof(PostEntry)));
+        MVDB_HIP(hipMalloc((void**)&sp->post_ptr, (size_t)(dim + 1) * sizeof(int64_t)));
+        MVDB_HIP(hipMemsetAsync(sp->post + nnz, 0xFF, 2 * sizeof(PostEntry), s));   // the padding: row kPostPadRow
+        if (nnz > 0) {
+            MVDB_TRY(keys[0].reserve((size_t)nnz));
+            MVDB_TRY(keys[1].reserve((size_t)nnz));
+            MVDB_TRY(pay_tmp.reserve((size_t)nnz));
+            MVDB_TRY(table.reserve((size_t)N));
+            MVDB_TRY(sums.reserve((size_t)nb));
+            // the last pass must land in sp->post: an odd number of passes starts from the other payload array
+            PostEntry* pay[2] = {sp->post, reinterpret_cast<PostEntry*>(pay_tmp.p)};
+            int src = passes & 1;
+            hipLaunchKernelGGL(postings_expand_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, (const SparseEntry*)sp->entries,
+                               (const int64_t*)sp->indptr, sp->n, nnz, keys[src].p, pay[src]);
+            MVDB_HIP(hipGetLastError());
+            const unsigned seg_blocks = (unsigned)((nseg + kPostWaves - 1) / kPostWaves);
+            for (int p = 0; p < passes; ++p, src ^= 1) {
+                const int shift = p * kPostRadixBits;
+                hipLaunchKernelGGL(postings_hist_kernel, dim3(seg_blocks), dim3(kPostThreads), 0, s, (const uint32_t*)keys[src].p, nnz, shift, nseg, table.p);
+                hipLaunchKernelGGL(postings_scan_sums_kernel, dim3((unsigned)nb), dim3(kPostThreads), 0, s, (const int64_t*)table.p, N, sums.p);
+                hipLaunchKernelGGL(postings_scan_top_kernel, dim3(1), dim3(kPostThreads), 0, s, sums.p, nb);
+                hipLaunchKernelGGL(postings_scan_apply_kernel, dim3((unsigned)nb), dim3(kPostThreads), 0, s, table.p, N, (const int64_t*)sums.p);
+                hipLaunchKernelGGL(postings_scatter_kernel, dim3(seg_blocks), dim3(kPostThreads), 0, s, (const uint32_t*)keys[src].p,
+                                   (const PostEntry*)pay[src], keys[src ^ 1].p, pay[src ^ 1], nnz, shift, nseg, (const int64_t*)table.p);
+                MVDB_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(postings_directory_kernel, dim3((unsigned)((dim + 1 + 255) / 256)), dim3(256), 0, s, (const uint32_t*)keys[src].p, nnz, dim,
+                               sp->post_ptr);
+            MVDB_HIP(hipGetLastError());
+        } else {
+            MVDB_HIP(hipMemsetAsync(sp->post_ptr, 0, (size_t)(dim + 1) * sizeof(int64_t), s));
+        }
+        sp->post_ptr_host.resize((size_t)dim + 1);
+        MVDB_HIP(hipMemcpyAsync(sp->post_ptr_host.data(), sp->post_ptr, (size_t)(dim + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        MVDB_HIP(hipStreamSynchronize(s));   // the one wait of the build: the host directory is read from here on, the temporaries go
+        return 0;
+    };
+    const int rc = profiled_launch("sparse_postings_build", s, build);
+    if (rc != 0) {
+        (void)hipStreamSynchronize(s);
+        (void)mvdb_sparse_drop_postings(sp);
+        return rc;
+    }
+    sp->has_post = true;
+    return 0;
+}
+
+int mvdb_sparse_postings_read(const mvdb_sparse* sp, int64_t* post_ptr_host, uint32_t* rows_host, float* values_host) {
+    if (!sp) return fail(MVDB_ERR_ARG, "the sparse store is NULL");
+    if (!sp->has_post) return fail(MVDB_ERR_ARG, "the sparse store has no postings (mvdb_sparse_build_postings)");
+    if (post_ptr_host) memcpy(post_ptr_host, sp->post_ptr_host.data(), sp->post_ptr_host.size() * sizeof(int64_t));
+    if ((rows_host || values_host) && sp->nnz > 0) {
+        DeviceGuard dg(sp->device);
+        std::vector<PostEntry> buf((size_t)sp->nnz);
+        MVDB_HIP(hipMemcpy(buf.data(), sp->post, buf.size() * sizeof(PostEntry), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < buf.size(); ++i) {
+            if (rows_host) rows_host[i] = buf[i].row;
+            if (values_host) memcpy(values_host + i, &buf[i].value, sizeof(float));
+        }
+    }
+    return 0;
+}
+
+int mvdb_index_sparse_postings_counters(const mvdb_index* idx, long long* calls, long long* launches, long long* entries) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (calls) *calls = (long long)idx->pp_calls.load();
+    if (launches) *launches = (long long)idx->pp_launches.load();
+    if (entries) *entries = (long long)idx->pp_entries.load();
     return 0;
 }
 
@@ -6311,7 +6557,7 @@ int mvdb_index_sparse_scores(const mvdb_index* idx, const mvdb_sparse* sp, const
     HostCall call(idx);
     if (!call.ws) return MVDB_ERR_HIP;
     Workspace* const ws = call.ws;
-    MVDB_TRY(stage_sparse_queries(ws, 0, q_indptr, q_indices_host, q_values_host, 1));
+    MVDB_TRY(stage_routed_queries(idx, sp, ws, 0, q_indptr, q_indices_host, q_values_host, 1));
     MVDB_TRY(ws->bsT.reserve((size_t)n));
     if (matched_host) MVDB_TRY(ws->spmatched.reserve((size_t)n));
     MVDB_TRY(sparse_column(idx, sp, ws, 1, 0, 1.0f, ws->bsT.p, matched_host ? ws->spmatched.p : nullptr));
@@ -6337,7 +6583,7 @@ int mvdb_index_search_sparse(const mvdb_index* idx, const mvdb_sparse* sp, const
     DeviceGuard dg(idx->device);
     HostCall call(idx);
     if (!call.ws) return MVDB_ERR_HIP;
-    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_TRY(stage_routed_queries(idx, sp, call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
     const size_t total = (size_t)nq * k;
     float* D_dev = nullptr;
     int64_t* I_dev = nullptr;
@@ -6362,7 +6608,7 @@ int mvdb_index_search_sparse_device(const mvdb_index* idx, const mvdb_sparse* sp
     SparseStreamCall call(idx, stream);
     if (!call.ws) return fail(MVDB_ERR_HIP, "workspace allocation failed");
     // the one host wait of this entry point: the staging copy of the queries belongs to the workspace (mvdb_index_search_boosted_device)
-    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_TRY(stage_routed_queries(idx, sp, call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
     MVDB_HIP(hipStreamSynchronize(call.ws->stream));
     return sparse_search_core(idx, sp, call.ws, nq, k, rs, label_offset, D_dev, I_dev);
 }
@@ -6383,9 +6629,9 @@ int mvdb_index_search_hybrid(const mvdb_index* idx, const mvdb_sparse* sp, const
     Workspace* const ws = call.ws;
     // the dense queries and, behind them in the same pinned staging buffer, the sparse ones
     const size_t qbytes = (size_t)nq * idx->ld * sizeof(float);
-    MVDB_TRY(ws->pin.reserve(qbytes + sparse_query_bytes(q_indptr_host, nq)));
+    MVDB_TRY(ws->pin.reserve(qbytes + routed_query_bytes(idx, sp, q_indptr_host, nq)));
     MVDB_TRY(call.stage(q_host, nq));
-    MVDB_TRY(stage_sparse_queries(ws, qbytes, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_TRY(stage_routed_queries(idx, sp, ws, qbytes, q_indptr_host, q_indices_host, q_values_host, nq));
     const size_t total = (size_t)nq * k;
     float* D_dev = nullptr;
     int64_t* I_dev = nullptr;
@@ -6408,7 +6654,7 @@ int mvdb_index_search_hybrid_device(const mvdb_index* idx, const mvdb_sparse* sp
     if (stream_capturing((hipStream_t)stream)) return fail(MVDB_ERR_ARG, "hybrid search cannot be captured into a hipGraph");
     StreamCall call(idx, stream, q_dev, nq);
     MVDB_TRY(call.rc);
-    MVDB_TRY(stage_sparse_queries(call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
+    MVDB_TRY(stage_routed_queries(idx, sp, call.ws, 0, q_indptr_host, q_indices_host, q_values_host, nq));
     MVDB_HIP(hipStreamSynchronize(call.ws->stream));
     return hybrid_core(idx, sp, call.ws, call.q, nq, k, normalize_q, dense_weight, sparse_weight, rs, label_offset, D_dev, I_dev);
 }

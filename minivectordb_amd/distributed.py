@@ -652,6 +652,15 @@ class DistributedShardedVectorDatabase:
     def find_most_similar_hybrid_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_SPARSE)
 
+    def build_sparse_postings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def drop_sparse_postings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def sparse_postings_info(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
     # ---- duplicate-pair search: not across ranks ------------------------------------------------------------------
     _NO_JOIN = ("DistributedShardedVectorDatabase has no duplicate-pair search: the two rows of a pair live on different "
                 "ranks, and results of variable length are not exchanged (use ShardedVectorDatabase on one device)")

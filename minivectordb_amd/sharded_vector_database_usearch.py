@@ -270,6 +270,15 @@ class ShardedVectorDatabaseUsearch(ShardedVectorDatabase):
     def find_most_similar_hybrid_batch(self, *args, **kwargs):
         raise NotImplementedError(self._NO_SPARSE)
 
+    def build_sparse_postings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def drop_sparse_postings(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
+    def sparse_postings_info(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_SPARSE)
+
     # ---- duplicate-pair search: not on the int8 cosine index ---------------------------------------------------------
     _NO_JOIN = ("ShardedVectorDatabaseUsearch keeps int8 codes on the device, not fp32 rows: the duplicate-pair search, a range "
                 "search of stored fp32 rows against each other, is not implemented (use ShardedVectorDatabase)")
