@@ -16,7 +16,16 @@ query vectors.  Device buffers, hipEvents on the current stream, the median of -
       bound_fma_ms         n x d x T FMAs at 64 FMA / clk / CU, the plain fp32 vector rate (--cus, --mhz: 256 CUs at 2400 MHz)
   case "one_group"   every row in group 0, 10M x 512 only, T = 8: every offer of a pass goes to the 8 words of one cache line.
 
-One JSON line per cell, to stdout and to --out (default profiles/maxsim_bench.jsonl)."""
+One JSON line per cell, to stdout and to --out (default profiles/maxsim_bench.jsonl).
+
+--mfma: the scoring pass on the matrix cores (index option maxsim_mfma, csrc/maxsim_mfma.hpp) beside the default pass, same
+process, same index, same device buffers: T = 4, 8, 32, 64, 256 at 1M and 10M x 512 and T = 32 at 10M x 1024, documents of 8
+consecutive rows.  The two settings alternate, --rounds times each (3 warm-up calls and --reps timed calls a time); a cell
+reports the median of its rounds' medians and the rounds themselves.  Out: profiles/maxsim_mfma_bench.jsonl.
+      valu_ms, mfma_ms     the call with maxsim_mfma = 0 / 1;  valu_passes, mfma_passes: corpus passes of one call
+      pass_bytes           bytes one pass reads: n (4 d + 4)
+      mfma_pass_gbs        pass_bytes x mfma_passes / mfma_ms: the whole call over its row bytes (an end-to-end rate)
+      same_groups          both settings return the same k groups in the same order (scores differ in the last bits)"""
 import argparse
 import json
 import os
@@ -33,6 +42,63 @@ from minivectordb_amd import _native  # noqa: E402
 from bench_distinct import launch_ms, timed_events  # noqa: E402
 
 
+def mfma_main(args):
+    k = args.k
+    stream = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(2029)
+    sink = open(args.out, "w")
+    shapes = [(n, 512, [4, 8, 32, 64, 256]) for n in args.rows] + [(max(args.rows), 1024, [32])]
+    for n, d, Ts in shapes:
+        idx = _native.FlatIndex(d)
+        idx.reserve(n)
+        idx.add_synthetic(n, 1234)
+        q = torch.from_numpy(rng.standard_normal((max(Ts), d), dtype=np.float32)).cuda()
+        Dc = torch.empty((1, k), dtype=torch.float32, device="cuda")
+        Ic = torch.empty((1, k), dtype=torch.int64, device="cuda")
+        D = torch.empty((k,), dtype=torch.float32, device="cuda")
+        G = torch.empty((k,), dtype=torch.int32, device="cuda")
+        idx.set_option("code8_single_query", 0)
+        exact_ms = round(timed_events(lambda: idx.search_device(q.data_ptr(), 1, k, Dc.data_ptr(), Ic.data_ptr(), stream=stream,
+                                                                normalize_q=True), args.reps), 4)
+        idx.set_option("code8_single_query", 1)
+        grouping = idx.grouping((np.arange(n, dtype=np.int64) // 8).astype(np.int32), (n + 7) // 8)
+        idx.set_option("maxsim_table_bytes", 4 << 30)   # (256 vectors x 1.25M documents: a table of 2.56 GB, above the default bound)
+        for T in Ts:
+            I_tok = torch.empty((k, T), dtype=torch.int64, device="cuda")
+            D_tok = torch.empty((k, T), dtype=torch.float32, device="cuda")
+
+            def maxsim():
+                idx.search_maxsim_device(q.data_ptr(), T, k, grouping, D.data_ptr(), G.data_ptr(), I_tok.data_ptr(), D_tok.data_ptr(),
+                                         stream=stream, normalize_q=True)
+
+            rounds, passes, groups = {0: [], 1: []}, {}, {}
+            for _ in range(args.rounds):
+                for on in (0, 1):
+                    idx.set_option("maxsim_mfma", on)
+                    (calls0, passes0), mfma0 = idx.maxsim_counters(), idx.maxsim_mfma_passes()
+                    rounds[on].append(round(timed_events(maxsim, args.reps), 4))
+                    torch.cuda.synchronize()
+                    calls1, passes1 = idx.maxsim_counters()
+                    passes[on] = (passes1 - passes0) // (calls1 - calls0)
+                    assert idx.maxsim_mfma_passes() - mfma0 == on * (passes1 - passes0)
+                    groups[on] = G.cpu().numpy().copy()
+            idx.set_option("maxsim_mfma", 0)
+            rec = {"bench": "maxsim_mfma", "n": n, "d": d, "T": T, "k": k, "reps": args.reps, "exact_scan_ms": exact_ms,
+                   "valu_ms": float(np.median(rounds[0])), "mfma_ms": float(np.median(rounds[1])), "valu_rounds": rounds[0],
+                   "mfma_rounds": rounds[1], "valu_passes": int(passes[0]), "mfma_passes": int(passes[1]), "pass_bytes": n * (4 * d + 4)}
+            rec["speedup"] = round(rec["valu_ms"] / rec["mfma_ms"], 3)
+            rec["mfma_over_scans"] = round(rec["mfma_ms"] / (rec["mfma_passes"] * exact_ms), 3)
+            rec["mfma_pass_gbs"] = round(rec["pass_bytes"] * rec["mfma_passes"] / rec["mfma_ms"] / 1e6, 1)
+            rec["same_groups"] = bool(np.array_equal(groups[0], groups[1]))
+            line = json.dumps(rec)
+            print(line, flush=True)
+            sink.write(line + "\n")
+            sink.flush()
+        grouping.free()
+        idx.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[1_000_000, 10_000_000])
@@ -42,8 +108,14 @@ def main():
     ap.add_argument("--cus", type=int, default=256)
     ap.add_argument("--mhz", type=float, default=2400.0)
     ap.add_argument("--adversarial-rows", type=int, default=10_000_000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "maxsim_bench.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--mfma", action="store_true", help="time the matrix-core scoring pass beside the default pass (see the module docstring)")
+    ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "maxsim_mfma_bench.jsonl" if args.mfma else "maxsim_bench.jsonl")
+    if args.mfma:
+        return mfma_main(args)
     d, k = 512, args.k
     stream = torch.cuda.current_stream().cuda_stream
     rng = np.random.default_rng(2029)

@@ -657,6 +657,16 @@ int mvdb_index_groups_counters(const mvdb_index* idx, long long* calls, long lon
  * The device variant follows the contract of mvdb_index_search_distinct_device: no synchronisation, no host read, one call at
  * a time per (index, stream), capturable into a hipGraph after one eager call of the same shape (same grouping, same set).
  * mvdb_index_maxsim_counters: calls served and corpus passes enqueued, both counted on the host.  Either pointer may be NULL.
+ * On the matrix cores.  Index option "maxsim_mfma" (0, the default: everything above; 1): on an index with d % 32 == 0,
+ * d <= 1024 and packed rows (ld == d) the scoring passes run on v_mfma_f32_32x32x2_f32 (maxsim_mfma.hpp), 32 vectors per
+ * pass whatever "maxsim_tokens_per_pass" says, ceil(T / 32) passes; every other index takes the passes above, silently, and
+ * that is the only fallback.  What changes in the contract is the score of a (row, vector): an fp32 dot product in the
+ * matrix instruction's summation order — reproducible run to run, independent of T, of the selection and of the rows around
+ * it, NOT bit-equal to the single-query scan's.  Like every fp32 summation order it obeys
+ * |s - s64| <= (d + 16) 2^-24 sum_i |q^_i x_i| (s64: the exact product of the stored row and the exactly normalised vector;
+ * the 16 covers the fp32 normalisation of q).  NaN never offered, ties to the lower position, -0.0 below +0.0, S by plain
+ * fp32 adds in the order t = 0 .. T-1, the padding and every limit: unchanged.  mvdb_index_maxsim_mfma_passes: the passes
+ * that ran this way (they are counted in mvdb_index_maxsim_counters' passes too); the pointer may be NULL.
  * No reference counterpart. */
 int mvdb_index_search_maxsim(const mvdb_index* idx, const float* q_host /*[T,d]*/, int T, int k, int normalize_q,
                              const mvdb_grouping* grp, const mvdb_rowset* rs, float* D_host /*[k]*/, int32_t* G_host /*[k]*/,
@@ -666,6 +676,7 @@ int mvdb_index_search_maxsim_device(const mvdb_index* idx, const float* q_dev /*
                                     int64_t* I_tok_dev /*[k,T] or NULL*/, float* D_tok_dev /*[k,T] or NULL*/,
                                     int64_t label_offset, void* stream);
 int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long long* passes);
+int mvdb_index_maxsim_mfma_passes(const mvdb_index* idx, int64_t* passes);
 
 /* ASSIGN AND K-MEANS: questions about the WHOLE corpus in terms of C vectors.  mvdb_index_assign labels every stored row with
  * the nearest (largest inner product) of C vectors; mvdb_index_kmeans clusters the rows into C clusters with spherical k-means

@@ -11,6 +11,7 @@ later ``import torch`` does not bring a second HIP runtime into the process.  If
 imported its runtime is loaded; otherwise torch's ``lib/libamdhip64.so`` is pre-loaded by path WITHOUT
 importing torch (a VectorDatabase-only user pays no 1-2 s ``import torch`` on the first query).
 """
+import contextlib
 import ctypes
 import os
 
@@ -172,6 +173,7 @@ PROTOTYPES = {
     "mvdb_index_search_maxsim_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
                                                        c_vp, c_vp, ctypes.c_int64, c_vp]),
     "mvdb_index_maxsim_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_index_maxsim_mfma_passes": (ctypes.c_int, [c_vp, c_vp]),
     "mvdb_index_assign": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_index_assign_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_index_assign_counters": (ctypes.c_int, [c_vp, c_vp, c_vp]),
@@ -449,6 +451,21 @@ class FlatIndex:
         """Per-index switch set in code (include/mvdb.h: mvdb_index_set_option): "shadow_single_query", "half_shadow",
         "compact_bytes"."""
         check(lib().mvdb_index_set_option(self._h, str(name).encode(), int(value)))
+        if name == "maxsim_mfma":
+            self._maxsim_mfma = int(value)  # (the library has no getter: _matrix_cores restores from this)
+
+    @contextlib.contextmanager
+    def _matrix_cores(self, on):
+        """matrix_cores=True of a MaxSim call: index option "maxsim_mfma" at 1 for the call, what it was afterwards."""
+        before = getattr(self, "_maxsim_mfma", 0)
+        if not on or before:
+            yield
+            return
+        self.set_option("maxsim_mfma", 1)
+        try:
+            yield
+        finally:
+            self.set_option("maxsim_mfma", before)
 
     def reload_env(self):
         """Re-read the MVDB_* hooks (the library reads them once, when the index is created)."""
@@ -917,11 +934,12 @@ class FlatIndex:
         return tuple(int(x.value) for x in v)
 
     # ---- MaxSim search: one question of T vectors, a group scores the sum of its per-vector maxima (include/mvdb.h "MAXSIM SEARCH") ----
-    def search_maxsim(self, q, k, grouping, rowset=None, normalize_q=False, with_tokens=True):
+    def search_maxsim(self, q, k, grouping, rowset=None, normalize_q=False, with_tokens=True, matrix_cores=False):
         """(D float32[k], G int32[k], I_tok int64[k, T], D_tok float32[k, T]) for ONE question q[T, d]: the k groups with the
         largest sum over the T vectors of the group's best row for each vector, best first (equal sums: the lower code);
         I_tok[j, t] is the row of group G[j] that answered vector t and D_tok[j, t] its score (both None without
-        with_tokens).  Fewer than k groups end in -FLT_MAX / -1 / -1 / -FLT_MAX."""
+        with_tokens).  Fewer than k groups end in -FLT_MAX / -1 / -1 / -FLT_MAX.  matrix_cores: the scoring pass on the
+        matrix cores for this call (index option "maxsim_mfma"; scores in the matrix instruction's summation order)."""
         q = np.ascontiguousarray(np.asarray(q, dtype=np.float32))
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"a MaxSim question is a [T, {self.d}] array (got shape {q.shape})")
@@ -930,26 +948,34 @@ class FlatIndex:
         G = np.empty(max(k, 0), dtype=np.int32)
         I_tok = np.empty((max(k, 0), T), dtype=np.int64) if with_tokens else None
         D_tok = np.empty((max(k, 0), T), dtype=np.float32) if with_tokens else None
-        check(lib().mvdb_index_search_maxsim(self._h, _ptr(q), T, k, int(bool(normalize_q)), grouping._h,
-                                             rowset._h if rowset is not None else None, _ptr(D), _ptr(G),
-                                             _ptr(I_tok) if with_tokens else None, _ptr(D_tok) if with_tokens else None))
+        with self._matrix_cores(matrix_cores):
+            check(lib().mvdb_index_search_maxsim(self._h, _ptr(q), T, k, int(bool(normalize_q)), grouping._h,
+                                                 rowset._h if rowset is not None else None, _ptr(D), _ptr(G),
+                                                 _ptr(I_tok) if with_tokens else None, _ptr(D_tok) if with_tokens else None))
         return D, G, I_tok, D_tok
 
     def search_maxsim_device(self, q_ptr, T, k, grouping, D_ptr, G_ptr, I_tok_ptr=0, D_tok_ptr=0, rowset=None, stream=0,
-                             normalize_q=False, label_offset=0):
+                             normalize_q=False, label_offset=0, matrix_cores=False):
         """Device-pointer variant of search_maxsim (I_tok: row numbers + label_offset; a 0 pointer: that output is not
         written); enqueues on `stream` and returns."""
-        check(lib().mvdb_index_search_maxsim_device(
-            self._h, ctypes.c_void_p(q_ptr), int(T), int(k), int(bool(normalize_q)), grouping._h,
-            rowset._h if rowset is not None else None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(G_ptr),
-            ctypes.c_void_p(I_tok_ptr) if I_tok_ptr else None, ctypes.c_void_p(D_tok_ptr) if D_tok_ptr else None,
-            int(label_offset), ctypes.c_void_p(stream)))
+        with self._matrix_cores(matrix_cores):
+            check(lib().mvdb_index_search_maxsim_device(
+                self._h, ctypes.c_void_p(q_ptr), int(T), int(k), int(bool(normalize_q)), grouping._h,
+                rowset._h if rowset is not None else None, ctypes.c_void_p(D_ptr), ctypes.c_void_p(G_ptr),
+                ctypes.c_void_p(I_tok_ptr) if I_tok_ptr else None, ctypes.c_void_p(D_tok_ptr) if D_tok_ptr else None,
+                int(label_offset), ctypes.c_void_p(stream)))
 
     def maxsim_counters(self):
         """(MaxSim searches served, corpus passes they enqueued): running totals counted on the host."""
         v = [ctypes.c_longlong(0) for _ in range(2)]
         check(lib().mvdb_index_maxsim_counters(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def maxsim_mfma_passes(self):
+        """Corpus passes of MaxSim searches that ran on the matrix cores (of maxsim_counters' passes): a running total."""
+        v = ctypes.c_int64(0)
+        check(lib().mvdb_index_maxsim_mfma_passes(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     # ---- assignment and k-means: every stored row labelled by the nearest of C vectors (include/mvdb.h "ASSIGN AND K-MEANS") ----
     def _centres(self, c):

@@ -161,6 +161,7 @@ struct Knobs {
     long long groups_partials_bytes = 64ll << 20;  // index option groups_partials_bytes: budget of the group hits search's block lists (mvdb.hip: groups_core)
     long long maxsim_table_bytes = 2ll << 30;  // index option maxsim_table_bytes: most bytes of a MaxSim search's table, T x n_groups x 8 (mvdb.hip: check_maxsim_state)
     int maxsim_tokens_per_pass = 0;    // index option maxsim_tokens_per_pass: query vectors per corpus pass of a MaxSim search (0: maxsim_scan.hpp maxsim_tokens_per_pass)
+    int maxsim_mfma = 0;               // index option maxsim_mfma: 1 the scoring pass of a MaxSim search runs on the matrix cores where the width allows (maxsim_mfma.hpp), 0 never
     int assign_vectors_per_pass = 0;   // index option assign_vectors_per_pass: vectors per corpus pass of an assignment (0: assign_scan.hpp assign_vectors_per_pass)
     int examples_vectors_per_pass = 0; // index option examples_vectors_per_pass: vectors per corpus pass of a search by examples (0: examples_scan.hpp examples_vectors_per_pass)
     long long probe_table_bytes = 256ll << 20;  // index option probe_table_bytes: most bytes of a probed search's item and candidate tables; beyond it the queries go in chunks (mvdb.hip: probe_core)

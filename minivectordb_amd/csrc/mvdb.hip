@@ -24,6 +24,7 @@
 #include "mmr_select.hpp"
 #include "distinct_select.hpp"
 #include "group_hits.hpp"
+#include "maxsim_mfma.hpp"
 #include "maxsim_scan.hpp"
 #include "assign_scan.hpp"
 #include "examples_scan.hpp"
@@ -628,7 +629,7 @@ struct mvdb_index {
     mutable MirroredCounter gh_ctr;
     mutable std::atomic<unsigned long long> gh_calls{0};
     // MaxSim search: calls served and corpus passes enqueued, both counted on the host
-    mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0};
+    mutable std::atomic<unsigned long long> mx_calls{0}, mx_passes{0}, mx_mfma_passes{0};  // (mx_mfma_passes: those of mx_passes on the matrix cores)
     // assignment (and the assignments of k-means): calls served and corpus passes enqueued, both counted on the host
     mutable std::atomic<unsigned long long> as_calls{0}, as_passes{0};
     // search by examples: calls served and corpus passes enqueued, both counted on the host
@@ -2621,8 +2622,10 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const int examples_vectors = idx->kn.examples_vectors_per_pass;
     const long long probe_table = idx->kn.probe_table_bytes;
     const int sparse_postings = idx->kn.sparse_postings;
+    const int maxsim_mfma = idx->kn.maxsim_mfma;
     idx->kn = read_knobs();
     idx->kn.sparse_postings = sparse_postings;
+    idx->kn.maxsim_mfma = maxsim_mfma;
     idx->kn.distinct_table_bytes = distinct_table;
     idx->kn.maxsim_table_bytes = maxsim_table;
     idx->kn.groups_partials_bytes = groups_partials;
@@ -2704,6 +2707,9 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "probe_table_bytes") {  // budget of a probed search's item and candidate tables: a call above it runs its queries in chunks
         if (value <= 0) return fail(MVDB_ERR_ARG, "probe_table_bytes must be positive");
         idx->kn.probe_table_bytes = value;
+    } else if (n == "maxsim_mfma") {  // 1: the scoring pass of a MaxSim search on the matrix cores where the width allows (maxsim_mfma.hpp), 0: never
+        if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "maxsim_mfma must be 0 or 1");
+        idx->kn.maxsim_mfma = (int)value;
     } else if (n == "sparse_postings") {  // 1: a sparse store that has postings is scored through them, 0: always the CSR pass
         if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "sparse_postings must be 0 or 1");
         idx->kn.sparse_postings = (int)value;
@@ -2713,7 +2719,7 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, sparse_postings, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, maxsim_mfma, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, sparse_postings, half_shadow, compact_bytes)", name);
     return 0;
 }
 
@@ -2798,6 +2804,11 @@ int mvdb_index_maxsim_counters(const mvdb_index* idx, long long* calls, long lon
     if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
     if (calls) *calls = (long long)idx->mx_calls.load();
     if (passes) *passes = (long long)idx->mx_passes.load();
+    return 0;
+}
+int mvdb_index_maxsim_mfma_passes(const mvdb_index* idx, int64_t* passes) {
+    if (!idx) return fail(MVDB_ERR_ARG, "index is NULL");
+    if (passes) *passes = (int64_t)idx->mx_mfma_passes.load();
     return 0;
 }
 int mvdb_index_assign_counters(const mvdb_index* idx, long long* calls, long long* passes) {
@@ -4831,7 +4842,9 @@ int maxsim_core(const mvdb_index* idx, Workspace* ws, const float* q, int T, int
     const int nlists = (int)std::max<int64_t>(1, std::min<int64_t>((ng + kDistinctThreads - 1) / kDistinctThreads, kMaxsimLists));
     MVDB_TRY(ws->mxtab.reserve((size_t)words));
     MVDB_TRY(ws->mxpart.reserve((size_t)nlists * kWave));
-    const int Tp = maxsim_tokens_per_pass(T, idx->ld, idx->kn.maxsim_tokens_per_pass);
+    // on the matrix cores (index option maxsim_mfma) where the width allows: 32 vectors a pass, whatever maxsim_tokens_per_pass says
+    const bool mfma = idx->kn.maxsim_mfma != 0 && maxsim_mfma_width_ok(idx->d, idx->ld);
+    const int Tp = mfma ? kMaxsimMfmaTokens : maxsim_tokens_per_pass(T, idx->ld, idx->kn.maxsim_tokens_per_pass);
 
     const int clear_gx = (int)std::max<int64_t>(1, std::min<int64_t>((words + 2047) / 2048, 2048));
     // (the clear runs under the scan's label, as a record of its own: it names no symbol)
@@ -4851,7 +4864,15 @@ int maxsim_core(const mvdb_index* idx, Workspace* ws, const float* q, int T, int
         a.q = q + (int64_t)v0 * idx->ld;
         a.Tp = std::min(Tp, T - v0);
         a.table = ws->mxtab.p + v0;
-        MVDB_TRY(launch_maxsim(a, idx->device, s));
+        if (mfma) {
+            MaxsimMfmaArgs b;
+            b.X = a.X, b.n = a.n, b.ld = a.ld, b.d4 = a.d4, b.q = a.q, b.Tp = a.Tp, b.normalize_q = a.normalize_q;
+            b.rows = a.rows, b.mask = a.mask, b.codes = a.codes, b.table = a.table, b.T = a.T;
+            MVDB_TRY(launch_maxsim_mfma(b, idx->device, device_lds_per_block(idx->device), s));
+            ++idx->mx_mfma_passes;
+        } else {
+            MVDB_TRY(launch_maxsim(a, idx->device, s));
+        }
         ++idx->mx_passes;
     }
 
