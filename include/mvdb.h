@@ -1273,6 +1273,45 @@ typedef struct mvdb_m3_out {
 int mvdb_encoder_forward_multi_device(mvdb_encoder* enc, const int32_t* ids_dev, const int32_t* mask_dev, int B, int S,
                                       int compute, float* dense_out_dev, const mvdb_m3_out* out, void* stream);
 
+/* ---- SPLADE: learned sparse vectors from the masked-language-model head (csrc/splade_head.hpp) ----
+ * With x[p,:] the last hidden state of valid token p, for every sentence b and vocabulary entry v
+ *   t[p,:] = LayerNorm(gelu(transform_w x[p,:] + transform_b)) (ln_g, ln_b; the encoder's ln_eps, erf-GELU)
+ *   z[p,v] = decoder_w[v,:] . t[p,:] + decoder_b[v]
+ *   w[b,v] = max over the valid tokens p of b of log(1 + relu(z[p,v]))        (a sentence without tokens: all 0)
+ * V = the encoder's vocab_size.  The transform runs in the call's compute mode.  THE VOCABULARY PRODUCT IS ALWAYS THE
+ * SPLIT-PRECISION FORM (fp16 x 3 on the 16-bit matrix cores, fp32 accumulate, 2^-22 per operand), whatever `compute` says.  The
+ * [tokens, V] logits are never written: the maximum is taken in the product's epilogue and merged by an unsigned-integer
+ * atomicMax on the weights' bits (w >= 0: bit order = value order; maximum is associative and commutative) — the same bits
+ * run to run, no floating-point atomic.  A logit of a valid token that is not finite ORs 1 into the overflow word (the pooled
+ * row's protocol); a NaN logit makes w[b,v] NaN, which the pruning drops.
+ *
+ * mvdb_encoder_set_mlm_head keeps the pointers (device, fp32, 16-byte aligned; the caller owns the memory) and builds the
+ * resident fp16 images of decoder_w and transform_w (it waits for the device); NULL removes the head.  decoder_w NULL: tied to
+ * the word embeddings of the weight table.  Needs hidden % 32 == 0.  unused_ids: at most 8 ids that never get a weight. */
+typedef struct mvdb_mlm_head {
+    const float* transform_w;  /* [H,H] nn.Linear layout */
+    const float* transform_b;  /* [H] */
+    const float* ln_g;         /* [H] */
+    const float* ln_b;         /* [H] */
+    const float* decoder_w;    /* [V,H], or NULL = the word embeddings */
+    const float* decoder_b;    /* [V] */
+    int n_unused;
+    int unused_ids[8];
+} mvdb_mlm_head;
+int mvdb_encoder_set_mlm_head(mvdb_encoder* enc, const mvdb_mlm_head* head);
+
+/* One forward, then the head.  Per sentence the max_terms largest weights that are > 0 and whose id is not an unused id (equal
+ * weights: the lower id), by ascending id: count_dev [B], indices_dev / values_dev [B,max_terms], 0 behind the count.
+ * weights_dev: NULL, or [B,V] for the unpruned weights; dense_out_dev: NULL, or [B,H] for the pooled row.  count_dev, indices_dev
+ * and values_dev go together; all three NULL (weights_dev alone) skips the lists.  The contract of
+ * mvdb_encoder_forward_multi_device: per-op kernels on one lane as plain launches on `stream`, no synchronisation, nothing
+ * allocated once the workspace has the size.  The [B,V] bits live in the encoder's workspace; a call whose buffer would pass
+ * 256 MiB runs its sentences in chunks.  MVDB_ERR_ARG, before anything is enqueued: no head set; max_terms outside [1, 1024];
+ * the lists asked for in part; no output asked for at all. */
+int mvdb_encoder_forward_splade_device(mvdb_encoder* enc, const int32_t* ids_dev, const int32_t* mask_dev, int B, int S,
+                                       int compute, float* dense_out_dev, int max_terms, float* weights_dev, int32_t* count_dev,
+                                       int32_t* indices_dev, float* values_dev, void* stream);
+
 /* 1 when a forward of B x S token slots is of the shape the ONE layer-walking launch serves (csrc/encoder_walk.hpp: at most 64
  * token slots — one sentence per call is the reference's only shape, embedding_model.py:62-71; beyond 64 slots the per-op kernels
  * are faster since round 6 —, exact fp32 matrix cores whatever `compute` says), 0 when it runs the per-op kernels.

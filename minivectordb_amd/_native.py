@@ -66,6 +66,20 @@ class M3Heads(ctypes.Structure):
     ]
 
 
+class MlmHead(ctypes.Structure):
+    """mirror of mvdb_mlm_head"""
+    _fields_ = [
+        ("transform_w", ctypes.c_void_p),
+        ("transform_b", ctypes.c_void_p),
+        ("ln_g", ctypes.c_void_p),
+        ("ln_b", ctypes.c_void_p),
+        ("decoder_w", ctypes.c_void_p),
+        ("decoder_b", ctypes.c_void_p),
+        ("n_unused", ctypes.c_int),
+        ("unused_ids", ctypes.c_int * 8),
+    ]
+
+
 class M3Out(ctypes.Structure):
     """mirror of mvdb_m3_out"""
     _fields_ = [
@@ -288,6 +302,9 @@ PROTOTYPES = {
     "mvdb_encoder_set_heads": (ctypes.c_int, [c_vp, ctypes.POINTER(M3Heads)]),
     "mvdb_encoder_forward_multi_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                                          ctypes.POINTER(M3Out), c_vp]),
+    "mvdb_encoder_set_mlm_head": (ctypes.c_int, [c_vp, ctypes.POINTER(MlmHead)]),
+    "mvdb_encoder_forward_splade_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                                          ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -2413,6 +2413,8 @@ __global__ void concat3_kernel(const float* a, const float* b, const float* c, i
     }
 }
 
+#include "splade_head.hpp"  // SPLADE: the MLM head's vocabulary product fused with the per-sentence maximum, and the pruning
+
 struct LayerW {
     const float *wqkv, *bqkv;  // fused (library owned)
     const float *wo, *bo, *ln1g, *ln1b, *w1, *b1, *w2, *b2, *ln2g, *ln2b;
@@ -2472,6 +2474,8 @@ struct EncoderKnobs {
     // the forward
     int split = env_raw_int("MVDB_ENCODER_SPLIT", 1);              // 0: never two lanes
     bool graph = env_not0("MVDB_ENCODER_GRAPH");                   // 0: plain launches
+    // SPLADE's [sentences, V] buffer: the sentences of a call run in chunks that keep it within this many KiB (256 MiB)
+    int splade_buf_kib = std::max(1, env_int("MVDB_SPLADE_BUF_KIB", 256 * 1024));
     // the layer-walking launch
     bool walk = env_not0("MVDB_ENCODER_WALK");                     // 0: the per-op kernels
     bool walk_roles = env_not0("MVDB_WALK_ROLES");                 // 0: every phase based at workgroup 0, the form before role placement
@@ -2547,6 +2551,14 @@ struct mvdb_encoder {
     mvdb_m3_heads heads{};
     _Float16* colbert_p = nullptr;             // compute = 2: the (hi | lo) image of colbert_w (ensure_x3_weights) and 1 / its scale
     float colbert_is = 1.f;
+    // SPLADE's head (mvdb_encoder_set_mlm_head; splade_head.hpp): the caller's pointers, the (hi | lo) images of the decoder
+    // matrix and of transform_w (built once per set_mlm_head) and the [sentences of a chunk, V] buffer of weight bits
+    bool have_mlm = false;
+    mvdb_mlm_head mlm{};
+    _Float16 *mlm_dec_p = nullptr, *mlm_tw_p = nullptr;
+    float mlm_dec_is = 1.f, mlm_tw_is = 1.f;
+    unsigned int* splade_buf = nullptr;
+    int64_t splade_cap = 0;                    // words
     PinnedBuf walk_pin;                        // host entry of the walking launch: [ids | mask | out] in ONE host-mapped buffer
     hipEvent_t walk_done = nullptr;            // recorded behind every forward of the device entry: the next one — on whatever
                                                // stream — waits for it (forwards share the staging buffers, the workspace and the
@@ -3471,10 +3483,68 @@ int enqueue_m3_heads(const LaneCall& c, const int32_t* ids, const mvdb_m3_out& o
     return 0;
 }
 
+// SPLADE's head behind the last layer, on the packed token states (splade_head.hpp).  The transform: the forward's own GEMM
+// launchers with the GELU epilogue into w.ffn, then the LayerNorm into w.ctx (both free behind the last layer) — ln_kernel on
+// the fp32 rows of the exact mode, splade_ln_image_kernel on the image the split-precision epilogue writes.  Then, per chunk of
+// sentences whose [sentences, V] bits fit the buffer: clear (a kernel node), splade_vocab_max_kernel, splade_prune_kernel.
+struct SpladeOut {
+    int max_terms;
+    float* weights;    // [B, V] or NULL
+    int32_t* count;    // [B] or NULL (then no lists)
+    int32_t* indices;  // [B, max_terms]
+    float* values;
+};
+int64_t splade_chunk_sentences(const mvdb_encoder* e, int B) {
+    const int64_t words = ((int64_t)e->kn.splade_buf_kib << 10) / 4;
+    return std::min<int64_t>(B, std::max<int64_t>(1, words / e->cfg.vocab_size));
+}
+int enqueue_splade_head(const LaneCall& c, const SpladeOut& o) {
+    mvdb_encoder* e = c.e;
+    const mvdb_mlm_head& hd = e->mlm;
+    const int H = e->cfg.hidden, V = e->cfg.vocab_size;
+    const Gemm g{c.compute == 2 ? c.xp : c.w.x, hd.transform_w, e->mlm_tw_p, e->mlm_tw_is, hd.transform_b, nullptr, c.w.ffn, H, H};
+    if (c.compute == 2) MVDB_TRY(launch_gemm_x3<EPI_BIAS_GELU>("enc_splade_transform", c, g));
+    else launch_gemm<EPI_BIAS_GELU>("enc_splade_transform", c, g);
+    with_vpt((H + 63) / 64, [&](auto vpt) {
+        constexpr int VPT = decltype(vpt)::value;
+        const dim3 grid((unsigned)((c.Tmax + 3) / 4));
+        if (c.compute == 2)
+            enqueue("enc_splade_ln", kname("splade_ln_image_kernel<%d>", VPT), splade_ln_image_kernel<VPT>, grid, 256, 0, c.s,
+                    reinterpret_cast<const _Float16*>(c.w.ffn), c.w.seq_start, c.B, hd.ln_g, hd.ln_b, e->cfg.ln_eps, H, c.w.ctx);
+        else
+            enqueue("enc_splade_ln", kname("ln_kernel<%d, false>", VPT), ln_kernel<VPT, false>, grid, 256, 0, c.s, c.w.ffn, c.w.seq_start, c.B,
+                    hd.ln_g, hd.ln_b, e->cfg.ln_eps, H, c.w.ctx, nullptr);
+    });
+    MVDB_TRY(ensure_dynamic_lds((const void*)splade_vocab_max_kernel, SV_LDS, e->device));
+    SpladeUnused unused{};
+    unused.n = hd.n_unused;
+    for (int i = 0; i < hd.n_unused; ++i) unused.id[i] = hd.unused_ids[i];
+    const int ncols = (V + SV_BN - 1) / SV_BN;
+    const int64_t chunk = splade_chunk_sentences(e, c.B);
+    for (int64_t b0 = 0; b0 < c.B; b0 += chunk) {
+        const int nb = (int)std::min<int64_t>(chunk, c.B - b0);
+        const int64_t words = (int64_t)nb * V;
+        const int nbands = (int)(((int64_t)nb * c.S + SV_BM - 1) / SV_BM);
+        enqueue("enc_splade_clear", kname("splade_zero_kernel"), splade_zero_kernel, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)),
+                256, 0, c.s, e->splade_buf, words);
+        enqueue("enc_splade_vocab", kname("splade_vocab_max_kernel"), splade_vocab_max_kernel, dim3((unsigned)((int64_t)nbands * ncols)), 256, SV_LDS,
+                c.s, c.w.ctx, e->mlm_dec_p, e->mlm_dec_is, hd.decoder_b, c.w.seq_start, (int)b0, (int)b0 + nb, H, V, nbands, ncols, e->splade_buf,
+                e->overflow_flag);
+        if (o.count)
+            enqueue("enc_splade_prune", kname("splade_prune_kernel"), splade_prune_kernel, dim3(nb), 256, 0, c.s, e->splade_buf, V, o.max_terms,
+                    unused, o.count + b0, o.indices + b0 * o.max_terms, o.values + b0 * o.max_terms, o.weights ? o.weights + b0 * V : nullptr);
+        else  // the unpruned weights alone
+            MVDB_HIP(hipMemcpyAsync(o.weights + b0 * V, e->splade_buf, (size_t)words * 4, hipMemcpyDeviceToDevice, c.s));
+    }
+    return 0;
+}
+
 // Enqueue every kernel of one forward on `s` (no allocation, no host sync: capturable in a hipGraph).
 // m3: the outputs of BGE-M3's heads wanted beside the pooled row (mvdb_encoder_forward_multi_device), or NULL.
+// sp: SPLADE's outputs (mvdb_encoder_forward_splade_device), or NULL.
 int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, const int32_t* mask, int B, int S,
-                 int compute, float* out, float* hidden, hipStream_t s, bool clear_flag = false, const mvdb_m3_out* m3 = nullptr) {
+                 int compute, float* out, float* hidden, hipStream_t s, bool clear_flag = false, const mvdb_m3_out* m3 = nullptr,
+                 const SpladeOut* sp = nullptr) {
     const mvdb_encoder_cfg& cfg = e->cfg;
     const EncoderKnobs& kn = e->kn;
     const int H = cfg.hidden, F = cfg.intermediate;
@@ -3533,6 +3603,7 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
         enqueue("enc_hidden", kname("unpack_hidden_kernel"), unpack_hidden_kernel, dim3((unsigned)Tmax), 256, 0, s, w.x, w.rank, w.seq_start, S, H,
                 hidden);
     if (m3) MVDB_TRY(enqueue_m3_heads(c, ids, *m3));
+    if (sp) MVDB_TRY(enqueue_splade_head(c, *sp));
     MVDB_HIP(hipGetLastError());
     return 0;
 }
@@ -3543,9 +3614,9 @@ int enqueue_lane(mvdb_encoder* e, mvdb_encoder::Lane& w, const int32_t* ids, con
 // tails and attention run beside the other's GEMMs.  Measured (B = 256): S = 512 63.3 vs 65.4 ms, ragged 40.6 vs
 // 43.9 ms; at S = 32 (T = 8192) it gains nothing (4.09 vs 4.06 ms) and costs 6 % on a ragged batch: not used there.
 int enqueue_forward(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B, int S, int compute,
-                    float* out, float* hidden, hipStream_t s, const mvdb_m3_out* m3 = nullptr) {
-    const bool split = !m3 && e->kn.split && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;  // (the heads: one lane)
-    if (!split) return enqueue_lane(e, e->lane[0], ids, mask, B, S, compute, out, hidden, s, true, m3);  // (clears the overflow word)
+                    float* out, float* hidden, hipStream_t s, const mvdb_m3_out* m3 = nullptr, const SpladeOut* sp = nullptr) {
+    const bool split = !m3 && !sp && e->kn.split && s && compute == 0 && B >= 64 && (int64_t)B * S >= 32768 && e->stream2;  // (the heads: one lane)
+    if (!split) return enqueue_lane(e, e->lane[0], ids, mask, B, S, compute, out, hidden, s, true, m3, sp);  // (clears the overflow word)
     MVDB_HIP(hipMemsetAsync(e->overflow_flag, 0, sizeof(unsigned int), s));  // (a memset node of the captured graph)
     const int b0 = B / 2, b1 = B - b0;
     const int H = e->cfg.hidden;
@@ -3563,7 +3634,8 @@ int enqueue_forward(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, in
 // and then releases the device's gate (when *walked comes back true); 2 = the same, the gate released by a host callback
 // behind the launch (the device entry never waits).
 int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B, int S, int compute,
-                 float* out, float* hidden, hipStream_t s, int walk_mode = 0, bool* walked = nullptr, const mvdb_m3_out* m3 = nullptr) {
+                 float* out, float* hidden, hipStream_t s, int walk_mode = 0, bool* walked = nullptr, const mvdb_m3_out* m3 = nullptr,
+                 const SpladeOut* sp = nullptr) {
     if (walked) *walked = false;
     if (compute != 0 && compute != 2)
         return fail(MVDB_ERR_ARG, "unknown compute mode %d (0 = exact-fp32 MFMA, 2 = split-precision fp16 x 3; 1, the single-bf16-product "
@@ -3624,7 +3696,7 @@ int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B
     const bool outer_capture = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
     int pslot = outer_capture ? -1 : prof_begin("encoder", s);
     int rc = 0;
-    if (use_graph && !hidden && !m3 && s && !outer_capture) {  // (the heads' outputs, like `hidden`: plain launches — DESIGN.md 6r)
+    if (use_graph && !hidden && !m3 && !sp && s && !outer_capture) {  // (the heads' outputs, like `hidden`: plain launches — DESIGN.md 6r)
         const GraphKey key{B, S, compute, ids, mask, out};
         auto it = e->graphs.find(key);
         if (it == e->graphs.end()) {
@@ -3650,7 +3722,7 @@ int forward_core(mvdb_encoder* e, const int32_t* ids, const int32_t* mask, int B
         }
         MVDB_HIP(hipGraphLaunch(it->second, s));
     } else {
-        rc = enqueue_forward(e, ids, mask, B, S, compute, out, hidden, s, m3);
+        rc = enqueue_forward(e, ids, mask, B, S, compute, out, hidden, s, m3, sp);
     }
     prof_end(pslot, s);
     return rc;
@@ -3822,6 +3894,9 @@ int mvdb_encoder_free(mvdb_encoder* e) {
         if (e->walk_aborts) (void)hipFree(e->walk_aborts);
         if (e->walk_aborts_host) (void)hipHostFree(e->walk_aborts_host);
         if (e->colbert_p) (void)hipFree(e->colbert_p);
+        void* mlm_bufs[] = {e->mlm_dec_p, e->mlm_tw_p, e->splade_buf};
+        for (void* p : mlm_bufs)
+            if (p) (void)hipFree(p);
         e->walk_pin.release();
     }
     delete e;
@@ -3932,6 +4007,87 @@ int mvdb_encoder_forward_multi_device(mvdb_encoder* e, const int32_t* ids_dev, c
     }
     // always the per-op kernels (walk_mode 0), one lane, plain launches
     MVDB_TRY(forward_core(e, ids_dev, mask_dev, B, S, compute, dense_out_dev, nullptr, s, 0, nullptr, &o));
+    if (ordered) MVDB_HIP(hipEventRecord(e->walk_done, s));
+    return 0;
+}
+
+int mvdb_encoder_set_mlm_head(mvdb_encoder* e, const mvdb_mlm_head* head) {
+    if (!e) return fail(MVDB_ERR_ARG, "encoder is NULL");
+    if (head) {
+        if (!head->transform_w || !head->transform_b || !head->ln_g || !head->ln_b || !head->decoder_b)
+            return fail(MVDB_ERR_ARG, "transform_w / transform_b / ln_g / ln_b / decoder_b is NULL");
+        const void* ptrs[] = {head->transform_w, head->transform_b, head->ln_g, head->ln_b, head->decoder_w};
+        for (const void* p : ptrs)
+            if ((uintptr_t)p % 16) return fail(MVDB_ERR_ARG, "the MLM head's tensors must be 16-byte aligned");
+        if (head->n_unused < 0 || head->n_unused > kSpladeMaxUnused)
+            return fail(MVDB_ERR_ARG, "n_unused %d outside [0, %d]", head->n_unused, kSpladeMaxUnused);
+        if (e->cfg.hidden % HBK) return fail(MVDB_ERR_ARG, "the MLM head needs hidden to be a multiple of %d", HBK);
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard dg(e->device);
+    MVDB_HIP(hipDeviceSynchronize());  // (a forward may still read the old images)
+    if (e->mlm_dec_p) (void)hipFree(e->mlm_dec_p);
+    if (e->mlm_tw_p) (void)hipFree(e->mlm_tw_p);
+    e->mlm_dec_p = e->mlm_tw_p = nullptr;
+    e->have_mlm = false;
+    e->mlm = head ? *head : mvdb_mlm_head{};
+    if (!head) return 0;
+    // the resident (hi | lo) images: the decoder matrix (tied: the word embeddings) and transform_w, once per set_mlm_head
+    const int64_t H = e->cfg.hidden, V = e->cfg.vocab_size;
+    unsigned int* scratch = nullptr;
+    MVDB_HIP(hipMalloc((void**)&scratch, sizeof(unsigned int)));
+    int rc = make_interleaved(e, head->decoder_w ? head->decoder_w : e->word, V * H, &e->mlm_dec_p, &e->mlm_dec_is, scratch, e->stream);
+    if (!rc) e->owned_h.pop_back();  // (owned through mlm_dec_p / mlm_tw_p: set_mlm_head replaces them)
+    if (!rc) {
+        rc = make_interleaved(e, head->transform_w, H * H, &e->mlm_tw_p, &e->mlm_tw_is, scratch, e->stream);
+        if (!rc) e->owned_h.pop_back();
+    }
+    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MVDB_ERR_HIP, "building the MLM head's images failed");
+    (void)hipFree(scratch);
+    if (rc) return rc;
+    e->have_mlm = true;
+    return 0;
+}
+
+int mvdb_encoder_forward_splade_device(mvdb_encoder* e, const int32_t* ids_dev, const int32_t* mask_dev, int B, int S, int compute,
+                                       float* dense_out_dev, int max_terms, float* weights_dev, int32_t* count_dev, int32_t* indices_dev,
+                                       float* values_dev, void* stream) {
+    if (!e) return fail(MVDB_ERR_ARG, "encoder is NULL");
+    if (!ids_dev || !mask_dev) return fail(MVDB_ERR_ARG, "NULL buffer");
+    if (B <= 0 || S <= 0) return fail(MVDB_ERR_ARG, "B and S must be positive");
+    std::lock_guard<std::mutex> lk(e->mu);
+    DeviceGuard dg(e->device);
+    // every check before anything is enqueued
+    if (!e->have_mlm) return fail(MVDB_ERR_ARG, "no MLM head: mvdb_encoder_set_mlm_head first");
+    if (max_terms < 1 || max_terms > kSpladeMaxTerms) return fail(MVDB_ERR_ARG, "max_terms %d outside [1, %d]", max_terms, kSpladeMaxTerms);
+    const int nlist = (count_dev != nullptr) + (indices_dev != nullptr) + (values_dev != nullptr);
+    if (nlist != 0 && nlist != 3) return fail(MVDB_ERR_ARG, "count_dev, indices_dev and values_dev go together");
+    if (!nlist && !weights_dev) return fail(MVDB_ERR_ARG, "no SPLADE output asked for");
+    hipStream_t s = (hipStream_t)stream;
+    // the workspace of the head, before the first launch: the [sentences of a chunk, V] bits; a pooled row nobody asked for
+    const int64_t words = splade_chunk_sentences(e, B) * e->cfg.vocab_size;
+    if (words > e->splade_cap) {
+        MVDB_HIP(hipDeviceSynchronize());
+        if (e->splade_buf) (void)hipFree(e->splade_buf);
+        e->splade_buf = nullptr;
+        e->splade_cap = 0;
+        MVDB_HIP(hipMalloc((void**)&e->splade_buf, (size_t)words * sizeof(unsigned int)));
+        e->splade_cap = words;
+    }
+    if (!dense_out_dev) {
+        MVDB_TRY(ensure_stage(e, 0, (int64_t)B * e->cfg.hidden));
+        dense_out_dev = e->out_stage;
+    }
+    // one forward at a time per encoder on the device (mvdb_encoder_forward_device): the workspace is shared
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool ordered = s && !(hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone);
+    if (ordered) {
+        if (!e->walk_done) MVDB_HIP(hipEventCreateWithFlags(&e->walk_done, hipEventDisableTiming));
+        else MVDB_HIP(hipStreamWaitEvent(s, e->walk_done, 0));
+    }
+    const SpladeOut o{max_terms, weights_dev, count_dev, indices_dev, values_dev};
+    // always the per-op kernels (walk_mode 0), one lane, plain launches
+    MVDB_TRY(forward_core(e, ids_dev, mask_dev, B, S, compute, dense_out_dev, nullptr, s, 0, nullptr, nullptr, &o));
     if (ordered) MVDB_HIP(hipEventRecord(e->walk_done, s));
     return 0;
 }

@@ -280,6 +280,113 @@ class GpuEncoder:
         return out
 
 
+    # ---- SPLADE: sparse vectors over the vocabulary from the masked-language-model head ------------------------------------
+    def set_mlm_head(self, state_dict_or_module, unused_token_ids=()):
+        """The MLM head of a ``BertForMaskedLM`` (``cls.predictions.*``) or ``XLMRobertaForMaskedLM`` (``lm_head.*``): a module
+        or its state dict.  The decoder weight may be absent (tied to the word embeddings).  unused_token_ids: at most 8 ids
+        that never get a weight.  ``set_mlm_head(None)`` removes the head."""
+        import torch
+        lib = self._native.lib()
+        if state_dict_or_module is None:
+            self._native.check(lib.mvdb_encoder_set_mlm_head(self._h, None))
+            self._mlm = None
+            return
+        sd = state_dict_or_module.state_dict() if hasattr(state_dict_or_module, "state_dict") else state_dict_or_module
+        bert = ("cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+                "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias",
+                "cls.predictions.decoder.weight", ("cls.predictions.decoder.bias", "cls.predictions.bias"))
+        xlmr = ("lm_head.dense.weight", "lm_head.dense.bias", "lm_head.layer_norm.weight", "lm_head.layer_norm.bias",
+                "lm_head.decoder.weight", ("lm_head.decoder.bias", "lm_head.bias"))
+        names = bert if bert[0] in sd else xlmr if xlmr[0] in sd else None
+        if names is None:
+            raise KeyError("no MLM head in the state dict: expected cls.predictions.* (BERT) or lm_head.* (XLM-R) names")
+        bias_name = next((k for k in names[5] if k in sd), None)
+        if bias_name is None:
+            raise KeyError(f"the MLM head has no decoder bias ({' / '.join(names[5])})")
+        H, V = self.hidden, self.cfg.vocab_size
+
+        def dev(t, shape):
+            t = torch.as_tensor(t).detach().to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+            return t.clone() if t.data_ptr() % 16 else t
+
+        keep = [dev(sd[names[0]], (H, H)), dev(sd[names[1]], (H,)), dev(sd[names[2]], (H,)), dev(sd[names[3]], (H,)),
+                dev(sd[bias_name], (V,))]
+        head = self._native.MlmHead(transform_w=keep[0].data_ptr(), transform_b=keep[1].data_ptr(), ln_g=keep[2].data_ptr(),
+                                    ln_b=keep[3].data_ptr(), decoder_b=keep[4].data_ptr())
+        if names[4] in sd:  # (absent: tied to the word embeddings the encoder already holds)
+            keep.append(dev(sd[names[4]], (V, H)))
+            head.decoder_w = keep[5].data_ptr()
+        unused = [int(i) for i in unused_token_ids]
+        if len(unused) > 8:
+            raise ValueError("at most 8 unused token ids")
+        head.n_unused = len(unused)
+        for i, v in enumerate(unused):
+            head.unused_ids[i] = v
+        torch.cuda.synchronize(self.device)
+        self._native.check(lib.mvdb_encoder_set_mlm_head(self._h, ctypes.byref(head)))
+        self._mlm = keep  # the encoder keeps the pointers: the tensors live as long as it does
+
+    @property
+    def has_mlm_head(self):
+        return getattr(self, "_mlm", None) is not None
+
+    def forward_splade_device(self, ids, mask, compute=None, max_terms=256, return_weights=False, return_dense=True):
+        """ids, mask: int32 torch tensors [B,S] on this device.  ONE forward and the MLM head, enqueued on torch's current
+        stream, no wait.  Returns the untrimmed torch tensors: ``count`` [B], ``indices`` / ``values`` [B,max_terms] (ascending
+        token ids, the first count[b] of a row are set, the rest 0); with return_dense ``dense`` [B,H]; with return_weights
+        ``weights`` [B,V], the unpruned weights."""
+        return self._splade_device(ids, mask, compute, max_terms, return_weights, return_dense)[0]
+
+    def _splade_device(self, ids, mask, compute, max_terms, return_weights, return_dense):
+        """forward_splade_device's result and the ONE buffer behind count / indices / values (word 0 is spare)."""
+        import torch
+        compute = self.default_compute if compute is None else compute
+        B, S = ids.shape
+        max_terms = int(max_terms)
+        mt = min(max(max_terms, 1), 1024)  # (the library refuses a max_terms outside [1, 1024] before it reads a buffer)
+        # [word 0 | count | indices | values]: the host entry brings them over in one copy
+        flat = torch.empty(1 + B + 2 * B * mt, dtype=torch.float32, device=self.device)
+        res = {"count": flat[1:1 + B].view(torch.int32), "indices": flat[1 + B:1 + B + B * mt].view(torch.int32).view(B, mt),
+               "values": flat[1 + B + B * mt:].view(B, mt)}
+        if return_dense:
+            res["dense"] = torch.empty((B, self.hidden), dtype=torch.float32, device=self.device)
+        if return_weights:
+            res["weights"] = torch.empty((B, self.cfg.vocab_size), dtype=torch.float32, device=self.device)
+        ptr = lambda k: ctypes.c_void_p(res[k].data_ptr() if k in res else 0)  # noqa: E731
+        self._native.check(self._native.lib().mvdb_encoder_forward_splade_device(
+            self._h, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(mask.data_ptr()), B, S, compute, ptr("dense"), max_terms,
+            ptr("weights"), ptr("count"), ptr("indices"), ptr("values"), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return res, flat
+
+    def forward_splade(self, ids, mask, compute=None, max_terms=256):
+        """ids, mask: int arrays [B,S] (host).  One forward, one stream wait.  Returns, per sentence, ``{token_id (int): weight
+        (float)}`` by ascending id — what ``VectorDatabase.set_sparse_vector`` takes.  compute = 2 re-runs in the exact mode
+        when the forward raised the overflow word, as `forward` does."""
+        import torch
+        compute = self.default_compute if compute is None else compute
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape != mask.shape:
+            raise ValueError("ids and mask must be [B,S] arrays of the same shape")
+        B = ids.shape[0]
+        with torch.cuda.device(self.device):
+            both = torch.from_numpy(np.stack([ids, mask])).to(self.device)
+
+            def run(mode):
+                res, flat = self._splade_device(both[0], both[1], mode, max_terms, False, False)
+                flat[0:1].view(torch.int32).copy_(self.overflow_flag())  # the overflow word rides along
+                return res, flat.cpu().numpy()  # (waits for the stream)
+
+            res, host = run(compute)
+            if compute == 2 and host[0:1].view(np.int32)[0]:
+                res, host = run(0)
+        mt = res["indices"].shape[1]
+        n = host[1:1 + B].view(np.int32)
+        idx = host[1 + B:1 + B + B * mt].view(np.int32).reshape(B, mt)
+        val = host[1 + B + B * mt:].reshape(B, mt)
+        return [dict(zip(idx[b, :n[b]].tolist(), val[b, :n[b]].tolist())) for b in range(B)]
+
+
 def load_m3_heads(path):
     """The two head files of a BGE-M3 directory, as state dicts of float32 CPU tensors: ``(sparse_linear, colbert_linear)``;
     a file that is not there gives None.  Needs no GPU."""
@@ -326,6 +433,9 @@ class EmbeddingModel:
             self.load_onnx_model()
         else:
             self.load_alternative_model()
+        # SPLADE: the MLM head of the checkpoint (mlm_head= a BertForMaskedLM / XLMRobertaForMaskedLM module or state dict)
+        if kwargs.get('mlm_head') is not None:
+            self.model.set_mlm_head(kwargs['mlm_head'], kwargs.get('mlm_unused_token_ids', ()))
 
     def load_onnx_model(self):
         raise NotImplementedError(
@@ -429,6 +539,24 @@ class EmbeddingModel:
         from ONE forward: BGE-M3's three outputs.  The lexical keys are INTEGER token ids, so the dict goes straight into
         ``VectorDatabase.set_sparse_vector`` (FlagEmbedding's ``lexical_weights`` has the same ids as strings: ``str(k)``)."""
         return self.extract_embeddings_multi_batch([text])[0]
+
+    # ---- SPLADE: {token_id: weight} over the vocabulary, for set_sparse_vector / find_most_similar_sparse ---------------------
+    def extract_sparse_embeddings_batch(self, texts, max_terms=256):
+        """One forward and the MLM head for the batch; per text the ``{token_id (int): weight (float)}`` dict of its max_terms
+        largest SPLADE weights, by ascending id.  Texts are tokenised as they stand (no ``passage`` prefix)."""
+        if self.model is None or not self.model.has_mlm_head:
+            raise ValueError(
+                "this encoder carries no MLM head: pass mlm_head= (a BertForMaskedLM / XLMRobertaForMaskedLM module or state "
+                "dict) to EmbeddingModel, or call model.set_mlm_head(...)")
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer loaded: pass tokenizer=... or model_path=... to EmbeddingModel")
+        batch = self.tokenizer(list(texts), max_length=512, padding=True, truncation=True, return_tensors='np')
+        ids = np.asarray(batch['input_ids'], dtype=np.int32)
+        mask = np.asarray(batch['attention_mask'], dtype=np.int32)
+        return self.model.forward_splade(ids, mask, max_terms=max_terms)
+
+    def extract_sparse_embeddings(self, text, max_terms=256):
+        return self.extract_sparse_embeddings_batch([text], max_terms=max_terms)[0]
 
     def extract_embeddings_quant_onnx(self, text):
         raise NotImplementedError("the quantised ONNX model is not available in minivectordb_amd")
