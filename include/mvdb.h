@@ -90,6 +90,14 @@ int mvdb_index_reload_env(mvdb_index* idx);
  *       free it); 1 again rebuilds the code with it at the next eligible query.  D, I, the candidate rows and the counters
  *       of a call do not depend on this option.  An allocation that fails leaves the index without the plane, no more.
  *   "half_shadow" (0 | 1, default 1): 0 = batches nominate from the fp32 rows (no second copy of the corpus).
+ *   "wide_shadow" (0 | 1, default 0): 1 = an inner-product index of width 1536, 2048, 3072 or 4096 with unpadded rows keeps an
+ *       fp16 shadow too (+2 bytes per stored element, built by the next batch) and its unfiltered batches of k <= 16 take the
+ *       certified pass (nomination over the shadow by a K-split kernel, fp32 re-score, certificate with mvdb_half_wide_eps,
+ *       refused queries re-run on the exact GEMM-tiled scan), from the same batch sizes as the narrower widths: 33 queries
+ *       below 100k rows, 8 from 100k, 2 from 500k.  Row lists, bitmaps, L2, k > 16, range search and the join are served as
+ *       with 0.  0 = these widths keep no shadow (one that exists is freed) and launch what they launched before.
+ *   "wide_shadow_blocks" (0 .. 65535, default 0 = by the device): most workgroups per query slab of that pass.  Diagnostic: a
+ *       small value makes every workgroup walk many tiles of a small corpus.
  *   "compact_bytes" (> 0, default 512 MiB): staging buffer of mvdb_index_remove_rows. */
 int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value);
 
@@ -1106,9 +1114,13 @@ int mvdb_rescue_tile_stats(int64_t* listed, int64_t* total);
  * (half_scan.hip: both operands rounded to fp16, d products accumulated in fp32, 64 nominees per query re-scored
  * in fp32): rounding of both operands, elements below fp16's normal range, worst-case fp32 accumulation, the fp32
  * re-score, |q| and the comparison (docs/DESIGN_NOTES.md section 4.3d; tests/test_split_bound.py).  Diagnostic.
- * mvdb_half_max_queries: queries per corpus pass of that pass at dimension d, 0 where it has no kernel. */
+ * mvdb_half_max_queries: queries per corpus pass of that pass at dimension d, 0 where it has no kernel.
+ * mvdb_half_wide_eps / mvdb_half_wide_queries: the bound and the queries per workgroup of the pass of option "wide_shadow"
+ * (d = 1536, 2048, 3072, 4096; both 0 at every other d; mvdb_half_max_queries stays 0 at these widths). */
 double mvdb_half_eps(int d);
 int mvdb_half_max_queries(int d);
+double mvdb_half_wide_eps(int d);
+int mvdb_half_wide_queries(int d);
 
 /* ---- int8 cosine index (csrc/cos8.hip) ---------------------------------------------------
  * Replaces usearch.index.Index(ndim=d, metric='cos', dtype='int8') built per query over the filtered rows

@@ -256,6 +256,8 @@ PROTOTYPES = {
     "mvdb_rescue_tile_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "mvdb_half_eps": (ctypes.c_double, [ctypes.c_int]),
     "mvdb_half_max_queries": (ctypes.c_int, [ctypes.c_int]),
+    "mvdb_half_wide_eps": (ctypes.c_double, [ctypes.c_int]),
+    "mvdb_half_wide_queries": (ctypes.c_int, [ctypes.c_int]),
     "mvdb_prof_enable": (ctypes.c_int, [ctypes.c_int]),
     "mvdb_prof_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_double)]),
@@ -466,7 +468,7 @@ class FlatIndex:
 
     def set_option(self, name, value):
         """Per-index switch set in code (include/mvdb.h: mvdb_index_set_option): "shadow_single_query", "half_shadow",
-        "compact_bytes"."""
+        "wide_shadow", "compact_bytes"."""
         check(lib().mvdb_index_set_option(self._h, str(name).encode(), int(value)))
         if name == "maxsim_mfma":
             self._maxsim_mfma = int(value)  # (the library has no getter: _matrix_cores restores from this)
@@ -1693,6 +1695,14 @@ def half_eps(d):
 
 def half_max_queries(d):
     return int(lib().mvdb_half_max_queries(int(d)))
+
+
+def half_wide_eps(d):
+    return float(lib().mvdb_half_wide_eps(int(d)))
+
+
+def half_wide_queries(d):
+    return int(lib().mvdb_half_wide_queries(int(d)))
 
 
 def encoder_splitk_planes(tokens, n, k, compute_units=256):

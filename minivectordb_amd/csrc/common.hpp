@@ -143,6 +143,9 @@ struct Knobs {
          disable_l2_cert = false,    // MVDB_DISABLE_* (L2_CERT: L2 batches back on the exact fp32 kernels)
          disable_half_shadow = false;  // MVDB_DISABLE_HALF_SHADOW (index option half_shadow = 0): no fp16 shadow, batches on the exact fp32 passes
     bool shadow_single_query = false;  // MVDB_SHADOW_SINGLE_QUERY (1: single queries through the certified fp16-shadow pass too)
+    int wide_shadow = 0;               // index option wide_shadow: 1 an inner-product index of width 1536 / 2048 / 3072 / 4096 keeps an fp16 shadow
+                                       // (+2 d bytes per row) and its unfiltered batches of k <= 16 take the certified pass (half_wide_scan.hip)
+    int wide_shadow_blocks = 0;        // index option wide_shadow_blocks (diagnostic): > 0, at most that many workgroups per query slab of that pass
     bool code8_single_query = true;    // index option code8_single_query: single queries over large inner-product indexes through the int8 prefilter
     long long code8_capacity = 32768;  // index option code8_capacity: candidates the prefilter may hand to the exact re-score
     int code8_front_plane = 1;         // index option code8_front_plane: 1 the code keeps a plane of the top 5 bits and the prefilter streams it

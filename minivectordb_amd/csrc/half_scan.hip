@@ -24,6 +24,8 @@
 //   flat_scan_h16_kernel<KT, KS, WV, NST, DEPTH>   the pass itself, over the shadow: 128 / 256 queries per pass (32 per wave),
 //       d = 128 .. 1024; DEPTH = 32: the rescue launch, which walks a LIST of tiles (rescue_tiles_kernel: the tiles the main launches
 //       flagged for its refused queries — HalfScanArgs::tflags — or every tile).  Algorithmic bytes per launch = rows scanned x d x 2.
+//   flat_scan_h16_wide_kernel<KT, QG, NK, KS, NST>   (half_wide_scan.hpp) the pass at d = 1536 .. 4096: a query group's K cut into NK
+//       parts held by NK waves, part-tile stages, the partial score tiles summed through an LDS exchange window by the group's owner wave.
 //   range_nominate_h16_kernel<KT, KS, WV, NST>   the same pipeline for a RANGE batch (mvdb_index_range_search*): a fixed floor per
 //       query instead of lists, candidate rows appended to per-query segments.  Algorithmic bytes per launch = rows x d x 2.
 //   flat_scan_seed_kernel<KQ, SKB, NG, NST>   the first launch of every pass: one 32-row tile of the fp32 rows per block (K
@@ -637,18 +639,6 @@ int launch_half_norms(const float* X, int64_t ld, int d, int64_t n, float* Hn, i
 // (160 - 256 registers of query fragments)
 bool half_shadow_dim(int d) { return d == 128 || d == 256 || d == 384 || d == 512 || d == 640 || d == 768 || d == 896 || d == 1024; }
 
-// One launch of a kernel that streams through a ring in dynamic LDS: the attribute that admits `lds` bytes, a grid of one block
-// per tile up to `per_cu` workgroups per CU (*nblocks_out, where asked for), the profiling bracket (profiled_launch).  symbol...: the format and the
-// arguments of prof_symbol.
-template <typename Args, typename... Sym>
-static int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int threads, int64_t ntiles, int per_cu, int device, hipStream_t stream,
-                       int* nblocks_out, const char* label, Sym... symbol) {
-    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
-    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * per_cu));
-    if (nblocks_out) *nblocks_out = nblocks;
-    return profiled_launch(label, stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks), dim3(threads), lds, stream, done, a); }, symbol...);
-}
-
 // The shapes of the launches that stream the whole shadow: the certified pass's main launches and the shared pass of a batch range
 // search (the ring and the workgroups per CU were measured for the former: the stream is the same).  A stage = a whole 32-row tile
 // (KS = KT: 16 / 24 / 32 KiB at d = 256 / 384 / 512: one barrier per tile).  256 queries per pass: eight waves (two per SIMD), a
@@ -687,7 +677,7 @@ static int launch_h16(int d, int nqpad, const HalfScanArgs& a, int device, hipSt
         using S = decltype(shape);
         static_assert(S::BPC * (S::kLds + S::WV * 32 * kHalfKeep * 8) <= 160 * 1024, "LDS budget of a CU");
         // (a launch without admission floors is the seed of an L2 pass over the shadow, mvdb.hip: launch_half_pass)
-        return launch_ring(flat_scan_h16_kernel<S::KT, S::KS, S::WV, S::NST>, a, S::kLds, S::WV * 64, a.tile1 - a.tile0, S::BPC, device, stream, nb,
+        return launch_ring(flat_scan_h16_kernel<S::KT, S::KS, S::WV, S::NST>, a, S::kLds, S::WV * 64, a.tile1 - a.tile0, S::BPC, 1, device, stream, nb,
                            a.thr0 ? "ip_scan_half" : "ip_scan_half_seed", "flat_scan_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV, S::NST,
                            kHalfKeep);
     });
@@ -880,9 +870,9 @@ int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipS
         static_assert(S::BPC * S::kLds <= 160 * 1024, "LDS budget of a CU");
         if (a.before)   // the range join: rows [0, a.n) with a.n the largest bound of the chunk, each query gated on its own
             return launch_ring(join_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC,
-                               device, stream, nullptr, "ip_scan_join_half", "join_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV,
+                               1, device, stream, nullptr, "ip_scan_join_half", "join_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV,
                                S::NST, NACC);
-        return launch_ring(range_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC, device,
+        return launch_ring(range_nominate_h16_kernel<S::KT, S::KS, S::WV, S::NST, NACC>, a, S::kLds, S::WV * 64, (a.n + 31) / 32, S::BPC, 1, device,
                            stream, nullptr, "ip_scan_range_half", "range_nominate_h16_kernel<%d, %d, %d, %d, %d>", S::KT, S::KS, S::WV, S::NST, NACC);
     });
 }
@@ -901,7 +891,7 @@ static int launch_h16_rescue_inst(const HalfScanArgs& a, int device, hipStream_t
     constexpr size_t lds = H16Shape<KT, KS, 4, NST>::kLds;
     static_assert(BPC * (lds + 4 * 32 * kRescueKeep * 8) <= 160 * 1024, "LDS budget of a CU");
     static_assert(BPC <= kRescueBlocksPerCu, "mvdb.hip sizes the lists by kRescueBlocksPerCu");
-    return launch_ring(flat_scan_h16_kernel<KT, KS, 4, NST, kRescueKeep>, a, lds, 256, a.tile1 - a.tile0, BPC, device, stream, nblocks_out,
+    return launch_ring(flat_scan_h16_kernel<KT, KS, 4, NST, kRescueKeep>, a, lds, 256, a.tile1 - a.tile0, BPC, 1, device, stream, nblocks_out,
                        "ip_scan_rescue", "flat_scan_h16_kernel<%d, %d, 4, %d, %d>", KT, KS, NST, kRescueKeep);
 }
 // The rescue launches' tile lists: thread w of slot s = blockIdx.y ORs word w of the flag rows of the slot's refused queries, adds
@@ -1278,7 +1268,7 @@ template <int KQ, int NG, int NST>
 static int launch_seed_inst(const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
     constexpr size_t lds = (size_t)4 * NST * HsStage<2>::kBytes + (size_t)4 * 3 * 4096;
     static_assert(lds + 128 <= 160 * 1024, "LDS budget of a CU");
-    return launch_ring(flat_scan_seed_kernel<KQ, 2, NG, NST>, a, lds, 256, a.tile1 - a.tile0, 1, device, stream, nblocks_out, "ip_scan_half_seed",
+    return launch_ring(flat_scan_seed_kernel<KQ, 2, NG, NST>, a, lds, 256, a.tile1 - a.tile0, 1, 1, device, stream, nblocks_out, "ip_scan_half_seed",
                        "flat_scan_seed_kernel<%d, 2, %d, %d>", KQ, NG, NST);
 }
 
@@ -1293,6 +1283,7 @@ static int launch_seed_kq(int nqpad, const HalfScanArgs& a, int device, hipStrea
 // seed = true: the seed launch (fp32 rows); else a main launch over the fp16 shadow a.Xh (which the caller has ensured)
 int launch_half_scan(int d, int nqpad, bool seed, const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out) {
     if (!seed) {
+        if (a.Xh && half_wide_queries(d) > 0) return launch_half_wide_scan(d, a, device, stream, nblocks_out);
         if (!a.Xh || !half_shadow_dim(d)) return fail(MVDB_ERR_ARG, "internal: the certified pass needs the fp16 shadow (d = %d)", d);
         return launch_h16(d, nqpad, a, device, stream, nblocks_out);
     }

@@ -44,6 +44,7 @@ struct HalfScanArgs {
     float flag_coef = 0.f;
     const int* tile_list = nullptr;  // rescue launch: the tiles to scan ...
     const int* tile_count = nullptr; // ... and how many
+    int max_blocks = 0;              // wide kernel only (index option wide_shadow_blocks): > 0, at most that many workgroups per query slab
 };
 
 struct HalfCertifyArgs {
@@ -141,11 +142,29 @@ struct HalfRangeArgs {
 };
 int launch_half_range(int d, int nqpad, const HalfRangeArgs& a, int device, hipStream_t stream);
 
+// One launch of a kernel that streams through a ring in dynamic LDS (half_scan.hip, half_wide_scan.hip): the attribute that admits
+// `lds` bytes, a grid of one block per tile up to `per_cu` workgroups per CU (*nblocks_out, where asked for) times `slabs` (grid.y:
+// the wide kernel's query slabs, 1 elsewhere), the profiling bracket (profiled_launch).  symbol...: the format and the arguments of
+// prof_symbol.
+template <typename Args, typename... Sym>
+int launch_ring(void (*kern)(Args), const Args& a, size_t lds, int threads, int64_t ntiles, int per_cu, int slabs, int device,
+                hipStream_t stream, int* nblocks_out, const char* label, Sym... symbol) {
+    MVDB_TRY(ensure_dynamic_lds((const void*)kern, lds, device));
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)device_cus(device) * per_cu));
+    if (nblocks_out) *nblocks_out = nblocks;
+    return profiled_launch(label, stream, [&](hipEvent_t done) { launch_kernel(kern, dim3(nblocks, slabs), dim3(threads), lds, stream, done, a); }, symbol...);
+}
+
 // queries per corpus pass of the widest instantiation for dimension d (0: no kernel for this d)
 int half_max_queries(int d);
 // queries per pass the launcher will use for a chunk of `nq` queries (a multiple of 32 * d / 128)
 int half_chunk_queries(int d, int nq);
 double half_eps(int d);
+// the wide route (half_wide_scan.hpp, d = 1536 / 2048 / 3072 / 4096; passes of 128 queries through launch_half_scan): queries per
+// workgroup of flat_scan_h16_wide_kernel, and the bound of that kernel's accumulation — both 0 at every other width
+int half_wide_queries(int d);
+double half_wide_eps(int d);
+int launch_half_wide_scan(int d, const HalfScanArgs& a, int device, hipStream_t stream, int* nblocks_out);
 // per unit |q| max|x|: bound on |range nomination score - the fp32 score of the exact scans| (the band of the shared range pass)
 double half_range_eps(int d);
 float half_xscale(float row_norm_bound);

@@ -1152,12 +1152,27 @@ bool tile_flags_wanted(const mvdb_index* idx) {
 
 thread_local bool tls_single_suspended = false;  // decided once per search (search_core), read by every routing question of that call
 
+// The wide route (index option wide_shadow; half_wide_scan.hip): an inner-product index of width 1536 / 2048 / 3072 / 4096 with
+// unpadded rows keeps an fp16 shadow and sends its unfiltered batches of k <= 16 through the certified pass, 128 queries per pass.
+// Everything else at these widths — row lists, bitmaps, L2, k > 16, range search, the join — is served as without the option.
+bool wide_dim_ok(const mvdb_index* idx) {
+    return idx->kn.wide_shadow != 0 && half_wide_queries(idx->d) > 0 && idx->metric == MVDB_METRIC_IP && idx->ld == idx->d;
+}
+bool wide_path_ok(const mvdb_index* idx) {
+    if (idx->kn.disable_half_scan || idx->kn.disable_half_shadow || idx->shadow.failed) return false;
+    return wide_dim_ok(idx) && half_xscale(idx->row_norm_bound) > 0.f;
+}
+// queries per pass of the certified route of this index, and the bound it certifies with
+int pass_max_queries(const mvdb_index* idx) { return wide_path_ok(idx) ? 128 : half_max_queries(idx->d); }
+int pass_chunk_queries(const mvdb_index* idx, int nq) { return wide_path_ok(idx) ? 128 : half_chunk_queries(idx->d, nq); }
+double pass_eps(const mvdb_index* idx) { return wide_path_ok(idx) ? half_wide_eps(idx->d) : half_eps(idx->d); }
+
 int half_min_nq(const mvdb_index* idx, int64_t n) {
     if (idx->kn.split_scan_min_nq >= 0) return idx->kn.split_scan_min_nq;
-    if (half_shadow_dim(idx->d) && idx->ld == idx->d && !idx->kn.disable_half_shadow && !idx->shadow.failed) {
+    if ((half_shadow_dim(idx->d) || wide_dim_ok(idx)) && idx->ld == idx->d && !idx->kn.disable_half_shadow && !idx->shadow.failed) {
         // (opt-in, MVDB_SHADOW_SINGLE_QUERY=1: ONE query too — 10M x 512: 2.86 -> ~1.6 ms per query, certified like any batch; off
         //  by default: the single-query scan is the headline's exact fp32 kernel and its roofline is defined on the fp32 bytes)
-        if (n >= 500000) return idx->kn.shadow_single_query && !tls_single_suspended ? 1 : 2;
+        if (n >= 500000) return idx->kn.shadow_single_query && !tls_single_suspended && !wide_dim_ok(idx) ? 1 : 2;
         if (n >= 100000) return 8;
     }
     return 33;
@@ -1167,7 +1182,9 @@ int half_min_nq(const mvdb_index* idx, int64_t n) {
 // (Until round 6 a second certified generation — bf16 (hi, lo) split products over the fp32 rows, scan_split_kernels.hpp —
 //  served the widths without an fp16 kernel; it is retired: those widths take the exact passes below.)
 bool split_path_ok(const mvdb_index* idx, int nq, int k, const int64_t* rows_dev, int64_t n) {
-    if (idx->kn.disable_split_scan || !half_path_ok(idx)) return false;
+    const bool wide = wide_path_ok(idx);
+    if (idx->kn.disable_split_scan || !(half_path_ok(idx) || wide)) return false;
+    if (wide && (nq < 2 || k > kHalfKeep)) return false;
     if (nq < half_min_nq(idx, n) || (nq == 1 && !(idx->kn.shadow_single_query && !tls_single_suspended))) return false;
     if (rows_dev || (idx->metric != MVDB_METRIC_IP && !l2_cert_ok(idx) && !l2_offsets_ok(idx, nq, n))) return false;
     // (k > 16 also needs the gated fp32-MFMA pass for the exact re-runs: the GEMM-tiled scan keeps 16 results per query)
@@ -1249,7 +1266,10 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     a.cand = cand;
     // SEED launch: the first min(tiles, CUs) tiles, one per block, every score dumped (32 keys per block and query);
     // phase_fold_kernel keeps each query's 16 best and publishes the 16th score as the first admission floor.
-    const int64_t seed_tiles = std::min<int64_t>(ntiles, cus);
+    // (the wide route, d = 1536 .. 4096: the seed is the wide kernel itself without floors, one tile per workgroup of its grid)
+    const bool wide = wide_path_ok(idx);
+    a.max_blocks = wide ? idx->kn.wide_shadow_blocks : 0;
+    const int64_t seed_tiles = std::min<int64_t>(ntiles, a.max_blocks > 0 ? std::min(cus, a.max_blocks) : cus);
     int gx = 0;
     a.tile0 = 0;
     a.tile1 = seed_tiles;
@@ -1261,7 +1281,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     const float* hn = idx->metric == MVDB_METRIC_L2 && a.Xh && !l2_cert_ok(idx) && !idx->kn.disable_l2_cert ? idx->shadow.ensure_offsets(idx, stream)
                                                                                                           : nullptr;
     const bool l2off = hn != nullptr;
-    if (l2off) {
+    if (l2off || wide) {
         a.hn = hn;
         MVDB_TRY(launch_half_scan(idx->d, nqpad, false, a, idx->device, stream, &gx));
         hipLaunchKernelGGL(phase_fold_kernel, dim3(nq), dim3(1024), 0, stream, cand, gx, (const uint64_t*)nullptr, seed_keys, floors);
@@ -1307,7 +1327,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
         a.twords = twords;
         a.flag_qn = qnorm;
         const double B = (double)idx->row_norm_bound;
-        a.flag_coef = (float)((2.25 * half_eps(idx->d) + 4.0 * idx->d * std::ldexp(1.0, -24)) * B * (1.0 + 1e-6));
+        a.flag_coef = (float)((2.25 * pass_eps(idx) + 4.0 * idx->d * std::ldexp(1.0, -24)) * B * (1.0 + 1e-6));
         if (flags_written) *flags_written = true;  // (the caller hands the rescue pass tile lists only if EVERY chunk's launches wrote flags)
     }
     for (size_t p = ends.size(); p-- > 0;) {
@@ -1332,7 +1352,7 @@ int launch_half_pass(const mvdb_index* idx, Workspace* ws, const float* q, int n
     c.d4 = idx->d4;
     c.q = q;
     c.qnorm = qnorm;
-    c.eps = (float)(half_eps(idx->d) * (double)idx->row_norm_bound * (1.0 + 1e-6));  // rounded up
+    c.eps = (float)(pass_eps(idx) * (double)idx->row_norm_bound * (1.0 + 1e-6));  // rounded up
     c.k = k;
     c.label_offset = label_offset;
     c.D = D;
@@ -1445,7 +1465,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
     *qsrc_out = qsrc;
     // chunk plan: 128 / 256 queries per pass while at least min_nq remain; what is left takes the exact passes
     const int min_nq = half_min_nq(idx, n);
-    const int chunk = half_max_queries(idx->d);
+    const int chunk = pass_max_queries(idx);
     std::vector<std::pair<int, int>> plan;  // (first query, count)
     int q0 = 0;
     // (L2 over rows of mixed norms: the pass nominates by q.x - |x|^2 / 2 with per-row offsets beside the shadow; rows of one
@@ -1483,7 +1503,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
         for (int c = 0; c < nchunks; ++c) {
             const int c0 = plan[c].first, take = plan[c].second;
             bool wrote = false;
-            MVDB_TRY(launch_half_pass(idx, ws, qsrc + (int64_t)c0 * idx->ld, take, half_chunk_queries(idx->d, take), k, n, label_offset,
+            MVDB_TRY(launch_half_pass(idx, ws, qsrc + (int64_t)c0 * idx->ld, take, pass_chunk_queries(idx, take), k, n, label_offset,
                                       D_dev + (int64_t)c0 * k, I_dev + (int64_t)c0 * k, ws->flags.p + c, ws->qfail.p + c0, mask32,
                                       ws->qfloor.p + c0, tile_flags ? ws->tflags.p + (size_t)c0 * twords : nullptr, twords, &wrote));
             flags_ok = flags_ok && wrote;
@@ -1558,7 +1578,7 @@ int certified_batch(const mvdb_index* idx, Workspace* ws, const ScanArgs& a, con
             _Float16* qf = reinterpret_cast<_Float16*>(ws->qsplit.p);
             float* qn2 = ws->qnorm.p;
             float* qinv = qn2 + 2 * kRescueQueries;
-            float eps = (float)(half_eps(idx->d) * (double)idx->row_norm_bound * (1.0 + 1e-6));
+            float eps = (float)(pass_eps(idx) * (double)idx->row_norm_bound * (1.0 + 1e-6));
             if (hn) eps = (float)((double)eps + std::ldexp(1.0, -22) * (double)idx->row_norm_bound * (1.0 + 1e-6));  // (launch_half_pass: the subtraction)
             {   // the launches' tile lists: what the refused queries' flags name (no flags: every tile)
                 RescueTilesArgs ta;
@@ -2047,7 +2067,7 @@ void ShadowStore::invalidate() {
 // other streams find complete data.  NULL (the fp32 path serves): no kernel for d, switched off, allocation failed, or the
 // stream is being captured (a build allocates and synchronises).
 const _Float16* ShadowStore::ensure(const mvdb_index* idx, hipStream_t s, float xscale) {
-    if (!half_shadow_dim(idx->d) || idx->ld != idx->d || idx->kn.disable_half_shadow || !(xscale > 0.f)) return nullptr;
+    if (!(half_shadow_dim(idx->d) || wide_dim_ok(idx)) || idx->ld != idx->d || idx->kn.disable_half_shadow || !(xscale > 0.f)) return nullptr;
     std::lock_guard<std::mutex> lk(idx->shadow_mu);
     if (Xh.p && scale == xscale && rows == idx->n) return Xh.p;
     if (failed || stream_capturing(s)) return nullptr;
@@ -2623,7 +2643,10 @@ int mvdb_index_reload_env(mvdb_index* idx) {
     const long long probe_table = idx->kn.probe_table_bytes;
     const int sparse_postings = idx->kn.sparse_postings;
     const int maxsim_mfma = idx->kn.maxsim_mfma;
+    const int wide_shadow = idx->kn.wide_shadow, wide_blocks = idx->kn.wide_shadow_blocks;
     idx->kn = read_knobs();
+    idx->kn.wide_shadow = wide_shadow;
+    idx->kn.wide_shadow_blocks = wide_blocks;
     idx->kn.sparse_postings = sparse_postings;
     idx->kn.maxsim_mfma = maxsim_mfma;
     idx->kn.distinct_table_bytes = distinct_table;
@@ -2713,13 +2736,22 @@ int mvdb_index_set_option(mvdb_index* idx, const char* name, long long value) {
     } else if (n == "sparse_postings") {  // 1: a sparse store that has postings is scored through them, 0: always the CSR pass
         if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "sparse_postings must be 0 or 1");
         idx->kn.sparse_postings = (int)value;
+    } else if (n == "wide_shadow") {  // 1: widths 1536 / 2048 / 3072 / 4096 keep an fp16 shadow (built by the next batch) and their batches take the certified pass
+        if (value < 0 || value > 1) return fail(MVDB_ERR_ARG, "wide_shadow must be 0 or 1");
+        DeviceGuard dg(idx->device);
+        MVDB_TRY(quiesce(idx));
+        if (value == 0 && wide_dim_ok(idx)) idx->shadow.drop();
+        idx->kn.wide_shadow = (int)value;
+    } else if (n == "wide_shadow_blocks") {  // diagnostic: a small grid makes every workgroup of the wide pass walk many tiles of a small corpus
+        if (value < 0 || value > 65535) return fail(MVDB_ERR_ARG, "wide_shadow_blocks must lie in [0, 65535]");
+        idx->kn.wide_shadow_blocks = (int)value;
     } else if (n == "half_shadow")
         idx->kn.disable_half_shadow = value == 0;
     else if (n == "compact_bytes") {
         if (value <= 0) return fail(MVDB_ERR_ARG, "compact_bytes must be positive");
         idx->kn.compact_bytes = value;
     } else
-        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, maxsim_mfma, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, sparse_postings, half_shadow, compact_bytes)", name);
+        return fail(MVDB_ERR_ARG, "unknown index option '%s' (shadow_single_query, code8_single_query, code8_capacity, code8_front_plane, code8_bit_plane, range_shared, join_shared, range_candidates, distinct_table_bytes, groups_partials_bytes, maxsim_table_bytes, maxsim_tokens_per_pass, maxsim_mfma, assign_vectors_per_pass, examples_vectors_per_pass, probe_table_bytes, sparse_postings, half_shadow, wide_shadow, wide_shadow_blocks, compact_bytes)", name);
     return 0;
 }
 
@@ -6956,6 +6988,8 @@ int mvdb_synth_fill_device(float* out_dev, int64_t n, int d, uint64_t seed, int6
 
 double mvdb_half_eps(int d) { return d > 0 ? half_eps(d) : 0.0; }
 int mvdb_half_max_queries(int d) { return d > 0 ? half_max_queries(d) : 0; }
+double mvdb_half_wide_eps(int d) { return d > 0 ? half_wide_eps(d) : 0.0; }
+int mvdb_half_wide_queries(int d) { return d > 0 ? half_wide_queries(d) : 0; }
 
 int64_t mvdb_split_rerun_count(void) {
     // diagnostic: the counters live on the devices (the search path never reports to the host); finished work only —

@@ -52,10 +52,11 @@ def shard_files_for_rank(storage_dir, rank, world):
 
 
 class ShardedVectorDatabase(UpdateMixin, FilterAndRerankMixin):
-    def __init__(self, storage_dir='db_shards', shard_size=5000, device=0, fast_single_query=False):
-        """storage_dir, shard_size: as in the reference (sharded_vector_database.py:9).  device, fast_single_query: see
-        VectorDatabase."""
+    def __init__(self, storage_dir='db_shards', shard_size=5000, device=0, fast_single_query=False, wide_batch_shadow=False):
+        """storage_dir, shard_size: as in the reference (sharded_vector_database.py:9).  device, fast_single_query,
+        wide_batch_shadow: see VectorDatabase."""
         self._fast_single_query = bool(fast_single_query)
+        self._wide_batch_shadow = bool(wide_batch_shadow)
         self.hash_vectorizer = None
         self.embedding_size = None
         self.storage_dir = storage_dir

@@ -30,12 +30,15 @@ from ._dbcore import FilterAndRerankMixin, UpdateMixin, _IdIndex, _RowStore
 
 
 class VectorDatabase(UpdateMixin, FilterAndRerankMixin):
-    def __init__(self, storage_file='db.pkl', device=0, fast_single_query=False):
+    def __init__(self, storage_file='db.pkl', device=0, fast_single_query=False, wide_batch_shadow=False):
         """storage_file: as in the reference (vector_database.py:8).  device: HIP device ordinal.  fast_single_query: every
         find_most_similar call (one query) nominates over an fp16 copy of the rows and is re-scored and certified in fp32 — the
         same ids and distances, about half the time per query from 500,000 rows x 256 / 384 / 512 on, 50 % more device memory
-        (include/mvdb.h: mvdb_index_set_option "shadow_single_query")."""
+        (include/mvdb.h: mvdb_index_set_option "shadow_single_query").  wide_batch_shadow: embeddings of width 1536, 2048, 3072 or
+        4096 keep an fp16 copy too (50 % more device memory) and find_most_similar_batch nominates over it, re-scored and certified
+        in fp32 (option "wide_shadow")."""
         self._fast_single_query = bool(fast_single_query)
+        self._wide_batch_shadow = bool(wide_batch_shadow)
         self.hash_vectorizer = None  # built lazily (sklearn) by hybrid_rerank_results
         self.embedding_size = None
         self.storage_file = storage_file
