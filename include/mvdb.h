@@ -1189,6 +1189,71 @@ int mvdb_cos8_search_rowset(const mvdb_cos8* ix, const float* q_host, int nq, in
 int mvdb_cos8_search_rowset_device(const mvdb_cos8* ix, const float* q_dev, int nq, int k, const mvdb_cos8_rowset* rs,
                                    int64_t label_offset, float* D_dev, int64_t* I_dev, void* stream);
 
+/* ---- binary index (csrc/bits.hip) -----------------------------------------------------------
+ * faiss.IndexBinaryFlat restated: packed bit rows on the device, exact Hamming top-k.
+ *
+ * d_bits is a multiple of 128 in [128, 4096]; a row is d_bits / 8 bytes.  The bytes are opaque: the distance
+ * H = popcount(row XOR query) does not depend on the bit order as long as rows and queries are packed alike.
+ * The *_float calls take fp32 vectors of length d_bits and pack them on the device (csrc/bits_kernels.hpp:
+ * bits_pack_kernel): bit i = (x[i] > 0) — NaN and -0 give 0 — in numpy.packbits' default layout, dimension 8 j in
+ * bit 7 of byte j (sentence-transformers' "ubinary").
+ * Results: D int32 Hamming distances ascending, I int64 rows, equal distances to the lower row; 1 <= k <= 64, a larger k
+ * is MVDB_ERR_ARG; when fewer than k rows are selected the tail is I = -1, D = INT32_MAX.  Every form of the scan
+ * returns the same bits (integer arithmetic): 1 to 8 queries per pass on the VALU, 32 per row read on the int8
+ * matrix cores.
+ * mask: NULL, or the flat index's bitmap format — bit r & 63 of 64-bit word r >> 6 set = row r selected,
+ * (ntotal + 63) / 64 words.  The host calls take it in host memory and upload it with the queries; the device
+ * calls take it resident on the device.
+ * Searches are re-entrant from many host threads; add / remove_rows / set_rows / reset / reserve take the index
+ * exclusively, run on its own stream and wait for its searches (as the int8 cosine index). */
+typedef struct mvdb_bits mvdb_bits;
+int mvdb_bits_create(int d_bits, int device, mvdb_bits** out);
+int mvdb_bits_free(mvdb_bits* ix);
+int mvdb_bits_reset(mvdb_bits* ix);
+int mvdb_bits_reserve(mvdb_bits* ix, int64_t n);
+int64_t mvdb_bits_ntotal(const mvdb_bits* ix);
+int mvdb_bits_dim(const mvdb_bits* ix);
+
+/* Which form a search of nq queries and k results takes — *form 1 the VALU form, 2 the matrix-core form — and the rows
+ * one whole stride of its full grid covers (tests place a row just past it). */
+int mvdb_bits_geometry(const mvdb_bits* ix, int nq, int k, int* form, int64_t* stride_rows);
+
+/* Append n rows: packed x[n, d_bits / 8] bytes, or fp32 x[n, d_bits] packed on the device; host memory (C-contiguous,
+ * uploaded in chunks) or dense device memory on the same GPU. */
+int mvdb_bits_add(mvdb_bits* ix, const uint8_t* x_host, int64_t n);
+int mvdb_bits_add_device(mvdb_bits* ix, const uint8_t* x_dev, int64_t n);
+int mvdb_bits_add_float(mvdb_bits* ix, const float* x_host, int64_t n);
+int mvdb_bits_add_float_device(mvdb_bits* ix, const float* x_dev, int64_t n);
+
+/* Rows [row0, row0 + n) back to the host: rows_host[n, d_bits / 8]. */
+int mvdb_bits_get_rows(const mvdb_bits* ix, int64_t row0, int64_t n, uint8_t* rows_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_bits_remove_rows(mvdb_bits* ix, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows in place.  rows_host is a host array, each row in [0, ntotal), any order; a
+ * duplicate, an out-of-range row or a NULL pointer with m > 0 is MVDB_ERR_ARG and leaves the index untouched. */
+int mvdb_bits_set_rows(mvdb_bits* ix, const int64_t* rows_host, const uint8_t* x_host, int64_t m);
+int mvdb_bits_set_rows_device(mvdb_bits* ix, const int64_t* rows_host, const uint8_t* x_dev, int64_t m);
+int mvdb_bits_set_rows_float(mvdb_bits* ix, const int64_t* rows_host, const float* x_host, int64_t m);
+int mvdb_bits_set_rows_float_device(mvdb_bits* ix, const int64_t* rows_host, const float* x_dev, int64_t m);
+
+/* k nearest rows by Hamming distance for nq queries: packed q[nq, d_bits / 8], or fp32 q[nq, d_bits] (_float). */
+int mvdb_bits_search(const mvdb_bits* ix, const uint8_t* q_host, int nq, int k, const uint64_t* mask_host, int32_t* D_host,
+                     int64_t* I_host);
+int mvdb_bits_search_float(const mvdb_bits* ix, const float* q_host, int nq, int k, const uint64_t* mask_host,
+                           int32_t* D_host, int64_t* I_host);
+/* The same through a chosen form: 0 as mvdb_bits_search, 1 the VALU form (passes of 8 queries), 2 the matrix-core form.
+ * For the benchmark that sets the crossover, and for tests of a form outside its range. */
+int mvdb_bits_search_form(const mvdb_bits* ix, const uint8_t* q_host, int nq, int k, const uint64_t* mask_host, int form,
+                          int32_t* D_host, int64_t* I_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_bits_search_device(const mvdb_bits* ix, const uint8_t* q_dev, int nq, int k, const uint64_t* mask_dev,
+                            int32_t* D_dev, int64_t* I_dev, void* stream);
+int mvdb_bits_search_float_device(const mvdb_bits* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev,
+                                  int32_t* D_dev, int64_t* I_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

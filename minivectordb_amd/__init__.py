@@ -12,7 +12,7 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
-           "EmbeddingModel", "AlternativeModel"]
+           "BinaryVectorDatabase", "EmbeddingModel", "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -28,6 +28,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "DistributedShardedVectorDatabase":
         from .distributed import DistributedShardedVectorDatabase
         return DistributedShardedVectorDatabase
+    if name == "BinaryVectorDatabase":
+        from .binary_vector_database import BinaryVectorDatabase
+        return BinaryVectorDatabase
     if name in ("EmbeddingModel", "AlternativeModel"):
         from . import embedding_model
         return getattr(embedding_model, name)

@@ -286,6 +286,30 @@ PROTOTYPES = {
     "mvdb_cos8_search_rowset": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_cos8_search_rowset_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64,
                                                       c_vp, c_vp, c_vp]),
+    # binary index (bits.hip)
+    "mvdb_bits_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_bits_free": (ctypes.c_int, [c_vp]),
+    "mvdb_bits_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_bits_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_bits_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_bits_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_bits_geometry": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int64)]),
+    "mvdb_bits_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_add_float": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_add_float_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_get_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "mvdb_bits_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_set_rows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_set_rows_float": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_set_rows_float_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_bits_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_bits_search_float": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_bits_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_bits_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_bits_search_float_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -1618,6 +1642,152 @@ class Cos8RowSet:
             self.close()
         except Exception:
             pass
+
+
+class BitsIndex:
+    """mvdb_bits*: packed bit rows on the device, exact Hamming top-k (include/mvdb.h "binary index").  Rows and queries are
+    uint8 [n, d_bits / 8] (opaque bytes) or, through the *_float methods, float32 [n, d_bits] sign-packed on the device
+    (np.packbits(x > 0) layout).  D int32 ascending, I int64 rows, ties to the lower row; missing slots -1 / INT32_MAX."""
+
+    FORM_AUTO, FORM_VALU, FORM_MFMA = 0, 1, 2
+
+    def __init__(self, d_bits, device=0):
+        self._h = ctypes.c_void_p()
+        self.d_bits = int(d_bits)
+        self.row_bytes = self.d_bits // 8
+        self.device = device
+        check(lib().mvdb_bits_create(self.d_bits, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_bits_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_bits_ntotal(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_bits_dim(self._h))
+
+    def reset(self):
+        check(lib().mvdb_bits_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_bits_reserve(self._h, int(n)))
+
+    def geometry(self, nq, k):
+        """(form, stride_rows): the form a search of this shape takes (FORM_VALU | FORM_MFMA) and the rows one whole stride
+        of its full grid covers."""
+        form, stride = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib().mvdb_bits_geometry(self._h, int(nq), int(k), ctypes.byref(form), ctypes.byref(stride)))
+        return form.value, stride.value
+
+    def _packed(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.uint8)))
+        if x.ndim != 2 or x.shape[1] != self.row_bytes:
+            raise ValueError(f"expected [n,{self.row_bytes}] uint8, got {x.shape}")
+        return x
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d_bits:
+            raise ValueError(f"expected [n,{self.d_bits}] float32, got {x.shape}")
+        return x
+
+    def _rows(self, rows, m):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        return rows
+
+    def _mask(self, mask_words):
+        if mask_words is None:
+            return None, ctypes.c_void_p()
+        mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+        if mask_words.shape[0] < (self.ntotal + 63) // 64:
+            raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+        return mask_words, _ptr(mask_words)
+
+    def add(self, x):
+        x = self._packed(x)
+        check(lib().mvdb_bits_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_float(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_bits_add_float(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_bits_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def add_float_device(self, ptr, n):
+        check(lib().mvdb_bits_add_float_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def get_rows(self, row0, n):
+        rows = np.empty((int(n), self.row_bytes), dtype=np.uint8)
+        check(lib().mvdb_bits_get_rows(self._h, int(row0), int(n), _ptr(rows)))
+        return rows
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_bits_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x):
+        x = self._packed(x)
+        rows = self._rows(rows, x.shape[0])
+        check(lib().mvdb_bits_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_float(self, rows, x):
+        x = self._floats(x)
+        rows = self._rows(rows, x.shape[0])
+        check(lib().mvdb_bits_set_rows_float(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_device(self, rows, x_ptr, m):
+        rows = self._rows(rows, m)
+        check(lib().mvdb_bits_set_rows_device(self._h, _ptr(rows), ctypes.c_void_p(x_ptr), int(m)))
+
+    def set_rows_float_device(self, rows, x_ptr, m):
+        rows = self._rows(rows, m)
+        check(lib().mvdb_bits_set_rows_float_device(self._h, _ptr(rows), ctypes.c_void_p(x_ptr), int(m)))
+
+    def _out(self, nq, k):
+        return np.empty((nq, int(k)), dtype=np.int32), np.empty((nq, int(k)), dtype=np.int64)
+
+    def search(self, q, k, mask_words=None, form=FORM_AUTO):
+        """Packed queries; mask_words: `pack_row_mask`'s uint64 words (bit set = row selected) or None; form: FORM_VALU /
+        FORM_MFMA force a form (benchmarks, tests)."""
+        q = self._packed(q)
+        D, I = self._out(q.shape[0], k)
+        keep, mp = self._mask(mask_words)
+        if form:
+            check(lib().mvdb_bits_search_form(self._h, _ptr(q), q.shape[0], int(k), mp, int(form), _ptr(D), _ptr(I)))
+        else:
+            check(lib().mvdb_bits_search(self._h, _ptr(q), q.shape[0], int(k), mp, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_float(self, q, k, mask_words=None):
+        q = self._floats(q)
+        D, I = self._out(q.shape[0], k)
+        keep, mp = self._mask(mask_words)
+        check(lib().mvdb_bits_search_float(self._h, _ptr(q), q.shape[0], int(k), mp, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_bits_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
+                                            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def search_float_device(self, q_ptr, nq, k, D_ptr, I_ptr, mask_ptr=0, stream=0):
+        check(lib().mvdb_bits_search_float_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k),
+                                                  ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(D_ptr),
+                                                  ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
 
 
 class Comm:
