@@ -1254,6 +1254,77 @@ int mvdb_bits_search_device(const mvdb_bits* ix, const uint8_t* q_dev, int nq, i
 int mvdb_bits_search_float_device(const mvdb_bits* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev,
                                   int32_t* D_dev, int64_t* I_dev, void* stream);
 
+/* ---- product-quantised index (csrc/pq.hip) -------------------------------------------------
+ * faiss.IndexPQ's place in the flat family: a row is M one-byte codes, each naming one of 256 centroids of its
+ * d / M-wide sub-vector; searched by asymmetric distance computation (ADC) from a 16-bit table held in LDS
+ * (DESIGN.md section 6v).
+ *
+ * Shape.  d <= 4096; M a multiple of 16 in [16, 256] that divides d; dsub = d / M in {1, 2, 4, 8, 16, 32}; metric
+ * MVDB_METRIC_IP or MVDB_METRIC_L2.  The device holds codes [n, M] bytes (a row is 1 to 16 whole 16-byte chunks) and
+ * codebooks [M, 256, dsub] fp32 — no fp32 rows.
+ * Encoding (add, and the assign step of train, under either metric): code[m] = argmin_c sum_j (x[m dsub + j] -
+ * cb[m][c][j])^2 in fp32, equal distances to the lower c, a sub-vector whose every distance is NaN gets code 0.  The
+ * summation order is unspecified.
+ * Query table, one launch per call.  t[m][c] = -q_m . cb[m][c] (IP) or |q_m - cb[m][c]|^2 (L2) in fp32; lo[m] = min_c
+ * t[m][c]; span = max_m (max_c t[m][c] - lo[m]); step = span / 65535 (1 if span == 0); u[m][c] = min(65535,
+ * rint((t[m][c] - lo[m]) / step)) as uint16; bias = sum_m lo[m] in fp32, ascending m.  A query whose table holds a
+ * non-finite value returns all padding.
+ * Score.  S(row) = sum_m u[m][code[row][m]], an integer <= 256 * 65535 < 2^24: candidates are ordered by smaller S,
+ * then the lower row, and every form and batch size returns the same bits.
+ * Results.  S_out int32 (may be NULL), I int64 rows, D = (float)((double)bias + (double)step * S) for L2 (ascending) and
+ * that value negated for IP (an estimate of q . x, best first); 1 <= k <= 64, a larger k is MVDB_ERR_ARG; missing slots
+ * are I = -1, S = INT32_MAX, D = FLT_MAX (L2) or -FLT_MAX (IP).
+ * mask: as mvdb_bits_search — host words in the host call, resident words in the device call.
+ * Codebooks.  set_codebooks and train are allowed only while ntotal == 0 (the stored codes name the centroids they
+ * were coded with); add, add_codes, train, lut and the searches without codebooks are MVDB_ERR_ARG.
+ * Threading: as the binary index — searches are re-entrant, mutators take the index exclusively on its own stream.
+ * Out of scope: set_rows (delete and store instead), OPQ rotations, re-ranking against the original vectors (the index
+ * holds none), any IVF coarse level. */
+typedef struct mvdb_pq mvdb_pq;
+int mvdb_pq_create(int d, int M, int metric, int device, mvdb_pq** out);
+int mvdb_pq_free(mvdb_pq* ix);
+int mvdb_pq_reset(mvdb_pq* ix);
+int mvdb_pq_reserve(mvdb_pq* ix, int64_t n);
+int64_t mvdb_pq_ntotal(const mvdb_pq* ix);
+int mvdb_pq_dim(const mvdb_pq* ix);
+int mvdb_pq_m(const mvdb_pq* ix);
+
+/* Codebooks to and from the host: cb_host[M, 256, dsub] fp32. */
+int mvdb_pq_set_codebooks(mvdb_pq* ix, const float* cb_host);
+int mvdb_pq_get_codebooks(const mvdb_pq* ix, float* cb_host);
+
+/* Lloyd's algorithm per sub-space under L2 on the device: starts from the codebooks now set and runs `iters` iterations
+ * (encode, then update) on the n <= 1,048,576 rows x_host[n, d], uploaded once.  The update adds the members of a
+ * centroid in fp64 in a fixed order — per-thread slices in row order, the slices in thread order — divides by the count
+ * in fp64 and rounds to fp32; a centroid without members keeps its value.  No floating-point atomics: bit-identical run
+ * to run, the rule mvdb_index_kmeans follows. */
+int mvdb_pq_train(mvdb_pq* ix, const float* x_host, int64_t n, int iters);
+
+/* Append n rows: fp32 x[n, d] encoded on the device (host or device memory), or codes[n, M] bytes as they come. */
+int mvdb_pq_add(mvdb_pq* ix, const float* x_host, int64_t n);
+int mvdb_pq_add_device(mvdb_pq* ix, const float* x_dev, int64_t n);
+int mvdb_pq_add_codes(mvdb_pq* ix, const uint8_t* codes_host, int64_t n);
+
+/* Codes of rows [row0, row0 + n) back to the host: codes_host[n, M]. */
+int mvdb_pq_get_codes(const mvdb_pq* ix, int64_t row0, int64_t n, uint8_t* codes_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_pq_remove_rows(mvdb_pq* ix, const int64_t* rows_host, int64_t m);
+
+/* For tests.  lut: the very tables the search launch reads for these queries, copied back and de-interleaved —
+ * lut_host[nq, M, 256] uint16, step_host[nq], bias_host[nq].  geometry: the queries a pass of a search of nq queries
+ * holds (1, 2 or 4) and the rows one whole stride of its full grid covers. */
+int mvdb_pq_lut(const mvdb_pq* ix, const float* q_host, int nq, uint16_t* lut_host, float* step_host, float* bias_host);
+int mvdb_pq_geometry(const mvdb_pq* ix, int nq, int k, int* queries_per_pass, int64_t* stride_rows);
+
+/* k best rows for nq fp32 queries q[nq, d]. */
+int mvdb_pq_search(const mvdb_pq* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
+                   int64_t* I_host, int32_t* S_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_pq_search_device(const mvdb_pq* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
+                          int64_t* I_dev, int32_t* S_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

@@ -12,7 +12,7 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
-           "BinaryVectorDatabase", "EmbeddingModel", "AlternativeModel"]
+           "BinaryVectorDatabase", "PQVectorDatabase", "EmbeddingModel", "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -31,6 +31,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "BinaryVectorDatabase":
         from .binary_vector_database import BinaryVectorDatabase
         return BinaryVectorDatabase
+    if name == "PQVectorDatabase":
+        from .pq_vector_database import PQVectorDatabase
+        return PQVectorDatabase
     if name in ("EmbeddingModel", "AlternativeModel"):
         from . import embedding_model
         return getattr(embedding_model, name)

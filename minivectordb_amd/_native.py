@@ -310,6 +310,27 @@ PROTOTYPES = {
     "mvdb_bits_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     "mvdb_bits_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_bits_search_float_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    # product-quantised index (pq.hip)
+    "mvdb_pq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_pq_free": (ctypes.c_int, [c_vp]),
+    "mvdb_pq_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_pq_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_pq_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_pq_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_pq_m": (ctypes.c_int, [c_vp]),
+    "mvdb_pq_set_codebooks": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_pq_get_codebooks": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_pq_train": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int]),
+    "mvdb_pq_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_pq_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_pq_add_codes": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_pq_get_codes": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "mvdb_pq_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_pq_lut": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_pq_geometry": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    "mvdb_pq_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_pq_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -1788,6 +1809,129 @@ class BitsIndex:
         check(lib().mvdb_bits_search_float_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k),
                                                   ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(D_ptr),
                                                   ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+
+class PQIndex:
+    """mvdb_pq*: product-quantised rows on the device, ADC top-k (include/mvdb.h "product-quantised index").  Rows and queries
+    are float32 [n, d]; a stored row is M code bytes.  search returns (D float32, I int64 rows, S int32 integer scores): smaller
+    S first, ties to the lower row; missing slots -1 / INT32_MAX / +-FLT_MAX."""
+
+    def __init__(self, d, M, metric=METRIC_IP, device=0):
+        self._h = ctypes.c_void_p()
+        self.d, self.M, self.metric, self.device = int(d), int(M), int(metric), device
+        check(lib().mvdb_pq_create(self.d, self.M, self.metric, device, ctypes.byref(self._h)))
+        self.dsub = self.d // self.M
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_pq_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_pq_ntotal(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_pq_dim(self._h))
+
+    @property
+    def m(self):
+        return int(lib().mvdb_pq_m(self._h))
+
+    def reset(self):
+        check(lib().mvdb_pq_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_pq_reserve(self._h, int(n)))
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def set_codebooks(self, cb):
+        cb = np.ascontiguousarray(cb, dtype=np.float32)
+        if cb.shape != (self.M, 256, self.dsub):
+            raise ValueError(f"expected codebooks [{self.M},256,{self.dsub}], got {cb.shape}")
+        check(lib().mvdb_pq_set_codebooks(self._h, _ptr(cb)))
+
+    def get_codebooks(self):
+        cb = np.empty((self.M, 256, self.dsub), dtype=np.float32)
+        check(lib().mvdb_pq_get_codebooks(self._h, _ptr(cb)))
+        return cb
+
+    def train(self, x, iters):
+        """`iters` iterations of Lloyd's algorithm per sub-space on the rows x, from the codebooks now set."""
+        x = self._floats(x)
+        check(lib().mvdb_pq_train(self._h, _ptr(x), x.shape[0], int(iters)))
+
+    def add(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_pq_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_pq_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def add_codes(self, codes):
+        codes = np.ascontiguousarray(np.atleast_2d(np.asarray(codes, dtype=np.uint8)))
+        if codes.ndim != 2 or codes.shape[1] != self.M:
+            raise ValueError(f"expected [n,{self.M}] uint8, got {codes.shape}")
+        check(lib().mvdb_pq_add_codes(self._h, _ptr(codes), codes.shape[0]))
+
+    def get_codes(self, row0, n):
+        codes = np.empty((int(n), self.M), dtype=np.uint8)
+        check(lib().mvdb_pq_get_codes(self._h, int(row0), int(n), _ptr(codes)))
+        return codes
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_pq_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def lut(self, q):
+        """(u uint16 [nq, M, 256], step [nq], bias [nq]): the tables a search of these queries reads."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        u = np.empty((nq, self.M, 256), dtype=np.uint16)
+        step, bias = np.empty(nq, dtype=np.float32), np.empty(nq, dtype=np.float32)
+        check(lib().mvdb_pq_lut(self._h, _ptr(q), nq, _ptr(u), _ptr(step), _ptr(bias)))
+        return u, step, bias
+
+    def geometry(self, nq, k):
+        """(queries per pass, stride_rows): the queries one pass of such a search holds and the rows one whole stride of its
+        full grid covers."""
+        per_pass, stride = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib().mvdb_pq_geometry(self._h, int(nq), int(k), ctypes.byref(per_pass), ctypes.byref(stride)))
+        return per_pass.value, stride.value
+
+    def search(self, q, k, mask_words=None):
+        """mask_words: `pack_row_mask`'s uint64 words (bit set = row selected) or None."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        S = np.empty((nq, int(k)), dtype=np.int32)
+        mp = ctypes.c_void_p()
+        if mask_words is not None:
+            mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+            if mask_words.shape[0] < (self.ntotal + 63) // 64:
+                raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+            mp = _ptr(mask_words)
+        check(lib().mvdb_pq_search(self._h, _ptr(q), nq, int(k), mp, _ptr(D), _ptr(I), _ptr(S)))
+        return D, I, S
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, S_ptr=0, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_pq_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
+                                          ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(S_ptr or None),
+                                          ctypes.c_void_p(stream)))
 
 
 class Comm:
