@@ -1325,6 +1325,84 @@ int mvdb_pq_search(const mvdb_pq* ix, const float* q_host, int nq, int k, const 
 int mvdb_pq_search_device(const mvdb_pq* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
                           int64_t* I_dev, int32_t* S_dev, void* stream);
 
+/* ---- 4-bit scalar-quantised index (csrc/sq4.hip) --------------------------------------------
+ * faiss.IndexScalarQuantizer(QT_4bit)'s place in the flat family: four bits per dimension, half of the int8 cosine
+ * index's bytes, searched with exact integer scores against an int8 query (DESIGN.md
+ * section 6w).
+ *
+ * Shape.  d is a multiple of 32 in [32, 4096]; a row is d / 2 bytes, 1 to 128 whole 16-byte chunks.  Byte j holds the
+ * code of dimension 2 j in its low nibble and that of 2 j + 1 in its high nibble (faiss' 4-bit packing).  The metric is
+ * the inner product.  No fp32 rows are kept.
+ * Ranges.  lo[d], hi[d] fp32, finite (a non-finite value is MVDB_ERR_ARG), from set_ranges or train, allowed only while
+ * ntotal == 0 (the stored codes were coded with them); add, add_codes, query and the searches without ranges are
+ * MVDB_ERR_ARG.  train: per-dimension min and max over the finite values of n <= 1,048,576 sample rows, on the device,
+ * independent of the order of the rows (a dimension without a finite value gets lo = hi = 0).  Derived once on the host in
+ * IEEE fp32 and uploaded: inv[i] = 15f / (hi[i] - lo[i]), s[i] = (hi[i] - lo[i]) / 15f; a dimension whose hi - lo is not
+ * a positive finite number gets inv = s = 0.
+ * Encode (add, set_rows).  u = (x[i] - lo[i]) * inv[i], one fp32 subtract and one fp32 multiply; the code is 15 if
+ * u >= 15, 0 if !(u > 0) (NaN, -inf and negatives), otherwise (int)rintf(u), ties to even.
+ * Query.  w[i] = q[i] * s[i] in fp32; amax = max |w[i]|; q8[i] = (int)rint((double)w[i] * (127.0 / (double)amax)) in
+ * [-127, 127], all zeros when amax == 0; step = (double)amax / 127.0; bias = sum (double)q[i] * (double)lo[i] in fp64,
+ * ascending i.  A query with a non-finite component, or a non-finite w, returns all padding.
+ * Score.  S(row) = sum q8[i] * code[row][i], an exact int32, |S| <= 127 * 15 * 4096 < 2^24: candidates are ordered by
+ * larger S, then the lower row, and every form and batch size returns the same bits.
+ * Results.  S_out int32 (may be NULL), I int64 rows, D = (float)(bias + step * S) in fp64 (the product rounded, then
+ * the sum): an estimate of q . x, best first; 1 <= k <= 64, a larger k is MVDB_ERR_ARG; missing slots are I = -1,
+ * S = INT32_MIN, D = -FLT_MAX.
+ * mask: as mvdb_bits_search — set bit = row selected; host words in the host call, resident words in the device call.
+ * Device pointers to fp32 rows and queries are 16-byte aligned.
+ * Threading: as the binary index — searches are re-entrant, mutators take the index exclusively on its own stream.
+ * Out of scope: L2; 6-bit or 8-bit codes; per-row scales; re-ranking against the original vectors (the index holds
+ * none); any IVF coarse level. */
+typedef struct mvdb_sq4 mvdb_sq4;
+int mvdb_sq4_create(int d, int device, mvdb_sq4** out);
+int mvdb_sq4_free(mvdb_sq4* ix);
+int mvdb_sq4_reset(mvdb_sq4* ix);
+int mvdb_sq4_reserve(mvdb_sq4* ix, int64_t n);
+int64_t mvdb_sq4_ntotal(const mvdb_sq4* ix);
+int mvdb_sq4_dim(const mvdb_sq4* ix);
+
+/* Ranges to and from the host: lo_host[d], hi_host[d] fp32.  train: x_host[n, d] fp32. */
+int mvdb_sq4_set_ranges(mvdb_sq4* ix, const float* lo_host, const float* hi_host);
+int mvdb_sq4_get_ranges(const mvdb_sq4* ix, float* lo_host, float* hi_host);
+int mvdb_sq4_train(mvdb_sq4* ix, const float* x_host, int64_t n);
+
+/* Append n rows: fp32 x[n, d] encoded on the device (host or device memory), or codes[n, d / 2] bytes as they come. */
+int mvdb_sq4_add(mvdb_sq4* ix, const float* x_host, int64_t n);
+int mvdb_sq4_add_device(mvdb_sq4* ix, const float* x_dev, int64_t n);
+int mvdb_sq4_add_codes(mvdb_sq4* ix, const uint8_t* codes_host, int64_t n);
+
+/* Codes of rows [row0, row0 + n) back to the host: codes_host[n, d / 2]. */
+int mvdb_sq4_get_codes(const mvdb_sq4* ix, int64_t row0, int64_t n, uint8_t* codes_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_sq4_remove_rows(mvdb_sq4* ix, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows in place, from fp32 rows (the encode kernel with a row list) or from codes.
+ * rows_host is a host array, each row in [0, ntotal), any order; a duplicate, an out-of-range row or a NULL pointer with
+ * m > 0 is MVDB_ERR_ARG and leaves the index untouched. */
+int mvdb_sq4_set_rows(mvdb_sq4* ix, const int64_t* rows_host, const float* x_host, int64_t m);
+int mvdb_sq4_set_rows_codes(mvdb_sq4* ix, const int64_t* rows_host, const uint8_t* codes_host, int64_t m);
+
+/* For tests.  query: the very int8 queries the scan reads for these fp32 queries, copied back and put in natural
+ * dimension order — q8_host[nq, d] —, with step_host[nq] and bias_host[nq] (fp64).  geometry: which form a search of nq
+ * queries and k results takes — *form 1 the VALU form, 2 the matrix-core form — and the rows one whole stride of its full
+ * grid covers. */
+int mvdb_sq4_query(const mvdb_sq4* ix, const float* q_host, int nq, int8_t* q8_host, double* step_host, double* bias_host);
+int mvdb_sq4_geometry(const mvdb_sq4* ix, int nq, int k, int* form, int64_t* stride_rows);
+
+/* k best rows for nq fp32 queries q[nq, d]. */
+int mvdb_sq4_search(const mvdb_sq4* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
+                    int64_t* I_host, int32_t* S_host);
+/* The same through a chosen form: 0 as mvdb_sq4_search, 1 the VALU form (passes of 4 queries), 2 the matrix-core form
+ * (d <= 2048, else MVDB_ERR_ARG).  For the benchmark that sets the hand-over, and for tests of a form outside its range. */
+int mvdb_sq4_search_form(const mvdb_sq4* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, int form,
+                         float* D_host, int64_t* I_host, int32_t* S_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_sq4_search_device(const mvdb_sq4* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
+                           int64_t* I_dev, int32_t* S_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

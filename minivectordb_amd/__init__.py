@@ -12,7 +12,7 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
-           "BinaryVectorDatabase", "PQVectorDatabase", "EmbeddingModel", "AlternativeModel"]
+           "BinaryVectorDatabase", "PQVectorDatabase", "SQ4VectorDatabase", "EmbeddingModel", "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -34,6 +34,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "PQVectorDatabase":
         from .pq_vector_database import PQVectorDatabase
         return PQVectorDatabase
+    if name == "SQ4VectorDatabase":
+        from .sq4_vector_database import SQ4VectorDatabase
+        return SQ4VectorDatabase
     if name in ("EmbeddingModel", "AlternativeModel"):
         from . import embedding_model
         return getattr(embedding_model, name)

@@ -331,6 +331,29 @@ PROTOTYPES = {
                                         ctypes.POINTER(ctypes.c_int64)]),
     "mvdb_pq_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_pq_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # 4-bit scalar-quantised index (sq4.hip)
+    "mvdb_sq4_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_sq4_free": (ctypes.c_int, [c_vp]),
+    "mvdb_sq4_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_sq4_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_sq4_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_sq4_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_sq4_set_ranges": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_sq4_get_ranges": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mvdb_sq4_train": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_add_codes": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_get_codes": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "mvdb_sq4_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_set_rows_codes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_sq4_query": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_sq4_geometry": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int64)]),
+    "mvdb_sq4_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_sq4_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_sq4_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -1932,6 +1955,151 @@ class PQIndex:
         check(lib().mvdb_pq_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
                                           ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(S_ptr or None),
                                           ctypes.c_void_p(stream)))
+
+
+class SQ4Index:
+    """mvdb_sq4*: rows of 4-bit codes on the device, exact integer top-k against an int8 query (include/mvdb.h "4-bit
+    scalar-quantised index").  Rows and queries are float32 [n, d]; a stored row is d / 2 bytes, dimension 2 j in the low nibble
+    of byte j.  search returns (D float32 estimates of q . x, I int64 rows, S int32 integer scores): larger S first, ties to the
+    lower row; missing slots -1 / INT32_MIN / -FLT_MAX."""
+
+    FORM_AUTO, FORM_VALU, FORM_MFMA = 0, 1, 2
+
+    def __init__(self, d, device=0):
+        self._h = ctypes.c_void_p()
+        self.d, self.row_bytes, self.device = int(d), int(d) // 2, device
+        check(lib().mvdb_sq4_create(self.d, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_sq4_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_sq4_ntotal(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_sq4_dim(self._h))
+
+    def reset(self):
+        check(lib().mvdb_sq4_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_sq4_reserve(self._h, int(n)))
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def _codes(self, codes):
+        codes = np.ascontiguousarray(np.atleast_2d(np.asarray(codes, dtype=np.uint8)))
+        if codes.ndim != 2 or codes.shape[1] != self.row_bytes:
+            raise ValueError(f"expected [n,{self.row_bytes}] uint8, got {codes.shape}")
+        return codes
+
+    def _rows(self, rows, m):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        return rows
+
+    def set_ranges(self, lo, hi):
+        lo, hi = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
+        if lo.shape != (self.d,) or hi.shape != (self.d,):
+            raise ValueError(f"expected lo and hi of {self.d} floats, got {lo.shape} and {hi.shape}")
+        check(lib().mvdb_sq4_set_ranges(self._h, _ptr(lo), _ptr(hi)))
+
+    def get_ranges(self):
+        lo, hi = np.empty(self.d, dtype=np.float32), np.empty(self.d, dtype=np.float32)
+        check(lib().mvdb_sq4_get_ranges(self._h, _ptr(lo), _ptr(hi)))
+        return lo, hi
+
+    def train(self, x):
+        """Ranges = the per-dimension min and max over the finite values of the rows x, found on the device."""
+        x = self._floats(x)
+        check(lib().mvdb_sq4_train(self._h, _ptr(x), x.shape[0]))
+
+    def add(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_sq4_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_sq4_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def add_codes(self, codes):
+        codes = self._codes(codes)
+        check(lib().mvdb_sq4_add_codes(self._h, _ptr(codes), codes.shape[0]))
+
+    def get_codes(self, row0, n):
+        codes = np.empty((int(n), self.row_bytes), dtype=np.uint8)
+        check(lib().mvdb_sq4_get_codes(self._h, int(row0), int(n), _ptr(codes)))
+        return codes
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_sq4_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x):
+        x = self._floats(x)
+        rows = self._rows(rows, x.shape[0])
+        check(lib().mvdb_sq4_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_codes(self, rows, codes):
+        codes = self._codes(codes)
+        rows = self._rows(rows, codes.shape[0])
+        check(lib().mvdb_sq4_set_rows_codes(self._h, _ptr(rows), _ptr(codes), rows.shape[0]))
+
+    def query(self, q):
+        """(q8 int8 [nq, d] in dimension order, step float64 [nq], bias float64 [nq]): what a search of these queries scans with."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        q8 = np.empty((nq, self.d), dtype=np.int8)
+        step, bias = np.empty(nq, dtype=np.float64), np.empty(nq, dtype=np.float64)
+        check(lib().mvdb_sq4_query(self._h, _ptr(q), nq, _ptr(q8), _ptr(step), _ptr(bias)))
+        return q8, step, bias
+
+    def geometry(self, nq, k):
+        """(form, stride_rows): the form a search of this shape takes (FORM_VALU | FORM_MFMA) and the rows one whole stride
+        of its full grid covers."""
+        form, stride = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib().mvdb_sq4_geometry(self._h, int(nq), int(k), ctypes.byref(form), ctypes.byref(stride)))
+        return form.value, stride.value
+
+    def search(self, q, k, mask_words=None, form=FORM_AUTO):
+        """mask_words: `pack_row_mask`'s uint64 words (bit set = row selected) or None; form: FORM_VALU / FORM_MFMA force a
+        form (benchmarks, tests)."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        S = np.empty((nq, int(k)), dtype=np.int32)
+        mp = ctypes.c_void_p()
+        if mask_words is not None:
+            mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+            if mask_words.shape[0] < (self.ntotal + 63) // 64:
+                raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+            mp = _ptr(mask_words)
+        if form:
+            check(lib().mvdb_sq4_search_form(self._h, _ptr(q), nq, int(k), mp, int(form), _ptr(D), _ptr(I), _ptr(S)))
+        else:
+            check(lib().mvdb_sq4_search(self._h, _ptr(q), nq, int(k), mp, _ptr(D), _ptr(I), _ptr(S)))
+        return D, I, S
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, S_ptr=0, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_sq4_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
+                                           ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(S_ptr or None),
+                                           ctypes.c_void_p(stream)))
 
 
 class Comm:
