@@ -1403,6 +1403,82 @@ int mvdb_sq4_search_form(const mvdb_sq4* ix, const float* q_host, int nq, int k,
 int mvdb_sq4_search_device(const mvdb_sq4* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
                            int64_t* I_dev, int32_t* S_dev, void* stream);
 
+/* ---- RaBitQ index (csrc/rabitq.hip) ---------------------------------------------------------
+ * faiss.IndexRaBitQ's place in the flat family: the sign bits of the centred, rotated row and two floats, scored against a
+ * query cut to 4 bits into an estimate of the inner product.
+ *
+ * Shape.  d is a multiple of 128 in [128, 4096]; a code row is d / 8 bytes in numpy.packbits order, 1 to 32 whole 16-byte
+ * chunks.  The metric is the inner product.  No fp32 rows are kept.
+ * Rotation.  signs[R, d / 8] bytes in packbits order, a set bit negates; R in [0, 4], R = 0 the identity.  P is the largest
+ * power of two <= d.  Round r negates the marked dimensions, then transforms the window [0, P) (r even) or [d - P, d)
+ * (r odd): for h = 1, 2, 4, ..., P / 2 in that order every pair (i, i + h) with (i & h) == 0 becomes (fl(a + b), fl(a - b))
+ * in fp32, then every window element is multiplied once by the fp32 nearest 1 / sqrt(P).  Elements outside the window pass.
+ * The rotation and the centroid c[d] (default: R = 0, c = 0) are accepted only while ntotal == 0.
+ * Encode (add, set_rows).  r = rotate(fl(x - c)); code bit i = r[i] > 0 (false for NaN and -0); f = |r|^2 / |r|_1 (0 when
+ * |r|_1 = 0) and g = <x - c, c>, the sums in fp64 over products exact in fp64, the quotient in fp64, each rounded to fp32
+ * once.  A row is its code and (f, g); B = 2 popcount(code) - d is derived by the library.
+ * Query.  q' = rotate(fl(q - c)); lo = min q', hi = max q'; delta = fl(fl(hi - lo) / 15), inv = fl(15 / fl(hi - lo)), both
+ * 0 unless hi - lo > 0; u[i] = clamp(rintf(fl(fl(q'[i] - lo) * inv)), 0, 15); U = sum u; qc = <q, c> in fp64, rounded once.
+ * Score.  T = sum u[i] code[i] (an exact integer), A = 2 T - U,
+ *     S = fl(fl(f * fl(fl(delta * (float)A) + fl(lo * (float)B))) + fl(g + qc)),
+ * every operation a single unfused fp32 one: candidates are ordered by larger S, then the lower row, and every form and
+ * batch size returns the same bits.  A NaN score is no candidate.
+ * Results.  I int64 rows, D = S, best first; 1 <= k <= 64, a larger k is MVDB_ERR_ARG; missing slots are I = -1,
+ * D = -FLT_MAX (as the 4-bit index).
+ * mask: as mvdb_bits_search — set bit = row selected; host words in the host call, resident words in the device call.
+ * Device pointers to fp32 rows and queries are 16-byte aligned.
+ * Threading: as the binary index — searches are re-entrant, mutators take the index exclusively on its own stream.
+ * Out of scope: L2; multi-bit codes; the error bound and any re-ranking; k > 64; any IVF coarse level. */
+typedef struct mvdb_rbq mvdb_rbq;
+int mvdb_rbq_create(int d, int device, mvdb_rbq** out);
+int mvdb_rbq_free(mvdb_rbq* ix);
+int mvdb_rbq_reset(mvdb_rbq* ix);
+int mvdb_rbq_reserve(mvdb_rbq* ix, int64_t n);
+int64_t mvdb_rbq_ntotal(const mvdb_rbq* ix);
+int mvdb_rbq_dim(const mvdb_rbq* ix);
+
+/* signs_host[rounds, d / 8] (may be NULL when rounds == 0; get: signs_host holds 4 d / 8 bytes or is NULL); c_host[d]. */
+int mvdb_rbq_set_rotation(mvdb_rbq* ix, const uint8_t* signs_host, int rounds);
+int mvdb_rbq_get_rotation(const mvdb_rbq* ix, uint8_t* signs_host, int* rounds);
+int mvdb_rbq_set_centroid(mvdb_rbq* ix, const float* c_host);
+int mvdb_rbq_get_centroid(const mvdb_rbq* ix, float* c_host);
+
+/* Append n rows: fp32 x[n, d] encoded on the device (host or device memory), or rows already encoded — codes[n, d / 8]
+ * and factors[n, 2] = (f, g) — as they come (persistence). */
+int mvdb_rbq_add(mvdb_rbq* ix, const float* x_host, int64_t n);
+int mvdb_rbq_add_device(mvdb_rbq* ix, const float* x_dev, int64_t n);
+int mvdb_rbq_add_codes(mvdb_rbq* ix, const uint8_t* codes_host, const float* factors_host, int64_t n);
+
+/* Rows [row0, row0 + n) back to the host: codes_host[n, d / 8], factors_host[n, 2]. */
+int mvdb_rbq_get_rows(const mvdb_rbq* ix, int64_t row0, int64_t n, uint8_t* codes_host, float* factors_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_rbq_remove_rows(mvdb_rbq* ix, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows in place from fp32 rows in host or device memory (the encode kernel with a row
+ * list).  rows_host is a host array, each row in [0, ntotal), any order; a duplicate, an out-of-range row or a NULL
+ * pointer with m > 0 is MVDB_ERR_ARG and leaves the index untouched. */
+int mvdb_rbq_set_rows(mvdb_rbq* ix, const int64_t* rows_host, const float* x_host, int64_t m);
+int mvdb_rbq_set_rows_device(mvdb_rbq* ix, const int64_t* rows_host, const float* x_dev, int64_t m);
+
+/* For tests.  query: the very 4-bit queries the scan reads for these fp32 queries, copied back and put in natural
+ * dimension order — u_host[nq, d] —, with params_host[nq, 4] = (lo, delta, qc, (float)U).  geometry: which form a search
+ * of nq queries and k results takes — *form 1 the VALU form, 2 the matrix-core form — and the rows one whole stride of
+ * its full grid covers. */
+int mvdb_rbq_query(const mvdb_rbq* ix, const float* q_host, int nq, uint8_t* u_host, float* params_host);
+int mvdb_rbq_geometry(const mvdb_rbq* ix, int nq, int k, int* form, int64_t* stride_rows);
+
+/* k best rows for nq fp32 queries q[nq, d]. */
+int mvdb_rbq_search(const mvdb_rbq* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
+                    int64_t* I_host);
+/* The same through a chosen form: 0 as mvdb_rbq_search, 1 the VALU form (passes of 4 queries), 2 the matrix-core form. */
+int mvdb_rbq_search_form(const mvdb_rbq* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, int form,
+                         float* D_host, int64_t* I_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_rbq_search_device(const mvdb_rbq* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
+                           int64_t* I_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

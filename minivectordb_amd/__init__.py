@@ -12,7 +12,8 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
-           "BinaryVectorDatabase", "PQVectorDatabase", "SQ4VectorDatabase", "EmbeddingModel", "AlternativeModel"]
+           "BinaryVectorDatabase", "PQVectorDatabase", "SQ4VectorDatabase", "RabitqVectorDatabase", "EmbeddingModel",
+           "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -37,6 +38,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "SQ4VectorDatabase":
         from .sq4_vector_database import SQ4VectorDatabase
         return SQ4VectorDatabase
+    if name == "RabitqVectorDatabase":
+        from .rabitq_vector_database import RabitqVectorDatabase
+        return RabitqVectorDatabase
     if name in ("EmbeddingModel", "AlternativeModel"):
         from . import embedding_model
         return getattr(embedding_model, name)

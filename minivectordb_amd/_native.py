@@ -354,6 +354,30 @@ PROTOTYPES = {
     "mvdb_sq4_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "mvdb_sq4_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_sq4_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # RaBitQ index (rabitq.hip)
+    "mvdb_rbq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_rbq_free": (ctypes.c_int, [c_vp]),
+    "mvdb_rbq_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_rbq_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_rbq_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_rbq_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_rbq_set_rotation": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
+    "mvdb_rbq_get_rotation": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_int)]),
+    "mvdb_rbq_set_centroid": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_rbq_get_centroid": (ctypes.c_int, [c_vp, c_vp]),
+    "mvdb_rbq_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_add_codes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_get_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
+    "mvdb_rbq_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_set_rows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_rbq_query": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_rbq_geometry": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int64)]),
+    "mvdb_rbq_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_rbq_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_rbq_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -2100,6 +2124,154 @@ class SQ4Index:
         check(lib().mvdb_sq4_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
                                            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(S_ptr or None),
                                            ctypes.c_void_p(stream)))
+
+
+class RabitqIndex:
+    """mvdb_rbq*: the sign bits of centred, rotated rows on the device, scored against a 4-bit query into an estimate of the
+    inner product (include/mvdb.h "RaBitQ index").  Rows and queries are float32 [n, d]; a stored row is d / 8 code bytes in
+    numpy.packbits order and the factors (f, g).  search returns (D float32 scores, I int64 rows): larger score first, ties to
+    the lower row; missing slots -FLT_MAX / -1."""
+
+    FORM_AUTO, FORM_VALU, FORM_MFMA = 0, 1, 2
+
+    def __init__(self, d, device=0):
+        self._h = ctypes.c_void_p()
+        self.d, self.row_bytes, self.device = int(d), int(d) // 8, device
+        check(lib().mvdb_rbq_create(self.d, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_rbq_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_rbq_ntotal(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_rbq_dim(self._h))
+
+    def reset(self):
+        check(lib().mvdb_rbq_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_rbq_reserve(self._h, int(n)))
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def _rows(self, rows, m):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        return rows
+
+    def set_rotation(self, signs):
+        """signs: uint8 [R, d / 8], R in [0, 4] rounds of numpy.packbits sign bits (a set bit negates); R = 0: the identity."""
+        signs = np.ascontiguousarray(signs, dtype=np.uint8).reshape(-1, self.row_bytes)
+        check(lib().mvdb_rbq_set_rotation(self._h, _ptr(signs) if len(signs) else ctypes.c_void_p(), signs.shape[0]))
+
+    def get_rotation(self):
+        signs, rounds = np.zeros((4, self.row_bytes), dtype=np.uint8), ctypes.c_int(0)
+        check(lib().mvdb_rbq_get_rotation(self._h, _ptr(signs), ctypes.byref(rounds)))
+        return signs[:rounds.value].copy()
+
+    def set_centroid(self, c):
+        c = np.ascontiguousarray(c, dtype=np.float32)
+        if c.shape != (self.d,):
+            raise ValueError(f"expected a centroid of {self.d} floats, got {c.shape}")
+        check(lib().mvdb_rbq_set_centroid(self._h, _ptr(c)))
+
+    def get_centroid(self):
+        c = np.empty(self.d, dtype=np.float32)
+        check(lib().mvdb_rbq_get_centroid(self._h, _ptr(c)))
+        return c
+
+    def add(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_rbq_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_rbq_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def add_codes(self, codes, factors):
+        """Rows already encoded: codes uint8 [n, d / 8], factors float32 [n, 2] = (f, g)."""
+        codes = np.ascontiguousarray(np.atleast_2d(np.asarray(codes, dtype=np.uint8)))
+        factors = np.ascontiguousarray(np.atleast_2d(np.asarray(factors, dtype=np.float32)))
+        if codes.shape[1] != self.row_bytes or factors.shape != (codes.shape[0], 2):
+            raise ValueError(f"expected [n,{self.row_bytes}] uint8 and [n,2] float32, got {codes.shape} and {factors.shape}")
+        check(lib().mvdb_rbq_add_codes(self._h, _ptr(codes), _ptr(factors), codes.shape[0]))
+
+    def get_rows(self, row0, n):
+        """(codes uint8 [n, d / 8], factors float32 [n, 2]) of rows [row0, row0 + n)."""
+        codes = np.empty((int(n), self.row_bytes), dtype=np.uint8)
+        factors = np.empty((int(n), 2), dtype=np.float32)
+        check(lib().mvdb_rbq_get_rows(self._h, int(row0), int(n), _ptr(codes), _ptr(factors)))
+        return codes, factors
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_rbq_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x):
+        x = self._floats(x)
+        rows = self._rows(rows, x.shape[0])
+        check(lib().mvdb_rbq_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_device(self, rows, ptr):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_rbq_set_rows_device(self._h, _ptr(rows), ctypes.c_void_p(ptr), rows.shape[0]))
+
+    def query(self, q):
+        """(u uint8 [nq, d] in dimension order, params float32 [nq, 4] = lo, delta, qc, U): what a search of these queries
+        scans with."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        u = np.empty((nq, self.d), dtype=np.uint8)
+        params = np.empty((nq, 4), dtype=np.float32)
+        check(lib().mvdb_rbq_query(self._h, _ptr(q), nq, _ptr(u), _ptr(params)))
+        return u, params
+
+    def geometry(self, nq, k):
+        """(form, stride_rows): the form a search of this shape takes (FORM_VALU | FORM_MFMA) and the rows one whole stride
+        of its full grid covers."""
+        form, stride = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib().mvdb_rbq_geometry(self._h, int(nq), int(k), ctypes.byref(form), ctypes.byref(stride)))
+        return form.value, stride.value
+
+    def search(self, q, k, mask_words=None, form=FORM_AUTO):
+        """mask_words: `pack_row_mask`'s uint64 words (bit set = row selected) or None; form: FORM_VALU / FORM_MFMA force a
+        form (benchmarks, tests)."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        mp = ctypes.c_void_p()
+        if mask_words is not None:
+            mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+            if mask_words.shape[0] < (self.ntotal + 63) // 64:
+                raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+            mp = _ptr(mask_words)
+        if form:
+            check(lib().mvdb_rbq_search_form(self._h, _ptr(q), nq, int(k), mp, int(form), _ptr(D), _ptr(I)))
+        else:
+            check(lib().mvdb_rbq_search(self._h, _ptr(q), nq, int(k), mp, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_rbq_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
+                                           ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
 
 
 class Comm:
