@@ -1479,6 +1479,80 @@ int mvdb_rbq_search_form(const mvdb_rbq* ix, const float* q_host, int nq, int k,
 int mvdb_rbq_search_device(const mvdb_rbq* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
                            int64_t* I_dev, void* stream);
 
+/* ---- MX INDEX (csrc/mx.hip) -----------------------------------------------------------------
+ * OCP microscaling rows — MXFP4 (4.25 bits per dimension) or MXFP8 (8.25) — scored on CDNA4's scaled matrix cores,
+ * v_mfma_scale_f32_16x16x128_f8f6f4, which takes the stored blocks as operands: no expansion of codes on the way
+ * (DESIGN.md section 6y).
+ *
+ * Shape.  format is 4 (MXFP4: E2M1 elements) or 8 (MXFP8: E4M3 elements), anything else MVDB_ERR_ARG; d is a multiple of
+ * 128 in [128, 4096] (one MFMA K step).  The metric is the inner product.  No fp32 rows are kept.  No training.
+ * Stored form, as seen from the host (add_codes / get_codes).  codes[n, d * format / 8] bytes — FP4: byte j holds
+ * dimension 2 j in its low nibble and 2 j + 1 in its high nibble; FP8: byte i is dimension i — and scales[n, d / 32]
+ * E8M0 bytes, byte = exponent + 127, one per block of 32 dimensions.
+ * Encode (add, add_device, set_rows).  Per block of 32 dimensions: amax = the largest |x| over the block's finite values;
+ * e = floor(log2(amax)) - emax, emax = 2 (E2M1) or 8 (E4M3), clamped to [-127, 127], e = 0 when amax == 0; u = x * 2^-e
+ * (exact); u is clamped to +-6 (E2M1) or +-448 (E4M3) in fp32 and then rounded to the nearest value of the element grid,
+ * ties to the even code; the sign bit of x is kept (a negative value that rounds to zero is -0: 0x8 / 0x80).  NaN becomes
+ * code 0, +-inf saturates.  The scale byte 0xFF (E8M0 NaN) and the E4M3 NaN codes 0x7F / 0xFF are never written;
+ * add_codes and set_rows_codes reject a scale byte 0xFF, and for FP8 a NaN element code, with MVDB_ERR_ARG.
+ * Query.  Every fp32 query is encoded per call as MXFP8 by the same rule with E4M3, whatever the row format.  A query
+ * with a non-finite component returns all padding.
+ * Score.  S(row, q) = sum over blocks 2^(ex + eq) sum_i a_i b_i, formed by the scaled MFMA into one fp32 accumulator per
+ * (row, query), K ascending in steps of 128.  One instruction shape (16x16x128) serves every batch size, so a query's
+ * result does not depend on how many queries share its call.  Against the exact dot product S64 of the decoded values,
+ * the bound stated for every d, and asserted by the tests at every d, is |S - S64| <= gamma sum |a b| with gamma =
+ * 4 (d + 16) 2^-24.  THE INSTRUCTION DOES NOT MEET IT AT d = 128.  Measured on an MI355X, the largest ratio in units of
+ * (d + 16) 2^-24 at d = 128 / 384 / 512 / 1024 / 2048 / 4096: MXFP4 2.44 / 0.84 / 0.52 / 0.24 / 0.09 / 0.03, MXFP8 4.56 /
+ * 1.40 / 1.10 / 0.62 / 0.16 / 0.06 — its error stays near 2e-5 (FP4 rows) and 4e-5 (FP8 rows) of sum |a b| at every
+ * width, so the bound holds with a factor of 2 from d = 384 up, and at d = 128 a slot can exceed it.  A NaN score (codes and scales from add_codes whose partial sums overflow to opposite infinities) is no candidate.
+ * Results.  D fp32 = S, best first; I int64 rows, ordered by larger S, then the lower row; 1 <= k <= 64, a larger k is
+ * MVDB_ERR_ARG; missing slots are I = -1, D = -FLT_MAX.
+ * mask: as mvdb_sq4_search — set bit = row selected; host words in the host call, resident words in the device call.
+ * Device pointers to fp32 rows and queries are 16-byte aligned.
+ * Threading: as the binary index — searches are re-entrant, mutators take the index exclusively on its own stream.
+ * Out of scope: MXFP6; L2; re-ranking; any IVF level; bit-identical agreement with numpy's summation order. */
+typedef struct mvdb_mx mvdb_mx;
+int mvdb_mx_create(int d, int format, int device, mvdb_mx** out);
+int mvdb_mx_free(mvdb_mx* ix);
+int mvdb_mx_reset(mvdb_mx* ix);
+int mvdb_mx_reserve(mvdb_mx* ix, int64_t n);
+int64_t mvdb_mx_ntotal(const mvdb_mx* ix);
+int mvdb_mx_dim(const mvdb_mx* ix);
+int mvdb_mx_format(const mvdb_mx* ix);
+
+/* Append n rows: fp32 x[n, d] encoded on the device (host or device memory), or rows already encoded — codes[n, d *
+ * format / 8] and scales[n, d / 32] — as they come (persistence). */
+int mvdb_mx_add(mvdb_mx* ix, const float* x_host, int64_t n);
+int mvdb_mx_add_device(mvdb_mx* ix, const float* x_dev, int64_t n);
+int mvdb_mx_add_codes(mvdb_mx* ix, const uint8_t* codes_host, const uint8_t* scales_host, int64_t n);
+
+/* Rows [row0, row0 + n) back to the host: codes_host[n, d * format / 8], scales_host[n, d / 32]. */
+int mvdb_mx_get_codes(const mvdb_mx* ix, int64_t row0, int64_t n, uint8_t* codes_host, uint8_t* scales_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_mx_remove_rows(mvdb_mx* ix, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows in place, from fp32 rows (the encode kernel with a row list) or from codes and
+ * scales.  rows_host is a host array, each row in [0, ntotal), any order; a duplicate, an out-of-range row or a NULL
+ * pointer with m > 0 is MVDB_ERR_ARG and leaves the index untouched. */
+int mvdb_mx_set_rows(mvdb_mx* ix, const int64_t* rows_host, const float* x_host, int64_t m);
+int mvdb_mx_set_rows_codes(mvdb_mx* ix, const int64_t* rows_host, const uint8_t* codes_host, const uint8_t* scales_host,
+                           int64_t m);
+
+/* For tests.  query: the very MXFP8 queries the scan reads for these fp32 queries, copied back and put in natural order —
+ * q8_host[nq, d] E4M3 bytes, scales_host[nq, d / 32] E8M0 bytes.  geometry: the queries one row read of a search of nq
+ * queries and k results serves (16, 32 or 64) and the rows one whole stride of its full grid covers. */
+int mvdb_mx_query(const mvdb_mx* ix, const float* q_host, int nq, uint8_t* q8_host, uint8_t* scales_host);
+int mvdb_mx_geometry(const mvdb_mx* ix, int nq, int k, int* queries_per_read, int64_t* stride_rows);
+
+/* k best rows for nq fp32 queries q[nq, d]. */
+int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
+                   int64_t* I_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_mx_search_device(const mvdb_mx* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
+                          int64_t* I_dev, void* stream);
+
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize
  *                                                minivectordb/embedding_model.py:66-70, :50-53 */

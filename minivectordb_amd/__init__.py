@@ -12,8 +12,8 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["VectorDatabase", "ShardedVectorDatabase", "ShardedVectorDatabaseUsearch", "DistributedShardedVectorDatabase",
-           "BinaryVectorDatabase", "PQVectorDatabase", "SQ4VectorDatabase", "RabitqVectorDatabase", "EmbeddingModel",
-           "AlternativeModel"]
+           "BinaryVectorDatabase", "PQVectorDatabase", "SQ4VectorDatabase", "RabitqVectorDatabase", "MXVectorDatabase",
+           "EmbeddingModel", "AlternativeModel"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU
@@ -41,6 +41,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "RabitqVectorDatabase":
         from .rabitq_vector_database import RabitqVectorDatabase
         return RabitqVectorDatabase
+    if name == "MXVectorDatabase":
+        from .mx_vector_database import MXVectorDatabase
+        return MXVectorDatabase
     if name in ("EmbeddingModel", "AlternativeModel"):
         from . import embedding_model
         return getattr(embedding_model, name)

@@ -378,6 +378,26 @@ PROTOTYPES = {
     "mvdb_rbq_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_rbq_search_form": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     "mvdb_rbq_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    # MX index (mx.hip)
+    "mvdb_mx_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_mx_free": (ctypes.c_int, [c_vp]),
+    "mvdb_mx_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_mx_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_mx_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_mx_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_mx_format": (ctypes.c_int, [c_vp]),
+    "mvdb_mx_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_add_codes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_get_codes": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
+    "mvdb_mx_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_set_rows_codes": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_mx_query": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_mx_geometry": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    "mvdb_mx_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_mx_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -2272,6 +2292,133 @@ class RabitqIndex:
         """All buffers are device pointers (ints); enqueues on `stream` and returns."""
         check(lib().mvdb_rbq_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
                                            ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+
+class MxIndex:
+    """mvdb_mx*: OCP microscaling rows on the device — MXFP4 (format 4) or MXFP8 (format 8) — scored against MXFP8 queries on the
+    scaled matrix cores (include/mvdb.h "MX INDEX").  Rows and queries are float32 [n, d]; a stored row is d * format / 8 code
+    bytes and d / 32 E8M0 scale bytes.  search returns (D float32 scores, I int64 rows): larger score first, ties to the lower
+    row; missing slots -FLT_MAX / -1."""
+
+    def __init__(self, d, format=4, device=0):
+        self._h = ctypes.c_void_p()
+        self.d, self.format, self.device = int(d), int(format), device
+        self.row_bytes, self.blocks = self.d * self.format // 8, self.d // 32
+        check(lib().mvdb_mx_create(self.d, self.format, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_mx_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_mx_ntotal(self._h))
+
+    @property
+    def dim(self):
+        return int(lib().mvdb_mx_dim(self._h))
+
+    def reset(self):
+        check(lib().mvdb_mx_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_mx_reserve(self._h, int(n)))
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def _coded(self, codes, scales):
+        codes = np.ascontiguousarray(np.atleast_2d(np.asarray(codes, dtype=np.uint8)))
+        scales = np.ascontiguousarray(np.atleast_2d(np.asarray(scales, dtype=np.uint8)))
+        if codes.shape[1] != self.row_bytes or scales.shape != (codes.shape[0], self.blocks):
+            raise ValueError(f"expected [n,{self.row_bytes}] and [n,{self.blocks}] uint8, got {codes.shape} and {scales.shape}")
+        return codes, scales
+
+    def _rows(self, rows, m):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != int(m):
+            raise ValueError(f"expected {int(m)} row numbers, got {rows.shape}")
+        return rows
+
+    def add(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_mx_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_mx_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def add_codes(self, codes, scales):
+        """Rows already encoded: codes uint8 [n, d * format / 8], scales uint8 [n, d / 32]."""
+        codes, scales = self._coded(codes, scales)
+        check(lib().mvdb_mx_add_codes(self._h, _ptr(codes), _ptr(scales), codes.shape[0]))
+
+    def get_codes(self, row0, n):
+        """(codes uint8 [n, d * format / 8], scales uint8 [n, d / 32]) of rows [row0, row0 + n)."""
+        codes = np.empty((int(n), self.row_bytes), dtype=np.uint8)
+        scales = np.empty((int(n), self.blocks), dtype=np.uint8)
+        check(lib().mvdb_mx_get_codes(self._h, int(row0), int(n), _ptr(codes), _ptr(scales)))
+        return codes, scales
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_mx_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x):
+        x = self._floats(x)
+        rows = self._rows(rows, x.shape[0])
+        check(lib().mvdb_mx_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def set_rows_codes(self, rows, codes, scales):
+        codes, scales = self._coded(codes, scales)
+        rows = self._rows(rows, codes.shape[0])
+        check(lib().mvdb_mx_set_rows_codes(self._h, _ptr(rows), _ptr(codes), _ptr(scales), rows.shape[0]))
+
+    def query(self, q):
+        """(E4M3 bytes uint8 [nq, d], E8M0 scales uint8 [nq, d / 32]), in dimension order: what a search of these queries
+        scans with."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        q8 = np.empty((nq, self.d), dtype=np.uint8)
+        scales = np.empty((nq, self.blocks), dtype=np.uint8)
+        check(lib().mvdb_mx_query(self._h, _ptr(q), nq, _ptr(q8), _ptr(scales)))
+        return q8, scales
+
+    def geometry(self, nq, k):
+        """(queries_per_read, stride_rows): the queries one row read of a search of this shape serves and the rows one whole
+        stride of its full grid covers."""
+        per, stride = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib().mvdb_mx_geometry(self._h, int(nq), int(k), ctypes.byref(per), ctypes.byref(stride)))
+        return per.value, stride.value
+
+    def search(self, q, k, mask_words=None):
+        """mask_words: `pack_row_mask`'s uint64 words (bit set = row selected) or None."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        mp = ctypes.c_void_p()
+        if mask_words is not None:
+            mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+            if mask_words.shape[0] < (self.ntotal + 63) // 64:
+                raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+            mp = _ptr(mask_words)
+        check(lib().mvdb_mx_search(self._h, _ptr(q), nq, int(k), mp, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_device(self, q_ptr, nq, k, D_ptr, I_ptr, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_mx_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
+                                          ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
 
 
 class Comm:
