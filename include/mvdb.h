@@ -1510,7 +1510,8 @@ int mvdb_rbq_search_device(const mvdb_rbq* ix, const float* q_dev, int nq, int k
  * mask: as mvdb_sq4_search — set bit = row selected; host words in the host call, resident words in the device call.
  * Device pointers to fp32 rows and queries are 16-byte aligned.
  * Threading: as the binary index — searches are re-entrant, mutators take the index exclusively on its own stream.
- * Out of scope: MXFP6; L2; re-ranking; any IVF level; bit-identical agreement with numpy's summation order. */
+ * Re-ranking: mvdb_mx_search_refined, in the section "REFINE STORE" below.
+ * Out of scope: MXFP6; L2; any IVF level; bit-identical agreement with numpy's summation order. */
 typedef struct mvdb_mx mvdb_mx;
 int mvdb_mx_create(int d, int format, int device, mvdb_mx** out);
 int mvdb_mx_free(mvdb_mx* ix);
@@ -1552,6 +1553,71 @@ int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const 
  * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
 int mvdb_mx_search_device(const mvdb_mx* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
                           int64_t* I_dev, void* stream);
+
+/* ---- REFINE STORE (csrc/refine.hip) ---------------------------------------------------------
+ * A compact copy of the rows, IEEE binary16, and the kernel that turns the candidates of ANY code index (binary, PQ,
+ * SQ4, RaBitQ, MX) into their exact top k: what faiss does with IndexRefineFlat (DESIGN.md
+ * section 6z).  The store knows nothing of the index in front of it; the caller keeps the two row numberings in step.
+ *
+ * Shape.  d is a multiple of 8 in [8, 4096] (a row is whole 16-byte chunks), anything else MVDB_ERR_ARG.  2 d bytes per
+ * row.  The metric is the inner product.
+ * Rows.  fp32 in, converted on the device by round-to-nearest-even, exactly numpy's astype(float16): overflow goes to
+ * +-inf, subnormals are kept, NaN stays NaN.  get_rows returns the stored bits.
+ * Candidates.  cand[nq, m] int64, 1 <= m <= 1024; nq <= 65535.  A candidate c counts only if 0 <= c < ntotal: -1, any
+ * other negative value and anything >= ntotal are skipped ON THE DEVICE — the device entry cannot see the ids on the host,
+ * and the kernel forms no address from an id it has not checked.  A row named twice in a query's list counts once.
+ * Score.  S = sum q_i * float(x_i), accumulated in fp32 by fmaf in an order that depends on d alone: a (query, row) pair
+ * has the same bits whatever nq, m, k, its position in the list, or the block that scored it.  Against the float64 product
+ * S64 of the stored values, |S - S64| <= (d + 16) 2^-24 sum |q_i x_i| (the any-order fp32 bound: derived, not measured).
+ * A NaN score is no candidate.
+ * Results.  D fp32 = S, best first; I int64 rows, larger S first, then the lower row; 1 <= k <= 64; missing slots are
+ * I = -1, D = -FLT_MAX.
+ * Device pointers to fp32 rows and queries are 16-byte aligned.
+ * Threading: as the MX index — re-ranks are re-entrant, mutators take the store exclusively on its own stream.
+ * Out of scope: fp32 or bf16 rows; rows in pinned host memory; L2. */
+typedef struct mvdb_refine mvdb_refine;
+int mvdb_refine_create(int d, int device, mvdb_refine** out);
+int mvdb_refine_free(mvdb_refine* st);
+int mvdb_refine_reset(mvdb_refine* st);
+int mvdb_refine_reserve(mvdb_refine* st, int64_t n);
+int64_t mvdb_refine_ntotal(const mvdb_refine* st);
+int mvdb_refine_dim(const mvdb_refine* st);
+
+/* Append n fp32 rows x[n, d] (host or device memory). */
+int mvdb_refine_add(mvdb_refine* st, const float* x_host, int64_t n);
+int mvdb_refine_add_device(mvdb_refine* st, const float* x_dev, int64_t n);
+
+/* Rows [row0, row0 + n) back to the host as binary16 bits: rows_host[n, d]. */
+int mvdb_refine_get_rows(const mvdb_refine* st, int64_t row0, int64_t n, uint16_t* rows_host);
+
+/* Remove the given rows (duplicates rejected); the remaining rows keep their relative order (np.delete numbering). */
+int mvdb_refine_remove_rows(mvdb_refine* st, const int64_t* rows_host, int64_t m);
+
+/* Overwrite the m listed stored rows in place from fp32 rows.  Argument rules as mvdb_mx_set_rows: a duplicate, an
+ * out-of-range row or a NULL pointer with m > 0 is MVDB_ERR_ARG and leaves the store untouched. */
+int mvdb_refine_set_rows(mvdb_refine* st, const int64_t* rows_host, const float* x_host, int64_t m);
+
+/* The k best of each query's m candidates, by the contract above. */
+int mvdb_refine_rerank(const mvdb_refine* st, const float* q_host, int nq, const int64_t* cand_host, int m, int k,
+                       float* D_host, int64_t* I_host);
+/* Every buffer in device memory, enqueued on `stream` (hipStream_t, NULL = legacy default stream), no host
+ * synchronisation; capturable into a hipGraph after one eager call of the same shape on that stream. */
+int mvdb_refine_rerank_device(const mvdb_refine* st, const float* q_dev, int nq, const int64_t* cand_dev, int m, int k,
+                              float* D_dev, int64_t* I_dev, void* stream);
+
+/* MX search with re-rank: fetch_k candidates by the MX score, their k best by the refine store's score (D, I as
+ * mvdb_refine_rerank).  1 <= k <= 64 and k <= fetch_k <= 1024; ntotal and d of the two objects must agree, else
+ * MVDB_ERR_ARG.  The MX scan keeps at most 64 rows per list, so the candidates are defined per SEGMENT of the rows.
+ * The candidate rule.  S = ceil(fetch_k / 64) segments and f = ceil(fetch_k / S).  With n = ntotal and L = 64 ceil(n /
+ * (64 S)), segment s is rows [s L, min(n, (s + 1) L)); a segment may be empty.  The candidates are the f best rows of
+ * every segment by the MX score, under the mask, ordered as mvdb_mx_search orders them.  fetch_k <= 64 means S = 1: the
+ * index's own top fetch_k.  A query with a non-finite component gets no candidates and returns all padding.
+ * The device entry runs S scans and the re-rank on `stream` with no host synchronisation, and is capturable after one
+ * eager call of the same shape on that stream (the workspaces of both objects are sized by that call). */
+int mvdb_mx_search_refined(const mvdb_mx* ix, const mvdb_refine* st, const float* q_host, int nq, int k, int fetch_k,
+                           const uint64_t* mask_host, float* D_host, int64_t* I_host);
+int mvdb_mx_search_refined_device(const mvdb_mx* ix, const mvdb_refine* st, const float* q_dev, int nq, int k, int fetch_k,
+                                  const uint64_t* mask_dev, float* D_dev, int64_t* I_dev, void* stream);
 
 /* ---- encoder (BERT-architecture sentence encoder: e5-small / e5-large) ---------------------
  * Replaces self.model(**batch_dict) + average_pool + F.normalize

@@ -398,6 +398,23 @@ PROTOTYPES = {
                                         ctypes.POINTER(ctypes.c_int64)]),
     "mvdb_mx_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "mvdb_mx_search_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mvdb_mx_search_refined": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "mvdb_mx_search_refined_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                     c_vp, c_vp]),
+    # refine store (refine.hip)
+    "mvdb_refine_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "mvdb_refine_free": (ctypes.c_int, [c_vp]),
+    "mvdb_refine_reset": (ctypes.c_int, [c_vp]),
+    "mvdb_refine_reserve": (ctypes.c_int, [c_vp, ctypes.c_int64]),
+    "mvdb_refine_ntotal": (ctypes.c_int64, [c_vp]),
+    "mvdb_refine_dim": (ctypes.c_int, [c_vp]),
+    "mvdb_refine_add": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_refine_add_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_refine_get_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "mvdb_refine_remove_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_refine_set_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64]),
+    "mvdb_refine_rerank": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "mvdb_refine_rerank_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     # encoder (encoder.hip)
     "mvdb_encoder_weight_count": (ctypes.c_int, [ctypes.POINTER(EncoderCfg)]),
     "mvdb_encoder_weight_name": (ctypes.c_char_p, [ctypes.POINTER(EncoderCfg), ctypes.c_int]),
@@ -2419,6 +2436,108 @@ class MxIndex:
         """All buffers are device pointers (ints); enqueues on `stream` and returns."""
         check(lib().mvdb_mx_search_device(self._h, ctypes.c_void_p(q_ptr), int(nq), int(k), ctypes.c_void_p(mask_ptr or None),
                                           ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+    def search_refined(self, q, k, store, fetch_k, mask_words=None):
+        """fetch_k candidates by the MX score (the candidate rule of include/mvdb.h "REFINE STORE"), their k best by the
+        `RefineStore`'s score.  (D, I) as `RefineStore.rerank`."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        mp = ctypes.c_void_p()
+        if mask_words is not None:
+            mask_words = np.ascontiguousarray(mask_words, dtype=np.uint64)
+            if mask_words.shape[0] < (self.ntotal + 63) // 64:
+                raise ValueError("the mask has fewer than (ntotal + 63) // 64 words")
+            mp = _ptr(mask_words)
+        check(lib().mvdb_mx_search_refined(self._h, store._h, _ptr(q), nq, int(k), int(fetch_k), mp, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_refined_device(self, q_ptr, nq, k, store, fetch_k, D_ptr, I_ptr, mask_ptr=0, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_mx_search_refined_device(self._h, store._h, ctypes.c_void_p(q_ptr), int(nq), int(k), int(fetch_k),
+                                                  ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(D_ptr),
+                                                  ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
+
+
+class RefineStore:
+    """mvdb_refine*: the rows as IEEE binary16 on the device, and the re-rank of a code index's candidates against them
+    (include/mvdb.h "REFINE STORE").  Rows and queries are float32 [n, d], d a multiple of 8 up to 4096.  rerank returns (D float32
+    scores, I int64 rows): larger score first, ties to the lower row; missing slots -FLT_MAX / -1."""
+
+    def __init__(self, d, device=0):
+        self._h = ctypes.c_void_p()
+        self.d, self.device = int(d), device
+        check(lib().mvdb_refine_create(self.d, device, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().mvdb_refine_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def ntotal(self):
+        return int(lib().mvdb_refine_ntotal(self._h))
+
+    def reset(self):
+        check(lib().mvdb_refine_reset(self._h))
+
+    def reserve(self, n):
+        check(lib().mvdb_refine_reserve(self._h, int(n)))
+
+    def _floats(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}] float32, got {x.shape}")
+        return x
+
+    def add(self, x):
+        x = self._floats(x)
+        check(lib().mvdb_refine_add(self._h, _ptr(x), x.shape[0]))
+
+    def add_device(self, ptr, n):
+        check(lib().mvdb_refine_add_device(self._h, ctypes.c_void_p(ptr), int(n)))
+
+    def get_rows(self, row0, n):
+        """The stored binary16 bits of rows [row0, row0 + n): uint16 [n, d] (view it as float16)."""
+        rows = np.empty((int(n), self.d), dtype=np.uint16)
+        check(lib().mvdb_refine_get_rows(self._h, int(row0), int(n), _ptr(rows)))
+        return rows
+
+    def remove_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        check(lib().mvdb_refine_remove_rows(self._h, _ptr(rows), rows.shape[0]))
+
+    def set_rows(self, rows, x):
+        x = self._floats(x)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1 or rows.shape[0] != x.shape[0]:
+            raise ValueError(f"expected {x.shape[0]} row numbers, got {rows.shape}")
+        check(lib().mvdb_refine_set_rows(self._h, _ptr(rows), _ptr(x), rows.shape[0]))
+
+    def rerank(self, q, cand, k):
+        """cand: int64 [nq, m] row numbers as any index's search returns them (-1 and out-of-range values are skipped, a row named
+        twice counts once), m <= 1024.  The k <= 64 best of each list."""
+        q = self._floats(q)
+        nq = q.shape[0]
+        cand = np.ascontiguousarray(np.atleast_2d(np.asarray(cand, dtype=np.int64)))
+        if cand.ndim != 2 or cand.shape[0] != nq:
+            raise ValueError(f"expected [{nq}, m] int64 candidates, got {cand.shape}")
+        D = np.empty((nq, int(k)), dtype=np.float32)
+        I = np.empty((nq, int(k)), dtype=np.int64)
+        check(lib().mvdb_refine_rerank(self._h, _ptr(q), nq, _ptr(cand), cand.shape[1], int(k), _ptr(D), _ptr(I)))
+        return D, I
+
+    def rerank_device(self, q_ptr, nq, cand_ptr, m, k, D_ptr, I_ptr, stream=0):
+        """All buffers are device pointers (ints); enqueues on `stream` and returns."""
+        check(lib().mvdb_refine_rerank_device(self._h, ctypes.c_void_p(q_ptr), int(nq), ctypes.c_void_p(cand_ptr), int(m), int(k),
+                                              ctypes.c_void_p(D_ptr), ctypes.c_void_p(I_ptr), ctypes.c_void_p(stream)))
 
 
 class Comm:

@@ -247,6 +247,11 @@ struct PinnedBuf {
     }
 };
 
+// refine.hip, for the code indexes' refined searches: the re-rank of mvdb_refine_rerank_device over lists that are still top-k
+// keys — keys_dev[nq, m], 0: no candidate, else key_row names the row — where a scan's merge left them.
+int refine_rerank_keys(const mvdb_refine* st, const float* q_dev, int nq, const uint64_t* keys_dev, int m, int k, float* D_dev,
+                       int64_t* I_dev, hipStream_t stream);
+
 // The stream a workspace created for itself (none for a caller's stream or the legacy default stream).  Declared as the FIRST
 // member of its workspace, so destroyed last: the workspace's buffers are freed before the stream they were used on goes.
 struct OwnedStream {

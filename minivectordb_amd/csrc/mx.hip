@@ -26,6 +26,7 @@ struct MxWorkspace {
     DevBuf<int> valid;
     DevBuf<uint64_t> mask;   // host API: the bitmap of this call
     DevBuf<uint64_t> cand;   // partial top-k lists
+    DevBuf<uint64_t> keys;   // refined search: the segments' merged lists, the re-rank's candidates
     DevBuf<int64_t> out;     // host API results, packed [I | D]
     PinnedBuf pin, pin_out;
     std::mutex use_mu;       // one search at a time per workspace
@@ -285,11 +286,48 @@ int search_core(const mvdb_mx* ix, MxWorkspace* ws, const float* q_dev, int nq, 
     return 0;
 }
 
+// The refined search (include/mvdb.h: the candidate rule): the rows in S segments of L, a scan and a merge per segment through
+// the one partial-list buffer — the stream orders them —, each merge leaving its f keys in the query's candidate list, then the
+// refine store's re-rank over those lists where they lie.
+int refined_core(const mvdb_mx* ix, const mvdb_refine* st, MxWorkspace* ws, const float* q_dev, int nq, int k, int fetch_k,
+                 const uint64_t* mask_dev, float* D, int64_t* I, bool capturing, hipStream_t s) {
+    if (ix->n == 0) return search_core(ix, ws, q_dev, nq, k, mask_dev, D, I, capturing, s);
+    const int S = (fetch_k + 63) / 64, f = (fetch_k + S - 1) / S;
+    const int64_t L = 64 * ((ix->n + 64ll * S - 1) / (64ll * S));
+    MVDB_TRY(build_queries(ix, ws, q_dev, nq, capturing, s));
+    const MxPlan p = mx_plan(ix->d, f, nq);
+    const int nblocks = mx_grid(std::min(L, ix->n), mx_tile_rows(ix->fmt), p.waves, p.per_cu, ix->device);
+    MVDB_TRY(ws_reserve(ws->cand, (size_t)nq * nblocks * f, capturing));
+    MVDB_TRY(ws_reserve(ws->keys, (size_t)nq * S * f, capturing));
+    for (int seg = 0; seg < S; ++seg) {
+        const int64_t r0 = seg * L;
+        const int64_t rows = std::min(ix->n, r0 + L) - r0;
+        if (rows > 0) {
+            MxScanArgs a{ix->codes + r0 * ix->rb, ix->scales + r0 * ix->sb, ix->d, rows, mask_dev ? mask_dev + r0 / 64 : nullptr,
+                         ws->q8.p, ws->qs.p, nq, f, ws->cand.p, r0};
+            MVDB_TRY(ix->fmt == 4 ? launch_scan<4>(ix, a, p, nblocks, s) : launch_scan<8>(ix, a, p, nblocks, s));
+        }
+        hipLaunchKernelGGL(mx_merge_keys_kernel, dim3(nq), dim3(kMxThreads), 0, s, ws->cand.p, rows > 0 ? nblocks : 0, f,
+                           ws->valid.p, seg, S, ws->keys.p);
+        MVDB_HIP(hipGetLastError());
+    }
+    return refine_rerank_keys(st, q_dev, nq, ws->keys.p, S * f, k, D, I, s);
+}
+
 int check_search(const mvdb_mx* ix, const void* q, int nq, int k, const void* D, const void* I) {
     if (!ix) return fail(MVDB_ERR_ARG, "index is NULL");
     if (!q || !D || !I) return fail(MVDB_ERR_ARG, "NULL buffer passed to search");
     if (nq <= 0) return fail(MVDB_ERR_ARG, "nq must be positive (got %d)", nq);
     if (k <= 0 || k > kMaxFusedK) return fail(MVDB_ERR_ARG, "mx: k must be in [1, %d] (got %d)", kMaxFusedK, k);
+    return 0;
+}
+
+int check_refined(const mvdb_mx* ix, const mvdb_refine* st, int k, int fetch_k) {
+    if (!st) return fail(MVDB_ERR_ARG, "the refine store is NULL");
+    if (fetch_k < k || fetch_k > 1024) return fail(MVDB_ERR_ARG, "mx: fetch_k must be in [k, 1024] (got %d, k = %d)", fetch_k, k);
+    if (mvdb_refine_dim(st) != ix->d || mvdb_refine_ntotal(st) != ix->n)
+        return fail(MVDB_ERR_ARG, "mx: the refine store holds %lld rows of %d dimensions, the index %lld of %d",
+                    (long long)mvdb_refine_ntotal(st), mvdb_refine_dim(st), (long long)ix->n, ix->d);
     return 0;
 }
 
@@ -610,13 +648,19 @@ int mvdb_mx_query(const mvdb_mx* ix, const float* q_host, int nq, uint8_t* q8_ho
     return 0;
 }
 
-// host API: stage the queries (and the bitmap), search on a private stream, one packed D2H, wait
-int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
-                   int64_t* I_host) {
+}  // extern "C"
+
+namespace {
+
+// host API: stage the queries (and the bitmap), search on a private stream, one packed D2H, wait.  st: nullptr, or the refine
+// store of a refined search.
+int search_host(const mvdb_mx* ix, const mvdb_refine* st, const float* q_host, int nq, int k, int fetch_k,
+                const uint64_t* mask_host, float* D_host, int64_t* I_host) {
     MVDB_TRY(check_search(ix, q_host, nq, k, D_host, I_host));
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(MVDB_ERR_HIP, "cannot select device %d", ix->device);
     std::shared_lock<std::shared_mutex> lk(ix->mu);
+    if (fetch_k) MVDB_TRY(check_refined(ix, st, k, fetch_k));
     MxWorkspace* ws = ws_acquire(ix);
     if (!ws) return fail(MVDB_ERR_HIP, "mx: cannot create a search workspace");
     WsBack back{ix, ws};
@@ -626,7 +670,8 @@ int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const 
     MVDB_TRY(ws->out.reserve(total + total / 2 + 1));  // I: total int64; D: total floats
     int64_t* Io = ws->out.p;
     float* Do = (float*)(ws->out.p + total);
-    MVDB_TRY(search_core(ix, ws, ws->qf.p, nq, k, mask_dev, Do, Io, false, ws->stream));
+    if (fetch_k) MVDB_TRY(refined_core(ix, st, ws, ws->qf.p, nq, k, fetch_k, mask_dev, Do, Io, false, ws->stream));
+    else MVDB_TRY(search_core(ix, ws, ws->qf.p, nq, k, mask_dev, Do, Io, false, ws->stream));
     const size_t bytes = total * (sizeof(int64_t) + sizeof(float));
     MVDB_TRY(ws->pin_out.reserve(bytes));
     MVDB_HIP(hipMemcpyAsync(ws->pin_out.p, ws->out.p, bytes, hipMemcpyDeviceToHost, ws->stream));
@@ -636,12 +681,13 @@ int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const 
     return 0;
 }
 
-int mvdb_mx_search_device(const mvdb_mx* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
-                          int64_t* I_dev, void* stream) {
+int search_device(const mvdb_mx* ix, const mvdb_refine* st, const float* q_dev, int nq, int k, int fetch_k,
+                  const uint64_t* mask_dev, float* D_dev, int64_t* I_dev, void* stream) {
     MVDB_TRY(check_search(ix, q_dev, nq, k, D_dev, I_dev));
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(MVDB_ERR_HIP, "cannot select device %d", ix->device);
     std::shared_lock<std::shared_mutex> lk(ix->mu);
+    if (fetch_k) MVDB_TRY(check_refined(ix, st, k, fetch_k));
     hipStream_t s = (hipStream_t)stream;
     MxWorkspace* ws = ws_for_stream(ix, s);
     if (!ws) return fail(MVDB_ERR_HIP, "mx: cannot create a search workspace");
@@ -650,7 +696,34 @@ int mvdb_mx_search_device(const mvdb_mx* ix, const float* q_dev, int nq, int k, 
     const bool capturing = s && hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusActive;
     if (capturing) ws->captured = true;
     RetireScope keep_old(ws->captured ? &ws->retired : nullptr);
+    if (fetch_k) return refined_core(ix, st, ws, q_dev, nq, k, fetch_k, mask_dev, D_dev, I_dev, capturing, s);
     return search_core(ix, ws, q_dev, nq, k, mask_dev, D_dev, I_dev, capturing, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvdb_mx_search(const mvdb_mx* ix, const float* q_host, int nq, int k, const uint64_t* mask_host, float* D_host,
+                   int64_t* I_host) {
+    return search_host(ix, nullptr, q_host, nq, k, 0, mask_host, D_host, I_host);
+}
+
+int mvdb_mx_search_device(const mvdb_mx* ix, const float* q_dev, int nq, int k, const uint64_t* mask_dev, float* D_dev,
+                          int64_t* I_dev, void* stream) {
+    return search_device(ix, nullptr, q_dev, nq, k, 0, mask_dev, D_dev, I_dev, stream);
+}
+
+int mvdb_mx_search_refined(const mvdb_mx* ix, const mvdb_refine* st, const float* q_host, int nq, int k, int fetch_k,
+                           const uint64_t* mask_host, float* D_host, int64_t* I_host) {
+    if (fetch_k <= 0) return fail(MVDB_ERR_ARG, "mx: fetch_k must be in [k, 1024] (got %d)", fetch_k);
+    return search_host(ix, st, q_host, nq, k, fetch_k, mask_host, D_host, I_host);
+}
+
+int mvdb_mx_search_refined_device(const mvdb_mx* ix, const mvdb_refine* st, const float* q_dev, int nq, int k, int fetch_k,
+                                  const uint64_t* mask_dev, float* D_dev, int64_t* I_dev, void* stream) {
+    if (fetch_k <= 0) return fail(MVDB_ERR_ARG, "mx: fetch_k must be in [k, 1024] (got %d)", fetch_k);
+    return search_device(ix, st, q_dev, nq, k, fetch_k, mask_dev, D_dev, I_dev, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 //   mx_encode_kernel<FMT>      fp32 rows -> codes + scales: one wave per row, a lane quad per MX block; also the queries.
 //   mx_scan_kernel<FMT,QB,REG> 16 QB queries per row read; REG: the B operands stay in registers (d <= 1024, <= 16 queries).
 //   mx_merge_kernel            the blocks' partial lists -> D (fp32 scores), I (int64 rows).
+//   mx_merge_keys_kernel       refined search: one segment's partial lists -> its best keys, left as keys for the re-rank.
 //   mx_move_kernel             codes and scales of listed rows, together: removal (gather) and set_rows_codes (scatter).
 #pragma once
 #include <float.h>
@@ -183,6 +184,7 @@ struct MxScanArgs {
     int nq;
     int k;
     uint64_t* cand;          // [nq][gridDim.x][k] keys
+    int64_t base = 0;        // added to a row's number in its key: the rows are a segment that starts there (refined search)
 };
 
 template <int N>
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(kMxMaxThreads) void mx_scan_kernel(MxScanArgs a) {
                     const int m = 4 * kb + j;
                     const int sel = __shfl(sel_l, m, kWave);
                     const float s = acc[t][g][j];
-                    const uint64_t key = make_key(s, (uint32_t)(rt + m));
+                    const uint64_t key = make_key(s, (uint32_t)(a.base + rt + m));
                     uint64_t todo = __ballot(qlive[g] && sel && s == s && key > gate[g]);
                     while (todo) {
                         const int srcl = __ffsll((long long)todo) - 1;
@@ -381,6 +383,29 @@ __global__ __launch_bounds__(kMxThreads) void mx_merge_kernel(const uint64_t* __
         D[o] = hit ? key_score(tk.key) : -FLT_MAX;
         I[o] = hit ? (int64_t)key_row(tk.key) : -1;
     }
+}
+
+// The refined search's merge, one block per query: the nlists partial lists of ONE segment -> its f best keys, left as keys in
+// slots [seg f, seg f + f) of the query's candidate list keys[nq, nseg f] for the re-rank to read (refine_kernels.hpp).  An
+// empty segment (nlists == 0) and a query that is not valid leave zeros: no candidates.
+__global__ __launch_bounds__(kMxThreads) void mx_merge_keys_kernel(const uint64_t* __restrict__ cand, int nlists, int f,
+                                                                   const int* __restrict__ valid, int seg, int nseg,
+                                                                   uint64_t* __restrict__ keys) {
+    constexpr int NW = kMxThreads / kWave;
+    __shared__ uint64_t sh[(NW - 1) * kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int qi = blockIdx.x;
+    const uint64_t* src = cand + (int64_t)qi * nlists * f;
+    WaveTopK tk;
+    tk.init(f);
+    const int64_t total = (int64_t)nlists * f;
+    for (int64_t i0 = (int64_t)wave * kWave; i0 < total; i0 += (int64_t)NW * kWave) {
+        const int64_t i = i0 + lane;
+        tk.offer(i < total ? src[i] : 0ull);
+    }
+    block_merge_topk(tk, sh, NW);
+    if (wave == 0 && lane < f) keys[((int64_t)qi * nseg + seg) * f + lane] = valid[qi] ? tk.key : 0ull;
 }
 
 __global__ void mx_fill_missing_kernel(float* D, int64_t* I, int64_t total) {

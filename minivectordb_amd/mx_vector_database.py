@@ -3,8 +3,12 @@
 A block of 32 dimensions is 32 small floats (E2M1 or E4M3) under one power-of-two scale byte, so there are no ranges and nothing
 is trained.  The rows live on the device (`_native.MxIndex`, include/mvdb.h "MX INDEX") and are scored by CDNA4's scaled matrix
 instruction, which takes the stored blocks as its operands.  The original vectors are NOT kept, so scores are estimates of the
-inner product, best first, and there is no re-ranking.  The query is encoded as MXFP8 per call, and a query's answer does not
-depend on how many queries share its call.
+inner product, best first.  The query is encoded as MXFP8 per call, and a query's answer does not depend on how many queries
+share its call.
+
+With `refine=True` the database also keeps every row as IEEE binary16 (`_native.RefineStore`, include/mvdb.h "REFINE STORE":
+2 more bytes per dimension), and a search takes `fetch_k` candidates by the MX score and returns their best k by the fp32 inner
+product with those rows: the scores are then products with the binary16 rows, not estimates.
 
 Ids, metadata and the metadata filters are `_dbcore`'s, as in SQ4VectorDatabase: the selected rows become a bitmap uploaded with
 the call.
@@ -25,9 +29,10 @@ class MXVectorDatabase:
     _live_value_index = FilterAndRerankMixin._live_value_index
     _row_count = FilterAndRerankMixin._row_count
 
-    def __init__(self, embedding_size, element_bits=4, storage_file=None, device=0):
+    def __init__(self, embedding_size, element_bits=4, storage_file=None, device=0, refine=False, fetch_k=None):
         """embedding_size: a multiple of 128 up to 4096.  element_bits: 4 (MXFP4) or 8 (MXFP8).  storage_file: None keeps
-        nothing on disk."""
+        nothing on disk.  refine: keep binary16 rows and re-rank every search against them.  fetch_k: candidates per query of a
+        refined search, at most 1024 (None: max(64, 4 k))."""
         from . import _native
         self.embedding_size = int(embedding_size)
         self.element_bits = int(element_bits)
@@ -37,6 +42,8 @@ class MXVectorDatabase:
         self.inverted_index = defaultdict(set)
         self.lock = threading.Lock()
         self.index = _native.MxIndex(self.embedding_size, self.element_bits, device=device)
+        self.fetch_k = fetch_k
+        self.refine = _native.RefineStore(self.embedding_size, device=device) if refine else None
         if storage_file is not None and os.path.exists(storage_file):
             with open(storage_file, 'rb') as f:
                 data = pickle.load(f)
@@ -46,8 +53,12 @@ class MXVectorDatabase:
             self.metadata = data['metadata']
             self._ids = _IdIndex(data['unique_ids'])
             self.inverted_index = data['inverted_index']
+            if self.refine is not None and 'refine_rows' not in data:
+                raise ValueError(f"{storage_file} was written without refine rows; open it with refine=False")
             if len(data['codes']):
                 self.index.add_codes(data['codes'], data['scales'])
+                if self.refine is not None:   # (binary16 -> fp32 -> binary16 is the identity)
+                    self.refine.add(data['refine_rows'].view(np.float16).astype(np.float32))
 
     # ---- ingest / delete / update --------------------------------------------------------------------------------
     def _vectors(self, embeddings, count):
@@ -69,7 +80,10 @@ class MXVectorDatabase:
             if not unique_ids:
                 return
             metadata_dicts = list(metadata_dicts) or [{} for _ in unique_ids]
-            self.index.add(self._vectors(embeddings, len(unique_ids)))
+            x = self._vectors(embeddings, len(unique_ids))
+            self.index.add(x)
+            if self.refine is not None:
+                self.refine.add(x)
             values = self._live_value_index()
             handle = self._ids.next
             self._ids.extend(unique_ids)
@@ -99,6 +113,8 @@ class MXVectorDatabase:
             row = self._ids.pop(unique_id)
             del self.metadata[row]
             self.index.remove_rows([row])
+            if self.refine is not None:
+                self.refine.remove_rows([row])
 
     def update_embedding(self, unique_id, embedding=None, metadata_dict=None):
         """Replace the stored vector (encoded in place, the row keeps its number), the metadata, or both; None means "keep"."""
@@ -112,6 +128,8 @@ class MXVectorDatabase:
             row = self._ids.row(unique_id)
             if embedding is not None:
                 self.index.set_rows([row], self._vectors([embedding], 1))
+                if self.refine is not None:
+                    self.refine.set_rows([row], self._vectors([embedding], 1))
             if metadata_dict is not None:
                 values = self._live_value_index()
                 if values is not None:
@@ -128,6 +146,8 @@ class MXVectorDatabase:
             codes, scales = self.index.get_codes(0, self.index.ntotal)
             data = {'embedding_size': self.embedding_size, 'element_bits': self.element_bits, 'codes': codes, 'scales': scales,
                     'unique_ids': list(self._ids.uids), 'metadata': self.metadata, 'inverted_index': self.inverted_index}
+            if self.refine is not None:
+                data['refine_rows'] = self.refine.get_rows(0, self.refine.ntotal)
             with open(self.storage_file, 'wb') as f:
                 pickle.dump(data, f)
 
@@ -153,7 +173,11 @@ class MXVectorDatabase:
             k = min(int(k), selected)
             if k <= 0:
                 return [([], [], []) for _ in range(nq)]
-            D, I = self.index.search(self._vectors(embeddings, nq), k, mask)
+            if self.refine is not None:
+                fetch_k = min(max(k, min(1024, self.fetch_k or max(64, 4 * k))), selected)
+                D, I = self.index.search_refined(self._vectors(embeddings, nq), k, self.refine, fetch_k, mask)
+            else:
+                D, I = self.index.search(self._vectors(embeddings, nq), k, mask)
             uids, metadata = self._ids.uids, self.metadata
             return [([uids[r] for r in I[i] if r >= 0], [float(s) for s, r in zip(D[i], I[i]) if r >= 0],
                      [metadata[r] for r in I[i] if r >= 0]) for i in range(nq)]
